@@ -32,9 +32,16 @@ Workloads (--config; every BASELINE.json config has a line):
        is the same thing.
 
 usage: python bench.py [--config c1..c5] [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full-grid]
+                       [--dump-outputs DIR]
        (N > 1: either under python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ... -- the launcher
         only provides RANK / WORLD_SIZE / LOCAL_RANK -- or as a plain `python bench.py --gpus N`, which then starts its
         own N rank processes as children (self_launch); the communicator is RCCL through the C-ABI either way)
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step goes to DIR/<name>.npy (float64),
+the arrays a caller of that path receives.  The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.  c2-c5: acq, mean, var of the rank's candidates (cbo_gp_fit_sweep's acq_out / mean_out /
+var_out; with several ranks rank r writes acq_rank<r>, ...) and winner_value, winner_index (the exchanged arg-max).  c1:
+x_new_set<s>, acq_set<s> of every exploration set and pick (cbo_trial_step's points, values and chosen set).
 """
 import argparse
 import ctypes
@@ -137,6 +144,30 @@ def cpu_baseline(X, y, Xs, y_best, cost, sample):
                        "baseline is understated (a stated baseline, never the target)" if sample < 512 else "")}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array to out_dir/<name>.npy as float64.  Should the arrays exceed DUMP_LIMIT_BYTES in all
+    (no config does: c4/c5 with --full-grid write 6 MB), every array larger than its share is replaced by a fixed seeded
+    sample of its elements, whose flat indices go to <name>_sample_index.npy.  Returns {name: shape} of what was written."""
+    arrays = {k: np.array(v, dtype=np.float64) for k, v in arrays.items()}
+    share = None
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // 8 // (2 * len(arrays))           # elements per array, with room for its indices
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        if share is not None and a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            written[name + "_sample_index"] = idx.astype(np.float64)
+            a = a.reshape(-1)[idx]
+        written[name] = a
+    for name, a in written.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in written.items()}
+
+
 def kernel_sources_sha():
     """sha256 over the kernel and C-ABI sources: ties a committed PMC measurement to the code it was taken on."""
     h = hashlib.sha256()
@@ -195,8 +226,8 @@ def bench_small_sets(args):
 
     def step():
         path.last_intervention = 1                  # (the set whose model is rebuilt: the same every step)
-        _, vals, choice = path.trial_step(best)     # one cbo_trial_step call: rebuild + sweep of every set + pick
-        return choice, vals
+        x_new, vals, choice = path.trial_step(best)     # one cbo_trial_step call: rebuild + sweep of every set + pick
+        return choice, vals, x_new
 
     def fence():
         if comm is not None:
@@ -204,15 +235,22 @@ def bench_small_sets(args):
         ctx.synchronize()
 
     for _ in range(max(5, args.warmup)):
-        choice, vals = step()
+        choice, vals, x_new = step()
     fence()
     t0 = time.perf_counter()
     for _ in range(steps):
-        choice, vals = step()
+        choice, vals, x_new = step()
     fence()
     elapsed = time.perf_counter() - t0
     if comm is not None:
         elapsed = comm.max(elapsed)
+    dumped = None
+    if args.dump_outputs and rank == 0:             # (every rank runs the same pass)
+        outs = {}
+        for s in range(len(es)):
+            outs[f"x_new_set{s}"], outs[f"acq_set{s}"] = x_new[s], vals[s]
+        outs["pick"] = [choice[1]]
+        dumped = dump_outputs(args.dump_outputs, outs)
     if rank == 0:
         per = elapsed / steps
         n_sets, m, n = 2, 200, 50
@@ -259,6 +297,8 @@ def bench_small_sets(args):
                                    "same_choice": bool(int(cpu_choice) == int(choice[1]))}
         else:
             out["cpu_baseline"] = None
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(out))
     if comm is not None:
         comm.barrier()
@@ -375,7 +415,11 @@ def main():
                          "hand-over (ncclSend / ncclRecv) has only ever run on one rank")
     ap.add_argument("--sequential", action="store_true",
                     help="refit, then sweep (two calls) instead of the one cbo_gp_fit_sweep call")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config is None:
         args.config = "c5" if args.dtype == "f32" else "c2"
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or os.environ.get("CBO_BENCH_SELF_LAUNCH") == "1"):
@@ -472,6 +516,21 @@ def main():
     elapsed = time.perf_counter() - t0
     if comm is not None:
         elapsed = comm.max(elapsed)            # the slowest rank's time
+
+    dumped = None
+    if args.dump_outputs:
+        # The arrays a caller of the timed call receives when it asks for them (cbo_gp_fit_sweep's acq_out / mean_out /
+        # var_out): the candidates keep the last step's q, mu, so this sweep of the unchanged model runs the epilogue on
+        # them and copies its results out -- the timed steps themselves stay as they were.
+        m = end - begin
+        acq, mean, var = np.empty(m), np.empty(m), np.empty(m)
+        _lib.check(lib.cbo_acq_sweep(model._handle, cands._handle, y_best, 0, 0.0, cost, _lib.dptr(acq), _lib.dptr(mean),
+                                     _lib.dptr(var), ctypes.byref(bv), ctypes.byref(bi)))
+        suffix = f"_rank{rank}" if world > 1 else ""
+        outs = {"acq" + suffix: acq, "mean" + suffix: mean, "var" + suffix: var}
+        if rank == 0:
+            outs["winner_value"], outs["winner_index"] = [winner[0]], [winner[1]]
+        dumped = dump_outputs(args.dump_outputs, outs)
 
     # c2 over several ranks: `value` above is the weak-scaling figure (one 16384-candidate grid per GPU, as measured since
     # round 1).  The same step on the config's ONE grid cut into `world` shards is timed here as well, by the same rules
@@ -715,6 +774,8 @@ def main():
             out["cpu_baseline"] = cpu_baseline(X, y, Xs, y_best, cost, min(args.cpu_sample, Xs.shape[0]))
         else:
             out["cpu_baseline"] = None
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(out))
     cands.close()
     model.close()

@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -68,7 +69,7 @@ def test_fails_loudly_without_gpu():
 def test_missing_library_is_an_import_error(tmp_path):
     code = ("import os; os.environ['CBO_HIP_LIB']=r'%s'; import cbo_with_oop_amd._lib as l\n"
             "try:\n    l.load()\nexcept ImportError as e:\n    print('IMPORTERROR')\n") % str(tmp_path / "nope.so")
-    out = subprocess.run(["python", "-c", code], cwd=ROOT, capture_output=True, text=True)
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
     assert "IMPORTERROR" in out.stdout, out.stderr
 
 

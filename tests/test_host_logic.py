@@ -272,6 +272,34 @@ def test_bench_launcher_reports_the_worst_exit_code_of_its_ranks():
     assert "libcbo_hip.so not found" in out.stderr and not [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    """--steps is the number of timed steps: 0 is refused rather than replaced by a default or divided by."""
+    for config in ("c1", "c2"):
+        out = _run_bench(["--config", config, "--steps", "0"], {"CBO_BENCH_DRY_RANKS": "1",
+                                                                "CBO_HIP_LIB": "/nonexistent/libcbo_hip.so"})
+        assert out.returncode == 2 and "--steps must be at least 1" in out.stderr, out.stderr[-2000:]
+
+
+def test_bench_dump_outputs_writes_float64_arrays_within_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs DIR): one float64 .npy per array; past the size limit a larger array is
+    replaced by a seeded sample of its elements and their flat indices, the same sample on every run."""
+    import bench
+    acq = np.arange(1000, dtype=np.float64)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"acq": acq, "pick": [3]})
+    assert shapes == {"acq": [1000], "pick": [1]}
+    a, p = np.load(tmp_path / "a" / "acq.npy"), np.load(tmp_path / "a" / "pick.npy")
+    assert a.dtype == p.dtype == np.float64 and np.array_equal(a, acq) and p[0] == 3.0
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1600)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"acq": acq, "pick": [3]})
+    total = sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in os.listdir(tmp_path / "b"))   # (npy header: 128 B)
+    assert sorted(os.listdir(tmp_path / "b")) == ["acq.npy", "acq_sample_index.npy", "pick.npy"] and total <= 1600
+    idx = np.load(tmp_path / "b" / "acq_sample_index.npy")
+    assert np.array_equal(np.load(tmp_path / "b" / "acq.npy"), acq[idx.astype(np.int64)])
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+
+
 def test_schedule_tuner_settles_near_the_best_candidate_on_a_simulated_device(tmp_path):
     """cbo_gp_fit_sweep chooses its schedule by timing the caller's own calls (csrc/schedule_tuner.h: host logic, no HIP).
     Against simulated devices -- step-time curves with the valley at a quarter of the pairs, at three eighths, at the

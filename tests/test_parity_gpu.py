@@ -1043,6 +1043,43 @@ def test_bench_lines_of_the_other_configs_carry_the_contract(hip):
     assert 0.5 < c3["roofline"]["isolated"]["frac"] < 1.0
 
 
+def test_bench_dump_outputs_are_what_the_timed_steps_computed(hip, tmp_path):
+    """bench.py --dump-outputs DIR: the line reports the --steps it was given; c2 writes acq, mean, var of the 16384
+    candidates (float64) whose arg-max is the line's winner, and the overlapped step writes the same bits as the two-call
+    step of --sequential; c1 writes each set's point and value and the pick, agreeing with the line."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+
+    def line(*args):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(args), env=env, capture_output=True,
+                             text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+
+    common = ["--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--post-steps", "0"]
+    fused = line(*common, "--dump-outputs", str(tmp_path / "fused"))
+    seq = line(*common, "--sequential", "--dump-outputs", str(tmp_path / "seq"))
+    assert fused["steps"] == seq["steps"] == 3 and fused["ms_per_step"] > 0
+    d = {k: np.load(tmp_path / "fused" / f"{k}.npy") for k in ("acq", "mean", "var", "winner_value", "winner_index")}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert d["acq"].shape == d["mean"].shape == d["var"].shape == (16384,) and np.all(d["var"] > 0)
+    w = int(d["winner_index"][0])
+    assert w == fused["winner"]["index"] == int(np.argmax(d["acq"])) and d["acq"][w] == d["winner_value"][0] == fused["winner"]["acq"]
+    for k, a in d.items():
+        assert np.array_equal(a, np.load(tmp_path / "seq" / f"{k}.npy")), k
+    c1 = line("--config", "c1", "--steps", "5", "--cpu-sample", "0", "--dump-outputs", str(tmp_path / "c1"))
+    assert c1["steps"] == 5
+    pick = np.load(tmp_path / "c1" / "pick.npy")
+    acq_sets = [np.load(tmp_path / "c1" / f"acq_set{s}.npy") for s in range(2)]
+    assert int(pick[0]) == c1["winner"]["set"] and acq_sets[int(pick[0])][0, 0] == c1["winner"]["acq"]
+    assert all(np.load(tmp_path / "c1" / f"x_new_set{s}.npy").shape == (1, 1) for s in range(2))
+
+
 def test_a_factor_taken_in_row_slices_is_the_factor(hip):
     """The hand-over of ``cbo_comm_share_factor`` between ranks cannot run on a one-GPU box (with one rank nobody lacks
     the factor).  Everything around the transfers is pinned here: model A holds the factor at the level the data need,
