@@ -1,7 +1,6 @@
 """The four methods of the reference's agent that drive the hot path, as a mixin/standalone class
-(/root/reference/src/CBO.py:209-277).  The experiment loop, monitor, do-calculus and graph classes stay
-the reference's own (out of scope); INTEGRATION.md shows the two-line change that makes
-``src/CBO.py`` use this module.
+(/root/reference/src/CBO.py:209-277; INTEGRATION.md shows the two-line change that makes ``src/CBO.py`` use it), and
+``CBO``, the whole agent on top of them (src/CBO.py:11-291: ``run``, ``observe``, ``intervene``, ``epsilon``).
 """
 from __future__ import annotations
 
@@ -264,3 +263,196 @@ class CBOAcquisitionPath:
 
     # BASELINE.json's north_star calls it select_intervention
     select_intervention = select_next_intervention
+
+
+class CBO(CBOAcquisitionPath):
+    """The reference's agent (src/CBO.py:11-291): ``run()``, its epsilon-greedy choice between ``observe()`` and
+    ``intervene()``, ``epsilon``, ``compute_cost``, and a minimal monitor.  ``intervene()`` is the acquisition path of
+    ``CBOAcquisitionPath``; ``observe()`` refits every graph-level GP of the graph in lockstep
+    (``graph.fit_all_gaussian_processes``: one device call per L-BFGS round for all of them) and refreshes the
+    do-calculus priors through ``DoCalculus``.
+
+    Arguments are the reference's (src/ArgumentParser.py:16-33 and the data loader's fields), with the data as plain
+    arrays instead of pickles: ``measurements`` / ``all_measurements`` map variable names to columns (the observational
+    rows the agent starts with / the whole observational data set it draws further rows from, src/CBO.py:190-200);
+    ``interventional_data[s]`` is (data_x, data_y) of exploration set s (what ``define_initial_data_cbo`` extracts from
+    the interventional data, src/Monitor.py:24-27); ``target_functions[s]`` (optional) maps (1, d) intervention values
+    to the (1, 1) target -- by default ``compute_interventions`` on the graph's SEM (src/Monitor.py:55-63).
+    ``exploration_set``: "MIS" / "POMIS" as in the reference, or the list of sets itself.  With ``causal_prior`` every
+    set's ``get_gp_name`` must name a graph GP; the constructor raises KeyError naming the first that does not.
+    ``lockstep=False`` fits the graph GPs one after another (the reference's order; same models)."""
+
+    def __init__(self, graph, measurements, all_measurements, interventional_data, exploration_set="MIS",
+                 num_interventions=10, initial_num_obs_samples=100, causal_prior=False, num_trials=40, task="min",
+                 num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
+                 lockstep=True, verbose=False):
+        from .DoCalculus import DoCalculus
+        from .GaussianProcessFactory import GaussianProcessType
+        from .graphs import _columns
+        self.graph = graph() if isinstance(graph, type) else graph
+        self.measurements = _columns(measurements)
+        self.all_measurements = _columns(all_measurements)
+        exploration = ([list(s) for s in self.graph.get_exploration_set(exploration_set)]
+                       if isinstance(exploration_set, str) else [list(s) for s in exploration_set])
+        self.num_interventions = num_interventions
+        self.max_n = initial_num_obs_samples + 50
+        self.initial_num_obs_samples = initial_num_obs_samples
+        self.num_trials = num_trials
+        self.num_additional_observations = num_additional_observations
+        self.type_cost = type_cost
+        self.name_index = name_index
+        self.lockstep = bool(lockstep)
+        self.verbose = verbose
+        gp_type = GaussianProcessType.CAUSAL_GP if causal_prior else GaussianProcessType.NON_CAUSAL_GP
+        if causal_prior:
+            # the do-calculus prior of set s is built on the graph GP get_gp_name(s) (src/DoCalculus.py:46-47; the
+            # reference raises KeyError at the first observe when the graph fits none of that name): checked up front
+            fitted = {self.graph.get_gp_name(d) for d in self.graph.fit_dependencies}
+            for s in exploration:
+                name = self.graph.get_gp_name(s)
+                if name not in fitted:
+                    raise KeyError(f"causal prior of exploration set {s}: the graph fits no GP named {name!r} "
+                                   f"(it fits {sorted(fitted)})")
+        data_x = [np.asarray(x, dtype=np.float64).reshape(len(x), -1) for x, _ in interventional_data]
+        data_y = [np.asarray(y, dtype=np.float64).reshape(-1, 1) for _, y in interventional_data]
+        if len(data_x) != len(exploration):
+            raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
+        super().__init__(gp_type, exploration, self.graph.get_cost_structure(type_cost), task, data_x, data_y,
+                         [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None)
+        if target_functions is None:
+            from functools import partial
+            from .utils_functions.graph_functions import compute_interventions
+            sem = self.graph.define_sem()
+            target_functions = [partial(compute_interventions, sem, {v: "" for v in s}, target_variable="Y")
+                                for s in exploration]
+        self.target_functions = list(target_functions)
+        self.do_calculus = DoCalculus(self)
+        self.graph_gps = {}
+        self.monitor = _Monitor(self)
+
+    # -- src/CBO.py:83-121 ---------------------------------------------------------------------------
+    def run(self):
+        """Fit the graph GPs, observe once, intervene once, then ``num_trials - 2`` epsilon-greedy trials
+        (``numpy.random.uniform(0., 1.) < epsilon``: observe, else intervene)."""
+        from numpy.random import uniform
+        self.graph_gps = self.graph.fit_all_gaussian_processes(self.measurements, lockstep=self.lockstep)
+        self.observe()
+        self.intervene()
+        self.monitor.start()
+        for _ in range(self.num_trials - 2):
+            if uniform(0., 1.) < self.epsilon:
+                self.observe()
+            else:
+                self.intervene()
+        self.monitor.stop()
+        return self.monitor
+
+    def observe(self):
+        """src/CBO.py:123-141: new observational rows, every graph GP refitted on all rows (in lockstep), the
+        do-calculus priors rebuilt from them."""
+        self.monitor.log_agent_behaviour(act=False)
+        new = self.get_new_observation()
+        self.measurements = {k: np.vstack([v, new[k]]) for k, v in self.measurements.items()}
+        self.graph_gps = self.graph.fit_all_gaussian_processes(self.measurements, lockstep=self.lockstep)
+        self.mean_functions, self.var_functions = self.do_calculus.update_all_do_functions(self.graph_gps)
+        self.monitor.log_agent_performance()
+
+    def intervene(self):
+        """src/CBO.py:143-173."""
+        self.monitor.log_agent_behaviour(act=True)
+        current_best = self.current_best_solution(self.monitor.current_best_y)
+        if self.monitor.agent_previously_observed() or not self.models:
+            self.update_all_gaussian_processes()
+        else:
+            self.update_gaussian_process_of_last_intervention(fit=True)
+        xs, ys = self.compute_best_acquisition_values(current_best)
+        intervention_set, intervention = self.select_next_intervention(ys)
+        cost = self.compute_cost(intervention_set, intervention, xs)
+        self.monitor.log_agent_performance(intervention_set, intervention, xs, cost)
+        self.models[intervention].optimize()
+
+    @property
+    def epsilon(self):
+        """src/CBO.py:175-188: (hull volume of the observations of the manipulative variables / volume of their
+        interventional box) / (rows / max_n)."""
+        from .utils_functions.utils import compute_coverage, update_hull
+        coverage_total = compute_coverage(self.measurements, self.graph.manipulative_variables,
+                                          self.interventional_ranges)[2]
+        coverage_obs = update_hull(self.measurements, self.graph.manipulative_variables)
+        rescale = self.n_measurements / self.max_n
+        return (coverage_obs / coverage_total) / rescale
+
+    @property
+    def n_measurements(self):
+        return next(iter(self.measurements.values())).shape[0]
+
+    @property
+    def interventional_ranges(self):
+        return self.graph.get_interventional_ranges()
+
+    def get_new_observation(self):
+        """src/CBO.py:196-200 -> cbo_functions.observe: the rows [initial_num_obs_samples, + num_additional_observations)
+        of the whole observational data set (the same rows at every observe, as in the reference)."""
+        lo = self.initial_num_obs_samples
+        return {k: v[lo:lo + self.num_additional_observations] for k, v in self.all_measurements.items()}
+
+    def compute_cost(self, intervention_set, intervention, acquisition_xs):
+        """src/CBO.py:279-291."""
+        from .utils_functions.cost_functions import total_cost
+        x = {v: acquisition_xs[intervention][0, i] for i, v in enumerate(intervention_set)}
+        return total_cost(intervention_set, self.costs, x)
+
+
+class _Monitor:
+    """What src/Monitor.py records of a run: per trial whether the agent intervened (1) or observed (0), the best
+    target value so far, the cumulative cost, and for interventions the set and the values chosen."""
+
+    def __init__(self, cbo):
+        import copy
+        self.cbo = cbo
+        task = cbo.task
+        best = [(np.min(y) if task == "min" else np.max(y), s) for s, y in enumerate(cbo.data_y)]
+        opt_y, s_best = (min if task == "min" else max)(best, key=lambda t: t[0])
+        self.current_best_y = {n: [np.inf if task == "min" else -np.inf] for n in cbo.intervention_names}
+        self.current_best_x = copy.deepcopy(self.current_best_y)
+        self.current_best_y[cbo.intervention_names[s_best]].append(float(opt_y))
+        self.global_opt = [float(opt_y)]
+        self.current_cost = [0.]
+        self.cumulative_cost = 0.
+        self.type_trial = []
+        self.chosen = []                 # per trial: (exploration set, values (1,d)) or None for an observe
+        self.start_time = self.total_time = None
+
+    def start(self):
+        import time
+        self.start_time = time.perf_counter()
+
+    def stop(self):
+        import time
+        self.total_time = time.perf_counter() - self.start_time
+
+    def log_agent_behaviour(self, act):
+        self.type_trial.append(1 if act else 0)
+
+    def agent_previously_observed(self):
+        return len(self.type_trial) >= 2 and self.type_trial[-2] == 0
+
+    def log_agent_performance(self, intervention_set=None, intervention=None, acquisition_xs=None, current_cost=None):
+        if current_cost is None:
+            self.global_opt.append(self.global_opt[-1])
+            self.current_cost.append(self.current_cost[-1])
+            self.chosen.append(None)
+            return
+        cbo = self.cbo
+        x_new = np.asarray(acquisition_xs[intervention], dtype=np.float64).reshape(1, -1)
+        y_new = np.asarray(cbo.target_functions[intervention](x_new), dtype=np.float64).reshape(1, 1)
+        cbo.data_x[intervention] = np.vstack((cbo.data_x[intervention], x_new))
+        cbo.data_y[intervention] = np.vstack((cbo.data_y[intervention], y_new))
+        cbo.models[intervention].set_data(cbo.data_x[intervention], cbo.data_y[intervention])
+        name = cbo.intervention_names[intervention]
+        self.current_best_x[name].append(float(x_new[0, 0]))
+        self.current_best_y[name].append(float(y_new[0, 0]))
+        self.global_opt.append(float(find_current_global(self.current_best_y, cbo.intervention_names, cbo.task)))
+        self.cumulative_cost += current_cost
+        self.current_cost.append(self.cumulative_cost)
+        self.chosen.append((list(intervention_set), x_new.copy()))

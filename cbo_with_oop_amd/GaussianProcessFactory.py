@@ -363,20 +363,14 @@ class HipGaussianProcess:
         ``_transform_gradients`` (gradient times 1 - exp(-theta)); ``"log"``: theta = exp(x)."""
         x = np.asarray(x, dtype=np.float64)
         theta = logexp_f(x) if transform == "logexp" else np.exp(x)
-        nl = self.lengthscale.size
-        noise = self.noise_var if self.fix_noise else theta[1 + nl]
         try:
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore", RuntimeWarning)
-                self.set_hyperparameters(theta[0], theta[1:1 + nl], noise, fit=not self.small)
+            _objective_set(self, theta)
             dv, dls, dn = self.log_likelihood_gradients()
         except np.linalg.LinAlgError:
             # paramz hands the optimiser inf and the clipped gradient of the last good point (and gives up after ten such
             # evaluations in a row); a large finite value keeps scipy's line search defined and is rejected the same way
             return 1e25, np.zeros_like(x)
-        g = np.asarray([dv, *dls] + ([] if self.fix_noise else [dn]), dtype=np.float64)
-        g = g * (logexp_gradfactor(theta) if transform == "logexp" else theta)
-        return -self._last_lml, -g
+        return _objective_value(self, theta, self._last_lml, dv, dls, dn, transform)
 
     def optimize(self, max_iters=1000, transform="logexp", **kwargs):
         """Hyper-parameter MLE (emukit ``GPyModelWrapper.optimize`` -> GPy ``optimize_restarts(1, robust=True)`` -- one run from
@@ -388,26 +382,12 @@ class HipGaussianProcess:
         refit plus the device likelihood and its analytic gradients.  ``transform="log"`` is rounds 1-4's parametrisation
         (theta = exp(x), same stationary point, another path to it).  GPy is not installed here: the trajectory is GPy's
         by construction, not by comparison (parity unpinned)."""
-        from scipy.optimize import OptimizeResult, fmin_l_bfgs_b
-        if transform not in ("logexp", "log"):
-            raise ValueError("transform must be 'logexp' (GPy / paramz) or 'log'")
-        theta0 = [self.variance, *self.lengthscale]
-        if not self.fix_noise:
-            theta0.append(self.noise_var)
-        theta0 = np.asarray(theta0, dtype=np.float64)
-        x0 = logexp_finv(theta0) if transform == "logexp" else np.log(theta0)
+        from scipy.optimize import fmin_l_bfgs_b
+        theta0, x0 = _optimizer_start(self, transform)
         x_opt, f_opt, info = fmin_l_bfgs_b(lambda x: self._objective(x, transform), x0, maxfun=int(max_iters),
                                            maxiter=int(max_iters))
         f_opt = self._objective(x_opt, transform)[0]          # opt_lbfgsb: f_opt = f_fp(x_opt)[0]; the model sits at x_opt
-        if f_opt >= 1e25:                     # the factorisation failed at the point the optimiser settled on
-            nl = self.lengthscale.size        # (GPy restores the previous parameters after a failed step): back to the
-            self.set_hyperparameters(theta0[0], theta0[1:1 + nl],      # starting point, which was fitted before
-                                     self.noise_var if self.fix_noise else theta0[1 + nl])
-        res = OptimizeResult(x=x_opt, fun=f_opt, jac=info["grad"], nfev=info["funcalls"], nit=info["nit"],
-                             status=info["warnflag"], message=info["task"], success=info["warnflag"] == 0,
-                             transform=transform)
-        self.optimization_result = res
-        return res
+        return _optimizer_finish(self, theta0, x_opt, f_opt, info, transform)
 
     def get_prediction_gradients(self, x):
         """emukit ``GPyModelWrapper.get_prediction_gradients`` -> GPy ``predictive_gradients``:
@@ -453,6 +433,124 @@ class HipGaussianProcess:
             self.close()
         except Exception:
             pass
+
+
+# the pieces of HipGaussianProcess._objective / optimize that the lockstep form shares with them
+
+def _objective_set(model, theta, fit=None):
+    """The model at theta (a small model is not fitted for its likelihood; a larger one is, and may raise
+    LinAlgError; ``fit`` overrides)."""
+    nl = model.lengthscale.size
+    noise = model.noise_var if model.fix_noise else theta[1 + nl]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        model.set_hyperparameters(theta[0], theta[1:1 + nl], noise, fit=(not model.small) if fit is None else fit)
+
+
+def _batched(model):
+    """The batched likelihood launch answers this model without a fit: fp64, at most 256 observations (above 128 in
+    the kernel's two-block form)."""
+    return model.dtype == "f64" and model.X.shape[0] <= 256
+
+
+def _objective_value(model, theta, lml, dv, dls, dn, transform):
+    """(-lml, -gradient with respect to x) from the likelihood and its gradients at theta(x)."""
+    g = np.asarray([dv, *dls] + ([] if model.fix_noise else [dn]), dtype=np.float64)
+    g = g * (logexp_gradfactor(theta) if transform == "logexp" else theta)
+    return -lml, -g
+
+
+def _optimizer_start(model, transform):
+    """(theta0, x0) of ``optimize``."""
+    if transform not in ("logexp", "log"):
+        raise ValueError("transform must be 'logexp' (GPy / paramz) or 'log'")
+    theta0 = [model.variance, *model.lengthscale]
+    if not model.fix_noise:
+        theta0.append(model.noise_var)
+    theta0 = np.asarray(theta0, dtype=np.float64)
+    return theta0, (logexp_finv(theta0) if transform == "logexp" else np.log(theta0))
+
+
+def _optimizer_finish(model, theta0, x_opt, f_opt, info, transform):
+    """What ``optimize`` does once the routine has returned and ``f_fp(x_opt)`` has been re-evaluated."""
+    from scipy.optimize import OptimizeResult
+    if f_opt >= 1e25:                     # the factorisation failed at the point the optimiser settled on
+        nl = model.lengthscale.size       # (GPy restores the previous parameters after a failed step): back to the
+        model.set_hyperparameters(theta0[0], theta0[1:1 + nl],     # starting point, which was fitted before
+                                  model.noise_var if model.fix_noise else theta0[1 + nl])
+    res = OptimizeResult(x=x_opt, fun=f_opt, jac=info["grad"], nfev=info["funcalls"], nit=info["nit"],
+                         status=info["warnflag"], message=info["task"], success=info["warnflag"] == 0,
+                         transform=transform)
+    model.optimization_result = res
+    return res
+
+
+def lml_gradients_batch(models):
+    """``log_likelihood_gradients`` of many models in one device call (``cbo_gp_lml_gradients_batch``: one launch for
+    every fp64 model of at most 256 observations -- for n <= 128 the same bits as one model alone, above in the
+    kernel's two-block form -- none of them fitted for it; larger models are fitted first).  Returns, per model, (lml,
+    d/d variance, d/d lengthscale (array), d/d noise_var), or None where Ky is not positive definite even with the
+    jitchol ladder's jitter (the model alone raises LinAlgError)."""
+    if not models:
+        return []
+    lib = _lib.load()
+    for m in models:
+        if not _batched(m):
+            m.ensure_fitted()
+    k = len(models)
+    handles = (ctypes.c_void_p * k)(*[m._handle for m in models])
+    lml, dv, dn = np.zeros(k), np.zeros(k), np.zeros(k)
+    dls = np.zeros(k * _lib.MAX_DIM)
+    status = np.zeros(k, dtype=np.int32)
+    _lib.check(lib.cbo_gp_lml_gradients_batch(k, handles, _lib.dptr(lml), _lib.dptr(dv), _lib.dptr(dls), _lib.dptr(dn),
+                                              status.ctypes.data_as(_lib.c_int_p)))
+    out = []
+    for i, m in enumerate(models):
+        rc = int(status[i])
+        if rc in (_lib.CBO_ERR_NOT_PD, _lib.CBO_ERR_NONPOS_DIAG):
+            out.append(None)
+            continue
+        _lib.check(rc)
+        m._last_lml = float(lml[i])
+        base = i * _lib.MAX_DIM
+        out.append((float(lml[i]), float(dv[i]), dls[base:base + m.lengthscale.size].copy(), float(dn[i])))
+    return out
+
+
+def optimize_together(models, max_iters=1000, transform="logexp"):
+    """``[m.optimize(max_iters, transform) for m in models]`` with the models' L-BFGS-B runs in lockstep: every round
+    evaluates the likelihood and gradients of all models that asked for a value in ONE device call
+    (``lml_gradients_batch``).  A model of at most 128 observations follows the trajectory ``optimize`` gives it alone,
+    bit for bit, and ends with the same result record; one of 128 < n <= 256 is evaluated by the two-block form without
+    a fit (``optimize`` alone refits it and takes the general path): the same likelihood and gradients to rounding.
+    Returns the results (``optimization_result`` of each model)."""
+    from .utils_functions.lockstep_lbfgsb import lockstep_fmin_l_bfgs_b
+    models = list(models)
+    starts = [_optimizer_start(m, transform) for m in models]
+
+    def evaluate(ks, xs):
+        values = [None] * len(ks)
+        batch = []
+        for j, (k, x) in enumerate(zip(ks, xs)):
+            m = models[k]
+            x = np.asarray(x, dtype=np.float64)
+            theta = logexp_f(x) if transform == "logexp" else np.exp(x)
+            try:
+                _objective_set(m, theta, fit=not _batched(m))
+            except np.linalg.LinAlgError:
+                values[j] = (1e25, np.zeros_like(x))
+                continue
+            batch.append((j, k, x, theta))
+        answers = lml_gradients_batch([models[k] for _, k, _, _ in batch])
+        for (j, k, x, theta), a in zip(batch, answers):
+            values[j] = (1e25, np.zeros_like(x)) if a is None else _objective_value(models[k], theta, *a, transform)
+        return values
+
+    runs = lockstep_fmin_l_bfgs_b(evaluate, [x0 for _, x0 in starts], maxfun=int(max_iters), maxiter=int(max_iters))
+    # opt_lbfgsb: f_opt = f_fp(x_opt)[0], every model re-evaluated at its x_opt -- one more batched call
+    finals = evaluate(list(range(len(models))), [x for x, _, _ in runs])
+    return [_optimizer_finish(m, theta0, x_opt, f_final[0], info, transform)
+            for m, (theta0, _), (x_opt, _, info), f_final in zip(models, starts, runs, finals)]
 
 
 class GaussianProcessFactory:

@@ -20,6 +20,7 @@ c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 
 ABI_VERSION = 5          # include/cbo_hip.h: CBO_HIP_ABI_VERSION
 ABI_DIAG_BASE = 1000     # CBO_HIP_ABI_DIAG_BASE: timing-only builds report ABI_DIAG_BASE + version
+MAX_DIM = 8              # CBO_MAX_DIM
 CBO_OK = 0
 CBO_ERR_INVALID = -1
 CBO_ERR_HIP = -2
@@ -91,6 +92,8 @@ SIGNATURES = {
     "cbo_gp_set_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p, ctypes.c_double]),
     "cbo_gp_log_marginal": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "cbo_gp_lml_gradients": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "cbo_gp_lml_gradients_batch": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                  c_int_p]),
     "cbo_gp_predict_gradients": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p,
                                                 c_double_p]),
     "cbo_gp_predict_grouped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, c_double_p,

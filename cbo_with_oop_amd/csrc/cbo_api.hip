@@ -108,6 +108,7 @@ struct cbo_ctx {
     int small_seq = 0;                                          // sequence number of the last multi-set call
     int polled_launches = 0;                                    // launches completed by polling since the last stream sync
     cbo_small_lml_result *lml_out = nullptr;                    // pinned, written by small_lml_kernel
+    cbo_small_lml_result *lml_batch_out = nullptr; int lml_batch_cap = 0;   // pinned, written by small_lml_batch_kernel
     double *q = nullptr, *mu = nullptr, *mean = nullptr, *var = nullptr, *acq = nullptr; size_t vec_elems = 0;
     double *part_val = nullptr; int64_t *part_idx = nullptr;
     double *best_val = nullptr; int64_t *best_idx = nullptr;   // device
@@ -390,7 +391,7 @@ static void destroy_ctx(cbo_ctx *c)
     for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : c->pool) hipEventDestroy(e);
     hipFree(c->W); hipFree(c->gpart); hipFree(c->mupart);
-    hipHostFree(c->sets_host); hipHostFree(c->small_out); hipHostFree(c->lml_out); hipFree(c->small_scratch); hipFree(c->small_part_val);
+    hipHostFree(c->sets_host); hipHostFree(c->small_out); hipHostFree(c->lml_out); hipHostFree(c->lml_batch_out); hipFree(c->small_scratch); hipFree(c->small_part_val);
     hipFree(c->small_part_idx); hipFree(c->small_info);
     hipFree(c->V); hipFree(c->q); hipFree(c->mu); hipFree(c->mean); hipFree(c->var); hipFree(c->acq);
     hipFree(c->part_val); hipFree(c->part_idx); hipFree(c->best_val); hipFree(c->best_idx);
@@ -2111,6 +2112,18 @@ static void lml_outputs(const cbo_gp *g, const double *grad_sums, double zz, dou
     if (lml_out) *lml_out = 0.5 * (-(double)g->n * 1.8378770664093453 - 2.0 * logdet - zz);
 }
 
+// the one-launch form of small_lml_gradients applies to this model
+static bool small_lml_eligible(const cbo_gp *g)
+{
+    return g->dtype == CBO_DTYPE_F64 && g->n_pad == kPadN && g->ctx->small_sets && g->n > 0;
+}
+
+// the batched launch also takes the next band, 128 < n <= 256, in its two-block form
+static bool mid_lml_eligible(const cbo_gp *g)
+{
+    return g->dtype == CBO_DTYPE_F64 && g->n_pad == 2 * kPadN && g->ctx->small_sets && g->n > kPadN;
+}
+
 // Models of at most 128 observations (every model the reference builds): likelihood and gradients in ONE launch, from
 // the data and the current hyper-parameters -- no fit beforehand, none left behind.  Returns 1 when done, 0 when the
 // general path has to take over (Ky not positive definite as assembled: the jitchol ladder lives there), < 0 on error.
@@ -2118,7 +2131,7 @@ static int small_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out
                                double *dnoise_out)
 {
     cbo_ctx *c = g->ctx;
-    if (!(g->dtype == CBO_DTYPE_F64 && g->n_pad == kPadN && c->small_sets && g->n > 0)) return 0;
+    if (!small_lml_eligible(g)) return 0;
     int rc = ensure_small_buffers(c, 1, 2);            // scratch of two workgroup slots >= factor + L^-1
     if (rc != CBO_OK) return rc;
     if (!c->lml_out) {
@@ -2144,6 +2157,9 @@ static int small_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out
     return 1;
 }
 
+static int general_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out, double *dlengthscale_out,
+                                 double *dnoise_out);
+
 extern "C" int cbo_gp_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out, double *dlengthscale_out,
                                     double *dnoise_out)
 {
@@ -2155,6 +2171,94 @@ extern "C" int cbo_gp_lml_gradients(cbo_gp *g, double *lml_out, double *dvarianc
         if (done < 0) return done;
         if (done == 1) return CBO_OK;
     }
+    return general_lml_gradients(g, lml_out, dvariance_out, dlengthscale_out, dnoise_out);
+}
+
+// Many models, one launch: every model small_lml_gradients would take goes into ONE small_lml_batch_kernel launch (one
+// workgroup each, the same device body, so the same bits), and so does every fp64 model of 128 < n <= 256 (the
+// kernel's two-block form; no fit either).  The others -- larger models, and those whose Ky is not positive definite as
+// assembled -- are answered one by one by general_lml_gradients, as cbo_gp_lml_gradients would.
+extern "C" int cbo_gp_lml_gradients_batch(int n_models, cbo_gp *const *gps, double *lml, double *dvar, double *dls,
+                                          double *dnoise, int *status)
+{
+    if (n_models <= 0 || !gps || !lml || !dvar || !dls || !dnoise || !status) return fail(CBO_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n_models; ++i) {
+        if (!gps[i]) return fail(CBO_ERR_INVALID, "NULL gp");
+        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all models must live on one context");
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int> small, rest;
+    bool any_mid = false;
+    for (int i = 0; i < n_models; ++i) {
+        const bool mid = mid_lml_eligible(gps[i]);
+        any_mid = any_mid || mid;
+        (small_lml_eligible(gps[i]) || mid ? small : rest).push_back(i);
+    }
+    const int ns = (int)small.size();
+    if (ns > 0) {
+        // descriptors + status words, and a scratch slot per model: factor + L^-1 (n <= 128), or the two-block slab
+        const size_t stride = any_mid ? mid_lml_scratch_doubles() : small_lml_scratch_doubles();
+        const size_t per_block = small_sets_scratch_doubles(1, 1);
+        const int blocks = (int)((stride + per_block - 1) / per_block);
+        int rc = ensure_small_buffers(c, ns, blocks);
+        if (rc != CBO_OK) return rc;
+        if ((size_t)ns * stride > c->small_scratch_elems)
+            return fail(CBO_ERR_INVALID, "likelihood batch: scratch smaller than expected");
+        if (ns > c->lml_batch_cap) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            hipHostFree(c->lml_batch_out);
+            c->lml_batch_out = nullptr; c->lml_batch_cap = 0;
+            const int cap = ns < 32 ? 32 : ns;
+            HIP_TRY(hipHostMalloc(&c->lml_batch_out, sizeof(cbo_small_lml_result) * cap));
+            std::memset(c->lml_batch_out, 0, sizeof(cbo_small_lml_result) * cap);
+            c->lml_batch_cap = cap;
+        }
+        for (int j = 0; j < ns; ++j) {
+            cbo_small_set st{};
+            fill_small_model(st, gps[small[(size_t)j]]);
+            c->sets_host[j] = st;
+        }
+        if (++c->small_seq == 0) c->small_seq = 1;
+        const int seq = c->small_seq;
+        cbo_small_lml_result *out = c->lml_batch_out;
+        launch_small_lml_batch(c->stream, c->sets_host, ns, c->small_scratch, (int64_t)stride, c->small_info, out, seq);
+        if (hipGetLastError() != hipSuccess) return fail(CBO_ERR_HIP, "small_lml_batch_kernel launch");
+        const bool ready = poll_until([&] {
+            for (int j = 0; j < ns; ++j)
+                if (*reinterpret_cast<volatile int *>(&out[j].seq) != seq) return false;
+            return true;
+        }, kPollBudgetUs);
+        if (!ready || c->profiling || polled_launch_needs_sync(c)) {
+            if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(CBO_ERR_HIP, "hipStreamSynchronize");
+            for (int j = 0; j < ns; ++j)
+                if (out[j].seq != seq) return fail(CBO_ERR_HIP, "likelihood batch kernel: no result record");
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        for (int j = 0; j < ns; ++j) {
+            const int i = small[(size_t)j];
+            if (out[j].info != 0) { rest.push_back(i); continue; }
+            const double *t = out[j].terms;
+            lml_outputs(gps[i], t, t[1 + CBO_MAX_DIM], t[1 + CBO_MAX_DIM + 1], t[1 + CBO_MAX_DIM + 2],
+                        t[1 + CBO_MAX_DIM + 3], &lml[i], &dvar[i], &dls[(size_t)i * CBO_MAX_DIM], &dnoise[i]);
+            status[i] = CBO_OK;
+        }
+    }
+    for (int i : rest) {
+        int rc = CBO_OK;
+        if (mid_lml_eligible(gps[i]) && !gps[i]->fitted) rc = cbo_gp_fit(gps[i], nullptr, nullptr);   // (jitchol ladder)
+        if (rc == CBO_OK)
+            rc = general_lml_gradients(gps[i], &lml[i], &dvar[i], &dls[(size_t)i * CBO_MAX_DIM], &dnoise[i]);
+        if (rc == CBO_ERR_HIP) return rc;               // the device is in trouble: no per-model answer means anything
+        status[i] = rc;
+    }
+    return CBO_OK;
+}
+
+static int general_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out, double *dlengthscale_out,
+                                 double *dnoise_out)
+{
+    cbo_ctx *c = g->ctx;
     if (!g->fitted) {                      // (a small model that was not positive definite as assembled lands here)
         if (g->n_pad != kPadN) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
         const int frc = cbo_gp_fit(g, nullptr, nullptr);

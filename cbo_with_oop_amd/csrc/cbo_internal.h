@@ -236,6 +236,12 @@ struct cbo_small_lml_result {
 };
 size_t small_lml_scratch_doubles();
 void launch_small_lml(hipStream_t s, const cbo_small_set &st, double *scratch, int *info, cbo_small_lml_result *out, int seq);
+// n_models models (n <= 256) in one launch: descriptors (pinned, device-mapped), `stride` doubles of scratch per model
+// (small_lml_scratch_doubles() when every n <= 128, else mid_lml_scratch_doubles()), info[b] zero on entry (zero
+// again afterwards), record out[b] (pinned) per model
+size_t mid_lml_scratch_doubles();
+void launch_small_lml_batch(hipStream_t s, const cbo_small_set *sets, int n_models, double *scratch, int64_t stride,
+                            int *info, cbo_small_lml_result *out, int seq);
 // sets / out may be pinned host memory (device-mapped): the kernel then reads the descriptors and writes the results
 // across the host link itself and the call needs no copy operation (the host may poll out[].seq instead of
 // synchronising the stream); info and ticket (device, n_sets ints each) must be zero on entry and are zero again afterwards

@@ -1,8 +1,9 @@
 """Problem tables the hot path needs from the reference's graph classes: exploration sets,
 interventional ranges and cost constants, plus the closed-form structural equation models in the
-additive form the device Monte-Carlo target takes.  The graph-level GP fits and the
-data-fitted SEMs of the coral graphs (sklearn regressors and mixtures fitted to SEM_data.mat,
-src/graphs/impl/CoralGraph.py:103-159) are out of scope.
+additive form the device Monte-Carlo target takes, and the graph-level GP fits of an observe
+step (fit dependencies, fit parameters, ``fit_all_gaussian_processes``).  The data-fitted SEMs of the coral graphs
+(sklearn regressors and mixtures fitted to SEM_data.mat, src/graphs/impl/CoralGraph.py:103-159) are out of scope
+(SURVEY.md §2 #11).
 
 Citations are relative to /root/reference/.
 """
@@ -23,6 +24,12 @@ def cost(fix_cost, variable_cost, intervention_value, **kwargs):
     return total_cost
 
 
+def _columns(measurements):
+    """{name: (N, 1) float64 column} from a mapping of columns (a dict of arrays, or anything indexable by name)."""
+    keys = measurements.keys() if hasattr(measurements, "keys") else measurements.columns
+    return {k: np.asarray(measurements[k], dtype=np.float64).reshape(-1, 1) for k in keys}
+
+
 def _cost_table(names, fixed, variable):
     return OrderedDict((n, partial(cost, f, variable)) for n, f in zip(names, fixed))
 
@@ -34,6 +41,54 @@ class _Graph:
     _ranges = OrderedDict()
     _mis = ()
     _pomis = ()
+    manipulative_variables = ()
+    # the graph-level GPs an observe step fits: the input columns of each, and its [lengthscale, variance, noise, ARD]
+    # (src/utils_functions/utils.py:40-45 reads them in that order; the noise is fixed at 1e-2 whatever the third value)
+    _fit_dependencies = ()
+    _fit_parameters = ()
+    # the output column of each graph GP: Y for all of them unless a graph says otherwise
+    _fit_outputs = ()
+
+    def __init__(self, measurements=None):
+        """``measurements``: the observational data, a mapping variable name -> column (what the reference's graph
+        constructors store, e.g. src/graphs/impl/CompleteGraph.py:27-29)."""
+        self.measurements = None if measurements is None else _columns(measurements)
+
+    @property
+    def fit_dependencies(self):
+        return [list(d) for d in self._fit_dependencies]
+
+    @property
+    def fit_parameters(self):
+        return [list(p) for p in self._fit_parameters]
+
+    @staticmethod
+    def get_gp_name(interventions):
+        """src/graphs/GraphInterface.py:37-43."""
+        return "gp_" + "_".join(interventions)
+
+    def fit_all_gaussian_processes(self, measurements=None, lockstep=True):
+        """CompleteGraph.py:114-137 / CoralGraph.py:186-212 / SimplifiedCoralGraph.py:194-220: one graph-level GP per fit
+        dependency (``fit_gaussian_process``, i.e. GPy's ``gp.optimize()`` on each), returned as {``gp_<deps>``: model}.
+        All of them are optimised together, one device call per L-BFGS round (``fit_gaussian_processes``;
+        ``lockstep=False`` fits them one by one -- the same models).
+
+        Deviation, documented: the reference builds the inputs from ``self.measurements`` -- the data the graph was
+        constructed with -- but the outputs from the ``measurements`` argument, so after the first observe the rows of
+        X and Y no longer belong together (their counts differ).  Here X and Y both come from the
+        same measurements: the argument when given, else the graph's own.  The complete graph's first GP keeps its
+        output C as written there (CompleteGraph.py:128)."""
+        from .utils_functions.utils import fit_gaussian_processes
+        data = self.measurements if measurements is None else _columns(measurements)
+        if data is None:
+            raise ValueError("fit_all_gaussian_processes: no measurements (pass them, or build the graph with them)")
+        deps = self.fit_dependencies
+        xs = [np.hstack([data[v] for v in d]) for d in deps]
+        outputs = list(self._fit_outputs) + ["Y"] * (len(deps) - len(self._fit_outputs))
+        ys = [data[o] for o in outputs]
+        names = [self.get_gp_name(d) for d in deps]
+        models = fit_gaussian_processes(xs, ys, self.fit_parameters, lockstep=lockstep)
+        return dict(zip(names, models))
 
     @classmethod
     def get_exploration_set(cls, set_name="MIS"):
@@ -72,6 +127,17 @@ class CompleteGraph(_Graph):
     _ranges = OrderedDict([("E", (-6, 3)), ("B", (-5, 4)), ("D", (-5, 5)), ("F", (-4, 4))])
     _mis = (("B",), ("D",), ("E",), ("B", "D"), ("B", "E"), ("D", "E"))
     _pomis = (("B",), ("D",), ("E",), ("B", "D"), ("D", "E"))
+    manipulative_variables = ("B", "D", "E")                       # CompleteGraph.py:21
+    # CompleteGraph.py:31-42 and :44-55
+    _fit_dependencies = (
+        ("B",), ("F",), ("D", "C"), ("B", "C"), ("A", "C", "E"), ("B", "C", "D"), ("D", "E", "C", "A"),
+        ("B", "E", "C", "A"), ("A", "B", "C", "D", "E"), ("A", "B", "C", "D", "E", "F"),
+    )
+    _fit_parameters = (
+        (1., 1., 0.0001, False), (1., 1., 10., False), (1., 1., 1., False), (1., 1., 1., False), (1., 1., 10., False),
+        (1., 1., 1., False), (1., 1., 10., False), (1., 1., 10., False), (1., 1., 10., False), (1., 1., 10., False),
+    )
+    _fit_outputs = ("C",)                                          # CompleteGraph.py:128: the first GP's output is C
 
     @staticmethod
     def define_sem():
@@ -106,6 +172,20 @@ class CoralGraph(_Graph):
         ("N", "T", "D"), ("O", "C", "T"), ("O", "C", "D"), ("C", "T", "D"), ("O", "T", "D"),
     )
     _pomis = _mis
+    manipulative_variables = ("N", "O", "C", "T", "D")            # CoralGraph.py:25
+    # CoralGraph.py:54-70 and :72-88 (SimplifiedCoralGraph.py:40-56 and :71-87 are the same tables); the thirteenth
+    # dependency lists N twice, as there
+    _fit_dependencies = (
+        ("N",), ("O", "S", "T", "D", "TE"), ("C", "N", "L", "TE"), ("T", "S"), ("D", "S"), ("N", "O", "S", "T", "D", "TE"),
+        ("N", "T", "S"), ("N", "D", "S"), ("O", "C", "N", "L", "TE", "S", "T", "D"), ("T", "C", "S", "TE", "L", "N"),
+        ("T", "D", "S"), ("C", "D", "S", "TE", "L", "N"), ("N", "C", "T", "S", "N", "L", "TE"), ("N", "T", "D", "S"),
+        ("C", "T", "D", "S", "N", "L", "TE"),
+    )
+    _fit_parameters = (
+        (1., 1., 10., False), (1., 1., 1., True), (1., 1., 1., True), (1., 1., 1., True), (1., 1., 10., True),
+        (1., 1., 1., False), (1., 1., 1., False), (1., 1., 1., False), (1., 1., 1., False), (1., 1., 1., False),
+        (1., 1., 1., False), (1., 1., 1., False), (1., 1., 1., False), (1., 1., 1., False), (1., 1., 1., False),
+    )
     # evaluation order of define_sem (CoralGraph.py:148-160) and the regressions' inputs (var_dependencies, :40-50)
     sem_order = ("N", "L", "TE", "C", "S", "T", "D", "P", "O", "CO", "Y")
     var_dependencies = OrderedDict([

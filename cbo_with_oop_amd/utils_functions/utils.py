@@ -41,6 +41,43 @@ def fit_gaussian_process(x, y, parameter_list):
     return gp
 
 
+def fit_gaussian_processes(xs, ys, parameter_lists, lockstep=True):
+    """``[fit_gaussian_process(x, y, p) for ...]`` -- the graph-level GPs of an observe step -- with the hyper-parameter
+    MLEs run together: every round of the models' L-BFGS-B runs is ONE device call for all of them
+    (``GaussianProcessFactory.optimize_together``).  Models of at most 128 rows get the trajectories and results of
+    fitting them one by one, bit for bit; those of 128 < n <= 256 are evaluated by the device's two-block form without
+    refits (the same values to rounding).  ``lockstep=False`` fits them one by one."""
+    from ..GaussianProcessFactory import GaussianProcessFactory, GaussianProcessType, optimize_together
+    if not lockstep:
+        return [fit_gaussian_process(x, y, p) for x, y, p in zip(xs, ys, parameter_lists)]
+    models = [GaussianProcessFactory.create(GaussianProcessType.GRAPH_GP, x, y, p)
+              for x, y, p in zip(xs, ys, parameter_lists)]
+    optimize_together(models)
+    return models
+
+
+def update_hull(observational_samples, manipulative_variables):
+    """src/utils_functions/cbo_functions.py:7-17: volume of the convex hull of the observations of the manipulative
+    variables (``observational_samples[v]`` a column per variable)."""
+    from scipy.spatial import ConvexHull
+    stack = np.column_stack([np.asarray(observational_samples[v], dtype=np.float64).reshape(-1)
+                             for v in manipulative_variables])
+    return ConvexHull(stack).volume
+
+
+def compute_coverage(observational_samples, manipulative_variables, dict_ranges):
+    """src/utils_functions/cbo_functions.py:26-41: (coverage of the observations' hull over the box of the interventional
+    ranges, the observations' hull, the box's volume)."""
+    import itertools
+    from scipy.spatial import ConvexHull
+    vertices = list(itertools.product(*[dict_ranges[v] for v in manipulative_variables]))
+    coverage_total = ConvexHull(vertices).volume
+    stack = np.column_stack([np.asarray(observational_samples[v], dtype=np.float64).reshape(-1)
+                             for v in manipulative_variables])
+    hull_obs = ConvexHull(stack)
+    return hull_obs.volume / coverage_total, hull_obs, coverage_total
+
+
 def space_bounds(space):
     """[(lo, hi)] from an emukit ParameterSpace (``get_bounds()``), from objects with ``.parameters``
     carrying ``.min/.max`` (graph_functions.py:80-93 builds ContinuousParameter(name, min, max)), or

@@ -154,6 +154,18 @@ int cbo_gp_log_marginal(cbo_gp *gp, double *lml_out);
  * ladder and the general path answers).  Larger models: CBO_ERR_NOT_FITTED until fitted. */
 int cbo_gp_lml_gradients(cbo_gp *gp, double *lml_out, double *dvariance_out, double *dlengthscale_out,
                          double *dnoise_out);
+/* The same for many independent models in one call: the graph-level GPs an observe step fits
+ * (src/graphs/impl/CompleteGraph.py:114-137, CoralGraph.py:186-212, SimplifiedCoralGraph.py:194-220: one
+ * src/utils_functions/utils.py:40-45 fit_gaussian_process, i.e. one GPy gp.optimize(), per fit dependency), each at its
+ * own optimiser iterate.  Every model cbo_gp_lml_gradients would answer in one launch (fp64, at most 128 observations)
+ * is answered inside ONE launch for all of them, with the same bits; the others -- larger models (fitted beforehand, as
+ * for cbo_gp_lml_gradients), and models whose Ky is not positive definite as assembled (fitted here with the jitchol
+ * ladder) -- by the general path, one by one, without touching the rest.  All models live on one context.  Outputs per
+ * model i: lml[i], dvar[i], dls[i * CBO_MAX_DIM + k] (k < 1, or < d if ard), dnoise[i], status[i] = CBO_OK or the
+ * error cbo_gp_lml_gradients would have returned for that model alone (its outputs are then undefined).  The call
+ * itself fails only on bad arguments or a device error. */
+int cbo_gp_lml_gradients_batch(int n_models, cbo_gp *const *gps, double *lml, double *dvar, double *dls,
+                               double *dnoise, int *status);
 
 /* Prediction gradients: emukit GPyModelWrapper.get_prediction_gradients -> GPy
  * predictive_gradients, called from CausalExpectedImprovement.evaluate_with_gradients
