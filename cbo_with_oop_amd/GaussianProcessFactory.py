@@ -66,9 +66,11 @@ class HipGaussianProcess:
     """GP posterior resident on one MI355X.  Duck-types the two objects the reference uses:
 
     * GPy ``GPRegression``: ``predict(Xnew)`` -> (mean (M,1), var (M,1)) with the Gaussian likelihood
-      noise included (used by src/DoCalculus.py:77), ``X``, ``Y``, ``set_XY``, ``optimize``.
+      noise included (used by src/DoCalculus.py:77), ``predict(Xnew, full_cov=True)``,
+      ``posterior_covariance_between_points``, ``X``, ``Y``, ``set_XY``, ``optimize``.
     * emukit ``GPyModelWrapper``: ``predict``, ``set_data`` (src/Monitor.py:160), ``optimize``
-      (src/CBO.py:173), ``X``, ``Y``, ``model``.
+      (src/CBO.py:173), ``predict_with_full_covariance``, ``predict_covariance``, ``get_covariance_between_points``,
+      ``calculate_variance_reduction``, ``X``, ``Y``, ``model``.
     """
 
     def __init__(self, x, y, *, variance=1.0, lengthscale=1.0, ard=False, noise_var=1e-10, mean_function=None,
@@ -187,14 +189,26 @@ class HipGaussianProcess:
         """emukit's wrapper exposes the GPy model as ``.model``; here they are the same object."""
         return self
 
-    def predict(self, x, include_likelihood=True):
-        """(mean (M,1), var (M,1)); GP.predict / GPyModelWrapper.predict."""
+    def _points(self, x):
         x = _lib.as_f64(x)
         if x.ndim != 2 or x.shape[1] != self.input_dim:
             raise ValueError(f"x must be (M, {self.input_dim})")
+        return x
+
+    def predict(self, x, include_likelihood=True, full_cov=False):
+        """(mean (M,1), var (M,1)); GP.predict / GPyModelWrapper.predict.  ``full_cov=True``: (mean (M,1), cov (M,M)),
+        GPy's full_cov branch (``cbo_gp_predict_cov``): not clipped, the likelihood noise on the diagonal only, and for
+        the causal kernel a diagonal of variance * exp(-r2_ii / 2) + v(x) rather than Kdiag (include/cbo_hip.h)."""
+        x = self._points(x)
         m = x.shape[0]
         pm, pv = self._prior(x)
         mean = np.empty(m)
+        if full_cov:
+            cov = np.empty((m, m))
+            self.ensure_fitted()
+            _lib.check(self._lib.cbo_gp_predict_cov(self._handle, m, _lib.dptr(x), _lib.dptr(pm), _lib.dptr(pv),
+                                                    int(include_likelihood), _lib.dptr(mean), _lib.dptr(cov)))
+            return mean[:, None], cov
         var = np.empty(m)
         self.ensure_fitted()
         _lib.check(self._lib.cbo_gp_predict(self._handle, m, _lib.dptr(x), _lib.dptr(pm), _lib.dptr(pv),
@@ -241,6 +255,45 @@ class HipGaussianProcess:
 
     def predict_noiseless(self, x):
         return self.predict(x, include_likelihood=False)
+
+    def posterior_covariance_between_points(self, X1, X2):
+        """GPy ``posterior_covariance_between_points`` without the likelihood: K(X1,X2) - (L^-1 K(X,X1))^T L^-1 K(X,X2),
+        (M1, M2) (``cbo_gp_cov_between``).  GPy is not installed here: parity unpinned."""
+        X1, X2 = self._points(X1), self._points(X2)
+        m1, m2 = X1.shape[0], X2.shape[0]
+        pv1 = self._prior(X1)[1]
+        pv2 = self._prior(X2)[1]
+        cov = np.empty((m1, m2))
+        self.ensure_fitted()
+        _lib.check(self._lib.cbo_gp_cov_between(self._handle, m1, _lib.dptr(X1), _lib.dptr(pv1), m2, _lib.dptr(X2),
+                                                _lib.dptr(pv2), _lib.dptr(cov)))
+        return cov
+
+    # emukit GPyModelWrapper's covariance interface.  Emukit is not installed here: the bodies restate emukit 0.4's
+    # gpy_model_wrappers.py from memory, and parity is unpinned for every one of them.
+    def predict_with_full_covariance(self, X):
+        """emukit ``predict_with_full_covariance``: ``model.predict(X, full_cov=True)`` -> (mean (M,1), cov (M,M)), noise
+        included.  Restated from memory, parity unpinned."""
+        return self.predict(X, full_cov=True)
+
+    def predict_covariance(self, X, with_noise=True):
+        """emukit ``predict_covariance``: the (M,M) covariance of ``model.predict(X, full_cov=True,
+        include_likelihood=with_noise)``, clipped elementwise at 1e-10 as recalled of emukit 0.4 (not checked against its
+        source).  Restated from memory, parity unpinned."""
+        _, cov = self.predict(X, include_likelihood=with_noise, full_cov=True)
+        return np.clip(cov, 1e-10, np.inf)
+
+    def get_covariance_between_points(self, X1, X2):
+        """emukit ``get_covariance_between_points``: ``model.posterior_covariance_between_points(X1, X2)``.  Restated from
+        memory, parity unpinned."""
+        return self.posterior_covariance_between_points(X1, X2)
+
+    def calculate_variance_reduction(self, x_train_new, x_test):
+        """emukit ``calculate_variance_reduction``: cov(x_train_new, x_test)^2 / predict(x_train_new)[1], the drop in
+        variance at ``x_test`` from observing ``x_train_new``.  Restated from memory, parity unpinned."""
+        covariance = self.posterior_covariance_between_points(x_train_new, x_test)
+        variance_prediction = self.predict(x_train_new)[1]
+        return covariance ** 2 / variance_prediction
 
     def set_data(self, X, Y, fit=True):
         """GPyModelWrapper.set_data -> GP.set_XY: replace the data and refit (src/Monitor.py:160).  When the new data

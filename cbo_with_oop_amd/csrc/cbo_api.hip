@@ -119,6 +119,7 @@ struct cbo_ctx {
     cbo_cands *scratch_k = nullptr;
     double *grads = nullptr; size_t grads_elems = 0;
     double *export_buf = nullptr; size_t export_elems = 0;
+    double *cov = nullptr; size_t cov_elems = 0;       // output of cbo_gp_predict_cov / cbo_gp_cov_between (grow-only)
     // small uploads (cbo_gp_upload_data / cbo_gp_set_data of a few KB, every trial of the reference's loop): one
     // pinned staging buffer the preparation kernel reads directly; `stage_done` guards its reuse
     double *stage = nullptr; hipEvent_t stage_done = nullptr; bool stage_pending = false;
@@ -386,7 +387,7 @@ static void destroy_ctx(cbo_ctx *c)
 {
     hipSetDevice(c->device);
     if (c->scratch_k) { cbo_cands_destroy(c->scratch_k); c->scratch_k = nullptr; }
-    hipFree(c->grads); hipFree(c->export_buf);
+    hipFree(c->grads); hipFree(c->export_buf); hipFree(c->cov);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : c->pool) hipEventDestroy(e);
@@ -2010,8 +2011,9 @@ extern "C" int cbo_acq_sweep_host(cbo_gp *g, int64_t m, const double *Xs, const 
 }
 
 // posterior mean / variance of m host points into the context's mean / var vectors (device), via the scratch set
+// (f64_solution: an fp32 model solves on its fp64 factor too, leaving V = L^-1 K* in the fp64 workspace)
 static int posterior_of_host_points(cbo_gp *g, int64_t m, const double *Xs, const double *pm, const double *pv,
-                                    int include_noise, cbo_cands **k_out)
+                                    int include_noise, cbo_cands **k_out, bool f64_solution = false)
 {
     const bool causal = g->X.sv != nullptr;
     if (causal && (!pm || !pv)) return fail(CBO_ERR_INVALID, "causal gp needs candidate prior mean/variance");
@@ -2019,7 +2021,7 @@ static int posterior_of_host_points(cbo_gp *g, int64_t m, const double *Xs, cons
     cbo_cands *k = nullptr;
     int rc = scratch_cands(c, m, g->d, Xs, causal ? pm : nullptr, causal ? pv : nullptr, &k);
     if (rc != CBO_OK) return rc;
-    rc = enqueue_posterior(g, k);
+    rc = enqueue_posterior(g, k, f64_solution);
     if (rc != CBO_OK) return rc;
     AcqParams p;
     p.variance = g->h.variance; p.noise_var = g->noise_var; p.y_best = 0.0; p.ei_jitter = 0.0; p.cost = 1.0;
@@ -2047,6 +2049,120 @@ extern "C" int cbo_gp_predict(cbo_gp *g, int64_t m, const double *Xs, const doub
     HIP_TRY(hipMemcpyAsync(var_out, c->var, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->profiling) c->timers.n_sweep += 1;
+    return CBO_OK;
+}
+
+// ---- joint posterior covariance (kernels_cov.hip) ----------------------------------------------------------------
+// Both entry points solve V = L^-1 K* afresh on every call (a model changed by cbo_gp_append, set_data, set_hyper or a
+// refit can never meet an old solution) into the context's fp64 workspace, which must hold all m columns at once, then
+// run cov_tile_kernel into the context's grow-only output buffer and copy it to the caller in one piece.
+
+// the fp64 solution of a candidate set with m_pad columns stays resident in ONE workspace chunk: its leading dimension
+static int resident_solution_ld(cbo_gp *g, int64_t m_pad, int64_t *ldv)
+{
+    int64_t chunk = 0;
+    int rc = ensure_workspaces(g->ctx, g->n_pad, m_pad, &chunk, ldv);
+    if (rc != CBO_OK) return rc;
+    if (chunk < m_pad) return fail(CBO_ERR_INVALID, "too many points: their solution L^-1 K* does not fit the workspace");
+    return CBO_OK;
+}
+
+static int ensure_cov(cbo_ctx *c, size_t elems)
+{
+    if (elems > c->cov_elems) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        hipFree(c->cov);
+        c->cov = nullptr; c->cov_elems = 0;
+        HIP_TRY(hipMalloc(&c->cov, sizeof(double) * elems));
+        c->cov_elems = elems;
+    }
+    return CBO_OK;
+}
+
+// C = K(X1, X2) - V1^T V2 for the points of k at columns [a_off, a_off + m1) and [b_off, b_off + m2), into c->cov
+static void enqueue_cov(cbo_gp *g, const cbo_cands *k, int64_t ldv, int64_t a_off, int64_t m1, int64_t b_off, int64_t m2,
+                        bool sym, double noise)
+{
+    const bool causal = g->X.sv != nullptr;
+    CovArgs a;
+    a.V = g->ctx->V; a.ldv = ldv;
+    a.a_off = a_off; a.b_off = b_off; a.v_cols = k->m_pad;
+    a.n_k = (int)g->n;
+    a.xs1 = k->P.xs + a_off; a.sq1 = k->P.sq + a_off; a.sv1 = causal ? k->P.sv + a_off : nullptr;
+    a.xs2 = k->P.xs + b_off; a.sq2 = k->P.sq + b_off; a.sv2 = causal ? k->P.sv + b_off : nullptr;
+    a.ldx = k->P.ld;
+    a.m1 = m1; a.m2 = m2;
+    a.C = g->ctx->cov; a.ldc = m2;
+    a.variance = g->h.variance; a.inv_l2 = 1.0 / (g->h.lengthscale * g->h.lengthscale); a.noise = noise;
+    a.zero_diag = g->h.zero_diag; a.tiles = 0;
+    launch_cov_tiles(g->ctx->stream, g->d, sym, a);
+}
+
+extern "C" int cbo_gp_predict_cov(cbo_gp *g, int64_t m, const double *Xs, const double *pm, const double *pv,
+                                  int include_noise, double *mean_out, double *cov_out)
+{
+    if (!g || !Xs || !cov_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (m <= 0) return fail(CBO_ERR_INVALID, "m must be positive");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    const bool causal = g->X.sv != nullptr;
+    if (causal && (!pv || (mean_out && !pm)))
+        return fail(CBO_ERR_INVALID, "causal gp needs the prior variance at the points (and the prior mean for the mean)");
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    int64_t ldv = 0;
+    int rc = resident_solution_ld(g, round_up(m, kStrip), &ldv);
+    if (rc != CBO_OK) return rc;
+    rc = ensure_cov(c, (size_t)m * (size_t)m);
+    if (rc != CBO_OK) return rc;
+    // without mean_out the prior mean is not needed: the epilogue's mean (discarded) is formed from pv in its place
+    cbo_cands *k = nullptr;
+    rc = posterior_of_host_points(g, m, Xs, (causal && !pm) ? pv : pm, pv, 0, &k, true);
+    if (rc != CBO_OK) return rc;
+    enqueue_cov(g, k, ldv, 0, m, 0, m, true, include_noise ? g->noise_var : 0.0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cov_out, c->cov, sizeof(double) * (size_t)m * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    if (mean_out) HIP_TRY(hipMemcpyAsync(mean_out, c->mean, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CBO_OK;
+}
+
+extern "C" int cbo_gp_cov_between(cbo_gp *g, int64_t m1, const double *X1, const double *pv1, int64_t m2,
+                                  const double *X2, const double *pv2, double *cov_out)
+{
+    if (!g || !X1 || !X2 || !cov_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (m1 <= 0 || m2 <= 0) return fail(CBO_ERR_INVALID, "m1 and m2 must be positive");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    const bool causal = g->X.sv != nullptr;
+    if (causal && (!pv1 || !pv2)) return fail(CBO_ERR_INVALID, "causal gp needs the prior variance at both point sets");
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    // one candidate set [X1 | filler | X2] with X2 starting on a strip boundary: one solve gives V1 and V2 side by side
+    const int d = g->d;
+    const int64_t off = round_up(m1, kStrip), mt = off + m2;
+    int64_t ldv = 0;
+    int rc = resident_solution_ld(g, round_up(mt, kStrip), &ldv);
+    if (rc != CBO_OK) return rc;
+    rc = ensure_cov(c, (size_t)m1 * (size_t)m2);
+    if (rc != CBO_OK) return rc;
+    std::vector<double> xs((size_t)mt * d), vs(causal ? (size_t)mt : 0);
+    std::memcpy(xs.data(), X1, sizeof(double) * (size_t)m1 * d);
+    for (int64_t i = m1; i < off; ++i) std::memcpy(&xs[(size_t)i * d], X1, sizeof(double) * d);   // filler: unused columns
+    std::memcpy(&xs[(size_t)off * d], X2, sizeof(double) * (size_t)m2 * d);
+    if (causal) {
+        std::memcpy(vs.data(), pv1, sizeof(double) * (size_t)m1);
+        for (int64_t i = m1; i < off; ++i) vs[(size_t)i] = pv1[0];
+        std::memcpy(&vs[(size_t)off], pv2, sizeof(double) * (size_t)m2);
+    }
+    // (no mean is formed: the prior variance also stands in for the prior mean the candidate set wants with it)
+    cbo_cands *k = nullptr;
+    rc = scratch_cands(c, mt, d, xs.data(), causal ? vs.data() : nullptr, causal ? vs.data() : nullptr, &k);
+    if (rc != CBO_OK) return rc;
+    rc = enqueue_posterior(g, k, true);
+    if (rc != CBO_OK) return rc;
+    enqueue_cov(g, k, ldv, 0, m1, off, m2, false, 0.0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cov_out, c->cov, sizeof(double) * (size_t)m1 * (size_t)m2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return CBO_OK;
 }
 

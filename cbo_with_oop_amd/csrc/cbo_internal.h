@@ -101,6 +101,22 @@ void launch_rhs(hipStream_t s, const double *y, const double *pm, int64_t n, dou
 void launch_kstar(hipStream_t s, const PointSet &X, const PointSet &C, int64_t c_begin, int64_t m_pad,
                   const KernelHyper &h, double *V, int64_t ldv, int64_t n_pad);
 
+// Joint posterior covariance (kernels_cov.hip): C[i][j] = K(X1_i, X2_j) - sum_{k < n_k} V[k][a_off + i] V[k][b_off + j]
+// for i < m1, j < m2 into C (row-major, ldc).  V is the resident solution L^-1 K* of a candidate set holding both point
+// sets (rows >= n are zero); xs / sq / sv the scaled SoA points (ld = ldx) of X1 and X2 (sv: sqrt of the prior variance,
+// null = non-causal).  sym: X1 = X2, upper tiles only, mirrored stores, zero-distance rule (zero_diag) and noise on the
+// diagonal.  Columns of V are read below v_cols only.
+struct CovArgs {
+    const double *V; int64_t ldv;
+    int64_t a_off, b_off, v_cols;
+    int n_k;
+    const double *xs1, *sq1, *sv1, *xs2, *sq2, *sv2; int64_t ldx;
+    int64_t m1, m2;
+    double *C; int64_t ldc;
+    double variance, inv_l2, noise;
+    int zero_diag, tiles;
+};
+void launch_cov_tiles(hipStream_t s, int d, bool sym, CovArgs a);
 // ---- fp32 sweep (kernels_f32.hip; BASELINE.json configs[4]) -----------------------------------------------
 // The fit stays fp64; factor, diagonal inverses and z are down-converted once per fit into a layout whose 16-row
 // groups are row-permuted (physical row 4 (k & 3) + (k >> 2) = logical row k) and padded to n32 = round_up(n_pad, 256).

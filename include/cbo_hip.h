@@ -138,6 +138,34 @@ int cbo_gp_append(cbo_gp *gp, const double *x_new, double y_new, double prior_me
 int cbo_gp_predict(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
                    const double *prior_var_s, int include_noise, double *mean_out, double *var_out);
 
+/* Joint posterior (emukit GPyModelWrapper.predict_with_full_covariance / predict_covariance /
+ * get_covariance_between_points / calculate_variance_reduction, the methods emukit's multipoint, variance-reduction and
+ * entropy acquisitions call next to src/utils_functions/causal_acquisition_functions.py).
+ *
+ * cbo_gp_predict_cov: GPy GP.predict(X, full_cov=True) -> PosteriorExact._raw_predict, full_cov branch,
+ * Kxx - (L^-1 Kx)^T (L^-1 Kx) (+ mean function, + Gaussian.predictive_values: noise_var on the diagonal when
+ * include_noise).  mean_out (m, may be NULL) is what cbo_gp_predict returns; cov_out is m*m row-major, exactly symmetric.
+ * cbo_gp_cov_between: GPy posterior_covariance_between_points(X1, X2) (include_likelihood=False):
+ * K(X1,X2) - (L^-1 K(X,X1))^T (L^-1 K(X,X2)); cov_out m1*m2 row-major; noise-free.
+ *
+ * The prior term follows the kernel GPy evaluates, in kmat's operation order (GEMM-trick squared distance, clip at 0,
+ * scale, exp, causal term):
+ *  - non-causal models (GPy RBF): Kxx = K(X) with X2 = None, so the squared distance on the diagonal of
+ *    cbo_gp_predict_cov is exactly 0 (the model's zero_diag rule, as for K(X,X)); cbo_gp_cov_between passes X2.
+ *  - causal models (CausalRBF.K, src/utils_functions/causal_kernels.py:53-61): X2 is always passed explicitly, no
+ *    diagonal shortcut, and sqrt(v(X1)) sqrt(v(X2))^T is added everywhere.  The diagonal of the full covariance is
+ *    therefore NOT Kdiag (variance + v, causal_kernels.py:64-79) but variance * exp(-r2_ii / 2) + v, r2_ii the rounding
+ *    residue of the GEMM-trick distance of a point to itself: GPy's quirk, kept.
+ * The full covariance is not clipped (the 1e-15 clip of cbo_gp_predict belongs to the diagonal branch).  Causal models
+ * need prior_var_* (and prior_mean_s when mean_out is requested): CBO_ERR_INVALID otherwise.  Unfitted model:
+ * CBO_ERR_NOT_FITTED; NULL arguments or m <= 0: CBO_ERR_INVALID; a failed device allocation: CBO_ERR_HIP.  fp32 models
+ * answer from the fp64 factor (the fp64 model's result).  Every call solves L^-1 K* afresh; the solution of all points
+ * must fit the context's workspace at once. */
+int cbo_gp_predict_cov(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
+                       const double *prior_var_s, int include_noise, double *mean_out, double *cov_out);
+int cbo_gp_cov_between(cbo_gp *gp, int64_t m1, const double *X1, const double *prior_var_1,
+                       int64_t m2, const double *X2, const double *prior_var_2, double *cov_out);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
