@@ -62,12 +62,27 @@ def _column(values, n, what):
     return v
 
 
+def standard_normals(size, m):
+    """The (size, M) standard normals ``np.random.multivariate_normal(mean, cov, size)`` draws for an M-dimensional
+    mean, from numpy's global legacy stream and in the same order: a seeded run stays aligned with GPy's."""
+    return np.random.standard_normal((int(size), int(m)))
+
+
+def gaussian_likelihood_samples(f, variance):
+    """GPy ``Gaussian.samples``: one ``np.random.normal(f_j, sqrt(variance), size=1)`` per element of ``f`` in flattened
+    order, reshaped to ``f``'s shape."""
+    f = np.asarray(f, dtype=np.float64)
+    scale = np.sqrt(variance)
+    return np.array([np.random.normal(fj, scale=scale, size=1) for fj in f.flatten()]).reshape(f.shape)
+
+
 class HipGaussianProcess:
     """GP posterior resident on one MI355X.  Duck-types the two objects the reference uses:
 
     * GPy ``GPRegression``: ``predict(Xnew)`` -> (mean (M,1), var (M,1)) with the Gaussian likelihood
       noise included (used by src/DoCalculus.py:77), ``predict(Xnew, full_cov=True)``,
-      ``posterior_covariance_between_points``, ``X``, ``Y``, ``set_XY``, ``optimize``.
+      ``posterior_covariance_between_points``, ``posterior_samples_f``, ``posterior_samples``, ``X``, ``Y``,
+      ``set_XY``, ``optimize``.
     * emukit ``GPyModelWrapper``: ``predict``, ``set_data`` (src/Monitor.py:160), ``optimize``
       (src/CBO.py:173), ``predict_with_full_covariance``, ``predict_covariance``, ``get_covariance_between_points``,
       ``calculate_variance_reduction``, ``X``, ``Y``, ``model``.
@@ -294,6 +309,50 @@ class HipGaussianProcess:
         covariance = self.posterior_covariance_between_points(x_train_new, x_test)
         variance_prediction = self.predict(x_train_new)[1]
         return covariance ** 2 / variance_prediction
+
+    # GPy GP's joint posterior samples.  GPy is not installed here: the bodies restate GPy 1.10's core/gp.py and
+    # likelihoods/gaussian.py from memory, parity unpinned.
+    last_sample_jitter = (0, 0.0)      # (retries, jitter) of the last posterior_samples_f call's factor of Sigma
+
+    def posterior_samples_f(self, X, size=10, normals=None, **predict_kwargs):
+        """GPy ``posterior_samples_f``: ``size`` joint draws of f at ``X`` from the noise-free posterior, shape (M, 1, size)
+        (``cbo_gp_posterior_samples``).  The normals default to ``standard_normals(size, M)`` -- exactly the draws, in the
+        same order, that ``np.random.multivariate_normal(mean, cov, size)`` takes inside GPy, so numpy's global stream is
+        left where GPy would leave it; ``normals=`` passes a (size, M) block of one's own.  GPy factors the covariance by
+        SVD, the device by Cholesky (with a jitter ladder, ``last_sample_jitter``): the draws have the same distribution
+        but are not GPy's draw for draw.  Parity unpinned: GPy not importable here."""
+        if predict_kwargs.get("kern") is not None:
+            raise NotImplementedError("posterior_samples_f: a kernel other than the model's (kern=) is not supported")
+        x = self._points(X)
+        m, size = x.shape[0], int(size)
+        if normals is None:
+            normals = standard_normals(size, m)
+        normals = _lib.as_f64(normals)
+        if normals.shape != (size, m):
+            raise ValueError(f"normals must be (size, M) = ({size}, {m}), got {normals.shape}")
+        pm, pv = self._prior(x)
+        out = np.empty((m, size))
+        tries = ctypes.c_int(0)
+        jitter = ctypes.c_double(0.0)
+        self.ensure_fitted()
+        _lib.check(self._lib.cbo_gp_posterior_samples(self._handle, m, _lib.dptr(x), _lib.dptr(pm), _lib.dptr(pv), size,
+                                                      _lib.dptr(normals), _lib.dptr(out), ctypes.byref(tries),
+                                                      ctypes.byref(jitter)))
+        self.last_sample_jitter = (tries.value, jitter.value)
+        return out[:, None, :]
+
+    def posterior_samples(self, X, size=10, Y_metadata=None, likelihood=None, **predict_kwargs):
+        """GPy ``posterior_samples``: ``posterior_samples_f`` with the likelihood's noise added on the host,
+        (M, 1, size).  The Gaussian likelihood draws one ``np.random.normal(f, sqrt(noise_var), size=1)`` per element
+        in flattened order (``gaussian_likelihood_samples``), as GPy's ``Gaussian.samples``.  Parity unpinned: GPy not
+        importable here."""
+        fsim = self.posterior_samples_f(X, size, **predict_kwargs)
+        for d in range(fsim.shape[1]):
+            if likelihood is None:
+                fsim[:, d] = gaussian_likelihood_samples(fsim[:, d], self.noise_var)
+            else:
+                fsim[:, d] = likelihood.samples(fsim[:, d], Y_metadata=Y_metadata)
+        return fsim
 
     def set_data(self, X, Y, fit=True):
         """GPyModelWrapper.set_data -> GP.set_XY: replace the data and refit (src/Monitor.py:160).  When the new data

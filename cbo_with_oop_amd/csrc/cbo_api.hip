@@ -120,6 +120,13 @@ struct cbo_ctx {
     double *grads = nullptr; size_t grads_elems = 0;
     double *export_buf = nullptr; size_t export_elems = 0;
     double *cov = nullptr; size_t cov_elems = 0;       // output of cbo_gp_predict_cov / cbo_gp_cov_between (grow-only)
+    // cbo_gp_posterior_samples (grow-only): the factor of Sigma in the factorisation's layout, its diagonal-tile
+    // inverses and status words, the transposed normals, the samples (which first hold the uploaded normals)
+    double *samp_A = nullptr; size_t samp_A_elems = 0;
+    double *samp_invDt = nullptr; size_t samp_invDt_elems = 0;
+    int *samp_info = nullptr;
+    double *samp_Z = nullptr; size_t samp_Z_elems = 0;
+    double *samp_out = nullptr; size_t samp_out_elems = 0;
     // small uploads (cbo_gp_upload_data / cbo_gp_set_data of a few KB, every trial of the reference's loop): one
     // pinned staging buffer the preparation kernel reads directly; `stage_done` guards its reuse
     double *stage = nullptr; hipEvent_t stage_done = nullptr; bool stage_pending = false;
@@ -388,6 +395,7 @@ static void destroy_ctx(cbo_ctx *c)
     hipSetDevice(c->device);
     if (c->scratch_k) { cbo_cands_destroy(c->scratch_k); c->scratch_k = nullptr; }
     hipFree(c->grads); hipFree(c->export_buf); hipFree(c->cov);
+    hipFree(c->samp_A); hipFree(c->samp_invDt); hipFree(c->samp_info); hipFree(c->samp_Z); hipFree(c->samp_out);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : c->pool) hipEventDestroy(e);
@@ -2080,8 +2088,9 @@ static int ensure_cov(cbo_ctx *c, size_t elems)
 }
 
 // C = K(X1, X2) - V1^T V2 for the points of k at columns [a_off, a_off + m1) and [b_off, b_off + m2), into c->cov
+// (or into C, row-major with leading dimension ldc)
 static void enqueue_cov(cbo_gp *g, const cbo_cands *k, int64_t ldv, int64_t a_off, int64_t m1, int64_t b_off, int64_t m2,
-                        bool sym, double noise)
+                        bool sym, double noise, double *C = nullptr, int64_t ldc = 0)
 {
     const bool causal = g->X.sv != nullptr;
     CovArgs a;
@@ -2092,7 +2101,7 @@ static void enqueue_cov(cbo_gp *g, const cbo_cands *k, int64_t ldv, int64_t a_of
     a.xs2 = k->P.xs + b_off; a.sq2 = k->P.sq + b_off; a.sv2 = causal ? k->P.sv + b_off : nullptr;
     a.ldx = k->P.ld;
     a.m1 = m1; a.m2 = m2;
-    a.C = g->ctx->cov; a.ldc = m2;
+    a.C = C ? C : g->ctx->cov; a.ldc = C ? ldc : m2;
     a.variance = g->h.variance; a.inv_l2 = 1.0 / (g->h.lengthscale * g->h.lengthscale); a.noise = noise;
     a.zero_diag = g->h.zero_diag; a.tiles = 0;
     launch_cov_tiles(g->ctx->stream, g->d, sym, a);
@@ -2163,6 +2172,110 @@ extern "C" int cbo_gp_cov_between(cbo_gp *g, int64_t m1, const double *X1, const
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(cov_out, c->cov, sizeof(double) * (size_t)m1 * (size_t)m2, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return CBO_OK;
+}
+
+// ---- joint posterior samples (kernels_samples.hip) ---------------------------------------------------------------
+// V = L^-1 K* is solved as for cbo_gp_predict_cov; cov_tile_kernel then writes Sigma + jitter I straight into a
+// factorisation buffer in the model factor's own layout ([m_pad][m_pad + 80], identity padding, zero right-hand-side
+// strip), launch_cholesky factors it and samples_tile_kernel forms mean + L Z^T.  A jitter retry re-runs only the cov
+// launch from the resident V.  The model's factor, z, alpha and status word are never written.
+
+static int grow_buffer(cbo_ctx *c, double **p, size_t *cap, size_t elems)
+{
+    if (elems > *cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        hipFree(*p);
+        *p = nullptr; *cap = 0;
+        HIP_TRY(hipMalloc(p, sizeof(double) * elems));
+        *cap = elems;
+    }
+    return CBO_OK;
+}
+
+// one attempt at the factor of Sigma + jitter I in c->samp_A (status words and fused-launch fallback as attempt_factor)
+static int attempt_sample_factor(cbo_gp *g, const cbo_cands *k, int64_t ldv, int64_t m, int64_t m_pad, int64_t lda,
+                                 double jitter, bool *pd)
+{
+    cbo_ctx *c = g->ctx;
+    FusedFallback fallback;
+    for (;;) {
+        launch_factor_padding(c->stream, c->samp_A, lda, m, m_pad);
+        enqueue_cov(g, k, ldv, 0, m, 0, m, true, jitter, c->samp_A, lda);
+        launch_cholesky(c->stream, c->side_stream, c->chol_events, c->samp_A, lda, m_pad, c->samp_invDt, c->samp_info);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->h_info, c->samp_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (*c->h_info == kCholFusedTimeout) {
+            if (fallback.active())
+                return fail(CBO_ERR_HIP, "a fused diagonal + panel launch gave up waiting, and so did the separate-launch repeat");
+            fallback.engage(c);
+            continue;
+        }
+        *pd = *c->h_info == 0;
+        return CBO_OK;
+    }
+}
+
+extern "C" int cbo_gp_posterior_samples(cbo_gp *g, int64_t m, const double *Xs, const double *pm, const double *pv,
+                                        int64_t n_samples, const double *normals, double *samples_out, int *tries_out,
+                                        double *jitter_out)
+{
+    if (!g || !Xs || !normals || !samples_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (m <= 0) return fail(CBO_ERR_INVALID, "m must be positive");
+    if (n_samples <= 0) return fail(CBO_ERR_INVALID, "n_samples must be positive");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    const bool causal = g->X.sv != nullptr;
+    if (causal && (!pv || !pm)) return fail(CBO_ERR_INVALID, "causal gp needs the prior mean and variance at the points");
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t s = n_samples;
+    const int64_t m_pad = round_up(m, kPadN), lda = m_pad + kRhsCols + kLdExtra;
+    const int64_t ldz = round_up(s, kPadN) + kLdExtra;
+    int64_t ldv = 0;
+    int rc = resident_solution_ld(g, round_up(m, kStrip), &ldv);
+    if (rc == CBO_OK) rc = grow_buffer(c, &c->samp_A, &c->samp_A_elems, (size_t)m_pad * (size_t)lda);
+    if (rc == CBO_OK) rc = grow_buffer(c, &c->samp_invDt, &c->samp_invDt_elems, (size_t)(m_pad / 16) * 256);
+    if (rc == CBO_OK) rc = grow_buffer(c, &c->samp_Z, &c->samp_Z_elems, (size_t)m_pad * (size_t)ldz);
+    if (rc == CBO_OK) rc = grow_buffer(c, &c->samp_out, &c->samp_out_elems, (size_t)m * (size_t)s);
+    if (rc != CBO_OK) return rc;
+    if (!c->samp_info) HIP_TRY(hipMalloc(&c->samp_info, sizeof(int) * (1 + kCholFlagSlots)));
+    // the ladder's base: 1e-6 mean(Kdiag(X*)), the prior diagonal variance + v(x) (summed in extended precision)
+    long double kdiag = 0.0L;
+    for (int64_t i = 0; i < m; ++i) kdiag += (long double)(g->h.variance + (causal ? pv[i] : 0.0));
+    const double base = (double)(kdiag / (long double)m) * 1e-6;
+    // the normals go through the output buffer (the product overwrites them) into Z = normals^T
+    HIP_TRY(hipMemcpyAsync(c->samp_out, normals, sizeof(double) * (size_t)m * (size_t)s, hipMemcpyHostToDevice, c->stream));
+    launch_normals_transpose(c->stream, c->samp_out, m, s, c->samp_Z, m_pad, ldz);
+    cbo_cands *k = nullptr;
+    rc = posterior_of_host_points(g, m, Xs, pm, pv, 0, &k, true);
+    if (rc != CBO_OK) return rc;
+    double jitter = 0.0;
+    int tries = 0;
+    for (;;) {
+        bool pd = false;
+        rc = attempt_sample_factor(g, k, ldv, m, m_pad, lda, jitter, &pd);
+        if (rc != CBO_OK) return rc;
+        if (pd) break;
+        jitter = tries == 0 ? base : jitter * 10.0;
+        ++tries;
+        if (tries > 5 || !std::isfinite(jitter))
+            return fail(CBO_ERR_NOT_PD, "posterior covariance not positive definite, even with jitter.");
+    }
+    SampArgs a;
+    a.U = c->samp_A; a.ldu = lda;
+    a.Z = c->samp_Z; a.ldz = ldz;
+    a.mean = c->mean;
+    a.m = m; a.s = s;
+    a.F = c->samp_out; a.ldf = s;
+    a.tiles_i = a.tiles_j = 0;
+    launch_samples_tiles(c->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(samples_out, c->samp_out, sizeof(double) * (size_t)m * (size_t)s, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (tries_out) *tries_out = tries;
+    if (jitter_out) *jitter_out = jitter;
     return CBO_OK;
 }
 

@@ -117,6 +117,23 @@ struct CovArgs {
     int zero_diag, tiles;
 };
 void launch_cov_tiles(hipStream_t s, int d, bool sym, CovArgs a);
+// Joint posterior samples (kernels_samples.hip): F[i][j] = mean[i] + sum_{k <= i} U[k][i] Z[k][j] for i < m, j < s into
+// F (row-major, ldf).  U is the upper factor launch_cholesky leaves in [m_pad][ldu] (only k <= i is read as the factor),
+// Z the transposed normals [m_pad][ldz] (ldz >= round_up(s, 128), rows >= m zero).  tiles_* are set by the launcher.
+struct SampArgs {
+    const double *U; int64_t ldu;
+    const double *Z; int64_t ldz;
+    const double *mean;
+    int64_t m, s;
+    double *F; int64_t ldf;
+    int tiles_i, tiles_j;
+};
+void launch_samples_tiles(hipStream_t st, SampArgs a);
+// Z[k][j] = normals[j][k] (normals: s rows of m) over [m_pad][ldz], zero outside k < m, j < s
+void launch_normals_transpose(hipStream_t st, const double *normals, int64_t m, int64_t s, double *Z, int64_t m_pad,
+                              int64_t ldz);
+// padding of a factorisation buffer [m_pad][lda] holding an m x m matrix: identity rows >= m, zero columns >= m above
+void launch_factor_padding(hipStream_t st, double *A, int64_t lda, int64_t m, int64_t m_pad);
 // ---- fp32 sweep (kernels_f32.hip; BASELINE.json configs[4]) -----------------------------------------------
 // The fit stays fp64; factor, diagonal inverses and z are down-converted once per fit into a layout whose 16-row
 // groups are row-permuted (physical row 4 (k & 3) + (k >> 2) = logical row k) and padded to n32 = round_up(n_pad, 256).

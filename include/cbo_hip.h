@@ -166,6 +166,27 @@ int cbo_gp_predict_cov(cbo_gp *gp, int64_t m, const double *Xs, const double *pr
 int cbo_gp_cov_between(cbo_gp *gp, int64_t m1, const double *X1, const double *prior_var_1,
                        int64_t m2, const double *X2, const double *prior_var_2, double *cov_out);
 
+/* Joint posterior samples (GPy GP.posterior_samples_f(X, size), which draws np.random.multivariate_normal(mean, cov,
+ * size) from the full_cov prediction): samples_out[i][j] = mean_i + sum_k L[i][k] normals[j][k], with L L^T = Sigma +
+ * jitter I.  Sigma is exactly cbo_gp_predict_cov(..., include_noise = 0, ...) (the causal diagonal quirk and the
+ * zero-distance rule included) and the mean is cbo_gp_predict's, bit for bit.  normals: n_samples * m row-major, one
+ * draw per row (the caller's standard normals: the library has no generator of its own); samples_out: m * n_samples
+ * row-major, point i, sample j.  GPy factors Sigma by SVD, this call by Cholesky: same distribution, other draws.
+ *
+ * Jitter ladder: a plain attempt, then 1e-6 * mean(Kdiag(X*)) on the diagonal, x10 per retry, at most 5 retries; Kdiag
+ * is the PRIOR diagonal, variance + v(x), which is always positive.  This differs on purpose from jitchol (cbo_gp_fit),
+ * whose base is the mean of the matrix's own diagonal: a posterior diagonal can be ~1e-12 or slightly negative at
+ * training points, where jitchol would give up with "non-positive diagonal".  *jitter_tries_out (retries taken) and
+ * *jitter_out (the jitter of the factor used) may be NULL.
+ *
+ * Unfitted model: CBO_ERR_NOT_FITTED; NULL arguments, m <= 0, n_samples <= 0, or a causal model without prior_var_s or
+ * prior_mean_s: CBO_ERR_INVALID; the ladder runs out: CBO_ERR_NOT_PD; a failed device allocation: CBO_ERR_HIP.  fp32
+ * models answer from the fp64 factor.  The solution L^-1 K* of all points must fit the context's workspace at once, as
+ * for cbo_gp_predict_cov.  The model is left untouched (factor, z, alpha, fitted state, candidate sets). */
+int cbo_gp_posterior_samples(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
+                             const double *prior_var_s, int64_t n_samples, const double *normals, double *samples_out,
+                             int *jitter_tries_out, double *jitter_out);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
