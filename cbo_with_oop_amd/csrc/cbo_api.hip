@@ -693,9 +693,19 @@ struct FusedFallback {
     ~FusedFallback() { if (on) set_panel_form_override(0); }
 };
 
-// GPy util.linalg.jitchol after a failed attempt: first mean(diag) * 1e-6, then x10 per retry, at most 5 retries.
+// GPy util.linalg.jitchol after a failed attempt: first `base` (1e-6 mean(diag)), then x10 per retry, at most 5
+// retries.  false: the ladder is exhausted (the caller reports CBO_ERR_NOT_PD).
+static bool jitter_step(double base, int *tries, double *jitter)
+{
+    *jitter = *tries == 0 ? base : *jitter * 10.0;
+    ++*tries;
+    return *tries <= 5 && std::isfinite(*jitter);
+}
+
+// the next jitter of the model's own ladder, whose base is 1e-6 mean(diag Ky)
 static int next_jitter(cbo_gp *g, int *tries, double *jitter)
 {
+    double base = 0.0;
     if (*tries == 0) {
         // diag of Ky as assembled (jitter-free): variance + v_i + (noise + 1e-8); the kernel's own
         // diagonal differs from this only when zero_diag is off and |x|^2 rounds differently from
@@ -710,25 +720,22 @@ static int next_jitter(cbo_gp *g, int *tries, double *jitter)
             sum += (long double)dv;
         }
         if (nonpos) return fail(CBO_ERR_NONPOS_DIAG, "not pd: non-positive diagonal elements");
-        *jitter = (double)(sum / (long double)g->n) * 1e-6;
-    } else {
-        *jitter *= 10.0;
+        base = (double)(sum / (long double)g->n) * 1e-6;
     }
-    ++*tries;
-    if (*tries > 5 || !std::isfinite(*jitter))
-        return fail(CBO_ERR_NOT_PD, "not positive definite, even with jitter.");
+    if (!jitter_step(base, tries, jitter)) return fail(CBO_ERR_NOT_PD, "not positive definite, even with jitter.");
     return CBO_OK;
 }
 
-// one attempt at the factorisation with `jitter` on the diagonal: *pd says whether it went through
-static int attempt_factor(cbo_gp *g, double jitter, bool *pd)
+// one attempt at a factorisation: enqueue() queues it on c->stream, info is its device status word; *pd says whether it
+// went through
+template <class Enqueue>
+static int attempt_factor(cbo_ctx *c, const int *info, Enqueue enqueue, bool *pd)
 {
-    cbo_ctx *c = g->ctx;
     FusedFallback fallback;
     for (;;) {
-        enqueue_factor(g, jitter);
+        enqueue();
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->h_info, g->info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_info, info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (*c->h_info == kCholFusedTimeout) {
             // a strip of a fused diagonal + panel launch gave up waiting (see potrf_panel_fused_kernel): the same
@@ -774,7 +781,7 @@ extern "C" int cbo_gp_fit(cbo_gp *g, int *tries_out, double *jitter_out)
     int tries = 0;
     for (;;) {
         bool pd = false;
-        int rc = attempt_factor(g, jitter, &pd);
+        int rc = attempt_factor(c, g->info, [&] { enqueue_factor(g, jitter); }, &pd);
         if (rc != CBO_OK) return rc;
         if (pd) break;
         rc = next_jitter(g, &tries, &jitter);
@@ -818,7 +825,7 @@ extern "C" int cbo_gp_fit_level(cbo_gp *g, int level, int *status, double *jitte
     if (rc == CBO_ERR_NONPOS_DIAG) { *status = -1; return CBO_OK; }
     if (rc != CBO_OK) return rc;
     bool pd = false;
-    rc = attempt_factor(g, jitter, &pd);
+    rc = attempt_factor(c, g->info, [&] { enqueue_factor(g, jitter); }, &pd);
     if (rc != CBO_OK) return rc;
     *status = pd ? 1 : 0;
     if (jitter_out) *jitter_out = jitter;
@@ -896,14 +903,16 @@ extern "C" int cbo_gp_upload_data(cbo_gp *g, int64_t n, const double *X, const d
     return upload_gp_data(g, n, X, y, pm, pv);      // leaves the model unfitted
 }
 
-static int ensure_export(cbo_ctx *c, size_t elems)
+// a grow-only device buffer *p of *cap doubles, to at least elems: the old one is freed only after the queued work that
+// may read it is done
+static int grow_buffer(cbo_ctx *c, double **p, size_t *cap, size_t elems)
 {
-    if (elems > c->export_elems) {
+    if (elems > *cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->export_buf);
-        c->export_buf = nullptr; c->export_elems = 0;
-        HIP_TRY(hipMalloc(&c->export_buf, sizeof(double) * elems));
-        c->export_elems = elems;
+        hipFree(*p);
+        *p = nullptr; *cap = 0;
+        HIP_TRY(hipMalloc(p, sizeof(double) * elems));
+        *cap = elems;
     }
     return CBO_OK;
 }
@@ -915,7 +924,7 @@ extern "C" int cbo_gp_get_posterior(cbo_gp *g, double *L_out, double *alpha_out)
     cbo_ctx *c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
     if (L_out) {
-        int rc = ensure_export(c, (size_t)g->n * (size_t)g->n);
+        int rc = grow_buffer(c, &c->export_buf, &c->export_elems, (size_t)g->n * (size_t)g->n);
         if (rc != CBO_OK) return rc;
         launch_export_lower(c->stream, g->A, g->lda, g->n, c->export_buf);
         HIP_TRY(hipMemcpyAsync(L_out, c->export_buf, sizeof(double) * g->n * g->n, hipMemcpyDeviceToHost, c->stream));
@@ -938,7 +947,7 @@ extern "C" int cbo_gp_assemble_kxx(cbo_gp *g, double *K_out)
     HIP_TRY(hipSetDevice(c->device));
     // scratch: [n_pad x lda] assembly + [n x n] symmetric export, from the context's grow-only export buffer
     const size_t a_elems = (size_t)g->n_pad * (size_t)g->lda;
-    int rc = ensure_export(c, a_elems + (size_t)g->n * (size_t)g->n);
+    int rc = grow_buffer(c, &c->export_buf, &c->export_elems, a_elems + (size_t)g->n * (size_t)g->n);
     if (rc != CBO_OK) return rc;
     double *Atmp = c->export_buf, *tmp = c->export_buf + a_elems;
     launch_kxx(c->stream, g->X, g->h, g->noise_var + kGpyDiagJitter, 0.0, Atmp, g->lda, g->n_pad);
@@ -1194,14 +1203,8 @@ static int enqueue_posterior_f32(cbo_gp *g, cbo_cands *k)
     if (rc != CBO_OK) return rc;
     rc = ensure_alpha(g);                     // the mean is K*^T alpha in fp64 (GPy's formula), see kernels_f32.hip
     if (rc != CBO_OK) return rc;
-    const size_t part_elems = (size_t)(g->n32 / 64) * (size_t)chunk;
-    if (part_elems > c->mupart_elems) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->mupart);
-        c->mupart = nullptr; c->mupart_elems = 0;
-        HIP_TRY(hipMalloc(&c->mupart, sizeof(double) * part_elems));
-        c->mupart_elems = part_elems;
-    }
+    rc = grow_buffer(c, &c->mupart, &c->mupart_elems, (size_t)(g->n32 / 64) * (size_t)chunk);
+    if (rc != CBO_OK) return rc;
     if (g->f32_stamp != g->fit_stamp) {
         PhaseScope ps(c, PH_CONVERT);
         launch_factor_to_f32(c->stream, g->A, g->lda, g->n_pad, g->invDt, g->Uf, g->ldu32, g->invF, g->n32);
@@ -2060,7 +2063,7 @@ extern "C" int cbo_gp_predict(cbo_gp *g, int64_t m, const double *Xs, const doub
     return CBO_OK;
 }
 
-// ---- joint posterior covariance (kernels_cov.hip) ----------------------------------------------------------------
+// ---- joint posterior covariance (kernels_joint.hip) --------------------------------------------------------------
 // Both entry points solve V = L^-1 K* afresh on every call (a model changed by cbo_gp_append, set_data, set_hyper or a
 // refit can never meet an old solution) into the context's fp64 workspace, which must hold all m columns at once, then
 // run cov_tile_kernel into the context's grow-only output buffer and copy it to the caller in one piece.
@@ -2072,18 +2075,6 @@ static int resident_solution_ld(cbo_gp *g, int64_t m_pad, int64_t *ldv)
     int rc = ensure_workspaces(g->ctx, g->n_pad, m_pad, &chunk, ldv);
     if (rc != CBO_OK) return rc;
     if (chunk < m_pad) return fail(CBO_ERR_INVALID, "too many points: their solution L^-1 K* does not fit the workspace");
-    return CBO_OK;
-}
-
-static int ensure_cov(cbo_ctx *c, size_t elems)
-{
-    if (elems > c->cov_elems) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->cov);
-        c->cov = nullptr; c->cov_elems = 0;
-        HIP_TRY(hipMalloc(&c->cov, sizeof(double) * elems));
-        c->cov_elems = elems;
-    }
     return CBO_OK;
 }
 
@@ -2121,7 +2112,7 @@ extern "C" int cbo_gp_predict_cov(cbo_gp *g, int64_t m, const double *Xs, const 
     int64_t ldv = 0;
     int rc = resident_solution_ld(g, round_up(m, kStrip), &ldv);
     if (rc != CBO_OK) return rc;
-    rc = ensure_cov(c, (size_t)m * (size_t)m);
+    rc = grow_buffer(c, &c->cov, &c->cov_elems, (size_t)m * (size_t)m);
     if (rc != CBO_OK) return rc;
     // without mean_out the prior mean is not needed: the epilogue's mean (discarded) is formed from pv in its place
     cbo_cands *k = nullptr;
@@ -2151,7 +2142,7 @@ extern "C" int cbo_gp_cov_between(cbo_gp *g, int64_t m1, const double *X1, const
     int64_t ldv = 0;
     int rc = resident_solution_ld(g, round_up(mt, kStrip), &ldv);
     if (rc != CBO_OK) return rc;
-    rc = ensure_cov(c, (size_t)m1 * (size_t)m2);
+    rc = grow_buffer(c, &c->cov, &c->cov_elems, (size_t)m1 * (size_t)m2);
     if (rc != CBO_OK) return rc;
     std::vector<double> xs((size_t)mt * d), vs(causal ? (size_t)mt : 0);
     std::memcpy(xs.data(), X1, sizeof(double) * (size_t)m1 * d);
@@ -2175,47 +2166,11 @@ extern "C" int cbo_gp_cov_between(cbo_gp *g, int64_t m1, const double *X1, const
     return CBO_OK;
 }
 
-// ---- joint posterior samples (kernels_samples.hip) ---------------------------------------------------------------
+// ---- joint posterior samples (kernels_joint.hip) -----------------------------------------------------------------
 // V = L^-1 K* is solved as for cbo_gp_predict_cov; cov_tile_kernel then writes Sigma + jitter I straight into a
 // factorisation buffer in the model factor's own layout ([m_pad][m_pad + 80], identity padding, zero right-hand-side
 // strip), launch_cholesky factors it and samples_tile_kernel forms mean + L Z^T.  A jitter retry re-runs only the cov
 // launch from the resident V.  The model's factor, z, alpha and status word are never written.
-
-static int grow_buffer(cbo_ctx *c, double **p, size_t *cap, size_t elems)
-{
-    if (elems > *cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(*p);
-        *p = nullptr; *cap = 0;
-        HIP_TRY(hipMalloc(p, sizeof(double) * elems));
-        *cap = elems;
-    }
-    return CBO_OK;
-}
-
-// one attempt at the factor of Sigma + jitter I in c->samp_A (status words and fused-launch fallback as attempt_factor)
-static int attempt_sample_factor(cbo_gp *g, const cbo_cands *k, int64_t ldv, int64_t m, int64_t m_pad, int64_t lda,
-                                 double jitter, bool *pd)
-{
-    cbo_ctx *c = g->ctx;
-    FusedFallback fallback;
-    for (;;) {
-        launch_factor_padding(c->stream, c->samp_A, lda, m, m_pad);
-        enqueue_cov(g, k, ldv, 0, m, 0, m, true, jitter, c->samp_A, lda);
-        launch_cholesky(c->stream, c->side_stream, c->chol_events, c->samp_A, lda, m_pad, c->samp_invDt, c->samp_info);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->h_info, c->samp_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (*c->h_info == kCholFusedTimeout) {
-            if (fallback.active())
-                return fail(CBO_ERR_HIP, "a fused diagonal + panel launch gave up waiting, and so did the separate-launch repeat");
-            fallback.engage(c);
-            continue;
-        }
-        *pd = *c->h_info == 0;
-        return CBO_OK;
-    }
-}
 
 extern "C" int cbo_gp_posterior_samples(cbo_gp *g, int64_t m, const double *Xs, const double *pm, const double *pv,
                                         int64_t n_samples, const double *normals, double *samples_out, int *tries_out,
@@ -2252,14 +2207,18 @@ extern "C" int cbo_gp_posterior_samples(cbo_gp *g, int64_t m, const double *Xs, 
     if (rc != CBO_OK) return rc;
     double jitter = 0.0;
     int tries = 0;
+    // the factor of Sigma + jitter I in c->samp_A
+    auto enqueue = [&] {
+        launch_factor_padding(c->stream, c->samp_A, lda, m, m_pad);
+        enqueue_cov(g, k, ldv, 0, m, 0, m, true, jitter, c->samp_A, lda);
+        launch_cholesky(c->stream, c->side_stream, c->chol_events, c->samp_A, lda, m_pad, c->samp_invDt, c->samp_info);
+    };
     for (;;) {
         bool pd = false;
-        rc = attempt_sample_factor(g, k, ldv, m, m_pad, lda, jitter, &pd);
+        rc = attempt_factor(c, c->samp_info, enqueue, &pd);
         if (rc != CBO_OK) return rc;
         if (pd) break;
-        jitter = tries == 0 ? base : jitter * 10.0;
-        ++tries;
-        if (tries > 5 || !std::isfinite(jitter))
+        if (!jitter_step(base, &tries, &jitter))
             return fail(CBO_ERR_NOT_PD, "posterior covariance not positive definite, even with jitter.");
     }
     SampArgs a;
@@ -2672,7 +2631,7 @@ extern "C" int cbo_gp_predict_do(cbo_gp *g, int64_t m, int64_t n_obs, const doub
     if (rc != CBO_OK) return rc;
     // staging for observed | values | iv_index: the export scratch (device), filled by three small copies
     const size_t need = (size_t)(n_obs * g->d) + (size_t)(m * n_iv) + CBO_MAX_DIM;
-    rc = ensure_export(c, need);
+    rc = grow_buffer(c, &c->export_buf, &c->export_elems, need);
     if (rc != CBO_OK) return rc;
     double *d_obs = c->export_buf, *d_val = d_obs + n_obs * g->d;
     int *d_idx = reinterpret_cast<int *>(d_val + m * n_iv);

@@ -101,10 +101,11 @@ void launch_rhs(hipStream_t s, const double *y, const double *pm, int64_t n, dou
 void launch_kstar(hipStream_t s, const PointSet &X, const PointSet &C, int64_t c_begin, int64_t m_pad,
                   const KernelHyper &h, double *V, int64_t ldv, int64_t n_pad);
 
-// Joint posterior covariance (kernels_cov.hip): C[i][j] = K(X1_i, X2_j) - sum_{k < n_k} V[k][a_off + i] V[k][b_off + j]
-// for i < m1, j < m2 into C (row-major, ldc).  V is the resident solution L^-1 K* of a candidate set holding both point
-// sets (rows >= n are zero); xs / sq / sv the scaled SoA points (ld = ldx) of X1 and X2 (sv: sqrt of the prior variance,
-// null = non-causal).  sym: X1 = X2, upper tiles only, mirrored stores, zero-distance rule (zero_diag) and noise on the
+// ---- joint posterior (kernels_joint.hip) ----------------------------------------------------------------
+// Covariance: C[i][j] = K(X1_i, X2_j) - sum_{k < n_k} V[k][a_off + i] V[k][b_off + j] for i < m1, j < m2 into C
+// (row-major, ldc).  V is the resident solution L^-1 K* of a candidate set holding both point sets (rows >= n are
+// zero); xs / sq / sv the scaled SoA points (ld = ldx) of X1 and X2 (sv: sqrt of the prior variance, null =
+// non-causal).  sym: X1 = X2, upper tiles only, mirrored stores, zero-distance rule (zero_diag) and noise on the
 // diagonal.  Columns of V are read below v_cols only.
 struct CovArgs {
     const double *V; int64_t ldv;
@@ -117,9 +118,9 @@ struct CovArgs {
     int zero_diag, tiles;
 };
 void launch_cov_tiles(hipStream_t s, int d, bool sym, CovArgs a);
-// Joint posterior samples (kernels_samples.hip): F[i][j] = mean[i] + sum_{k <= i} U[k][i] Z[k][j] for i < m, j < s into
-// F (row-major, ldf).  U is the upper factor launch_cholesky leaves in [m_pad][ldu] (only k <= i is read as the factor),
-// Z the transposed normals [m_pad][ldz] (ldz >= round_up(s, 128), rows >= m zero).  tiles_* are set by the launcher.
+// Samples: F[i][j] = mean[i] + sum_{k <= i} U[k][i] Z[k][j] for i < m, j < s into F (row-major, ldf).  U is the upper
+// factor launch_cholesky leaves in [m_pad][ldu] (only k <= i is read as the factor), Z the transposed normals
+// [m_pad][ldz] (ldz >= round_up(s, 128), rows >= m zero).  tiles_* are set by the launcher.
 struct SampArgs {
     const double *U; int64_t ldu;
     const double *Z; int64_t ldz;

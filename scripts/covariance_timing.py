@@ -1,4 +1,4 @@
-"""Timing of the joint posterior (cbo_gp_predict_cov / cbo_gp_cov_between, cov_tile_kernel of kernels_cov.hip) on one
+"""Timing of the joint posterior (cbo_gp_predict_cov / cbo_gp_cov_between, cov_tile_kernel of kernels_joint.hip) on one
 MI355X, at (n, m) = (50, 200) (reference scale), (1024, 4096), (4096, 8192) and (4096, 16384).
 
 Two runs make one report:

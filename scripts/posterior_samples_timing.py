@@ -1,5 +1,5 @@
 """Timing of the joint posterior samples (cbo_gp_posterior_samples: solve, cov_tile_kernel, factorisation,
-samples_tile_kernel of kernels_samples.hip) on one MI355X, at (n, m, s) = (50, 200, 100) (reference scale),
+samples_tile_kernel of kernels_joint.hip) on one MI355X, at (n, m, s) = (50, 200, 100) (reference scale),
 (1024, 4096, 1024), (4096, 4096, 4096) and (4096, 8192, 1024).
 
 Two runs make one report:

@@ -1,4 +1,4 @@
-"""GPU tests of the joint posterior (cbo_gp_predict_cov / cbo_gp_cov_between, kernels_cov.hip) against the numpy
+"""GPU tests of the joint posterior (cbo_gp_predict_cov / cbo_gp_cov_between, kernels_joint.hip) against the numpy
 restatement of GPy's full_cov branch and posterior_covariance_between_points:
     K(X1, X2) - (L^-1 K(X, X1))^T (L^-1 K(X, X2))   (+ noise_var I for predict(full_cov=True)),
 with GPy's RBF K(X) (zero diagonal distance) for non-causal models and CausalRBF.K (X2 explicit, rank-1 term) for

@@ -1,4 +1,4 @@
-"""GPU tests of the joint posterior samples (cbo_gp_posterior_samples, kernels_samples.hip): with the identity as normals
+"""GPU tests of the joint posterior samples (cbo_gp_posterior_samples, kernels_joint.hip): with the identity as normals
 the samples minus the mean are the device's factor L of Sigma + jitter I, checked against the numpy restatement of
 GPy's full_cov branch (tests/test_covariance_gpu.py); with random normals they are mean + L Z^T."""
 import ctypes
