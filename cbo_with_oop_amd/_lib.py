@@ -95,6 +95,9 @@ SIGNATURES = {
                                           c_double_p, c_double_p, c_double_p]),
     "cbo_gp_posterior_samples": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p,
                                                 ctypes.c_int64, c_double_p, c_double_p, c_int_p, c_double_p]),
+    "cbo_gp_integrated_variance_reduction": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p,
+                                                            ctypes.c_int64, c_double_p, c_double_p, ctypes.c_double,
+                                                            c_double_p, c_double_p, c_int64_p]),
     "cbo_gp_set_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p, ctypes.c_double]),
     "cbo_gp_log_marginal": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "cbo_gp_lml_gradients": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),

@@ -127,6 +127,7 @@ struct cbo_ctx {
     int *samp_info = nullptr;
     double *samp_Z = nullptr; size_t samp_Z_elems = 0;
     double *samp_out = nullptr; size_t samp_out_elems = 0;
+    double *ivr_part = nullptr; size_t ivr_part_elems = 0;   // cbo_gp_integrated_variance_reduction: [m][tiles] partials
     // small uploads (cbo_gp_upload_data / cbo_gp_set_data of a few KB, every trial of the reference's loop): one
     // pinned staging buffer the preparation kernel reads directly; `stage_done` guards its reuse
     double *stage = nullptr; hipEvent_t stage_done = nullptr; bool stage_pending = false;
@@ -396,6 +397,7 @@ static void destroy_ctx(cbo_ctx *c)
     if (c->scratch_k) { cbo_cands_destroy(c->scratch_k); c->scratch_k = nullptr; }
     hipFree(c->grads); hipFree(c->export_buf); hipFree(c->cov);
     hipFree(c->samp_A); hipFree(c->samp_invDt); hipFree(c->samp_info); hipFree(c->samp_Z); hipFree(c->samp_out);
+    hipFree(c->ivr_part);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : c->pool) hipEventDestroy(e);
@@ -1231,6 +1233,28 @@ static int enqueue_posterior_f32(cbo_gp *g, cbo_cands *k)
     return CBO_OK;
 }
 
+// V[:, 0:cols) = L^-1 K(X, X*) for the candidates [c_begin, c_begin + cols) of k (cols a multiple of kStrip) on the fp64
+// factor, with q, mu of those columns: the K* kernel, then the substitution in the schedule prefer_right_looking picks
+static int solve_columns(cbo_gp *g, const cbo_cands *k, int64_t c_begin, int64_t cols, double *V, int64_t ldv, double *q,
+                         double *mu)
+{
+    cbo_ctx *c = g->ctx;
+    {
+        PhaseScope ps(c, PH_KSTAR);
+        launch_kstar(c->stream, g->X, k->P, c_begin, cols, g->h, V, ldv, g->n_pad);
+    }
+    if (prefer_right_looking(c, g->n_pad, cols)) return enqueue_right_looking(g, V, ldv, cols, q, mu);
+    {
+        PhaseScope ps(c, PH_TRSM);
+        launch_trsm_strips(c->stream, g->A, g->lda, g->invDt, V, ldv, g->n_pad, cols, g->z, q, mu);
+    }
+    if (c->profiling) {
+        c->timers.n_trsm_launches += 1;
+        c->timers.trsm_flops += (double)g->n_pad * (double)g->n_pad * (double)cols;
+    }
+    return CBO_OK;
+}
+
 // q = colsum((L^-1 K*)^2), mu = (L^-1 K*)^T z for all candidates, chunk by chunk.
 static int enqueue_posterior(cbo_gp *g, cbo_cands *k, bool want_f64_solution = false)
 {
@@ -1250,24 +1274,8 @@ static int enqueue_posterior(cbo_gp *g, cbo_cands *k, bool want_f64_solution = f
     }
     for (int64_t c0 = 0; c0 < k->m_pad; c0 += chunk) {
         const int64_t cols = (k->m_pad - c0 < chunk) ? (k->m_pad - c0) : chunk;
-        {
-            PhaseScope ps(c, PH_KSTAR);
-            launch_kstar(c->stream, g->X, k->P, c0, cols, g->h, Vws, ldv, g->n_pad);
-        }
-        if (prefer_right_looking(c, g->n_pad, cols)) {
-            rc = enqueue_right_looking(g, Vws, ldv, cols, c->q + c0, c->mu + c0);
-            if (rc != CBO_OK) return rc;
-            continue;
-        }
-        {
-            PhaseScope ps(c, PH_TRSM);
-            launch_trsm_strips(c->stream, g->A, g->lda, g->invDt, Vws, ldv, g->n_pad, cols, g->z, c->q + c0,
-                               c->mu + c0);
-        }
-        if (c->profiling) {
-            c->timers.n_trsm_launches += 1;
-            c->timers.trsm_flops += (double)g->n_pad * (double)g->n_pad * (double)cols;
-        }
+        rc = solve_columns(g, k, c0, cols, Vws, ldv, c->q + c0, c->mu + c0);
+        if (rc != CBO_OK) return rc;
     }
     HIP_TRY(hipGetLastError());
     if (Vws != c->V) { k->v_stamp = g->fit_stamp; k->v_rows = g->n; }
@@ -2235,6 +2243,96 @@ extern "C" int cbo_gp_posterior_samples(cbo_gp *g, int64_t m, const double *Xs, 
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (tries_out) *tries_out = tries;
     if (jitter_out) *jitter_out = jitter;
+    return CBO_OK;
+}
+
+// ---- integrated variance reduction (kernels_joint.hip ivr_tile_kernel, kernels_acq.hip ivr_finish_kernel) -------------
+// One scratch candidate set [Xs | filler | Xint], the integration points from column `off` (a tile boundary).  The
+// candidates are solved once into workspace columns [0, round_up(m, kStrip)) and their predictive variance is taken from
+// that solution (acq_kernel, include_noise = 1: cbo_gp_predict's bits).  The integration points follow in chunks of
+// whole tiles solved into the columns that remain from `off` on; each chunk's tile pass leaves one partial per
+// (candidate, global tile column), so the result does not depend on the chunking.  The model's factor, z, alpha and
+// status word are only read.
+
+extern "C" int cbo_gp_integrated_variance_reduction(cbo_gp *g, int64_t m, const double *Xs, const double *pv_s, int64_t p,
+                                                    const double *Xint, const double *pv_int, double cost, double *ivr_out,
+                                                    double *best_val, int64_t *best_idx)
+{
+    if (!g || !Xs || !Xint || (!ivr_out && !best_val && !best_idx)) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (m <= 0 || p <= 0) return fail(CBO_ERR_INVALID, "m and p must be positive");
+    if (!(cost > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    const bool causal = g->X.sv != nullptr;
+    if (causal && (!pv_s || !pv_int))
+        return fail(CBO_ERR_INVALID, "causal gp needs the prior variance at the candidates and the integration points");
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int d = g->d;
+    const int64_t mc = round_up(m, kStrip), off = round_up(m, kJointTile), mt = off + p;
+    int64_t chunk = 0, ldv = 0;
+    // (a failed allocation stays behind for hipGetLastError: it is cleared, or the next call's launch check reports it)
+    int rc = ensure_workspaces(c, g->n_pad, off + round_up(p, kJointTile), &chunk, &ldv);
+    if (rc != CBO_OK) { (void)hipGetLastError(); return rc; }
+    if (chunk < off + kJointTile)
+        return fail(CBO_ERR_INVALID, "too many candidates: their solution L^-1 K* and one tile of integration points do "
+                                     "not fit the workspace");
+    const int64_t pc = (chunk - off) / kJointTile * kJointTile;     // integration points per chunk
+    const int64_t tiles = (p + kJointTile - 1) / kJointTile;
+    rc = grow_buffer(c, &c->ivr_part, &c->ivr_part_elems, (size_t)m * (size_t)tiles);
+    if (rc != CBO_OK) { (void)hipGetLastError(); return rc; }
+    std::vector<double> xs((size_t)mt * d), vs(causal ? (size_t)mt : 0);
+    std::memcpy(xs.data(), Xs, sizeof(double) * (size_t)m * d);
+    for (int64_t i = m; i < off; ++i) std::memcpy(&xs[(size_t)i * d], Xs, sizeof(double) * d);   // filler: never read
+    std::memcpy(&xs[(size_t)off * d], Xint, sizeof(double) * (size_t)p * d);
+    if (causal) {
+        std::memcpy(vs.data(), pv_s, sizeof(double) * (size_t)m);
+        for (int64_t i = m; i < off; ++i) vs[(size_t)i] = pv_s[0];
+        std::memcpy(&vs[(size_t)off], pv_int, sizeof(double) * (size_t)p);
+    }
+    // (the prior variance stands in for the prior mean: the mean acq_kernel forms on the way is not used)
+    cbo_cands *k = nullptr;
+    rc = scratch_cands(c, mt, d, xs.data(), causal ? vs.data() : nullptr, causal ? vs.data() : nullptr, &k);
+    if (rc == CBO_OK) rc = prepare_cands(g, k);
+    if (rc == CBO_OK) rc = solve_columns(g, k, 0, mc, c->V, ldv, c->q, c->mu);
+    if (rc != CBO_OK) return rc;
+    AcqParams pr;
+    pr.variance = g->h.variance; pr.noise_var = g->noise_var; pr.y_best = 0.0; pr.ei_jitter = 0.0; pr.cost = 1.0;
+    pr.task = CBO_TASK_MIN; pr.include_noise = 1; pr.want_ei = 0;
+    {
+        PhaseScope ps(c, PH_ACQ);
+        launch_acq(c->stream, c->q, c->mu, causal ? k->pm : nullptr, causal ? k->pv : nullptr, m, pr, nullptr, c->var,
+                   nullptr, c->part_val, c->part_idx, 0, acq_blocks_for(m));
+    }
+    IvrArgs a;
+    a.Vc = c->V; a.Vi = c->V + off; a.ldv = ldv;
+    a.c_cols = mc;
+    a.n_k = (int)g->n;
+    a.xs1 = k->P.xs; a.sq1 = k->P.sq; a.sv1 = causal ? k->P.sv : nullptr;
+    a.ldx = k->P.ld;
+    a.m = m;
+    a.part = c->ivr_part; a.ldp = tiles;
+    a.variance = g->h.variance; a.inv_l2 = 1.0 / (g->h.lengthscale * g->h.lengthscale);
+    for (int64_t p0 = 0; p0 < p; p0 += pc) {
+        const int64_t pw = (p - p0 < pc) ? (p - p0) : pc;
+        const int64_t w = round_up(pw, kStrip);                      // solved columns (<= pc: pc is a multiple of 128)
+        // (q and mu of the integration points are not used: the candidates' part of both vectors is left alone)
+        rc = solve_columns(g, k, off + p0, w, c->V + off, ldv, c->q + off, c->mu + off);
+        if (rc != CBO_OK) return rc;
+        a.i_cols = w;
+        a.xs2 = k->P.xs + off + p0; a.sq2 = k->P.sq + off + p0; a.sv2 = causal ? k->P.sv + off + p0 : nullptr;
+        a.p = pw;
+        a.tile0 = p0 / kJointTile;
+        launch_ivr_tiles(c->stream, d, a);
+    }
+    const int nb = ivr_finish_blocks_for(m);
+    launch_ivr_finish(c->stream, c->ivr_part, tiles, (int)tiles, c->var, m, (double)p, cost, ivr_out ? c->acq : nullptr,
+                      c->part_val, c->part_idx, nb);
+    launch_argmax_final(c->stream, c->part_val, c->part_idx, nb, c->h_best_val, c->h_best_idx);
+    HIP_TRY(hipGetLastError());
+    if (ivr_out) HIP_TRY(hipMemcpyAsync(ivr_out, c->acq, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (best_val) *best_val = *c->h_best_val;
+    if (best_idx) *best_idx = *c->h_best_idx;
     return CBO_OK;
 }
 

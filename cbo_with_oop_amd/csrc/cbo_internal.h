@@ -135,6 +135,26 @@ void launch_normals_transpose(hipStream_t st, const double *normals, int64_t m, 
                               int64_t ldz);
 // padding of a factorisation buffer [m_pad][lda] holding an m x m matrix: identity rows >= m, zero columns >= m above
 void launch_factor_padding(hipStream_t st, double *A, int64_t lda, int64_t m, int64_t m_pad);
+// Integrated variance reduction, one chunk of integration points: for i < m and the chunk's tile columns T,
+// part[i * ldp + tile0 + T] = sum over j < p of tile T of C_ij^2, C = K(Xc_i, Xint_j) - sum_{k < n_k} Vc[k][i] Vi[k][j]
+// (cov_tile_kernel's cross element, squared).  Vc / Vi: the candidates' and the chunk's solutions L^-1 K* (leading
+// dimension ldv, rows >= n zero), read below c_cols / i_cols columns only; xs / sq / sv as for CovArgs (1: candidates,
+// 2: the chunk's points).  The chunk starts on global tile column tile0 (its first point is 128 tile0).
+constexpr int kJointTile = 128;                    // output tile side of kernels_joint.hip
+struct IvrArgs {
+    const double *Vc, *Vi; int64_t ldv, c_cols, i_cols;
+    int n_k;
+    const double *xs1, *sq1, *sv1, *xs2, *sq2, *sv2; int64_t ldx;
+    int64_t m, p;
+    double *part; int64_t ldp; int64_t tile0;
+    double variance, inv_l2;
+};
+void launch_ivr_tiles(hipStream_t s, int d, IvrArgs a);
+// the closing launch (kernels_acq.hip): ivr[i] = ((sum_t part[i * ldp + t] / var[i]) / p) / cost, t < tiles in order, for
+// i < m (ivr may be null); arg-max partials of ivr per workgroup (n_blocks <= 2048) for launch_argmax_final
+void launch_ivr_finish(hipStream_t s, const double *part, int64_t ldp, int tiles, const double *var, int64_t m, double p,
+                       double cost, double *ivr, double *part_val, int64_t *part_idx, int n_blocks);
+int ivr_finish_blocks_for(int64_t m);
 // ---- fp32 sweep (kernels_f32.hip; BASELINE.json configs[4]) -----------------------------------------------
 // The fit stays fp64; factor, diagonal inverses and z are down-converted once per fit into a layout whose 16-row
 // groups are row-permuted (physical row 4 (k & 3) + (k >> 2) = logical row k) and padded to n32 = round_up(n_pad, 256).

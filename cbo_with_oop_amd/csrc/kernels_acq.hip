@@ -172,6 +172,47 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const double *__restr
     block_argmax(bv, bi, best_val, best_idx);
 }
 
+// Integrated variance reduction, the closing launch behind ivr_tile_kernel (kernels_joint.hip): one wave per candidate.
+// Lane l sums the row's partials l, l + 64, ... in order, a butterfly sums the 64 lanes (every lane ends with the same
+// value), then ((sum / var) / p) / cost -- emukit's mean of cov^2 / var, over the quotient's cost.  var is acq_kernel's
+// predictive variance (noise included), cbo_gp_predict's bits.  Arg-max partials per workgroup as acq_kernel leaves them.
+__global__ __launch_bounds__(256) void ivr_finish_kernel(const double *__restrict__ part, int64_t ldp, int tiles,
+                                                         const double *__restrict__ var, int64_t m, double p, double cost,
+                                                         double *__restrict__ ivr, double *__restrict__ part_val,
+                                                         int64_t *__restrict__ part_idx)
+{
+    const int lane = threadIdx.x & 63;
+    double bv = -INFINITY;
+    int64_t bi = kNoIndex;
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += (int64_t)gridDim.x * 4) {
+        const double *row = part + i * ldp;
+        double s = 0.0;
+        for (int t = lane; t < tiles; t += 64) s = s + row[t];
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) s = s + __shfl_xor(s, off);
+        const double v = ((s / var[i]) / p) / cost;
+        if (lane == 0) {
+            if (ivr) ivr[i] = v;
+            if (better(v, i, bv, bi)) { bv = v; bi = i; }
+        }
+    }
+    block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
+}
+
+int ivr_finish_blocks_for(int64_t m)
+{
+    int64_t b = (m + 3) / 4;                          // one wave per candidate
+    if (b > 2048) b = 2048;
+    return (int)b;
+}
+
+void launch_ivr_finish(hipStream_t s, const double *part, int64_t ldp, int tiles, const double *var, int64_t m, double p,
+                       double cost, double *ivr, double *part_val, int64_t *part_idx, int n_blocks)
+{
+    hipLaunchKernelGGL(ivr_finish_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, part, ldp, tiles, var, m, p, cost, ivr,
+                       part_val, part_idx);
+}
+
 // Mean of consecutive runs (np.mean over the observed rows of one intervention, DoCalculus.py:59-60): one
 // wave per run, 16-byte-free strided reads (runs are short: N_obs ~ 100..1000), shuffle reduction.
 __global__ __launch_bounds__(256) void group_mean_kernel(const double *__restrict__ in, int64_t n_groups,

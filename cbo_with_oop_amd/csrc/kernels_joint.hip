@@ -1,11 +1,11 @@
-// The joint posterior on fp64 MFMA (v_mfma_f64_16x16x4_f64), gfx950: covariance and samples.
+// The joint posterior on fp64 MFMA (v_mfma_f64_16x16x4_f64), gfx950: covariance, samples and integrated variance reduction.
 //
 //     cov_tile_kernel:     C[i][j] = K(X1_i, X2_j) - sum_k V1[k][i] V2[k][j]
 //     samples_tile_kernel: F[i][j] = mu[i] + sum_{k <= i} U[k][i] Z[k][j]
 //
 // with V = L^-1 K(X, .) (the sweep's solution, resident), U^T U = Sigma + jitter I (U[k][i] = L[i][k]), Z = normals^T.
 //
-// Both run one main loop (tile_mainloop).  One 128 x 128 output tile per 256-thread workgroup, wave (wr, wc) owning
+// All three run one main loop (tile_mainloop).  One 128 x 128 output tile per 256-thread workgroup, wave (wr, wc) owning
 // the 64 x 64 quarter (wr, wc) as 4 x 4 MFMA blocks.  Both operands are k-major rows, which is exactly what the f64
 // MFMA reads: A fragment "A[i = lane&15][k = lane>>4]" = A[k][i], B fragment "B[k = lane>>4][j = lane&15]" = B[k][j].
 // Stages of 16 rows x 128 columns of each operand go to LDS by LDS-DMA (one 1 KiB row per instruction, double
@@ -28,9 +28,12 @@
 // mirrored lower half (cov SYM stores both halves, the factorisation leaves them), so the stages of the diagonal block
 // mask k > i explicitly.  Tiles are dispatched heaviest row first.
 //
+// ivr_tile_kernel (cbo_gp_integrated_variance_reduction): the cross covariance of candidates and integration points,
+// squared and reduced along each row of the tile in the epilogue; one partial per row and tile leaves the kernel.
+//
 // Roofline: fp64 MFMA bound at the sizes they are meant for: n_pad m^2 flop for SYM (the upper half of the product),
-// 2 n_pad m1 m2 for the cross covariance, m^2 s for the samples; per tile and k row 2 KiB of operands (mostly from L2)
-// against 64 MFMAs.
+// 2 n_pad m1 m2 for the cross covariance and for IVR, m^2 s for the samples; per tile and k row 2 KiB of operands
+// (mostly from L2) against 64 MFMAs.
 #include "cbo_device.h"
 
 #include <algorithm>
@@ -42,6 +45,7 @@ namespace cbo {
 #define TILE_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 constexpr int kTile = 128;                        // output tile side
+static_assert(kTile == kJointTile, "cbo_internal.h names the tile side for the host code");
 constexpr int kTileKB = 16;                       // k rows per LDS stage (4 MFMA k-steps)
 constexpr int kTileLd = kTile + 16;               // LDS row stride: rows kq and kq+1 land 32 banks apart (ds_read_b64)
 constexpr int kTileStage = 2 * kTileKB * kTileLd; // doubles per stage: the A rows, then the B rows
@@ -208,6 +212,87 @@ __global__ __launch_bounds__(256, 2) void cov_tile_kernel(CovArgs a)
     }
 }
 
+// ivr_tile_kernel: emukit IntegratedVarianceReduction, mean_j cov(x_i, x_j)^2 / var(x_i) over the integration points,
+// without the m x p covariance: the cross element of cov_tile_kernel (same main loop, same epilogue operations), squared
+// and summed over the tile's columns j < p.  Each row's 128 squares go in a fixed order: over bj in the lane, a
+// butterfly over the 16 lanes of a row (every lane ends with the same value: a + b == b + a), then the wc = 0 half plus
+// the wc = 1 half through LDS.  One partial per (candidate, global tile column); no atomics.
+template <int D>
+__global__ __launch_bounds__(256, 2) void ivr_tile_kernel(IvrArgs a)
+{
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    __shared__ __align__(16) double lds[2 * kTileStage];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 1, wc = wave & 1;
+    const int lc = lane & 15, kq = lane >> 4;
+    const int64_t i0 = (int64_t)ti * kTile, j0 = (int64_t)tj * kTile;
+
+    // columns past what was solved are clamped onto its last pair: they only feed rows >= m and columns >= p
+    int64_t ca = i0 + 2 * lane, cb = j0 + 2 * lane;
+    ca = ca < a.c_cols - 2 ? ca : a.c_cols - 2;
+    cb = cb < a.i_cols - 2 ? cb : a.i_cols - 2;
+    d4 acc[4][4];
+    tile_mainloop<false>(a.Vc + ca, a.ldv, a.Vi + cb, a.ldv, a.n_k / kTileKB, acc, lds);
+
+    // epilogue: the tile's points to LDS as in cov_tile_kernel, then (K - acc)^2 summed along the rows
+    double *px1 = lds, *px2 = lds + D * kTile;
+    double *q1 = lds + 2 * D * kTile, *q2 = q1 + kTile, *v1 = q2 + kTile, *v2 = v1 + kTile;
+    double *red = v2 + kTile;                            // [2][kTile]: the row sums of the two column halves
+    const bool causal = a.sv1 != nullptr;
+    if (tid < kTile) {
+        const int64_t gi = i0 + tid;
+        const bool in = gi < a.m;
+#pragma unroll
+        for (int k = 0; k < D; ++k) px1[k * kTile + tid] = in ? a.xs1[(int64_t)k * a.ldx + gi] : 0.0;
+        q1[tid] = in ? a.sq1[gi] : 0.0;
+        v1[tid] = (in && causal) ? a.sv1[gi] : 0.0;
+    } else {
+        const int t = tid - kTile;
+        const int64_t gj = j0 + t;
+        const bool in = gj < a.p;
+#pragma unroll
+        for (int k = 0; k < D; ++k) px2[k * kTile + t] = in ? a.xs2[(int64_t)k * a.ldx + gj] : 0.0;
+        q2[t] = in ? a.sq2[gj] : 0.0;
+        v2[t] = (in && causal) ? a.sv2[gj] : 0.0;
+    }
+    __syncthreads();
+
+    // row by row: the four elements of a row in this lane (bj order), the 16 lanes of the row, the half to LDS
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int li = wr * 64 + bi * 16 + kq + 4 * r;
+            double xi[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) xi[k] = px1[k * kTile + li];
+            double s = 0.0;
+#pragma unroll
+            for (int bj = 0; bj < 4; ++bj) {
+                const int lj = wc * 64 + bj * 16 + lc;
+                double xj[D];
+#pragma unroll
+                for (int k = 0; k < D; ++k) xj[k] = px2[k * kTile + lj];
+                double kv = kernel_value<D>(xi, xj, q1[li], q2[lj], a.variance, a.inv_l2, false);
+                if (causal) kv = __dadd_rn(kv, __dmul_rn(v1[li], v2[lj]));
+                const double c = __dsub_rn(kv, acc[bi][bj][r]);
+                // (a select, not a product: a column past p may hold anything, NaN included)
+                s = __dadd_rn(s, j0 + lj < a.p ? __dmul_rn(c, c) : 0.0);
+            }
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) s = __dadd_rn(s, __shfl_xor(s, off));
+            if (lc == 0) red[wc * kTile + li] = s;
+        }
+    __syncthreads();
+    if (tid < kTile) {
+        const int64_t gi = i0 + tid;
+        if (gi < a.m) a.part[gi * a.ldp + a.tile0 + tj] = __dadd_rn(red[tid], red[kTile + tid]);
+    }
+}
+
 __global__ __launch_bounds__(256, 2) void samples_tile_kernel(SampArgs a)
 {
     const int t = blockIdx.x;
@@ -303,6 +388,22 @@ void launch_cov_tiles(hipStream_t s, int d, bool sym, CovArgs a)
     } else {
         a.tiles = 0;
         launch_cov_d<false>(s, d, a, dim3((unsigned)t2, (unsigned)t1));
+    }
+}
+
+void launch_ivr_tiles(hipStream_t s, int d, IvrArgs a)
+{
+    const dim3 grid((unsigned)((a.p + kTile - 1) / kTile), (unsigned)((a.m + kTile - 1) / kTile));
+    a.n_k = (int)round_up(a.n_k, kTileKB);
+    switch (d) {
+        case 1: hipLaunchKernelGGL(ivr_tile_kernel<1>, grid, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL(ivr_tile_kernel<2>, grid, dim3(256), 0, s, a); break;
+        case 3: hipLaunchKernelGGL(ivr_tile_kernel<3>, grid, dim3(256), 0, s, a); break;
+        case 4: hipLaunchKernelGGL(ivr_tile_kernel<4>, grid, dim3(256), 0, s, a); break;
+        case 5: hipLaunchKernelGGL(ivr_tile_kernel<5>, grid, dim3(256), 0, s, a); break;
+        case 6: hipLaunchKernelGGL(ivr_tile_kernel<6>, grid, dim3(256), 0, s, a); break;
+        case 7: hipLaunchKernelGGL(ivr_tile_kernel<7>, grid, dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL(ivr_tile_kernel<8>, grid, dim3(256), 0, s, a); break;
     }
 }
 

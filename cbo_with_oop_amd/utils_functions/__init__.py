@@ -3,6 +3,7 @@
 from .causal_acquisition_functions import AcquisitionQuotient, CausalExpectedImprovement, CandidateGrid  # noqa: F401
 from .causal_optimizer import CausalGradientAcquisitionOptimizer  # noqa: F401
 from .cost_functions import Cost, total_cost  # noqa: F401
+from .integrated_variance import IntegratedVarianceReduction  # noqa: F401
 from .utils import (compute_coverage, find_current_global, find_next_y_point, find_next_y_points,  # noqa: F401
                     fit_gaussian_process, fit_gaussian_processes, update_hull)
 from .graph_functions import (AdditiveSEM, Term, compute_interventions, get_parameter_space, intervene_dict,  # noqa: F401

@@ -40,9 +40,8 @@ class CausalGradientAcquisitionOptimizer:
         self._grid, self._grid_model = None, None
 
     def sample_uniform(self, point_count):
-        """emukit ``ParameterSpace.sample_uniform`` on the GLOBAL numpy generator: one ``np.random.uniform(low, high,
-        (point_count, 1))`` per parameter, in the parameters' order, stacked as columns."""
-        return np.hstack([np.random.uniform(low=lo, high=hi, size=(point_count, 1)) for lo, hi in self.bounds])
+        """emukit ``ParameterSpace.sample_uniform`` on the GLOBAL numpy generator (``sample_uniform`` below)."""
+        return sample_uniform(self.bounds, point_count)
 
     def optimize_from_uniform_anchors(self, acquisition):
         """The reference's ``_optimize`` (:26-65) for a space without context or constraints."""
@@ -82,6 +81,9 @@ class CausalGradientAcquisitionOptimizer:
         ``CausalExpectedImprovement``.  ``refine=True`` adds the reference's gradient stage: from the best grid point
         with scipy's L-BFGS-B (``num_starts=1``, what the reference does with its best anchor), or from the
         ``num_starts`` best grid points at once (``refine_batched``)."""
+        if (refine or self.anchors == "uniform") and not has_gradients(acquisition):
+            raise ValueError(f"{type(_numerator(acquisition)).__name__} has no gradients: it cannot be refined with "
+                             "L-BFGS (use refine=False and anchors='grid')")
         if self.anchors == "uniform":
             return self.optimize_from_uniform_anchors(acquisition)
         # the grid of this optimiser stays on the device while the model object is the same (no allocation per call)
@@ -108,6 +110,23 @@ class CausalGradientAcquisitionOptimizer:
             if fs[best] >= fx[0, 0]:
                 x, fx = xs[best][None, :].copy(), np.array([[fs[best]]])
         return x, fx
+
+
+def sample_uniform(bounds, point_count):
+    """emukit ``ParameterSpace.sample_uniform`` on the GLOBAL numpy generator: one ``np.random.uniform(low, high,
+    (point_count, 1))`` per parameter, in the parameters' order, stacked as columns."""
+    return np.hstack([np.random.uniform(low=lo, high=hi, size=(point_count, 1)) for lo, hi in bounds])
+
+
+def _numerator(acquisition):
+    num = getattr(acquisition, "numerator", None)
+    return acquisition if num is None else num
+
+
+def has_gradients(acquisition):
+    """Whether ``acquisition`` can be refined by gradient: for a quotient, whether its numerator can (the quotient reports
+    gradients whatever it divides, as emukit's does).  An object that does not say is taken to have them."""
+    return bool(getattr(_numerator(acquisition), "has_gradients", True))
 
 
 def _values_and_gradients(acquisition, X):

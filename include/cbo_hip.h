@@ -187,6 +187,29 @@ int cbo_gp_posterior_samples(cbo_gp *gp, int64_t m, const double *Xs, const doub
                              const double *prior_var_s, int64_t n_samples, const double *normals, double *samples_out,
                              int *jitter_tries_out, double *jitter_out);
 
+/* Integrated variance reduction (emukit IntegratedVarianceReduction.evaluate, which averages
+ * GPyModelWrapper.calculate_variance_reduction(x_i, Xint) = cov(x_i, Xint)^2 / predict(x_i)[1] over the integration
+ * points), for m candidates at once and divided by a cost, as emukit's Quotient with a Cost has it:
+ *     ivr_out[i] = ((sum_j C(x_i, xint_j)^2 / var_i) / p) / cost,
+ * C = cbo_gp_cov_between(Xs, Xint) element for element (same prior term, same rounding), var_i = cbo_gp_predict's
+ * variance with the noise (include_noise = 1), bit for bit.  No m x p matrix is stored: the squares are summed in the
+ * product's epilogue, one partial per candidate and 128-column tile, and the partials in a fixed order, so two calls give
+ * the same bits.  best_val / best_idx: the arg-max of ivr_out (lowest index on ties, NaN maximal).  ivr_out (m),
+ * best_val and best_idx may each be NULL, but not all three.
+ *
+ * The solution of the m candidates must fit the context's workspace (CBO_HIP_WORKSPACE_MB) together with one
+ * 128-column tile of integration points; the integration points need not fit: they are solved in chunks of whole tiles
+ * in the workspace that remains, and the result is the same bits for any number of chunks.  The candidates are solved
+ * once per call.
+ *
+ * Unfitted model: CBO_ERR_NOT_FITTED; NULL arguments, m <= 0, p <= 0, cost <= 0 (or NaN), a causal model without
+ * prior_var_s or prior_var_int, or candidates whose solution does not fit: CBO_ERR_INVALID; a failed device allocation:
+ * CBO_ERR_HIP.  fp32 models answer from the fp64 factor (the fp64 model's result).  The model is left untouched
+ * (factor, z, alpha, fitted state, candidate sets). */
+int cbo_gp_integrated_variance_reduction(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_var_s,
+                                         int64_t p, const double *Xint, const double *prior_var_int, double cost,
+                                         double *ivr_out, double *best_val, int64_t *best_idx);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
