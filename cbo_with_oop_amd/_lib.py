@@ -98,6 +98,10 @@ SIGNATURES = {
     "cbo_gp_integrated_variance_reduction": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p,
                                                             ctypes.c_int64, c_double_p, c_double_p, ctypes.c_double,
                                                             c_double_p, c_double_p, c_int64_p]),
+    "cbo_gp_mes_gumbel": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                         c_double_p, c_double_p, c_double_p, c_double_p]),
+    "cbo_acq_sweep_mes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_double,
+                                         c_double_p, c_double_p, c_double_p, c_double_p, c_int64_p]),
     "cbo_gp_set_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p, ctypes.c_double]),
     "cbo_gp_log_marginal": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "cbo_gp_lml_gradients": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),

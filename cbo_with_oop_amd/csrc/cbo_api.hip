@@ -1307,9 +1307,10 @@ static int copy_posterior_out(cbo_ctx *c, const cbo_cands *k, double *acq_out, d
     return CBO_OK;
 }
 
+// mes: max-value entropy search's epilogue (mes_acq_kernel) in the place of EI's; y_best, task and ei_jitter are then unused
 static int enqueue_finish(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost, double *acq_out,
                           double *mean_out, double *var_out, const double *q_src, const double *mu_src,
-                          bool with_status = false, bool copy_out = true)
+                          bool with_status = false, bool copy_out = true, const MesParams *mes = nullptr)
 {
     cbo_ctx *c = g->ctx;
     const bool causal = g->X.sv != nullptr;
@@ -1319,9 +1320,14 @@ static int enqueue_finish(cbo_gp *g, cbo_cands *k, double y_best, int task, doub
     const int nb = acq_blocks_for(k->m);
     {
         PhaseScope ps(c, PH_ACQ);
-        launch_acq(c->stream, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, p,
-                   mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr, c->part_val,
-                   c->part_idx, k->index_offset, nb);
+        if (mes)
+            launch_mes_acq(c->stream, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, *mes,
+                           mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr,
+                           c->part_val, c->part_idx, k->index_offset, nb);
+        else
+            launch_acq(c->stream, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, p,
+                       mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr, c->part_val,
+                       c->part_idx, k->index_offset, nb);
         // the winner (and, behind a factorisation, its status word) goes straight to pinned host memory
         launch_argmax_final(c->stream, c->part_val, c->part_idx, nb, c->h_best_val, c->h_best_idx,
                             with_status ? g->info : nullptr, with_status ? c->h_info : nullptr);
@@ -1339,7 +1345,8 @@ static void complete_finish(cbo_ctx *c, double *best_val, int64_t *best_idx)
 }
 
 static int finish_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
-                        double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx)
+                        double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx,
+                        const MesParams *mes = nullptr)
 {
     cbo_ctx *c = g->ctx;
     // keep q, mu with the candidates (two small device copies): the next sweep of an unchanged model skips the
@@ -1355,7 +1362,8 @@ static int finish_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, double
         k->fit_stamp = g->fit_stamp;
     }
     const double *q_src = cached ? k->q : c->q, *mu_src = cached ? k->mu : c->mu;
-    int rc = enqueue_finish(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, q_src, mu_src);
+    int rc = enqueue_finish(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, q_src, mu_src, false, true,
+                            mes);
     if (rc != CBO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     complete_finish(c, best_val, best_idx);
@@ -1483,12 +1491,12 @@ extern "C" int cbo_gp_append(cbo_gp *g, const double *x_new, double y_new, doubl
     return CBO_OK;
 }
 
-extern "C" int cbo_acq_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
-                             double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx)
+// q, mu of the candidates for the fitted model (the cached copies, one appended row, or the substitution), then the
+// epilogue: EI / cost, or max-value entropy search / cost when mes is given
+static int sweep_impl(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost, double *acq_out,
+                      double *mean_out, double *var_out, double *best_val, int64_t *best_idx, const MesParams *mes)
 {
-    int rc = check_sweep_args(g, k, task);
-    if (rc != CBO_OK) return rc;
-    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    int rc = CBO_OK;
     cbo_ctx *c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
     if (k->keep_v && k->V && k->v_stamp != 0 && k->v_stamp == g->parent_stamp && k->v_rows == g->n - 1 &&
@@ -1506,7 +1514,37 @@ extern "C" int cbo_acq_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, d
         rc = ensure_workspaces(c, g->n_pad, k->m_pad, &chunk, &ldv);
         if (rc != CBO_OK) return rc;
     }
-    return finish_sweep(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx);
+    return finish_sweep(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, mes);
+}
+
+extern "C" int cbo_acq_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
+                             double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx)
+{
+    int rc = check_sweep_args(g, k, task);
+    if (rc != CBO_OK) return rc;
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    return sweep_impl(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, nullptr);
+}
+
+// ---- max-value entropy search (kernels_mes.hip) ------------------------------------------------------------------------
+// emukit MaxValueEntropySearch.evaluate over a candidate set: the EI sweep's path up to q, mu (cached re-sweep, appended
+// row, fp32 strip), then mes_acq_kernel in the place of acq_kernel
+extern "C" int cbo_acq_sweep_mes(cbo_gp *g, cbo_cands *k, int n_samples, const double *mins, double cost, double *acq_out,
+                                 double *mean_out, double *var_out, double *best_val, int64_t *best_idx)
+{
+    int rc = check_sweep_args(g, k, CBO_TASK_MIN);
+    if (rc != CBO_OK) return rc;
+    if (n_samples <= 0 || n_samples > kMesMaxSamples)
+        return fail(CBO_ERR_INVALID, "the number of Gumbel samples must be in 1.." + std::to_string(kMesMaxSamples));
+    if (!mins) return fail(CBO_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n_samples; ++i)
+        if (!std::isfinite(mins[i])) return fail(CBO_ERR_INVALID, "the Gumbel samples must be finite");
+    if (!(cost > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    MesParams p{};
+    p.variance = g->h.variance; p.noise_var = g->noise_var; p.cost = cost; p.k = n_samples;
+    for (int i = 0; i < n_samples; ++i) p.mins[i] = mins[i];
+    return sweep_impl(g, k, 0.0, CBO_TASK_MIN, 0.0, cost, acq_out, mean_out, var_out, best_val, best_idx, &p);
 }
 
 // Refit and sweep in one call, the two overlapped: what CBO.intervene() does for the set it has just
@@ -2067,6 +2105,52 @@ extern "C" int cbo_gp_predict(cbo_gp *g, int64_t m, const double *Xs, const doub
     HIP_TRY(hipMemcpyAsync(mean_out, c->mean, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(var_out, c->var, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->profiling) c->timers.n_sweep += 1;
+    return CBO_OK;
+}
+
+// emukit MaxValueEntropySearch.update_parameters' model.predict(grid) and _fit_gumbel: the grid's predictive mean and
+// variance (noise included) as cbo_gp_predict leaves them on the device, then the three bisections in one launch on them;
+// only the quantiles (and, when asked, the mean and variance) come back
+extern "C" int cbo_gp_mes_gumbel(cbo_gp *g, int64_t m, const double *Xg, const double *pm, const double *pv,
+                                 double *quantiles3, double *a_out, double *b_out, double *mean_out, double *var_out)
+{
+    if (!g || !Xg || !quantiles3 || !a_out || !b_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (m <= 0) return fail(CBO_ERR_INVALID, "m must be positive");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    cbo_cands *k = nullptr;
+    int rc = posterior_of_host_points(g, m, Xg, pm, pv, 1, &k);
+    if (rc != CBO_OK) return rc;
+    // part_val / part_idx: free device scratch between sweeps (2048 entries each)
+    launch_gumbel_quantiles(c->stream, c->mean, c->var, m, c->part_val, c->part_idx);
+    HIP_TRY(hipGetLastError());
+    double out[5];
+    int64_t status[3];
+    HIP_TRY(hipMemcpyAsync(out, c->part_val, sizeof(out), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status, c->part_idx, sizeof(status), hipMemcpyDeviceToHost, c->stream));
+    if (mean_out) HIP_TRY(hipMemcpyAsync(mean_out, c->mean, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIP_TRY(hipMemcpyAsync(var_out, c->var, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int j = 0; j < 3; ++j) {
+        char msg[160];
+        if (status[j] == 1) {
+            std::snprintf(msg, sizeof msg, "Gumbel fit: f(a) and f(b) must have different signs (quantile %.2f on "
+                          "[%.17g, %.17g])", 0.25 * (j + 1), out[3], out[4]);
+            return fail(CBO_ERR_INVALID, msg);
+        }
+        if (status[j] != 0) {
+            std::snprintf(msg, sizeof msg, "Gumbel fit: bisection of quantile %.2f failed to converge after 10000 "
+                          "iterations", 0.25 * (j + 1));
+            return fail(CBO_ERR_INVALID, msg);
+        }
+    }
+    for (int j = 0; j < 3; ++j) quantiles3[j] = out[j];
+    // _fit_gumbel: b = (q25 - q75) / (log(log(4/3)) - log(log(4))), a = q50 - b log(log(2))
+    const double b = (out[0] - out[2]) / (std::log(std::log(4.0 / 3.0)) - std::log(std::log(4.0)));
+    *b_out = b;
+    *a_out = out[1] - b * std::log(std::log(2.0));
     if (c->profiling) c->timers.n_sweep += 1;
     return CBO_OK;
 }

@@ -136,6 +136,43 @@ __device__ __forceinline__ double cephes_erf_small(double x)       // |x| <= 1
     q = horner(q, z, 4.92673942608635921086E4);
     return x * p * recip_plain(q);
 }
+// cephes erfc's rational functions without their exp(-x^2) factor, p / q ~ exp(x^2) erfc(x) = erfcx(x): P / Q on [1, 8),
+// R / S from 8 on (numerator and denominator apart: the callers divide as they need)
+__device__ __forceinline__ void cephes_erfc_pq(double z, double &p, double &q)
+{
+    p = 2.46196981473530512524E-10;
+    p = horner(p, z, 5.64189564831068821977E-1);
+    p = horner(p, z, 7.46321056442269912687E0);
+    p = horner(p, z, 4.86371970985681366614E1);
+    p = horner(p, z, 1.96520832956077098242E2);
+    p = horner(p, z, 5.26445194995477358631E2);
+    p = horner(p, z, 9.34528527171957607540E2);
+    p = horner(p, z, 1.02755188689515710272E3);
+    p = horner(p, z, 5.57535335369399327526E2);
+    q = z + 1.32281951154744992508E1;
+    q = horner(q, z, 8.67072140885989742329E1);
+    q = horner(q, z, 3.54937778887819891062E2);
+    q = horner(q, z, 9.75708501743205489753E2);
+    q = horner(q, z, 1.82390916687909736289E3);
+    q = horner(q, z, 2.24633760818710981792E3);
+    q = horner(q, z, 1.65666309194161350182E3);
+    q = horner(q, z, 5.57535340817727675546E2);
+}
+__device__ __forceinline__ void cephes_erfc_rs(double z, double &p, double &q)
+{
+    p = 5.64189583547755073984E-1;
+    p = horner(p, z, 1.27536670759978104416E0);
+    p = horner(p, z, 5.01905042251180477414E0);
+    p = horner(p, z, 6.16021097993053585195E0);
+    p = horner(p, z, 7.40974269950448939160E0);
+    p = horner(p, z, 2.97886665372100240670E0);
+    q = z + 2.26052863220117276590E0;
+    q = horner(q, z, 9.39603524938001434673E0);
+    q = horner(q, z, 1.20489539808096656605E1);
+    q = horner(q, z, 1.70814450747565897222E1);
+    q = horner(q, z, 9.60896809063285878198E0);
+    q = horner(q, z, 3.36907645100081516050E0);
+}
 // e = exp(-a^2 / 2), computed by the caller (who needs it for the density)
 __device__ __forceinline__ double ndtr_with_exp(double a, double e)
 {
@@ -151,42 +188,52 @@ __device__ __forceinline__ double ndtr_with_exp(double a, double e)
         c = 1.0 - fabs(erf_x);
     } else if (z * z > MAXLOG) {
         c = 0.0;                                       // cephes: underflow
-    } else if (z < 8.0) {
-        double p = 2.46196981473530512524E-10;
-        p = horner(p, z, 5.64189564831068821977E-1);
-        p = horner(p, z, 7.46321056442269912687E0);
-        p = horner(p, z, 4.86371970985681366614E1);
-        p = horner(p, z, 1.96520832956077098242E2);
-        p = horner(p, z, 5.26445194995477358631E2);
-        p = horner(p, z, 9.34528527171957607540E2);
-        p = horner(p, z, 1.02755188689515710272E3);
-        p = horner(p, z, 5.57535335369399327526E2);
-        double q = z + 1.32281951154744992508E1;
-        q = horner(q, z, 8.67072140885989742329E1);
-        q = horner(q, z, 3.54937778887819891062E2);
-        q = horner(q, z, 9.75708501743205489753E2);
-        q = horner(q, z, 1.82390916687909736289E3);
-        q = horner(q, z, 2.24633760818710981792E3);
-        q = horner(q, z, 1.65666309194161350182E3);
-        q = horner(q, z, 5.57535340817727675546E2);
-        c = (e * p) * recip_plain(q);
     } else {
-        double p = 5.64189583547755073984E-1;
-        p = horner(p, z, 1.27536670759978104416E0);
-        p = horner(p, z, 5.01905042251180477414E0);
-        p = horner(p, z, 6.16021097993053585195E0);
-        p = horner(p, z, 7.40974269950448939160E0);
-        p = horner(p, z, 2.97886665372100240670E0);
-        double q = z + 2.26052863220117276590E0;
-        q = horner(q, z, 9.39603524938001434673E0);
-        q = horner(q, z, 1.20489539808096656605E1);
-        q = horner(q, z, 1.70814450747565897222E1);
-        q = horner(q, z, 9.60896809063285878198E0);
-        q = horner(q, z, 3.36907645100081516050E0);
+        double p, q;
+        if (z < 8.0) cephes_erfc_pq(z, p, q);
+        else cephes_erfc_rs(z, p, q);
         c = (e * p) * recip_plain(q);
     }
     const double y = 0.5 * c;
     return select_f64(x > 0, 1.0 - y, y);
+}
+
+// scipy.special.log_ndtr(a) (scipy 1.15, real argument): t = a / sqrt 2 (as a * SQRT1_2), then
+//     a < -1:  log(erfcx(-t) / 2) - t^2          else:  log1p(-erfc(t) / 2)
+// with cephes' erf / erfc as in ndtr_with_exp.  scipy's erfcx is the Faddeeva package's; here erfcx(y) for y > 1 / sqrt 2 is
+// cephes erfc's rational function without its exponential (P / Q below 8, R / S beyond: the same relative accuracy as
+// erfc itself) and exp(y^2) (1 - erf(y)) below 1.  Only the Gumbel fit of max-value entropy search calls it (a few
+// hundred thousand evaluations per fit): IEEE divisions and the device library's exp / log / log1p throughout.
+__device__ __forceinline__ double log_ndtr(double a)
+{
+#pragma clang fp contract(off)
+    const double SQRTH = 7.07106781186547524401E-1, MAXLOG = 7.09782712893383996843E2;
+    const double t = a * SQRTH;
+    double p, q;
+    if (a < -1.0) {
+        const double y = -t;                           // > 1 / sqrt 2
+        double erfcx;
+        if (y < 1.0) {
+            erfcx = exp(y * y) * (1.0 - cephes_erf_small(y));
+        } else {
+            if (y < 8.0) cephes_erfc_pq(y, p, q);
+            else cephes_erfc_rs(y, p, q);
+            erfcx = p / q;
+        }
+        return log(erfcx / 2.0) - t * t;
+    }
+    const double z = fabs(t);
+    double c;
+    if (z < 1.0) {
+        c = 1.0 - cephes_erf_small(t);
+    } else if (z * z > MAXLOG) {
+        c = 0.0;                                       // (t >= 1 here: erfc underflows)
+    } else {
+        if (z < 8.0) cephes_erfc_pq(z, p, q);
+        else cephes_erfc_rs(z, p, q);
+        c = (exp(-(z * z)) * p) / q;
+    }
+    return log1p(-(c / 2.0));
 }
 
 // (va, ia) beats (vb, ib): larger value, NaN maximal (numpy.argmax), lowest index on ties
@@ -207,6 +254,27 @@ __device__ __forceinline__ void wave_argmax(double &v, int64_t &i)
         if (better(ov, oi, v, i)) { v = ov; i = oi; }
     }
 }
+
+// arg-max of a 256-thread workgroup into *out_v / *out_i (written by thread 0)
+__device__ __forceinline__ void block_argmax(double v, int64_t i, double *out_v, int64_t *out_i)
+{
+    __shared__ double sv[4];
+    __shared__ int64_t si[4];
+    wave_argmax(v, i);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sv[wave] = v; si[wave] = i; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double bv = sv[0];
+        int64_t bi = si[0];
+        for (int w = 1; w < 4; ++w)
+            if (better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
+        *out_v = bv;
+        *out_i = bi;
+    }
+}
+
+constexpr int64_t kNoIndex = INT64_MAX;
 
 // Posterior epilogue of one candidate (GPy Posterior._raw_predict / GP.predict + CausalRBF.Kdiag,
 // causal_kernels.py:64-79): var = clip(Kdiag - q, 1e-15) (+ noise), mean = mu + m(x*).

@@ -313,6 +313,23 @@ void launch_acq(hipStream_t s, const double *q, const double *mu, const double *
 void launch_argmax_final(hipStream_t s, const double *part_val, const int64_t *part_idx, int n, double *best_val,
                          int64_t *best_idx, const int *status_src = nullptr, int *status_dst = nullptr);
 int acq_blocks_for(int64_t m);
+// ---- max-value entropy search (kernels_mes.hip) -----------------------------------------------------------------
+// The Gumbel samples travel in the kernel arguments: at most kMesMaxSamples of them.
+constexpr int kMesMaxSamples = 64;
+struct MesParams {
+    double variance, noise_var, cost;
+    int k;
+    double mins[kMesMaxSamples];
+};
+// acq_kernel's mean and variance (noise included), then mes = mean over the k samples of emukit's per-sample term, / cost;
+// launch grid and arg-max partials as launch_acq (acq_blocks_for)
+void launch_mes_acq(hipStream_t s, const double *q, const double *mu, const double *pm, const double *pv, int64_t m,
+                    const MesParams &p, double *mean_out, double *var_out, double *acq_out, double *part_val,
+                    int64_t *part_idx, int64_t index_offset, int n_blocks);
+// The three bisections of emukit's _fit_gumbel (vals 0.25, 0.5, 0.75) on the predictive mean / variance of m grid points,
+// one workgroup each: out[0..3) the quantiles, out[3] = left, out[4] = right; status[j] = 0 converged, 1 the bracket does
+// not change sign (scipy's ValueError), 2 no convergence within maxiter (scipy's RuntimeError).
+void launch_gumbel_quantiles(hipStream_t s, const double *mean, const double *var, int64_t m, double *out, int64_t *status);
 // out[g] = mean of in[g*group .. (g+1)*group)
 void launch_group_mean(hipStream_t s, const double *in, int64_t n_groups, int64_t group, double *out);
 

@@ -16,26 +16,6 @@
 
 namespace cbo {
 
-__device__ __forceinline__ void block_argmax(double v, int64_t i, double *out_v, int64_t *out_i)
-{
-    __shared__ double sv[4];
-    __shared__ int64_t si[4];
-    wave_argmax(v, i);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sv[wave] = v; si[wave] = i; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double bv = sv[0];
-        int64_t bi = si[0];
-        for (int w = 1; w < 4; ++w)
-            if (better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
-        *out_v = bv;
-        *out_i = bi;
-    }
-}
-
-constexpr int64_t kNoIndex = INT64_MAX;
-
 // Two consecutive candidates per lane and iteration (16-byte loads and stores), the next iteration's operands requested
 // before this one's arithmetic: with one candidate per lane and the load at the top of the loop body the pass was bound by
 // memory LATENCY -- 32 KB in flight per CU -- and ran at 0.29 of the HBM roofline whatever the arithmetic cost (round 5: halving

@@ -1,0 +1,258 @@
+// emukit's max-value entropy search (MES, Wang & Jegelka 2017) for gfx950: the scoring pass of a sweep and the Gumbel fit.
+//
+// Restates emukit 0.4's emukit.bayesian_optimization.acquisitions.MaxValueEntropySearch from memory (emukit is not a
+// dependency; parity is unpinned, the contract is DESIGN.md §4e):
+//   evaluate(x):          fsd = max(sqrt(var), 1e-10), gamma = (mins - mean) / fsd (M x K),
+//                         minus_cdf = clip(1 - ndtr(gamma), 1e-10, 1),
+//                         mean_k(-gamma pdf(gamma) / (2 minus_cdf) - log(minus_cdf))
+//   update_parameters():  _fit_gumbel's three scipy.optimize.bisect calls on
+//                         probf(x) = 1 - exp(sum_i log_ndtr(-(x - fmean_i) / fsd_i))
+// mean and variance come from q = sum V^2, mu = V^T z exactly as acq_kernel forms them (kernels_acq.hip).
+#include "cbo_device.h"
+
+#pragma clang fp contract(off)
+
+namespace cbo {
+
+// One sample's term of emukit's evaluate: -gamma pdf(gamma) / (2 minus_cdf) - log(minus_cdf).  The density and cephes ndtr
+// share one exponential (ndtr_with_exp); 1 - ndtr(gamma) is formed as written, not as ndtr(-gamma).
+__device__ __forceinline__ double mes_term(double min_k, double mean, double fsd)
+{
+    const double g = (min_k - mean) / fsd;                           // IEEE division, as numpy
+    const double e = exp_nonpositive(-(g * g) / 2.0);
+    const double pdf = e * 0.3989422804014327;                      // scipy _norm_pdf: exp(-x**2/2)/sqrt(2 pi), to an ulp
+    double mc = 1.0 - ndtr_with_exp(g, e);
+    mc = select_f64(mc < 1e-10, 1e-10, mc);                         // np.clip(minus_cdf, 1e-10, 1) (NaN stays NaN; mc <= 1)
+    return ((-g) * pdf) / (2.0 * mc) - log(mc);
+}
+
+// mean over the k samples in numpy's order for a row of an (M, K) array reduced along its last axis (np.mean(axis=1):
+// pairwise_sum): below 8 terms one running sum from 0; from 8 on, eight accumulators over the leading multiple of 8, combined
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the rest one by one; then / K
+__device__ __forceinline__ double mes_of(double mean, double var, const MesParams &p)
+{
+    double fsd = sqrt(var);                                          // IEEE square root (np.sqrt)
+    fsd = select_f64(fsd < 1e-10, 1e-10, fsd);                      // np.maximum(fsd, 1e-10); NaN stays NaN
+    const int full = p.k - p.k % 8;
+    double r[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int k = 0;
+    for (; k < full; k += 8) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + mes_term(p.mins[k + j], mean, fsd);
+    }
+    double s = (p.k < 8) ? 0.0 : ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; k < p.k; ++k) s = s + mes_term(p.mins[k], mean, fsd);
+    return (s / (double)p.k) / p.cost;
+}
+
+// acq_kernel's structure (kernels_acq.hip): two consecutive candidates per lane and iteration, the next iteration's operands
+// and the previous one's results issued together right behind the iteration's only wait.  Unlike the EI pass this one is
+// bound by fp64 arithmetic (about a hundred vector instructions per sample), not by HBM; the two candidates of a lane are
+// scored one after the other (one copy of the sample loop).
+template <bool CAUSAL, bool MV>
+__global__ __launch_bounds__(256) void mes_acq_kernel(const double *__restrict__ q, const double *__restrict__ mu,
+                                                      const double *__restrict__ pm, const double *__restrict__ pv,
+                                                      int64_t m, MesParams p, double *__restrict__ mean_out,
+                                                      double *__restrict__ var_out, double *__restrict__ acq_out,
+                                                      double *__restrict__ part_val, int64_t *__restrict__ part_idx,
+                                                      int64_t index_offset)
+{
+    double bv = -INFINITY;
+    int64_t bi = kNoIndex;
+    constexpr bool causal = CAUSAL;
+    if (!MV) { mean_out = nullptr; var_out = nullptr; }
+    AcqParams ap;                                                    // the posterior epilogue's fields of the EI pass
+    ap.variance = p.variance; ap.noise_var = p.noise_var; ap.y_best = 0.0; ap.ei_jitter = 0.0; ap.cost = 1.0;
+    ap.task = CBO_TASK_MIN; ap.include_noise = 1; ap.want_ei = 0;
+    const int64_t stride = 2 * (int64_t)gridDim.x * blockDim.x;
+    int64_t cu = 2 * (int64_t)blockIdx.x * blockDim.x;
+    const unsigned lane2 = 2 * threadIdx.x;
+    const int64_t span = 2 * (int64_t)blockDim.x;
+    auto fetch = [&](int64_t base, d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2) __attribute__((always_inline)) {
+        if (base + span <= m) {                                      // (uniform) every lane has its two candidates
+            q2 = *reinterpret_cast<const d2 *>(q + base + lane2);
+            mu2 = *reinterpret_cast<const d2 *>(mu + base + lane2);
+            if (causal) {
+                pm2 = *reinterpret_cast<const d2 *>(pm + base + lane2);
+                pv2 = *reinterpret_cast<const d2 *>(pv + base + lane2);
+            }
+            return;
+        }
+        const int64_t at = base + lane2;
+        if (at + 1 < m) {
+            q2 = *reinterpret_cast<const d2 *>(q + at);
+            mu2 = *reinterpret_cast<const d2 *>(mu + at);
+            if (causal) {
+                pm2 = *reinterpret_cast<const d2 *>(pm + at);
+                pv2 = *reinterpret_cast<const d2 *>(pv + at);
+            }
+        } else if (at < m) {
+            q2 = d2{q[at], q[at]};
+            mu2 = d2{mu[at], mu[at]};
+            if (causal) {
+                pm2 = d2{pm[at], pm[at]};
+                pv2 = d2{pv[at], pv[at]};
+            }
+        }
+    };
+    auto store = [&](int64_t base, const d2 &mean2, const d2 &var2, const d2 &acq2) __attribute__((always_inline)) {
+        const int64_t c = base + lane2;
+        if (base + span <= m) {                                      // (uniform)
+            if (mean_out) *reinterpret_cast<d2 *>(mean_out + base + lane2) = mean2;
+            if (var_out) *reinterpret_cast<d2 *>(var_out + base + lane2) = var2;
+            if (acq_out) *reinterpret_cast<d2 *>(acq_out + base + lane2) = acq2;
+        } else if (c + 1 < m) {
+            if (mean_out) *reinterpret_cast<d2 *>(mean_out + c) = mean2;
+            if (var_out) *reinterpret_cast<d2 *>(var_out + c) = var2;
+            if (acq_out) *reinterpret_cast<d2 *>(acq_out + c) = acq2;
+        } else if (c < m) {
+            if (mean_out) mean_out[c] = mean2[0];
+            if (var_out) var_out[c] = var2[0];
+            if (acq_out) acq_out[c] = acq2[0];
+        }
+    };
+    d2 qn = {0.0, 0.0}, mun = {0.0, 0.0}, pmn = {0.0, 0.0}, pvn = {0.0, 0.0};
+    d2 mean_done = {0.0, 0.0}, var_done = {0.0, 0.0}, acq_done = {0.0, 0.0};
+    fetch(cu, qn, mun, pmn, pvn);
+    for (int64_t done = -1; cu < m; done = cu, cu += stride) {
+        d2 q2 = qn, mu2 = mun, pm2 = pmn, pv2 = pvn;
+        asm volatile("" : "+v"(q2), "+v"(mu2), "+v"(pm2), "+v"(pv2) : : "memory");
+        if (done >= 0) store(done, mean_done, var_done, acq_done);
+        fetch(cu + stride, qn, mun, pmn, pvn);
+        const bool full = cu + span <= m;                            // uniform
+        const int64_t c = cu + lane2;
+        const bool one = full || c < m, two = full || c + 1 < m;
+        d2 mean2, var2, acq2;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            double mean, var;
+            posterior_of(q2[e], mu2[e], causal ? pm2[e] : 0.0, causal ? pv2[e] : 0.0, causal, ap, mean, var);
+            mean2[e] = mean;
+            var2[e] = var;
+        }
+#pragma unroll 1
+        for (int e = 0; e < 2; ++e) {
+            const double v = mes_of(e ? mean2[1] : mean2[0], e ? var2[1] : var2[0], p);
+            if (e) acq2[1] = v; else acq2[0] = v;
+        }
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const double acq = acq2[e];
+            const int64_t gi = c + e + index_offset;
+            if ((e == 0 ? one : two) && !(acq < bv) && better(acq, gi, bv, bi)) { bv = acq; bi = gi; }
+        }
+        mean_done = mean2;
+        var_done = var2;
+        acq_done = acq2;
+    }
+    if (cu - stride >= 2 * (int64_t)blockIdx.x * blockDim.x) store(cu - stride, mean_done, var_done, acq_done);
+    block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
+}
+
+void launch_mes_acq(hipStream_t s, const double *q, const double *mu, const double *pm, const double *pv, int64_t m,
+                    const MesParams &p, double *mean_out, double *var_out, double *acq_out, double *part_val,
+                    int64_t *part_idx, int64_t index_offset, int n_blocks)
+{
+    const bool causal = pv != nullptr, mv = mean_out || var_out;
+    auto kernel = causal ? (mv ? mes_acq_kernel<true, true> : mes_acq_kernel<true, false>)
+                         : (mv ? mes_acq_kernel<false, true> : mes_acq_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(256), 0, s, q, mu, pm, pv, m, p, mean_out, var_out, acq_out, part_val,
+                       part_idx, index_offset);
+}
+
+// ---- the Gumbel fit ------------------------------------------------------------------------------------------------
+constexpr int kGumbelThreads = 1024;
+constexpr int kGumbelWaves = kGumbelThreads / 64;
+
+// sum_i log_ndtr(-(x - mean_i) / sqrt(var_i)) over the m grid points: thread t sums i = t, t + 1024, ... in order, a
+// butterfly sums each wave, every thread sums the 16 wave partials in wave order -- every thread returns the same bits.
+// `buf` alternates between two LDS rows from call to call, so one barrier per call suffices.
+__device__ double gumbel_log_sum(const double *__restrict__ mean, const double *__restrict__ var, int64_t m, double x,
+                                 double (*part)[kGumbelWaves], int &buf)
+{
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < m; i += kGumbelThreads) s = s + log_ndtr(-(x - mean[i]) / sqrt(var[i]));
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) s = s + __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0) part[buf][threadIdx.x >> 6] = s;
+    __syncthreads();
+    double t = part[buf][0];
+#pragma unroll
+    for (int w = 1; w < kGumbelWaves; ++w) t = t + part[buf][w];
+    buf ^= 1;
+    return t;
+}
+
+// One workgroup per quantile (val = 0.25, 0.5, 0.75).  left = min(fmean - 5 fsd), right = max(fmean + 5 fsd), then scipy's
+// bisect (scipy/optimize/Zeros/bisect.c) with xtol = 2e-12, rtol = 4 eps, maxiter = 10000, on f(x) = probf(x) - val:
+//     fa = f(xa), fb = f(xb); fa fb > 0: error; fa == 0: xa; fb == 0: xb; dm = xb - xa;
+//     repeat: dm *= .5; xm = xa + dm; fm = f(xm); if fm fa >= 0: xa = xm; if fm == 0 or |dm| < xtol + rtol |xm|: xm
+// Every thread holds the whole state and takes the same decisions from the same sums: the control flow is uniform.
+__global__ __launch_bounds__(kGumbelThreads) void gumbel_quantiles_kernel(const double *__restrict__ mean,
+                                                                          const double *__restrict__ var, int64_t m,
+                                                                          double *__restrict__ out,
+                                                                          int64_t *__restrict__ status)
+{
+    __shared__ double part[2][kGumbelWaves];
+    __shared__ double lr[2][kGumbelWaves];
+    int buf = 0;
+    const double val = 0.25 * (double)(blockIdx.x + 1);
+    // bracket: min / max are exact whatever the order; a NaN anywhere makes both NaN (np.min / np.max propagate it)
+    double lo = INFINITY, hi = -INFINITY;
+    for (int64_t i = threadIdx.x; i < m; i += kGumbelThreads) {
+        const double sd = sqrt(var[i]);
+        const double a = mean[i] - 5.0 * sd, b = mean[i] + 5.0 * sd;
+        lo = (isnan(a) || a < lo) ? a : lo;
+        hi = (isnan(b) || b > hi) ? b : hi;
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double ol = __shfl_xor(lo, off), oh = __shfl_xor(hi, off);
+        lo = (isnan(ol) || ol < lo) ? ol : lo;
+        hi = (isnan(oh) || oh > hi) ? oh : hi;
+    }
+    if ((threadIdx.x & 63) == 0) { lr[0][threadIdx.x >> 6] = lo; lr[1][threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    lo = lr[0][0];
+    hi = lr[1][0];
+    for (int w = 1; w < kGumbelWaves; ++w) {
+        lo = (isnan(lr[0][w]) || lr[0][w] < lo) ? lr[0][w] : lo;
+        hi = (isnan(lr[1][w]) || lr[1][w] > hi) ? lr[1][w] : hi;
+    }
+    auto f = [&](double x) { return (1.0 - exp(gumbel_log_sum(mean, var, m, x, part, buf))) - val; };
+    const double xtol = 2e-12, rtol = 4.0 * 2.220446049250313e-16;
+    double xa = lo, result = lo;
+    int64_t st = 0;
+    const double fa = f(lo);
+    const double fb = f(hi);
+    if (fa * fb > 0.0) {
+        st = 1;
+    } else if (fa == 0.0) {
+        result = lo;
+    } else if (fb == 0.0) {
+        result = hi;
+    } else {
+        double dm = hi - lo;
+        st = 2;
+        for (int it = 0; it < 10000; ++it) {
+            dm *= 0.5;
+            const double xm = xa + dm;
+            const double fm = f(xm);
+            if (fm * fa >= 0.0) xa = xm;
+            if (fm == 0.0 || fabs(dm) < xtol + rtol * fabs(xm)) { result = xm; st = 0; break; }
+        }
+        if (st == 2) result = xa;
+    }
+    if (threadIdx.x == 0) {
+        out[blockIdx.x] = result;
+        status[blockIdx.x] = st;
+        if (blockIdx.x == 0) { out[3] = lo; out[4] = hi; }
+    }
+}
+
+void launch_gumbel_quantiles(hipStream_t s, const double *mean, const double *var, int64_t m, double *out, int64_t *status)
+{
+    hipLaunchKernelGGL(gumbel_quantiles_kernel, dim3(3), dim3(kGumbelThreads), 0, s, mean, var, m, out, status);
+}
+
+}  // namespace cbo

@@ -103,14 +103,24 @@ def default_grid_shape(d, budget=None):
 
 
 def find_next_y_point(space, model, current_global_best, evaluated_set, costs_functions, task='min',
-                      grid_shape=None, candidates=None, anchors="grid", num_anchor_points=None):
+                      grid_shape=None, candidates=None, anchors="grid", num_anchor_points=None, acquisition="EI"):
     """utils.py:29-37.  Returns (y_acquisition (1,1), x_new (1,d)).
 
     ``candidates`` (optional (M,d) array or CandidateGrid) overrides the regular grid over ``space``.
     ``anchors="uniform"``: the reference's own optimiser instead of the grid -- 100 uniform anchors from numpy's global
     generator, one batched device sweep over them, L-BFGS from the best (causal_optimizer.py:26-65), then the
     acquisition re-evaluated at the point found (utils.py:36) -- the four lines of the reference's function.
+    ``acquisition="MES"``: emukit's ``MaxValueEntropySearch(model, space) / Cost`` over the same grid in the place of the
+    causal EI (its Gumbel fit draws from numpy's global generator; ``current_global_best`` is not used).  MES minimises and
+    has no gradients: ``task="max"`` and ``anchors="uniform"`` raise ``ValueError``.
     """
+    if acquisition not in ("EI", "MES"):
+        raise ValueError(f"acquisition must be 'EI' or 'MES', not {acquisition!r}")
+    if acquisition == "MES":
+        if task != "min":
+            raise ValueError("acquisition='MES' minimises: task must be 'min'")
+        if anchors != "grid":
+            raise ValueError("acquisition='MES' has no gradients: anchors must be 'grid'")
     cost_acquisition = Cost(costs_functions, evaluated_set)
     if anchors == "uniform":
         from .causal_optimizer import CausalGradientAcquisitionOptimizer
@@ -118,7 +128,11 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
         acquisition = CausalExpectedImprovement(current_global_best, task, model) / cost_acquisition
         x_new, _ = optimizer.optimize(acquisition)
         return acquisition.evaluate(x_new), x_new
-    ei = CausalExpectedImprovement(current_global_best, task, model)
+    if acquisition == "MES":
+        from .max_value_entropy import MaxValueEntropySearch
+        ei = MaxValueEntropySearch(model, space)
+    else:
+        ei = CausalExpectedImprovement(current_global_best, task, model)
     own = False
     if candidates is None:
         bounds = space_bounds(space)

@@ -210,6 +210,37 @@ int cbo_gp_integrated_variance_reduction(cbo_gp *gp, int64_t m, const double *Xs
                                          int64_t p, const double *Xint, const double *prior_var_int, double cost,
                                          double *ivr_out, double *best_val, int64_t *best_idx);
 
+/* Max-value entropy search (emukit MaxValueEntropySearch, Wang & Jegelka 2017; emukit 0.4 restated from memory, parity
+ * unpinned: DESIGN.md §4e), the entropy acquisition emukit users reach for after EI, in two calls.
+ *
+ * cbo_gp_mes_gumbel: MaxValueEntropySearch.update_parameters' model.predict(grid) (noise included) and _fit_gumbel's three
+ * scipy.optimize.bisect(lambda x: probf(x) - val, left, right, maxiter=10000) calls, val = 0.25, 0.5, 0.75, with
+ *     probf(x) = 1 - exp(sum_i log_ndtr(-(x - fmean_i) / fsd_i)),  fsd = sqrt(fvar),
+ *     left = min(fmean - 5 fsd), right = max(fmean + 5 fsd),
+ * scipy's xtol = 2e-12 and rtol = 4 eps, and scipy's loop (Zeros/bisect.c); quantiles3 = (q25, q50, q75),
+ * b = (q25 - q75) / (log(log(4/3)) - log(log(4))), a = q50 - b log(log(2)).  The m grid points Xg (emukit stacks model.X
+ * on top of its uniform grid; the caller does) are predicted as cbo_gp_predict predicts them and the bisections run on the
+ * device from that mean and variance: nothing comes back in between.  mean_out / var_out (m, may be NULL): the grid's
+ * mean and variance, bit for bit cbo_gp_predict's.  The sums over the grid run in a fixed order (two calls give the same
+ * bits), not numpy's: a decision of the bisection can differ from scipy's where probf(x) - val is at rounding level.
+ * A bracket whose ends do not change sign (scipy's ValueError) or a bisection that does not converge: CBO_ERR_INVALID
+ * with a message.  Unfitted model: CBO_ERR_NOT_FITTED; NULL arguments, m <= 0, a causal model without prior_mean_g and
+ * prior_var_g: CBO_ERR_INVALID.  The model is only read.
+ *
+ * cbo_acq_sweep_mes: MaxValueEntropySearch.evaluate / Cost over a candidate set, with the arg-max:
+ *     acq = mean_k(-g_k pdf(g_k) / (2 c_k) - log(c_k)) / cost,  g_k = (mins[k] - mean) / max(sqrt(var), 1e-10),
+ *     c_k = clip(1 - ndtr(g_k), 1e-10, 1),
+ * mean / var as cbo_acq_sweep forms them (same path: the candidates' cached q, mu when the fit stamp matches, one appended
+ * row, the fp32 strip of fp32 models), so mean_out / var_out are bit for bit cbo_acq_sweep's.  The mean over the samples
+ * is summed in numpy's order (np.mean(axis=1)).  best_idx: lowest index on ties, NaN maximal, offset by the set's
+ * index_offset.  acq_out / mean_out / var_out (m doubles each) may be NULL.  n_samples is at most 64 (the samples travel
+ * in the kernel's arguments).  n_samples <= 0 or > 64, NULL or non-finite mins, cost <= 0 or NaN, a causal model whose
+ * candidates carry no prior: CBO_ERR_INVALID; unfitted model: CBO_ERR_NOT_FITTED.  The model is only read. */
+int cbo_gp_mes_gumbel(cbo_gp *gp, int64_t m, const double *Xg, const double *prior_mean_g, const double *prior_var_g,
+                      double *quantiles3, double *a, double *b, double *mean_out, double *var_out);
+int cbo_acq_sweep_mes(cbo_gp *gp, cbo_cands *cands, int n_samples, const double *mins, double cost, double *acq_out,
+                      double *mean_out, double *var_out, double *best_val, int64_t *best_idx);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
