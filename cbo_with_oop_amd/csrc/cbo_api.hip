@@ -68,6 +68,22 @@ struct EventPair {
     int phase;
 };
 
+// A grow-only buffer of `cap` elements (device memory, or pinned host memory that the kernels read and write directly),
+// resized only by grow() below and freed with its owner.  It converts to its pointer.
+template <class T, bool Pinned = false>
+struct GrowBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf &) = delete;
+    GrowBuf &operator=(const GrowBuf &) = delete;
+    ~GrowBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) Pinned ? hipHostFree(p) : hipFree(p); p = nullptr; cap = 0; }
+};
+template <class T>
+using PinnedBuf = GrowBuf<T, true>;
+
 struct cbo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -95,21 +111,21 @@ struct cbo_ctx {
     std::vector<hipEvent_t> pool;
     cbo_timers timers{};
     // sweep workspaces (grown on demand)
-    double *V = nullptr; size_t V_bytes = 0;
-    double *W = nullptr; size_t W_bytes = 0;          // -Ky^-1 for the likelihood gradients
-    double *gpart = nullptr; size_t gpart_elems = 0;
-    double *mupart = nullptr; size_t mupart_elems = 0;   // fp32 sweep: per-row-tile partial sums of K*^T alpha
+    GrowBuf<double> V;                                // the fp32 sweep's workspace too (as floats)
+    GrowBuf<double> W;                                // -Ky^-1 for the likelihood gradients, L^-T V for the prediction's
+    GrowBuf<double> gpart;
+    GrowBuf<double> mupart;                           // fp32 sweep: per-row-tile partial sums of K*^T alpha
     // multi-set sweep of small models (cbo_acq_sweep_sets): descriptors, per-workgroup scratch, partial and final winners
-    cbo_small_set *sets_host = nullptr; int sets_cap = 0;       // pinned, read by the kernel directly
-    cbo_small_result *small_out = nullptr;                      // pinned, written by the kernel directly
-    double *small_scratch = nullptr; size_t small_scratch_elems = 0;
-    double *small_part_val = nullptr; int64_t *small_part_idx = nullptr; size_t small_part_elems = 0;
-    int *small_info = nullptr;                                  // device, sets_cap status words + sets_cap tickets (zero between calls)
-    int small_seq = 0;                                          // sequence number of the last multi-set call
+    PinnedBuf<cbo_small_set> sets_host;                         // read by the kernel directly
+    PinnedBuf<cbo_small_result> small_out;                      // written by the kernel directly
+    GrowBuf<double> small_scratch;
+    GrowBuf<double> small_part_val; GrowBuf<int64_t> small_part_idx;
+    GrowBuf<int> small_info;                                    // cap / 2 status words + cap / 2 tickets (zero between calls)
+    int small_seq = 0;                                          // sequence number of the last polled launch
     int polled_launches = 0;                                    // launches completed by polling since the last stream sync
-    cbo_small_lml_result *lml_out = nullptr;                    // pinned, written by small_lml_kernel
-    cbo_small_lml_result *lml_batch_out = nullptr; int lml_batch_cap = 0;   // pinned, written by small_lml_batch_kernel
-    double *q = nullptr, *mu = nullptr, *mean = nullptr, *var = nullptr, *acq = nullptr; size_t vec_elems = 0;
+    PinnedBuf<cbo_small_lml_result> lml_out;                    // written by small_lml_kernel
+    PinnedBuf<cbo_small_lml_result> lml_batch_out;              // written by small_lml_batch_kernel
+    GrowBuf<double> q, mu, mean, var, acq;                      // per candidate
     double *part_val = nullptr; int64_t *part_idx = nullptr;
     double *best_val = nullptr; int64_t *best_idx = nullptr;   // device
     double *h_best_val = nullptr; int64_t *h_best_idx = nullptr; // pinned host
@@ -117,17 +133,15 @@ struct cbo_ctx {
     // host-buffer entry points (cbo_gp_predict, _grouped, _gradients, cbo_acq_sweep_host) reuse ONE grow-only candidate
     // set instead of creating and destroying one per call; gradient / export scratch likewise
     cbo_cands *scratch_k = nullptr;
-    double *grads = nullptr; size_t grads_elems = 0;
-    double *export_buf = nullptr; size_t export_elems = 0;
-    double *cov = nullptr; size_t cov_elems = 0;       // output of cbo_gp_predict_cov / cbo_gp_cov_between (grow-only)
-    // cbo_gp_posterior_samples (grow-only): the factor of Sigma in the factorisation's layout, its diagonal-tile
-    // inverses and status words, the transposed normals, the samples (which first hold the uploaded normals)
-    double *samp_A = nullptr; size_t samp_A_elems = 0;
-    double *samp_invDt = nullptr; size_t samp_invDt_elems = 0;
-    int *samp_info = nullptr;
-    double *samp_Z = nullptr; size_t samp_Z_elems = 0;
-    double *samp_out = nullptr; size_t samp_out_elems = 0;
-    double *ivr_part = nullptr; size_t ivr_part_elems = 0;   // cbo_gp_integrated_variance_reduction: [m][tiles] partials
+    GrowBuf<double> grads;
+    GrowBuf<double> export_buf;
+    GrowBuf<double> cov;                               // output of cbo_gp_predict_cov / cbo_gp_cov_between
+    // cbo_gp_posterior_samples: the factor of Sigma in the factorisation's layout, its diagonal-tile inverses and status
+    // words, the transposed normals, the samples (which first hold the uploaded normals)
+    GrowBuf<double> samp_A, samp_invDt;
+    GrowBuf<int> samp_info;
+    GrowBuf<double> samp_Z, samp_out;
+    GrowBuf<double> ivr_part;                          // cbo_gp_integrated_variance_reduction: [m][tiles] partials
     // small uploads (cbo_gp_upload_data / cbo_gp_set_data of a few KB, every trial of the reference's loop): one
     // pinned staging buffer the preparation kernel reads directly; `stage_done` guards its reuse
     double *stage = nullptr; hipEvent_t stage_done = nullptr; bool stage_pending = false;
@@ -187,7 +201,7 @@ struct cbo_cands {
     std::vector<double> prepared_ls;
     // q = sum V^2 and mu = V^T z of the last sweep, valid while the model's fit stamp is the one recorded here:
     // between refits only the incumbent changes, and EI / cost / arg-max are recomputed from these two vectors
-    double *q = nullptr, *mu = nullptr;
+    GrowBuf<double> q, mu;
     uint64_t fit_stamp = 0;
     // cbo_cands_keep_solution: V = L^-1 K* stays resident so that an appended observation extends it by one row
     bool keep_v = false;
@@ -196,6 +210,29 @@ struct cbo_cands {
     uint64_t v_stamp = 0;
     double *partial = nullptr;       // [64][m_pad] slice sums of the row update
 };
+
+// b to at least n elements (nothing happens when they fit): an old buffer is freed only after the queued work that may
+// read it is done.  A failed allocation leaves b empty and is cleared from the runtime's error state, where it would
+// otherwise fail the next call's launch check.  zero: a new buffer is cleared.
+template <class T, bool Pinned>
+static int grow(cbo_ctx *c, GrowBuf<T, Pinned> &b, size_t n, bool zero = false)
+{
+    if (n <= b.cap) return CBO_OK;
+    if (b.p) HIP_TRY(hipStreamSynchronize(c->stream));
+    b.release();
+    void *p = nullptr;
+    const hipError_t e = Pinned ? hipHostMalloc(&p, sizeof(T) * n) : hipMalloc(&p, sizeof(T) * n);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CBO_ERR_HIP, std::string(Pinned ? "hipHostMalloc" : "hipMalloc") + " of " +
+                                     std::to_string(sizeof(T) * n) + " bytes: " + hipGetErrorString(e));
+    }
+    b.p = static_cast<T *>(p);
+    b.cap = n;
+    if (zero && Pinned) std::memset(p, 0, sizeof(T) * n);
+    if (zero && !Pinned) HIP_TRY(hipMemset(p, 0, sizeof(T) * n));
+    return CBO_OK;
+}
 
 // ---- profiling helpers ---------------------------------------------------------------------------
 static hipEvent_t get_event(cbo_ctx *c)
@@ -391,20 +428,14 @@ extern "C" void cbo_shutdown(cbo_ctx *c)
     destroy_ctx(c);
 }
 
+// (the grow-only buffers go with `delete c`)
 static void destroy_ctx(cbo_ctx *c)
 {
     hipSetDevice(c->device);
     if (c->scratch_k) { cbo_cands_destroy(c->scratch_k); c->scratch_k = nullptr; }
-    hipFree(c->grads); hipFree(c->export_buf); hipFree(c->cov);
-    hipFree(c->samp_A); hipFree(c->samp_invDt); hipFree(c->samp_info); hipFree(c->samp_Z); hipFree(c->samp_out);
-    hipFree(c->ivr_part);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto &p : c->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : c->pool) hipEventDestroy(e);
-    hipFree(c->W); hipFree(c->gpart); hipFree(c->mupart);
-    hipHostFree(c->sets_host); hipHostFree(c->small_out); hipHostFree(c->lml_out); hipHostFree(c->lml_batch_out); hipFree(c->small_scratch); hipFree(c->small_part_val);
-    hipFree(c->small_part_idx); hipFree(c->small_info);
-    hipFree(c->V); hipFree(c->q); hipFree(c->mu); hipFree(c->mean); hipFree(c->var); hipFree(c->acq);
     hipFree(c->part_val); hipFree(c->part_idx); hipFree(c->best_val); hipFree(c->best_idx);
     hipHostFree(c->h_best_val); hipHostFree(c->h_best_idx); hipHostFree(c->h_info); hipHostFree(c->stage);
     if (c->stage_done) hipEventDestroy(c->stage_done);
@@ -539,6 +570,24 @@ static void free_gp_data(cbo_gp *g)
     g->fitted = false;
 }
 
+// X (n, d) | y | prior mean | prior variance into the context's pinned staging buffer once the kernel that read it last is
+// done, and the model's host copy of the prior variance
+static int stage_data(cbo_gp *g, int64_t n, const double *X, const double *y, const double *pm, const double *pv)
+{
+    cbo_ctx *c = g->ctx;
+    if (c->stage_pending) { HIP_TRY(hipEventSynchronize(c->stage_done)); c->stage_pending = false; }
+    double *st = c->stage;
+    std::memcpy(st, X, sizeof(double) * n * g->d);
+    std::memcpy(st + n * g->d, y, sizeof(double) * n);
+    g->h_pv.clear();
+    if (pv) {
+        std::memcpy(st + n * g->d + n, pm, sizeof(double) * n);
+        std::memcpy(st + n * g->d + 2 * n, pv, sizeof(double) * n);
+        g->h_pv.assign(pv, pv + n);
+    }
+    return CBO_OK;
+}
+
 static int upload_gp_data(cbo_gp *g, int64_t n, const double *X, const double *y, const double *pm, const double *pv)
 {
     cbo_ctx *c = g->ctx;
@@ -579,17 +628,9 @@ static int upload_gp_data(cbo_gp *g, int64_t n, const double *X, const double *y
     if (stage_need <= kStageBytes) {
         // small upload: host arrays -> pinned staging -> ONE kernel that reads the staging buffer itself.  The
         // caller's buffers are free as soon as they are copied here; nothing to wait for on the stream.
-        if (c->stage_pending) { HIP_TRY(hipEventSynchronize(c->stage_done)); c->stage_pending = false; }
-        double *st = c->stage;
-        std::memcpy(st, X, sizeof(double) * n * g->d);
-        std::memcpy(st + n * g->d, y, sizeof(double) * n);
-        g->h_pv.clear();
-        if (pv) {
-            std::memcpy(st + n * g->d + n, pm, sizeof(double) * n);
-            std::memcpy(st + n * g->d + 2 * n, pv, sizeof(double) * n);
-            g->h_pv.assign(pv, pv + n);
-        }
-        launch_prep_points_staged(c->stream, st, n, g->d, g->h.ard ? g->ls_dev : nullptr, pv != nullptr, g->raw, g->y,
+        const int rc = stage_data(g, n, X, y, pm, pv);
+        if (rc != CBO_OK) return rc;
+        launch_prep_points_staged(c->stream, c->stage, n, g->d, g->h.ard ? g->ls_dev : nullptr, pv != nullptr, g->raw, g->y,
                                   g->X.pm, g->X.pv, g->X.xs, n_pad, g->X.sq, g->X.sv);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->stage_done, c->stream));
@@ -752,6 +793,18 @@ static int attempt_factor(cbo_ctx *c, const int *info, Enqueue enqueue, bool *pd
     }
 }
 
+// the model is fitted from here on, at `tries` steps of the jitter ladder: a new stamp for every cache keyed on the fit
+static void mark_fitted(cbo_gp *g, int tries, double jitter)
+{
+    g->fitted = true;
+    g->fit_stamp = ++g_fit_stamp;
+    g->parent_stamp = 0;
+    g->alpha_ready = false;
+    g->tries = tries;
+    g->jitter = jitter;
+    if (g->ctx->profiling) g->ctx->timers.n_fit += 1;
+}
+
 // the factor in g->A is the model's: what every consumer of a fitted model expects beside it
 static int adopt_factor(cbo_gp *g, int tries, double jitter)
 {
@@ -761,13 +814,7 @@ static int adopt_factor(cbo_gp *g, int tries, double jitter)
     HIP_TRY(hipMemcpy2DAsync(g->z, sizeof(double), g->A + g->n_pad, sizeof(double) * g->lda, sizeof(double),
                              (size_t)g->n_pad, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipGetLastError());
-    g->fitted = true;
-    g->fit_stamp = ++g_fit_stamp;
-    g->parent_stamp = 0;
-    g->alpha_ready = false;
-    g->tries = tries;
-    g->jitter = jitter;
-    if (c->profiling) c->timers.n_fit += 1;
+    mark_fitted(g, tries, jitter);
     return CBO_OK;
 }
 
@@ -905,20 +952,6 @@ extern "C" int cbo_gp_upload_data(cbo_gp *g, int64_t n, const double *X, const d
     return upload_gp_data(g, n, X, y, pm, pv);      // leaves the model unfitted
 }
 
-// a grow-only device buffer *p of *cap doubles, to at least elems: the old one is freed only after the queued work that
-// may read it is done
-static int grow_buffer(cbo_ctx *c, double **p, size_t *cap, size_t elems)
-{
-    if (elems > *cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(*p);
-        *p = nullptr; *cap = 0;
-        HIP_TRY(hipMalloc(p, sizeof(double) * elems));
-        *cap = elems;
-    }
-    return CBO_OK;
-}
-
 extern "C" int cbo_gp_get_posterior(cbo_gp *g, double *L_out, double *alpha_out)
 {
     if (!g) return fail(CBO_ERR_INVALID, "gp is NULL");
@@ -926,7 +959,7 @@ extern "C" int cbo_gp_get_posterior(cbo_gp *g, double *L_out, double *alpha_out)
     cbo_ctx *c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
     if (L_out) {
-        int rc = grow_buffer(c, &c->export_buf, &c->export_elems, (size_t)g->n * (size_t)g->n);
+        int rc = grow(c, c->export_buf, (size_t)g->n * (size_t)g->n);
         if (rc != CBO_OK) return rc;
         launch_export_lower(c->stream, g->A, g->lda, g->n, c->export_buf);
         HIP_TRY(hipMemcpyAsync(L_out, c->export_buf, sizeof(double) * g->n * g->n, hipMemcpyDeviceToHost, c->stream));
@@ -949,7 +982,7 @@ extern "C" int cbo_gp_assemble_kxx(cbo_gp *g, double *K_out)
     HIP_TRY(hipSetDevice(c->device));
     // scratch: [n_pad x lda] assembly + [n x n] symmetric export, from the context's grow-only export buffer
     const size_t a_elems = (size_t)g->n_pad * (size_t)g->lda;
-    int rc = grow_buffer(c, &c->export_buf, &c->export_elems, a_elems + (size_t)g->n * (size_t)g->n);
+    int rc = grow(c, c->export_buf, a_elems + (size_t)g->n * (size_t)g->n);
     if (rc != CBO_OK) return rc;
     double *Atmp = c->export_buf, *tmp = c->export_buf + a_elems;
     launch_kxx(c->stream, g->X, g->h, g->noise_var + kGpyDiagJitter, 0.0, Atmp, g->lda, g->n_pad);
@@ -972,8 +1005,8 @@ static int cands_reserve(cbo_cands *k, int64_t m, int d, bool prior)
         const int cd = d > k->cap_d ? d : k->cap_d;
         const bool cp = prior || k->cap_prior;
         hipFree(k->raw); hipFree(k->P.xs); hipFree(k->P.sq); hipFree(k->P.sv); hipFree(k->pm); hipFree(k->pv);
-        hipFree(k->q); hipFree(k->mu);
-        k->raw = k->P.xs = k->P.sq = k->P.sv = k->pm = k->pv = k->q = k->mu = nullptr;
+        k->q.release(); k->mu.release();
+        k->raw = k->P.xs = k->P.sq = k->P.sv = k->pm = k->pv = nullptr;
         k->cap_m_pad = 0; k->cap_d = 0; k->cap_prior = false; k->fit_stamp = 0;
         hipError_t e = hipMalloc(&k->raw, sizeof(double) * cap * cd);
         if (e == hipSuccess) e = hipMalloc(&k->P.xs, sizeof(double) * cd * cap);
@@ -987,19 +1020,26 @@ static int cands_reserve(cbo_cands *k, int64_t m, int d, bool prior)
     return CBO_OK;
 }
 
-// (re)fill a candidate set from host arrays; every cache keyed on its old contents is dropped
+// a candidate set now holds m points of dimension d (its buffers reserved for them): every cache keyed on its old
+// contents is dropped
+static void cands_describe(cbo_cands *k, int64_t m, int d, bool prior, int64_t index_offset)
+{
+    k->m = m; k->d = d; k->index_offset = index_offset;
+    k->m_pad = round_up(m, kStrip);
+    k->P.n = m; k->P.ld = k->m_pad; k->P.d = d;
+    k->has_prior = prior;
+    k->prepared_for = nullptr; k->prepared_ls.clear();
+    k->fit_stamp = 0; k->v_stamp = 0;
+}
+
+// (re)fill a candidate set from host arrays
 static int cands_fill(cbo_cands *k, int64_t m, int d, const double *Xs, const double *pm, const double *pv,
                       int64_t index_offset)
 {
     cbo_ctx *c = k->ctx;
     int rc = cands_reserve(k, m, d, pv != nullptr);
     if (rc != CBO_OK) return rc;
-    k->m = m; k->d = d; k->index_offset = index_offset;
-    k->m_pad = round_up(m, kStrip);
-    k->P.n = m; k->P.ld = k->m_pad; k->P.d = d;
-    k->has_prior = pv != nullptr;
-    k->prepared_for = nullptr; k->prepared_ls.clear();
-    k->fit_stamp = 0; k->v_stamp = 0;
+    cands_describe(k, m, d, pv != nullptr, index_offset);
     hipError_t e = hipMemcpyAsync(k->raw, Xs, sizeof(double) * m * d, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && pv) e = hipMemcpyAsync(k->pm, pm, sizeof(double) * m, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && pv) e = hipMemcpyAsync(k->pv, pv, sizeof(double) * m, hipMemcpyHostToDevice, c->stream);
@@ -1034,17 +1074,60 @@ extern "C" int cbo_cands_create(cbo_ctx *c, int64_t m, int d, const double *Xs, 
 }
 
 // the context's reusable candidate set for the host-buffer entry points (no allocation once it has grown)
+static cbo_cands *scratch_set(cbo_ctx *c)
+{
+    if (!c->scratch_k) { c->scratch_k = new cbo_cands(); c->scratch_k->ctx = c; }
+    return c->scratch_k;
+}
+
 static int scratch_cands(cbo_ctx *c, int64_t m, int d, const double *Xs, const double *pm, const double *pv,
                          cbo_cands **out)
 {
     int rc = check_cands_args(c, m, d, Xs, pm, pv);
     if (rc != CBO_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->scratch_k) { c->scratch_k = new cbo_cands(); c->scratch_k->ctx = c; }
-    rc = cands_fill(c->scratch_k, m, d, Xs, pm, pv, 0);
+    rc = cands_fill(scratch_set(c), m, d, Xs, pm, pv, 0);
     if (rc != CBO_OK) return rc;
     *out = c->scratch_k;
     return CBO_OK;
+}
+
+// The scratch set of m host points for model g: prior closures only when g is causal.  pm == nullptr: the posterior mean
+// is not wanted, and the prior variance stands in for the prior mean the set carries beside it (the mean formed from it
+// is discarded).
+static int scratch_points(cbo_gp *g, int64_t m, const double *Xs, const double *pm, const double *pv, cbo_cands **out)
+{
+    const bool causal = g->X.sv != nullptr;
+    return scratch_cands(g->ctx, m, g->d, Xs, causal ? (pm ? pm : pv) : nullptr, causal ? pv : nullptr, out);
+}
+
+// The scratch set [X1 | filler | X2] for model g: X2 starts on column round_up(m1, align), so that one solve gives both
+// sets' solutions side by side; the filler repeats X1's first point (its columns are never read).  pv1 / pv2: the prior
+// variances of a causal model (no mean is formed).
+static int scratch_pair(cbo_gp *g, int64_t m1, const double *X1, const double *pv1, int64_t m2, const double *X2,
+                        const double *pv2, int64_t align, cbo_cands **out)
+{
+    const bool causal = g->X.sv != nullptr;
+    const int d = g->d;
+    const int64_t off = round_up(m1, align), mt = off + m2;
+    std::vector<double> xs((size_t)mt * d), vs(causal ? (size_t)mt : 0);
+    std::memcpy(xs.data(), X1, sizeof(double) * (size_t)m1 * d);
+    for (int64_t i = m1; i < off; ++i) std::memcpy(&xs[(size_t)i * d], X1, sizeof(double) * d);
+    std::memcpy(&xs[(size_t)off * d], X2, sizeof(double) * (size_t)m2 * d);
+    if (causal) {
+        std::memcpy(vs.data(), pv1, sizeof(double) * (size_t)m1);
+        for (int64_t i = m1; i < off; ++i) vs[(size_t)i] = pv1[0];
+        std::memcpy(&vs[(size_t)off], pv2, sizeof(double) * (size_t)m2);
+    }
+    return scratch_points(g, mt, xs.data(), nullptr, vs.data(), out);
+}
+
+// the candidates' own copies of q, mu (the sweep cache), allocated on first use for the buffers' capacity
+static int cands_cache_vectors(cbo_cands *k)
+{
+    int rc = grow(k->ctx, k->q, (size_t)k->cap_m_pad);
+    if (rc == CBO_OK) rc = grow(k->ctx, k->mu, (size_t)k->cap_m_pad);
+    return rc;
 }
 
 extern "C" void cbo_cands_destroy(cbo_cands *k)
@@ -1052,9 +1135,19 @@ extern "C" void cbo_cands_destroy(cbo_cands *k)
     if (!k) return;
     hipSetDevice(k->ctx->device);
     hipStreamSynchronize(k->ctx->stream);
-    hipFree(k->raw); hipFree(k->pm); hipFree(k->pv); hipFree(k->q); hipFree(k->mu); hipFree(k->V); hipFree(k->partial);
+    hipFree(k->raw); hipFree(k->pm); hipFree(k->pv); hipFree(k->V); hipFree(k->partial);
     hipFree(k->P.xs); hipFree(k->P.sq); hipFree(k->P.sv);
     delete k;
+}
+
+// the per-candidate vectors q, mu and the epilogue's mean, var, acq for m_pad candidates
+static int grow_vectors(cbo_ctx *c, int64_t m_pad)
+{
+    for (GrowBuf<double> *b : {&c->q, &c->mu, &c->mean, &c->var, &c->acq}) {
+        const int rc = grow(c, *b, (size_t)m_pad);
+        if (rc != CBO_OK) return rc;
+    }
+    return CBO_OK;
 }
 
 static int ensure_workspaces(cbo_ctx *c, int64_t n_pad, int64_t m_pad, int64_t *chunk_cols, int64_t *ldv,
@@ -1066,25 +1159,9 @@ static int ensure_workspaces(cbo_ctx *c, int64_t n_pad, int64_t m_pad, int64_t *
     const int64_t max_cols = (int64_t)(c->max_ws_bytes / (elem * (size_t)n_pad)) / kStrip * kStrip;
     if (cols > max_cols) cols = max_cols < kStrip ? kStrip : max_cols;
     const int64_t ld = cols + (int64_t)(128 / elem);
-    const size_t need = elem * (size_t)n_pad * (size_t)ld;
-    if (need > c->V_bytes) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->V);
-        c->V = nullptr; c->V_bytes = 0;
-        HIP_TRY(hipMalloc(&c->V, need));
-        c->V_bytes = need;
-    }
-    if ((size_t)m_pad > c->vec_elems) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->q); hipFree(c->mu); hipFree(c->mean); hipFree(c->var); hipFree(c->acq);
-        c->q = c->mu = c->mean = c->var = c->acq = nullptr; c->vec_elems = 0;
-        HIP_TRY(hipMalloc(&c->q, sizeof(double) * m_pad));
-        HIP_TRY(hipMalloc(&c->mu, sizeof(double) * m_pad));
-        HIP_TRY(hipMalloc(&c->mean, sizeof(double) * m_pad));
-        HIP_TRY(hipMalloc(&c->var, sizeof(double) * m_pad));
-        HIP_TRY(hipMalloc(&c->acq, sizeof(double) * m_pad));
-        c->vec_elems = (size_t)m_pad;
-    }
+    int rc = grow(c, c->V, (elem * (size_t)n_pad * (size_t)ld + sizeof(double) - 1) / sizeof(double));
+    if (rc == CBO_OK) rc = grow_vectors(c, m_pad);
+    if (rc != CBO_OK) return rc;
     *chunk_cols = cols;
     *ldv = ld;
     return CBO_OK;
@@ -1195,8 +1272,6 @@ static int own_solution_buffer(cbo_gp *g, cbo_cands *k, double **V, int64_t *ldv
 
 // fp32 sweep (CBO_DTYPE_F32 models): K* in fp64 arithmetic rounded to fp32, substitution on the f32 MFMA, q and mu
 // accumulated in fp64.  Left-looking strip kernel only; the fp32 copies of the factor follow the fit lazily.
-static int ensure_alpha(cbo_gp *g);
-
 static int enqueue_posterior_f32(cbo_gp *g, cbo_cands *k)
 {
     cbo_ctx *c = g->ctx;
@@ -1205,14 +1280,14 @@ static int enqueue_posterior_f32(cbo_gp *g, cbo_cands *k)
     if (rc != CBO_OK) return rc;
     rc = ensure_alpha(g);                     // the mean is K*^T alpha in fp64 (GPy's formula), see kernels_f32.hip
     if (rc != CBO_OK) return rc;
-    rc = grow_buffer(c, &c->mupart, &c->mupart_elems, (size_t)(g->n32 / 64) * (size_t)chunk);
+    rc = grow(c, c->mupart, (size_t)(g->n32 / 64) * (size_t)chunk);
     if (rc != CBO_OK) return rc;
     if (g->f32_stamp != g->fit_stamp) {
         PhaseScope ps(c, PH_CONVERT);
         launch_factor_to_f32(c->stream, g->A, g->lda, g->n_pad, g->invDt, g->Uf, g->ldu32, g->invF, g->n32);
         g->f32_stamp = g->fit_stamp;
     }
-    float *Vf = reinterpret_cast<float *>(c->V);
+    float *Vf = reinterpret_cast<float *>(c->V.p);
     k->v_stamp = 0;
     for (int64_t c0 = 0; c0 < k->m_pad; c0 += chunk) {
         const int64_t cols = (k->m_pad - c0 < chunk) ? (k->m_pad - c0) : chunk;
@@ -1353,10 +1428,8 @@ static int finish_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, double
     // substitution altogether
     const bool cached = k->fit_stamp != 0 && k->fit_stamp == g->fit_stamp;
     if (!cached && c->sweep_cache) {
-        if (!k->q) {
-            HIP_TRY(hipMalloc(&k->q, sizeof(double) * k->cap_m_pad));
-            HIP_TRY(hipMalloc(&k->mu, sizeof(double) * k->cap_m_pad));
-        }
+        const int rc = cands_cache_vectors(k);
+        if (rc != CBO_OK) return rc;
         HIP_TRY(hipMemcpyAsync(k->q, c->q, sizeof(double) * k->m_pad, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(k->mu, c->mu, sizeof(double) * k->m_pad, hipMemcpyDeviceToDevice, c->stream));
         k->fit_stamp = g->fit_stamp;
@@ -1509,9 +1582,8 @@ static int sweep_impl(cbo_gp *g, cbo_cands *k, double y_best, int task, double e
         k->fit_stamp = 0;
         rc = enqueue_posterior(g, k);
         if (rc != CBO_OK) return rc;
-    } else if ((size_t)k->m_pad > c->vec_elems) {
-        int64_t chunk = 0, ldv = 0;                      // mean / var / acq scratch of the epilogue
-        rc = ensure_workspaces(c, g->n_pad, k->m_pad, &chunk, &ldv);
+    } else {
+        rc = grow_vectors(c, k->m_pad);                  // mean / var / acq scratch of the epilogue
         if (rc != CBO_OK) return rc;
     }
     return finish_sweep(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, mes);
@@ -1636,10 +1708,8 @@ extern "C" int cbo_gp_fit_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task
     // unchanged model starts from them): no device copies between the closing launch and the acquisition kernel
     double *qbuf = c->q, *mubuf = c->mu;
     if (c->sweep_cache) {
-        if (!k->q) {
-            HIP_TRY(hipMalloc(&k->q, sizeof(double) * k->cap_m_pad));
-            HIP_TRY(hipMalloc(&k->mu, sizeof(double) * k->cap_m_pad));
-        }
+        rc = cands_cache_vectors(k);
+        if (rc != CBO_OK) return rc;
         qbuf = k->q;
         mubuf = k->mu;
         k->fit_stamp = 0;                                  // not valid until this call has succeeded
@@ -1709,13 +1779,7 @@ extern "C" int cbo_gp_fit_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task
         rc = next_jitter(g, &tries, &jitter);
         if (rc != CBO_OK) return rc;
     }
-    g->fitted = true;
-    g->fit_stamp = ++g_fit_stamp;
-    g->parent_stamp = 0;
-    g->alpha_ready = false;
-    g->tries = tries;
-    g->jitter = jitter;
-    if (c->profiling) c->timers.n_fit += 1;
+    mark_fitted(g, tries, jitter);
     if (tries_out) *tries_out = tries;
     if (jitter_out) *jitter_out = jitter;
     if (Vws != c->V) { k->v_stamp = g->fit_stamp; k->v_rows = g->n; }
@@ -1767,11 +1831,47 @@ static bool poll_until(Pred done, double budget_us)
         if (std::chrono::duration<double, std::micro>(clk::now() - t0).count() > budget_us) return done();
     }
 }
-static bool polled_launch_needs_sync(cbo_ctx *c)
+
+// One launch whose results come back in n pinned records out[0..n), each closed by the call's sequence number, which
+// launch(seq) receives when it queues the launch (it returns CBO_OK or an error).  The records are polled
+// (kPollBudgetUs); the stream is synchronised when the poll gave up, when profiling, or when the periodic reap is due.
+// A record that has not arrived then is the error `missing`; the caller reads the records after this call's fence.
+// CBO_HIP_TRACE_SLOW=1: a call that takes more than a millisecond says on stderr where the time went (a value above 1 is
+// the threshold in microseconds instead).
+template <class Rec, class Launch>
+static int polled_launch(cbo_ctx *c, const char *name, const Rec *out, int n, const char *missing, Launch launch)
 {
-    if (++c->polled_launches < kPolledLaunchesPerSync) return false;
-    c->polled_launches = 0;
-    return true;
+    if (++c->small_seq == 0) c->small_seq = 1;
+    const int seq = c->small_seq;
+    static const bool trace_slow = std::getenv("CBO_HIP_TRACE_SLOW") != nullptr;
+    static const double trace_over_us = trace_slow && std::atof(std::getenv("CBO_HIP_TRACE_SLOW")) > 1.0
+                                            ? std::atof(std::getenv("CBO_HIP_TRACE_SLOW")) : 1000.0;
+    using clk = std::chrono::steady_clock;
+    const clk::time_point t_begin = trace_slow ? clk::now() : clk::time_point();
+    const int rc = launch(seq);
+    if (rc != CBO_OK) return rc;
+    const clk::time_point t_launched = trace_slow ? clk::now() : clk::time_point();
+    const bool all = poll_until([&] {
+        for (int j = 0; j < n; ++j)
+            if (*reinterpret_cast<const volatile int *>(&out[j].seq) != seq) return false;
+        return true;
+    }, kPollBudgetUs);
+    const clk::time_point t_polled = trace_slow ? clk::now() : clk::time_point();
+    const bool reap = ++c->polled_launches >= kPolledLaunchesPerSync;
+    if (reap) c->polled_launches = 0;
+    if (!all || c->profiling || reap) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (trace_slow) {
+        const clk::time_point t_end = clk::now();
+        auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+        if (us(t_begin, t_end) > trace_over_us)
+            std::fprintf(stderr, "[cbo] slow %s call #%d: launch %.1f us, poll %.1f us (%s), synchronise %.1f us (%s)\n",
+                         name, seq, us(t_begin, t_launched), us(t_launched, t_polled), all ? "records arrived" : "gave up",
+                         us(t_polled, t_end), !all ? "after the poll gave up" : reap ? "periodic reap" : "none");
+    }
+    for (int j = 0; j < n; ++j)
+        if (out[j].seq != seq) return fail(CBO_ERR_HIP, missing);
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return CBO_OK;
 }
 
 // the model half of a one-workgroup kernel's descriptor
@@ -1786,38 +1886,19 @@ static void fill_small_model(cbo_small_set &st, const cbo_gp *g)
     st.stage = nullptr; st.stage_ls = nullptr; st.raw = g->raw; st.pv = g->X.pv;
 }
 
+// descriptors, result records, status words and tickets for n_sets sets (at least 32), scratch and partial winners for
+// `blocks` workgroups per set
 static int ensure_small_buffers(cbo_ctx *c, int n_sets, int blocks)
 {
-    if (n_sets > c->sets_cap) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipHostFree(c->sets_host); hipHostFree(c->small_out); hipFree(c->small_info);
-        c->sets_host = nullptr; c->small_out = nullptr; c->small_info = nullptr;
-        c->sets_cap = 0;
-        const int cap = n_sets < 32 ? 32 : n_sets;
-        HIP_TRY(hipHostMalloc(&c->sets_host, sizeof(cbo_small_set) * cap));
-        HIP_TRY(hipHostMalloc(&c->small_out, sizeof(cbo_small_result) * cap));
-        HIP_TRY(hipMalloc(&c->small_info, sizeof(int) * 2 * cap));
-        HIP_TRY(hipMemset(c->small_info, 0, sizeof(int) * 2 * cap));
-        std::memset(c->small_out, 0, sizeof(cbo_small_result) * cap);
-        c->sets_cap = cap;
-    }
+    const size_t cap = n_sets < 32 ? 32 : (size_t)n_sets;
     const size_t scratch = small_sets_scratch_doubles(n_sets, blocks), parts = (size_t)n_sets * (size_t)blocks;
-    if (scratch > c->small_scratch_elems) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->small_scratch);
-        c->small_scratch = nullptr; c->small_scratch_elems = 0;
-        HIP_TRY(hipMalloc(&c->small_scratch, sizeof(double) * scratch));
-        c->small_scratch_elems = scratch;
-    }
-    if (parts > c->small_part_elems) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->small_part_val); hipFree(c->small_part_idx);
-        c->small_part_val = nullptr; c->small_part_idx = nullptr; c->small_part_elems = 0;
-        HIP_TRY(hipMalloc(&c->small_part_val, sizeof(double) * parts));
-        HIP_TRY(hipMalloc(&c->small_part_idx, sizeof(int64_t) * parts));
-        c->small_part_elems = parts;
-    }
-    return CBO_OK;
+    int rc = grow(c, c->sets_host, cap);
+    if (rc == CBO_OK) rc = grow(c, c->small_out, cap, true);
+    if (rc == CBO_OK) rc = grow(c, c->small_info, 2 * cap, true);
+    if (rc == CBO_OK) rc = grow(c, c->small_scratch, scratch);
+    if (rc == CBO_OK) rc = grow(c, c->small_part_val, parts);
+    if (rc == CBO_OK) rc = grow(c, c->small_part_idx, parts);
+    return rc;
 }
 
 // staged_set >= 0 (cbo_trial_step): that set's new data sit in the context's staging buffer, its model's host-side state
@@ -1876,44 +1957,14 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
             st.cost = costs[small[j]];
         }
         const int ns = (int)small.size();
-        if (++c->small_seq == 0) c->small_seq = 1;
-        const int seq = c->small_seq;
-        // CBO_HIP_TRACE_SLOW=1: a call that takes more than a millisecond says on stderr where the time went
-        // (a value above 1 is the threshold in microseconds instead)
-        static const bool trace_slow = std::getenv("CBO_HIP_TRACE_SLOW") != nullptr;
-        static const double trace_over_us = trace_slow && std::atof(std::getenv("CBO_HIP_TRACE_SLOW")) > 1.0
-                                                ? std::atof(std::getenv("CBO_HIP_TRACE_SLOW")) : 1000.0;
-        using clk = std::chrono::steady_clock;
-        const clk::time_point t_begin = trace_slow ? clk::now() : clk::time_point();
-        clk::time_point t_launched, t_polled;
-        launch_small_sets(c->stream, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val, c->small_part_idx,
-                          c->small_info, c->small_info + c->sets_cap, c->small_out, seq);
-        HIP_TRY(hipGetLastError());
-        if (trace_slow) t_launched = clk::now();
-        // the result records arrive in pinned memory, each closed by the call's sequence number: poll them (kPollBudgetUs),
-        // then let the runtime wait (jobs that really take that long)
-        {
-            const bool all = poll_until([&] {
-                for (int j = 0; j < ns; ++j)
-                    if (*reinterpret_cast<volatile int *>(&c->small_out[j].seq) != seq) return false;
-                return true;
-            }, kPollBudgetUs);
-            if (trace_slow) t_polled = clk::now();
-            const bool reap = polled_launch_needs_sync(c);
-            if (!all || c->profiling || reap) HIP_TRY(hipStreamSynchronize(c->stream));
-            if (trace_slow) {
-                const clk::time_point t_end = clk::now();
-                auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-                if (us(t_begin, t_end) > trace_over_us)
-                    std::fprintf(stderr, "[cbo] slow cbo_acq_sweep_sets call #%d: launch %.1f us, poll %.1f us (%s), "
-                                 "synchronise %.1f us (%s)\n", seq, us(t_begin, t_launched), us(t_launched, t_polled),
-                                 all ? "records arrived" : "gave up", us(t_polled, t_end),
-                                 !all ? "after the poll gave up" : reap ? "periodic reap" : "none");
-            }
-            for (int j = 0; j < ns; ++j)
-                if (c->small_out[j].seq != seq) return fail(CBO_ERR_HIP, "multi-set sweep: no result record");
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
+        auto launch = [&](int seq) -> int {
+            launch_small_sets(c->stream, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val, c->small_part_idx,
+                              c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq);
+            HIP_TRY(hipGetLastError());
+            return CBO_OK;
+        };
+        rc = polled_launch(c, "cbo_acq_sweep_sets", c->small_out.p, ns, "multi-set sweep: no result record", launch);
+        if (rc != CBO_OK) return rc;
         for (int j = 0; j < ns; ++j) {
             if (c->small_out[j].info != 0) continue;        // not positive definite as assembled: the jitchol ladder below
             best_vals[small[(size_t)j]] = c->small_out[j].best_val;
@@ -1948,8 +1999,6 @@ extern "C" int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *
     if (n_sets <= 0 || !gps || !chosen_out) return fail(CBO_ERR_INVALID, "bad argument");
     if (refit_set >= n_sets) return fail(CBO_ERR_INVALID, "refit_set out of range");
     int staged = -1;
-    int64_t prev_n = 0;
-    bool prev_fitted = false;
     if (refit_set >= 0) {
         cbo_gp *g = gps[refit_set];
         if (!g) return fail(CBO_ERR_INVALID, "gp is NULL");
@@ -1975,18 +2024,8 @@ extern "C" int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *
         }
         if (fuse) {
             HIP_TRY(hipSetDevice(c->device));
-            if (c->stage_pending) { HIP_TRY(hipEventSynchronize(c->stage_done)); c->stage_pending = false; }
-            double *sb = c->stage;
-            std::memcpy(sb, X, sizeof(double) * n * g->d);
-            std::memcpy(sb + n * g->d, y, sizeof(double) * n);
-            g->h_pv.clear();
-            if (pv) {
-                std::memcpy(sb + n * g->d + n, pm, sizeof(double) * n);
-                std::memcpy(sb + n * g->d + 2 * n, pv, sizeof(double) * n);
-                g->h_pv.assign(pv, pv + n);
-            }
-            prev_n = g->n;
-            prev_fitted = g->fitted;
+            const int rc = stage_data(g, n, X, y, pm, pv);
+            if (rc != CBO_OK) return rc;
             g->n = n;
             g->X.n = n;
             g->fitted = false;
@@ -2008,8 +2047,6 @@ extern "C" int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *
             g->n = 0;
             g->X.n = 0;
             g->fitted = false;
-            (void)prev_n;
-            (void)prev_fitted;
         }
         return rc;
     }
@@ -2067,19 +2104,12 @@ extern "C" int cbo_acq_sweep_host(cbo_gp *g, int64_t m, const double *Xs, const 
     return cbo_acq_sweep(g, k, y_best, task, ei_jitter, cost, acq_out, nullptr, nullptr, best_val, best_idx);
 }
 
-// posterior mean / variance of m host points into the context's mean / var vectors (device), via the scratch set
-// (f64_solution: an fp32 model solves on its fp64 factor too, leaving V = L^-1 K* in the fp64 workspace)
-static int posterior_of_host_points(cbo_gp *g, int64_t m, const double *Xs, const double *pm, const double *pv,
-                                    int include_noise, cbo_cands **k_out, bool f64_solution = false)
+// the posterior mean / variance of the first m points of k from q, mu into the context's mean / var vectors (device):
+// acq_kernel without EI
+static int enqueue_mean_var(cbo_gp *g, const cbo_cands *k, int64_t m, int include_noise)
 {
-    const bool causal = g->X.sv != nullptr;
-    if (causal && (!pm || !pv)) return fail(CBO_ERR_INVALID, "causal gp needs candidate prior mean/variance");
     cbo_ctx *c = g->ctx;
-    cbo_cands *k = nullptr;
-    int rc = scratch_cands(c, m, g->d, Xs, causal ? pm : nullptr, causal ? pv : nullptr, &k);
-    if (rc != CBO_OK) return rc;
-    rc = enqueue_posterior(g, k, f64_solution);
-    if (rc != CBO_OK) return rc;
+    const bool causal = g->X.sv != nullptr;
     AcqParams p;
     p.variance = g->h.variance; p.noise_var = g->noise_var; p.y_best = 0.0; p.ei_jitter = 0.0; p.cost = 1.0;
     p.task = CBO_TASK_MIN; p.include_noise = include_noise ? 1 : 0; p.want_ei = 0;
@@ -2089,7 +2119,38 @@ static int posterior_of_host_points(cbo_gp *g, int64_t m, const double *Xs, cons
                    nullptr, c->part_val, c->part_idx, 0, acq_blocks_for(m));
     }
     HIP_TRY(hipGetLastError());
-    *k_out = k;
+    return CBO_OK;
+}
+
+// posterior mean / variance of a prepared candidate set into the context's mean / var vectors
+// (f64_solution: an fp32 model solves on its fp64 factor too, leaving V = L^-1 K* in the fp64 workspace)
+static int posterior_of_set(cbo_gp *g, cbo_cands *k, int include_noise, bool f64_solution = false)
+{
+    const int rc = enqueue_posterior(g, k, f64_solution);
+    if (rc != CBO_OK) return rc;
+    return enqueue_mean_var(g, k, k->m, include_noise);
+}
+
+// the same for m host points, uploaded to the scratch set
+static int posterior_of_host_points(cbo_gp *g, int64_t m, const double *Xs, const double *pm, const double *pv,
+                                    int include_noise, cbo_cands **k_out, bool f64_solution = false)
+{
+    if (g->X.sv != nullptr && (!pm || !pv)) return fail(CBO_ERR_INVALID, "causal gp needs candidate prior mean/variance");
+    int rc = scratch_points(g, m, Xs, pm, pv, k_out);
+    if (rc != CBO_OK) return rc;
+    return posterior_of_set(g, *k_out, include_noise, f64_solution);
+}
+
+// group means of the context's mean / var vectors (n_groups groups of `group` consecutive points) into the (now free)
+// q / mu vectors, and to the caller
+static int group_means_out(cbo_ctx *c, int64_t n_groups, int64_t group, double *mean_out, double *var_out)
+{
+    launch_group_mean(c->stream, c->mean, n_groups, group, c->q);
+    launch_group_mean(c->stream, c->var, n_groups, group, c->mu);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(mean_out, c->q, sizeof(double) * n_groups, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(var_out, c->mu, sizeof(double) * n_groups, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return CBO_OK;
 }
 
@@ -2102,8 +2163,8 @@ extern "C" int cbo_gp_predict(cbo_gp *g, int64_t m, const double *Xs, const doub
     cbo_cands *k = nullptr;
     int rc = posterior_of_host_points(g, m, Xs, pm, pv, include_noise, &k);
     if (rc != CBO_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(mean_out, c->mean, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(var_out, c->var, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+    rc = copy_posterior_out(c, k, nullptr, mean_out, var_out);
+    if (rc != CBO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->profiling) c->timers.n_sweep += 1;
     return CBO_OK;
@@ -2130,8 +2191,8 @@ extern "C" int cbo_gp_mes_gumbel(cbo_gp *g, int64_t m, const double *Xg, const d
     int64_t status[3];
     HIP_TRY(hipMemcpyAsync(out, c->part_val, sizeof(out), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(status, c->part_idx, sizeof(status), hipMemcpyDeviceToHost, c->stream));
-    if (mean_out) HIP_TRY(hipMemcpyAsync(mean_out, c->mean, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
-    if (var_out) HIP_TRY(hipMemcpyAsync(var_out, c->var, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+    rc = copy_posterior_out(c, k, nullptr, mean_out, var_out);
+    if (rc != CBO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int j = 0; j < 3; ++j) {
         char msg[160];
@@ -2204,11 +2265,10 @@ extern "C" int cbo_gp_predict_cov(cbo_gp *g, int64_t m, const double *Xs, const 
     int64_t ldv = 0;
     int rc = resident_solution_ld(g, round_up(m, kStrip), &ldv);
     if (rc != CBO_OK) return rc;
-    rc = grow_buffer(c, &c->cov, &c->cov_elems, (size_t)m * (size_t)m);
-    if (rc != CBO_OK) return rc;
-    // without mean_out the prior mean is not needed: the epilogue's mean (discarded) is formed from pv in its place
+    rc = grow(c, c->cov, (size_t)m * (size_t)m);
     cbo_cands *k = nullptr;
-    rc = posterior_of_host_points(g, m, Xs, (causal && !pm) ? pv : pm, pv, 0, &k, true);
+    if (rc == CBO_OK) rc = scratch_points(g, m, Xs, pm, pv, &k);
+    if (rc == CBO_OK) rc = posterior_of_set(g, k, 0, true);
     if (rc != CBO_OK) return rc;
     enqueue_cov(g, k, ldv, 0, m, 0, m, true, include_noise ? g->noise_var : 0.0);
     HIP_TRY(hipGetLastError());
@@ -2229,27 +2289,13 @@ extern "C" int cbo_gp_cov_between(cbo_gp *g, int64_t m1, const double *X1, const
     cbo_ctx *c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
     // one candidate set [X1 | filler | X2] with X2 starting on a strip boundary: one solve gives V1 and V2 side by side
-    const int d = g->d;
-    const int64_t off = round_up(m1, kStrip), mt = off + m2;
+    const int64_t off = round_up(m1, kStrip);
     int64_t ldv = 0;
-    int rc = resident_solution_ld(g, round_up(mt, kStrip), &ldv);
-    if (rc != CBO_OK) return rc;
-    rc = grow_buffer(c, &c->cov, &c->cov_elems, (size_t)m1 * (size_t)m2);
-    if (rc != CBO_OK) return rc;
-    std::vector<double> xs((size_t)mt * d), vs(causal ? (size_t)mt : 0);
-    std::memcpy(xs.data(), X1, sizeof(double) * (size_t)m1 * d);
-    for (int64_t i = m1; i < off; ++i) std::memcpy(&xs[(size_t)i * d], X1, sizeof(double) * d);   // filler: unused columns
-    std::memcpy(&xs[(size_t)off * d], X2, sizeof(double) * (size_t)m2 * d);
-    if (causal) {
-        std::memcpy(vs.data(), pv1, sizeof(double) * (size_t)m1);
-        for (int64_t i = m1; i < off; ++i) vs[(size_t)i] = pv1[0];
-        std::memcpy(&vs[(size_t)off], pv2, sizeof(double) * (size_t)m2);
-    }
-    // (no mean is formed: the prior variance also stands in for the prior mean the candidate set wants with it)
+    int rc = resident_solution_ld(g, round_up(off + m2, kStrip), &ldv);
+    if (rc == CBO_OK) rc = grow(c, c->cov, (size_t)m1 * (size_t)m2);
     cbo_cands *k = nullptr;
-    rc = scratch_cands(c, mt, d, xs.data(), causal ? vs.data() : nullptr, causal ? vs.data() : nullptr, &k);
-    if (rc != CBO_OK) return rc;
-    rc = enqueue_posterior(g, k, true);
+    if (rc == CBO_OK) rc = scratch_pair(g, m1, X1, pv1, m2, X2, pv2, kStrip, &k);
+    if (rc == CBO_OK) rc = enqueue_posterior(g, k, true);
     if (rc != CBO_OK) return rc;
     enqueue_cov(g, k, ldv, 0, m1, off, m2, false, 0.0);
     HIP_TRY(hipGetLastError());
@@ -2281,12 +2327,12 @@ extern "C" int cbo_gp_posterior_samples(cbo_gp *g, int64_t m, const double *Xs, 
     const int64_t ldz = round_up(s, kPadN) + kLdExtra;
     int64_t ldv = 0;
     int rc = resident_solution_ld(g, round_up(m, kStrip), &ldv);
-    if (rc == CBO_OK) rc = grow_buffer(c, &c->samp_A, &c->samp_A_elems, (size_t)m_pad * (size_t)lda);
-    if (rc == CBO_OK) rc = grow_buffer(c, &c->samp_invDt, &c->samp_invDt_elems, (size_t)(m_pad / 16) * 256);
-    if (rc == CBO_OK) rc = grow_buffer(c, &c->samp_Z, &c->samp_Z_elems, (size_t)m_pad * (size_t)ldz);
-    if (rc == CBO_OK) rc = grow_buffer(c, &c->samp_out, &c->samp_out_elems, (size_t)m * (size_t)s);
+    if (rc == CBO_OK) rc = grow(c, c->samp_A, (size_t)m_pad * (size_t)lda);
+    if (rc == CBO_OK) rc = grow(c, c->samp_invDt, (size_t)(m_pad / 16) * 256);
+    if (rc == CBO_OK) rc = grow(c, c->samp_Z, (size_t)m_pad * (size_t)ldz);
+    if (rc == CBO_OK) rc = grow(c, c->samp_out, (size_t)m * (size_t)s);
+    if (rc == CBO_OK) rc = grow(c, c->samp_info, 1 + kCholFlagSlots);
     if (rc != CBO_OK) return rc;
-    if (!c->samp_info) HIP_TRY(hipMalloc(&c->samp_info, sizeof(int) * (1 + kCholFlagSlots)));
     // the ladder's base: 1e-6 mean(Kdiag(X*)), the prior diagonal variance + v(x) (summed in extended precision)
     long double kdiag = 0.0L;
     for (int64_t i = 0; i < m; ++i) kdiag += (long double)(g->h.variance + (causal ? pv[i] : 0.0));
@@ -2352,41 +2398,22 @@ extern "C" int cbo_gp_integrated_variance_reduction(cbo_gp *g, int64_t m, const 
     cbo_ctx *c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const int d = g->d;
-    const int64_t mc = round_up(m, kStrip), off = round_up(m, kJointTile), mt = off + p;
+    const int64_t mc = round_up(m, kStrip), off = round_up(m, kJointTile);
     int64_t chunk = 0, ldv = 0;
-    // (a failed allocation stays behind for hipGetLastError: it is cleared, or the next call's launch check reports it)
     int rc = ensure_workspaces(c, g->n_pad, off + round_up(p, kJointTile), &chunk, &ldv);
-    if (rc != CBO_OK) { (void)hipGetLastError(); return rc; }
+    if (rc != CBO_OK) return rc;
     if (chunk < off + kJointTile)
         return fail(CBO_ERR_INVALID, "too many candidates: their solution L^-1 K* and one tile of integration points do "
                                      "not fit the workspace");
     const int64_t pc = (chunk - off) / kJointTile * kJointTile;     // integration points per chunk
     const int64_t tiles = (p + kJointTile - 1) / kJointTile;
-    rc = grow_buffer(c, &c->ivr_part, &c->ivr_part_elems, (size_t)m * (size_t)tiles);
-    if (rc != CBO_OK) { (void)hipGetLastError(); return rc; }
-    std::vector<double> xs((size_t)mt * d), vs(causal ? (size_t)mt : 0);
-    std::memcpy(xs.data(), Xs, sizeof(double) * (size_t)m * d);
-    for (int64_t i = m; i < off; ++i) std::memcpy(&xs[(size_t)i * d], Xs, sizeof(double) * d);   // filler: never read
-    std::memcpy(&xs[(size_t)off * d], Xint, sizeof(double) * (size_t)p * d);
-    if (causal) {
-        std::memcpy(vs.data(), pv_s, sizeof(double) * (size_t)m);
-        for (int64_t i = m; i < off; ++i) vs[(size_t)i] = pv_s[0];
-        std::memcpy(&vs[(size_t)off], pv_int, sizeof(double) * (size_t)p);
-    }
-    // (the prior variance stands in for the prior mean: the mean acq_kernel forms on the way is not used)
+    rc = grow(c, c->ivr_part, (size_t)m * (size_t)tiles);
     cbo_cands *k = nullptr;
-    rc = scratch_cands(c, mt, d, xs.data(), causal ? vs.data() : nullptr, causal ? vs.data() : nullptr, &k);
+    if (rc == CBO_OK) rc = scratch_pair(g, m, Xs, pv_s, p, Xint, pv_int, kJointTile, &k);
     if (rc == CBO_OK) rc = prepare_cands(g, k);
     if (rc == CBO_OK) rc = solve_columns(g, k, 0, mc, c->V, ldv, c->q, c->mu);
+    if (rc == CBO_OK) rc = enqueue_mean_var(g, k, m, 1);
     if (rc != CBO_OK) return rc;
-    AcqParams pr;
-    pr.variance = g->h.variance; pr.noise_var = g->noise_var; pr.y_best = 0.0; pr.ei_jitter = 0.0; pr.cost = 1.0;
-    pr.task = CBO_TASK_MIN; pr.include_noise = 1; pr.want_ei = 0;
-    {
-        PhaseScope ps(c, PH_ACQ);
-        launch_acq(c->stream, c->q, c->mu, causal ? k->pm : nullptr, causal ? k->pv : nullptr, m, pr, nullptr, c->var,
-                   nullptr, c->part_val, c->part_idx, 0, acq_blocks_for(m));
-    }
     IvrArgs a;
     a.Vc = c->V; a.Vi = c->V + off; a.ldv = ldv;
     a.c_cols = mc;
@@ -2504,24 +2531,18 @@ static int small_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out
     if (!small_lml_eligible(g)) return 0;
     int rc = ensure_small_buffers(c, 1, 2);            // scratch of two workgroup slots >= factor + L^-1
     if (rc != CBO_OK) return rc;
-    if (!c->lml_out) {
-        if (hipHostMalloc(&c->lml_out, sizeof(cbo_small_lml_result)) != hipSuccess) return fail(CBO_ERR_HIP, "hipHostMalloc");
-        std::memset(c->lml_out, 0, sizeof(cbo_small_lml_result));
-    }
+    rc = grow(c, c->lml_out, 1, true);
+    if (rc != CBO_OK) return rc;
     cbo_small_set st{};
     fill_small_model(st, g);
-    if (++c->small_seq == 0) c->small_seq = 1;
-    const int seq = c->small_seq;
-    launch_small_lml(c->stream, st, c->small_scratch, c->small_info, c->lml_out, seq);
-    if (hipGetLastError() != hipSuccess) return fail(CBO_ERR_HIP, "small_lml_kernel launch");
-    const bool ready = poll_until([&] { return *reinterpret_cast<volatile int *>(&c->lml_out->seq) == seq; }, kPollBudgetUs);
-    if (!ready || c->profiling || polled_launch_needs_sync(c)) {
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(CBO_ERR_HIP, "hipStreamSynchronize");
-        if (c->lml_out->seq != seq) return fail(CBO_ERR_HIP, "likelihood kernel: no result record");
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (c->lml_out->info != 0) return 0;
-    const double *t = c->lml_out->terms;
+    auto launch = [&](int seq) -> int {
+        launch_small_lml(c->stream, st, c->small_scratch, c->small_info, c->lml_out, seq);
+        return hipGetLastError() != hipSuccess ? fail(CBO_ERR_HIP, "small_lml_kernel launch") : CBO_OK;
+    };
+    rc = polled_launch(c, "cbo_gp_lml_gradients", c->lml_out.p, 1, "likelihood kernel: no result record", launch);
+    if (rc != CBO_OK) return rc;
+    if (c->lml_out.p->info != 0) return 0;
+    const double *t = c->lml_out.p->terms;
     lml_outputs(g, t, t[1 + CBO_MAX_DIM], t[1 + CBO_MAX_DIM + 1], t[1 + CBO_MAX_DIM + 2], t[1 + CBO_MAX_DIM + 3], lml_out,
                 dvariance_out, dlengthscale_out, dnoise_out);
     return 1;
@@ -2573,38 +2594,22 @@ extern "C" int cbo_gp_lml_gradients_batch(int n_models, cbo_gp *const *gps, doub
         const int blocks = (int)((stride + per_block - 1) / per_block);
         int rc = ensure_small_buffers(c, ns, blocks);
         if (rc != CBO_OK) return rc;
-        if ((size_t)ns * stride > c->small_scratch_elems)
+        if ((size_t)ns * stride > c->small_scratch.cap)
             return fail(CBO_ERR_INVALID, "likelihood batch: scratch smaller than expected");
-        if (ns > c->lml_batch_cap) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            hipHostFree(c->lml_batch_out);
-            c->lml_batch_out = nullptr; c->lml_batch_cap = 0;
-            const int cap = ns < 32 ? 32 : ns;
-            HIP_TRY(hipHostMalloc(&c->lml_batch_out, sizeof(cbo_small_lml_result) * cap));
-            std::memset(c->lml_batch_out, 0, sizeof(cbo_small_lml_result) * cap);
-            c->lml_batch_cap = cap;
-        }
+        rc = grow(c, c->lml_batch_out, ns < 32 ? 32 : (size_t)ns, true);
+        if (rc != CBO_OK) return rc;
         for (int j = 0; j < ns; ++j) {
             cbo_small_set st{};
             fill_small_model(st, gps[small[(size_t)j]]);
             c->sets_host[j] = st;
         }
-        if (++c->small_seq == 0) c->small_seq = 1;
-        const int seq = c->small_seq;
         cbo_small_lml_result *out = c->lml_batch_out;
-        launch_small_lml_batch(c->stream, c->sets_host, ns, c->small_scratch, (int64_t)stride, c->small_info, out, seq);
-        if (hipGetLastError() != hipSuccess) return fail(CBO_ERR_HIP, "small_lml_batch_kernel launch");
-        const bool ready = poll_until([&] {
-            for (int j = 0; j < ns; ++j)
-                if (*reinterpret_cast<volatile int *>(&out[j].seq) != seq) return false;
-            return true;
-        }, kPollBudgetUs);
-        if (!ready || c->profiling || polled_launch_needs_sync(c)) {
-            if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(CBO_ERR_HIP, "hipStreamSynchronize");
-            for (int j = 0; j < ns; ++j)
-                if (out[j].seq != seq) return fail(CBO_ERR_HIP, "likelihood batch kernel: no result record");
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
+        auto launch = [&](int seq) -> int {
+            launch_small_lml_batch(c->stream, c->sets_host, ns, c->small_scratch, (int64_t)stride, c->small_info, out, seq);
+            return hipGetLastError() != hipSuccess ? fail(CBO_ERR_HIP, "small_lml_batch_kernel launch") : CBO_OK;
+        };
+        rc = polled_launch(c, "cbo_gp_lml_gradients_batch", out, ns, "likelihood batch kernel: no result record", launch);
+        if (rc != CBO_OK) return rc;
         for (int j = 0; j < ns; ++j) {
             const int i = small[(size_t)j];
             if (out[j].info != 0) { rest.push_back(i); continue; }
@@ -2643,16 +2648,9 @@ static int general_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_o
     if (chunk < n_pad) return fail(CBO_ERR_UNSUPPORTED, "likelihood gradients need an n_pad x n_pad workspace (raise CBO_HIP_WORKSPACE_MB)");
     const int64_t ldw = n_pad + kLdExtra;
     const size_t w_bytes = sizeof(double) * (size_t)n_pad * (size_t)ldw;
-    const size_t part_elems = (size_t)lml_grad_tiles(n_pad) * (size_t)(1 + g->d);
-    if (w_bytes > c->W_bytes || part_elems > c->gpart_elems) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        hipFree(c->W); hipFree(c->gpart);
-        c->W = nullptr; c->gpart = nullptr; c->W_bytes = 0; c->gpart_elems = 0;
-        HIP_TRY(hipMalloc(&c->W, w_bytes));
-        c->W_bytes = w_bytes;
-        HIP_TRY(hipMalloc(&c->gpart, sizeof(double) * part_elems));
-        c->gpart_elems = part_elems;
-    }
+    rc = grow(c, c->W, (size_t)n_pad * (size_t)ldw);
+    if (rc == CBO_OK) rc = grow(c, c->gpart, (size_t)lml_grad_tiles(n_pad) * (size_t)(1 + g->d));
+    if (rc != CBO_OK) return rc;
     // V = L^-1 (identity right-hand sides), q_j = (Ky^-1)_jj
     launch_set_identity(c->stream, c->V, ldv, n_pad);
     if (prefer_right_looking(c, n_pad, n_pad)) {
@@ -2713,9 +2711,9 @@ extern "C" int cbo_gp_predict_gradients(cbo_gp *g, int64_t m, const double *Xs, 
     HIP_TRY(hipSetDevice(c->device));
     const bool causal = g->X.sv != nullptr;
     if (causal && !pv_s) return fail(CBO_ERR_INVALID, "causal gp needs the prior variance at the prediction points");
-    // the prior mean does not enter the gradients (GPy ignores the mean function there): the variances stand in
+    // (the prior mean does not enter the gradients: GPy ignores the mean function there)
     cbo_cands *k = nullptr;
-    int rc = scratch_cands(c, m, g->d, Xs, causal ? pv_s : nullptr, causal ? pv_s : nullptr, &k);
+    int rc = scratch_points(g, m, Xs, nullptr, pv_s, &k);
     if (rc != CBO_OK) return rc;
     rc = prepare_cands(g, k);
     if (rc == CBO_OK) rc = ensure_alpha(g);
@@ -2728,24 +2726,10 @@ extern "C" int cbo_gp_predict_gradients(cbo_gp *g, int64_t m, const double *Xs, 
     rc = ensure_workspaces(c, g->n_pad, k->m_pad, &chunk, &ldv);
     c->max_ws_bytes = saved_cap;
     if (rc != CBO_OK) return rc;
-    const size_t w_bytes = sizeof(double) * (size_t)g->n_pad * (size_t)ldv;
-    const size_t grad_elems = 2 * (size_t)k->m_pad * (size_t)g->d;
-    if (w_bytes > c->W_bytes || grad_elems > c->grads_elems || (g->h.ard && !g->inv_ls_dev)) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (w_bytes > c->W_bytes) {
-            hipFree(c->W);
-            c->W = nullptr; c->W_bytes = 0;
-            HIP_TRY(hipMalloc(&c->W, w_bytes));
-            c->W_bytes = w_bytes;
-        }
-        if (grad_elems > c->grads_elems) {
-            hipFree(c->grads);
-            c->grads = nullptr; c->grads_elems = 0;
-            HIP_TRY(hipMalloc(&c->grads, sizeof(double) * grad_elems));
-            c->grads_elems = grad_elems;
-        }
-        if (g->h.ard && !g->inv_ls_dev) HIP_TRY(hipMalloc(&g->inv_ls_dev, sizeof(double) * CBO_MAX_DIM));
-    }
+    rc = grow(c, c->W, (size_t)g->n_pad * (size_t)ldv);
+    if (rc == CBO_OK) rc = grow(c, c->grads, 2 * (size_t)k->m_pad * (size_t)g->d);
+    if (rc != CBO_OK) return rc;
+    if (g->h.ard && !g->inv_ls_dev) HIP_TRY(hipMalloc(&g->inv_ls_dev, sizeof(double) * CBO_MAX_DIM));
     if (g->h.ard) {
         double il[CBO_MAX_DIM] = {0};
         for (int i = 0; i < g->d; ++i) il[i] = 1.0 / g->ls[(size_t)i];
@@ -2780,14 +2764,7 @@ extern "C" int cbo_gp_predict_grouped(cbo_gp *g, int64_t m_groups, int64_t group
     cbo_cands *k = nullptr;
     int rc = posterior_of_host_points(g, m, Xs, pm, pv, include_noise, &k);
     if (rc != CBO_OK) return rc;
-    // group means into the (now free) q / mu vectors
-    launch_group_mean(c->stream, c->mean, m_groups, group, c->q);
-    launch_group_mean(c->stream, c->var, m_groups, group, c->mu);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(mean_out, c->q, sizeof(double) * m_groups, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(var_out, c->mu, sizeof(double) * m_groups, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return CBO_OK;
+    return group_means_out(c, m_groups, group, mean_out, var_out);
 }
 
 // Do-calculus prior of a batch of candidate interventions, inputs built on the device (SURVEY.md §8 f1;
@@ -2807,42 +2784,25 @@ extern "C" int cbo_gp_predict_do(cbo_gp *g, int64_t m, int64_t n_obs, const doub
     cbo_ctx *c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const int64_t total = m * n_obs;
-    if (!c->scratch_k) { c->scratch_k = new cbo_cands(); c->scratch_k->ctx = c; }
-    cbo_cands *k = c->scratch_k;
+    cbo_cands *k = scratch_set(c);
     int rc = cands_reserve(k, total, g->d, false);
     if (rc != CBO_OK) return rc;
     // staging for observed | values | iv_index: the export scratch (device), filled by three small copies
     const size_t need = (size_t)(n_obs * g->d) + (size_t)(m * n_iv) + CBO_MAX_DIM;
-    rc = grow_buffer(c, &c->export_buf, &c->export_elems, need);
+    rc = grow(c, c->export_buf, need);
     if (rc != CBO_OK) return rc;
     double *d_obs = c->export_buf, *d_val = d_obs + n_obs * g->d;
     int *d_idx = reinterpret_cast<int *>(d_val + m * n_iv);
     HIP_TRY(hipMemcpyAsync(d_obs, observed, sizeof(double) * n_obs * g->d, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_val, values, sizeof(double) * m * n_iv, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_idx, iv_index, sizeof(int) * g->d, hipMemcpyHostToDevice, c->stream));
-    k->m = total; k->d = g->d; k->index_offset = 0;
-    k->m_pad = round_up(total, kStrip);
-    k->P.n = total; k->P.ld = k->m_pad; k->P.d = g->d;
-    k->has_prior = false;
-    k->prepared_for = nullptr; k->prepared_ls.clear();
-    k->fit_stamp = 0; k->v_stamp = 0;
+    cands_describe(k, total, g->d, false, 0);
     launch_expand_interventions(c->stream, d_obs, n_obs, g->d, d_val, n_iv, d_idx, m, k->raw);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));               // the host buffers are the caller's
-    rc = enqueue_posterior(g, k);
+    rc = posterior_of_set(g, k, include_noise);
     if (rc != CBO_OK) return rc;
-    AcqParams p;
-    p.variance = g->h.variance; p.noise_var = g->noise_var; p.y_best = 0.0; p.ei_jitter = 0.0; p.cost = 1.0;
-    p.task = CBO_TASK_MIN; p.include_noise = include_noise ? 1 : 0; p.want_ei = 0;
-    launch_acq(c->stream, c->q, c->mu, nullptr, nullptr, total, p, c->mean, c->var, nullptr, c->part_val, c->part_idx, 0,
-               acq_blocks_for(total));
-    launch_group_mean(c->stream, c->mean, m, n_obs, c->q);
-    launch_group_mean(c->stream, c->var, m, n_obs, c->mu);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(mean_out, c->q, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(var_out, c->mu, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return CBO_OK;
+    return group_means_out(c, m, n_obs, mean_out, var_out);
 }
 
 // ---- tiny host-side reductions -------------------------------------------------------------------

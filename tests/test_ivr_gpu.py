@@ -267,6 +267,23 @@ def test_failed_workspace_allocation_is_a_hip_error(lib, monkeypatch):
     ctx.close()
 
 
+def test_failed_output_allocation_leaves_the_context_usable(lib):
+    """cbo_gp_predict_cov with an m x m output larger than the device's memory (2^18 points at n = 4096: 512 GiB) returns
+    CBO_ERR_HIP before it writes the caller's buffers, and the next call on the same context succeeds."""
+    from cbo_with_oop_amd import _lib
+    ctx = _lib.Context(0)
+    X, y, Xc, _ = random_problem(4096, 64, 1, d=1, seed=13)
+    g = model(X, y, noise_var=1e-2, context=ctx)
+    P = _lib.dptr
+    big, cov = np.zeros((1 << 18, 1)), np.empty(1)
+    assert g._lib.cbo_gp_predict_cov(g._handle, 1 << 18, P(big), None, None, 1, None, P(cov)) == lib.CBO_ERR_HIP
+    mean, cov = np.empty(64), np.empty((64, 64))
+    assert g._lib.cbo_gp_predict_cov(g._handle, 64, P(Xc), None, None, 1, P(mean), P(cov)) == lib.CBO_OK
+    assert np.all(np.isfinite(mean)) and np.all(np.isfinite(cov)) and np.array_equal(cov, cov.T)
+    g.close()
+    ctx.close()
+
+
 def test_full_size_on_sampled_candidates(lib):
     n, m, p = 4096, 8192, 16384
     X, y, Xc, Xint = random_problem(n, m, p, seed=7)
