@@ -19,7 +19,6 @@ c_int_p = ctypes.POINTER(ctypes.c_int)
 c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 
 ABI_VERSION = 5          # include/cbo_hip.h: CBO_HIP_ABI_VERSION
-ABI_DIAG_BASE = 1000     # CBO_HIP_ABI_DIAG_BASE: timing-only builds report ABI_DIAG_BASE + version
 MAX_DIM = 8              # CBO_MAX_DIM
 CBO_OK = 0
 CBO_ERR_INVALID = -1
@@ -182,11 +181,7 @@ def load():
                 fn.restype = restype
                 fn.argtypes = argtypes
             version = lib.cbo_abi_version()
-            if version >= ABI_DIAG_BASE and os.environ.get("CBO_HIP_ALLOW_DIAG") != "1":
-                raise ImportError(
-                    f"{LIB_PATH} is a timing-only diagnostic build (cbo_abi_version() = {version}): its results may be "
-                    f"wrong by construction.  Measurement scripts opt in with CBO_HIP_ALLOW_DIAG=1.")
-            if version % ABI_DIAG_BASE != ABI_VERSION:
+            if version != ABI_VERSION:
                 raise ImportError(f"{LIB_PATH} has ABI version {version}, this package binds version {ABI_VERSION}: "
                                   f"rebuild it (`make -C cbo_with_oop_amd/csrc`)")
             _lib = lib

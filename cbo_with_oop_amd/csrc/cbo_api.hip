@@ -298,14 +298,7 @@ static void resolve_events(cbo_ctx *c)
 // ---- context -------------------------------------------------------------------------------------
 static void destroy_ctx(cbo_ctx *c);
 
-extern "C" int cbo_abi_version(void)
-{
-#ifdef CBO_DIAG_KNOBS
-    return CBO_HIP_ABI_DIAG_BASE + CBO_HIP_ABI_VERSION;
-#else
-    return (f32_debug_mask() != 0 ? CBO_HIP_ABI_DIAG_BASE : 0) + CBO_HIP_ABI_VERSION;
-#endif
-}
+extern "C" int cbo_abi_version(void) { return CBO_HIP_ABI_VERSION; }
 extern "C" const char *cbo_last_error(void) { return g_err.c_str(); }
 
 extern "C" int cbo_device_count(int *count_out)
@@ -346,18 +339,17 @@ extern "C" int cbo_init(int device_id, cbo_ctx **out)
         e = hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, (prio_low + prio_high) / 2);
     // The sweep streams leave a few CUs per XCD to the factorisation: its diagonal-block kernel needs a whole
     // CU's LDS and would otherwise wait behind a queue of half-LDS sweep workgroups that keep every CU partly
-    // occupied.  CU-mask bit b is CU b/8 of XCD b%8 on this device (scripts/probes/cumask_probe.hip).
+    // occupied.  CU-mask bit b is CU b/8 of XCD b%8 on this device (scripts/probes/cumask_probe.hip).  Four CUs per XCD
+    // measured best of 2-10 (profiles/r04_reserve_scan.txt).
     if (e == hipSuccess) {
-        int reserve = 4;
-        const char *rv = std::getenv("CBO_HIP_PIPE_RESERVE");
-        if (rv) reserve = std::atoi(rv);
+        constexpr int reserve = 4;
         const int n_cu = prop.multiProcessorCount;
         std::vector<uint32_t> mask((size_t)(n_cu + 31) / 32, 0u);
         for (int b = 0; b < n_cu; ++b)
             if (b / 8 >= reserve) mask[(size_t)b / 32] |= 1u << (b % 32);
         bool masked = false;
         c->n_cu_pipe = n_cu;
-        if (reserve > 0 && reserve * 8 < n_cu) {
+        if (reserve * 8 < n_cu) {
             masked = hipExtStreamCreateWithCUMask(&c->sweep_stream, (uint32_t)mask.size(), mask.data()) == hipSuccess &&
                      hipExtStreamCreateWithCUMask(&c->bulk_stream, (uint32_t)mask.size(), mask.data()) == hipSuccess;
             if (masked) c->n_cu_pipe = n_cu - reserve * 8;
@@ -460,43 +452,6 @@ extern "C" int cbo_synchronize(cbo_ctx *c)
     HIP_TRY(hipDeviceSynchronize());            // every stream of the device, the communicator's included
     return CBO_OK;
 }
-
-#ifdef CBO_DIAG_KNOBS
-// Timing-only (diagnostic build): the LDS-staged update kernel alone, C[klen:n, :] -= U[0:klen, klen:n]^T U[0:klen, :] on
-// an n x n array of noise (upper part only when `upper`), `reps` launches between two events -- the bulk trailing
-// update of a factorisation at a given K (scripts/update_kernel_timing.py).
-__global__ void diag_fill_kernel(double *p, int64_t n)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        p[i] = 1e-3 * (double)((i * 2654435761u) & 1023u) - 0.5;
-}
-extern "C" int cbo_diag_update_kernel_time(cbo_ctx *c, int n, int klen, int chunk_blocks, int half_lds, int upper, int reps,
-                                           double *ms_out)
-{
-    if (!c || !ms_out) return fail(CBO_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
-    const int64_t lda = (int64_t)n + 80;
-    double *A = nullptr;
-    HIP_TRY(hipMalloc(&A, sizeof(double) * (size_t)n * (size_t)lda));
-    hipLaunchKernelGGL(diag_fill_kernel, dim3(4096), dim3(256), 0, c->stream, A, (int64_t)n * lda);
-    hipEvent_t a, b;
-    HIP_TRY(hipEventCreate(&a));
-    HIP_TRY(hipEventCreate(&b));
-    launch_gemm_update(c->stream, A, lda, A, lda, A, lda, 0, klen, klen, n, n, chunk_blocks, half_lds != 0, upper != 0, nullptr);
-    HIP_TRY(hipEventRecord(a, c->stream));
-    for (int r = 0; r < reps; ++r)
-        launch_gemm_update(c->stream, A, lda, A, lda, A, lda, 0, klen, klen, n, n, chunk_blocks, half_lds != 0, upper != 0, nullptr);
-    HIP_TRY(hipEventRecord(b, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, a, b));
-    *ms_out = (double)ms / reps;
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    hipFree(A);
-    return CBO_OK;
-}
-#endif
 
 extern "C" int cbo_set_profiling(cbo_ctx *c, int enabled)
 {

@@ -217,31 +217,6 @@ __device__ __forceinline__ void diag_trailing(Diag2Shared &sh, const d4 (&x)[9],
     }
 }
 
-#ifdef CBO_DIAG_KNOBS
-// Timing-only build: bit 1 = the worker waves of the block factorisation skip their trailing tiles, bit 2 = their
-// row-panel thirds as well (what the chain wave's tile factor costs with nothing beside it; results are wrong)
-__device__ int g_diag_knob;
-extern "C" int cbo_diag_set_knob(int v) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_diag_knob), &v, sizeof(int)); }
-#define DIAG_KNOB(bit) (g_diag_knob & (bit))
-// Timing-only build: s_memtime stamps of the last diagonal-block launch, [wave][interval][slot] (scripts/diag_stamps.py)
-__device__ unsigned long long g_diag_stamps[4 * 9 * 4];
-#define DSTAMP(wave_, jb_, slot_) do { if ((threadIdx.x & 63) == 0) g_diag_stamps[((wave_) * 9 + (jb_)) * 4 + (slot_)] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int cbo_diag_chol_stamps(unsigned long long *out)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_diag_stamps), sizeof(unsigned long long) * 4 * 9 * 4);
-}
-__device__ unsigned long long g_small_stamps[16];
-#define SSTAMP(i_) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_small_stamps[(i_)] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int cbo_diag_small_stamps(unsigned long long *out)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_small_stamps), sizeof(unsigned long long) * 16);
-}
-#else
-#define DIAG_KNOB(bit) false
-#define DSTAMP(wave_, jb_, slot_) do { } while (0)
-#define SSTAMP(i_) do { } while (0)
-#endif
-
 // A store of the factor that a workgroup of the SAME launch may read (the strips of the fused diagonal + panel launch):
 // written through to the coherence point of the device instead of resting in this XCD's L2.
 // Fences of the fused diagonal + panel protocol (see potrf_panel_fused_kernel).  The consumer's ACQUIRE is always there
@@ -284,7 +259,6 @@ __device__ __forceinline__ void diag_worker(Diag2Shared &sh, double *A, int64_t 
     constexpr int nown = (ct0 + 6 <= 8) ? 3 : 2;
     // tiles that are not due (ct <= jb) are solved along on whatever S holds there (cheaper than branching around a
     // chain of four MFMAs) and stored nowhere
-    DSTAMP(W + 1, jb, 0);
     if (W == jb % 3) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -339,7 +313,6 @@ __device__ __forceinline__ void diag_worker(Diag2Shared &sh, double *A, int64_t 
             }
         }
     }
-    DSTAMP(W + 1, jb, 1);
     if (PUBLISH && W == jb % 3) {
         // tile jb's inverse (and diagonal factor) are out: flag[1] counts them.  The wait overlaps the rendezvous.
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -349,7 +322,6 @@ __device__ __forceinline__ void diag_worker(Diag2Shared &sh, double *A, int64_t 
     while (__hip_atomic_load(&sh.xcount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 3 * (jb + 1))
         __builtin_amdgcn_s_sleep(1);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    DSTAMP(W + 1, jb, 2);
     // the whole panel into registers (tiles <= jb are finished rows whose products nobody stores: zeros)
     d4 x[9], nx[9];
 #pragma unroll
@@ -368,8 +340,7 @@ __device__ __forceinline__ void diag_worker(Diag2Shared &sh, double *A, int64_t 
     // trailing tiles T(ti, tj) -= X_ti^T X_tj, jb < ti <= 7, ti <= tj <= 8, except the next diagonal tile (wave 0's).
     // Ownership is by column (a compile-time list per wave), tiles go four at a time with their accumulation chains
     // interleaved; a tile that is not due (ti <= jb) is computed on stale operands and simply not written back.
-    if (!DIAG_KNOB(1)) diag_trailing<W>(sh, x, nx, jb, lane, tiles);
-    DSTAMP(W + 1, jb, 3);
+    diag_trailing<W>(sh, x, nx, jb, lane, tiles);
     if (PUBLISH) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's write-through stores have arrived
         AGENT_RELEASE();
@@ -409,7 +380,6 @@ __device__ __forceinline__ void diag128_factor_in_lds(Diag2Shared &sh, double *A
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) af[kk] = sh.Yt[jb & 1][4 * kk + kq][lc];
         if (wave == 0) {
-            DSTAMP(0, jb, 0);
             if (jb + 1 < tiles) {
                 // two half-sums each: a chain of dependent f64 MFMAs runs at about half the issue rate
                 d4 x = {0.0, 0.0, 0.0, 0.0}, xb = {0.0, 0.0, 0.0, 0.0}, acc, accb = {0.0, 0.0, 0.0, 0.0};
@@ -428,14 +398,11 @@ __device__ __forceinline__ void diag128_factor_in_lds(Diag2Shared &sh, double *A
                 acc = MFMA_F64(x[2], -x[2], acc);
                 accb = MFMA_F64(x[3], -x[3], accb);
                 acc += accb;
-                DSTAMP(0, jb, 1);
                 const d4 u = factor_tile_regs(acc, lane, r0 + o + 16, info, sh.Yt[(jb + 1) & 1], nullptr,
                                               jb + 2 == tiles ? last_blocks : 4);
-                DSTAMP(0, jb, 2);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sh.S[o + 16 + kq + 4 * r][o + 16 + lc] = u[r];
             }
-            DSTAMP(0, jb, 3);
         } else {
             const int w = wave - 1;
             if (w == 0) diag_worker<0, PUBLISH>(sh, A, lda, r0, rcol, invDt, zvec, jb, af, lane, tiles, flag);
@@ -456,7 +423,6 @@ __global__ __launch_bounds__(256) void potrf_diag128_v2_kernel(double *A, int64_
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    DSTAMP(wave, 8, 0);
     {
         const unsigned s0 = lds_byte_address(&sh.S[0][0]);
         const double *g = A + (int64_t)(r0 + wave * 32) * lda + r0 + lane * 2;
@@ -474,9 +440,7 @@ __global__ __launch_bounds__(256) void potrf_diag128_v2_kernel(double *A, int64_
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    DSTAMP(wave, 8, 1);
     diag128_factor_in_lds(sh, A, lda, r0, rcol, invDt, info, zvec, 8);
-    DSTAMP(wave, 8, 2);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -964,7 +928,6 @@ __device__ __forceinline__ void small_model_factor(SmallShared &sh, const cbo_sm
         }
     }
     __syncthreads();
-    SSTAMP(1);
     if (phases & 1) {
     switch (st.d) {
         case 1: small_assemble<1>(sh, st, tiles); break;
@@ -986,10 +949,8 @@ __device__ __forceinline__ void small_model_factor(SmallShared &sh, const cbo_sm
         if (tid < st.n) sh.blk.S[tid][128] = pmsrc ? __dadd_rn(staged_y, -staged_pm) : staged_y;   // r = y - m(X)
     }
     __syncthreads();
-    SSTAMP(2);
     diag128_factor_in_lds(sh.blk, Us, kSmallLd, 0, 128, invs, info_word, nullptr, tiles, nullptr,
                           skip_padding ? (st.n - 16 * (tiles - 1) + 3) / 4 : 4);
-    SSTAMP(3);
     // (ends with a barrier.)  Every wave's stores of factor rows / inverses / z are complete before anyone re-reads them
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1028,7 +989,6 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
     extern __shared__ __align__(16) unsigned char smem_raw[];
     SmallShared &sh = *reinterpret_cast<SmallShared *>(smem_raw);
     const int set = blockIdx.y, blk = blockIdx.x;
-    SSTAMP(0);
     const cbo_small_set st = BYVAL ? byval.s[set] : sets[set];
     const int slot = set * blocks_per_set + blk;
     if (phases == 1) {                                            // one workgroup per set: factor it, nothing else
@@ -1062,7 +1022,6 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
 
     double iv[8][4], zr[8][4];
     small_model_factor(sh, st, tiles, Us, invs, &info[set], iv, zr, phases, true);
-    SSTAMP(4);
     // ---- K(X, X*) of this wave's 16 candidates, straight into the result layout
     const double inv_l2 = 1.0 / (st.lengthscale * st.lengthscale);
     d4 acc[8];
@@ -1079,7 +1038,6 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    SSTAMP(5);
     // ---- V = L^-1 K*, q = sum V^2, mu = V^T z (lane partials, then over the four lane groups: the strip kernel's order)
     double qacc = 0.0, macc = 0.0;
     panel_solve_tiles(&sh.blk.S[kq][lc], acc, iv, tiles, [&](int s, const d4 &x) {
@@ -1094,7 +1052,6 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
     macc += __shfl_xor(macc, 16);
     macc += __shfl_xor(macc, 32);
 
-    SSTAMP(6);
     // ---- epilogue and the workgroup's arg-max
     AcqParams p;
     p.variance = st.variance; p.noise_var = st.noise_var; p.y_best = st.y_best; p.ei_jitter = st.ei_jitter;
@@ -1117,9 +1074,7 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
         for (int w = 1; w < 4; ++w)
             if (better(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
     }
-    SSTAMP(7);
     small_set_finish(bv, bi, set, slot, blocks_per_set, part_val, part_idx, info, ticket, out, seq, &last_flag);
-    SSTAMP(8);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1638,8 +1593,8 @@ void launch_small_sets(hipStream_t s, const cbo_small_set *sets, int n_sets, int
     // ONE launch, no dependency between workgroups.  Many blocks per set (16k-candidate grids on 25 coral sets: 6400
     // workgroups): factoring the model 256 times over costs more than a second launch -- one workgroup per set factors,
     // then the sweep workgroups start from the factor.
-    static const int two_phase_from = [] { const char *e = std::getenv("CBO_HIP_SMALL_TWO_PHASE"); return e ? std::atoi(e) : 12; }();
-    const bool two_phase = two_phase_from > 0 && blocks_per_set >= two_phase_from;
+    constexpr int kTwoPhaseFromBlocks = 12;
+    const bool two_phase = blocks_per_set >= kTwoPhaseFromBlocks;
     auto launch = [&](const dim3 &g, int phases) {
         if (n_sets <= kSmallByValue)
             hipLaunchKernelGGL(small_sets_kernel<true>, g, dim3(256), sizeof(SmallShared), s, args, sets, scratch,
@@ -2001,9 +1956,14 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
                         (int)sizeof(PanelShared));
     hipFuncSetAttribute(reinterpret_cast<const void *>(potrf_panel_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                         (int)sizeof(Diag2Shared));
-    // 4: diagonal block + row panel in one launch; 2: separate launches (lean panel kernel, beside a pipelined sweep the
-    // half-LDS strip kernel); 3: the lean panel kernel also beside a pipelined sweep; 1: the strip kernel as panel solver
-    static const int panel_form_env = [] { const char *e = std::getenv("CBO_HIP_PANEL_FORM"); return e ? std::atoi(e) : 4; }();
+    // 4: diagonal block + row panel in one launch; 5: the same as two launches, the block's and an LDS-free one of the
+    // strips; 2: separate launches (lean panel kernel, beside a pipelined sweep the half-LDS strip kernel).  Any other
+    // value means 4.
+    static const int panel_form_env = [] {
+        const char *e = std::getenv("CBO_HIP_PANEL_FORM");
+        const int form = e ? std::atoi(e) : 4;
+        return (form == 2 || form == 5) ? form : 4;
+    }();
     const int panel_form = g_panel_form_override > 0 ? g_panel_form_override : panel_form_env;
     // polls a strip of a fused launch makes before it gives up (read per factorisation: a test sets it to -1)
     const int spin_limit = [] { const char *e = std::getenv("CBO_HIP_FUSED_SPIN_LIMIT"); return e ? std::atoi(e) : kFusedSpinLimit; }();
@@ -2017,7 +1977,7 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
     };
     const int np = (int)(n_pad / 128);
     // info_dev[0] is the status word; info_dev[1 + 2p], [2 + 2p] the publication counts of panel p's fused launch
-    const bool fused = (panel_form == 4 || panel_form == 5) && 2 * np <= kCholFlagSlots;
+    const bool fused = panel_form != 2 && 2 * np <= kCholFlagSlots;
     const bool split = panel_form == 5;
     // (a launch, not hipMemsetAsync: the runtime's fill costs two kernels and ~8 us of marker gaps around each)
     if (!info_zeroed) hipLaunchKernelGGL(zero_ints_kernel, dim3(1), dim3(256), 0, s, info_dev, fused ? 1 + 2 * np : 1);
@@ -2035,9 +1995,10 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
     // rows, so the trailing matrix below the pair is updated once with K = 256 (half the read-modify-write
     // passes); the bulk of that update runs on the side stream under the next pair's diagonal/panel work.
     double *zvec = pipe ? pipe->zvec : nullptr;
-    // beside a pipelined sweep the panel solves use the half-LDS kernel, which fits next to a sweep workgroup
+    // unfused panel solves: the lean panel kernel, or beside a pipelined sweep the strip kernel -- the half-LDS one, which
+    // fits next to a sweep workgroup, when the pipeline runs on half-LDS stages
+    const bool lean_panel = !pipe;
     const bool half_lds = pipe && pipe->half_lds;
-    const bool lean_panel = ((panel_form == 2 || panel_form == 4 || panel_form == 5) && !pipe) || panel_form == 3;
     int pair = 0;
     auto sweep_rows = [&](int r0, int klen) {
         if (pipe && r0 < pipe->tail_begin) sweep_pipe_pair(*pipe, s, A, lda, invDt, n_pad, pair++, r0, klen);
@@ -2052,7 +2013,7 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
     int pending = -1;                      // event index of the bulk update still in flight
     // Large trailing matrices, groups of G pairs (CBO_HIP_BULK_GROUP caps G: 1 = pairs only, 2, 4 = default).  The bulk update is
     // the LDS-staged GEMM kernel, whose rate grows with K (16384 points, all columns: 0.68 / 0.75 / 0.83 of peak at K = 256 /
-    // 512 / 1024: scripts/update_kernel_timing.py), and it accumulates into C sequentially from C's own value, so one K = 256 G
+    // 512 / 1024: profiles/r03_update_kernel_timing.txt), and it accumulates into C sequentially from C's own value, so one K = 256 G
     // pass gives the bits of G passes of K = 256.  Group j = pairs [G j, G j + G); S = 256 G; G_g = the S rows of group g:
     //   chain:  pair p of group j: factor; rows of pair p+1 -= pair p (rows kernel, as ever);
     //           [first pair of the group: wait bigA(j-1)]  near(p): the rows from pair p+2 to the end of G_{j+1} -= pair p (K = 256)
@@ -2086,12 +2047,12 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
         const bool first_of_group = grouped && group_left == group_pairs;
         const bool last_of_group = grouped && group_left == 1;
         // beside a bulk update that fills the device the strips go as an LDS-free launch of their own (launch_panel_fused)
-        const bool split_now = split || (grouped && group_split && panel_form == 4);
+        const bool split_now = split || (grouped && group_split);
         if (fused && n2 > 0) launch_panel_fused(s, A, lda, r0, rcol, invDt, info_dev, zvec, n2, flags + 2 * (r0 / 128), spin_limit, nullptr, split_now);
         else launch_diag(r0);
         if (n2 <= 0) { sweep_rows(r0, 128); break; }
         if (fused) {}
-        else if (lean_panel) launch_panel_trsm(s, A, lda, r0, r0 + 128, n2, invDt, info_dev);   // (beside a pipelined sweep: the half-LDS strip kernel)
+        else if (lean_panel) launch_panel_trsm(s, A, lda, r0, r0 + 128, n2, invDt, info_dev);
         else
         launch_trsm_strips(s, A + (int64_t)r0 * lda + r0, lda, invDt + (int64_t)(r0 / 16) * 256,
                            A + (int64_t)r0 * lda + r0 + 128, lda, 128, n2, nullptr, nullptr, nullptr, false, half_lds);

@@ -32,19 +32,9 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 #define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#ifndef F32_DBG
-#define F32_DBG 0          // timing-only builds (scripts/f32_variants.sh): bit mask of pieces to leave out; results are wrong
-#endif
-int f32_debug_mask() { return F32_DBG; }       // a non-zero mask changes cbo_abi_version(): _lib.load() refuses the build
-#if (F32_DBG & 1)
-#define SCHED_DS(n)
-#define SCHED_MFMA(n)
-#define SCHED_VMEM(n)
-#else
 #define SCHED_DS(n) __builtin_amdgcn_sched_group_barrier(0x100, (n), 0)
 #define SCHED_MFMA(n) __builtin_amdgcn_sched_group_barrier(0x008, (n), 0)
 #define SCHED_VMEM(n) __builtin_amdgcn_sched_group_barrier(0x010, (n), 0)
-#endif
 
 constexpr int kRB = 256;                  // rows per block
 constexpr int kT = kRB / 16;              // 16-row tiles per block
@@ -184,15 +174,10 @@ __global__ __launch_bounds__(256) void trsm_strip_f32_kernel(const float *__rest
 #pragma unroll
                 for (int t = 0; t < kT; ++t) af[(jj + 1) & 1][t] = abase[4 * (jj + 1) * kLd + 16 * t];
                 bf[(jj + 1) & 1] = bbase[4 * (jj + 1) * 16];
-                if (!(F32_DBG & 2) && jj < kParts) issue_part(ahead, bnext, jj);
+                if (jj < kParts) issue_part(ahead, bnext, jj);
                 if (jj == kParts) advance(ahead);
-                if (!(F32_DBG & 4)) {
 #pragma unroll
-                    for (int t = 0; t < kT; ++t) acc[t] = MFMA_F32(af[jj & 1][t], bf[jj & 1], acc[t]);
-                } else {
-#pragma unroll
-                    for (int t = 0; t < kT; ++t) asm volatile("" ::"v"(af[jj & 1][t]), "v"(bf[jj & 1]));
-                }
+                for (int t = 0; t < kT; ++t) acc[t] = MFMA_F32(af[jj & 1][t], bf[jj & 1], acc[t]);
                 SCHED_DS(kT + 1);
                 if (jj < kBPieces) { SCHED_VMEM(3); } else if (jj < kParts) { SCHED_VMEM(2); }
                 SCHED_MFMA(kT);
@@ -210,7 +195,7 @@ __global__ __launch_bounds__(256) void trsm_strip_f32_kernel(const float *__rest
         auto diag_stage = [&](auto mc) __attribute__((always_inline)) {
             constexpr int m = decltype(mc)::value;
             STAGE_TOP();
-            if (!(F32_DBG & 16) && m == 0 && i0 + kRB < n) {
+            if (m == 0 && i0 + kRB < n) {
                 // next block's right-hand sides (K* rows), raw: negated when the block starts, so that no wait for
                 // them lands inside the pipeline
 #pragma unroll
@@ -254,41 +239,29 @@ __global__ __launch_bounds__(256) void trsm_strip_f32_kernel(const float *__rest
                     qacc = fma(xd, xd, qacc);
                 }
             };
-            if (!(F32_DBG & 8)) {
-                const f4 x = solve_tile(0, acc[s]);
-#if (F32_DBG & 32)
-                emit_tile(s, x);
+            const f4 x = solve_tile(0, acc[s]);
+            // tile s+1 first (its four updates, interleaved with tile s+2's so that no MFMA waits on its
+            // predecessor), then its solve chain with the rest of tile s's updates in between
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                    for (int t = s + 1; t < kT; ++t) acc[t] = MFMA_F32(uf[0][t][kk], x[kk], acc[t]);
-                const f4 y = solve_tile(1, acc[s + 1]);
-                emit_tile(s + 1, y);
-#else
-                // tile s+1 first (its four updates, interleaved with tile s+2's so that no MFMA waits on its
-                // predecessor), then its solve chain with the rest of tile s's updates in between
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    acc[s + 1] = MFMA_F32(uf[0][s + 1][kk], x[kk], acc[s + 1]);
-                    if constexpr (s + 2 < kT) acc[s + 2] = MFMA_F32(uf[0][s + 2][kk], x[kk], acc[s + 2]);
-                }
-                emit_tile(s, x);
-                f4 y1 = {0.f, 0.f, 0.f, 0.f}, y2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    if (kk & 1) y2 = MFMA_F32(iv[1][kk], acc[s + 1][kk], y2);
-                    else y1 = MFMA_F32(iv[1][kk], acc[s + 1][kk], y1);
-#pragma unroll
-                    for (int t = s + 3; t < kT; ++t) acc[t] = MFMA_F32(uf[0][t][kk], x[kk], acc[t]);
-                }
-                const f4 y = y1 + y2;
-                emit_tile(s + 1, y);
-#endif
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                    for (int t = s + 2; t < kT; ++t) acc[t] = MFMA_F32(uf[1][t][kk], y[kk], acc[t]);
+            for (int kk = 0; kk < 4; ++kk) {
+                acc[s + 1] = MFMA_F32(uf[0][s + 1][kk], x[kk], acc[s + 1]);
+                if constexpr (s + 2 < kT) acc[s + 2] = MFMA_F32(uf[0][s + 2][kk], x[kk], acc[s + 2]);
             }
+            emit_tile(s, x);
+            f4 y1 = {0.f, 0.f, 0.f, 0.f}, y2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                if (kk & 1) y2 = MFMA_F32(iv[1][kk], acc[s + 1][kk], y2);
+                else y1 = MFMA_F32(iv[1][kk], acc[s + 1][kk], y1);
+#pragma unroll
+                for (int t = s + 3; t < kT; ++t) acc[t] = MFMA_F32(uf[0][t][kk], x[kk], acc[t]);
+            }
+            const f4 y = y1 + y2;
+            emit_tile(s + 1, y);
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+                for (int t = s + 2; t < kT; ++t) acc[t] = MFMA_F32(uf[1][t][kk], y[kk], acc[t]);
             extra_prev = 1;
             buf = (buf == 2) ? 0 : buf + 1;
         };

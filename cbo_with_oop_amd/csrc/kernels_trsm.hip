@@ -56,26 +56,6 @@ struct StageGeom {
     static constexpr int kDiagStores = 4 * kDiagTiles;   // V stores a wave issues per diagonal stage
     static_assert(kParts <= kKS - 2, "the DMA groups and the cursor update ride under the first k-steps");
 };
-#ifdef CBO_DIAG_KNOBS
-// Timing-only build (make DIAG=1 -> libcbo_hip_diag.so): waves 0 and 4 of workgroup 0 of trsm_pair_kernel stamp s_memtime at
-// the milestones of every stage into a debug buffer read back by cbo_diag_trsm_stamps (scripts/pair_timeline.py).
-__device__ unsigned long long g_trsm_stamps[8 * 4096];
-extern "C" int cbo_diag_trsm_stamps(unsigned long long *out, int n)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trsm_stamps), sizeof(unsigned long long) * (size_t)n);   // 8 per stage
-}
-// Timing-only: every workgroup of the last trsm_update_kernel launch leaves [start, end, hw id | xcc id << 32, start, end in
-// s_memrealtime's 100 MHz] (s_memtime runs at the shader clock), and
-// workgroup (7, gridDim.y / 2) its stage tops: scripts/update_kernel_stamps.py
-__device__ unsigned long long g_upd_wg[5 * 65536];
-__device__ unsigned long long g_upd_stage[128];
-extern "C" int cbo_diag_upd_stamps(unsigned long long *wg, unsigned long long *stage)
-{
-    int rc = (int)hipMemcpyFromSymbol(wg, HIP_SYMBOL(g_upd_wg), sizeof(unsigned long long) * 5 * 65536);
-    if (rc == 0) rc = (int)hipMemcpyFromSymbol(stage, HIP_SYMBOL(g_upd_stage), sizeof(unsigned long long) * 128);
-    return rc;
-}
-#endif
 
 // One continuous software pipeline over "stages" of KB U-rows (described for KB = 32).  Row block b (rows
 // i0 = 128 b) consists of nst = i0/32 regular stages (k rows [32 j, 32 j + 32) against the block's 128 columns)
@@ -904,12 +884,6 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
     __shared__ __align__(16) double zl[SWEEP ? 2 * kPB : 2];           // z rows of the current and the next pair
     __shared__ __align__(16) double handbuf[SWEEP ? 4 * 64 * 2 : 2];   // (q, mu) lane partials, (cw, 0) -> (cw, 1)
 
-#ifdef CBO_DIAG_KNOBS
-    // timing-only (CBO_HIP_STRIP_MASK=256, diagnostic build): waves 0 and 4 of workgroup 0 stamp every stage -- slot 0 the
-    // stage top passed, 1 the solved tile published / final, 2 the stage's last instruction issued (scripts/pair_timeline.py)
-    const int dmask = accumulate >> 8;
-    accumulate &= 1;
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);         // wave-uniform: LDS bases stay scalar
@@ -1040,20 +1014,6 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
         // what is younger than its last instruction may still be in flight: what stage k-2 issued after its DMA (a2: the
         // solver's V stores), and all of stage k-1 -- what it issued ahead of its DMA (b1: the hand-issued loads), the DMA, what
         // it issued after (a1).
-#ifdef CBO_DIAG_KNOBS
-        const bool stamp_on = SWEEP && (dmask & 256) && blockIdx.x == 0 && lane == 0 && cw == 0;
-        int stamp_i = 0;
-#define PSTAMP(slot)                                                                                       \
-        do {                                                                                               \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            if (stamp_on && stamp_i < 4096) g_trsm_stamps[8 * stamp_i + 4 * H + (slot)] = __builtin_amdgcn_s_memtime(); \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-        } while (0)
-#define PSTAMP_NEXT() do { if (stamp_on) ++stamp_i; } while (0)
-#else
-#define PSTAMP(slot)
-#define PSTAMP_NEXT()
-#endif
         int a1 = 0, b1 = 0, a2 = 0;
         auto wait_top = [&]() __attribute__((always_inline)) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1076,7 +1036,6 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
             a2 = a1;
             a1 = 0;
             b1 = 0;
-            PSTAMP(0);
         };
         static_assert(kPDma + kL0 + kL1 + 16 <= 63 && kL1 >= kL0, "s_waitcnt vmcnt is a 6-bit count; the cases of wait_top");
 
@@ -1137,7 +1096,7 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            PSTAMP(2); PSTAMP_NEXT(); buf = (buf == 2) ? 0 : buf + 1;                   // the last k-step sits in af[1], bf[1]
+            buf = (buf == 2) ? 0 : buf + 1;                                             // the last k-step sits in af[1], bf[1]
         };
         // the diagonal phase of the pair at i0; P0: the first pair, which has no regular stage before it (nothing deferred)
         auto diag_phase = [&](int i0, auto first_pair_tag) __attribute__((always_inline)) {
@@ -1174,11 +1133,9 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
                     asm volatile("" : "+v"(x));
 #pragma unroll
                     for (int r = 0; r < 4; ++r) xreg[(kq + 4 * r) * 16 + lc] = x[r];      // B-operand layout [row][column]
-                    PSTAMP(3);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();                                       // (cw, 1) may read x now
                     __builtin_amdgcn_s_setprio(0);
-                    PSTAMP(1);
                     // Its own U fragments only now: the eight waves read the whole 16 x 256 tile once per column group in this
                     // stage -- 128 KB, a thousand cycles of the LDS -- and ahead of the publication those reads were the stage's
                     // serial head (1400-2300 cycles from the stage top to this barrier in the first timeline, (cw, 1) waiting).
@@ -1228,7 +1185,7 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
                         qacc = 0.0;
                         macc = 0.0;
                     }
-                    PSTAMP(2); PSTAMP_NEXT(); buf = (buf == 2) ? 0 : buf + 1;
+                    buf = (buf == 2) ? 0 : buf + 1;
                 }
 #pragma unroll
                 for (int m = 0; m < kPD1; ++m) {
@@ -1244,7 +1201,7 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
                         }
                         a1 += m == 0 ? kL0 : kL1;
                     }
-                    PSTAMP(2); PSTAMP_NEXT(); buf = (buf == 2) ? 0 : buf + 1;
+                    buf = (buf == 2) ? 0 : buf + 1;
                 }
             } else {
 #pragma unroll
@@ -1261,10 +1218,8 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
 #pragma unroll
                         for (int kk = 0; kk < 4; ++kk) uf[t][kk] = abase0[(4 * kk) * kPLd + kRB + 16 * t];
                     }
-                    PSTAMP(3);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();                                       // x is published
-                    PSTAMP(1);
 #pragma unroll
                     for (int kk = 0; kk < 4; ++kk) xb[kk] = xreg[(4 * kk + kq) * 16 + lc];
                     // the stage's DMA issue and the cursor arithmetic ride behind the fold's MFMAs, one piece each (ahead of the
@@ -1288,7 +1243,7 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
                         for (int t = 0; t < kT; ++t) af[1][t] = uf[t][3];               // k-step 3: behind the next stage top
                         bf[1] = xb[3];
                     }
-                    PSTAMP(2); PSTAMP_NEXT(); buf = (buf == 2) ? 0 : buf + 1;
+                    buf = (buf == 2) ? 0 : buf + 1;
                 }
 #pragma unroll
                 for (int m = 0; m < kPD1; ++m) {
@@ -1326,7 +1281,6 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
                     __builtin_amdgcn_sched_barrier(0);
                     x += x2;
                     asm volatile("" : "+v"(x));
-                    PSTAMP(1);
                     auto emit = [&](int hh, const d4 &xx) __attribute__((always_inline)) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -1391,7 +1345,7 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
                         qacc = 0.0;
                         macc = 0.0;
                     }
-                    PSTAMP(2); PSTAMP_NEXT(); buf = (buf == 2) ? 0 : buf + 1;
+                    buf = (buf == 2) ? 0 : buf + 1;
                 }
             }
         };
@@ -1414,8 +1368,6 @@ __global__ __launch_bounds__(512) void trsm_pair_kernel(const double *__restrict
     };
     if (h == 0) run(std::integral_constant<int, 0>{});
     else run(std::integral_constant<int, 1>{});
-#undef PSTAMP
-#undef PSTAMP_NEXT
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1449,16 +1401,6 @@ __global__ __launch_bounds__(256) void trsm_update_kernel(const double *__restri
     __shared__ __align__(16) double lds[kNBuf * (kA + kB)];
 
     const int tid = threadIdx.x;
-#ifdef CBO_DIAG_KNOBS
-    const unsigned long long upd_t0 = __builtin_amdgcn_s_memtime();
-    const unsigned long long upd_r0 = __builtin_amdgcn_s_memrealtime();
-    const int upd_id = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const bool upd_probe = tid == 0 && blockIdx.x == 7 && blockIdx.y == gridDim.y / 2;
-    int upd_k = 0;
-#define UPD_STAMP() do { if (upd_probe && upd_k < 128) g_upd_stage[upd_k++] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define UPD_STAMP() do { } while (0)
-#endif
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lc = lane & 15, kq = lane >> 4;
@@ -1514,7 +1456,6 @@ __global__ __launch_bounds__(256) void trsm_update_kernel(const double *__restri
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[t][r] = -Cc[(int64_t)(ib + 16 * t + kq + 4 * r) * ldc];
 
-    UPD_STAMP();                                    // [0] C tile in registers
     locate();
 #pragma unroll
     for (int part = 0; part < kParts; ++part) issue_part(0, part);
@@ -1522,7 +1463,6 @@ __global__ __launch_bounds__(256) void trsm_update_kernel(const double *__restri
 #pragma unroll
     for (int part = 0; part < kParts; ++part) issue_part(1, part);
     advance();
-    UPD_STAMP();                                    // [1] two stages of DMA issued
 
     int buf = 0;
     // vmcnt bookkeeping (in-order retirement): at the top of a stage this wave's DMA of the stage must have
@@ -1538,7 +1478,6 @@ __global__ __launch_bounds__(256) void trsm_update_kernel(const double *__restri
             if (boundary) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kDma + kAccMoves) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kDma) : "memory");
             __builtin_amdgcn_s_barrier();
-            UPD_STAMP();                            // [2 + stage] stage top passed
             boundary = (boundary > 0) ? boundary - 1 : 0;
             if (j == 0 && i0 + kRB < ie) {
                 // next block's C, ahead of this stage's DMA in issue order
@@ -1588,33 +1527,17 @@ __global__ __launch_bounds__(256) void trsm_update_kernel(const double *__restri
         }
 #pragma unroll
         for (int t = 0; t < kT; ++t) acc[t] = MFMA_F64(af[1][t], bf[1], acc[t]);
-        UPD_STAMP();                                // block's last MFMAs issued
 #pragma unroll
         for (int t = 0; t < kT; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) Cc[(int64_t)(i0 + 16 * t + kq + 4 * r) * ldc] = -acc[t][r];
         asm volatile("" ::: "memory");
-        UPD_STAMP();                                // stores issued
 #pragma unroll
         for (int t = 0; t < kT; ++t) acc[t] = accn[t];
         boundary = 2;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#ifdef CBO_DIAG_KNOBS
-    UPD_STAMP();                                    // drained
-    if (tid == 0 && upd_id < 65536) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_upd_wg[5 * upd_id] = upd_t0;
-        g_upd_wg[5 * upd_id + 1] = __builtin_amdgcn_s_memtime();
-        g_upd_wg[5 * upd_id + 2] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-        g_upd_wg[5 * upd_id + 3] = upd_r0;
-        g_upd_wg[5 * upd_id + 4] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
-#undef UPD_STAMP
 }
 
 void launch_trsm_strips(hipStream_t s, const double *U, int64_t ldu, const double *invDt, double *V, int64_t ldv,
@@ -1641,13 +1564,6 @@ void launch_trsm_strips(hipStream_t s, const double *U, int64_t ldu, const doubl
         return !(e && atoi(e) == 8);
     }();
     if (pairs && n >= kPB && n % kPB == 0) {
-#ifdef CBO_DIAG_KNOBS
-        static const int pair_mask = [] {
-            const char *e = getenv("CBO_HIP_STRIP_MASK");          // 256: stage stamps on (scripts/pair_timeline.py)
-            return e ? atoi(e) : 0;
-        }();
-        const int acc = (accumulate ? 1 : 0) | (pair_mask << 8);
-#endif
         if (q != nullptr)
             hipLaunchKernelGGL((trsm_pair_kernel<true>), grid, dim3(512), 0, s, U, ldu, invDt, V, ldv, (int)n, z, q, mu, acc);
         else

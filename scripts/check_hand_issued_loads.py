@@ -1,10 +1,12 @@
-"""Build-time check of trsm_strip8_kernel's hand-issued loads (kernels_trsm.hip): the loads for the next block are
-issued by inline asm, so the compiler does not know their results arrive later.  That is only sound if no instruction
-touches a destination register between the load and the point where the kernel has waited for it (the block end, first
-use: v_xor / v_mov / ds_write).  This script compiles the file to ISA and verifies exactly that, for both instantiations.
+"""Build-time check of the hand-issued loads of trsm_strip8_kernel and trsm_pair_kernel (kernels_trsm.hip): the loads for
+the next block are issued by inline asm, so the compiler does not know their results arrive later.  That is only sound if
+no instruction touches a destination register between the load and the point where the kernel has waited for it (the
+block end, first use: v_xor / v_mov / ds_write).  This script compiles the file to ISA and verifies exactly that, for both
+instantiations of each kernel; an instantiation it cannot find, or one without loads (or, for the pair kernel, without
+pins), is a problem.
 usage: python scripts/check_hand_issued_loads.py [device-assembly.s]  (exit code 0 = ok).  With a path (what
-cbo_with_oop_amd/csrc/Makefile does for the product AND the DIAG=1 object, on the assembly that becomes the object) it
-checks that file; without, it compiles the source itself (CHECK_DIAG=1: with -DCBO_DIAG_KNOBS); also run by tests/test_abi.py"""
+cbo_with_oop_amd/csrc/Makefile does, on the assembly that becomes the object) it checks that file; without, it compiles
+the source itself; also run by tests/test_abi.py"""
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,14 +22,23 @@ def registers(text):
     return out
 
 
+def instantiations(asm_text, symbol, kernel):
+    """The listings of cbo::<kernel><true> and <false> (symbol: its mangled name up to the template arguments), and a
+    problem for each of the two the assembly lacks: a gate that finds nothing to check must not pass."""
+    bodies = re.split(r"\n(?=" + symbol + r"\S*:)", asm_text)[1:]
+    problems = [f"{kernel}<{arg}>: not found in the assembly" for arg, tag in (("true", "ILb1E"), ("false", "ILb0E"))
+                if not any(b.startswith(symbol + tag) for b in bodies)]
+    return bodies, problems
+
+
 def check(asm_text):
     """Every instruction that names a destination register of a hand-issued load must be a hand-issued load itself or
     come after the kernel's pin (an empty inline-asm statement, which the source places behind the stage-top wait that
     retires the loads) within its basic block.  Those registers stay live from the loads at kernel start to the kernel's
     end, so any other mention is a copy or a reuse the loads would race with.  Code ahead of the first such load in the
     listing (the entry block) is exempt."""
-    problems, checked = [], 0
-    kernels = re.split(r"\n(?=_ZN3cbo18trsm_strip8_kernel\S*:)", asm_text)[1:]
+    kernels, problems = instantiations(asm_text, "_ZN3cbo18trsm_strip8_kernel", "trsm_strip8_kernel")
+    checked = 0
     for body in kernels:
         name = body.split(":", 1)[0]
         raw = body.split("\n")
@@ -80,8 +91,9 @@ def check_pair(asm_text):
     pin of a register ("; ahead-pin vN" inside an inline-asm bracket) lands it, a load of the same registers re-arms them,
     and any OTHER instruction that names an in-flight register is a violation (a copy, a spill or a reuse the load would
     race with).  At a merge the in-flight sets are united."""
-    problems, checked = [], 0
-    for body in re.split(r"\n(?=_ZN3cbo16trsm_pair_kernel\S*:)", asm_text)[1:]:
+    kernels, problems = instantiations(asm_text, "_ZN3cbo16trsm_pair_kernel", "trsm_pair_kernel")
+    checked = 0
+    for body in kernels:
         name = body.split(":", 1)[0]
         raw = body.split(".end_amdhsa_kernel")[0].split("\n") if ".end_amdhsa_kernel" in body else body.split("\n")
         last = max(i for i, l in enumerate(raw) if "s_endpgm" in l)
@@ -145,20 +157,16 @@ def main():
     if len(sys.argv) > 1:
         # the Makefile's form: the device assembly of the very compilation that becomes the object (-save-temps=obj)
         text = open(sys.argv[1]).read()
-        checked, problems = check(text)
-        c2, p2 = check_pair(text)
-        checked, problems = checked + c2, problems + p2
     else:
-        flags = ["-DCBO_DIAG_KNOBS"] if os.environ.get("CHECK_DIAG") else []
         with tempfile.TemporaryDirectory() as d:
             out = os.path.join(d, "k.s")
-            subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950"] + flags +
-                                  ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(SRC), "-S",
+            subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
+                                   "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(SRC), "-S",
                                    "--cuda-device-only", SRC, "-o", out], stderr=subprocess.DEVNULL)
             text = open(out).read()
-            checked, problems = check(text)
-            c2, p2 = check_pair(text)
-            checked, problems = checked + c2, problems + p2
+    checked, problems = check(text)
+    c2, p2 = check_pair(text)
+    checked, problems = checked + c2, problems + p2
     print(f"checked {checked} hand-issued load sites; {len(problems)} problem(s)")
     for p in problems:
         print("  ", p)

@@ -1,6 +1,6 @@
 """The coral graph's count of exploration sets (S = 25) with this package's default grids (200 / 64x64 / 32x32x16 candidates for
-d = 1 / 2 / 3) and 50 observations per set: latency of the one multi-set call (CBO_HIP_SMALL_TWO_PHASE=0: every workgroup
-factors its set's model itself; default: one workgroup per set factors first when a set has 12 or more candidate blocks)."""
+d = 1 / 2 / 3) and 50 observations per set: latency of the one multi-set call (one workgroup per set factors first when a
+set has 12 or more candidate blocks)."""
 import os, sys, time, ctypes
 sys.path.insert(0, os.getcwd())
 import numpy as np
