@@ -145,3 +145,133 @@ def refined_variance(post, Xs, vXs=None, iterations=4, include_noise=True):
     if include_noise:
         var = var + np.longdouble(post.noise_var)
     return np.asarray(var, dtype=np.float64)[:, None]
+
+
+# ------------------------------------------------------------------ long-double linear algebra on GIVEN fp64 factors
+# (oracle/gp_linalg_ld.c): the device's own L, alpha go in, so that a test measures one stage of the device at a time.
+_LINALG = None
+
+
+def _linalg():
+    global _LINALG
+    if _LINALG is None:
+        path = os.path.join(_HERE, "libgp_linalg_ld.so")
+        if not os.path.exists(path):
+            subprocess.check_call(["make", "-C", _HERE, "libgp_linalg_ld.so"])
+        lib = ctypes.CDLL(path)
+        P = ctypes.POINTER(ctypes.c_double)
+        PL = ctypes.POINTER(ctypes.c_longdouble)
+        PI = ctypes.POINTER(ctypes.c_long)
+        lib.ld_backward_error_rows.restype = ctypes.c_int
+        lib.ld_backward_error_rows.argtypes = [ctypes.c_long, P, P, PI, ctypes.c_long, PL, PI, PI]
+        lib.ld_solve_many.restype = ctypes.c_int
+        lib.ld_solve_many.argtypes = [ctypes.c_long, P, ctypes.c_long, P, P, P, PL, PL, PL, P]
+        lib.ld_lml_gradients.restype = ctypes.c_int
+        lib.ld_lml_gradients.argtypes = [ctypes.c_long, ctypes.c_int, P, P, P, P, ctypes.c_double, P, ctypes.c_int,
+                                         PL, PL, PL]
+        lib.ld_prediction_gradients.restype = ctypes.c_int
+        lib.ld_prediction_gradients.argtypes = [ctypes.c_long, ctypes.c_int, P, P, P, ctypes.c_long, P, P, P,
+                                                ctypes.c_double, P, ctypes.c_int, PL, PL, PL, PL]
+        _LINALG = lib
+    return _LINALG
+
+
+def _c64(a, shape=None):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    return a if shape is None else a.reshape(shape)
+
+
+def _pl(a):
+    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_longdouble))
+
+
+def _check_rc(rc, what):
+    if rc != 0:
+        raise np.linalg.LinAlgError(f"{what}: non-positive pivot or diagonal at row {rc - 1}" if rc > 0 else
+                                    f"{what}: invalid argument or out of memory")
+
+
+def _hyper(X, lengthscale):
+    X = _c64(X)
+    if X.ndim == 1:
+        X = X[:, None]
+    ls = np.atleast_1d(_c64(lengthscale)).copy()
+    return X, ls, int(ls.size > 1)
+
+
+def backward_error_rows(L, A, rows):
+    """max over the sampled rows i and all j of |(L L^T - A)_ij| / sqrt(A_ii A_jj), in long double (only the lower
+    triangle of L is read).  Returns (value as numpy.longdouble, (i, j) where it is reached).  O(n^2 |rows|)."""
+    L, A = _c64(L), _c64(A)
+    n = L.shape[0]
+    assert L.shape == A.shape == (n, n)
+    rows = np.ascontiguousarray(np.unique(np.asarray(rows, dtype=np.int64)), dtype=np.int64)
+    out = np.zeros(1, dtype=np.longdouble)
+    bi, bj = ctypes.c_long(-1), ctypes.c_long(-1)
+    rc = _linalg().ld_backward_error_rows(n, _p(L), _p(A), rows.ctypes.data_as(ctypes.POINTER(ctypes.c_long)),
+                                          rows.size, _pl(out), ctypes.byref(bi), ctypes.byref(bj))
+    _check_rc(rc, "backward_error_rows")
+    return out[0], (bi.value, bj.value)
+
+
+def solve_many(L, B, z=None, r=None, return_v=False):
+    """v_k = L^-1 b_k for every column of B (n, m), in long double: returns (q, mu) with q_k = sum v_k^2 and
+    mu_k = v_k^T z (numpy.longdouble arrays; mu is None without z or r) -- the two reductions of the sweep
+    (kernels_trsm.hip).  ``z`` is taken as given; ``r`` instead: z = L^-1 r in long double.  ``return_v``: V rounded to
+    fp64 as a third result."""
+    L = _c64(L)
+    n = L.shape[0]
+    B = _c64(B)
+    if B.ndim == 1:
+        B = B[:, None]
+    m = B.shape[1]
+    assert B.shape[0] == n
+    q = np.zeros(m, dtype=np.longdouble)
+    mu = np.zeros(m, dtype=np.longdouble) if (z is not None or r is not None) else None
+    V = np.empty((n, m)) if return_v else None
+    z_, r_ = _c64(z, (-1,)), (None if z is not None else _c64(r, (-1,)))
+    rc = _linalg().ld_solve_many(n, _p(L), m, _p(B), _p(z_), _p(r_), _pl(q), _pl(mu), None, _p(V))
+    _check_rc(rc, "solve_many")
+    return (q, mu, V) if return_v else (q, mu)
+
+
+def lml_and_gradients(L, X, y, mX=None, vX=None, variance=1.0, lengthscale=1.0):
+    """Log marginal likelihood and its gradients (gp_oracle.log_marginal_likelihood_gradients restated) with every
+    solve on the GIVEN factor L: alpha = (L L^T)^-1 (y - m(X)), log det = 2 sum log L_ii, W = (L L^T)^-1 formed from L,
+    1/2 tr((alpha alpha^T - W) dK) contracted in long double with kernel entries from direct coordinate differences.
+    O(n^3) long-double work: n <= ~2100.  Returns (values, magnitudes), dicts of numpy.longdouble with keys lml,
+    d_variance, d_noise (scalars) and d_lengthscale (array); the magnitudes are the same sums over absolute terms."""
+    L = _c64(L)
+    n = L.shape[0]
+    X, ls, ard = _hyper(X, lengthscale)
+    d = X.shape[1]
+    r = _c64(y, (-1,)) - (0.0 if mX is None else _c64(mX, (-1,)))
+    r = np.ascontiguousarray(r)
+    nl = d if ard else 1
+    out = np.zeros(3 + nl, dtype=np.longdouble)
+    mag = np.zeros(3 + nl, dtype=np.longdouble)
+    rc = _linalg().ld_lml_gradients(n, d, _p(L), _p(X), _p(r), _p(_c64(vX, (-1,))), float(variance), _p(ls), ard,
+                                    _pl(out), _pl(mag), None)
+    _check_rc(rc, "lml_and_gradients")
+    unpack = lambda a: {"lml": a[0], "d_variance": a[1], "d_noise": a[2], "d_lengthscale": a[3:].copy()}
+    return unpack(out), unpack(mag)
+
+
+def prediction_gradients(L, alpha, X, Xs, vX=None, vXs=None, variance=1.0, lengthscale=1.0):
+    """(dmean (M,d), dvar (M,d)) of gp_oracle.predict_gradients with the solves Ky^-1 k(X, x*) on the GIVEN factor L
+    and the GIVEN alpha, in long double; plus their magnitudes (the same sums over absolute terms).  Returns
+    (dmean, dvar, mag_mean, mag_var), numpy.longdouble arrays."""
+    L = _c64(L)
+    n = L.shape[0]
+    X, ls, ard = _hyper(X, lengthscale)
+    Xs = _c64(Xs)
+    d = X.shape[1]
+    m = Xs.shape[0]
+    outs = [np.zeros((m, d), dtype=np.longdouble) for _ in range(4)]
+    rc = _linalg().ld_prediction_gradients(n, d, _p(L), _p(_c64(alpha, (-1,))), _p(X), m, _p(Xs),
+                                           _p(_c64(vX, (-1,))), _p(_c64(vXs, (-1,)) if vX is not None else None),
+                                           float(variance), _p(ls), ard, *(_pl(a) for a in outs))
+    _check_rc(rc, "prediction_gradients")
+    return tuple(outs)
