@@ -94,9 +94,11 @@ struct cbo_ctx {
     std::vector<hipEvent_t> pipe_events;      // factorisation -> sweep dependencies
     hipEvent_t ev_join = nullptr, ev_join2 = nullptr, ev_fork = nullptr;
     hipEvent_t region_a = nullptr, region_b = nullptr;
-    int pipe_chunk_blocks = 1;        // row blocks per update workgroup (1 since the updates go in K = 512 groups: profiles/r03_schedule_crossover.txt)
-    bool pipe_half_lds = true;
     double pipe_tail_frac = -1.0;    // CBO_HIP_PIPE_TAIL: rows (fraction) left to the closing left-looking launch; < 0 = automatic
+    int pipe_group = 0;              // CBO_HIP_PIPE_GROUP: 1 = never grouped, G >= 2 = groups of G pairs, 0 = automatic
+    int pipe_lead = -1;              // CBO_HIP_PIPE_LEAD: pairs alone ahead of the first group; < 0 = automatic
+    CholOptions chol;                // the factorisation's launch forms
+    int vec_solve_form = 2;          // CBO_HIP_VEC_SOLVE_FORM: 1 = the single-vector solves as per-block launches
     int n_cu = 256;
     int n_cu_pipe = 256;             // CUs the pipelined sweep's streams may use (the rest is kept for the factorisation)
     ScheduleTable schedule;          // (padded rows, padded candidates) -> measured schedule of cbo_gp_fit_sweep (schedule_tuner.h)
@@ -393,6 +395,21 @@ extern "C" int cbo_init(int device_id, cbo_ctx **out)
     if (om) c->overlap_mode = std::atoi(om);
     const char *tf = std::getenv("CBO_HIP_PIPE_TAIL");
     if (tf) c->pipe_tail_frac = std::atof(tf);
+    // (groups beyond 4 pairs -- K = 1024 -- are not covered by the tests: clamped)
+    const char *pg = std::getenv("CBO_HIP_PIPE_GROUP");
+    if (pg) c->pipe_group = std::min(std::max(std::atoi(pg), 0), 4);
+    const char *pl = std::getenv("CBO_HIP_PIPE_LEAD");
+    if (pl) c->pipe_lead = std::atoi(pl);
+    const char *pf = std::getenv("CBO_HIP_PANEL_FORM");
+    if (pf && (std::atoi(pf) == 2 || std::atoi(pf) == 5)) c->chol.panel_form = std::atoi(pf);     // any other value means 4
+    const char *sl = std::getenv("CBO_HIP_FUSED_SPIN_LIMIT");
+    if (sl) c->chol.spin_limit = std::atoi(sl);
+    const char *bg = std::getenv("CBO_HIP_BULK_GROUP");
+    if (bg) c->chol.bulk_group = std::atoi(bg);
+    const char *g4 = std::getenv("CBO_HIP_BULK_GROUP4_ROWS");
+    if (g4) c->chol.group4_rows = std::atoi(g4);
+    const char *vf = std::getenv("CBO_HIP_VEC_SOLVE_FORM");
+    if (vf) c->vec_solve_form = std::atoi(vf);
     {
         static std::once_flag once;
         std::call_once(once, [] { std::atexit(shutdown_all_at_exit); });
@@ -664,7 +681,16 @@ extern "C" int cbo_gp_jitter(const cbo_gp *g, int *tries_out, double *jitter_out
     return CBO_OK;
 }
 
-static void enqueue_factor(cbo_gp *g, double jitter)
+// the factorisation's launch forms for one attempt: `separate` = the repeat after a fused diagonal + panel launch gave up
+// (kCholFusedTimeout), with the separate-launch kernels whatever CBO_HIP_PANEL_FORM says
+static CholOptions chol_options(const cbo_ctx *c, bool separate)
+{
+    CholOptions o = c->chol;
+    if (separate) o.panel_form = 2;
+    return o;
+}
+
+static void enqueue_factor(cbo_gp *g, double jitter, bool separate)
 {
     cbo_ctx *c = g->ctx;
     {
@@ -674,22 +700,10 @@ static void enqueue_factor(cbo_gp *g, double jitter)
     }
     {
         PhaseScope ps(c, PH_CHOL);
-        launch_cholesky(c->stream, c->side_stream, c->chol_events, g->A, g->lda, g->n_pad, g->invDt, g->info, nullptr, true);
+        launch_cholesky(c->stream, c->side_stream, c->chol_events, g->A, g->lda, g->n_pad, g->invDt, g->info,
+                        chol_options(c, separate), nullptr, true);
     }
 }
-
-// Scope of a factorisation's repeat with the separate-launch kernels after a fused launch gave up (kCholFusedTimeout).
-struct FusedFallback {
-    bool on = false;
-    bool active() const { return on; }
-    void engage(cbo_ctx *c)
-    {
-        on = true;
-        ++c->fused_fallbacks;
-        set_panel_form_override(2);
-    }
-    ~FusedFallback() { if (on) set_panel_form_override(0); }
-};
 
 // GPy util.linalg.jitchol after a failed attempt: first `base` (1e-6 mean(diag)), then x10 per retry, at most 5
 // retries.  false: the ladder is exhausted (the caller reports CBO_ERR_NOT_PD).
@@ -724,23 +738,23 @@ static int next_jitter(cbo_gp *g, int *tries, double *jitter)
     return CBO_OK;
 }
 
-// one attempt at a factorisation: enqueue() queues it on c->stream, info is its device status word; *pd says whether it
-// went through
+// one attempt at a factorisation: enqueue(separate) queues it on c->stream (separate: see chol_options), info is its
+// device status word; *pd says whether it went through
 template <class Enqueue>
 static int attempt_factor(cbo_ctx *c, const int *info, Enqueue enqueue, bool *pd)
 {
-    FusedFallback fallback;
-    for (;;) {
-        enqueue();
+    for (bool separate = false;;) {
+        enqueue(separate);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(c->h_info, info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (*c->h_info == kCholFusedTimeout) {
             // a strip of a fused diagonal + panel launch gave up waiting (see potrf_panel_fused_kernel): the same
             // attempt again with the separate-launch kernels -- same bits, no protocol between workgroups
-            if (fallback.active())
+            if (separate)
                 return fail(CBO_ERR_HIP, "a fused diagonal + panel launch gave up waiting, and so did the separate-launch repeat");
-            fallback.engage(c);
+            separate = true;
+            ++c->fused_fallbacks;
             continue;
         }
         *pd = *c->h_info == 0;
@@ -785,7 +799,7 @@ extern "C" int cbo_gp_fit(cbo_gp *g, int *tries_out, double *jitter_out)
     int tries = 0;
     for (;;) {
         bool pd = false;
-        int rc = attempt_factor(c, g->info, [&] { enqueue_factor(g, jitter); }, &pd);
+        int rc = attempt_factor(c, g->info, [&](bool separate) { enqueue_factor(g, jitter, separate); }, &pd);
         if (rc != CBO_OK) return rc;
         if (pd) break;
         rc = next_jitter(g, &tries, &jitter);
@@ -829,7 +843,7 @@ extern "C" int cbo_gp_fit_level(cbo_gp *g, int level, int *status, double *jitte
     if (rc == CBO_ERR_NONPOS_DIAG) { *status = -1; return CBO_OK; }
     if (rc != CBO_OK) return rc;
     bool pd = false;
-    rc = attempt_factor(c, g->info, [&] { enqueue_factor(g, jitter); }, &pd);
+    rc = attempt_factor(c, g->info, [&](bool separate) { enqueue_factor(g, jitter, separate); }, &pd);
     if (rc != CBO_OK) return rc;
     *status = pd ? 1 : 0;
     if (jitter_out) *jitter_out = jitter;
@@ -867,7 +881,7 @@ static int ensure_alpha(cbo_gp *g)
         PhaseScope ps(c, PH_ALPHA);
         // one launch (a chain of workgroups); the per-block launches where that form does not apply
         chained = launch_backsolve_chain(c->stream, g->A, g->lda, g->n_pad, g->invDt, g->A + g->n_pad, g->lda,
-                                         g->alpha + g->n_pad, g->alpha, g->info);
+                                         g->alpha + g->n_pad, g->alpha, g->info, c->chol.spin_limit, c->vec_solve_form);
         if (!chained) launch_backsolve(c->stream, g->A, g->lda, g->n_pad, g->invDt, g->alpha);
     }
     HIP_TRY(hipGetLastError());
@@ -1162,8 +1176,6 @@ static SweepPipe make_pipe(cbo_gp *g, double *V, int64_t ldv, int64_t cols, doub
     pipe.bulk = c->bulk_stream;
     pipe.V = V; pipe.ldv = ldv; pipe.m_pad = cols;
     pipe.zvec = g->z; pipe.q = q; pipe.mu = mu;
-    pipe.chunk_blocks = c->pipe_chunk_blocks;
-    pipe.half_lds = c->pipe_half_lds;
     pipe.events = &c->pipe_events;
     pipe.mark = pipe_mark; pipe.user = c;
     pipe.tail_begin = (int)g->n_pad;                     // no tail unless the caller sets one
@@ -1476,7 +1488,7 @@ extern "C" int cbo_gp_append(cbo_gp *g, const double *x_new, double y_new, doubl
     launch_kstar(c->stream, g->X, g->probe->P, 0, g->probe->m_pad, g->h, c->V, ldv, g->n_pad);
     launch_gather_column(c->stream, c->V, ldv, g->n_pad, g->alpha + g->n_pad);      // work vector (alpha's scratch half)
     const bool chained = launch_forward_chain(c->stream, g->A, g->lda, g->n_pad, g->invDt, g->alpha + g->n_pad, g->lvec,
-                                              g->info);
+                                              g->info, c->chol.spin_limit, c->vec_solve_form);
     if (!chained) launch_forward_vec(c->stream, g->A, g->lda, g->n_pad, g->invDt, g->alpha + g->n_pad, g->lvec);
     HIP_TRY(hipGetLastError());
     // l^T z and l^T l by one device reduction (16 bytes come back)
@@ -1612,19 +1624,14 @@ extern "C" int cbo_gp_fit_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task
     using clk = std::chrono::steady_clock;
     const clk::time_point t_call = clk::now();
     auto us_since = [](clk::time_point a) { return std::chrono::duration<double, std::micro>(clk::now() - a).count(); };
-    static const int pipe_group_env = [] {
-        const char *e = std::getenv("CBO_HIP_PIPE_GROUP");           // 1 = never grouped, G >= 2 = groups of G pairs
-        const int v = e ? std::atoi(e) : 0;                          // (groups beyond 4 pairs -- K = 1024 -- are not
-        return v < 0 ? 0 : (v > 4 ? 4 : v);                          //  covered by the tests: clamped)
-    }();
     const int nb = (int)(g->n_pad / 128);
     const int all_pairs = (nb + 1) / 2;
-    const bool forced = c->overlap_mode == 0 || c->overlap_mode == 1 || c->pipe_tail_frac >= 0.0 || pipe_group_env != 0 ||
+    const bool forced = c->overlap_mode == 0 || c->overlap_mode == 1 || c->pipe_tail_frac >= 0.0 || c->pipe_group != 0 ||
                         all_pairs < 2;
     ScheduleEntry *entry = nullptr;
     ScheduleChoice choice;
     if (forced) {
-        choice.group = pipe_group_env >= 2 ? pipe_group_env : (pipe_group_env == 0 && k->m_pad / kStrip >= c->n_cu_pipe) ? 2 : 0;
+        choice.group = c->pipe_group >= 2 ? c->pipe_group : (c->pipe_group == 0 && k->m_pad / kStrip >= c->n_cu_pipe) ? 2 : 0;
         if (c->overlap_mode == 0 || (all_pairs < 2 && c->overlap_mode != 1)) choice.pairs = kSequence;
         else if (c->pipe_tail_frac >= 0.0) {
             int tail_blocks = (int)(c->pipe_tail_frac * nb + 0.5);
@@ -1674,16 +1681,15 @@ extern "C" int cbo_gp_fit_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task
     pipe.group = choice.group;
     // pairs that do not fill a group go alone ahead of the first one (CBO_HIP_PIPE_LEAD forces the count where the schedule is
     // forced; there the default stays 0: whole groups from the first pair, what the forced schedules of rounds 3-5 meant)
-    static const int pipe_lead_env = [] { const char *e = std::getenv("CBO_HIP_PIPE_LEAD"); return e ? std::atoi(e) : -1; }();
     int pairs = choice.pairs;
     pipe.lead = 0;
     if (pipe.group >= 2 && pairs >= 1 && pairs * 256 < (int)g->n_pad)
-        pipe.lead = forced ? (pipe_lead_env > 0 ? pipe_lead_env : 0) : (pipe_lead_env >= 0 ? pipe_lead_env : pairs % pipe.group);
+        pipe.lead = forced ? (c->pipe_lead > 0 ? c->pipe_lead : 0) : (c->pipe_lead >= 0 ? c->pipe_lead : pairs % pipe.group);
     pipe.tail_begin = pairs * 256;
     if (pipe.tail_begin > (int)g->n_pad) pipe.tail_begin = (int)g->n_pad;
     double jitter = 0.0;
     int tries = 0;
-    FusedFallback fallback;
+    bool separate = false;                                 // the attempts after a fused launch gave up (chol_options)
     for (;;) {
         // fork: the sweep stream starts after what is queued on the main stream (candidate preparation)
         HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
@@ -1703,7 +1709,8 @@ extern "C" int cbo_gp_fit_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task
         launch_zero_pair(c->sweep_stream, qbuf, mubuf, k->m_pad);
         {
             PhaseScope ps(c, PH_CHOL);
-            launch_cholesky(c->stream, c->side_stream, c->chol_events, g->A, g->lda, g->n_pad, g->invDt, g->info, &pipe, true);
+            launch_cholesky(c->stream, c->side_stream, c->chol_events, g->A, g->lda, g->n_pad, g->invDt, g->info,
+                            chol_options(c, separate), &pipe, true);
         }
         // join: everything the sweep streams were given is done before the main stream goes on (the last
         // pair has no rows below it, so the bulk stream's last launch precedes the sweep stream's in-panel solve
@@ -1726,9 +1733,10 @@ extern "C" int cbo_gp_fit_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (*c->h_info == 0) break;
         if (*c->h_info == kCholFusedTimeout) {                 // as in cbo_gp_fit: the attempt again, separate launches
-            if (fallback.active())
+            if (separate)
                 return fail(CBO_ERR_HIP, "a fused diagonal + panel launch gave up waiting, and so did the separate-launch repeat");
-            fallback.engage(c);
+            separate = true;
+            ++c->fused_fallbacks;
             continue;
         }
         rc = next_jitter(g, &tries, &jitter);
@@ -1746,12 +1754,12 @@ extern "C" int cbo_gp_fit_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task
             HIP_TRY(hipStreamSynchronize(c->stream));
         }
         complete_finish(c, best_val, best_idx);
-        if (entry) schedule_report(c->n_cu, c->n_cu_pipe, *entry, choice, fallback.active() ? -1 : tries, us_since(t_call) * 1e-3, 0.0, 0.0);
+        if (entry) schedule_report(c->n_cu, c->n_cu_pipe, *entry, choice, separate ? -1 : tries, us_since(t_call) * 1e-3, 0.0, 0.0);
         return CBO_OK;
     }
     rc = finish_sweep(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx);
     if (rc == CBO_OK && entry)
-        schedule_report(c->n_cu, c->n_cu_pipe, *entry, choice, fallback.active() ? -1 : tries, us_since(t_call) * 1e-3, 0.0, 0.0);
+        schedule_report(c->n_cu, c->n_cu_pipe, *entry, choice, separate ? -1 : tries, us_since(t_call) * 1e-3, 0.0, 0.0);
     return rc;
 }
 
@@ -2301,10 +2309,11 @@ extern "C" int cbo_gp_posterior_samples(cbo_gp *g, int64_t m, const double *Xs, 
     double jitter = 0.0;
     int tries = 0;
     // the factor of Sigma + jitter I in c->samp_A
-    auto enqueue = [&] {
+    auto enqueue = [&](bool separate) {
         launch_factor_padding(c->stream, c->samp_A, lda, m, m_pad);
         enqueue_cov(g, k, ldv, 0, m, 0, m, true, jitter, c->samp_A, lda);
-        launch_cholesky(c->stream, c->side_stream, c->chol_events, c->samp_A, lda, m_pad, c->samp_invDt, c->samp_info);
+        launch_cholesky(c->stream, c->side_stream, c->chol_events, c->samp_A, lda, m_pad, c->samp_invDt, c->samp_info,
+                        chol_options(c, separate));
     };
     for (;;) {
         bool pd = false;
@@ -2619,8 +2628,7 @@ static int general_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_o
     HIP_TRY(hipMemsetAsync(c->W, 0, w_bytes, c->stream));
     for (int k0 = 0; k0 < (int)n_pad; k0 += 256) {
         const int klen = (k0 + 256 <= (int)n_pad) ? 256 : 128;
-        launch_gemm_update(c->stream, c->V, ldv, c->V, ldv, c->W, ldw, k0, klen, 0, k0 + klen, k0 + klen,
-                           c->pipe_chunk_blocks, true, true);
+        launch_gemm_update(c->stream, c->V, ldv, c->V, ldv, c->W, ldw, k0, klen, 0, k0 + klen, k0 + klen, true);
     }
     launch_lml_grad(c->stream, g->X, g->h, g->alpha, c->W, ldw, n_pad, c->gpart, c->part_val);
     launch_lml_terms(c->stream, g->A, g->lda, n_pad, g->z, c->part_val + 16);

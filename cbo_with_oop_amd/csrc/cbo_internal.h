@@ -182,8 +182,6 @@ struct SweepPipe {
     int64_t ldv, m_pad;
     double *zvec;                        // contiguous copy of z, written panel by panel by the diagonal kernel
     double *q, *mu;                      // zeroed on `stream` by the caller
-    int chunk_blocks;                    // row blocks per workgroup of the update kernel
-    bool half_lds;                       // 16-row stages (two workgroups per CU) for every kernel of the pipeline
     bool lower_tri;                      // the right-hand sides are lower triangular (identity: V = L^-1), so rows
                                          // [r0, r0+klen) only reach columns < r0+klen: launch just those strips
     int group;                           // G >= 2: updates in groups of G pairs (K = 256 G on `bulk`), see sweep_pipe_pair
@@ -198,16 +196,24 @@ struct SweepPipe {
 // info_dev: 1 + kCholFlagSlots ints (status word, then one publication counter per 128-row panel)
 constexpr int kCholFlagSlots = 1024;
 constexpr int kCholFusedTimeout = -2147483647 - 1;     // status word when a strip of a fused launch gave up waiting
+constexpr int kFusedSpinLimit = 1 << 22;               // polls before that give-up (negative: at the first wait)
+// The factorisation's launch forms (cbo_init reads them from the environment, DESIGN.md's knob list)
+struct CholOptions {
+    int panel_form = 4;                  // CBO_HIP_PANEL_FORM: 4 = diagonal block + row panel in one launch; 5 = the same as
+                                         // two launches, the block's and an LDS-free one of the strips; 2 = separate launches
+    int spin_limit = kFusedSpinLimit;    // CBO_HIP_FUSED_SPIN_LIMIT: polls of a fused launch's strip, of a vector chain
+    int bulk_group = 4;                  // CBO_HIP_BULK_GROUP: the most pairs per group of bulk updates (1 = pairs only)
+    int group4_rows = 10240;             // CBO_HIP_BULK_GROUP4_ROWS: groups of four while this many rows lie below the group
+};
 // info_zeroed: the caller's launch_rhs has cleared the first cholesky_info_ints(n_pad) ints of info_dev on the same stream
 void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &events, double *A, int64_t lda,
-                     int64_t n_pad, double *invDt, int *info_dev, const SweepPipe *pipe = nullptr, bool info_zeroed = false);
+                     int64_t n_pad, double *invDt, int *info_dev, const CholOptions &opt, const SweepPipe *pipe = nullptr,
+                     bool info_zeroed = false);
 inline int cholesky_info_ints(int64_t n_pad)
 {
     const int np = (int)(n_pad / 128);
     return 2 * np <= kCholFlagSlots ? 1 + 2 * np : 1;
 }
-// > 0: launch_cholesky of this thread uses that panel form (CBO_HIP_PANEL_FORM's values) whatever the environment says
-void set_panel_form_override(int form);
 // pair p of the pipelined sweep: rows [r0, r0 + klen) of the factor are final on stream `chain`
 void sweep_pipe_pair(const SweepPipe &pipe, hipStream_t chain, const double *A, int64_t lda, const double *invDt,
                      int64_t n_pad, int p, int r0, int klen);
@@ -219,13 +225,15 @@ void launch_backsolve(hipStream_t s, const double *A, int64_t lda, int64_t n_pad
 void launch_forward_vec(hipStream_t s, const double *A, int64_t lda, int64_t n_pad, const double *invDt, double *w,
                         double *out);
 void launch_gather_column(hipStream_t s, const double *V, int64_t ldv, int64_t n_pad, double *dst);
-// one-launch forms (a chain of workgroups, one per 128-row block); false = not applicable, nothing was launched.  `info`
-// is the model's status word: a give-up leaves kCholFusedTimeout in it and the caller
-// repeats the solve with the per-block launches (launch_backsolve_vec / launch_forward_vec) after resetting it.
+// one-launch forms (a chain of workgroups, one per 128-row block); false = not applicable (one block, or form 1 =
+// CBO_HIP_VEC_SOLVE_FORM's per-block launches), nothing was launched.  `info` is the model's status word: a give-up
+// (spin_limit polls) leaves kCholFusedTimeout in it and the caller repeats the solve with the per-block launches
+// (launch_backsolve_vec / launch_forward_vec) after resetting it.
 bool launch_backsolve_chain(hipStream_t s, const double *A, int64_t lda, int64_t n_pad, const double *invDt,
-                            const double *src, int64_t src_stride, double *work, double *out, int *info);
+                            const double *src, int64_t src_stride, double *work, double *out, int *info, int spin_limit,
+                            int form);
 bool launch_forward_chain(hipStream_t s, const double *A, int64_t lda, int64_t n_pad, const double *invDt, const double *w,
-                          double *out, int *info);
+                          double *out, int *info, int spin_limit, int form);
 void launch_backsolve_vec(hipStream_t s, const double *A, int64_t lda, int64_t n_pad, const double *invDt,
                           const double *src, int64_t src_stride, double *work, double *out);
 // Gradients of the posterior mean and variance w.r.t. the prediction inputs (GPy predictive_gradients), batched:
@@ -247,15 +255,11 @@ void launch_expand_interventions(hipStream_t s, const double *observed, int64_t 
 void launch_trsm_strips(hipStream_t s, const double *U, int64_t ldu, const double *invDt, double *V, int64_t ldv,
                         int64_t n, int64_t m_pad, const double *z, double *q, double *mu, bool accumulate = false,
                         bool half_lds = false);
-// C[i0_begin:i0_end, :] -= U[k0:k0+klen, i0_begin:i0_end]^T V[k0:k0+klen, :]  (C and V share the workspace V)
-void launch_trsm_update(hipStream_t s, const double *U, int64_t ldu, double *V, int64_t ldv, int k0, int klen,
-                        int i0_begin, int i0_end, int64_t m_pad, int chunk_blocks, bool half_lds = true);
-// the same kernel as a plain GEMM update with its own output:
-// C[i0_begin:i0_end, 0:m_pad] -= U[k0:k0+klen, i0_begin:i0_end]^T V[k0:k0+klen, 0:m_pad]; upper_only skips the
-// workgroups that lie entirely below the diagonal
+// C[i0_begin:i0_end, 0:m_pad] -= U[k0:k0+klen, i0_begin:i0_end]^T V[k0:k0+klen, 0:m_pad] (C may be V itself: the
+// pipelined sweep); upper_only skips the workgroups that lie entirely below the diagonal
 void launch_gemm_update(hipStream_t s, const double *U, int64_t ldu, const double *V, int64_t ldv, double *C,
-                        int64_t ldc, int k0, int klen, int i0_begin, int i0_end, int64_t m_pad, int chunk_blocks,
-                        bool half_lds, bool upper_only, const int *skip_if = nullptr);
+                        int64_t ldc, int k0, int klen, int i0_begin, int i0_end, int64_t m_pad, bool upper_only,
+                        const int *skip_if = nullptr);
 
 // One (model, candidate set) pair of a multi-set sweep of small models (kernels_chol.hip, small_sets_kernel): every
 // pointer is device memory; filled on the host per call and uploaded as an array.

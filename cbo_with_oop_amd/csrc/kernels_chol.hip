@@ -24,7 +24,6 @@
 #include <hip/hip_ext.h>
 #include <climits>
 #include <atomic>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -561,7 +560,6 @@ __global__ __launch_bounds__(256) void panel_trsm_kernel(double *A, int64_t lda,
 // the launch and everything after it in the factorisation drains) and the host then repeats the factorisation with the
 // separate-launch kernels (CBO_HIP_PANEL_FORM=2's), same bits: cbo_gp_fit / cbo_gp_fit_sweep.
 constexpr int kFusedTimeout = kCholFusedTimeout;
-constexpr int kFusedSpinLimit = 1 << 22;      // default of CBO_HIP_FUSED_SPIN_LIMIT (negative: give up at the first wait)
 
 __device__ __forceinline__ double coherent_load(const double *p)
 {
@@ -695,11 +693,6 @@ void launch_panel_fused(hipStream_t s, double *A, int64_t lda, int r0, int rcol,
     hipExtLaunchKernelGGL(potrf_panel_fused_kernel, dim3((unsigned)(n_cols / kStrip)), dim3(256), 0, s, nullptr, done, 0, A,
                           lda, r0, rcol, invDt, info, zvec, r0 + 128, flag, spin_limit, 0);
 }
-
-// Set by the host around the repeat of a factorisation whose fused launch gave up (kCholFusedTimeout): the repeat uses
-// the separate-launch kernels whatever CBO_HIP_PANEL_FORM says.
-thread_local int g_panel_form_override = 0;
-void set_panel_form_override(int form) { g_panel_form_override = form; }
 
 void launch_panel_trsm(hipStream_t s, double *A, int64_t lda, int r0, int col0, int n_cols, const double *invDt,
                        const int *skip_if, hipEvent_t done = nullptr)
@@ -1830,6 +1823,17 @@ static void launch_syrk(hipStream_t s, double *A, int64_t lda, int r0, int n1, i
                        ti_begin, skip_if);
 }
 
+// slot i of an event vector, created on first use
+static hipEvent_t event_slot(std::vector<hipEvent_t> &ev, size_t i)
+{
+    while (ev.size() <= i) {
+        hipEvent_t e;
+        hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence);
+        ev.push_back(e);
+    }
+    return ev[i];
+}
+
 // Rows [r0, r0 + klen) of U (all columns) and of z are final on stream `chain`: hand them to the sweep.
 // Two sweep streams with a look-ahead of one panel pair: `stream` solves the pair's rows of V (sd) and folds
 // them into the NEXT pair's rows only (first); `bulk` folds them into everything below that (rest).  The
@@ -1839,24 +1843,17 @@ static void launch_syrk(hipStream_t s, double *A, int64_t lda, int r0, int n1, i
 void sweep_pipe_pair(const SweepPipe &pipe, hipStream_t chain, const double *A, int64_t lda, const double *invDt,
                      int64_t n_pad, int p, int r0, int klen)
 {
-    auto pipe_event = [&](int kind, int pp) -> hipEvent_t {      // kind 0: chain, 1: sd done, 2: rest done
-        std::vector<hipEvent_t> &ev = *pipe.events;
-        const size_t slot = (size_t)(3 * pp + kind);
-        while (ev.size() <= slot) {
-            hipEvent_t e;
-            hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence);
-            ev.push_back(e);
-        }
-        return ev[slot];
+    auto pipe_event = [&](int kind, int pp) {      // kind 0: chain, 1: sd done, 2: rest done
+        return event_slot(*pipe.events, (size_t)(3 * pp + kind));
     };
     const int64_t cols = (pipe.lower_tri && r0 + klen < pipe.m_pad) ? (int64_t)(r0 + klen) : pipe.m_pad;
     const double m = (double)cols;
     hipEventRecord(pipe_event(0, p), chain);
     hipStreamWaitEvent(pipe.stream, pipe_event(0, p), 0);
     if (pipe.mark) pipe.mark(pipe.user, pipe.stream, 1, (double)klen * (double)klen * m);
+    // (every kernel of the pipeline runs on 16-row, half-LDS stages: two workgroups per CU)
     launch_trsm_strips(pipe.stream, A + (int64_t)r0 * lda + r0, lda, invDt + (int64_t)(r0 / 16) * 256,
-                       pipe.V + (int64_t)r0 * pipe.ldv, pipe.ldv, klen, cols, pipe.zvec + r0, pipe.q, pipe.mu, true,
-                       pipe.half_lds);
+                       pipe.V + (int64_t)r0 * pipe.ldv, pipe.ldv, klen, cols, pipe.zvec + r0, pipe.q, pipe.mu, true, true);
     if (pipe.mark) pipe.mark(pipe.user, pipe.stream, 0, 0.0);
     hipEventRecord(pipe_event(1, p), pipe.stream);
     const int below = r0 + klen;
@@ -1865,7 +1862,7 @@ void sweep_pipe_pair(const SweepPipe &pipe, hipStream_t chain, const double *A, 
     auto update = [&](hipStream_t st, int k0, int kl, int i0, int i1) {
         if (i0 >= i1) return;
         if (pipe.mark) pipe.mark(pipe.user, st, 1, 2.0 * (double)kl * (double)(i1 - i0) * m);
-        launch_trsm_update(st, A, lda, pipe.V, pipe.ldv, k0, kl, i0, i1, cols, pipe.chunk_blocks, pipe.half_lds);
+        launch_gemm_update(st, A, lda, pipe.V, pipe.ldv, pipe.V, pipe.ldv, k0, kl, i0, i1, cols, false);
         if (pipe.mark) pipe.mark(pipe.user, st, 0, 0.0);
     };
     // Groups of G pairs, as in launch_cholesky's bulk updates (and for the same reason: the update kernel's rate grows
@@ -1917,15 +1914,10 @@ void sweep_pipe_tail(const SweepPipe &pipe, hipStream_t chain, const double *A, 
                      int64_t n_pad, int pairs_done)
 {
     std::vector<hipEvent_t> &ev = *pipe.events;
-    const size_t slot = (size_t)(3 * pairs_done);
-    while (ev.size() <= slot) {
-        hipEvent_t e;
-        hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence);
-        ev.push_back(e);
-    }
+    const hipEvent_t last = event_slot(ev, (size_t)(3 * pairs_done));
     if (pairs_done > 0) {
-        hipEventRecord(ev[slot], pipe.stream);                                   // sd and first of the last pair
-        hipStreamWaitEvent(chain, ev[slot], 0);
+        hipEventRecord(last, pipe.stream);                                       // sd and first of the last pair
+        hipStreamWaitEvent(chain, last, 0);
         hipStreamWaitEvent(chain, ev[(size_t)(3 * (pairs_done - 1) + 2)], 0);      // rest of the last pair
     }
     const int t0 = pipe.tail_begin;
@@ -1946,7 +1938,8 @@ __global__ void zero_ints_kernel(int *p, int n)
 // side stream while the main stream factors and solves pair p; the two meet before pair p's own update of pair
 // p+1's rows (schedule inside).
 void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &events, double *A, int64_t lda,
-                     int64_t n_pad, double *invDt, int *info_dev, const SweepPipe *pipe, bool info_zeroed)
+                     int64_t n_pad, double *invDt, int *info_dev, const CholOptions &opt, const SweepPipe *pipe,
+                     bool info_zeroed)
 {
     // > 64 KiB of dynamic LDS needs the opt-in on the current device (cheap; done per call so that several
     // devices in one process are all covered)
@@ -1956,38 +1949,22 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
                         (int)sizeof(PanelShared));
     hipFuncSetAttribute(reinterpret_cast<const void *>(potrf_panel_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                         (int)sizeof(Diag2Shared));
-    // 4: diagonal block + row panel in one launch; 5: the same as two launches, the block's and an LDS-free one of the
-    // strips; 2: separate launches (lean panel kernel, beside a pipelined sweep the half-LDS strip kernel).  Any other
-    // value means 4.
-    static const int panel_form_env = [] {
-        const char *e = std::getenv("CBO_HIP_PANEL_FORM");
-        const int form = e ? std::atoi(e) : 4;
-        return (form == 2 || form == 5) ? form : 4;
-    }();
-    const int panel_form = g_panel_form_override > 0 ? g_panel_form_override : panel_form_env;
-    // polls a strip of a fused launch makes before it gives up (read per factorisation: a test sets it to -1)
-    const int spin_limit = [] { const char *e = std::getenv("CBO_HIP_FUSED_SPIN_LIMIT"); return e ? std::atoi(e) : kFusedSpinLimit; }();
     // the bulk trailing update takes the LDS-staged GEMM form (trsm_update_kernel<16>, one row block per workgroup) while
     // at least this many rows lie below the pair, the 64x64-tile SYRK from L2 fragments below that (round-2 scan)
-    constexpr int syrk_gemm_rows = 6144, syrk_gemm_chunk = 1;
-    constexpr bool syrk_gemm_half = true;
+    constexpr int syrk_gemm_rows = 6144;
     auto launch_diag = [&](int rr) {
         hipLaunchKernelGGL(potrf_diag128_v2_kernel, dim3(1), dim3(256), sizeof(Diag2Shared), s, A, lda, rr, (int)n_pad,
                            invDt, info_dev, pipe ? pipe->zvec : nullptr);
     };
     const int np = (int)(n_pad / 128);
     // info_dev[0] is the status word; info_dev[1 + 2p], [2 + 2p] the publication counts of panel p's fused launch
-    const bool fused = panel_form != 2 && 2 * np <= kCholFlagSlots;
-    const bool split = panel_form == 5;
+    const bool fused = opt.panel_form != 2 && 2 * np <= kCholFlagSlots;
+    const bool split = opt.panel_form == 5;
     // (a launch, not hipMemsetAsync: the runtime's fill costs two kernels and ~8 us of marker gaps around each)
     if (!info_zeroed) hipLaunchKernelGGL(zero_ints_kernel, dim3(1), dim3(256), 0, s, info_dev, fused ? 1 + 2 * np : 1);
     int *flags = info_dev + 1;
     const int rcol = (int)n_pad;
-    while ((int)events.size() < 2 * np + 2) {
-        hipEvent_t e;
-        hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence);
-        events.push_back(e);
-    }
+    event_slot(events, (size_t)(2 * np + 1));          // (and every slot before it)
     // the side stream starts after everything queued on the main stream so far (K assembly, rhs)
     hipEventRecord(events[2 * np], s);
     hipStreamWaitEvent(side, events[2 * np], 0);
@@ -1995,10 +1972,9 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
     // rows, so the trailing matrix below the pair is updated once with K = 256 (half the read-modify-write
     // passes); the bulk of that update runs on the side stream under the next pair's diagonal/panel work.
     double *zvec = pipe ? pipe->zvec : nullptr;
-    // unfused panel solves: the lean panel kernel, or beside a pipelined sweep the strip kernel -- the half-LDS one, which
-    // fits next to a sweep workgroup, when the pipeline runs on half-LDS stages
+    // unfused panel solves: the lean panel kernel, or beside a pipelined sweep the half-LDS strip kernel, which fits next
+    // to a sweep workgroup
     const bool lean_panel = !pipe;
-    const bool half_lds = pipe && pipe->half_lds;
     int pair = 0;
     auto sweep_rows = [&](int r0, int klen) {
         if (pipe && r0 < pipe->tail_begin) sweep_pipe_pair(*pipe, s, A, lda, invDt, n_pad, pair++, r0, klen);
@@ -2026,9 +2002,6 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
     // are used while every pair's bulk update would take the GEMM form anyway; the last ~6000 rows go pair by pair as before.
     // Groups of four while at least CBO_HIP_BULK_GROUP4_ROWS (10240) rows lie below the group, of two below that: round 5,
     // 16384 points 29.61 (G = 2) -> 29.07 ms on one box (thresholds 4096 / 6144 / 8192: 29.63 / 29.82 / 29.28).
-    static const int bulk_group = [] { const char *e = std::getenv("CBO_HIP_BULK_GROUP"); return e ? std::atoi(e) : 4; }();
-    static const int group4_rows = [] { const char *e = std::getenv("CBO_HIP_BULK_GROUP4_ROWS"); return e ? std::atoi(e) : 10240; }();
-    constexpr bool group_split = true;     // inside groups the strips of a fused launch go as an LDS-free launch of their own
     int group_left = 0;                    // pairs of the open group still to come, this one included
     int group_pairs = 0, group_g0 = 0, group_first_k = 0;
     int pending_big_a = -1;                // event index of the last bigA
@@ -2036,26 +2009,38 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
         const int r0 = 128 * k;
         const int n2 = (int)n_pad - r0 - 128;
         const int n3_pair = (int)n_pad - r0 - 256;                   // rows below this pair
-        if (group_left == 0 && bulk_group >= 2 && (fused || lean_panel)) {
+        if (group_left == 0 && opt.bulk_group >= 2 && (fused || lean_panel)) {
             // a group opens here if the rows below it still take the GEMM form for every pair of the group
             int G = 0;
-            if (bulk_group >= 4 && n3_pair - 1024 >= group4_rows && n3_pair - 1024 >= syrk_gemm_rows && n3_pair - 1024 >= 1024) G = 4;
+            if (opt.bulk_group >= 4 && n3_pair - 1024 >= opt.group4_rows && n3_pair - 1024 >= syrk_gemm_rows &&
+                n3_pair - 1024 >= 1024)
+                G = 4;
             else if (n3_pair - 512 >= syrk_gemm_rows && n3_pair - 512 >= 512) G = 2;
             if (G != 0) { group_pairs = G; group_left = G; group_g0 = r0; group_first_k = k; }
         }
         const bool grouped = group_left > 0;
         const bool first_of_group = grouped && group_left == group_pairs;
         const bool last_of_group = grouped && group_left == 1;
-        // beside a bulk update that fills the device the strips go as an LDS-free launch of their own (launch_panel_fused)
-        const bool split_now = split || (grouped && group_split);
-        if (fused && n2 > 0) launch_panel_fused(s, A, lda, r0, rcol, invDt, info_dev, zvec, n2, flags + 2 * (r0 / 128), spin_limit, nullptr, split_now);
-        else launch_diag(r0);
+        // inside groups, beside a bulk update that fills the device, the strips go as an LDS-free launch of their own
+        // (launch_panel_fused)
+        const bool split_now = split || grouped;
+        // the 128-row panel at r with `cols` columns to its right (none: the diagonal block alone); `done` completes with
+        // its last launch (a pipelined sweep's strip solves are never given one: see `carried`)
+        auto factor_panel = [&](int r, int cols, hipEvent_t done) {
+            if (fused && cols > 0) {
+                launch_panel_fused(s, A, lda, r, rcol, invDt, info_dev, zvec, cols, flags + 2 * (r / 128), opt.spin_limit,
+                                   done, split_now);
+                return;
+            }
+            launch_diag(r);
+            if (cols <= 0) return;
+            if (lean_panel) launch_panel_trsm(s, A, lda, r, r + 128, cols, invDt, info_dev, done);
+            else
+                launch_trsm_strips(s, A + (int64_t)r * lda + r, lda, invDt + (int64_t)(r / 16) * 256,
+                                   A + (int64_t)r * lda + r + 128, lda, 128, cols, nullptr, nullptr, nullptr, false, true);
+        };
+        factor_panel(r0, n2, nullptr);
         if (n2 <= 0) { sweep_rows(r0, 128); break; }
-        if (fused) {}
-        else if (lean_panel) launch_panel_trsm(s, A, lda, r0, r0 + 128, n2, invDt, info_dev);
-        else
-        launch_trsm_strips(s, A + (int64_t)r0 * lda + r0, lda, invDt + (int64_t)(r0 / 16) * 256,
-                           A + (int64_t)r0 * lda + r0 + 128, lda, 128, n2, nullptr, nullptr, nullptr, false, half_lds);
         // rows of the pair's second panel: K = 128 update with the first panel
         launch_syrk_rows(s, A, lda, r0, 128, n2, rcol, info_dev);
         const int r1 = r0 + 128;
@@ -2066,16 +2051,9 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
         const bool carried = bulk && (fused || lean_panel);
         const hipEvent_t ev_panel = (carried && gemm_form && (!grouped || last_of_group)) ? events[2 * k] : nullptr;
         const hipEvent_t ev_rows = (carried && !gemm_form) ? events[2 * k] : nullptr;
-        if (fused && n3 > 0)
-            launch_panel_fused(s, A, lda, r1, rcol, invDt, info_dev, zvec, n3, flags + 2 * (r1 / 128), spin_limit, ev_panel, split_now);
-        else launch_diag(r1);
-        if (n3 <= 0) { sweep_rows(r0, 256); break; }
-        if (fused) {}
-        else if (lean_panel) launch_panel_trsm(s, A, lda, r1, r1 + 128, n3, invDt, info_dev, ev_panel);
-        else
-        launch_trsm_strips(s, A + (int64_t)r1 * lda + r1, lda, invDt + (int64_t)(r1 / 16) * 256,
-                           A + (int64_t)r1 * lda + r1 + 128, lda, 128, n3, nullptr, nullptr, nullptr, false, half_lds);
+        factor_panel(r1, n3, ev_panel);
         sweep_rows(r0, 256);
+        if (n3 <= 0) break;
         if (grouped) {
             const int S = 256 * group_pairs, g0 = group_g0, n = (int)n_pad;
             const int next_end = (g0 + 2 * S < n) ? g0 + 2 * S : n;                   // end of G_{j+1}
@@ -2083,21 +2061,18 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
                 // the group's bulk update (K = S) on the side stream, first the rows the chain needs next
                 hipStreamWaitEvent(side, events[2 * k], 0);
                 const int a_end = (g0 + 3 * S < n) ? g0 + 3 * S : n;                  // end of G_{j+2}
-                launch_gemm_update(side, A, lda, A, lda, A, lda, g0, S, next_end, a_end, n_pad + kRhsCols, syrk_gemm_chunk,
-                                   syrk_gemm_half, true, info_dev);
+                launch_gemm_update(side, A, lda, A, lda, A, lda, g0, S, next_end, a_end, n_pad + kRhsCols, true, info_dev);
                 hipEventRecord(events[2 * group_first_k + 1], side);                  // (the first pair's slot: it has no bulk update of its own)
                 pending_big_a = 2 * group_first_k + 1;
                 if (a_end < n)
-                    launch_gemm_update(side, A, lda, A, lda, A, lda, g0, S, a_end, n, n_pad + kRhsCols, syrk_gemm_chunk,
-                                       syrk_gemm_half, true, info_dev);
+                    launch_gemm_update(side, A, lda, A, lda, A, lda, g0, S, a_end, n, n_pad + kRhsCols, true, info_dev);
                 hipEventRecord(events[2 * k + 1], side);
                 pending = 2 * k + 1;
             }
             // the next pair's rows on the chain as ever, then the rest of the rows up to the end of the next group
             launch_syrk_rows(s, A, lda, r0, 256, n3, rcol, info_dev, 256, nullptr);
             if (first_of_group && pending_big_a >= 0) hipStreamWaitEvent(s, events[pending_big_a], 0);
-            launch_gemm_update(s, A, lda, A, lda, A, lda, r0, 256, r0 + 512, next_end, n_pad + kRhsCols, syrk_gemm_chunk,
-                               syrk_gemm_half, true, info_dev);
+            launch_gemm_update(s, A, lda, A, lda, A, lda, r0, 256, r0 + 512, next_end, n_pad + kRhsCols, true, info_dev);
             --group_left;
             continue;
         }
@@ -2114,8 +2089,8 @@ void launch_cholesky(hipStream_t s, hipStream_t side, std::vector<hipEvent_t> &e
             // 64-column strips x 256-row chunks, upper part only, the rhs strip as one more strip): the 64x64-tile SYRK
             // reads its operands as fragment-shaped loads from L2 and tops out near half the fp64 MFMA rate
             if (gemm_form)
-                launch_gemm_update(side, A, lda, A, lda, A, lda, r0, 256, r0 + 256 + 256, (int)n_pad, n_pad + kRhsCols,
-                                   syrk_gemm_chunk, syrk_gemm_half, true, info_dev);
+                launch_gemm_update(side, A, lda, A, lda, A, lda, r0, 256, r0 + 256 + 256, (int)n_pad, n_pad + kRhsCols, true,
+                                   info_dev);
             else
                 launch_syrk(side, A, lda, r0, 256, n3, rcol, 4, n3 / 64, info_dev);
             hipEventRecord(events[2 * k + 1], side);
@@ -2463,17 +2438,8 @@ __global__ __launch_bounds__(256) void forward_chain_kernel(const double *__rest
     chain_publish(out + b0, sh.al);
 }
 
-// CBO_HIP_VEC_SOLVE_FORM=1: the per-block launches.  `info` is the model's status word (0 after a fit).
-static bool vec_chain_enabled(int nb)
-{
-    static const int form = [] { const char *e = std::getenv("CBO_HIP_VEC_SOLVE_FORM"); return e ? std::atoi(e) : 2; }();
-    return form != 1 && nb >= 2;
-}
-static int vec_spin_limit()
-{
-    const char *e = std::getenv("CBO_HIP_FUSED_SPIN_LIMIT");
-    return e ? std::atoi(e) : kFusedSpinLimit;
-}
+// form 1 (CBO_HIP_VEC_SOLVE_FORM=1): the per-block launches.  `info` is the model's status word (0 after a fit).
+static bool vec_chain_enabled(int nb, int form) { return form != 1 && nb >= 2; }
 
 // ~151 KB of dynamic LDS needs the opt-in ON THE CURRENT DEVICE: done per call (cheap), as launch_cholesky does, so that
 // every device of a process that drives several (cbo_comm_init_all) is covered -- a function-local static would cover
@@ -2490,29 +2456,30 @@ static bool vec_chain_opt_in()
 }
 
 bool launch_backsolve_chain(hipStream_t s, const double *A, int64_t lda, int64_t n_pad, const double *invDt,
-                            const double *src, int64_t src_stride, double *work, double *out, int *info)
+                            const double *src, int64_t src_stride, double *work, double *out, int *info, int spin_limit,
+                            int form)
 {
     const int nb = (int)(n_pad / 128);
-    if (!vec_chain_enabled(nb)) return false;
+    if (!vec_chain_enabled(nb, form)) return false;
     if (!vec_chain_opt_in()) return false;
     hipLaunchKernelGGL(copy_strided_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, src, src_stride,
                        n_pad, work);
     hipLaunchKernelGGL(fill_sentinel_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, out, n_pad);
     hipLaunchKernelGGL(backsolve_chain_kernel, dim3(nb), dim3(256), sizeof(VecChainShared), s, A, lda, invDt, nb, work, out,
-                       info, vec_spin_limit());
+                       info, spin_limit);
     // a launch the runtime refused (nothing ran): the caller takes the per-block launches, which fill `out` themselves
     return hipGetLastError() == hipSuccess;
 }
 
 bool launch_forward_chain(hipStream_t s, const double *A, int64_t lda, int64_t n_pad, const double *invDt, const double *w,
-                          double *out, int *info)
+                          double *out, int *info, int spin_limit, int form)
 {
     const int nb = (int)(n_pad / 128);
-    if (!vec_chain_enabled(nb)) return false;
+    if (!vec_chain_enabled(nb, form)) return false;
     if (!vec_chain_opt_in()) return false;
     hipLaunchKernelGGL(fill_sentinel_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, s, out, n_pad);
     hipLaunchKernelGGL(forward_chain_kernel, dim3(nb), dim3(256), sizeof(VecChainShared), s, A, lda, invDt, nb, w, out,
-                       info, vec_spin_limit());
+                       info, spin_limit);
     return hipGetLastError() == hipSuccess;          // (forward_chain_kernel leaves `w` untouched: the fallback can still use it)
 }
 

@@ -1576,23 +1576,16 @@ void launch_trsm_strips(hipStream_t s, const double *U, int64_t ldu, const doubl
         hipLaunchKernelGGL((trsm_strip8_kernel<false>), grid, dim3(512), 0, s, U, ldu, invDt, V, ldv, (int)n, z, q, mu, 0);
 }
 
-void launch_trsm_update(hipStream_t s, const double *U, int64_t ldu, double *V, int64_t ldv, int k0, int klen,
-                        int i0_begin, int i0_end, int64_t m_pad, int chunk_blocks, bool half_lds)
-{
-    launch_gemm_update(s, U, ldu, V, ldv, V, ldv, k0, klen, i0_begin, i0_end, m_pad, chunk_blocks, half_lds, false, nullptr);
-}
-
 void launch_gemm_update(hipStream_t s, const double *U, int64_t ldu, const double *V, int64_t ldv, double *C,
-                        int64_t ldc, int k0, int klen, int i0_begin, int i0_end, int64_t m_pad, int chunk_blocks,
-                        bool half_lds, bool upper_only, const int *skip_if)
+                        int64_t ldc, int k0, int klen, int i0_begin, int i0_end, int64_t m_pad, bool upper_only,
+                        const int *skip_if)
 {
     if (i0_begin >= i0_end || m_pad <= 0 || klen <= 0) return;
-    // klen: a multiple of the stage height KB (16 or 32) and at least two stages, which the vmcnt bookkeeping assumes --
+    // klen: a multiple of the stage height KB = 16 and at least two stages, which the vmcnt bookkeeping assumes --
     // 128 or 256 for a panel (pair), 512 for the bulk groups of launch_cholesky, 256 G for the groups of a pipelined sweep
-    // (G = 2..4, cbo_gp_fit_sweep clamps CBO_HIP_PIPE_GROUP to that); the row range a multiple of 128
-    const int chunk_rows = chunk_blocks * kRB;
-    const unsigned chunks = (unsigned)((i0_end - i0_begin + chunk_rows - 1) / chunk_rows);
-    const dim3 grid((unsigned)(m_pad / kStrip), chunks);
+    // (G = 2..4, cbo_init clamps CBO_HIP_PIPE_GROUP to that); the row range a multiple of 128.  One row block per workgroup
+    // (the best count since the updates go in K = 512 groups: profiles/r03_schedule_crossover.txt)
+    const dim3 grid((unsigned)(m_pad / kStrip), (unsigned)((i0_end - i0_begin + kRB - 1) / kRB));
     const int up = upper_only ? 1 : 0;
     // (Round 5: the same update on trsm_pair_kernel's regular stages -- one 512-thread workgroup per CU on 256-row pairs,
     // hand-issued loads of the next pair's C tile -- gave the same bits and lost in place: C2 step 5.40 -> 5.48 ms, the
@@ -1602,12 +1595,8 @@ void launch_gemm_update(hipStream_t s, const double *U, int64_t ldu, const doubl
     // round 3 and dropped: its K-loops are only 4-8 stages long between C moves, and two independent half-LDS workgroups
     // per CU hide those block boundaries better -- 16384-point factorisation 32.0 ms with KB = 16 x 2 workgroups,
     // 37.6-37.9 ms with either full-LDS form; C2 overlapped step 5.73 vs 6.17-6.27 ms.)
-    if (!half_lds)
-        hipLaunchKernelGGL(trsm_update_kernel<32>, grid, dim3(256), 0, s, U, ldu, V, ldv, C, ldc, k0, klen, i0_begin,
-                           i0_end, chunk_rows, up, skip_if);
-    else
-        hipLaunchKernelGGL(trsm_update_kernel<16>, grid, dim3(256), 0, s, U, ldu, V, ldv, C, ldc, k0, klen, i0_begin,
-                           i0_end, chunk_rows, up, skip_if);
+    hipLaunchKernelGGL(trsm_update_kernel<16>, grid, dim3(256), 0, s, U, ldu, V, ldv, C, ldc, k0, klen, i0_begin, i0_end, kRB,
+                       up, skip_if);
 }
 
 // ------------------------------------------------------------------------------------------------
