@@ -101,6 +101,10 @@ SIGNATURES = {
                                          c_double_p, c_double_p, c_double_p, c_double_p]),
     "cbo_acq_sweep_mes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_double,
                                          c_double_p, c_double_p, c_double_p, c_double_p, c_int64_p]),
+    "cbo_acq_sweep_constrained": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_int, c_void_pp, c_void_pp,
+                                                 c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p,
+                                                 c_double_p, c_int64_p]),
     "cbo_gp_set_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p, ctypes.c_double]),
     "cbo_gp_log_marginal": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "cbo_gp_lml_gradients": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),

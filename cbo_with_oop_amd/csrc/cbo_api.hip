@@ -144,6 +144,7 @@ struct cbo_ctx {
     GrowBuf<int> samp_info;
     GrowBuf<double> samp_Z, samp_out;
     GrowBuf<double> ivr_part;                          // cbo_gp_integrated_variance_reduction: [m][tiles] partials
+    GrowBuf<double> con_terms;                         // cbo_acq_sweep_constrained: [n_con][m_pad] probabilities of feasibility
     // small uploads (cbo_gp_upload_data / cbo_gp_set_data of a few KB, every trial of the reference's loop): one
     // pinned staging buffer the preparation kernel reads directly; `stage_done` guards its reuse
     double *stage = nullptr; hipEvent_t stage_done = nullptr; bool stage_pending = false;
@@ -1386,24 +1387,35 @@ static void complete_finish(cbo_ctx *c, double *best_val, int64_t *best_idx)
     if (c->profiling) c->timers.n_sweep += 1;
 }
 
+// Where the epilogue reads a pair's q, mu.  They are kept with the candidates (two small device copies) so that the next
+// sweep of an unchanged model skips the substitution altogether; `own`: they must END in the candidates' own buffers, also
+// with the sweep cache off (an epilogue over several pairs: the context's vectors hold one pair's at a time) -- the
+// buffers are then storage only, the stamp that would let a later sweep reuse them stays unset.
+static int settle_vectors(cbo_gp *g, cbo_cands *k, bool own, const double **q_src, const double **mu_src)
+{
+    cbo_ctx *c = g->ctx;
+    const bool cached = k->fit_stamp != 0 && k->fit_stamp == g->fit_stamp;
+    if (!cached && (c->sweep_cache || own)) {
+        const int rc = cands_cache_vectors(k);
+        if (rc != CBO_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(k->q, c->q, sizeof(double) * k->m_pad, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(k->mu, c->mu, sizeof(double) * k->m_pad, hipMemcpyDeviceToDevice, c->stream));
+        if (c->sweep_cache) k->fit_stamp = g->fit_stamp;
+    }
+    *q_src = (cached || own) ? k->q : c->q;
+    *mu_src = (cached || own) ? k->mu : c->mu;
+    return CBO_OK;
+}
+
 static int finish_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
                         double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx,
                         const MesParams *mes = nullptr)
 {
     cbo_ctx *c = g->ctx;
-    // keep q, mu with the candidates (two small device copies): the next sweep of an unchanged model skips the
-    // substitution altogether
-    const bool cached = k->fit_stamp != 0 && k->fit_stamp == g->fit_stamp;
-    if (!cached && c->sweep_cache) {
-        const int rc = cands_cache_vectors(k);
-        if (rc != CBO_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(k->q, c->q, sizeof(double) * k->m_pad, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(k->mu, c->mu, sizeof(double) * k->m_pad, hipMemcpyDeviceToDevice, c->stream));
-        k->fit_stamp = g->fit_stamp;
-    }
-    const double *q_src = cached ? k->q : c->q, *mu_src = cached ? k->mu : c->mu;
-    int rc = enqueue_finish(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, q_src, mu_src, false, true,
-                            mes);
+    const double *q_src = nullptr, *mu_src = nullptr;
+    int rc = settle_vectors(g, k, false, &q_src, &mu_src);
+    if (rc != CBO_OK) return rc;
+    rc = enqueue_finish(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, q_src, mu_src, false, true, mes);
     if (rc != CBO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     complete_finish(c, best_val, best_idx);
@@ -1531,14 +1543,12 @@ extern "C" int cbo_gp_append(cbo_gp *g, const double *x_new, double y_new, doubl
     return CBO_OK;
 }
 
-// q, mu of the candidates for the fitted model (the cached copies, one appended row, or the substitution), then the
-// epilogue: EI / cost, or max-value entropy search / cost when mes is given
-static int sweep_impl(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost, double *acq_out,
-                      double *mean_out, double *var_out, double *best_val, int64_t *best_idx, const MesParams *mes)
+// q, mu of the candidates for the fitted model: the cached copies, one appended row, or the substitution (which leaves
+// them in the context's vectors for settle_vectors)
+static int enqueue_vectors(cbo_gp *g, cbo_cands *k)
 {
     int rc = CBO_OK;
     cbo_ctx *c = g->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     if (k->keep_v && k->V && k->v_stamp != 0 && k->v_stamp == g->parent_stamp && k->v_rows == g->n - 1 &&
         k->v_rows_cap == g->n_pad && k->fit_stamp == k->v_stamp && k->q) {
         // the model is the one this V belongs to plus one observation: one new row instead of the substitution
@@ -1547,12 +1557,18 @@ static int sweep_impl(cbo_gp *g, cbo_cands *k, double y_best, int task, double e
     }
     if (!(c->sweep_cache && k->fit_stamp != 0 && k->fit_stamp == g->fit_stamp)) {
         k->fit_stamp = 0;
-        rc = enqueue_posterior(g, k);
-        if (rc != CBO_OK) return rc;
-    } else {
-        rc = grow_vectors(c, k->m_pad);                  // mean / var / acq scratch of the epilogue
-        if (rc != CBO_OK) return rc;
+        return enqueue_posterior(g, k);
     }
+    return grow_vectors(c, k->m_pad);                    // mean / var / acq scratch of the epilogue
+}
+
+// then the epilogue: EI / cost, or max-value entropy search / cost when mes is given
+static int sweep_impl(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost, double *acq_out,
+                      double *mean_out, double *var_out, double *best_val, int64_t *best_idx, const MesParams *mes)
+{
+    HIP_TRY(hipSetDevice(g->ctx->device));
+    const int rc = enqueue_vectors(g, k);
+    if (rc != CBO_OK) return rc;
     return finish_sweep(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, mes);
 }
 
@@ -1584,6 +1600,97 @@ extern "C" int cbo_acq_sweep_mes(cbo_gp *g, cbo_cands *k, int n_samples, const d
     p.variance = g->h.variance; p.noise_var = g->noise_var; p.cost = cost; p.k = n_samples;
     for (int i = 0; i < n_samples; ++i) p.mins[i] = mins[i];
     return sweep_impl(g, k, 0.0, CBO_TASK_MIN, 0.0, cost, acq_out, mean_out, var_out, best_val, best_idx, &p);
+}
+
+// ---- constrained acquisition (kernels_con.hip) -------------------------------------------------------------------------
+// EI times the constraints' probabilities of feasibility over a cost, one pass with the arg-max.  Every (model, set) pair is
+// brought up to date by the sweep's own steps (enqueue_vectors, settle_vectors), one after the other on the stream, its
+// vectors ending in the set's own buffers; then the one epilogue reads them all.
+extern "C" int cbo_acq_sweep_constrained(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
+                                         int n_con, cbo_gp *const *con_gps, cbo_cands *const *con_cands,
+                                         const double *con_value, const double *con_jitter, const int *con_sense,
+                                         double *acq_out, double *ei_out, double *pof_out, double *best_val,
+                                         int64_t *best_idx)
+{
+    if (n_con < 0 || n_con > CBO_MAX_CONSTRAINTS)
+        return fail(CBO_ERR_INVALID, "the number of constraints must be in 0.." + std::to_string(CBO_MAX_CONSTRAINTS));
+    if ((g == nullptr) != (k == nullptr)) return fail(CBO_ERR_INVALID, "gp and candidates must be given (or left out) together");
+    const bool objective = g != nullptr;
+    if (!objective && n_con < 1) return fail(CBO_ERR_INVALID, "no objective and no constraint");
+    if (!objective && ei_out) return fail(CBO_ERR_INVALID, "ei_out without an objective");
+    if (n_con > 0 && (!con_gps || !con_cands || !con_value || !con_jitter || !con_sense))
+        return fail(CBO_ERR_INVALID, "NULL argument");
+    if (!(cost > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    cbo_gp *gps[kConMaxModels];
+    cbo_cands *sets[kConMaxModels];
+    int nm = 0;
+    if (objective) { gps[nm] = g; sets[nm] = k; ++nm; }
+    for (int i = 0; i < n_con; ++i, ++nm) {
+        gps[nm] = con_gps[i];
+        sets[nm] = con_cands[i];
+        if (!std::isfinite(con_value[i]) || !std::isfinite(con_jitter[i]))
+            return fail(CBO_ERR_INVALID, "the constraints' values and jitters must be finite");
+        if (con_sense[i] != CBO_CON_LE && con_sense[i] != CBO_CON_GE)
+            return fail(CBO_ERR_INVALID, "a constraint's sense must be CBO_CON_LE or CBO_CON_GE");
+    }
+    for (int i = 0; i < nm; ++i) {
+        const int rc = check_sweep_args(gps[i], sets[i], (objective && i == 0) ? task : CBO_TASK_MIN);
+        if (rc != CBO_OK) return rc;
+        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "the pairs live on different contexts");
+        if (sets[i]->m != sets[0]->m) return fail(CBO_ERR_INVALID, "the candidate sets differ in size");
+        for (int j = 0; j < i; ++j)
+            if (sets[j] == sets[i] && gps[j] != gps[i])
+                return fail(CBO_ERR_INVALID, "one candidate set with two models: its q, mu are one model's");
+    }
+    for (int i = 0; i < nm; ++i)
+        if (!gps[i]->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t m = sets[0]->m;
+    ConParams p{};
+    p.y_best = y_best; p.ei_jitter = ei_jitter; p.cost = cost;
+    p.n_models = nm; p.has_objective = objective ? 1 : 0; p.task = objective ? task : CBO_TASK_MIN;
+    for (int i = 0; i < nm; ++i) {
+        bool seen = false;                                   // (the same pair twice: its vectors are settled already)
+        for (int j = 0; j < i; ++j) seen = seen || sets[j] == sets[i];
+        const double *q_src = sets[i]->q, *mu_src = sets[i]->mu;
+        if (!seen) {
+            int rc = enqueue_vectors(gps[i], sets[i]);
+            if (rc == CBO_OK) rc = settle_vectors(gps[i], sets[i], true, &q_src, &mu_src);
+            if (rc != CBO_OK) return rc;
+        }
+        const bool causal = gps[i]->X.sv != nullptr;
+        ConModel &md = p.mdl[i];
+        md.q = q_src; md.mu = mu_src;
+        md.pm = causal ? sets[i]->pm : nullptr; md.pv = causal ? sets[i]->pv : nullptr;
+        md.variance = gps[i]->h.variance; md.noise_var = gps[i]->noise_var;
+        const int ci = i - (objective ? 1 : 0);
+        if (ci >= 0) { md.value = con_value[ci]; md.jitter = con_jitter[ci]; md.sense = con_sense[ci]; }
+    }
+    // per-candidate outputs: acq and the objective's EI in the epilogue's vectors, the constraints' terms in one of their own
+    int rc = grow_vectors(c, sets[0]->m_pad);
+    const int64_t ldt = sets[0]->m_pad;                      // (rows of whole strips: every row starts 16-byte aligned)
+    if (rc == CBO_OK && pof_out) rc = grow(c, c->con_terms, (size_t)n_con * (size_t)ldt);
+    if (rc != CBO_OK) return rc;
+    if (ei_out) p.mdl[0].out = c->mean;
+    if (pof_out)
+        for (int i = 0; i < n_con; ++i) p.mdl[i + (objective ? 1 : 0)].out = c->con_terms + (int64_t)i * ldt;
+    const int nb = acq_blocks_for(m);
+    {
+        PhaseScope ps(c, PH_ACQ);
+        launch_constrained_acq(c->stream, p, m, acq_out ? c->acq.p : nullptr, c->part_val, c->part_idx, sets[0]->index_offset,
+                               nb);
+        launch_argmax_final(c->stream, c->part_val, c->part_idx, nb, c->h_best_val, c->h_best_idx);
+    }
+    HIP_TRY(hipGetLastError());
+    rc = copy_posterior_out(c, sets[0], acq_out, ei_out, nullptr);
+    if (rc != CBO_OK) return rc;
+    for (int i = 0; pof_out && i < n_con; ++i)
+        HIP_TRY(hipMemcpyAsync(pof_out + (int64_t)i * m, c->con_terms + (int64_t)i * ldt, sizeof(double) * (size_t)m,
+                               hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    complete_finish(c, best_val, best_idx);
+    return CBO_OK;
 }
 
 // Refit and sweep in one call, the two overlapped: what CBO.intervene() does for the set it has just

@@ -333,6 +333,27 @@ void launch_mes_acq(hipStream_t s, const double *q, const double *mu, const doub
 // one workgroup each: out[0..3) the quantiles, out[3] = left, out[4] = right; status[j] = 0 converged, 1 the bracket does
 // not change sign (scipy's ValueError), 2 no convergence within maxiter (scipy's RuntimeError).
 void launch_gumbel_quantiles(hipStream_t s, const double *mean, const double *var, int64_t m, double *out, int64_t *status);
+// ---- constrained acquisition (kernels_con.hip) ------------------------------------------------------------------
+// EI times probabilities of feasibility over a cost, from the q, mu of several (model, candidate set) pairs at once.  The
+// pointer table travels in the kernel arguments: model 0 is the objective when has_objective, every other one a constraint.
+constexpr int kConMaxModels = CBO_MAX_CONSTRAINTS + 1;
+struct ConModel {
+    const double *q, *mu, *pm, *pv;                    // pm, pv: the set's prior closures, null for a non-causal model
+    double *out;                                       // the model's own term per candidate (EI, pof_k) or null
+    double variance, noise_var;
+    double value, jitter;                              // constraints: bound and jitter
+    int sense, pad_;                                   // constraints: CBO_CON_LE / CBO_CON_GE
+};
+struct ConParams {
+    ConModel mdl[kConMaxModels];
+    double y_best, ei_jitter, cost;
+    int n_models, has_objective, task, pad_;
+};
+// acq = (((t_0 t_1) t_2) ...) / cost for i < m (acq_out may be null), t_0 = acquisition_of at cost 1 when has_objective,
+// every other t_k = ndtr(+-(value - (mean + jitter)) / sqrt(var)) of acq_kernel's mean and variance (noise included);
+// launch grid and arg-max partials as launch_acq (acq_blocks_for)
+void launch_constrained_acq(hipStream_t s, const ConParams &p, int64_t m, double *acq_out, double *part_val,
+                            int64_t *part_idx, int64_t index_offset, int n_blocks);
 // out[g] = mean of in[g*group .. (g+1)*group)
 void launch_group_mean(hipStream_t s, const double *in, int64_t n_groups, int64_t group, double *out);
 

@@ -1,0 +1,186 @@
+// Constrained acquisition for gfx950: Expected Improvement times probabilities of feasibility over a cost, with the arg-max,
+// in one pass over the candidates -- emukit's
+//     Quotient(Product(Product(ExpectedImprovement(model), ProbabilityOfFeasibility(c_0)), ProbabilityOfFeasibility(c_1)) ..., Cost)
+//
+// Restates emukit 0.4's emukit.bayesian_optimization.acquisitions.ProbabilityOfFeasibility from memory (emukit is not a
+// dependency; parity is unpinned, the contract is DESIGN.md §4f):
+//   evaluate(x):  mean, variance = model.predict(x); mean += jitter; sd = sqrt(variance);
+//                 scipy.stats.norm.cdf(max_value, mean, sd)            = ndtr((max_value - mean) / sd)
+// and emukit.core.acquisition's Product (a * b) and Quotient (a / b).  A constraint of the other sense, value <= g(x), is the
+// complement by symmetry, ndtr(-u).  Every model's mean and variance come from its q = sum V^2, mu = V^T z exactly as
+// acq_kernel forms them (kernels_acq.hip); the EI term is that kernel's acquisition_of at cost 1.
+// HBM-bound like the EI pass: 2 doubles in per model and candidate (4 for a causal one), nothing out but the workgroup's
+// arg-max partial unless per-candidate outputs are asked for.
+#include "cbo_device.h"
+
+#pragma clang fp contract(off)
+
+namespace cbo {
+
+// ndtr(+-(value - (mean + jitter)) / sd).  sd and the quotient as acquisition_of has them (one hardware estimate, the
+// quotient corrected by its own remainder: within half an ulp and a bit of the IEEE one), the density's exponential shared
+// with cephes ndtr (ndtr_with_exp).  A NaN mean or variance gives NaN.
+__device__ __forceinline__ double feasibility_of(double mean, double var, double value, double jitter, int sense)
+{
+    double s, rs;
+    bool special;
+    sqrt_and_reciprocal(var, s, rs, special);
+    const double a = value - (mean + jitter);
+    double u = a * rs;
+    u = fma(fma(-u, s, a), rs, u);
+    if (__builtin_expect(special, 0)) u = a / s;                    // (a zero or infinite variance: the IEEE quotient)
+    if (sense != CBO_CON_LE) u = -u;                                // (uniform)
+    const double e = exp_nonpositive(-(u * u) / 2.0);
+    return ndtr_with_exp(u, e);
+}
+
+// acq_kernel's structure (kernels_acq.hip; its comments say why): two consecutive candidates per lane and step (16-byte
+// loads and stores), addresses "scalar base + 32-bit lane offset", and every memory operation of a step issued in one place
+// right behind the step's only wait.  A step here is ONE model's term of one pair of candidates: the operands it prefetches
+// are the next model's (the first model's of the workgroup's next pair after the last), the result it stores the previous
+// step's -- so the registers hold two models' operands whatever the number of models, and the loop over the models has a
+// uniform trip count with the table in the kernel arguments (scalar loads).
+// CAUSAL: some model's candidates carry a prior mean / variance (the others skip those loads: uniform); OUT: per-candidate
+// results are written (acq, and each model's own term where its `out` is set).  The common call asks for neither.
+template <bool CAUSAL, bool OUT>
+__global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64_t m, double *__restrict__ acq_out,
+                                                              double *__restrict__ part_val,
+                                                              int64_t *__restrict__ part_idx, int64_t index_offset)
+{
+    double bv = -INFINITY;
+    int64_t bi = kNoIndex;
+    if (!OUT) acq_out = nullptr;
+    const int nm = p.n_models;
+    const int64_t stride = 2 * (int64_t)gridDim.x * blockDim.x;
+    int64_t cu = 2 * (int64_t)blockIdx.x * blockDim.x;
+    const unsigned lane2 = 2 * threadIdx.x;
+    const int64_t span = 2 * (int64_t)blockDim.x;
+    // operands of the pair at base + lane2 for one model (the second of an odd tail: a copy of the first, never stored)
+    auto fetch = [&](const ConModel &md, int64_t base, d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2) __attribute__((always_inline)) {
+        const double *__restrict__ q = md.q, *__restrict__ mu = md.mu, *__restrict__ pm = md.pm, *__restrict__ pv = md.pv;
+        const bool causal = CAUSAL && pv != nullptr;             // (uniform)
+        if (base + span <= m) {                                  // (uniform) every lane has its two candidates
+            q2 = *reinterpret_cast<const d2 *>(q + base + lane2);
+            mu2 = *reinterpret_cast<const d2 *>(mu + base + lane2);
+            if (causal) {
+                pm2 = *reinterpret_cast<const d2 *>(pm + base + lane2);
+                pv2 = *reinterpret_cast<const d2 *>(pv + base + lane2);
+            }
+            return;
+        }
+        const int64_t at = base + lane2;
+        if (at + 1 < m) {
+            q2 = *reinterpret_cast<const d2 *>(q + at);
+            mu2 = *reinterpret_cast<const d2 *>(mu + at);
+            if (causal) {
+                pm2 = *reinterpret_cast<const d2 *>(pm + at);
+                pv2 = *reinterpret_cast<const d2 *>(pv + at);
+            }
+        } else if (at < m) {
+            q2 = d2{q[at], q[at]};
+            mu2 = d2{mu[at], mu[at]};
+            if (causal) {
+                pm2 = d2{pm[at], pm[at]};
+                pv2 = d2{pv[at], pv[at]};
+            }
+        }
+    };
+    auto store = [&](double *__restrict__ dst, int64_t base, const d2 &v) __attribute__((always_inline)) {
+        if (!dst) return;                                        // (uniform)
+        const int64_t c = base + lane2;
+        if (base + span <= m) *reinterpret_cast<d2 *>(dst + base + lane2) = v;       // (uniform)
+        else if (c + 1 < m) *reinterpret_cast<d2 *>(dst + c) = v;
+        else if (c < m) dst[c] = v[0];
+    };
+    AcqParams ap;                                                // the fields posterior_of / acquisition_of read, per model
+    ap.y_best = p.y_best; ap.ei_jitter = p.ei_jitter; ap.cost = 1.0;
+    ap.task = p.task; ap.include_noise = 1; ap.want_ei = 1;
+    d2 qn = {0.0, 0.0}, mun = {0.0, 0.0}, pmn = {0.0, 0.0}, pvn = {0.0, 0.0};
+    // results waiting for the next step's store: one model's term, and the finished product of a pair
+    d2 term_done = {0.0, 0.0}, acq_done = {0.0, 0.0};
+    double *term_dst = nullptr;
+    int64_t term_base = 0, acq_base = -1;
+    fetch(p.mdl[0], cu, qn, mun, pmn, pvn);
+    for (; cu < m; cu += stride) {
+        const bool full = cu + span <= m;                        // uniform
+        const int64_t c = cu + lane2;
+        const bool one = full || c < m, two = full || c + 1 < m;
+        d2 acc = {0.0, 0.0};
+        for (int k = 0; k < nm; ++k) {
+            const ConModel &md = p.mdl[k];
+            d2 q2 = qn, mu2 = mun, pm2 = pmn, pv2 = pvn;
+            // (the operands are in their registers before anything below is issued; nothing memory moves across this line)
+            if (CAUSAL) asm volatile("" : "+v"(q2), "+v"(mu2), "+v"(pm2), "+v"(pv2) : : "memory");
+            else asm volatile("" : "+v"(q2), "+v"(mu2) : : "memory");
+            if (OUT) {
+                store(term_dst, term_base, term_done);
+                if (acq_base >= 0) store(acq_out, acq_base, acq_done);
+                acq_base = -1;
+            }
+            const bool last = k + 1 == nm;
+            fetch(p.mdl[last ? 0 : k + 1], last ? cu + stride : cu, qn, mun, pmn, pvn);
+            const bool causal = CAUSAL && md.pv != nullptr;      // (uniform)
+            ap.variance = md.variance;
+            ap.noise_var = md.noise_var;
+            d2 mean2, var2, t2;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                double mean, var;
+                posterior_of(q2[e], mu2[e], causal ? pm2[e] : 0.0, causal ? pv2[e] : 0.0, causal, ap, mean, var);
+                mean2[e] = mean;
+                var2[e] = var;
+            }
+            if (k == 0 && p.has_objective) {                     // (uniform) cbo_acq_sweep's acq at cost 1
+                t2[0] = acquisition_of(mean2[0], var2[0], ap);
+                t2[1] = acquisition_of(mean2[1], var2[1], ap);
+                acc = t2;
+            } else {
+                t2[0] = feasibility_of(mean2[0], var2[0], md.value, md.jitter, md.sense);
+                t2[1] = feasibility_of(mean2[1], var2[1], md.value, md.jitter, md.sense);
+                if (k == 0) acc = t2;
+                else acc = acc * t2;
+            }
+            if (OUT) { term_dst = md.out; term_base = cu; term_done = t2; }
+        }
+        if (nm == 1 && p.has_objective) {
+            // no constraint: acquisition_of's own quotient (the reciprocal of the cost, corrected by the remainder), so that
+            // the result is cbo_acq_sweep's bits for every cost
+            const double rc = 1.0 / p.cost;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const double qv = acc[e] * rc;
+                acc[e] = fma(fma(-qv, p.cost, acc[e]), rc, qv);
+            }
+        } else {
+            acc[0] = acc[0] / p.cost;                            // IEEE division (emukit's Quotient is numpy's)
+            acc[1] = acc[1] / p.cost;
+        }
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const double acq = acc[e];
+            const int64_t gi = c + e + index_offset;
+            if ((e == 0 ? one : two) && !(acq < bv) && better(acq, gi, bv, bi)) { bv = acq; bi = gi; }
+        }
+        if (OUT) { acq_done = acc; acq_base = cu; }
+    }
+    if (OUT) {
+        store(term_dst, term_base, term_done);
+        if (acq_base >= 0) store(acq_out, acq_base, acq_done);
+    }
+    block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
+}
+
+void launch_constrained_acq(hipStream_t s, const ConParams &p, int64_t m, double *acq_out, double *part_val,
+                            int64_t *part_idx, int64_t index_offset, int n_blocks)
+{
+    bool causal = false, out = acq_out != nullptr;
+    for (int k = 0; k < p.n_models; ++k) {
+        causal = causal || p.mdl[k].pv != nullptr;
+        out = out || p.mdl[k].out != nullptr;
+    }
+    auto kernel = causal ? (out ? constrained_acq_kernel<true, true> : constrained_acq_kernel<true, false>)
+                         : (out ? constrained_acq_kernel<false, true> : constrained_acq_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(256), 0, s, p, m, acq_out, part_val, part_idx, index_offset);
+}
+
+}  // namespace cbo

@@ -2,6 +2,7 @@
 (/root/reference/src/utils_functions/__init__.py star-imports the same modules)."""
 from .causal_acquisition_functions import AcquisitionQuotient, CausalExpectedImprovement, CandidateGrid  # noqa: F401
 from .causal_optimizer import CausalGradientAcquisitionOptimizer  # noqa: F401
+from .constrained import AcquisitionProduct, ProbabilityOfFeasibility  # noqa: F401
 from .cost_functions import Cost, total_cost  # noqa: F401
 from .integrated_variance import IntegratedVarianceReduction  # noqa: F401
 from .max_value_entropy import MaxValueEntropySearch  # noqa: F401

@@ -128,6 +128,12 @@ class CausalExpectedImprovement:
         ``Acquisition.__truediv__`` builds a Quotient there)."""
         return AcquisitionQuotient(self, cost)
 
+    def __mul__(self, other):
+        """``CausalExpectedImprovement(...) * ProbabilityOfFeasibility(...)``: emukit's ``Acquisition.__mul__`` builds a
+        Product there; here the flattened ``AcquisitionProduct`` of constrained.py (one device call)."""
+        from .constrained import AcquisitionProduct
+        return AcquisitionProduct([self, other])
+
 
 class AcquisitionQuotient:
     """emukit ``Quotient`` of the improvement and a ``Cost``: ``evaluate(x) = EI(x) / Cost(x)`` where the cost of

@@ -103,7 +103,8 @@ def default_grid_shape(d, budget=None):
 
 
 def find_next_y_point(space, model, current_global_best, evaluated_set, costs_functions, task='min',
-                      grid_shape=None, candidates=None, anchors="grid", num_anchor_points=None, acquisition="EI"):
+                      grid_shape=None, candidates=None, anchors="grid", num_anchor_points=None, acquisition="EI",
+                      constraints=None):
     """utils.py:29-37.  Returns (y_acquisition (1,1), x_new (1,d)).
 
     ``candidates`` (optional (M,d) array or CandidateGrid) overrides the regular grid over ``space``.
@@ -113,6 +114,9 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     ``acquisition="MES"``: emukit's ``MaxValueEntropySearch(model, space) / Cost`` over the same grid in the place of the
     causal EI (its Gumbel fit draws from numpy's global generator; ``current_global_best`` is not used).  MES minimises and
     has no gradients: ``task="max"`` and ``anchors="uniform"`` raise ``ValueError``.
+    ``constraints`` (a list of ``ProbabilityOfFeasibility``, each over the model of a node that must stay in range): the
+    grid is scored with ``EI * prod PoF / Cost`` in one device call (constrained.py); together with
+    ``acquisition="MES"`` or ``anchors="uniform"`` it raises ``ValueError``.  ``None``: nothing changes.
     """
     if acquisition not in ("EI", "MES"):
         raise ValueError(f"acquisition must be 'EI' or 'MES', not {acquisition!r}")
@@ -121,6 +125,11 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
             raise ValueError("acquisition='MES' minimises: task must be 'min'")
         if anchors != "grid":
             raise ValueError("acquisition='MES' has no gradients: anchors must be 'grid'")
+    if constraints is not None:
+        if acquisition != "EI":
+            raise ValueError("constraints multiply the causal EI: acquisition must be 'EI'")
+        if anchors != "grid":
+            raise ValueError("constraints are scored over the grid: anchors must be 'grid'")
     cost_acquisition = Cost(costs_functions, evaluated_set)
     if anchors == "uniform":
         from .causal_optimizer import CausalGradientAcquisitionOptimizer
@@ -133,6 +142,9 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
         ei = MaxValueEntropySearch(model, space)
     else:
         ei = CausalExpectedImprovement(current_global_best, task, model)
+    if constraints:
+        from .constrained import AcquisitionProduct
+        ei = AcquisitionProduct([ei] + list(constraints))      # the sets of the constraints' models follow the grid's
     own = False
     if candidates is None:
         bounds = space_bounds(space)
@@ -153,6 +165,8 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
         else:
             y = ei.sweep(x_new, cost=point_cost, want_acq=True)["acq"]
     finally:
+        if constraints:
+            ei.close()
         if own:
             grid.close()
     return y, x_new

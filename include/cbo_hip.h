@@ -238,6 +238,44 @@ int cbo_gp_mes_gumbel(cbo_gp *gp, int64_t m, const double *Xg, const double *pri
 int cbo_acq_sweep_mes(cbo_gp *gp, cbo_cands *cands, int n_samples, const double *mins, double cost, double *acq_out,
                       double *mean_out, double *var_out, double *best_val, int64_t *best_idx);
 
+/* Constrained acquisition: Expected Improvement times the probability that up to CBO_MAX_CONSTRAINTS other nodes of the
+ * graph stay inside their range, over a cost -- emukit's
+ *     Quotient(Product(Product(ExpectedImprovement, ProbabilityOfFeasibility_0), ProbabilityOfFeasibility_1) ..., Cost):
+ *     acq_i = (((EI_i * pof_0i) * pof_1i) * ...) / cost        (multiplications left to right, one IEEE division last)
+ * in ONE pass over the m candidates with the arg-max, from the q = sum V^2, mu = V^T z of n_con + 1 (model, candidate set)
+ * pairs.  emukit's ProbabilityOfFeasibility is restated from memory (emukit is not a dependency; parity is unpinned, the
+ * contract is DESIGN.md §4f).
+ *  - EI_i: what cbo_acq_sweep(gp, cands, y_best, task, ei_jitter, 1.0, ...) writes to acq_out[i], bit for bit (the 'max'
+ *    task's sign quirk included); ei_out (m, may be NULL).
+ *  - pof_ki = ndtr(u) for con_sense[k] = CBO_CON_LE (scipy.stats.norm.cdf(con_value, mean, sd)), ndtr(-u) for
+ *    CBO_CON_GE, u = (con_value[k] - (mean_ki + con_jitter[k])) / sqrt(var_ki); mean / var: constraint model k's
+ *    cbo_gp_predict(..., include_noise = 1) at candidate i of con_cands[k], bit for bit; ndtr is the cephes restatement
+ *    the EI pass uses, the quotient is within an ulp of the IEEE one.  pof_out (n_con * m, constraint-major, may be NULL).
+ *  - gp == NULL and cands == NULL: no objective, acq = (pof_0 * pof_1 * ...) / cost (ProbabilityOfFeasibility.evaluate on
+ *    its own, or a product of them); n_con >= 1, ei_out must be NULL, y_best / task / ei_jitter are not read.
+ *  - n_con = 0 (with an objective): cbo_acq_sweep's acq_out, best_val and best_idx with the same cost (only the sign of a
+ *    zero can differ).
+ *  - best_idx: lowest index on ties, NaN maximal, offset by the index_offset of the objective's set (of the first
+ *    constraint's without an objective).  acq_out (m) may be NULL.
+ * Every pair reaches its q, mu exactly as cbo_acq_sweep would (the candidates' cached copies when the fit stamp matches,
+ * one appended row after cbo_gp_append, the fp32 strip of fp32 models, the chunked substitution otherwise), one pair after
+ * the other; the vectors stay in the candidates' own buffers, also with CBO_HIP_SWEEP_CACHE=0 (same bits either way).
+ * Every set has the same m, candidate i of every set is the same intervention; a set may serve several pairs only with
+ * the same model.  Out of scope: refitting in the same call (cbo_gp_fit_sweep) and the single launch of small sets
+ * (cbo_acq_sweep_sets).  The models are only read.
+ * CBO_ERR_INVALID: n_con outside 0..CBO_MAX_CONSTRAINTS (or 0 without an objective), only one of gp / cands NULL, a NULL
+ * among the first n_con entries or a NULL array with n_con > 0, pairs on different contexts, sets whose m differ,
+ * gp->d != cands->d in a pair, a causal model whose set carries no prior, one set with two models, a non-finite con_value
+ * or con_jitter, a sense other than the two, cost <= 0 or NaN, a bad task with an objective, ei_out without one.
+ * An unfitted model: CBO_ERR_NOT_FITTED. */
+#define CBO_MAX_CONSTRAINTS 8
+enum { CBO_CON_LE = 0, CBO_CON_GE = 1 };
+int cbo_acq_sweep_constrained(cbo_gp *gp, cbo_cands *cands, double y_best, int task, double ei_jitter, double cost,
+                              int n_con, cbo_gp *const *con_gps, cbo_cands *const *con_cands,
+                              const double *con_value, const double *con_jitter, const int *con_sense,
+                              double *acq_out, double *ei_out, double *pof_out /* n_con * m, constraint-major */,
+                              double *best_val, int64_t *best_idx);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
