@@ -130,6 +130,9 @@ SIGNATURES = {
     "cbo_acq_sweep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
                                      ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_double_p,
                                      c_double_p, c_int64_p]),
+    "cbo_acq_sweep_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
+                                           ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p,
+                                           c_int64_p, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_sweep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
                                         ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_double_p,
                                         c_double_p, c_int64_p, c_int_p, c_double_p]),

@@ -145,6 +145,11 @@ struct cbo_ctx {
     GrowBuf<double> samp_Z, samp_out;
     GrowBuf<double> ivr_part;                          // cbo_gp_integrated_variance_reduction: [m][tiles] partials
     GrowBuf<double> con_terms;                         // cbo_acq_sweep_constrained: [n_con][m_pad] probabilities of feasibility
+    // cbo_acq_sweep_batch: the fantasy rows [batch_size - 1][m_pad], the working copy of q, the pivot column [n_pad], the
+    // slice sums of the pass over V [kBatchMaxSlices][m_pad], the pick's scalars, and the winners (pinned: written by kernels)
+    GrowBuf<double> batch_W, batch_q, batch_col, batch_part;
+    GrowBuf<BatchState> batch_state;
+    PinnedBuf<double> batch_h_vals; PinnedBuf<int64_t> batch_h_idxs;
     // small uploads (cbo_gp_upload_data / cbo_gp_set_data of a few KB, every trial of the reference's loop): one
     // pinned staging buffer the preparation kernel reads directly; `stage_done` guards its reuse
     double *stage = nullptr; hipEvent_t stage_done = nullptr; bool stage_pending = false;
@@ -1545,7 +1550,7 @@ extern "C" int cbo_gp_append(cbo_gp *g, const double *x_new, double y_new, doubl
 
 // q, mu of the candidates for the fitted model: the cached copies, one appended row, or the substitution (which leaves
 // them in the context's vectors for settle_vectors)
-static int enqueue_vectors(cbo_gp *g, cbo_cands *k)
+static int enqueue_vectors(cbo_gp *g, cbo_cands *k, bool *substituted = nullptr)
 {
     int rc = CBO_OK;
     cbo_ctx *c = g->ctx;
@@ -1557,6 +1562,7 @@ static int enqueue_vectors(cbo_gp *g, cbo_cands *k)
     }
     if (!(c->sweep_cache && k->fit_stamp != 0 && k->fit_stamp == g->fit_stamp)) {
         k->fit_stamp = 0;
+        if (substituted) *substituted = true;
         return enqueue_posterior(g, k);
     }
     return grow_vectors(c, k->m_pad);                    // mean / var / acq scratch of the epilogue
@@ -1579,6 +1585,123 @@ extern "C" int cbo_acq_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, d
     if (rc != CBO_OK) return rc;
     if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
     return sweep_impl(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, nullptr);
+}
+
+// ---- greedy batch selection (kernels_batch.hip) ---------------------------------------------------------
+// emukit GreedyBatchPointCalculator over a candidate set without touching the model: pick 0 is the plain sweep; every
+// further pick is one pass over the resident V = L^-1 K* whose pivot the device reads from the previous pick's winner,
+// then the EI / arg-max epilogue on the working copy of q.  Everything is queued; the call synchronises once.
+extern "C" int cbo_acq_sweep_batch(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
+                                   int batch_size, int update_incumbent, double *best_vals, int64_t *best_idxs,
+                                   double *acq_out, double *mean_out, double *var_out)
+{
+    int rc = check_sweep_args(g, k, task);
+    if (rc != CBO_OK) return rc;
+    if (batch_size < 1 || batch_size > CBO_MAX_BATCH)
+        return fail(CBO_ERR_INVALID, "batch_size must be in 1.." + std::to_string(CBO_MAX_BATCH));
+    if (batch_size > k->m) return fail(CBO_ERR_INVALID, "batch_size exceeds the number of candidates");
+    if (!best_vals || !best_idxs) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (!(cost > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    if (update_incumbent != 0 && update_incumbent != 1) return fail(CBO_ERR_INVALID, "update_incumbent must be 0 or 1");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool f32 = g->dtype == CBO_DTYPE_F32;
+    if (batch_size == 1 && !f32)
+        return sweep_impl(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_vals, best_idxs, nullptr);
+    int64_t chunk = 0, ld_ws = 0;
+    rc = ensure_workspaces(c, g->n_pad, k->m_pad, &chunk, &ld_ws);
+    if (rc != CBO_OK) return rc;
+    if (batch_size > 1 && chunk < k->m_pad)
+        return fail(CBO_ERR_UNSUPPORTED, "cbo_acq_sweep_batch needs L^-1 K* of all " + std::to_string(k->m_pad) +
+                                             " padded candidates resident at once; the workspace holds " +
+                                             std::to_string(chunk) + " columns: raise CBO_HIP_WORKSPACE_MB");
+    // q, mu of pick 0 as cbo_acq_sweep reaches them; an fp32 model answers from its fp64 factor and leaves the
+    // candidates' cache (which holds the fp32 sweep's vectors) alone
+    const double *q_src = nullptr, *mu_src = nullptr;
+    bool substituted = false;
+    if (f32) {
+        rc = enqueue_posterior(g, k, true);
+        substituted = true;
+        q_src = c->q; mu_src = c->mu;
+    } else {
+        rc = enqueue_vectors(g, k, &substituted);
+        if (rc == CBO_OK) rc = settle_vectors(g, k, false, &q_src, &mu_src);
+    }
+    if (rc != CBO_OK) return rc;
+    auto kept = [&] {
+        return k->keep_v && k->V && k->v_stamp != 0 && k->v_stamp == g->fit_stamp && k->v_rows == g->n &&
+               k->v_rows_cap == g->n_pad;
+    };
+    const double *V = nullptr;
+    int64_t ldv = 0;
+    if (batch_size > 1) {
+        if (!kept() && !substituted) {           // q, mu came from the cache (q_src is the candidates' copy): V alone
+            rc = enqueue_posterior(g, k);
+            if (rc != CBO_OK) return rc;
+        }
+        if (kept()) { V = k->V; ldv = k->v_ld; }
+        else { V = c->V; ldv = ld_ws; }
+    }
+    const int64_t m_pad = k->m_pad;
+    rc = grow(c, c->batch_state, 1);
+    if (rc == CBO_OK) rc = grow(c, c->batch_h_vals, CBO_MAX_BATCH);
+    if (rc == CBO_OK) rc = grow(c, c->batch_h_idxs, CBO_MAX_BATCH);
+    if (rc == CBO_OK && batch_size > 1) rc = grow(c, c->batch_W, (size_t)(batch_size - 1) * (size_t)m_pad);
+    if (rc == CBO_OK && batch_size > 1) rc = grow(c, c->batch_q, (size_t)m_pad);
+    if (rc == CBO_OK && batch_size > 1) rc = grow(c, c->batch_col, (size_t)g->n_pad);
+    if (rc == CBO_OK && batch_size > 1) rc = grow(c, c->batch_part, (size_t)batch_slices(g->n) * (size_t)m_pad);
+    if (rc != CBO_OK) return rc;
+    const bool causal = g->X.sv != nullptr;
+    const double *pm = causal ? k->pm : nullptr, *pv = causal ? k->pv : nullptr;
+    AcqParams p;
+    p.variance = g->h.variance; p.noise_var = g->noise_var; p.y_best = y_best; p.ei_jitter = ei_jitter; p.cost = cost;
+    p.task = task; p.include_noise = 1; p.want_ei = 1;
+    const int nb = acq_blocks_for(k->m);
+    {
+        PhaseScope ps(c, PH_ACQ);
+        launch_batch_state_init(c->stream, c->batch_state, y_best);
+        const double *q_cur = q_src;
+        for (int t = 0; t < batch_size; ++t) {
+            const bool last = t == batch_size - 1;
+            if (t == 1)
+                HIP_TRY(hipMemcpyAsync(c->batch_q, q_src, sizeof(double) * m_pad, hipMemcpyDeviceToDevice, c->stream));
+            if (t >= 1) {
+                BatchPivotArgs pa{};
+                pa.best_val = c->best_val; pa.best_idx = c->best_idx;
+                pa.index_offset = k->index_offset; pa.m = k->m; pa.m_pad = m_pad; pa.n = g->n;
+                pa.V = V; pa.ldv = ldv; pa.col = c->batch_col; pa.W = c->batch_W;
+                pa.q = c->batch_q; pa.mu = mu_src; pa.pm = pm; pa.pv = pv;
+                pa.xs = k->P.xs; pa.sq = k->P.sq; pa.sv = causal ? k->P.sv : nullptr; pa.ldx = k->P.ld; pa.dims = k->d;
+                pa.variance = g->h.variance; pa.noise_var = g->noise_var;
+                pa.t = t; pa.task = task; pa.update_incumbent = update_incumbent;
+                pa.state = c->batch_state; pa.h_vals = c->batch_h_vals; pa.h_idxs = c->batch_h_idxs;
+                BatchFinalArgs fa{};
+                fa.m = k->m; fa.m_pad = m_pad; fa.W = c->batch_W; fa.q = c->batch_q;
+                fa.xs = k->P.xs; fa.sq = k->P.sq; fa.sv = pa.sv; fa.ldx = k->P.ld;
+                fa.variance = g->h.variance; fa.inv_l2 = 1.0 / (g->h.lengthscale * g->h.lengthscale);
+                fa.t = t; fa.state = c->batch_state;
+                launch_batch_pick(c->stream, pa, fa, c->batch_col, c->batch_part);
+                q_cur = c->batch_q;
+                if (update_incumbent) p.y_best_dev = &c->batch_state.p->y_best;
+            }
+            launch_acq(c->stream, q_cur, mu_src, pm, pv, k->m, p, (last && mean_out) ? c->mean.p : nullptr,
+                       (last && var_out) ? c->var.p : nullptr, (last && acq_out) ? c->acq.p : nullptr, c->part_val,
+                       c->part_idx, k->index_offset, nb);
+            launch_argmax_final(c->stream, c->part_val, c->part_idx, nb, c->best_val, c->best_idx);
+        }
+        launch_batch_record(c->stream, c->best_val, c->best_idx, batch_size - 1, c->batch_h_vals, c->batch_h_idxs);
+    }
+    HIP_TRY(hipGetLastError());
+    rc = copy_posterior_out(c, k, acq_out, mean_out, var_out);
+    if (rc != CBO_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int t = 0; t < batch_size; ++t) {
+        best_vals[t] = c->batch_h_vals.p[t];
+        best_idxs[t] = c->batch_h_idxs.p[t];
+    }
+    if (c->profiling) c->timers.n_sweep += 1;
+    return CBO_OK;
 }
 
 // ---- max-value entropy search (kernels_mes.hip) ------------------------------------------------------------------------

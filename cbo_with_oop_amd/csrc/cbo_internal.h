@@ -308,6 +308,7 @@ void launch_small_sets(hipStream_t s, const cbo_small_set *sets, int n_sets, int
 struct AcqParams {
     double variance, noise_var, y_best, ei_jitter, cost;
     int task, include_noise, want_ei;
+    const double *y_best_dev = nullptr;                // when set, acq_kernel reads the incumbent from here (device memory)
 };
 // var = clip(kss - q) (+ noise), mean = mu + m(X*), acq = +-EI / cost; per-block arg-max partials.
 void launch_acq(hipStream_t s, const double *q, const double *mu, const double *pm, const double *pv, int64_t m,
@@ -379,6 +380,45 @@ void launch_append_commit(hipStream_t s, double *A, int64_t lda, int64_t n, int6
 int append_row_slices(int64_t n);
 void launch_append_row(hipStream_t s, double *V, int64_t ldv, int64_t n, const double *lvec, int64_t m_pad,
                        const double *krow, double d, double zn, double *partial, double *q, double *mu);
+
+// ---- greedy batch selection (kernels_batch.hip) --------------------------------------------------
+// One further pick of cbo_acq_sweep_batch.  Pick t >= 1 reads its pivot -- the winner of pick t - 1 -- from device memory.
+constexpr int kBatchMaxSlices = 64;                    // row slices of the pass over V (partial: kBatchMaxSlices x m_pad)
+struct BatchState {                                    // the current pick's scalars, device memory
+    double d;                                          // sqrt of the believed point's predictive variance + 1e-8
+    double x[CBO_MAX_DIM], sq, sv;                     // its scaled coordinates, |x|^2, sqrt(v(x))
+    double y_best;                                     // the incumbent (moves with update_incumbent)
+    double wp[CBO_MAX_BATCH];                          // W[s][p] of the earlier fantasy rows
+    int64_t p;                                         // its local index
+};
+struct BatchPivotArgs {
+    const double *best_val; const int64_t *best_idx;   // device: the previous pick's winner
+    int64_t index_offset, m, m_pad, n;
+    const double *V; int64_t ldv;
+    double *col;                                       // [n] the pivot column, contiguous
+    const double *W;                                   // [t - 1][m_pad] earlier fantasy rows
+    const double *q, *mu, *pm, *pv;                    // working q; mu and the prior closures (pm, pv null: non-causal)
+    const double *xs, *sq, *sv; int64_t ldx; int dims; // the candidates' scaled SoA points
+    double variance, noise_var;
+    int t, task, update_incumbent;
+    BatchState *state;
+    double *h_vals; int64_t *h_idxs;                   // pinned host: slot t - 1 takes the previous winner
+};
+struct BatchFinalArgs {
+    const double *partial; int slices;                 // set by the launcher
+    int64_t m, m_pad;
+    double *W; double *q;                              // row t - 1 of W is written, q updated in place
+    const double *xs, *sq, *sv; int64_t ldx;           // sv null: non-causal
+    double variance, inv_l2;
+    int t;
+    const BatchState *state;
+};
+int batch_slices(int64_t n);
+void launch_batch_state_init(hipStream_t s, BatchState *st, double y_best);
+void launch_batch_record(hipStream_t s, const double *best_val, const int64_t *best_idx, int slot, double *h_vals,
+                         int64_t *h_idxs);
+// pivot, pass and final stage of one pick; col: n doubles, partial: batch_slices(n) * m_pad doubles of scratch
+void launch_batch_pick(hipStream_t s, const BatchPivotArgs &pa, BatchFinalArgs fa, double *col, double *partial);
 
 // Monte-Carlo target of an additive SEM: mean_out[i] = mean over draws of node `target` under intervention i.
 // partial: m * sem_partial_blocks(n_draws) doubles of workspace.

@@ -32,6 +32,7 @@ __global__ __launch_bounds__(256) void acq_kernel(const double *__restrict__ q, 
 {
     double bv = -INFINITY;
     int64_t bi = kNoIndex;
+    if (p.y_best_dev) p.y_best = *p.y_best_dev;                  // (uniform) cbo_acq_sweep_batch: the incumbent lives on the device
     constexpr bool causal = CAUSAL;
     if (!MV) { mean_out = nullptr; var_out = nullptr; }
     const int64_t stride = 2 * (int64_t)gridDim.x * blockDim.x;

@@ -96,6 +96,38 @@ class CausalExpectedImprovement:
         return {"best_val": best_val.value, "best_idx": best_idx.value, "acq": col(acq), "mean": col(mean),
                 "var": col(var)}
 
+    def sweep_batch(self, candidates, batch_size, cost=1.0, update_incumbent=False, want_acq=False, want_posterior=False):
+        """Greedy batch selection (emukit ``GreedyBatchPointCalculator``, the Kriging believer) in ONE device call
+        (``cbo_acq_sweep_batch``): pick the best candidate, believe the model's own prediction there, pick again,
+        ``batch_size`` times; the model is not touched.  Returns dict(best_val (B,), best_idx (B,), acq, mean, var) -- the
+        per-candidate arrays are the state at the LAST pick.  ``update_incumbent=False`` keeps this acquisition's incumbent
+        for the whole batch (it is a constructor argument, as in the reference); ``True`` lowers it to the believed value
+        after each pick (raises it for task 'max'), as emukit's own ``ExpectedImprovement`` would see it through
+        ``min(model.Y)``.  Pick 0 is ``sweep``'s result, bit for bit."""
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+            raise ValueError(f"batch_size must be a positive int, not {batch_size!r}")
+        batch_size = int(batch_size)
+        own = not isinstance(candidates, CandidateGrid)
+        grid = CandidateGrid(candidates, self.model) if own else candidates
+        m = len(grid)
+        acq = np.empty(m) if want_acq else None
+        mean = np.empty(m) if want_posterior else None
+        var = np.empty(m) if want_posterior else None
+        best_vals = np.empty(batch_size)
+        best_idxs = np.empty(batch_size, dtype=np.int64)
+        try:
+            self.model.ensure_fitted()
+            _lib.check(_lib.load().cbo_acq_sweep_batch(
+                self.model._handle, grid._handle, float(np.asarray(self.current_global_min).reshape(-1)[0]),
+                _lib.TASK_CODE[self.task], float(self.jitter), float(cost), batch_size, int(bool(update_incumbent)),
+                _lib.dptr(best_vals), best_idxs.ctypes.data_as(_lib.c_int64_p), _lib.dptr(acq), _lib.dptr(mean),
+                _lib.dptr(var)))
+        finally:
+            if own:
+                grid.close()
+        col = lambda a: None if a is None else a[:, None]
+        return {"best_val": best_vals, "best_idx": best_idxs, "acq": col(acq), "mean": col(mean), "var": col(var)}
+
     def evaluate(self, x):
         """(M,1) improvement, as the reference's ``evaluate`` (:27-43)."""
         return self.sweep(x, cost=1.0, want_acq=True)["acq"]
@@ -149,6 +181,10 @@ class AcquisitionQuotient:
     def sweep(self, candidates, **kwargs):
         return self.numerator.sweep(candidates, cost=float(self.denominator.evaluate(self._points(candidates))),
                                     **kwargs)
+
+    def sweep_batch(self, candidates, batch_size, **kwargs):
+        return self.numerator.sweep_batch(candidates, batch_size,
+                                          cost=float(self.denominator.evaluate(self._points(candidates))), **kwargs)
 
     def evaluate(self, x):
         return self.sweep(x, want_acq=True)["acq"]

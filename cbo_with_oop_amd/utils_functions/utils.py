@@ -104,7 +104,7 @@ def default_grid_shape(d, budget=None):
 
 def find_next_y_point(space, model, current_global_best, evaluated_set, costs_functions, task='min',
                       grid_shape=None, candidates=None, anchors="grid", num_anchor_points=None, acquisition="EI",
-                      constraints=None):
+                      batch_size=None, constraints=None):
     """utils.py:29-37.  Returns (y_acquisition (1,1), x_new (1,d)).
 
     ``candidates`` (optional (M,d) array or CandidateGrid) overrides the regular grid over ``space``.
@@ -117,7 +117,19 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     ``constraints`` (a list of ``ProbabilityOfFeasibility``, each over the model of a node that must stay in range): the
     grid is scored with ``EI * prod PoF / Cost`` in one device call (constrained.py); together with
     ``acquisition="MES"`` or ``anchors="uniform"`` it raises ``ValueError``.  ``None``: nothing changes.
+    ``batch_size`` (a positive int): greedy batch selection over the grid (greedy_batch.py, one ``cbo_acq_sweep_batch``
+    call): returns (y (B,1), x (B,d)), row 0 being the single-point result; together with ``acquisition="MES"``,
+    ``constraints`` or ``anchors="uniform"`` it raises ``ValueError``.  ``None``: nothing changes.
     """
+    if batch_size is not None:
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+            raise ValueError(f"batch_size must be a positive int, not {batch_size!r}")
+        if acquisition != "EI":
+            raise ValueError("batch selection believes the causal EI's model: acquisition must be 'EI'")
+        if constraints is not None:
+            raise ValueError("batch selection is not defined for constrained acquisitions: constraints must be None")
+        if anchors != "grid":
+            raise ValueError("batch selection picks from the grid: anchors must be 'grid'")
     if acquisition not in ("EI", "MES"):
         raise ValueError(f"acquisition must be 'EI' or 'MES', not {acquisition!r}")
     if acquisition == "MES":
@@ -156,6 +168,8 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
         grid, own = CandidateGrid(candidates, model), True
     try:
         batch_cost = float(cost_acquisition.evaluate(grid.points))      # ONE scalar for the batch (Quotient)
+        if batch_size is not None:
+            return _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, int(batch_size))
         res = ei.sweep(grid, cost=batch_cost)
         x_new = grid.points[res["best_idx"] - grid.index_offset][None, :].copy()
         # utils.py:36 re-evaluates the acquisition at x_new alone; only variable costs change the value
@@ -169,6 +183,21 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
             ei.close()
         if own:
             grid.close()
+    return y, x_new
+
+
+def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
+    """``find_next_y_point(batch_size=B)``: (y (B,1), x (B,d)) of one ``sweep_batch``.  y[t] is the pick's acquisition over
+    the point's own cost where variable costs make that differ from the batch's (utils.py:36): pick 0 by the single-point
+    path's re-evaluation, the later picks -- whose believed model exists on the device only -- by rescaling."""
+    res = ei.sweep_batch(grid, batch_size, cost=batch_cost)
+    x_new = grid.points[res["best_idx"] - grid.index_offset].copy()
+    y = np.asarray(res["best_val"], dtype=np.float64).reshape(-1, 1).copy()
+    for t in range(batch_size):
+        point_cost = float(cost_acquisition.evaluate(x_new[t:t + 1]))
+        if point_cost != batch_cost:
+            y[t, 0] = (ei.sweep(x_new[t:t + 1], cost=point_cost, want_acq=True)["acq"][0, 0] if t == 0
+                       else y[t, 0] * batch_cost / point_cost)
     return y, x_new
 
 

@@ -370,6 +370,36 @@ int cbo_acq_sweep(cbo_gp *gp, cbo_cands *cands, double y_best, int task, double 
                   double cost, double *acq_out, double *mean_out, double *var_out, double *best_val,
                   int64_t *best_idx);
 
+/* Greedy batch selection: emukit's GreedyBatchPointCalculator (the Kriging believer) over a candidate set.  Pick the
+ * arg-max, add it to the model as a fake observation whose y is the model's own prediction there, pick again,
+ * batch_size times in all -- without touching the model.
+ *  - Pick 0 is cbo_acq_sweep(gp, cands, y_best, task, ei_jitter, cost, ...): best_vals[0] / best_idxs[0] are its bits and,
+ *    with batch_size == 1, so are acq_out / mean_out / var_out.  q, mu are reached as cbo_acq_sweep reaches them (the
+ *    candidates' cached copies, a kept solution whose stamp matches, one appended row, else the substitution); fp32
+ *    models answer from the fp64 factor (the fp64 model's result).
+ *  - Pick t >= 1, with p the local index of pick t - 1 (read on the device; one synchronisation for the whole batch):
+ *        s2  = max(Kdiag_p - q_p, 1e-15) + noise_var + 1e-8      (cbo_gp_predict's clipped latent variance + what
+ *        d   = sqrt(s2)                                            cbo_gp_fit puts on Ky's diagonal; Kdiag_p = variance + v(x_p))
+ *        c_j = k(x_p, x_j) - sum_{i<n} V_ip V_ij - sum_{s<t} W_sp W_sj
+ *        W_tj = c_j / d,   q_j <- q_j + W_tj^2,   mu_j unchanged (the believed residual is zero)
+ *    with V = L^-1 K* and k in the kernel-matrix kernel's operation order (X2 explicit), then the EI / cost / arg-max pass
+ *    of cbo_acq_sweep on the updated q: lowest index on ties, NaN maximal, index_offset added, task max's sign quirk.
+ *  - update_incumbent = 0: y_best stays fixed (the reference's CausalExpectedImprovement, whose incumbent is a constructor
+ *    argument); 1: after each pick y_best <- min(y_best, mean_p) (max for CBO_TASK_MAX) on the device -- what emukit's
+ *    ExpectedImprovement sees through min(model.Y) once the believed point is in the data.
+ *  - acq_out / mean_out / var_out (m doubles each, may be NULL): the state at the LAST pick.
+ *  - The model (factor, z, alpha, fitted state) and the candidates (cached q, mu, kept V, stamps) are left as they were:
+ *    the fantasy rows W and the working copy of q live in the context's scratch.  A cbo_acq_sweep after the call returns
+ *    the bits it returned before; two identical calls return the same bits (fixed summation orders).
+ *  - batch_size > 1 needs V of ALL candidates resident at once: the candidates' own buffer (cbo_cands_keep_solution) or
+ *    one chunk of the workspace; CBO_ERR_UNSUPPORTED (naming CBO_HIP_WORKSPACE_MB) when the workspace holds fewer columns.
+ * CBO_ERR_INVALID: cbo_acq_sweep's argument checks; batch_size outside 1..CBO_MAX_BATCH or above the candidate count; NULL
+ * best_vals / best_idxs; cost <= 0 or NaN; update_incumbent other than 0 or 1.  Unfitted model: CBO_ERR_NOT_FITTED. */
+#define CBO_MAX_BATCH 64
+int cbo_acq_sweep_batch(cbo_gp *gp, cbo_cands *cands, double y_best, int task, double ei_jitter, double cost,
+                        int batch_size, int update_incumbent, double *best_vals, int64_t *best_idxs, double *acq_out,
+                        double *mean_out, double *var_out);
+
 /* Refit (as cbo_gp_fit, jitchol ladder included) and sweep (as cbo_acq_sweep) in one call, overlapped: the
  * sweep's substitution advances panel by panel on a second stream while the factorisation's chain of short
  * kernels runs.  This is the pair of calls CBO.intervene() makes for the set it has just intervened on
