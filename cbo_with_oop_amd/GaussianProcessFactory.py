@@ -401,6 +401,28 @@ class HipGaussianProcess:
         self._y_flat = np.ascontiguousarray(self.Y[:, 0])
         return True
 
+    def append_block(self, X_new, Y_new):
+        """``k`` more observations in one device step (the results of a batch coming back together): the factor grows
+        by ``k`` columns instead of being rebuilt (``cbo_gp_append_block``, at most ``_lib.MAX_APPEND`` points per call).
+        Returns False -- and changes nothing -- when the shortcut does not apply (model not fitted yet, jitter in the
+        factor, padded size exhausted, fp32 model, non-positive pivot); the caller then uses ``set_data``."""
+        if self.stale:
+            return False
+        X_new = _lib.as_f64(X_new).reshape(-1, self.input_dim)
+        y_new = _lib.as_f64(Y_new).reshape(-1)
+        if y_new.shape[0] != X_new.shape[0]:
+            raise ValueError(f"X_new has {X_new.shape[0]} rows, Y_new {y_new.shape[0]}")
+        pm, pv = self._prior(X_new)
+        done = ctypes.c_int(0)
+        _lib.check(self._lib.cbo_gp_append_block(self._handle, X_new.shape[0], _lib.dptr(X_new), _lib.dptr(y_new),
+                                                 _lib.dptr(pm), _lib.dptr(pv), ctypes.byref(done)))
+        if not done.value:
+            return False
+        self.X = np.vstack([self.X, X_new])
+        self.Y = np.vstack([self.Y, y_new[:, None]])
+        self._y_flat = np.ascontiguousarray(self.Y[:, 0])
+        return True
+
     def _grew_by_one_row(self, X, Y):
         """The new data are the resident ones plus one observation (what src/Monitor.py:148-160 produces every
         trial) and the model is fitted: the append shortcut applies."""

@@ -20,6 +20,7 @@ c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 
 ABI_VERSION = 5          # include/cbo_hip.h: CBO_HIP_ABI_VERSION
 MAX_DIM = 8              # CBO_MAX_DIM
+MAX_APPEND = 64          # CBO_MAX_APPEND
 CBO_OK = 0
 CBO_ERR_INVALID = -1
 CBO_ERR_HIP = -2
@@ -127,6 +128,8 @@ SIGNATURES = {
     "cbo_cands_keep_solution": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "cbo_gp_append": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                      c_int_p]),
+    "cbo_gp_append_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                           c_int_p]),
     "cbo_acq_sweep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
                                      ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_double_p,
                                      c_double_p, c_int64_p]),

@@ -148,6 +148,7 @@ struct cbo_ctx {
     // cbo_acq_sweep_batch: the fantasy rows [batch_size - 1][m_pad], the working copy of q, the pivot column [n_pad], the
     // slice sums of the pass over V [kBatchMaxSlices][m_pad], the pick's scalars, and the winners (pinned: written by kernels)
     GrowBuf<double> batch_W, batch_q, batch_col, batch_part;
+    GrowBuf<double> append_part;                       // block append: slice sums of the pass over V [slices][kp][m_pad]
     GrowBuf<BatchState> batch_state;
     PinnedBuf<double> batch_h_vals; PinnedBuf<int64_t> batch_h_idxs;
     // small uploads (cbo_gp_upload_data / cbo_gp_set_data of a few KB, every trial of the reference's loop): one
@@ -183,6 +184,20 @@ struct cbo_gp {
     double append_d = 0.0, append_zn = 0.0;
     double *lvec = nullptr;          // [n_pad] the new column of U, contiguous
     cbo_cands *probe = nullptr;      // the appended point as a one-candidate set (scaled coordinates, prior)
+    // cbo_gp_append_block: the last block, allocated on first use.  Two sides: a call builds its block on the side that
+    // is not current and makes it current only when it commits, so a declined call leaves the last block's intact.
+    int k_last = 1;                  // observations the last successful append added (1: cbo_gp_append)
+    int blk_side = 0;                // the side that holds the last committed block
+    int64_t blk_rows = 0;            // padded rows the buffers below were allocated for
+    double *blk_mem = nullptr;       // everything below, one allocation
+    double *blk_B[2] = {nullptr, nullptr};       // [n_pad][64]  B = L^-1 K(X, Xb)
+    double *blk_L22[2] = {nullptr, nullptr};     // [64][64]     lower Cholesky factor of the Schur block
+    double *blk_zb[2] = {nullptr, nullptr};      // [64]
+    double *blk_y[2] = {nullptr, nullptr};       // [64]         the block's targets as uploaded
+    double *blk_Kbb[2] = {nullptr, nullptr};     // [64][80]     K(Xb, Xb)
+    double *blk_part = nullptr;                  // [64][65][64] slice sums of B^T B and B^T z
+    int *blk_status = nullptr;                   // the Schur kernel's status word
+    cbo_cands *blk_probe[2] = {nullptr, nullptr};   // the block's points as a candidate set (scaled coordinates, prior)
     // backward substitution through the forward kernel (prediction gradients of whole grids): the reversed factor and
     // its diagonal-tile inverses, built on first use after a fit; 1 / lengthscale per dimension (ARD)
     double *T = nullptr, *invT = nullptr, *inv_ls_dev = nullptr;
@@ -667,8 +682,11 @@ extern "C" void cbo_gp_destroy(cbo_gp *g)
 {
     if (g && g->probe) { cbo_cands_destroy(g->probe); g->probe = nullptr; }
     if (!g) return;
+    for (cbo_cands *&p : g->blk_probe)
+        if (p) { cbo_cands_destroy(p); p = nullptr; }
     hipSetDevice(g->ctx->device);
     hipStreamSynchronize(g->ctx->stream);
+    hipFree(g->blk_mem);
     free_gp_data(g);
     hipFree(g->info);
     hipFree(g->ls_dev); hipFree(g->inv_ls_dev);
@@ -1541,10 +1559,161 @@ extern "C" int cbo_gp_append(cbo_gp *g, const double *x_new, double y_new, doubl
     g->X.n = g->n;
     g->append_d = d;
     g->append_zn = zn;
+    g->k_last = 1;
     g->parent_stamp = g->fit_stamp;
     g->fit_stamp = ++g_fit_stamp;
     g->alpha_ready = false;
     *appended_out = 1;
+    return CBO_OK;
+}
+
+// ---- block append (kernels_append.hip) --------------------------------------------------------------------
+// the model's block buffers for its padded size (one allocation; a model whose padded size changed was refitted since)
+static int ensure_block_buffers(cbo_gp *g)
+{
+    cbo_ctx *c = g->ctx;
+    if (g->blk_mem && g->blk_rows == g->n_pad) return CBO_OK;
+    if (g->blk_mem) HIP_TRY(hipStreamSynchronize(c->stream));
+    hipFree(g->blk_mem);
+    g->blk_mem = nullptr; g->blk_rows = 0;
+    const size_t per_side = (size_t)g->n_pad * kAppendLd + (size_t)kAppendLd * kAppendLd + 2 * (size_t)kAppendLd +
+                            (size_t)kAppendLd * (kAppendLd + kLdExtra);
+    const size_t part = (size_t)64 * (kAppendLd + 1) * kAppendLd;
+    const size_t total = 2 * per_side + part + 2;                     // the last two doubles hold the status word
+    const hipError_t e = hipMalloc(&g->blk_mem, sizeof(double) * total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        g->blk_mem = nullptr;
+        return fail(CBO_ERR_HIP, std::string("block append buffers: ") + hipGetErrorString(e));
+    }
+    HIP_TRY(hipMemsetAsync(g->blk_mem, 0, sizeof(double) * total, c->stream));
+    double *p = g->blk_mem;
+    for (int s = 0; s < 2; ++s) {
+        g->blk_B[s] = p; p += (size_t)g->n_pad * kAppendLd;
+        g->blk_L22[s] = p; p += (size_t)kAppendLd * kAppendLd;
+        g->blk_zb[s] = p; p += kAppendLd;
+        g->blk_y[s] = p; p += kAppendLd;
+        g->blk_Kbb[s] = p; p += (size_t)kAppendLd * (kAppendLd + kLdExtra);
+    }
+    g->blk_part = p; p += part;
+    g->blk_status = reinterpret_cast<int *>(p);
+    g->blk_rows = g->n_pad;
+    return CBO_OK;
+}
+
+extern "C" int cbo_gp_append_block(cbo_gp *g, int k, const double *X_new, const double *y_new,
+                                   const double *prior_mean_new, const double *prior_var_new, int *appended_out)
+{
+    if (!g || !X_new || !y_new || !appended_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    *appended_out = 0;
+    if (k < 1 || k > CBO_MAX_APPEND)
+        return fail(CBO_ERR_INVALID, "k must be in 1.." + std::to_string(CBO_MAX_APPEND));
+    const bool causal = g->X.sv != nullptr;
+    if (causal && (!prior_mean_new || !prior_var_new))
+        return fail(CBO_ERR_INVALID, "a causal model needs the prior mean and the prior variance of the new points");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    if (k == 1)
+        return cbo_gp_append(g, X_new, y_new[0], causal ? prior_mean_new[0] : 0.0, causal ? prior_var_new[0] : 0.0,
+                             appended_out);
+    if (g->tries != 0 || g->n + k > g->n_pad) return CBO_OK;
+    if (g->dtype != CBO_DTYPE_F64) return CBO_OK;
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_block_buffers(g);
+    if (rc != CBO_OK) return rc;
+    const int side = 1 - g->blk_side;
+    // the new points as a candidate set (kept with the model: no allocation after the first block on each side); the
+    // caller's arrays are read by the copies queued here, which are complete at the call's first synchronisation
+    if (!g->blk_probe[side]) { g->blk_probe[side] = new cbo_cands(); g->blk_probe[side]->ctx = c; }
+    cbo_cands *p = g->blk_probe[side];
+    rc = cands_reserve(p, CBO_MAX_APPEND, g->d, causal);
+    if (rc != CBO_OK) return rc;
+    cands_describe(p, k, g->d, causal, 0);
+    HIP_TRY(hipMemcpyAsync(p->raw, X_new, sizeof(double) * k * g->d, hipMemcpyHostToDevice, c->stream));
+    if (causal) {
+        HIP_TRY(hipMemcpyAsync(p->pm, prior_mean_new, sizeof(double) * k, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(p->pv, prior_var_new, sizeof(double) * k, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(g->blk_y[side], y_new, sizeof(double) * k, hipMemcpyHostToDevice, c->stream));
+    rc = prepare_cands(g, p);
+    if (rc != CBO_OK) return rc;
+    int64_t chunk = 0, ldv = 0;
+    rc = ensure_workspaces(c, g->n_pad, p->m_pad, &chunk, &ldv);
+    if (rc != CBO_OK) return rc;
+    const int kp = (int)round_up(k, 16);
+    const int64_t ldk = kAppendLd + kLdExtra;
+    // K(X, Xb) and K(Xb, Xb) by the K* kernel, B by the k-column forward solve, then the Schur block
+    launch_kstar(c->stream, g->X, p->P, 0, p->m_pad, g->h, c->V, ldv, g->n_pad);
+    PointSet pb = p->P;
+    pb.n = k;
+    launch_kstar(c->stream, pb, p->P, 0, p->m_pad, g->h, g->blk_Kbb[side], ldk, 64);
+    launch_append_forward(c->stream, g->A, g->lda, g->n_pad, g->invDt, c->V, ldv, kp, g->blk_B[side]);
+    AppendSchurArgs sa{};
+    sa.part = g->blk_part; sa.k = k;
+    sa.Kbb = g->blk_Kbb[side]; sa.ldk = ldk;
+    sa.pv = causal ? p->pv : nullptr; sa.pm = causal ? p->pm : nullptr;
+    sa.y_new = g->blk_y[side];
+    sa.variance = g->h.variance; sa.sigma = g->noise_var + kGpyDiagJitter;
+    sa.L22 = g->blk_L22[side]; sa.zb = g->blk_zb[side]; sa.status = g->blk_status;
+    launch_append_schur(c->stream, g->blk_B[side], g->n, g->z, sa);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_info, g->blk_status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (*c->h_info != 0) return CBO_OK;                     // jitchol's business: full refit
+    HIP_TRY(hipMemcpyAsync(g->raw + g->n * g->d, p->raw, sizeof(double) * k * g->d, hipMemcpyDeviceToDevice, c->stream));
+    AppendCommitArgs ca{};
+    ca.A = g->A; ca.lda = g->lda; ca.n = g->n; ca.n_pad = g->n_pad; ca.k = k;
+    ca.B = g->blk_B[side]; ca.L22 = g->blk_L22[side]; ca.zb = g->blk_zb[side]; ca.y_new = g->blk_y[side];
+    ca.z = g->z; ca.y = g->y;
+    ca.dims = g->X.d; ca.xs = g->X.xs; ca.ldx = g->X.ld; ca.sq = g->X.sq; ca.sv = g->X.sv; ca.pm = g->X.pm; ca.pv = g->X.pv;
+    ca.pxs = p->P.xs; ca.ldp = p->P.ld; ca.psq = p->P.sq; ca.psv = p->P.sv; ca.pm_new = p->pm; ca.pv_new = p->pv;
+    launch_append_block_commit(c->stream, ca, g->invDt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (causal) g->h_pv.insert(g->h_pv.end(), prior_var_new, prior_var_new + k);
+    g->n += k;
+    g->X.n = g->n;
+    g->k_last = k;
+    g->blk_side = side;
+    g->parent_stamp = g->fit_stamp;
+    g->fit_stamp = ++g_fit_stamp;
+    g->alpha_ready = false;
+    *appended_out = 1;
+    return CBO_OK;
+}
+
+// V[n-k : n, :] for a model that was extended by cbo_gp_append_block: K(Xb, X*) by the K* kernel with the block's points
+// as its rows, then one pass over V for all k rows; q, mu (the candidates' cached copies) move along and take the new
+// fit stamp.
+static int extend_solution_by_block(cbo_gp *g, cbo_cands *k)
+{
+    cbo_ctx *c = g->ctx;
+    int rc = prepare_cands(g, k);
+    if (rc != CBO_OK) return rc;
+    int64_t chunk = 0, ldv = 0;
+    rc = ensure_workspaces(c, g->n_pad, k->m_pad, &chunk, &ldv);      // c->V: scratch for the 64-row K* slab
+    if (rc != CBO_OK) return rc;
+    if (chunk < k->m_pad) return CBO_OK;                               // cannot happen for a resident V; fall through
+    const int kb = g->k_last, kp = (int)round_up(kb, 16), side = g->blk_side;
+    const int64_t n0 = g->n - kb;
+    int slices = 1, rps = 64;
+    append_rows_plan(n0, k->m_pad, &slices, &rps);
+    rc = grow(c, c->append_part, (size_t)slices * (size_t)kp * (size_t)k->m_pad);
+    if (rc != CBO_OK) return rc;
+    PointSet pb = g->blk_probe[side]->P;                               // the block's points, scaled as the model's
+    pb.n = kb;
+    launch_kstar(c->stream, pb, k->P, 0, k->m_pad, g->h, c->V, ldv, 64);
+    AppendRowsArgs ra{};
+    ra.k = kb; ra.m_pad = k->m_pad;
+    ra.Kb = c->V; ra.ldk = ldv;
+    ra.L22 = g->blk_L22[side]; ra.zb = g->blk_zb[side];
+    ra.Vnew = k->V + n0 * k->v_ld; ra.ldv = k->v_ld;
+    ra.q = k->q; ra.mu = k->mu;
+    launch_append_rows(c->stream, k->V, k->v_ld, g->blk_B[side], n0, kp, c->append_part, ra);
+    HIP_TRY(hipGetLastError());
+    k->v_rows = g->n;
+    k->v_stamp = g->fit_stamp;
+    k->fit_stamp = g->fit_stamp;
     return CBO_OK;
 }
 
@@ -1554,10 +1723,11 @@ static int enqueue_vectors(cbo_gp *g, cbo_cands *k, bool *substituted = nullptr)
 {
     int rc = CBO_OK;
     cbo_ctx *c = g->ctx;
-    if (k->keep_v && k->V && k->v_stamp != 0 && k->v_stamp == g->parent_stamp && k->v_rows == g->n - 1 &&
+    if (k->keep_v && k->V && k->v_stamp != 0 && k->v_stamp == g->parent_stamp && k->v_rows == g->n - g->k_last &&
         k->v_rows_cap == g->n_pad && k->fit_stamp == k->v_stamp && k->q) {
-        // the model is the one this V belongs to plus one observation: one new row instead of the substitution
-        rc = extend_solution_by_one_row(g, k);
+        // the model is the one this V belongs to plus the last appended block: its new rows instead of the substitution
+        // (one observation, cbo_gp_append: the one-row kernels)
+        rc = g->k_last == 1 ? extend_solution_by_one_row(g, k) : extend_solution_by_block(g, k);
         if (rc != CBO_OK) return rc;
     }
     if (!(c->sweep_cache && k->fit_stamp != 0 && k->fit_stamp == g->fit_stamp)) {

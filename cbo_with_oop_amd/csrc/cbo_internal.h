@@ -381,6 +381,45 @@ int append_row_slices(int64_t n);
 void launch_append_row(hipStream_t s, double *V, int64_t ldv, int64_t n, const double *lvec, int64_t m_pad,
                        const double *krow, double d, double zn, double *partial, double *q, double *mu);
 
+// ---- block append (kernels_append.hip) ------------------------------------------------------------
+constexpr int kAppendLd = 64;                          // leading dimension of B [n_pad][64] and L22 [64][64]
+constexpr int kAppendMaxSlices = 8;                    // row slices of the pass over V (partial: slices x kp x m_pad)
+// out = L^-1 W for the first kp (a multiple of 16, <= 64) columns of W [n_pad][ldw] (W is destroyed); out: [n_pad][kAppendLd]
+void launch_append_forward(hipStream_t s, const double *A, int64_t lda, int64_t n_pad, const double *invDt, double *W,
+                           int64_t ldw, int kp, double *out);
+struct AppendSchurArgs {
+    const double *part; int slices;                    // set by the launcher: append_schur_slices(n) x 65 x 64 doubles
+    int k;
+    const double *Kbb; int64_t ldk;                    // K(Xb, Xb), X2 explicit, causal term included
+    const double *pv, *pm;                             // the new points' prior variance and mean (null: non-causal)
+    const double *y_new;
+    double variance, sigma;                            // sigma = noise_var + 1e-8
+    double *L22, *zb;                                  // [64][64] lower (zero elsewhere), [64]
+    int *status;                                       // 0, or the first pivot (1-based) that is not positive and finite
+};
+int append_schur_slices(int64_t n);
+void launch_append_schur(hipStream_t s, const double *B, int64_t n, const double *z, AppendSchurArgs a);
+struct AppendCommitArgs {
+    double *A; int64_t lda, n, n_pad; int k;
+    const double *B, *L22, *zb, *y_new;
+    double *z, *y;
+    int dims; double *xs; int64_t ldx; double *sq, *sv, *pm, *pv;       // the model's points (sv null: non-causal)
+    const double *pxs; int64_t ldp; const double *psq, *psv, *pm_new, *pv_new;   // the block's points as a candidate set
+};
+void launch_append_block_commit(hipStream_t s, const AppendCommitArgs &a, double *invDt);
+struct AppendRowsArgs {
+    const double *part; int slices;                    // set by the launcher
+    int k; int64_t m_pad;
+    const double *Kb; int64_t ldk;                     // K(Xb, X*) [64][ldk]
+    const double *L22, *zb;
+    double *Vnew; int64_t ldv;                         // row n of the resident V
+    double *q, *mu;
+};
+void append_rows_plan(int64_t rows, int64_t m_pad, int *slices, int *rows_per_slice);
+// rows: the rows of V the block was appended to (n before the append); part: slices * kp * m_pad doubles of scratch
+void launch_append_rows(hipStream_t s, const double *V, int64_t ldv, const double *B, int64_t rows, int kp, double *part,
+                        const AppendRowsArgs &a);
+
 // ---- greedy batch selection (kernels_batch.hip) --------------------------------------------------
 // One further pick of cbo_acq_sweep_batch.  Pick t >= 1 reads its pivot -- the winner of pick t - 1 -- from device memory.
 constexpr int kBatchMaxSlices = 64;                    // row slices of the pass over V (partial: kBatchMaxSlices x m_pad)

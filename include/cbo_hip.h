@@ -129,6 +129,30 @@ int cbo_gp_upload_data(cbo_gp *gp, int64_t n, const double *X, const double *y,
 int cbo_gp_append(cbo_gp *gp, const double *x_new, double y_new, double prior_mean_new, double prior_var_new,
                   int *appended_out);
 
+/* k more observations for a fitted model in one device step -- the results of a batch picked by cbo_acq_sweep_batch
+ * coming back together (src/Monitor.py:148-160 appends once per result).  With L the current factor, z = L^-1 (y - m),
+ * Xb the k new points and sigma = noise_var + 1e-8:
+ *     B   = L^-1 K(X, Xb)                          (n x k)
+ *     S   = K(Xb, Xb) + sigma I - B^T B            (k x k; the diagonal prior term is variance + v(x), as cbo_gp_append's;
+ *                                                   off-diagonal entries with X2 explicit, + sqrt(v) sqrt(v) when causal)
+ *     L22 = chol(S),   zb = L22^-1 ((yb - m(Xb)) - B^T z)
+ *     U[0:n, n:n+k] = B,  U[n:n+k, n:n+k] = L22^T,  z[n:n+k] = zb   (the rhs column of the factor's buffer carries z too)
+ * The resident data (y, coordinates, prior closures) grow by k rows and the diagonal-tile inverses gain the columns of
+ * the new rows.  *appended_out = 1: the model is fitted on n + k points, same results as a full refit up to rounding.
+ * *appended_out = 0: nothing at all changed and the caller refits with cbo_gp_set_data -- under cbo_gp_append's rules:
+ * jitter in the current factor, n + k beyond the padded size (n + k equal to it is allowed), an fp32 model, or a pivot
+ * of S that is not positive and finite (decided on the device before anything is committed).  k = 1 is cbo_gp_append
+ * itself.  A candidate set that keeps its solution (cbo_cands_keep_solution) and was swept on the model just before
+ * the block gains the k new rows of V in one pass at its next sweep:  C = K(Xb, X*) - B^T V[0:n, :],  W = L22^-1 C,
+ * V[n:n+k, :] = W,  q += sum_r W_r^2,  mu += sum_r W_r zb_r (r in row order); every other set takes the substitution.
+ * Every sum has a fixed order: two identical call sequences give the same bits.
+ * X_new: k * d row-major; prior_mean_new / prior_var_new: k values each for a causal model, NULL otherwise.
+ * CBO_ERR_INVALID: k outside 1..CBO_MAX_APPEND, NULL gp, X_new, y_new or appended_out, a causal model without both prior
+ * arrays; CBO_ERR_NOT_FITTED: the model is not fitted. */
+#define CBO_MAX_APPEND 64
+int cbo_gp_append_block(cbo_gp *gp, int k, const double *X_new, const double *y_new, const double *prior_mean_new,
+                        const double *prior_var_new, int *appended_out);
+
 /* GPyModelWrapper.predict -> GP.predict -> Posterior._raw_predict (called from
  * src/utils_functions/causal_acquisition_functions.py:33 and src/DoCalculus.py:77):
  * mean = K*^T Ky^-1 (y-m) + m(X*), var = clip(Kdiag - |L^-1 K*|^2, 1e-15) (+ noise). */
