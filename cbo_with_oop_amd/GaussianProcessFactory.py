@@ -491,6 +491,32 @@ class HipGaussianProcess:
         self._last_lml = lml.value
         return dv.value, dls, dn.value
 
+    def _loo(self, want_mean=False, want_var=False, want_lpd=False):
+        """``cbo_gp_loo`` of the fitted model: (mean, var, lpd, sum of lpd), None where not asked for."""
+        self.ensure_fitted()
+        n = self.X.shape[0]
+        mean, var, lpd = (np.zeros(n) if want else None for want in (want_mean, want_var, want_lpd))
+        total = ctypes.c_double(0.0)
+        _lib.check(self._lib.cbo_gp_loo(self._handle, _lib.dptr(mean), _lib.dptr(var), _lib.dptr(lpd), ctypes.byref(total)))
+        return mean, var, lpd, total.value
+
+    def loo(self):
+        """GPy ``model.inference_method.LOO(kern, X, Y, likelihood, posterior)``: the leave-one-out log predictive
+        density of every observation, (n, 1), GPy's shape and sign -- computed on the device from the resident factor
+        (``cbo_gp_loo``; Rasmussen & Williams 5.4.2).  A factor that carries jitchol jitter gives the LOO of the
+        jittered Ky (``jitter_tries`` tells)."""
+        return self._loo(want_lpd=True)[2][:, None]
+
+    def loo_predict(self):
+        """(mean (n, 1), var (n, 1)) of every observation predicted from the other n - 1; the variance is that of the
+        observation, noise included."""
+        mean, var, _, _ = self._loo(want_mean=True, want_var=True)
+        return mean[:, None], var[:, None]
+
+    def loo_score(self):
+        """The LOO pseudo-likelihood, the sum of ``loo()``, summed on the device in a fixed order."""
+        return self._loo()[3]
+
     def _objective(self, x, transform="log"):
         """(negative log marginal likelihood, its gradient with respect to x) at theta(x) = [variance, lengthscale(s),
         (noise)]: ``transform="logexp"``: theta = log(1 + exp(x)), paramz's ``Model._objective_grads`` with

@@ -111,6 +111,8 @@ SIGNATURES = {
     "cbo_gp_lml_gradients": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_lml_gradients_batch": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_double_p, c_double_p, c_double_p, c_double_p,
                                                   c_int_p]),
+    "cbo_gp_loo": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "cbo_gp_loo_batch": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_double_p, c_double_p, c_int_p]),
     "cbo_gp_predict_gradients": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p,
                                                 c_double_p]),
     "cbo_gp_predict_grouped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, c_double_p,

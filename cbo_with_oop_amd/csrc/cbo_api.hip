@@ -127,6 +127,8 @@ struct cbo_ctx {
     int polled_launches = 0;                                    // launches completed by polling since the last stream sync
     PinnedBuf<cbo_small_lml_result> lml_out;                    // written by small_lml_kernel
     PinnedBuf<cbo_small_lml_result> lml_batch_out;              // written by small_lml_batch_kernel
+    PinnedBuf<cbo_small_loo_result> loo_out;                    // written by small_loo_batch_kernel
+    int loo_route = 0;               // CBO_HIP_LOO_ROUTE: 1 = trailing-system chunks always, 2 = full-height chunks, else automatic
     GrowBuf<double> q, mu, mean, var, acq;                      // per candidate
     double *part_val = nullptr; int64_t *part_idx = nullptr;
     double *best_val = nullptr; int64_t *best_idx = nullptr;   // device
@@ -408,6 +410,8 @@ extern "C" int cbo_init(int device_id, cbo_ctx **out)
     c->n_cu = prop.multiProcessorCount;
     const char *sm = std::getenv("CBO_HIP_SWEEP");
     if (sm) c->sweep_mode = std::atoi(sm);
+    const char *lr = std::getenv("CBO_HIP_LOO_ROUTE");
+    if (lr) c->loo_route = std::atoi(lr);
     const char *sc = std::getenv("CBO_HIP_SWEEP_CACHE");
     if (sc && std::atoi(sc) == 0) c->sweep_cache = false;
     const char *ss = std::getenv("CBO_HIP_SMALL_SETS");
@@ -3041,6 +3045,130 @@ static int general_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_o
     HIP_TRY(hipMemcpyAsync(hs, c->part_val, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     lml_outputs(g, hs, hs[16], hs[17], hs[20], hs[22], lml_out, dvariance_out, dlengthscale_out, dnoise_out);
+    return CBO_OK;
+}
+
+// ---- leave-one-out cross-validation (kernels_loo.hip) ---------------------------------------------------
+// The general path: c = diag(Ky^-1) is the vector of squared column norms of L^-1, which the substitution kernels return
+// as q when their right-hand sides are the identity.  The identity goes through in column chunks that fit the workspace.
+// Chunk [c0, c0 + w) is zero above row c0, and so is its solution: the kernels get the trailing system only -- factor,
+// diagonal inverses, z and V offset to (r0, r0), r0 = c0 rounded down to the pair kernel's 256-row block, height n_pad -
+// r0.  Every kernel address is "base + offset" with offsets that are multiples of 128 doubles, so the offset bases keep
+// the 16-byte alignment the LDS-DMA loads need.  A model whose whole identity fits the workspace and
+// that prefer_right_looking would sweep right-looking takes the schedule of the likelihood gradients instead (lower-
+// triangular right-hand sides: the zero part is skipped there too, and the device is filled whatever the column count).
+// Outputs are host pointers; each may be null.
+static int general_loo(cbo_gp *g, double *mean_out, double *var_out, double *lpd_out, double *sum_out)
+{
+    cbo_ctx *c = g->ctx;
+    int rc = ensure_alpha(g);
+    if (rc != CBO_OK) return rc;
+    const int64_t n_pad = g->n_pad;
+    int64_t chunk = 0, ldv = 0;
+    rc = ensure_workspaces(c, n_pad, n_pad, &chunk, &ldv);
+    if (rc != CBO_OK) return rc;
+    const int nb = loo_finish_blocks(g->n);
+    rc = grow(c, c->gpart, (size_t)nb + 1);
+    if (rc != CBO_OK) return rc;
+    if (c->loo_route != 1 && c->loo_route != 2 && chunk >= n_pad && prefer_right_looking(c, n_pad, n_pad)) {
+        launch_set_identity(c->stream, c->V, ldv, n_pad);
+        rc = enqueue_right_looking(g, c->V, ldv, n_pad, c->q, c->mu, true);
+        if (rc != CBO_OK) return rc;
+    } else {
+        for (int64_t c0 = 0; c0 < n_pad; c0 += chunk) {
+            const int64_t cols = (n_pad - c0 < chunk) ? (n_pad - c0) : chunk;
+            const int64_t r0 = c->loo_route == 2 ? 0 : c0 / 256 * 256;
+            const int64_t rows = n_pad - r0;
+            PhaseScope ps(c, PH_TRSM);
+            launch_loo_identity_chunk(c->stream, c->V, ldv, rows, cols, c0 - r0);
+            launch_trsm_strips(c->stream, g->A + r0 * g->lda + r0, g->lda, g->invDt + (r0 / 16) * 256, c->V, ldv, rows,
+                               cols, g->z + r0, c->q + c0, c->mu + c0);
+            if (c->profiling) {
+                c->timers.n_trsm_launches += 1;
+                c->timers.trsm_flops += (double)rows * (double)rows * (double)cols;
+            }
+        }
+    }
+    double *partial = c->gpart, *sum_dev = c->gpart + nb;
+    launch_loo_finish(c->stream, c->q, g->alpha, g->y, g->n, mean_out ? c->mean.p : nullptr, var_out ? c->var.p : nullptr,
+                      lpd_out ? c->acq.p : nullptr, partial, sum_dev);
+    HIP_TRY(hipGetLastError());
+    const size_t bytes = sizeof(double) * (size_t)g->n;
+    if (mean_out) HIP_TRY(hipMemcpyAsync(mean_out, c->mean, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIP_TRY(hipMemcpyAsync(var_out, c->var, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (lpd_out) HIP_TRY(hipMemcpyAsync(lpd_out, c->acq, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (sum_out) HIP_TRY(hipMemcpyAsync(sum_out, sum_dev, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CBO_OK;
+}
+
+extern "C" int cbo_gp_loo(cbo_gp *g, double *mean_out, double *var_out, double *lpd_out, double *sum_lpd_out)
+{
+    if (!g) return fail(CBO_ERR_INVALID, "gp is NULL");
+    if (!mean_out && !var_out && !lpd_out && !sum_lpd_out) return fail(CBO_ERR_INVALID, "cbo_gp_loo: every output is NULL");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    HIP_TRY(hipSetDevice(g->ctx->device));
+    return general_loo(g, mean_out, var_out, lpd_out, sum_lpd_out);
+}
+
+// Many models, one launch: every fp64 model of at most 128 observations goes into ONE small_loo_batch_kernel launch (one
+// workgroup each, from the data and the current hyper-parameters: no fit, nothing of the model touched).  The others --
+// larger models, and small ones whose Ky is not positive definite as assembled (fitted here with the jitchol ladder) --
+// are answered one by one by general_loo, as cbo_gp_loo would.
+extern "C" int cbo_gp_loo_batch(int n_models, cbo_gp *const *gps, double *sum_lpd, double *lpd_cat, int *status)
+{
+    if (n_models <= 0 || !gps || !sum_lpd || !status) return fail(CBO_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n_models; ++i) {
+        if (!gps[i]) return fail(CBO_ERR_INVALID, "NULL gp");
+        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all models must live on one context");
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int> small, rest;
+    std::vector<int64_t> offset((size_t)n_models);
+    int64_t total = 0;
+    for (int i = 0; i < n_models; ++i) {
+        offset[(size_t)i] = total;
+        total += gps[i]->n;
+        (small_lml_eligible(gps[i]) ? small : rest).push_back(i);
+    }
+    const int ns = (int)small.size();
+    if (ns > 0) {
+        int rc = ensure_small_buffers(c, ns, 1);
+        if (rc != CBO_OK) return rc;
+        if ((size_t)ns * small_loo_scratch_doubles() > c->small_scratch.cap)
+            return fail(CBO_ERR_INVALID, "leave-one-out batch: scratch smaller than expected");
+        rc = grow(c, c->loo_out, ns < 32 ? 32 : (size_t)ns, true);
+        if (rc != CBO_OK) return rc;
+        for (int j = 0; j < ns; ++j) {
+            cbo_small_set st{};
+            fill_small_model(st, gps[small[(size_t)j]]);
+            c->sets_host[j] = st;
+        }
+        cbo_small_loo_result *out = c->loo_out;
+        auto launch = [&](int seq) -> int {
+            launch_small_loo_batch(c->stream, c->sets_host, ns, c->small_scratch, c->small_info, out, seq);
+            return hipGetLastError() != hipSuccess ? fail(CBO_ERR_HIP, "small_loo_batch_kernel launch") : CBO_OK;
+        };
+        rc = polled_launch(c, "cbo_gp_loo_batch", out, ns, "leave-one-out batch kernel: no result record", launch);
+        if (rc != CBO_OK) return rc;
+        for (int j = 0; j < ns; ++j) {
+            const int i = small[(size_t)j];
+            if (out[j].info != 0) { rest.push_back(i); continue; }
+            sum_lpd[i] = out[j].sum;
+            if (lpd_cat) std::memcpy(lpd_cat + offset[(size_t)i], out[j].lpd, sizeof(double) * (size_t)gps[i]->n);
+            status[i] = CBO_OK;
+        }
+    }
+    for (int i : rest) {
+        cbo_gp *g = gps[i];
+        int rc = CBO_OK;
+        if (!g->fitted && g->n_pad == kPadN) rc = cbo_gp_fit(g, nullptr, nullptr);   // (jitchol ladder)
+        if (rc == CBO_OK && !g->fitted) rc = fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+        if (rc == CBO_OK) rc = general_loo(g, nullptr, nullptr, lpd_cat ? lpd_cat + offset[(size_t)i] : nullptr, &sum_lpd[i]);
+        if (rc == CBO_ERR_HIP) return rc;               // the device is in trouble: no per-model answer means anything
+        status[i] = rc;
+    }
     return CBO_OK;
 }
 

@@ -299,6 +299,26 @@ void launch_small_lml(hipStream_t s, const cbo_small_set &st, double *scratch, i
 size_t mid_lml_scratch_doubles();
 void launch_small_lml_batch(hipStream_t s, const cbo_small_set *sets, int n_models, double *scratch, int64_t stride,
                             int *info, cbo_small_lml_result *out, int seq);
+// ---- leave-one-out cross-validation (kernels_loo.hip) ---------------------------------------------
+// record of one model of small_loo_batch_kernel (pinned host memory, written by the kernel): the three per-point outputs
+// of its n <= 128 points, their lpd summed in index order, the first non-positive pivot (1-based) or 0
+struct cbo_small_loo_result {
+    double sum;
+    double mean[128], var[128], lpd[128];
+    int info, seq;
+};
+size_t small_loo_scratch_doubles();                    // per model: factor rows + inverses
+// n_models models (n <= 128) in one launch: descriptors (pinned, device-mapped), info[b] zero on entry (zero again afterwards)
+void launch_small_loo_batch(hipStream_t s, const cbo_small_set *sets, int n_models, double *scratch, int *info,
+                            cbo_small_loo_result *out, int seq);
+// V[i][j] = 1 where i == j + shift, else 0, for i < rows, j < cols (cols even, V + i ldv + j 16-byte aligned): columns
+// [c0, c0 + cols) of the identity seen from row r0 = c0 - shift on
+void launch_loo_identity_chunk(hipStream_t s, double *V, int64_t ldv, int64_t rows, int64_t cols, int64_t shift);
+// mean, var, lpd (each may be null) of the points i < n from c = diag(Ky^-1), alpha and y; sum_out[0] = sum of lpd in a
+// fixed order through partial (loo_finish_blocks(n) doubles of scratch)
+int loo_finish_blocks(int64_t n);
+void launch_loo_finish(hipStream_t s, const double *c, const double *alpha, const double *y, int64_t n, double *mean_out,
+                       double *var_out, double *lpd_out, double *partial, double *sum_out);
 // sets / out may be pinned host memory (device-mapped): the kernel then reads the descriptors and writes the results
 // across the host link itself and the call needs no copy operation (the host may poll out[].seq instead of
 // synchronising the stream); info and ticket (device, n_sets ints each) must be zero on entry and are zero again afterwards

@@ -329,6 +329,31 @@ int cbo_gp_lml_gradients(cbo_gp *gp, double *lml_out, double *dvariance_out, dou
 int cbo_gp_lml_gradients_batch(int n_models, cbo_gp *const *gps, double *lml, double *dvar, double *dls,
                                double *dnoise, int *status);
 
+/* Leave-one-out cross-validation of the fitted model, all on the device (Rasmussen & Williams 5.4.2; what GPy exposes as
+ * model.inference_method.LOO -- restated from memory, parity with GPy is not pinned by a recorded GPy output).  With
+ * r = y - m(X), alpha = Ky^-1 r and c_i = (Ky^-1)_ii, for every observation i < n:
+ *     mean_out[i] = y_i - alpha_i / c_i       the prediction of y_i from the other n - 1 observations
+ *     var_out[i]  = 1 / c_i                   its predictive variance, of y_i: the noise and the 1e-8 of Ky included
+ *     lpd_out[i]  = -1/2 log 2 pi + 1/2 log c_i - 1/2 alpha_i^2 / c_i      (GPy's return value and sign)
+ * and *sum_lpd_out = sum_i lpd_out[i], the LOO pseudo-likelihood, summed on the device in a fixed order (two identical
+ * calls return the same bits).  Each of the four outputs may be NULL, not all of them (CBO_ERR_INVALID; a NULL gp too).
+ * Unfitted model: CBO_ERR_NOT_FITTED.  The model is only read: factor, z, fitted state, candidate sets with their
+ * cached vectors and kept solutions stay as they are (alpha is materialised as by cbo_gp_get_posterior).  A factor that
+ * carries jitchol jitter is used as it is -- the result is the LOO of the jittered Ky; cbo_gp_jitter tells.  fp32
+ * models answer from the fp64 factor.  After cbo_gp_append / cbo_gp_append_block the n + k observations are covered.
+ * Causal models need nothing extra: m(X) and v(X) are in z and in the factor. */
+int cbo_gp_loo(cbo_gp *gp, double *mean_out, double *var_out, double *lpd_out, double *sum_lpd_out);
+/* The same for many models in one call (every exploration set of a trial, with and without the causal prior).  Every
+ * fp64 model of at most 128 observations need not be fitted: all of them are answered inside ONE launch, from the data
+ * and the current hyper-parameters, and are left as they were -- with the same bits whatever else the batch holds.
+ * Larger models must be fitted beforehand and are answered one by one as by cbo_gp_loo; a small model whose Ky is not
+ * positive definite as assembled is fitted here with the jitchol ladder and answered that way too.  All models live on
+ * one context.  Outputs per model i: sum_lpd[i]; lpd_cat (may be NULL) takes the per-point lpd of all models one after
+ * the other in model order (n_0 + n_1 + ... doubles); status[i] = CBO_OK or the error cbo_gp_loo would have returned for
+ * that model alone (its outputs are then undefined).  The call itself fails only on bad arguments (n_models <= 0, NULL
+ * gps, sum_lpd or status, a NULL model, models of different contexts: CBO_ERR_INVALID) or a device error. */
+int cbo_gp_loo_batch(int n_models, cbo_gp *const *gps, double *sum_lpd, double *lpd_cat, int *status);
+
 /* Prediction gradients: emukit GPyModelWrapper.get_prediction_gradients -> GPy
  * predictive_gradients, called from CausalExpectedImprovement.evaluate_with_gradients
  * (src/utils_functions/causal_acquisition_functions.py:54) inside the L-BFGS refinement of
