@@ -549,6 +549,24 @@ class HipGaussianProcess:
         f_opt = self._objective(x_opt, transform)[0]          # opt_lbfgsb: f_opt = f_fp(x_opt)[0]; the model sits at x_opt
         return _optimizer_finish(self, theta0, x_opt, f_opt, info, transform)
 
+    def generate_hyperparameters_samples(self, n_samples=20, n_burnin=100, subsample_interval=10, step_size=1e-1,
+                                         leapfrog_steps=20):
+        """emukit ``GPyModelWrapper.generate_hyperparameters_samples``: ``optimize()``, a multiplicative 1 % perturbation of
+        the parameters (``theta * (1 + 0.01 * np.random.randn(P))``, numpy's global generator), GPy's HMC over the
+        Logexp-transformed parameters (``integrated_hyper.hmc_sample`` on this model's ``_objective``) for
+        ``n_burnin + n_samples * subsample_interval`` samples, and ``samples[n_burnin::subsample_interval]``: an
+        (n_samples, P) array of (variance, lengthscale(s), noise variance) rows -- without the noise column for a model whose
+        noise is fixed.  The model is LEFT AT THE CHAIN'S LAST STATE, unfitted (``stale``): the next use refits it there.
+        emukit and GPy are not installed here: restated from memory, parity unpinned."""
+        from .utils_functions.integrated_hyper import hmc_sample
+        self.optimize()
+        theta0, _ = _optimizer_start(self, "logexp")
+        theta0 = theta0 * (1.0 + 0.01 * np.random.randn(theta0.size))
+        num = int(n_burnin) + int(n_samples) * int(subsample_interval)
+        samples = hmc_sample(lambda x: self._objective(x, "logexp"), theta0, num, int(leapfrog_steps), float(step_size))
+        _objective_set(self, samples[-1], fit=False)         # (the last evaluation may have been a rejected proposal)
+        return samples[int(n_burnin)::int(subsample_interval)]
+
     def get_prediction_gradients(self, x):
         """emukit ``GPyModelWrapper.get_prediction_gradients`` -> GPy ``predictive_gradients``:
         (d mean / d x (M,d), d var / d x (M,d)).  As in GPy, the mean function's and the causal rank-1 term's own

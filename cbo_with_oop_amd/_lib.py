@@ -21,6 +21,7 @@ c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 ABI_VERSION = 5          # include/cbo_hip.h: CBO_HIP_ABI_VERSION
 MAX_DIM = 8              # CBO_MAX_DIM
 MAX_APPEND = 64          # CBO_MAX_APPEND
+MAX_HYPER_SAMPLES = 256  # CBO_MAX_HYPER_SAMPLES
 CBO_OK = 0
 CBO_ERR_INVALID = -1
 CBO_ERR_HIP = -2
@@ -106,6 +107,8 @@ SIGNATURES = {
                                                  ctypes.c_double, ctypes.c_double, ctypes.c_int, c_void_pp, c_void_pp,
                                                  c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p,
                                                  c_double_p, c_int64_p]),
+    "cbo_acq_sweep_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_double,
+                                           ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_int64_p]),
     "cbo_gp_set_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p, ctypes.c_double]),
     "cbo_gp_log_marginal": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "cbo_gp_lml_gradients": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),

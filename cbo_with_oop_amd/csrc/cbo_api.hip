@@ -129,6 +129,10 @@ struct cbo_ctx {
     PinnedBuf<cbo_small_lml_result> lml_batch_out;              // written by small_lml_batch_kernel
     PinnedBuf<cbo_small_loo_result> loo_out;                    // written by small_loo_batch_kernel
     int loo_route = 0;               // CBO_HIP_LOO_ROUTE: 1 = trailing-system chunks always, 2 = full-height chunks, else automatic
+    // cbo_acq_sweep_hyper: the samples as the kernel reads them (pinned), the general path's running sum [m_pad]
+    PinnedBuf<double> hyper_host;
+    GrowBuf<double> hyper_sum;
+    int hyper_schedule = 0;          // CBO_HIP_HYPER_SCHEDULE: 1 = every workgroup factors every sample, 2 = two launches, else automatic
     GrowBuf<double> q, mu, mean, var, acq;                      // per candidate
     double *part_val = nullptr; int64_t *part_idx = nullptr;
     double *best_val = nullptr; int64_t *best_idx = nullptr;   // device
@@ -412,6 +416,8 @@ extern "C" int cbo_init(int device_id, cbo_ctx **out)
     if (sm) c->sweep_mode = std::atoi(sm);
     const char *lr = std::getenv("CBO_HIP_LOO_ROUTE");
     if (lr) c->loo_route = std::atoi(lr);
+    const char *hs = std::getenv("CBO_HIP_HYPER_SCHEDULE");
+    if (hs) c->hyper_schedule = std::atoi(hs);
     const char *sc = std::getenv("CBO_HIP_SWEEP_CACHE");
     if (sc && std::atoi(sc) == 0) c->sweep_cache = false;
     const char *ss = std::getenv("CBO_HIP_SMALL_SETS");
@@ -2351,6 +2357,109 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
         if (rc != CBO_OK) return rc;
     }
     return CBO_OK;
+}
+
+// ---- the causal EI marginalised over hyper-parameter samples (kernels_hyper.hip) -------------------------
+// The general path of cbo_acq_sweep_hyper: per sample the model's own set_hyper + fit + sweep, the acquisition kept on the
+// device and added into the running sum; then the division with the arg-max; then the model back as it was.
+static int hyper_general_path(cbo_gp *g, cbo_cands *k, int n_samples, int n_ls, const double *hyper, double y_best, int task,
+                              double ei_jitter, double cost, double *acq_out, double *best_val, int64_t *best_idx)
+{
+    cbo_ctx *c = g->ctx;
+    const double variance0 = g->h.variance, noise0 = g->noise_var;
+    const std::vector<double> ls0 = g->ls;
+    const bool was_fitted = g->fitted;
+    const int nb = acq_blocks_for(k->m);
+    int rc = grow(c, c->hyper_sum, (size_t)k->m_pad);
+    for (int h = 0; h < n_samples && rc == CBO_OK; ++h) {
+        const double *row = hyper + (size_t)h * (size_t)(n_ls + 2);
+        rc = cbo_gp_set_hyper(g, row[0], row + 1, row[1 + n_ls]);
+        if (rc == CBO_OK) rc = cbo_gp_fit(g, nullptr, nullptr);
+        if (rc == CBO_OK) rc = enqueue_vectors(g, k);
+        const double *q_src = nullptr, *mu_src = nullptr;
+        if (rc == CBO_OK) rc = settle_vectors(g, k, false, &q_src, &mu_src);
+        // (acq_out only says that the per-candidate values are wanted: they stay in the context's vector)
+        if (rc == CBO_OK) rc = enqueue_finish(g, k, y_best, task, ei_jitter, cost, c->acq, nullptr, nullptr, q_src, mu_src,
+                                              false, false);
+        if (rc != CBO_OK) break;
+        launch_hyper_accumulate(c->stream, c->hyper_sum, c->acq, k->m, h == 0, nb);
+        if (hipGetLastError() != hipSuccess) rc = fail(CBO_ERR_HIP, "hyper_accumulate_kernel launch");
+    }
+    if (rc == CBO_OK) {
+        launch_hyper_finish(c->stream, c->hyper_sum, k->m, n_samples, acq_out ? c->acq.p : nullptr, c->part_val, c->part_idx,
+                            k->index_offset, nb);
+        launch_argmax_final(c->stream, c->part_val, c->part_idx, nb, c->h_best_val, c->h_best_idx);
+        if (hipGetLastError() != hipSuccess) rc = fail(CBO_ERR_HIP, "hyper_finish_kernel launch");
+        if (rc == CBO_OK) rc = copy_posterior_out(c, k, acq_out, nullptr, nullptr);
+        if (rc == CBO_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(CBO_ERR_HIP, "hipStreamSynchronize");
+        if (rc == CBO_OK) complete_finish(c, best_val, best_idx);
+    }
+    // the model back as it was, whatever happened (the first error is the one reported)
+    const std::string err = g_err;
+    int back = cbo_gp_set_hyper(g, variance0, ls0.data(), noise0);
+    if (back == CBO_OK && was_fitted) back = cbo_gp_fit(g, nullptr, nullptr);
+    if (rc != CBO_OK) { g_err = err; return rc; }
+    return back;
+}
+
+extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const double *hyper, double y_best, int task,
+                                   double ei_jitter, double cost, double *acq_out, double *best_val, int64_t *best_idx)
+{
+    int rc = check_sweep_args(g, k, task);
+    if (rc != CBO_OK) return rc;
+    if (n_samples < 1 || n_samples > CBO_MAX_HYPER_SAMPLES)
+        return fail(CBO_ERR_INVALID, "the number of hyper-parameter samples must be in 1.." + std::to_string(CBO_MAX_HYPER_SAMPLES));
+    if (!hyper) return fail(CBO_ERR_INVALID, "hyper is NULL");
+    if (!acq_out && (!best_val || !best_idx)) return fail(CBO_ERR_INVALID, "nothing to return: acq_out, best_val / best_idx are NULL");
+    if (!(cost > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    if (g->n <= 0 || g->n_pad <= 0) return fail(CBO_ERR_INVALID, "gp holds no data (a previous upload failed)");
+    const int n_ls = g->h.ard ? g->d : 1;
+    const int row_len = n_ls + 2;
+    for (int h = 0; h < n_samples; ++h) {
+        const double *row = hyper + (size_t)h * (size_t)row_len;
+        for (int j = 0; j <= n_ls; ++j)
+            if (!std::isfinite(row[j]) || !(row[j] > 0.0))
+                return fail(CBO_ERR_INVALID, "hyper row " + std::to_string(h) + ": variance and lengthscales must be finite and positive");
+        if (!std::isfinite(row[1 + n_ls]) || row[1 + n_ls] < 0.0)
+            return fail(CBO_ERR_INVALID, "hyper row " + std::to_string(h) + ": noise_var must be finite and non-negative");
+    }
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t blocks64 = (k->m + 63) / 64;
+    if (g->dtype == CBO_DTYPE_F64 && g->n_pad == kPadN && c->small_sets && blocks64 <= 65535) {
+        const int blocks = (int)blocks64;
+        rc = ensure_small_buffers(c, 1, blocks > n_samples ? blocks : n_samples);
+        if (rc == CBO_OK) rc = grow(c, c->hyper_host, (size_t)CBO_MAX_HYPER_SAMPLES * (CBO_MAX_DIM + 2));
+        if (rc == CBO_OK && acq_out) rc = grow_vectors(c, k->m_pad);
+        if (rc != CBO_OK) return rc;
+        std::memcpy(c->hyper_host.p, hyper, sizeof(double) * (size_t)n_samples * (size_t)row_len);
+        const bool causal = g->X.sv != nullptr;
+        cbo_small_set st{};
+        fill_small_model(st, g);
+        st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
+        st.m = k->m; st.index_offset = k->index_offset;
+        st.task = task; st.y_best = y_best; st.ei_jitter = ei_jitter; st.cost = cost;
+        auto launch = [&](int seq) -> int {
+            launch_hyper_avg(c->stream, st, k->raw, c->hyper_host, n_samples, n_ls, acq_out ? c->acq.p : nullptr, blocks,
+                             c->hyper_schedule, c->small_scratch, c->small_part_val, c->small_part_idx, c->small_info,
+                             c->small_info + c->small_info.cap / 2, c->small_out, seq);
+            HIP_TRY(hipGetLastError());
+            return CBO_OK;
+        };
+        rc = polled_launch(c, "cbo_acq_sweep_hyper", c->small_out.p, 1, "marginalised sweep: no result record", launch);
+        if (rc != CBO_OK) return rc;
+        if (c->small_out[0].info == 0) {
+            if (acq_out) {
+                HIP_TRY(hipMemcpyAsync(acq_out, c->acq, sizeof(double) * k->m, hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+            }
+            if (best_val) *best_val = c->small_out[0].best_val;
+            if (best_idx) *best_idx = c->small_out[0].best_idx;
+            return CBO_OK;
+        }
+        // a sample that is not positive definite as assembled: the jitchol ladder of the general path
+    }
+    return hyper_general_path(g, k, n_samples, n_ls, hyper, y_best, task, ei_jitter, cost, acq_out, best_val, best_idx);
 }
 
 // One reference-scale trial in ONE call (src/CBO.py:143-173, CBO.intervene): the model of the set that was intervened on

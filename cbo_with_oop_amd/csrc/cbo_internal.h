@@ -325,6 +325,22 @@ void launch_loo_finish(hipStream_t s, const double *c, const double *alpha, cons
 void launch_small_sets(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
                        double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq);
 
+// ---- hyper-parameter-marginalised EI (kernels_hyper.hip) ----------------------------------------------
+// One launch (schedule 1) or two (2; 0 = by the number of candidate blocks) for a model of at most 128 observations: st is
+// fill_small_model's descriptor plus the candidates' prior closures, m, index_offset and EI's scalars; craw the set's raw AoS
+// coordinates; hyper (pinned, device-mapped) n_samples rows of (variance, lengthscale x n_ls, noise_var); acq_out (device, m)
+// or null.  scratch: hyper_avg_scratch_doubles(blocks, n_samples); part_val / part_idx: `blocks` entries; info[0], ticket[0]
+// zero on entry (zero again afterwards); the record out[0] (pinned) carries the winner and the status word.
+size_t hyper_avg_scratch_doubles(int blocks, int n_samples);
+void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
+                      int n_ls, double *acq_out, int blocks, int schedule, double *scratch, double *part_val,
+                      int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq);
+// the general path: sum[i] = (first ? 0 : sum[i]) + acq[i] for i < m; then acq_out[i] = sum[i] / n_samples (acq_out may be
+// null) with arg-max partials per workgroup (n_blocks <= 2048) for launch_argmax_final
+void launch_hyper_accumulate(hipStream_t s, double *sum, const double *acq, int64_t m, bool first, int n_blocks);
+void launch_hyper_finish(hipStream_t s, const double *sum, int64_t m, int n_samples, double *acq_out, double *part_val,
+                         int64_t *part_idx, int64_t index_offset, int n_blocks);
+
 struct AcqParams {
     double variance, noise_var, y_best, ei_jitter, cost;
     int task, include_noise, want_ei;

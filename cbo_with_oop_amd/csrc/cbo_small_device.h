@@ -1,6 +1,6 @@
 // Device functions of the one-workgroup kernels, shared by the translation units that factor a block inside LDS
 // (kernels_chol.hip: the blocked factorisation's diagonal block, small_sets_kernel, small_lml_kernel; kernels_loo.hip:
-// small_loo_batch_kernel): the register Cholesky of a 16x16 tile, the decoupled-wave factorisation of a 128-row block,
+// small_loo_batch_kernel; kernels_hyper.hip: hyper_avg_kernel): the register Cholesky of a 16x16 tile, the decoupled-wave factorisation of a 128-row block,
 // the tile solve of a 128-row block for one wave's 16 columns, and the model side of a small model (points, K(X,X) +
 // diag, factor, inverses and z).  One definition, so every kernel that factors a small model produces the same bits.
 #pragma once
@@ -619,6 +619,75 @@ __device__ __forceinline__ void small_model_factor(SmallShared &sh, const cbo_sm
             iv[s][kk] = (s < tiles) ? invs[s * 256 + (4 * kk + kq) * 16 + lc] : 0.0;
             zr[s][kk] = (s < tiles) ? Us[(int64_t)(16 * s + kq + 4 * kk) * kSmallLd + 128] : 0.0;
         }
+}
+
+template <int D>
+__device__ __forceinline__ double small_kstar(const SmallShared &sh, const cbo_small_set &st, int row, const double *xc,
+                                              double csq, double csv, double inv_l2)
+{
+    // (no branch around the value -- the four of a tile interleave; rows beyond n are zeros in LDS)
+    double xi[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) xi[k] = sh.xs[k][row];
+    double v = kernel_value<D>(xi, xc, sh.sq[row], csq, st.variance, inv_l2, false);
+    const double vc = __dadd_rn(v, __dmul_rn(sh.sv[row], csv));
+    v = (st.sv != nullptr) ? vc : v;
+    return (row < st.n) ? v : 0.0;
+}
+
+template <int D>
+__device__ __forceinline__ void small_kstar_tiles(const SmallShared &sh, const cbo_small_set &st, int tiles,
+                                                  const double *xc, double csq, double csv, double inv_l2, int kq,
+                                                  d4 (&acc)[8])
+{
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        if (t < tiles) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[t][r] = small_kstar<D>(sh, st, 16 * t + kq + 4 * r, xc, csq, csv, inv_l2);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[t][r] = 0.0;
+        }
+    }
+}
+
+// The last workgroup of a set to finish (an atomic ticket) reduces the set's per-workgroup winners, hands the result
+// record to the host (pinned, device-mapped memory; `seq` is stored last, after a system-scope fence, so that the host
+// can poll it) and re-arms the set's status word and ticket for the next call.
+__device__ __forceinline__ void small_set_finish(double bv, int64_t bi, int set, int slot, int blocks_per_set,
+                                                 double *__restrict__ part_val, int64_t *__restrict__ part_idx,
+                                                 int *__restrict__ info, int *__restrict__ ticket,
+                                                 cbo_small_result *__restrict__ out, int seq, int *last_flag)
+{
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        part_val[slot] = bv;
+        part_idx[slot] = bi;
+        __threadfence();
+        *last_flag = (atomicAdd(&ticket[set], 1) == blocks_per_set - 1) ? 1 : 0;
+    }
+    __syncthreads();
+    if (*last_flag == 0 || tid >= 64) return;
+    __threadfence();
+    const int status = (tid == 0) ? atomicAdd(&info[set], 0) : 0;       // (in flight with the loads below)
+    bv = -INFINITY;
+    bi = INT64_MAX;
+    for (int b = tid; b < blocks_per_set; b += 64) {
+        const double v = __builtin_nontemporal_load(&part_val[set * blocks_per_set + b]);
+        const int64_t i = __builtin_nontemporal_load(&part_idx[set * blocks_per_set + b]);
+        if (better(v, i, bv, bi)) { bv = v; bi = i; }
+    }
+    wave_argmax(bv, bi);
+    if (tid == 0) {
+        out[set].best_val = bv;
+        out[set].best_idx = bi;
+        out[set].info = status;
+        __threadfence_system();
+        *reinterpret_cast<volatile int *>(&out[set].seq) = seq;
+        info[set] = 0;
+        ticket[set] = 0;
+    }
 }
 
 // Up to kSmallByValue descriptors travel as kernel arguments (no read across the host link before the first

@@ -285,75 +285,6 @@ void launch_panel_trsm(hipStream_t s, double *A, int64_t lda, int r0, int col0, 
                           done, 0, A, lda, r0, col0, invDt, skip_if);
 }
 
-template <int D>
-__device__ __forceinline__ double small_kstar(const SmallShared &sh, const cbo_small_set &st, int row, const double *xc,
-                                              double csq, double csv, double inv_l2)
-{
-    // (no branch around the value -- the four of a tile interleave; rows beyond n are zeros in LDS)
-    double xi[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) xi[k] = sh.xs[k][row];
-    double v = kernel_value<D>(xi, xc, sh.sq[row], csq, st.variance, inv_l2, false);
-    const double vc = __dadd_rn(v, __dmul_rn(sh.sv[row], csv));
-    v = (st.sv != nullptr) ? vc : v;
-    return (row < st.n) ? v : 0.0;
-}
-
-template <int D>
-__device__ __forceinline__ void small_kstar_tiles(const SmallShared &sh, const cbo_small_set &st, int tiles,
-                                                  const double *xc, double csq, double csv, double inv_l2, int kq,
-                                                  d4 (&acc)[8])
-{
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        if (t < tiles) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][r] = small_kstar<D>(sh, st, 16 * t + kq + 4 * r, xc, csq, csv, inv_l2);
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][r] = 0.0;
-        }
-    }
-}
-
-// The last workgroup of a set to finish (an atomic ticket) reduces the set's per-workgroup winners, hands the result
-// record to the host (pinned, device-mapped memory; `seq` is stored last, after a system-scope fence, so that the host
-// can poll it) and re-arms the set's status word and ticket for the next call.
-__device__ __forceinline__ void small_set_finish(double bv, int64_t bi, int set, int slot, int blocks_per_set,
-                                                 double *__restrict__ part_val, int64_t *__restrict__ part_idx,
-                                                 int *__restrict__ info, int *__restrict__ ticket,
-                                                 cbo_small_result *__restrict__ out, int seq, int *last_flag)
-{
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        part_val[slot] = bv;
-        part_idx[slot] = bi;
-        __threadfence();
-        *last_flag = (atomicAdd(&ticket[set], 1) == blocks_per_set - 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (*last_flag == 0 || tid >= 64) return;
-    __threadfence();
-    const int status = (tid == 0) ? atomicAdd(&info[set], 0) : 0;       // (in flight with the loads below)
-    bv = -INFINITY;
-    bi = INT64_MAX;
-    for (int b = tid; b < blocks_per_set; b += 64) {
-        const double v = __builtin_nontemporal_load(&part_val[set * blocks_per_set + b]);
-        const int64_t i = __builtin_nontemporal_load(&part_idx[set * blocks_per_set + b]);
-        if (better(v, i, bv, bi)) { bv = v; bi = i; }
-    }
-    wave_argmax(bv, bi);
-    if (tid == 0) {
-        out[set].best_val = bv;
-        out[set].best_idx = bi;
-        out[set].info = status;
-        __threadfence_system();
-        *reinterpret_cast<volatile int *>(&out[set].seq) = seq;
-        info[set] = 0;
-        ticket[set] = 0;
-    }
-}
-
 template <bool BYVAL>
 __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
                                                          double *scratch, int blocks_per_set,

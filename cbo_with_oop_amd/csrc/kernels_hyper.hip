@@ -1,0 +1,320 @@
+// The causal EI marginalised over hyper-parameter samples (emukit IntegratedHyperParameterAcquisition).
+//
+// hyper_avg_kernel: one workgroup of 256 threads per 64 candidates, small_sets_kernel's layout, for a model of at most 128
+// observations.  The workgroup walks the H samples in index order; for sample h it prepares the model's and its own
+// candidates' points from their RAW coordinates with sample h's lengthscales (prep_points_kernel's arithmetic), assembles
+// and factors K(X,X) + (noise_h + 1e-8) I inside LDS, forms K(X,X*) in the MFMA result registers, solves, and adds
+// acquisition_of(...) of its candidates to a per-candidate sum -- all with the device functions of cbo_small_device.h, so
+// each term is what cbo_acq_sweep writes for a model with sample h's hyper-parameters.  The sum is s = 0; s = s + acq_h
+// (h = 0..H-1), the result s / H: one IEEE division.  Nothing resident is read but the raw points, the targets and the
+// prior closures; nothing resident is written.
+//   phases 3: every workgroup factors every sample itself (its own scratch slot, reused sample after sample);
+//   phases 1: workgroup h factors sample h into scratch slot h and returns;  phases 2: the sweep reads factor h back.
+// The accumulate / finish kernels at the end serve the general path (larger, fp32 or jitter-needing models), whose
+// per-sample terms come from cbo_acq_sweep itself.
+#include <atomic>
+
+#include "cbo_small_device.h"
+
+namespace cbo {
+
+// One point from AoS raw coordinates: x[k] = raw[k] / ls[k] (ARD; ls null: unscaled), |x|^2 in prep_points_kernel's order
+__device__ __forceinline__ void hyper_point(const double *__restrict__ raw, int64_t i, int d, const double *ls, bool in,
+                                            double (&x)[CBO_MAX_DIM], double &sum)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < CBO_MAX_DIM; ++k) x[k] = 0.0;
+    if (in) {
+#pragma unroll
+        for (int k = 0; k < CBO_MAX_DIM; ++k)
+            if (k < d) {
+                double v = raw[i * d + k];
+                if (ls) v = v / ls[k];
+                x[k] = v;
+            }
+    }
+    if (d == 8) {
+        double r[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] = __dmul_rn(x[k], x[k]);
+        sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
+                        __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
+    } else {
+        sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < CBO_MAX_DIM; ++k)
+            if (k < d) sum = __dadd_rn(sum, __dmul_rn(x[k], x[k]));
+    }
+}
+
+// The descriptor of sample h: the model's with the sample's variance, lengthscale and noise in the place of its own
+__device__ __forceinline__ cbo_small_set hyper_sample_set(const cbo_small_set &st, const double *__restrict__ row, int n_ls)
+{
+    cbo_small_set sh = st;
+    sh.variance = row[0];
+    sh.lengthscale = st.ard ? 1.0 : row[1];
+    sh.noise_var = row[1 + n_ls];
+    sh.diag_add = __dadd_rn(sh.noise_var, kGpyDiagJitter);             // Ky = K + (noise + 1e-8) I
+    return sh;
+}
+
+// The model's points of sample h into LDS (threads 0..127), as the resident copies of a model with that sample's
+// lengthscales hold them.  The caller synchronises.
+__device__ __forceinline__ void hyper_model_points(SmallShared &sh, const cbo_small_set &st, const double *ls)
+{
+    const int tid = threadIdx.x;
+    if (tid < 128) {
+        const bool in = tid < st.n;
+        double x[CBO_MAX_DIM], sum;
+        hyper_point(st.raw, tid, st.d, ls, in, x, sum);
+#pragma unroll
+        for (int k = 0; k < CBO_MAX_DIM; ++k)
+            if (k < st.d) sh.xs[k][tid] = x[k];
+        sh.sq[tid] = sum;
+        sh.sv[tid] = (in && st.sv) ? sqrt(st.pv[tid]) : 0.0;
+    }
+}
+
+// K(X,X) + diag and the rhs into the block, the factorisation of the `tiles` real tiles into the scratch slot (Us, invs):
+// small_model_factor's steps between its point loads and its read-back, on points that are already in LDS
+__device__ __forceinline__ void hyper_factor(SmallShared &sh, const cbo_small_set &st, int tiles, double rhs, double *Us,
+                                             double *invs, int *info_word)
+{
+    const int tid = threadIdx.x;
+    switch (st.d) {
+        case 1: small_assemble<1>(sh, st, tiles); break;
+        case 2: small_assemble<2>(sh, st, tiles); break;
+        case 3: small_assemble<3>(sh, st, tiles); break;
+        case 4: small_assemble<4>(sh, st, tiles); break;
+        case 5: small_assemble<5>(sh, st, tiles); break;
+        case 6: small_assemble<6>(sh, st, tiles); break;
+        case 7: small_assemble<7>(sh, st, tiles); break;
+        default: small_assemble<8>(sh, st, tiles); break;
+    }
+    const int rows = 16 * tiles;
+    for (int r = tid >> 4; r < rows; r += 16)
+        for (int c = rows + (tid & 15); c < kDiagLd; c += 16) {
+            if (c == 128 && r < st.n) continue;                                                // (the rhs: below)
+            sh.blk.S[r][c] = 0.0;
+        }
+    if (tid < st.n) sh.blk.S[tid][128] = rhs;                                                  // r = y - m(X)
+    __syncthreads();
+    diag128_factor_in_lds(sh.blk, Us, kSmallLd, 0, 128, invs, info_word, nullptr, tiles, nullptr,
+                          (st.n - 16 * (tiles - 1) + 3) / 4);
+    // (ends with a barrier.)  Every wave's stores of factor rows / inverses / z are complete before anyone re-reads them
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+struct HyperArgs {
+    cbo_small_set st;                  // fill_small_model's descriptor + the candidates' prior closures, m, index_offset, EI's scalars
+    const double *craw;                // the candidates' raw AoS coordinates
+    const double *hyper;               // n_samples rows of (variance, lengthscale x n_ls, noise_var): pinned host memory
+    int n_samples, n_ls;
+    double *acq_out;                   // [m] device, or null
+};
+
+__global__ __launch_bounds__(256) void hyper_avg_kernel(const HyperArgs a, double *scratch, int blocks,
+                                                        double *__restrict__ part_val, int64_t *__restrict__ part_idx,
+                                                        int *__restrict__ info, int *__restrict__ ticket,
+                                                        cbo_small_result *__restrict__ out, int seq, int phases)
+{
+    __shared__ int last_flag;
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    SmallShared &sh = *reinterpret_cast<SmallShared *>(smem_raw);
+    const cbo_small_set &st = a.st;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lc = lane & 15, kq = lane >> 4;
+    const int blk = blockIdx.x;
+    const int tiles = (st.n + 15) / 16;
+    const int row_len = a.n_ls + 2;
+    // r = y - m(X) does not depend on the sample
+    double rhs = 0.0;
+    if (tid < st.n) {
+        const double yv = st.y[tid];
+        rhs = st.pm ? __dadd_rn(yv, -st.pm[tid]) : yv;
+    }
+    if (phases == 1) {                                            // workgroup h: factor sample h into slot h, nothing else
+        const double *row = a.hyper + (int64_t)blk * row_len;
+        const cbo_small_set sth = hyper_sample_set(st, row, a.n_ls);
+        double *fs = scratch + (int64_t)blk * kSmallScratch;
+        hyper_model_points(sh, st, st.ard ? row + 1 : nullptr);
+        __syncthreads();
+        hyper_factor(sh, sth, tiles, rhs, fs, fs + 128 * kSmallLd, &info[0]);
+        return;
+    }
+
+    // this wave's 16 candidates (clamped: lanes beyond the set compute, nobody looks)
+    const int64_t c = (int64_t)blk * 64 + wave * 16 + lc;
+    const int64_t cc = (c < st.m) ? c : st.m - 1;
+    const bool causal = st.sv != nullptr;
+    const double cpm_c = st.cpm ? st.cpm[cc] : 0.0, cpv_c = st.cpv ? st.cpv[cc] : 0.0;
+    const double csv = causal ? sqrt(cpv_c) : 0.0;
+
+    double sum = 0.0;
+    for (int h = 0; h < a.n_samples; ++h) {
+        const double *row = a.hyper + (int64_t)h * row_len;
+        const double *ls = st.ard ? row + 1 : nullptr;
+        const cbo_small_set sth = hyper_sample_set(st, row, a.n_ls);
+        // phases 3: the workgroup's own slot, sample after sample; phases 2: slot h holds sample h's factor
+        double *my = scratch + (int64_t)(phases == 2 ? h : blk) * kSmallScratch;
+        double *Us = my, *invs = my + 128 * kSmallLd;
+        double xc[CBO_MAX_DIM], csq;
+        hyper_point(a.craw, cc, st.d, ls, true, xc, csq);
+        __syncthreads();                                          // the previous sample's solve has read the block and the points
+        hyper_model_points(sh, st, ls);
+        __syncthreads();
+        if (phases & 1) hyper_factor(sh, sth, tiles, rhs, Us, invs, &info[0]);
+        // ---- the factor back into LDS (rows of the factored tiles), inverses and z to registers
+        {
+            const unsigned s0 = lds_byte_address(&sh.blk.S[0][0]);
+            const int rows = 16 * tiles;
+            for (int p = wave; p < rows; p += 4)
+                glds16(Us + (int64_t)p * kSmallLd + lane * 2, __builtin_amdgcn_readfirstlane(s0 + 8u * (unsigned)(p * kDiagLd)));
+        }
+        double iv[8][4], zr[8][4];
+#pragma unroll
+        for (int s = 0; s < 8; ++s)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                iv[s][kk] = (s < tiles) ? invs[s * 256 + (4 * kk + kq) * 16 + lc] : 0.0;
+                zr[s][kk] = (s < tiles) ? Us[(int64_t)(16 * s + kq + 4 * kk) * kSmallLd + 128] : 0.0;
+            }
+        // ---- K(X, X*) of this wave's 16 candidates, straight into the result layout
+        const double inv_l2 = 1.0 / (sth.lengthscale * sth.lengthscale);
+        d4 acc[8];
+        switch (st.d) {
+            case 1: small_kstar_tiles<1>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+            case 2: small_kstar_tiles<2>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+            case 3: small_kstar_tiles<3>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+            case 4: small_kstar_tiles<4>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+            case 5: small_kstar_tiles<5>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+            case 6: small_kstar_tiles<6>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+            case 7: small_kstar_tiles<7>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+            default: small_kstar_tiles<8>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+
+        // ---- V = L^-1 K*, q = sum V^2, mu = V^T z (lane partials, then over the four lane groups: the strip kernel's order)
+        double qacc = 0.0, macc = 0.0;
+        panel_solve_tiles(&sh.blk.S[kq][lc], acc, iv, tiles, [&](int s, const d4 &x) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                qacc = fma(x[r], x[r], qacc);
+                macc = fma(x[r], zr[s][r], macc);
+            }
+        });
+        qacc += __shfl_xor(qacc, 16);
+        qacc += __shfl_xor(qacc, 32);
+        macc += __shfl_xor(macc, 16);
+        macc += __shfl_xor(macc, 32);
+
+        AcqParams p;
+        p.variance = sth.variance; p.noise_var = sth.noise_var; p.y_best = st.y_best; p.ei_jitter = st.ei_jitter;
+        p.cost = st.cost; p.task = st.task; p.include_noise = 1; p.want_ei = 1;
+        if (kq == 0 && c < st.m) {
+            double mean, var;
+            posterior_of(qacc, macc, cpm_c, cpv_c, causal, p, mean, var);
+            sum = __dadd_rn(sum, acquisition_of(mean, var, p));
+        }
+    }
+
+    // ---- the mean, and the workgroup's arg-max of it
+    double bv = -INFINITY;
+    int64_t bi = INT64_MAX;
+    if (kq == 0 && c < st.m) {
+        bv = __ddiv_rn(sum, (double)a.n_samples);
+        bi = c + st.index_offset;
+        if (a.acq_out) a.acq_out[c] = bv;
+    }
+    wave_argmax(bv, bi);
+    double *red_v = &sh.sq[0];                         // free by now
+    int64_t *red_i = reinterpret_cast<int64_t *>(&sh.sv[0]);
+    __syncthreads();
+    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (better(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
+    }
+    small_set_finish(bv, bi, 0, blk, blocks, part_val, part_idx, info, ticket, out, seq, &last_flag);
+}
+
+size_t hyper_avg_scratch_doubles(int blocks, int n_samples)
+{
+    return (size_t)(blocks > n_samples ? blocks : n_samples) * kSmallScratch;
+}
+
+// From this many candidate blocks on, the samples are factored once by a first launch of n_samples workgroups and the sweep
+// reads the factors back (phases 1 + 2); below, every workgroup factors every sample itself (phases 3).  The threshold is
+// small_sets_kernel's own; profiles/hyper_avg_timing.json has both schedules at the three shapes of DESIGN.md §4j.
+constexpr int kHyperTwoPhaseFromBlocks = 12;
+
+void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
+                      int n_ls, double *acq_out, int blocks, int schedule, double *scratch, double *part_val,
+                      int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq)
+{
+    {
+        static std::atomic<unsigned long long> opted;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || !((opted.load(std::memory_order_relaxed) >> (dev & 63)) & 1ull)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(hyper_avg_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallShared)) == hipSuccess)
+                opted.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
+        }
+    }
+    HyperArgs a{};
+    a.st = st; a.craw = craw; a.hyper = hyper; a.n_samples = n_samples; a.n_ls = n_ls; a.acq_out = acq_out;
+    const bool two_phase = schedule == 2 || (schedule != 1 && blocks >= kHyperTwoPhaseFromBlocks);
+    if (two_phase) {
+        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)n_samples), dim3(256), sizeof(SmallShared), s, a, scratch, blocks,
+                           part_val, part_idx, info, ticket, out, seq, 1);
+        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, scratch, blocks,
+                           part_val, part_idx, info, ticket, out, seq, 2);
+    } else {
+        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, scratch, blocks,
+                           part_val, part_idx, info, ticket, out, seq, 3);
+    }
+}
+
+// ---- the general path's two kernels ------------------------------------------------------------------------------------
+// sum[i] = (first ? 0 : sum[i]) + acq[i]: the running sum of the per-sample acquisitions, in sample order
+__global__ __launch_bounds__(256) void hyper_accumulate_kernel(double *__restrict__ sum, const double *__restrict__ acq,
+                                                               int64_t m, int first)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+        sum[i] = __dadd_rn(first ? 0.0 : sum[i], acq[i]);
+}
+
+// acq[i] = sum[i] / n_samples (acq_out may be null) and the workgroups' arg-max partials for launch_argmax_final
+__global__ __launch_bounds__(256) void hyper_finish_kernel(const double *__restrict__ sum, int64_t m, int n_samples,
+                                                           double *__restrict__ acq_out, double *__restrict__ part_val,
+                                                           int64_t *__restrict__ part_idx, int64_t index_offset)
+{
+    double bv = -INFINITY;
+    int64_t bi = kNoIndex;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = __ddiv_rn(sum[i], (double)n_samples);
+        if (acq_out) acq_out[i] = v;
+        if (better(v, i + index_offset, bv, bi)) { bv = v; bi = i + index_offset; }
+    }
+    block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
+}
+
+void launch_hyper_accumulate(hipStream_t s, double *sum, const double *acq, int64_t m, bool first, int n_blocks)
+{
+    hipLaunchKernelGGL(hyper_accumulate_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, sum, acq, m, first ? 1 : 0);
+}
+
+void launch_hyper_finish(hipStream_t s, const double *sum, int64_t m, int n_samples, double *acq_out, double *part_val,
+                         int64_t *part_idx, int64_t index_offset, int n_blocks)
+{
+    hipLaunchKernelGGL(hyper_finish_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, sum, m, n_samples, acq_out, part_val,
+                       part_idx, index_offset);
+}
+
+}  // namespace cbo

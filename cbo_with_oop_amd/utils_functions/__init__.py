@@ -5,6 +5,7 @@ from .causal_optimizer import CausalGradientAcquisitionOptimizer  # noqa: F401
 from .constrained import AcquisitionProduct, ProbabilityOfFeasibility  # noqa: F401
 from .cost_functions import Cost, total_cost  # noqa: F401
 from .greedy_batch import GreedyBatchPointCalculator  # noqa: F401
+from .integrated_hyper import IntegratedHyperParameterAcquisition, hmc_sample  # noqa: F401
 from .integrated_variance import IntegratedVarianceReduction  # noqa: F401
 from .max_value_entropy import MaxValueEntropySearch  # noqa: F401
 from .utils import (compute_coverage, find_current_global, find_next_y_point, find_next_y_points,  # noqa: F401

@@ -104,7 +104,7 @@ def default_grid_shape(d, budget=None):
 
 def find_next_y_point(space, model, current_global_best, evaluated_set, costs_functions, task='min',
                       grid_shape=None, candidates=None, anchors="grid", num_anchor_points=None, acquisition="EI",
-                      batch_size=None, constraints=None):
+                      batch_size=None, hyper_samples=None, constraints=None):
     """utils.py:29-37.  Returns (y_acquisition (1,1), x_new (1,d)).
 
     ``candidates`` (optional (M,d) array or CandidateGrid) overrides the regular grid over ``space``.
@@ -120,7 +120,22 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     ``batch_size`` (a positive int): greedy batch selection over the grid (greedy_batch.py, one ``cbo_acq_sweep_batch``
     call): returns (y (B,1), x (B,d)), row 0 being the single-point result; together with ``acquisition="MES"``,
     ``constraints`` or ``anchors="uniform"`` it raises ``ValueError``.  ``None``: nothing changes.
+    ``hyper_samples`` (an (H, P) array of hyper-parameter samples, or an int: that many drawn by the model's HMC with the
+    defaults): the grid is scored with the EI marginalised over the samples, over the cost, in one device call
+    (integrated_hyper.py, ``cbo_acq_sweep_hyper``); together with ``acquisition="MES"``, ``constraints``, ``batch_size`` or
+    ``anchors="uniform"`` it raises ``ValueError``.  ``None``: nothing changes.
     """
+    if hyper_samples is not None:
+        if acquisition != "EI":
+            raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI'")
+        if constraints is not None:
+            raise ValueError("the marginalised EI is not defined with constraints: constraints must be None")
+        if batch_size is not None:
+            raise ValueError("the marginalised EI picks one point: batch_size must be None")
+        if anchors != "grid":
+            raise ValueError("the marginalised EI is scored over the grid: anchors must be 'grid'")
+        if isinstance(hyper_samples, bool) or (isinstance(hyper_samples, (int, np.integer)) and hyper_samples < 1):
+            raise ValueError(f"hyper_samples must be an (H, P) array or a positive int, not {hyper_samples!r}")
     if batch_size is not None:
         if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
             raise ValueError(f"batch_size must be a positive int, not {batch_size!r}")
@@ -157,6 +172,13 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     if constraints:
         from .constrained import AcquisitionProduct
         ei = AcquisitionProduct([ei] + list(constraints))      # the sets of the constraints' models follow the grid's
+    if hyper_samples is not None:
+        from .integrated_hyper import IntegratedHyperParameterAcquisition
+        generator = lambda mdl: CausalExpectedImprovement(current_global_best, task, mdl)      # noqa: E731
+        if isinstance(hyper_samples, (int, np.integer)):
+            ei = IntegratedHyperParameterAcquisition(model, generator, n_samples=int(hyper_samples))
+        else:
+            ei = IntegratedHyperParameterAcquisition(model, generator, samples=hyper_samples)
     own = False
     if candidates is None:
         bounds = space_bounds(space)

@@ -300,6 +300,40 @@ int cbo_acq_sweep_constrained(cbo_gp *gp, cbo_cands *cands, double y_best, int t
                               double *acq_out, double *ei_out, double *pof_out /* n_con * m, constraint-major */,
                               double *best_val, int64_t *best_idx);
 
+/* The causal EI over a cost, marginalised over hyper-parameter samples, with the arg-max -- emukit's
+ * IntegratedHyperParameterAcquisition(model, acquisition_generator, n_samples) around ExpectedImprovement / Cost, whose
+ * evaluate() is `for sample in samples: model.fix_model_hyperparameters(sample); acquisition_value += acquisition.evaluate(x)`
+ * and `return acquisition_value / n_samples` (emukit 0.4 restated from memory; emukit is not a dependency, parity is
+ * unpinned, the contract is DESIGN.md §4j):
+ *     acq_out[i] = ((((0 + a_0i) + a_1i) + ...) + a_(H-1)i) / H       (additions in sample order, one IEEE division last)
+ * where a_hi is what cbo_acq_sweep(gp_h, cands, y_best, task, ei_jitter, cost, ...) writes to acq_out[i] for a model gp_h
+ * with the data of gp and the hyper-parameters of sample h -- the 'max' task's sign quirk and the causal priors included;
+ * m(.) and v(.) at X and X* do not depend on the sample.  Two identical calls return the same bits.
+ * hyper: n_samples rows of (variance, lengthscale x L, noise_var), L = d if the model is ard else 1: GPy's parameter order
+ * for GPRegression with an RBF kernel (rbf.variance, rbf.lengthscale, Gaussian_noise.variance).
+ * best_idx: lowest index on ties, NaN maximal, offset by the set's index_offset.  acq_out (m) may be NULL; best_val and
+ * best_idx may be NULL when acq_out is not.
+ *  - An fp64 model of at most 128 observations (unless CBO_HIP_SMALL_SETS=0, or above 65535 candidate blocks of 64) is
+ *    answered by one launch (two from 12 candidate blocks on) that factors every sample's Ky inside LDS from the model's
+ *    and the set's RAW coordinates.  The model need not be fitted, and NOTHING of the model or the candidate set is touched:
+ *    factor, z, fit stamp, hyper-parameters, the scaled point sets, cached q / mu, kept solutions.  A cbo_acq_sweep before
+ *    and after the call returns the same bits.
+ *  - Larger and fp32 models, and a small model one of whose samples is not positive definite as assembled, take the general
+ *    path: for h in order cbo_gp_set_hyper, cbo_gp_fit (the jitchol ladder) and cbo_acq_sweep with the acquisition kept on
+ *    the device and added in by a small kernel; one closing kernel divides and takes the arg-max.  Afterwards the model's
+ *    hyper-parameters are restored and, if it was fitted on entry, it is refitted: the same factor (the fit is
+ *    deterministic) under a NEW fit stamp, so the caches of every candidate set swept with this model are recomputed at
+ *    their next sweep, and a kept solution no longer extends by an append.  A sample whose ladder runs out: CBO_ERR_NOT_PD
+ *    (CBO_ERR_NONPOS_DIAG), after restoring.
+ * CBO_ERR_INVALID: cbo_acq_sweep's argument checks, n_samples outside 1..CBO_MAX_HYPER_SAMPLES, NULL hyper, NULL best_val
+ * or best_idx together with NULL acq_out, cost <= 0 or NaN, a non-finite or non-positive variance or lengthscale or a
+ * negative or non-finite noise_var in any row.  There is no CBO_ERR_NOT_FITTED: neither path needs a fit. */
+#define CBO_MAX_HYPER_SAMPLES 256
+int cbo_acq_sweep_hyper(cbo_gp *gp, cbo_cands *cands, int n_samples,
+                        const double *hyper /* n_samples rows of (variance, lengthscale x L, noise_var) */,
+                        double y_best, int task, double ei_jitter, double cost, double *acq_out /* m, may be NULL */,
+                        double *best_val, int64_t *best_idx);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
