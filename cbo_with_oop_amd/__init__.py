@@ -2,7 +2,8 @@
 ChampiB/CBO_with_OOP API surface (see DESIGN.md).  Importing the package does not touch the GPU;
 creating a model does, and fails loudly when libcbo_hip.so or a gfx950 device is missing."""
 from .GaussianProcessFactory import GaussianProcessFactory, GaussianProcessType, HipGaussianProcess  # noqa: F401
-from .utils_functions import (CandidateGrid, CausalExpectedImprovement, Cost,  # noqa: F401
+from .utils_functions import (CandidateGrid, CausalExpectedImprovement, CausalMeanPluginExpectedImprovement,  # noqa: F401
+                              CausalNegativeLowerConfidenceBound, CausalProbabilityOfImprovement, Cost, ModelVariance,
                               IntegratedHyperParameterAcquisition, IntegratedVarianceReduction, MaxValueEntropySearch, find_current_global, find_next_y_point, total_cost)
 from .CBO import CBOAcquisitionPath  # noqa: F401
 from .DoCalculus import DoCalculus, do_prior_functions  # noqa: F401

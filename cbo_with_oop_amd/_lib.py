@@ -34,6 +34,7 @@ CBO_ERR_COMM = -8
 
 TASK_CODE = {"min": 0, "max": 1}
 DTYPE_CODE = {"f64": 0, "f32": 1}
+ACQ_KIND_CODE = {"LCB": 1, "PI": 2, "VAR": 3, "MPEI": 4}      # CBO_ACQ_LCB, _PI, _VAR, _MPEI
 
 
 class CboTimers(ctypes.Structure):
@@ -109,6 +110,10 @@ SIGNATURES = {
                                                  c_double_p, c_int64_p]),
     "cbo_acq_sweep_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_double,
                                            ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_int64_p]),
+    "cbo_acq_sweep_kind": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                          ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
+                                          c_int64_p]),
+    "cbo_gp_plugin_incumbent": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p]),
     "cbo_gp_set_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p, ctypes.c_double]),
     "cbo_gp_log_marginal": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "cbo_gp_lml_gradients": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),

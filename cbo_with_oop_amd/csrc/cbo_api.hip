@@ -151,6 +151,7 @@ struct cbo_ctx {
     GrowBuf<double> samp_Z, samp_out;
     GrowBuf<double> ivr_part;                          // cbo_gp_integrated_variance_reduction: [m][tiles] partials
     GrowBuf<double> con_terms;                         // cbo_acq_sweep_constrained: [n_con][m_pad] probabilities of feasibility
+    GrowBuf<double> plugin_y;                          // cbo_acq_sweep_kind (MPEI), cbo_gp_plugin_incumbent: the incumbent, one double
     // cbo_acq_sweep_batch: the fantasy rows [batch_size - 1][m_pad], the working copy of q, the pivot column [n_pad], the
     // slice sums of the pass over V [kBatchMaxSlices][m_pad], the pick's scalars, and the winners (pinned: written by kernels)
     GrowBuf<double> batch_W, batch_q, batch_col, batch_part;
@@ -1384,15 +1385,19 @@ static int copy_posterior_out(cbo_ctx *c, const cbo_cands *k, double *acq_out, d
 }
 
 // mes: max-value entropy search's epilogue (mes_acq_kernel) in the place of EI's; y_best, task and ei_jitter are then unused
+// kind: CBO_ACQ_LCB / _PI / _VAR: pointwise_acq_kernel in the place of EI's, ei_jitter being the kind's parameter; 0 and
+// CBO_ACQ_MPEI: EI -- with y_best_dev, its incumbent is read from there (device memory) and y_best is unused
 static int enqueue_finish(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost, double *acq_out,
                           double *mean_out, double *var_out, const double *q_src, const double *mu_src,
-                          bool with_status = false, bool copy_out = true, const MesParams *mes = nullptr)
+                          bool with_status = false, bool copy_out = true, const MesParams *mes = nullptr, int kind = 0,
+                          const double *y_best_dev = nullptr)
 {
     cbo_ctx *c = g->ctx;
     const bool causal = g->X.sv != nullptr;
     AcqParams p;
     p.variance = g->h.variance; p.noise_var = g->noise_var; p.y_best = y_best; p.ei_jitter = ei_jitter; p.cost = cost;
     p.task = task; p.include_noise = 1; p.want_ei = 1;
+    p.y_best_dev = y_best_dev;
     const int nb = acq_blocks_for(k->m);
     {
         PhaseScope ps(c, PH_ACQ);
@@ -1400,6 +1405,10 @@ static int enqueue_finish(cbo_gp *g, cbo_cands *k, double y_best, int task, doub
             launch_mes_acq(c->stream, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, *mes,
                            mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr,
                            c->part_val, c->part_idx, k->index_offset, nb);
+        else if (kind == CBO_ACQ_LCB || kind == CBO_ACQ_PI || kind == CBO_ACQ_VAR)
+            launch_pointwise_acq(c->stream, kind, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, p,
+                                 mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr,
+                                 c->part_val, c->part_idx, k->index_offset, nb);
         else
             launch_acq(c->stream, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, p,
                        mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr, c->part_val,
@@ -1442,13 +1451,14 @@ static int settle_vectors(cbo_gp *g, cbo_cands *k, bool own, const double **q_sr
 
 static int finish_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
                         double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx,
-                        const MesParams *mes = nullptr)
+                        const MesParams *mes = nullptr, int kind = 0, const double *y_best_dev = nullptr)
 {
     cbo_ctx *c = g->ctx;
     const double *q_src = nullptr, *mu_src = nullptr;
     int rc = settle_vectors(g, k, false, &q_src, &mu_src);
     if (rc != CBO_OK) return rc;
-    rc = enqueue_finish(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, q_src, mu_src, false, true, mes);
+    rc = enqueue_finish(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, q_src, mu_src, false, true, mes,
+                        kind, y_best_dev);
     if (rc != CBO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     complete_finish(c, best_val, best_idx);
@@ -1748,14 +1758,16 @@ static int enqueue_vectors(cbo_gp *g, cbo_cands *k, bool *substituted = nullptr)
     return grow_vectors(c, k->m_pad);                    // mean / var / acq scratch of the epilogue
 }
 
-// then the epilogue: EI / cost, or max-value entropy search / cost when mes is given
+// then the epilogue: EI / cost, max-value entropy search / cost when mes is given, or a point-wise kind's (enqueue_finish)
 static int sweep_impl(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost, double *acq_out,
-                      double *mean_out, double *var_out, double *best_val, int64_t *best_idx, const MesParams *mes)
+                      double *mean_out, double *var_out, double *best_val, int64_t *best_idx, const MesParams *mes,
+                      int kind = 0, const double *y_best_dev = nullptr)
 {
     HIP_TRY(hipSetDevice(g->ctx->device));
     const int rc = enqueue_vectors(g, k);
     if (rc != CBO_OK) return rc;
-    return finish_sweep(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, mes);
+    return finish_sweep(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, mes, kind,
+                        y_best_dev);
 }
 
 extern "C" int cbo_acq_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
@@ -2644,6 +2656,74 @@ extern "C" int cbo_gp_predict(cbo_gp *g, int64_t m, const double *Xs, const doub
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->profiling) c->timers.n_sweep += 1;
     return CBO_OK;
+}
+
+// ---- point-wise acquisitions (kernels_pointwise.hip) -------------------------------------------------------
+// The plug-in incumbent of emukit's MeanPluginExpectedImprovement, min (max) over model.predict(model.X)[0], into the
+// context's device double: the model's own points become the scratch set (device copies of what was uploaded: the raw
+// coordinates and the prior closures) and are predicted as cbo_gp_predict predicts host points -- the same preparation,
+// substitution and epilogue, so the same bits -- then one reduction.  Queued; the caller synchronises.
+static int enqueue_plugin_incumbent(cbo_gp *g, int task)
+{
+    cbo_ctx *c = g->ctx;
+    const bool causal = g->X.sv != nullptr;
+    cbo_cands *k = scratch_set(c);
+    int rc = cands_reserve(k, g->n, g->d, causal);
+    if (rc != CBO_OK) return rc;
+    cands_describe(k, g->n, g->d, causal, 0);
+    HIP_TRY(hipMemcpyAsync(k->raw, g->raw, sizeof(double) * g->n * g->d, hipMemcpyDeviceToDevice, c->stream));
+    if (causal) {
+        HIP_TRY(hipMemcpyAsync(k->pm, g->X.pm, sizeof(double) * g->n, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(k->pv, g->X.pv, sizeof(double) * g->n, hipMemcpyDeviceToDevice, c->stream));
+    }
+    rc = posterior_of_set(g, k, 1);
+    if (rc == CBO_OK) rc = grow(c, c->plugin_y, 1);
+    if (rc != CBO_OK) return rc;
+    launch_plugin_incumbent(c->stream, c->mean, g->n, task, c->plugin_y);
+    HIP_TRY(hipGetLastError());
+    return CBO_OK;
+}
+
+extern "C" int cbo_gp_plugin_incumbent(cbo_gp *g, int task, double *incumbent_out)
+{
+    if (!g || !incumbent_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (task != CBO_TASK_MIN && task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = enqueue_plugin_incumbent(g, task);
+    if (rc != CBO_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(incumbent_out, c->plugin_y, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CBO_OK;
+}
+
+// emukit NegativeLowerConfidenceBound, ProbabilityOfImprovement, ModelVariance and MeanPluginExpectedImprovement over a
+// cost: the EI sweep's path up to q, mu (sweep_impl), then the kind's epilogue.  The plug-in EI's incumbent is formed first
+// (its prediction uses the context's vectors, which the sweep's substitution then overwrites) and stays on the device.
+extern "C" int cbo_acq_sweep_kind(cbo_gp *g, cbo_cands *k, int kind, double y_best, int task, double param, double cost,
+                                  double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx)
+{
+    if (kind != CBO_ACQ_LCB && kind != CBO_ACQ_PI && kind != CBO_ACQ_VAR && kind != CBO_ACQ_MPEI)
+        return fail(CBO_ERR_INVALID, "kind must be CBO_ACQ_LCB, CBO_ACQ_PI, CBO_ACQ_VAR or CBO_ACQ_MPEI");
+    if (kind == CBO_ACQ_VAR) { y_best = 0.0; task = CBO_TASK_MIN; param = 0.0; }       // not read
+    if (kind == CBO_ACQ_MPEI) y_best = 0.0;                                             // not read
+    int rc = check_sweep_args(g, k, task);
+    if (rc != CBO_OK) return rc;
+    if (!std::isfinite(param)) return fail(CBO_ERR_INVALID, "param (beta / jitter) must be finite");
+    if (kind == CBO_ACQ_LCB && param < 0.0) return fail(CBO_ERR_INVALID, "beta must not be negative");
+    if (kind == CBO_ACQ_PI && !std::isfinite(y_best)) return fail(CBO_ERR_INVALID, "y_best must be finite");
+    if (!(cost > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    const double *y_best_dev = nullptr;
+    if (kind == CBO_ACQ_MPEI) {
+        HIP_TRY(hipSetDevice(g->ctx->device));
+        rc = enqueue_plugin_incumbent(g, task);
+        if (rc != CBO_OK) return rc;
+        y_best_dev = g->ctx->plugin_y;
+    }
+    return sweep_impl(g, k, y_best, task, param, cost, acq_out, mean_out, var_out, best_val, best_idx, nullptr, kind,
+                      y_best_dev);
 }
 
 // emukit MaxValueEntropySearch.update_parameters' model.predict(grid) and _fit_gumbel: the grid's predictive mean and

@@ -317,4 +317,22 @@ __device__ __forceinline__ double acquisition_of(double mean, double var, const 
     return fma(fma(-qv, p.cost, imp), rc, qv);
 }
 
+// emukit ProbabilityOfFeasibility / ProbabilityOfImprovement of one candidate: ndtr(+-(value - (mean + jitter)) / sd).  sd and the quotient as acquisition_of has them (one hardware estimate, the
+// quotient corrected by its own remainder: within half an ulp and a bit of the IEEE one), the density's exponential shared
+// with cephes ndtr (ndtr_with_exp).  A NaN mean or variance gives NaN.
+__device__ __forceinline__ double feasibility_of(double mean, double var, double value, double jitter, int sense)
+{
+#pragma clang fp contract(off)
+    double s, rs;
+    bool special;
+    sqrt_and_reciprocal(var, s, rs, special);
+    const double a = value - (mean + jitter);
+    double u = a * rs;
+    u = fma(fma(-u, s, a), rs, u);
+    if (__builtin_expect(special, 0)) u = a / s;                    // (a zero or infinite variance: the IEEE quotient)
+    if (sense != CBO_CON_LE) u = -u;                                // (uniform)
+    const double e = exp_nonpositive(-(u * u) / 2.0);
+    return ndtr_with_exp(u, e);
+}
+
 }  // namespace cbo

@@ -391,6 +391,15 @@ struct ConParams {
 // launch grid and arg-max partials as launch_acq (acq_blocks_for)
 void launch_constrained_acq(hipStream_t s, const ConParams &p, int64_t m, double *acq_out, double *part_val,
                             int64_t *part_idx, int64_t index_offset, int n_blocks);
+// ---- point-wise acquisitions (kernels_pointwise.hip) -------------------------------------------------
+// kind CBO_ACQ_LCB / _PI / _VAR: acq_kernel's mean and variance (noise included), then the kind's value / cost.  p.ei_jitter
+// carries the kind's parameter (beta; PI's jitter), p.y_best PI's incumbent; p.want_ei and p.y_best_dev are not read.
+// Launch grid and arg-max partials as launch_acq (acq_blocks_for).
+void launch_pointwise_acq(hipStream_t s, int kind, const double *q, const double *mu, const double *pm, const double *pv,
+                          int64_t m, const AcqParams &p, double *mean_out, double *var_out, double *acq_out,
+                          double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks);
+// out[0] (device) = min (CBO_TASK_MIN) or max of mean[0:n), NaN if any of them is
+void launch_plugin_incumbent(hipStream_t s, const double *mean, int64_t n, int task, double *out);
 // out[g] = mean of in[g*group .. (g+1)*group)
 void launch_group_mean(hipStream_t s, const double *in, int64_t n_groups, int64_t group, double *out);
 

@@ -17,22 +17,7 @@
 
 namespace cbo {
 
-// ndtr(+-(value - (mean + jitter)) / sd).  sd and the quotient as acquisition_of has them (one hardware estimate, the
-// quotient corrected by its own remainder: within half an ulp and a bit of the IEEE one), the density's exponential shared
-// with cephes ndtr (ndtr_with_exp).  A NaN mean or variance gives NaN.
-__device__ __forceinline__ double feasibility_of(double mean, double var, double value, double jitter, int sense)
-{
-    double s, rs;
-    bool special;
-    sqrt_and_reciprocal(var, s, rs, special);
-    const double a = value - (mean + jitter);
-    double u = a * rs;
-    u = fma(fma(-u, s, a), rs, u);
-    if (__builtin_expect(special, 0)) u = a / s;                    // (a zero or infinite variance: the IEEE quotient)
-    if (sense != CBO_CON_LE) u = -u;                                // (uniform)
-    const double e = exp_nonpositive(-(u * u) / 2.0);
-    return ndtr_with_exp(u, e);
-}
+// (one constraint's term: feasibility_of, cbo_device.h -- shared with the probability of improvement, kernels_pointwise.hip)
 
 // acq_kernel's structure (kernels_acq.hip; its comments say why): two consecutive candidates per lane and step (16-byte
 // loads and stores), addresses "scalar base + 32-bit lane offset", and every memory operation of a step issued in one place

@@ -120,6 +120,11 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     ``batch_size`` (a positive int): greedy batch selection over the grid (greedy_batch.py, one ``cbo_acq_sweep_batch``
     call): returns (y (B,1), x (B,d)), row 0 being the single-point result; together with ``acquisition="MES"``,
     ``constraints`` or ``anchors="uniform"`` it raises ``ValueError``.  ``None``: nothing changes.
+    ``acquisition="LCB" | "PI" | "MPEI" | "VAR"``: the point-wise acquisitions of pointwise_acquisitions.py -- emukit's
+    ``NegativeLowerConfidenceBound`` (beta 1), ``ProbabilityOfImprovement``, ``MeanPluginExpectedImprovement`` and
+    ``ModelVariance`` -- over the cost, on the grid or with ``anchors="uniform"`` (they have gradients).  ``"MPEI"`` and
+    ``"VAR"`` do not use ``current_global_best``, ``"VAR"`` does not use ``task``.  Together with ``constraints``,
+    ``batch_size`` or ``hyper_samples`` they raise those branches' ``ValueError``.
     ``hyper_samples`` (an (H, P) array of hyper-parameter samples, or an int: that many drawn by the model's HMC with the
     defaults): the grid is scored with the EI marginalised over the samples, over the cost, in one device call
     (integrated_hyper.py, ``cbo_acq_sweep_hyper``); together with ``acquisition="MES"``, ``constraints``, ``batch_size`` or
@@ -145,8 +150,8 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
             raise ValueError("batch selection is not defined for constrained acquisitions: constraints must be None")
         if anchors != "grid":
             raise ValueError("batch selection picks from the grid: anchors must be 'grid'")
-    if acquisition not in ("EI", "MES"):
-        raise ValueError(f"acquisition must be 'EI' or 'MES', not {acquisition!r}")
+    if acquisition not in ("EI", "MES") + POINTWISE_ACQUISITIONS:
+        raise ValueError(f"acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR', not {acquisition!r}")
     if acquisition == "MES":
         if task != "min":
             raise ValueError("acquisition='MES' minimises: task must be 'min'")
@@ -161,14 +166,10 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     if anchors == "uniform":
         from .causal_optimizer import CausalGradientAcquisitionOptimizer
         optimizer = CausalGradientAcquisitionOptimizer(space, num_anchor_points=num_anchor_points, anchors="uniform")
-        acquisition = CausalExpectedImprovement(current_global_best, task, model) / cost_acquisition
+        acquisition = _acquisition_for(acquisition, model, current_global_best, task, space) / cost_acquisition
         x_new, _ = optimizer.optimize(acquisition)
         return acquisition.evaluate(x_new), x_new
-    if acquisition == "MES":
-        from .max_value_entropy import MaxValueEntropySearch
-        ei = MaxValueEntropySearch(model, space)
-    else:
-        ei = CausalExpectedImprovement(current_global_best, task, model)
+    ei = _acquisition_for(acquisition, model, current_global_best, task, space)
     if constraints:
         from .constrained import AcquisitionProduct
         ei = AcquisitionProduct([ei] + list(constraints))      # the sets of the constraints' models follow the grid's
@@ -206,6 +207,26 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
         if own:
             grid.close()
     return y, x_new
+
+
+POINTWISE_ACQUISITIONS = ("LCB", "PI", "MPEI", "VAR")
+
+
+def _acquisition_for(name, model, current_global_best, task, space):
+    """The acquisition object ``find_next_y_point(acquisition=name)`` scores with (defaults: beta 1, jitter 0)."""
+    if name == "MES":
+        from .max_value_entropy import MaxValueEntropySearch
+        return MaxValueEntropySearch(model, space)
+    if name in POINTWISE_ACQUISITIONS:
+        from . import pointwise_acquisitions as pw
+        if name == "LCB":
+            return pw.CausalNegativeLowerConfidenceBound(task, model)
+        if name == "PI":
+            return pw.CausalProbabilityOfImprovement(current_global_best, task, model)
+        if name == "MPEI":
+            return pw.CausalMeanPluginExpectedImprovement(task, model)
+        return pw.ModelVariance(model)
+    return CausalExpectedImprovement(current_global_best, task, model)
 
 
 def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):

@@ -334,6 +334,41 @@ int cbo_acq_sweep_hyper(cbo_gp *gp, cbo_cands *cands, int n_samples,
                         double y_best, int task, double ei_jitter, double cost, double *acq_out /* m, may be NULL */,
                         double *best_val, int64_t *best_idx);
 
+/* The point-wise acquisitions a GPy / emukit user reaches for next to EI, over a cost, with the arg-max: emukit's
+ * NegativeLowerConfidenceBound, ProbabilityOfImprovement, MeanPluginExpectedImprovement and (experimental design)
+ * ModelVariance under a Quotient with a Cost (emukit 0.4 restated from memory; emukit is not a dependency, parity is
+ * unpinned, the contract is DESIGN.md §4k).  mean / var: cbo_gp_predict(..., include_noise = 1) at the candidate, bit for
+ * bit -- what cbo_acq_sweep writes to mean_out / var_out; s = sqrt(var), the IEEE square root.
+ *  - CBO_ACQ_LCB:  acq = -(mean - param * s) / cost for task 'min', (mean + param * s) / cost for 'max'; param = beta,
+ *    finite and >= 0; y_best is not read.  One rounding per operation, as numpy applies them.  The value can be negative,
+ *    and it is divided by the cost all the same, as emukit's Quotient does: a negative bound then FAVOURS the costly
+ *    intervention.
+ *  - CBO_ACQ_PI:   acq = ndtr(u) / cost for 'min', ndtr(-u) / cost for 'max', u = (y_best - (mean + param)) / s; param = the
+ *    jitter.  At cost 1 bit for bit the pof_out of cbo_acq_sweep_constrained(NULL, NULL, ..., n_con = 1, the same model and
+ *    set, con_value = y_best, con_jitter = param, CBO_CON_LE for 'min', CBO_CON_GE for 'max').
+ *  - CBO_ACQ_VAR:  acq = var / cost; y_best, task and param are not read.
+ *  - CBO_ACQ_MPEI: cbo_acq_sweep(gp, cands, cbo_gp_plugin_incumbent(gp, task), task, param, cost, ...) bit for bit -- acq_out,
+ *    best_val and best_idx -- with the incumbent kept on the device (no host round trip); param = EI's jitter, y_best is not
+ *    read.  A NaN incumbent (a NaN prior mean at a training point) gives cbo_acq_sweep's result for y_best = NaN.
+ * The quotient by the cost is cbo_acq_sweep's: the IEEE one for every cost whose significand is not all ones; only the sign
+ * of a zero can differ.  best_idx: lowest index on ties, NaN maximal, offset by the set's index_offset.  acq_out / mean_out
+ * / var_out (m doubles each), best_val and best_idx may be NULL.  q, mu are reached exactly as cbo_acq_sweep reaches them
+ * (the candidates' cached copies when the fit stamp matches, one appended row or block after cbo_gp_append /
+ * cbo_gp_append_block, the fp32 strip of fp32 models, the chunked substitution otherwise), and the model and the set are
+ * left as cbo_acq_sweep leaves them.  Out of scope: the single launch of small sets (cbo_acq_sweep_sets, cbo_trial_step),
+ * refitting in the same call (cbo_gp_fit_sweep), the batch, hyper-marginalised and constrained calls, the multi-GPU exchange.
+ * CBO_ERR_INVALID: cbo_acq_sweep's argument checks, a kind outside 1..4, a non-finite param, beta < 0, a non-finite y_best
+ * for CBO_ACQ_PI, cost <= 0 or NaN, a bad task for every kind but CBO_ACQ_VAR.  Unfitted model: CBO_ERR_NOT_FITTED.
+ *
+ * cbo_gp_plugin_incumbent: the incumbent CBO_ACQ_MPEI uses -- min (task 'min') or max ('max') over the n posterior means
+ * at the model's own inputs, cbo_gp_predict(gp, n, X, prior closures at X, include_noise = 1)'s bits (computed as that
+ * prediction, from the device copies of the data), NaN if any of them is (np.min / np.max).  NULL argument, bad task:
+ * CBO_ERR_INVALID; unfitted model: CBO_ERR_NOT_FITTED.  The model is only read. */
+enum { CBO_ACQ_LCB = 1, CBO_ACQ_PI = 2, CBO_ACQ_VAR = 3, CBO_ACQ_MPEI = 4 };
+int cbo_acq_sweep_kind(cbo_gp *gp, cbo_cands *cands, int kind, double y_best, int task, double param, double cost,
+                       double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx);
+int cbo_gp_plugin_incumbent(cbo_gp *gp, int task, double *incumbent_out);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
