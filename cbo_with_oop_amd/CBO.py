@@ -22,10 +22,19 @@ class _FixedCosts:
 
 class CBOAcquisitionPath:
     """Holds exactly the state those methods read on the reference's ``CBO`` object: ``gp_type``,
-    ``exploration_set``, ``costs``, ``task``, per-set data, spaces, prior closures and models."""
+    ``exploration_set``, ``costs``, ``task``, per-set data, spaces, prior closures and models.  ``acquisition`` (``"EI"``,
+    the reference's, or ``"LCB" | "PI" | "MPEI" | "VAR"``) and ``acquisition_param`` (beta, default 1; the jitter of PI and
+    MPEI, default 0) name what every exploration set is scored with (``find_next_y_points``); they are fixed
+    at construction."""
 
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
-                 var_functions=None, grid_shapes=None, keep_solutions=True, comm="env"):
+                 var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
+                 acquisition_param=None):
+        from .utils_functions.utils import sets_acquisition
+        # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
+        # (``find_next_y_points``); fixed at construction and checked here, before any device call
+        self._kind = sets_acquisition(acquisition, acquisition_param)
+        self.acquisition, self.acquisition_param = acquisition, acquisition_param
         self.gp_type = gp_type
         self.exploration_set = exploration_set
         self.es_size = len(exploration_set)
@@ -137,13 +146,14 @@ class CBOAcquisitionPath:
         return cached[1]
 
     def compute_best_acquisition_values(self, current_best):
-        """CBO.py:237-260: the loop over the exploration sets, as ONE device call (``cbo_acq_sweep_sets``); across
-        several GPUs, this rank's share of it and one arg-max exchange per set."""
+        """CBO.py:237-260: the loop over the exploration sets, as ONE device call (``cbo_acq_sweep_sets``, or
+        ``cbo_acq_sweep_sets_kind`` for the path's point-wise ``acquisition``); across several GPUs, this rank's share of
+        it and one arg-max exchange per set."""
         mode, world, rank = self.placement()
         if mode == "single":
             grids = [self.candidate_grid(s) for s in range(self.es_size)]
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
-                                      cache=self._call_cache)
+                                      cache=self._call_cache, acquisition=self._kind)
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -159,7 +169,7 @@ class CBOAcquisitionPath:
                              for s in mine}
                 _, ys = find_next_y_points([self.models[s] for s in mine], current_best,
                                            [self.exploration_set[s] for s in mine], _FixedCosts(full_cost, mine), self.task,
-                                           grids, cache=self._call_cache, raw=True)
+                                           grids, cache=self._call_cache, raw=True, acquisition=self._kind)
                 local = {s: ys[i] for i, s in enumerate(mine)}
         except Exception as exc:  # noqa: BLE001 -- re-raised below, after the exchanges
             failure = exc
@@ -203,8 +213,9 @@ class CBOAcquisitionPath:
         ``data_x / data_y`` of that set), ``compute_best_acquisition_values`` and ``select_next_intervention``.  Returns
         ``(xs, ys, (exploration set, index))`` -- what those three return -- and leaves ``last_intervention`` at the pick.
         At the reference's model sizes the three calls' host glue costs as much as the one launch that serves them
-        (``cbo_trial_step``); anything the one call does not cover (several ranks, a model rebuilt with other prior closures
-        or other hyper-parameters, the first trial) takes the three calls."""
+        (``cbo_trial_step``, ``cbo_trial_step_kind`` for a point-wise ``acquisition``); anything the one call does not cover
+        (several ranks, a model rebuilt with other prior closures or other hyper-parameters, the first trial) takes the
+        three calls."""
         import ctypes
         from . import _lib
         from .utils_functions.utils import winners_to_points
@@ -231,15 +242,25 @@ class CBOAcquisitionPath:
         pm, pv = model._prior(model.X)
         st["y_best"].fill(current_best if type(current_best) is float else
                           float(np.asarray(current_best, dtype=np.float64).reshape(-1)[0]))
-        fixed = st.get("trial_args")             # the pointers that do not change from trial to trial, made once
+        fixed = st.get("trial_args")             # what does not change from trial to trial, made once
         if fixed is None:
+            # (the entry was made by this path's compute_best_acquisition_values: st["kind"] is this path's kind)
             chosen = ctypes.c_int(-1)
-            fixed = st["trial_args"] = (_lib.load().cbo_trial_step, _lib.dptr(st["y_best"]), _lib.dptr(st["batch_cost"]),
+            lib = _lib.load()
+            kind = st["kind"]
+            fixed = st["trial_args"] = (kind, lib.cbo_trial_step if kind[0] == "EI" else lib.cbo_trial_step_kind,
+                                        _lib.dptr(st["y_best"]), _lib.dptr(st["batch_cost"]),
                                         _lib.dptr(st["vals"]), st["idxs"].ctypes.data_as(_lib.c_int64_p), chosen,
-                                        ctypes.byref(chosen))
-        call, y_best, batch_cost, vals, idxs, chosen, chosen_ref = fixed
-        rc = call(self.es_size, st["gps"], st["cds"], s, model.X.shape[0], _lib.dptr(model.X), _lib.dptr(model._y_flat),
-                  _lib.dptr(pm), _lib.dptr(pv), y_best, _lib.TASK_CODE[self.task], 0.0, batch_cost, vals, idxs, chosen_ref)
+                                        ctypes.byref(chosen), kind[0] == "EI")
+        kind, call, y_best, batch_cost, vals, idxs, chosen, chosen_ref, ei = fixed
+        if ei:
+            rc = call(self.es_size, st["gps"], st["cds"], s, model.X.shape[0], _lib.dptr(model.X), _lib.dptr(model._y_flat),
+                      _lib.dptr(pm), _lib.dptr(pv), y_best, _lib.TASK_CODE[self.task], 0.0, batch_cost, vals, idxs,
+                      chosen_ref)
+        else:
+            rc = call(self.es_size, st["gps"], st["cds"], s, model.X.shape[0], _lib.dptr(model.X), _lib.dptr(model._y_flat),
+                      _lib.dptr(pm), _lib.dptr(pv), _lib.ACQ_KIND_CODE[kind[0]], y_best, _lib.TASK_CODE[self.task], kind[1],
+                      batch_cost, vals, idxs, chosen_ref)
         if rc:
             _lib.check(rc)
         model.stale = model.small            # (a larger model was refitted by the general path inside the call)
@@ -247,8 +268,14 @@ class CBOAcquisitionPath:
             if not m.small:
                 m.stale = False
         xs, ys = winners_to_points(st, self.models, st["grids"], current_best, self.task)
-        self.last_intervention = chosen.value
-        return xs, ys, (self.exploration_set[chosen.value], chosen.value)
+        pick = chosen.value
+        if not ei and np.array([y[0, 0] for y in ys], dtype=np.float64).tobytes() != st["vals"].tobytes():
+            # the library picked among the winners at their batch costs; a variable cost has re-evaluated some at their own:
+            # the pick is ``select_next_intervention``'s over those, as the three calls make it.  (The EI's one-call form
+            # keeps the library's pick, as it always has.)
+            pick = self.select_next_intervention(ys)[1]
+        self.last_intervention = pick
+        return xs, ys, (self.exploration_set[pick], pick)
 
     def current_best_solution(self, current_best_y):
         """CBO.py:262-267 (the monitor's ``current_best_y`` dict is passed in)."""
@@ -280,12 +307,14 @@ class CBO(CBOAcquisitionPath):
     to the (1, 1) target -- by default ``compute_interventions`` on the graph's SEM (src/Monitor.py:55-63).
     ``exploration_set``: "MIS" / "POMIS" as in the reference, or the list of sets itself.  With ``causal_prior`` every
     set's ``get_gp_name`` must name a graph GP; the constructor raises KeyError naming the first that does not.
-    ``lockstep=False`` fits the graph GPs one after another (the reference's order; same models)."""
+    ``lockstep=False`` fits the graph GPs one after another (the reference's order; same models).
+    ``acquisition`` / ``acquisition_param``: what ``intervene()`` scores the exploration sets with, as for
+    ``CBOAcquisitionPath`` (default: the reference's causal EI)."""
 
     def __init__(self, graph, measurements, all_measurements, interventional_data, exploration_set="MIS",
                  num_interventions=10, initial_num_obs_samples=100, causal_prior=False, num_trials=40, task="min",
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
-                 lockstep=True, verbose=False):
+                 lockstep=True, verbose=False, acquisition="EI", acquisition_param=None):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType
         from .graphs import _columns
@@ -318,7 +347,8 @@ class CBO(CBOAcquisitionPath):
         if len(data_x) != len(exploration):
             raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
         super().__init__(gp_type, exploration, self.graph.get_cost_structure(type_cost), task, data_x, data_y,
-                         [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None)
+                         [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None,
+                         acquisition=acquisition, acquisition_param=acquisition_param)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions

@@ -2287,18 +2287,51 @@ static int ensure_small_buffers(cbo_ctx *c, int n_sets, int blocks)
 }
 
 // staged_set >= 0 (cbo_trial_step): that set's new data sit in the context's staging buffer, its model's host-side state
-// is already the new one, and the one-launch path -- which the caller has checked the set takes -- prepares and stores them
+// is already the new one, and the one-launch path -- which the caller has checked the set takes -- prepares and stores them.
+// kind: kEiKind = the causal EI (small_sets_kernel, cbo_gp_fit_sweep / cbo_acq_sweep), else one of CBO_ACQ_* (DESIGN.md §4l:
+// small_sets_kind_kernel, cbo_gp_fit + cbo_acq_sweep_kind), ei_jitter then being the kind's parameter -- the caller has run
+// check_kind_args.
+constexpr int kEiKind = 0;
 static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
-                           double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs, int staged_set);
+                           double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs, int staged_set,
+                           int kind);
 
 extern "C" int cbo_acq_sweep_sets(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
                                   double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs)
 {
-    return sweep_sets_impl(n_sets, gps, cands, y_best, task, ei_jitter, costs, best_vals, best_idxs, -1);
+    return sweep_sets_impl(n_sets, gps, cands, y_best, task, ei_jitter, costs, best_vals, best_idxs, -1, kEiKind);
+}
+
+// cbo_acq_sweep_kind's checks of its scalars for every set of a multi-set call, before anything is touched; what the kind
+// does not read is put to cbo_acq_sweep_kind's neutral values (the model variance reads neither task nor parameter)
+static int check_kind_args(int n_sets, int kind, const double *y_best, int *task, double *param, const double *costs)
+{
+    if (kind != CBO_ACQ_LCB && kind != CBO_ACQ_PI && kind != CBO_ACQ_VAR && kind != CBO_ACQ_MPEI)
+        return fail(CBO_ERR_INVALID, "kind must be CBO_ACQ_LCB, CBO_ACQ_PI, CBO_ACQ_VAR or CBO_ACQ_MPEI");
+    if (n_sets <= 0 || !y_best || !costs) return fail(CBO_ERR_INVALID, "bad argument");
+    if (kind == CBO_ACQ_VAR) { *task = CBO_TASK_MIN; *param = 0.0; }
+    if (*task != CBO_TASK_MIN && *task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
+    if (!std::isfinite(*param)) return fail(CBO_ERR_INVALID, "param (beta / jitter) must be finite");
+    if (kind == CBO_ACQ_LCB && *param < 0.0) return fail(CBO_ERR_INVALID, "beta must not be negative");
+    for (int i = 0; i < n_sets; ++i) {
+        if (kind == CBO_ACQ_PI && !std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite");
+        if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    }
+    return CBO_OK;
+}
+
+extern "C" int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int kind,
+                                       const double *y_best, int task, double param, const double *costs,
+                                       double *best_vals, int64_t *best_idxs)
+{
+    const int rc = check_kind_args(n_sets, kind, y_best, &task, &param, costs);
+    if (rc != CBO_OK) return rc;
+    return sweep_sets_impl(n_sets, gps, cands, y_best, task, param, costs, best_vals, best_idxs, -1, kind);
 }
 
 static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
-                           double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs, int staged_set)
+                           double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs, int staged_set,
+                           int kind)
 {
     if (n_sets <= 0 || !gps || !cands || !y_best || !costs || !best_vals || !best_idxs)
         return fail(CBO_ERR_INVALID, "bad argument");
@@ -2338,17 +2371,25 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
             st.cxs = k->P.xs; st.csq = k->P.sq; st.csv = causal ? k->P.sv : nullptr;
             st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
             st.cld = k->P.ld; st.m = k->m; st.index_offset = k->index_offset;
-            st.task = task; st.y_best = y_best[small[j]]; st.ei_jitter = ei_jitter;
+            // (only the EI and the probability of improvement read the caller's incumbent)
+            st.task = task; st.y_best = (kind == kEiKind || kind == CBO_ACQ_PI) ? y_best[small[j]] : 0.0;
+            st.ei_jitter = ei_jitter;
             st.cost = costs[small[j]];
         }
         const int ns = (int)small.size();
         auto launch = [&](int seq) -> int {
-            launch_small_sets(c->stream, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val, c->small_part_idx,
-                              c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq);
+            if (kind == kEiKind)
+                launch_small_sets(c->stream, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val, c->small_part_idx,
+                                  c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq);
+            else
+                launch_small_sets_kind(c->stream, kind, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val,
+                                       c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out,
+                                       seq);
             HIP_TRY(hipGetLastError());
             return CBO_OK;
         };
-        rc = polled_launch(c, "cbo_acq_sweep_sets", c->small_out.p, ns, "multi-set sweep: no result record", launch);
+        rc = polled_launch(c, kind == kEiKind ? "cbo_acq_sweep_sets" : "cbo_acq_sweep_sets_kind", c->small_out.p, ns,
+                           "multi-set sweep: no result record", launch);
         if (rc != CBO_OK) return rc;
         for (int j = 0; j < ns; ++j) {
             if (c->small_out[j].info != 0) continue;        // not positive definite as assembled: the jitchol ladder below
@@ -2360,7 +2401,12 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
     for (int i = 0; i < n_sets; ++i) {
         if (done[(size_t)i]) continue;
         int rc;
-        if (!gps[i]->fitted)
+        if (kind != kEiKind) {
+            rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
+            if (rc == CBO_OK)
+                rc = cbo_acq_sweep_kind(gps[i], cands[i], kind, y_best[i], task, ei_jitter, costs[i], nullptr, nullptr,
+                                        nullptr, &best_vals[i], &best_idxs[i]);
+        } else if (!gps[i]->fitted)
             rc = cbo_gp_fit_sweep(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
                                   &best_vals[i], &best_idxs[i], nullptr, nullptr);
         else
@@ -2479,10 +2525,38 @@ extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const
 // (src/CBO.py:237-260) and the set to intervene on next is picked (src/CBO.py:269-277) -- cbo_gp_upload_data +
 // cbo_acq_sweep_sets + cbo_argmax_sets without the three trips through the caller's language, which at the reference's
 // model sizes (one 29 us launch for all sets) cost as much as the device work.
+static int trial_step_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
+                           const double *X, const double *y, const double *pm, const double *pv, const double *y_best,
+                           int task, double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs,
+                           int *chosen_out, int kind);
+
 extern "C" int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
                               const double *X, const double *y, const double *pm, const double *pv, const double *y_best,
                               int task, double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs,
                               int *chosen_out)
+{
+    return trial_step_impl(n_sets, gps, cands, refit_set, n, X, y, pm, pv, y_best, task, ei_jitter, costs, best_vals,
+                           best_idxs, chosen_out, kEiKind);
+}
+
+// cbo_trial_step with a point-wise epilogue: everything the sweep would refuse is refused before the
+// model's host-side state moves to the new data
+extern "C" int cbo_trial_step_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
+                                   const double *X, const double *y, const double *pm, const double *pv, int kind,
+                                   const double *y_best, int task, double param, const double *costs, double *best_vals,
+                                   int64_t *best_idxs, int *chosen_out)
+{
+    const int rc = check_kind_args(n_sets, kind, y_best, &task, &param, costs);
+    if (rc != CBO_OK) return rc;
+    if (!gps || !cands || !best_vals || !best_idxs || !chosen_out) return fail(CBO_ERR_INVALID, "bad argument");
+    return trial_step_impl(n_sets, gps, cands, refit_set, n, X, y, pm, pv, y_best, task, param, costs, best_vals, best_idxs,
+                           chosen_out, kind);
+}
+
+static int trial_step_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
+                           const double *X, const double *y, const double *pm, const double *pv, const double *y_best,
+                           int task, double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs,
+                           int *chosen_out, int kind)
 {
     if (n_sets <= 0 || !gps || !chosen_out) return fail(CBO_ERR_INVALID, "bad argument");
     if (refit_set >= n_sets) return fail(CBO_ERR_INVALID, "refit_set out of range");
@@ -2523,7 +2597,7 @@ extern "C" int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *
             if (rc != CBO_OK) return rc;
         }
     }
-    int rc = sweep_sets_impl(n_sets, gps, cands, y_best, task, ei_jitter, costs, best_vals, best_idxs, staged);
+    int rc = sweep_sets_impl(n_sets, gps, cands, y_best, task, ei_jitter, costs, best_vals, best_idxs, staged, kind);
     if (rc != CBO_OK && staged >= 0) {
         // The launch that was to carry the new data into the resident arrays failed (or was never queued): the host-side
         // state already describes the new data, the device arrays may hold either.  Finish the upload from the staging

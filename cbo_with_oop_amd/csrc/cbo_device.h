@@ -335,4 +335,28 @@ __device__ __forceinline__ double feasibility_of(double mean, double var, double
     return ndtr_with_exp(u, e);
 }
 
+// One candidate's value over the cost.  p.ei_jitter carries the kind's parameter: beta (LCB), the jitter (PI).
+//   LCB: the compiler's IEEE square root (np.sqrt's bits), then the operations as numpy applies them, one rounding each
+//   PI:  feasibility_of (cbo_device.h) with the incumbent as the bound: the PoF pass's bits
+//   VAR: the predictive variance itself
+// then acquisition_of's quotient: the reciprocal of the cost (uniform, hoisted out of the loop) corrected by the remainder
+// -- the IEEE quotient for every cost whose significand is not all ones; only the sign of a zero can differ.
+template <int KIND>
+__device__ __forceinline__ double pointwise_of(double mean, double var, const AcqParams &p)
+{
+#pragma clang fp contract(off)
+    double v;
+    if (KIND == CBO_ACQ_LCB) {
+        const double bs = p.ei_jitter * __dsqrt_rn(var);
+        v = p.task == CBO_TASK_MIN ? -(mean - bs) : mean + bs;     // (uniform)
+    } else if (KIND == CBO_ACQ_PI) {
+        v = feasibility_of(mean, var, p.y_best, p.ei_jitter, p.task == CBO_TASK_MIN ? CBO_CON_LE : CBO_CON_GE);
+    } else {
+        v = var;
+    }
+    const double rc = 1.0 / p.cost;
+    const double qv = v * rc;
+    return fma(fma(-qv, p.cost, v), rc, qv);
+}
+
 }  // namespace cbo

@@ -324,6 +324,12 @@ void launch_loo_finish(hipStream_t s, const double *c, const double *alpha, cons
 // synchronising the stream); info and ticket (device, n_sets ints each) must be zero on entry and are zero again afterwards
 void launch_small_sets(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
                        double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq);
+// the same launch with a point-wise epilogue (kernels_sets_kind.hip, small_sets_kind_kernel): kind
+// CBO_ACQ_LCB / _PI / _VAR / _MPEI; the descriptors' ei_jitter carries the kind's parameter, y_best PI's incumbent (the
+// plug-in EI forms its own inside the launch)
+void launch_small_sets_kind(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set,
+                            double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket,
+                            cbo_small_result *out, int seq);
 
 // ---- hyper-parameter-marginalised EI (kernels_hyper.hip) ----------------------------------------------
 // One launch (schedule 1) or two (2; 0 = by the number of candidate blocks) for a model of at most 128 observations: st is

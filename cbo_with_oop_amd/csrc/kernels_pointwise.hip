@@ -19,28 +19,7 @@
 
 namespace cbo {
 
-// One candidate's value over the cost.  p.ei_jitter carries the kind's parameter: beta (LCB), the jitter (PI).
-//   LCB: the compiler's IEEE square root (np.sqrt's bits), then the operations as numpy applies them, one rounding each
-//   PI:  feasibility_of (cbo_device.h) with the incumbent as the bound: the PoF pass's bits
-//   VAR: the predictive variance itself
-// then acquisition_of's quotient: the reciprocal of the cost (uniform, hoisted out of the loop) corrected by the remainder
-// -- the IEEE quotient for every cost whose significand is not all ones; only the sign of a zero can differ.
-template <int KIND>
-__device__ __forceinline__ double pointwise_of(double mean, double var, const AcqParams &p)
-{
-    double v;
-    if (KIND == CBO_ACQ_LCB) {
-        const double bs = p.ei_jitter * __dsqrt_rn(var);
-        v = p.task == CBO_TASK_MIN ? -(mean - bs) : mean + bs;     // (uniform)
-    } else if (KIND == CBO_ACQ_PI) {
-        v = feasibility_of(mean, var, p.y_best, p.ei_jitter, p.task == CBO_TASK_MIN ? CBO_CON_LE : CBO_CON_GE);
-    } else {
-        v = var;
-    }
-    const double rc = 1.0 / p.cost;
-    const double qv = v * rc;
-    return fma(fma(-qv, p.cost, v), rc, qv);
-}
+// (pointwise_of, one candidate's value over the cost, lives in cbo_device.h: the one-launch multi-set sweep shares it.)
 
 // acq_kernel's structure (kernels_acq.hip; its comments say why): two consecutive candidates per lane and iteration (16-byte
 // loads and stores), addresses "scalar base + 32-bit lane offset", and every memory operation of an iteration issued in one

@@ -212,21 +212,55 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
 POINTWISE_ACQUISITIONS = ("LCB", "PI", "MPEI", "VAR")
 
 
-def _acquisition_for(name, model, current_global_best, task, space):
-    """The acquisition object ``find_next_y_point(acquisition=name)`` scores with (defaults: beta 1, jitter 0)."""
+def _acquisition_for(name, model, current_global_best, task, space, param=None):
+    """The acquisition object ``find_next_y_point(acquisition=name)`` scores with (defaults: beta 1, jitter 0; ``param``
+    replaces the default of a point-wise kind that has one)."""
     if name == "MES":
         from .max_value_entropy import MaxValueEntropySearch
         return MaxValueEntropySearch(model, space)
     if name in POINTWISE_ACQUISITIONS:
         from . import pointwise_acquisitions as pw
+        extra = () if param is None else (param,)
         if name == "LCB":
-            return pw.CausalNegativeLowerConfidenceBound(task, model)
+            return pw.CausalNegativeLowerConfidenceBound(task, model, *extra)
         if name == "PI":
-            return pw.CausalProbabilityOfImprovement(current_global_best, task, model)
+            return pw.CausalProbabilityOfImprovement(current_global_best, task, model, *extra)
         if name == "MPEI":
-            return pw.CausalMeanPluginExpectedImprovement(task, model)
+            return pw.CausalMeanPluginExpectedImprovement(task, model, *extra)
         return pw.ModelVariance(model)
     return CausalExpectedImprovement(current_global_best, task, model)
+
+
+def sets_acquisition(acquisition="EI", acquisition_param=None):
+    """(name, parameter) of the acquisition a multi-set sweep scores with, checked on the host before any device call:
+    ``"EI"`` (no parameter: today's call, ``None``), ``"LCB"`` (beta, default 1, finite and not negative), ``"PI"`` and
+    ``"MPEI"`` (the jitter, default 0, finite), ``"VAR"`` (no parameter: 0 travels).  Anything else raises ``ValueError``.
+    An answer of this function is accepted in the place of the name (and returned as it is)."""
+    import math
+    if type(acquisition) is tuple and acquisition_param is None and len(acquisition) == 2:
+        name, param = acquisition                 # an earlier answer of this function (a path keeps its own): checked again
+        sets_acquisition(name, None if name in ("EI", "VAR") else param)
+        return acquisition
+    if not isinstance(acquisition, str) or acquisition not in ("EI",) + POINTWISE_ACQUISITIONS:
+        raise ValueError(f"acquisition must be 'EI', 'LCB', 'PI', 'MPEI' or 'VAR' in a multi-set sweep, not {acquisition!r}")
+    if acquisition == "EI":
+        if acquisition_param is not None:
+            raise ValueError("acquisition_param: the multi-set EI takes none (its jitter is the reference's 0)")
+        return "EI", None
+    what = "acquisition_param (beta)" if acquisition == "LCB" else "acquisition_param (jitter)"
+    if acquisition_param is None:
+        return acquisition, (1.0 if acquisition == "LCB" else 0.0)
+    if acquisition == "VAR":
+        raise ValueError("acquisition_param: the model variance takes none")
+    try:
+        param = float(np.asarray(acquisition_param, dtype=np.float64).reshape(-1)[0])
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"{what} must be a finite number, not {acquisition_param!r}") from None
+    if not math.isfinite(param):
+        raise ValueError(f"{what} must be a finite number, not {acquisition_param!r}")
+    if acquisition == "LCB" and param < 0.0:
+        raise ValueError(f"{what} must not be negative, not {acquisition_param!r}")
+    return acquisition, param
 
 
 def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
@@ -244,7 +278,8 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
     return y, x_new
 
 
-def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False):
+def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
+                       acquisition="EI", acquisition_param=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -252,9 +287,17 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     change while models, grids and cost functions stay the same objects: the handle arrays and the batch costs.
     Returns (xs, ys): lists of (1,d) points and (1,1) acquisition values.  ``raw=True`` (the multi-GPU caller): the
     batch costs are given (``costs_functions.values``, those of the whole grid) and ys are (value, global index)
-    pairs for the arg-max exchange, xs is None."""
+    pairs for the arg-max exchange, xs is None.
+    ``acquisition="LCB" | "PI" | "MPEI" | "VAR"`` with ``acquisition_param`` (beta, default 1; the jitter of PI and MPEI,
+    default 0): the point-wise acquisitions of ``find_next_y_point`` in the same one call (``cbo_acq_sweep_sets_kind``,
+    DESIGN.md §4l) -- per set what ``find_next_y_point(acquisition=...)`` returns.  ``"EI"`` is today's call, untouched.  The
+    cache entry records the kind: a changed kind rebuilds nothing but the call.  Unknown names, a negative beta and a
+    non-finite parameter raise ``ValueError`` before any device call."""
     import ctypes
     from .. import _lib
+    kind = sets_acquisition(acquisition, acquisition_param)
+    if kind[0] != "EI" and task not in _lib.TASK_CODE:
+        raise ValueError(f"task must be 'min' or 'max', not {task!r}")
     s = len(models)
     # The cache entry holds the models, grids and cost table themselves (strong references, compared with ``is``)
     # next to their device handles: an ``id()`` alone comes back as soon as CPython reuses a freed address, and the
@@ -278,10 +321,19 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
         if cache is not None:
             cache["sweep_sets"] = st
     costs, batch_cost, vals, idxs = st["costs"], st["batch_cost"], st["vals"], st["idxs"]
+    if st.get("kind") != kind:
+        st.pop("trial_args", None)               # (CBOAcquisitionPath.trial_step's fixed arguments name the kind's call)
+        st["kind"] = kind
     st["y_best"][:] = float(np.asarray(current_global_best, dtype=np.float64).reshape(-1)[0])
-    _lib.check(_lib.load().cbo_acq_sweep_sets(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
-                                              _lib.dptr(batch_cost), _lib.dptr(vals),
-                                              idxs.ctypes.data_as(_lib.c_int64_p)))
+    if kind[0] == "EI":
+        _lib.check(_lib.load().cbo_acq_sweep_sets(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
+                                                  _lib.dptr(batch_cost), _lib.dptr(vals),
+                                                  idxs.ctypes.data_as(_lib.c_int64_p)))
+    else:
+        _lib.check(_lib.load().cbo_acq_sweep_sets_kind(s, st["gps"], st["cds"], _lib.ACQ_KIND_CODE[kind[0]],
+                                                       _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], kind[1],
+                                                       _lib.dptr(batch_cost), _lib.dptr(vals),
+                                                       idxs.ctypes.data_as(_lib.c_int64_p)))
     for i in range(s):
         if not models[i].small:                  # the general path fitted it on the way (deferred refit)
             models[i].stale = False
@@ -293,8 +345,9 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
 def winners_to_points(st, models, grids, current_global_best, task):
     """(xs, ys) of utils.py:36 from the winners a multi-set sweep left in ``st`` (the cache entry of
     ``find_next_y_points``): the grid point of every set and its acquisition value re-evaluated at that point alone --
-    only variable costs change the value."""
+    only variable costs change the value -- through the acquisition class of the kind the entry records."""
     costs, batch_cost, vals, idxs = st["costs"], st["batch_cost"], st["vals"], st["idxs"]
+    name, param = st.get("kind", ("EI", None))
     xs, ys = [], []
     winners, values, batch = idxs.tolist(), vals.tolist(), batch_cost.tolist()
     for i in range(len(models)):
@@ -304,8 +357,8 @@ def winners_to_points(st, models, grids, current_global_best, task):
         if point_cost == batch[i]:
             y = np.array(((values[i],),))
         else:
-            y = CausalExpectedImprovement(current_global_best, task, models[i]).sweep(x_new, cost=point_cost,
-                                                                                      want_acq=True)["acq"]
+            y = _acquisition_for(name, models[i], current_global_best, task, None, param).sweep(x_new, cost=point_cost,
+                                                                                                want_acq=True)["acq"]
         xs.append(x_new)
         ys.append(y)
     return xs, ys

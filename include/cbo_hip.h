@@ -355,8 +355,9 @@ int cbo_acq_sweep_hyper(cbo_gp *gp, cbo_cands *cands, int n_samples,
  * / var_out (m doubles each), best_val and best_idx may be NULL.  q, mu are reached exactly as cbo_acq_sweep reaches them
  * (the candidates' cached copies when the fit stamp matches, one appended row or block after cbo_gp_append /
  * cbo_gp_append_block, the fp32 strip of fp32 models, the chunked substitution otherwise), and the model and the set are
- * left as cbo_acq_sweep leaves them.  Out of scope: the single launch of small sets (cbo_acq_sweep_sets, cbo_trial_step),
- * refitting in the same call (cbo_gp_fit_sweep), the batch, hyper-marginalised and constrained calls, the multi-GPU exchange.
+ * left as cbo_acq_sweep leaves them.  Out of scope: refitting in the same call (cbo_gp_fit_sweep), the batch,
+ * hyper-marginalised and constrained calls, the multi-GPU exchange.  (The single launch of small sets has the kinds through
+ * cbo_acq_sweep_sets_kind and cbo_trial_step_kind, below.)
  * CBO_ERR_INVALID: cbo_acq_sweep's argument checks, a kind outside 1..4, a non-finite param, beta < 0, a non-finite y_best
  * for CBO_ACQ_PI, cost <= 0 or NaN, a bad task for every kind but CBO_ACQ_VAR.  Unfitted model: CBO_ERR_NOT_FITTED.
  *
@@ -577,6 +578,29 @@ int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int 
                    const double *X, const double *y, const double *prior_mean_X, const double *prior_var_X,
                    const double *y_best, int task, double ei_jitter, const double *costs, double *best_vals,
                    int64_t *best_idxs, int *chosen_out);
+
+/* cbo_acq_sweep_sets and cbo_trial_step for the point-wise acquisitions of cbo_acq_sweep_kind: kind is one
+ * of CBO_ACQ_LCB | _PI | _VAR | _MPEI, param its parameter (beta; PI's jitter; not read; EI's jitter), y_best[i] is read by
+ * CBO_ACQ_PI only (the array itself must be given).  Routing is cbo_acq_sweep_sets': fp64 models of at most 128 observations
+ * are factored AND swept by one launch inside LDS (small_sets_kind_kernel: the EI launch's sequence with the kind's
+ * epilogue; for CBO_ACQ_MPEI the workgroup first runs the model's own points through its factor for the plug-in incumbent)
+ * -- they need no fit, and their fitted state and caches are left alone; larger models, fp32 models and sets whose
+ * factorisation needs jitchol's jitter take the general path inside the same call: cbo_gp_fit if unfitted, then
+ * cbo_acq_sweep_kind.
+ * Contract: for every set, best_vals[i] and best_idxs[i] are bit for bit what cbo_acq_sweep_kind(gps[i], cands[i], kind,
+ * y_best[i], task, param, costs[i], ...) returns on a fitted twin of the model -- the same tie rule: lowest index wins, NaN
+ * is maximal, the set's index_offset is applied.  cbo_trial_step_kind is bit for bit cbo_gp_upload_data +
+ * cbo_acq_sweep_sets_kind + cbo_argmax_sets.
+ * CBO_ERR_INVALID, before any model is touched: cbo_acq_sweep_sets' (cbo_trial_step's) argument checks, a kind outside 1..4,
+ * a non-finite param, beta < 0, a non-finite y_best[i] for CBO_ACQ_PI, costs[i] <= 0 or NaN, a bad task for every kind but
+ * CBO_ACQ_VAR.  Out of scope: max-value entropy search, constrained, batch and hyper-marginalised epilogues in the one
+ * launch. */
+int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int kind, const double *y_best,
+                            int task, double param, const double *costs, double *best_vals, int64_t *best_idxs);
+int cbo_trial_step_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
+                        const double *X, const double *y, const double *prior_mean_X, const double *prior_var_X,
+                        int kind, const double *y_best, int task, double param, const double *costs, double *best_vals,
+                        int64_t *best_idxs, int *chosen_out);
 
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
