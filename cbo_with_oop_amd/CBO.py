@@ -20,21 +20,63 @@ class _FixedCosts:
         self.values = [by_set[s] for s in order]
 
 
+def checked_path_constraints(constraints, kind=("EI", None)):
+    """``CBOAcquisitionPath``'s ``constraints`` checked on the host: a list of ``(name, sense, value, jitter)`` (jitter 0
+    where it was left out), empty for ``None``."""
+    import math
+    from .utils_functions.constrained import MAX_CONSTRAINTS, SENSE_CODE
+    if not constraints:
+        return []
+    if kind[0] != "EI":
+        raise ValueError("constraints multiply the causal EI: acquisition must be 'EI'")
+    if len(constraints) > MAX_CONSTRAINTS:
+        raise ValueError(f"at most {MAX_CONSTRAINTS} constraints, not {len(constraints)}")
+    out = []
+    for entry in constraints:
+        if not isinstance(entry, (tuple, list)) or len(entry) not in (3, 4):
+            raise ValueError(f"a constraint is (name, sense, value[, jitter]), not {entry!r}")
+        name, sense, value = entry[:3]
+        jitter = entry[3] if len(entry) == 4 else 0.0
+        if sense not in SENSE_CODE:
+            raise ValueError(f"constraint {name!r}: sense must be '<=' or '>=', not {sense!r}")
+        try:
+            value, jitter = float(value), float(jitter)
+        except (TypeError, ValueError):
+            raise ValueError(f"constraint {name!r}: value and jitter must be finite numbers") from None
+        if not (math.isfinite(value) and math.isfinite(jitter)):
+            raise ValueError(f"constraint {name!r}: value and jitter must be finite numbers")
+        out.append((name, sense, value, jitter))
+    return out
+
+
 class CBOAcquisitionPath:
     """Holds exactly the state those methods read on the reference's ``CBO`` object: ``gp_type``,
     ``exploration_set``, ``costs``, ``task``, per-set data, spaces, prior closures and models.  ``acquisition`` (``"EI"``,
     the reference's, or ``"LCB" | "PI" | "MPEI" | "VAR"``) and ``acquisition_param`` (beta, default 1; the jitter of PI and
     MPEI, default 0) name what every exploration set is scored with (``find_next_y_points``); they are fixed
-    at construction."""
+    at construction.
+    ``constraints`` (a list of ``(name, sense, value[, jitter])``, at most 8, shared by all sets; ``sense`` ``"<="`` or
+    ``">="``) with ``constraint_data_y`` (``constraint_data_y[s][c]`` is (n_s, 1): the values of node ``c`` at ``data_x[s]``)
+    make every set's score ``EI * prod PoF / cost``: the path keeps ``constraint_models[s][c]`` --
+    non-causal models from the factory on ``data_x[s]`` -- rebuilds them with the objectives and passes them on.  They need
+    ``acquisition="EI"`` and a single process."""
 
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
-                 acquisition_param=None):
+                 acquisition_param=None, constraints=None, constraint_data_y=None):
         from .utils_functions.utils import sets_acquisition
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
         self._kind = sets_acquisition(acquisition, acquisition_param)
         self.acquisition, self.acquisition_param = acquisition, acquisition_param
+        self.constraints = checked_path_constraints(constraints, self._kind)
+        if self.constraints:
+            if constraint_data_y is None or len(constraint_data_y) != len(exploration_set) \
+                    or any(len(row) != len(self.constraints) for row in constraint_data_y):
+                raise ValueError("constraint_data_y must hold, for every exploration set, one column per constraint")
+        # (kept as given, like data_x / data_y: the caller appends to its lists between trials)
+        self.constraint_data_y = constraint_data_y if self.constraints else None
+        self.constraint_models = []
         self.gp_type = gp_type
         self.exploration_set = exploration_set
         self.es_size = len(exploration_set)
@@ -71,6 +113,23 @@ class CBOAcquisitionPath:
                              [self.mean_functions[s], self.var_functions[s]], emukit_wrapper=True)
             for s in range(self.es_size)
         ]
+        if self.constraints:
+            self.constraint_models = [[self._constraint_model(s, c) for c in range(len(self.constraints))]
+                                      for s in range(self.es_size)]
+
+    def _constraint_model(self, s, c, fit=True):
+        from .GaussianProcessFactory import GaussianProcessType
+        return GPFactory.create(GaussianProcessType.NON_CAUSAL_GP, self.data_x[s], self.constraint_data_y[s][c], [None, None],
+                                emukit_wrapper=True, fit=fit)
+
+    def set_constraints(self):
+        """Per set the ``ProbabilityOfFeasibility`` factors of this path's constraints over its constraint models (what
+        ``find_next_y_points`` takes), or ``None`` without constraints."""
+        if not self.constraints:
+            return None
+        from .utils_functions.constrained import ProbabilityOfFeasibility
+        return [[ProbabilityOfFeasibility(self.constraint_models[s][c], jitter, value, sense=sense)
+                 for c, (_, sense, value, jitter) in enumerate(self.constraints)] for s in range(self.es_size)]
 
     def update_gaussian_process_of_last_intervention(self, fit=False):
         """CBO.py:224-235.  By default the rebuilt model is left unfitted: ``compute_best_acquisition_values``
@@ -78,6 +137,8 @@ class CBOAcquisitionPath:
         ``fit=True`` restores the reference's timing (a not-PD error then surfaces here)."""
         s = self.last_intervention
         model = self.models[s]
+        for c in range(len(self.constraints)):              # (the set's constraint models take the same rows)
+            self.constraint_models[s][c].rebuild(self.data_x[s], self.constraint_data_y[s][c], fit=fit)
         if model is not None and model.mean_function is self.mean_functions[s] \
                 and model.variance_adjustment is self.var_functions[s]:
             model.rebuild(self.data_x[s], self.data_y[s], fit=fit)      # same handle: no allocation, no new grid
@@ -150,10 +211,12 @@ class CBOAcquisitionPath:
         ``cbo_acq_sweep_sets_kind`` for the path's point-wise ``acquisition``); across several GPUs, this rank's share of
         it and one arg-max exchange per set."""
         mode, world, rank = self.placement()
+        if self.constraints and mode != "single":
+            raise ValueError(f"constraints are scored by a single process: the placement is {mode!r}")
         if mode == "single":
             grids = [self.candidate_grid(s) for s in range(self.es_size)]
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
-                                      cache=self._call_cache, acquisition=self._kind)
+                                      cache=self._call_cache, acquisition=self._kind, constraints=self.set_constraints())
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -214,15 +277,16 @@ class CBOAcquisitionPath:
         ``(xs, ys, (exploration set, index))`` -- what those three return -- and leaves ``last_intervention`` at the pick.
         At the reference's model sizes the three calls' host glue costs as much as the one launch that serves them
         (``cbo_trial_step``, ``cbo_trial_step_kind`` for a point-wise ``acquisition``); anything the one call does not cover
-        (several ranks, a model rebuilt with other prior closures or other hyper-parameters, the first trial) takes the
-        three calls."""
+        (several ranks, a model rebuilt with other prior closures or other hyper-parameters, the first trial,
+        constraints) takes the three calls."""
         import ctypes
         from . import _lib
         from .utils_functions.utils import winners_to_points
         s = self.last_intervention
         st = self._call_cache.get("sweep_sets")
         model = self.models[s] if (s is not None and self.models) else None
-        fast = (st is not None and model is not None and (self.comm is None or self.comm.world == 1)
+        fast = (st is not None and model is not None and not self.constraints
+                and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
                 and model._hyper_initial and st["cost_table"] is self.costs
                 and st["models"] == self.models)             # (lists of the same objects: compared by identity first)
@@ -309,20 +373,38 @@ class CBO(CBOAcquisitionPath):
     set's ``get_gp_name`` must name a graph GP; the constructor raises KeyError naming the first that does not.
     ``lockstep=False`` fits the graph GPs one after another (the reference's order; same models).
     ``acquisition`` / ``acquisition_param``: what ``intervene()`` scores the exploration sets with, as for
-    ``CBOAcquisitionPath`` (default: the reference's causal EI)."""
+    ``CBOAcquisitionPath`` (default: the reference's causal EI).
+    ``constraints`` (``{"node": (sense, value[, jitter])}``): other nodes of the graph that must stay in range; every set is
+    scored with ``EI * prod PoF / cost``.  ``constraint_functions[s][node]`` maps (M, d) intervention values
+    of set s to the (M, 1) values of the node -- by default ``compute_interventions`` on the graph's SEM with
+    ``target_variable=node``.  A constrained node that is the target, or that some exploration set manipulates, raises
+    ``ValueError``.  The incumbent stays the plain best observation (``find_current_global``), as in emukit's recipe; the
+    monitor records ``constraint_values`` and ``feasible`` per trial."""
+
+    TARGET = "Y"
 
     def __init__(self, graph, measurements, all_measurements, interventional_data, exploration_set="MIS",
                  num_interventions=10, initial_num_obs_samples=100, causal_prior=False, num_trials=40, task="min",
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
-                 lockstep=True, verbose=False, acquisition="EI", acquisition_param=None):
+                 lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
+                 constraint_functions=None):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType
         from .graphs import _columns
+        from .utils_functions.utils import sets_acquisition
         self.graph = graph() if isinstance(graph, type) else graph
         self.measurements = _columns(measurements)
         self.all_measurements = _columns(all_measurements)
         exploration = ([list(s) for s in self.graph.get_exploration_set(exploration_set)]
                        if isinstance(exploration_set, str) else [list(s) for s in exploration_set])
+        constraints = dict(constraints or {})
+        for node in constraints:
+            if node == self.TARGET:
+                raise ValueError(f"constraint on {node!r}: the target itself cannot be constrained")
+            sets = [s for s in exploration if node in s]
+            if sets:
+                raise ValueError(f"constraint on {node!r}: exploration set {sets[0]} manipulates it")
+        path_constraints = [(node,) + tuple(spec) for node, spec in constraints.items()]
         self.num_interventions = num_interventions
         self.max_n = initial_num_obs_samples + 50
         self.initial_num_obs_samples = initial_num_obs_samples
@@ -346,13 +428,26 @@ class CBO(CBOAcquisitionPath):
         data_y = [np.asarray(y, dtype=np.float64).reshape(-1, 1) for _, y in interventional_data]
         if len(data_x) != len(exploration):
             raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
-        super().__init__(gp_type, exploration, self.graph.get_cost_structure(type_cost), task, data_x, data_y,
-                         [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None,
-                         acquisition=acquisition, acquisition_param=acquisition_param)
-        if target_functions is None:
+        path_constraints = checked_path_constraints(path_constraints, sets_acquisition(acquisition, acquisition_param))
+        sem = None
+        if path_constraints and constraint_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions
             sem = self.graph.define_sem()
+            constraint_functions = [{node: partial(compute_interventions, sem, {v: "" for v in s}, target_variable=node)
+                                     for node in constraints} for s in exploration]
+        self.constraint_functions = constraint_functions if path_constraints else None
+        # the initial constraint data: the functions at the rows of the initial data_x[s]
+        constraint_data_y = [[np.asarray(self.constraint_functions[s][node](data_x[s]), dtype=np.float64).reshape(-1, 1)
+                              for node, _, _, _ in path_constraints] for s in range(len(exploration))] if path_constraints else None
+        super().__init__(gp_type, exploration, self.graph.get_cost_structure(type_cost), task, data_x, data_y,
+                         [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None,
+                         acquisition=acquisition, acquisition_param=acquisition_param, constraints=path_constraints,
+                         constraint_data_y=constraint_data_y)
+        if target_functions is None:
+            from functools import partial
+            from .utils_functions.graph_functions import compute_interventions
+            sem = sem or self.graph.define_sem()
             target_functions = [partial(compute_interventions, sem, {v: "" for v in s}, target_variable="Y")
                                 for s in exploration]
         self.target_functions = list(target_functions)
@@ -400,6 +495,8 @@ class CBO(CBOAcquisitionPath):
         cost = self.compute_cost(intervention_set, intervention, xs)
         self.monitor.log_agent_performance(intervention_set, intervention, xs, cost)
         self.models[intervention].optimize()
+        for model in (self.constraint_models[intervention] if self.constraints else ()):
+            model.optimize()
 
     @property
     def epsilon(self):
@@ -451,6 +548,10 @@ class _Monitor:
         self.cumulative_cost = 0.
         self.type_trial = []
         self.chosen = []                 # per trial: (exploration set, values (1,d)) or None for an observe
+        # with constraints, per trial: {node: value at the chosen intervention} and whether all of them are in range
+        # (None for an observe)
+        self.constraint_values = []
+        self.feasible = []
         self.start_time = self.total_time = None
 
     def start(self):
@@ -472,6 +573,8 @@ class _Monitor:
             self.global_opt.append(self.global_opt[-1])
             self.current_cost.append(self.current_cost[-1])
             self.chosen.append(None)
+            self.constraint_values.append(None)
+            self.feasible.append(None)
             return
         cbo = self.cbo
         x_new = np.asarray(acquisition_xs[intervention], dtype=np.float64).reshape(1, -1)
@@ -479,6 +582,15 @@ class _Monitor:
         cbo.data_x[intervention] = np.vstack((cbo.data_x[intervention], x_new))
         cbo.data_y[intervention] = np.vstack((cbo.data_y[intervention], y_new))
         cbo.models[intervention].set_data(cbo.data_x[intervention], cbo.data_y[intervention])
+        values, feasible = {}, True
+        for c, (node, sense, bound, _) in enumerate(cbo.constraints):
+            v = float(np.asarray(cbo.constraint_functions[intervention][node](x_new), dtype=np.float64).reshape(-1)[0])
+            column = cbo.constraint_data_y[intervention][c] = np.vstack((cbo.constraint_data_y[intervention][c], [[v]]))
+            cbo.constraint_models[intervention][c].set_data(cbo.data_x[intervention], column)
+            values[node] = v
+            feasible = feasible and (v <= bound if sense == "<=" else v >= bound)
+        self.constraint_values.append(values if cbo.constraints else None)
+        self.feasible.append(feasible if cbo.constraints else None)
         name = cbo.intervention_names[intervention]
         self.current_best_x[name].append(float(x_new[0, 0]))
         self.current_best_y[name].append(float(y_new[0, 0]))

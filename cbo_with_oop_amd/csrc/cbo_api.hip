@@ -2417,6 +2417,140 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
     return CBO_OK;
 }
 
+// ---- constrained acquisition for every set of a trial (kernels_sets_con.hip) ------------------------------
+// cbo_acq_sweep_sets' routing applied to every model of a set: a set all of whose 1 + n_con[i] models are fp64 with at most
+// 128 observations is factored AND swept, model after model, by the workgroups of one launch; every other set -- and a set one
+// of whose models met a non-positive pivot there -- takes cbo_gp_fit on its unfitted models and cbo_acq_sweep_constrained.
+extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best,
+                                              int task, double ei_jitter, const double *costs, const int *n_con,
+                                              cbo_gp *const *con_gps, cbo_cands *const *con_cands, const double *con_value,
+                                              const double *con_jitter, const int *con_sense, double *best_vals,
+                                              int64_t *best_idxs)
+{
+    // what needs no handle first
+    if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
+    if (!y_best || !costs || !n_con || !best_vals || !best_idxs)
+        return fail(CBO_ERR_INVALID, "NULL argument: y_best, costs, n_con, best_vals and best_idxs must be given");
+    if (task != CBO_TASK_MIN && task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
+    int64_t total_con = 0;
+    for (int i = 0; i < n_sets; ++i) {
+        if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive (set " + std::to_string(i) + ")");
+        if (n_con[i] < 0 || n_con[i] > CBO_MAX_CONSTRAINTS)
+            return fail(CBO_ERR_INVALID, "n_con of set " + std::to_string(i) + " must be in 0.." +
+                                             std::to_string(CBO_MAX_CONSTRAINTS));
+        total_con += n_con[i];
+    }
+    if (total_con > 0) {
+        if (!con_value) return fail(CBO_ERR_INVALID, "con_value is NULL with constraints");
+        if (!con_jitter) return fail(CBO_ERR_INVALID, "con_jitter is NULL with constraints");
+        if (!con_sense) return fail(CBO_ERR_INVALID, "con_sense is NULL with constraints");
+        for (int64_t j = 0; j < total_con; ++j) {
+            if (!std::isfinite(con_value[j])) return fail(CBO_ERR_INVALID, "con_value must be finite");
+            if (!std::isfinite(con_jitter[j])) return fail(CBO_ERR_INVALID, "con_jitter must be finite");
+            if (con_sense[j] != CBO_CON_LE && con_sense[j] != CBO_CON_GE)
+                return fail(CBO_ERR_INVALID, "con_sense must be CBO_CON_LE or CBO_CON_GE");
+        }
+    }
+    // the handles
+    if (!gps || !cands) return fail(CBO_ERR_INVALID, "NULL argument: gps and cands must be given");
+    if (total_con > 0 && (!con_gps || !con_cands))
+        return fail(CBO_ERR_INVALID, "con_gps / con_cands is NULL with constraints");
+    std::vector<int64_t> first((size_t)n_sets + 1, 0);       // set i's constraints: [first[i], first[i + 1])
+    for (int i = 0; i < n_sets; ++i) first[(size_t)i + 1] = first[(size_t)i] + n_con[i];
+    for (int i = 0; i < n_sets; ++i) {
+        cbo_gp *sg[kConMaxModels];
+        cbo_cands *sk[kConMaxModels];
+        int nm = 0;
+        sg[nm] = gps[i]; sk[nm] = cands[i]; ++nm;
+        for (int64_t j = first[(size_t)i]; j < first[(size_t)i + 1]; ++j, ++nm) { sg[nm] = con_gps[j]; sk[nm] = con_cands[j]; }
+        for (int a = 0; a < nm; ++a) {
+            const int rc = check_sweep_args(sg[a], sk[a], task);
+            if (rc != CBO_OK) return rc;
+            if (sg[a]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all models must live on one context");
+            if (sg[a]->n <= 0 || sg[a]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
+            if (sk[a]->m != sk[0]->m) return fail(CBO_ERR_INVALID, "the candidate sets of a set differ in size");
+            for (int b = 0; b < a; ++b)
+                if (sk[b] == sk[a] && sg[b] != sg[a])
+                    return fail(CBO_ERR_INVALID, "one candidate set with two models: its scaled points are one model's");
+        }
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    auto small_model = [&](const cbo_gp *g) { return g->dtype == CBO_DTYPE_F64 && g->n_pad == kPadN && c->small_sets; };
+    std::vector<int> small;
+    int blocks = 1, n_pairs = 0, max_pairs = 1;
+    for (int i = 0; i < n_sets; ++i) {
+        bool ok = small_model(gps[i]);
+        for (int64_t j = first[(size_t)i]; ok && j < first[(size_t)i + 1]; ++j) ok = small_model(con_gps[j]);
+        if (!ok) continue;
+        small.push_back(i);
+        n_pairs += 1 + n_con[i];
+        if (1 + n_con[i] > max_pairs) max_pairs = 1 + n_con[i];
+        const int b = (int)((cands[i]->m + 63) / 64);
+        if (b > blocks) blocks = b;
+    }
+    std::vector<char> done((size_t)n_sets, 0);
+    if (!small.empty() && blocks <= 65535) {
+        const int ns = (int)small.size();
+        // descriptors for every pair; status words, tickets, records, scratch and partial winners per set
+        int rc = ensure_small_buffers(c, n_pairs, 1);
+        if (rc == CBO_OK) rc = ensure_small_buffers(c, ns, blocks);
+        if (rc != CBO_OK) return rc;
+        int p = 0;
+        std::vector<int> first_pair((size_t)ns, 0);
+        for (int j = 0; j < ns; ++j) {
+            const int i = small[(size_t)j];
+            first_pair[(size_t)j] = p;
+            for (int a = 0; a <= n_con[i]; ++a, ++p) {
+                const int64_t cj = first[(size_t)i] + a - 1;
+                cbo_gp *g = a == 0 ? gps[i] : con_gps[cj];
+                cbo_cands *k = a == 0 ? cands[i] : con_cands[cj];
+                rc = prepare_cands(g, k);
+                if (rc != CBO_OK) return rc;
+                const bool causal = g->X.sv != nullptr;
+                cbo_small_set &st = c->sets_host[p];
+                fill_small_model(st, g);
+                st.cxs = k->P.xs; st.csq = k->P.sq; st.csv = causal ? k->P.sv : nullptr;
+                st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
+                st.cld = k->P.ld; st.m = k->m; st.index_offset = cands[i]->index_offset;
+                if (a == 0) { st.task = task; st.y_best = y_best[i]; st.ei_jitter = ei_jitter; }
+                else { st.task = con_sense[cj]; st.y_best = con_value[cj]; st.ei_jitter = con_jitter[cj]; }
+                st.cost = costs[i];
+            }
+        }
+        for (int j = 0; j < ns; ++j) c->sets_host[j].pad_ = first_pair[(size_t)j];      // the table: set j's first pair
+        auto launch = [&](int seq) -> int {
+            launch_small_sets_con(c->stream, c->sets_host, n_pairs, ns, max_pairs, blocks, c->small_scratch, c->small_part_val,
+                                  c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq);
+            HIP_TRY(hipGetLastError());
+            return CBO_OK;
+        };
+        rc = polled_launch(c, "cbo_acq_sweep_sets_constrained", c->small_out.p, ns, "multi-set sweep: no result record", launch);
+        if (rc != CBO_OK) return rc;
+        for (int j = 0; j < ns; ++j) {
+            if (c->small_out[j].info != 0) continue;        // some model not positive definite as assembled: the ladder below
+            best_vals[small[(size_t)j]] = c->small_out[j].best_val;
+            best_idxs[small[(size_t)j]] = c->small_out[j].best_idx;
+            done[(size_t)small[(size_t)j]] = 1;
+        }
+    }
+    for (int i = 0; i < n_sets; ++i) {
+        if (done[(size_t)i]) continue;
+        const int64_t f = first[(size_t)i];
+        int rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
+        for (int64_t j = f; rc == CBO_OK && j < first[(size_t)i + 1]; ++j)
+            if (!con_gps[j]->fitted) rc = cbo_gp_fit(con_gps[j], nullptr, nullptr);
+        if (rc == CBO_OK)
+            rc = cbo_acq_sweep_constrained(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], n_con[i],
+                                           n_con[i] ? con_gps + f : nullptr, n_con[i] ? con_cands + f : nullptr,
+                                           n_con[i] ? con_value + f : nullptr, n_con[i] ? con_jitter + f : nullptr,
+                                           n_con[i] ? con_sense + f : nullptr, nullptr, nullptr, nullptr, &best_vals[i],
+                                           &best_idxs[i]);
+        if (rc != CBO_OK) return rc;
+    }
+    return CBO_OK;
+}
+
 // ---- the causal EI marginalised over hyper-parameter samples (kernels_hyper.hip) -------------------------
 // The general path of cbo_acq_sweep_hyper: per sample the model's own set_hyper + fit + sweep, the acquisition kept on the
 // device and added into the running sum; then the division with the arg-max; then the model back as it was.

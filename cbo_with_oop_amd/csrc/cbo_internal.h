@@ -270,6 +270,8 @@ struct cbo_small_set {
     int n, d, zero_diag, task;
     double variance, lengthscale, noise_var, diag_add, y_best, ei_jitter, cost;
     int ard, pad_;                                     // inputs pre-scaled per dimension (lengthscale gradient per dimension)
+                                                       // pad_: 0, but in small_sets_con_kernel's list of pairs, where descriptor
+                                                       // s carries the index of set s's first pair
     // cbo_trial_step: the model's NEW data have not been uploaded -- they sit in pinned (device-mapped) memory as
     // [X (n,d) | y (n) | prior mean (n) | prior variance (n)] and every workgroup of the set prepares the points from there
     // itself (the arithmetic of prep_points_staged_kernel); the set's first workgroup also fills the resident copies
@@ -330,6 +332,14 @@ void launch_small_sets(hipStream_t s, const cbo_small_set *sets, int n_sets, int
 void launch_small_sets_kind(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set,
                             double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket,
                             cbo_small_result *out, int seq);
+// the same launch with the constrained epilogue (kernels_sets_con.hip, small_sets_con_kernel): `pairs` holds
+// one descriptor per (model, candidate set) pair, a set's pairs consecutive with the objective first; a constraint's value,
+// jitter and sense ride in y_best, ei_jitter and task; pairs[s].pad_ = index of set s's first pair.  max_pairs = the most
+// pairs of one set (<= 1 + CBO_MAX_CONSTRAINTS).  scratch, part_val, part_idx: n_sets * blocks_per_set slots; info, ticket,
+// out: one per SET, as above
+void launch_small_sets_con(hipStream_t s, const cbo_small_set *pairs, int n_pairs, int n_sets, int max_pairs,
+                           int blocks_per_set, double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket,
+                           cbo_small_result *out, int seq);
 
 // ---- hyper-parameter-marginalised EI (kernels_hyper.hip) ----------------------------------------------
 // One launch (schedule 1) or two (2; 0 = by the number of candidate blocks) for a model of at most 128 observations: st is

@@ -279,7 +279,7 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
 
 
 def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
-                       acquisition="EI", acquisition_param=None):
+                       acquisition="EI", acquisition_param=None, constraints=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -292,10 +292,18 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     default 0): the point-wise acquisitions of ``find_next_y_point`` in the same one call (``cbo_acq_sweep_sets_kind``,
     DESIGN.md §4l) -- per set what ``find_next_y_point(acquisition=...)`` returns.  ``"EI"`` is today's call, untouched.  The
     cache entry records the kind: a changed kind rebuilds nothing but the call.  Unknown names, a negative beta and a
-    non-finite parameter raise ``ValueError`` before any device call."""
+    non-finite parameter raise ``ValueError`` before any device call.
+    ``constraints`` (one entry per set, each a possibly empty list of ``ProbabilityOfFeasibility``): every set is scored with
+    ``EI * prod PoF / cost`` in the same one call (``cbo_acq_sweep_sets_constrained``) -- per set what
+    ``find_next_y_point(constraints=[...])`` returns.  Each constraint model gets a ``CandidateGrid`` over the set's own grid
+    points with the set's ``index_offset``, built once and kept in the cache entry while the model object stays the same.
+    Non-empty constraints with another ``acquisition`` than ``"EI"`` or with ``raw=True``, a wrong length, more than 8
+    constraints in a set and a non-finite ``max_value`` or ``jitter`` raise ``ValueError`` before any device call.  ``None``,
+    or every list empty, takes exactly today's calls."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition(acquisition, acquisition_param)
+    constraints = checked_set_constraints(constraints, len(models), kind, raw)
     if kind[0] != "EI" and task not in _lib.TASK_CODE:
         raise ValueError(f"task must be 'min' or 'max', not {task!r}")
     s = len(models)
@@ -325,7 +333,12 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
         st.pop("trial_args", None)               # (CBOAcquisitionPath.trial_step's fixed arguments name the kind's call)
         st["kind"] = kind
     st["y_best"][:] = float(np.asarray(current_global_best, dtype=np.float64).reshape(-1)[0])
-    if kind[0] == "EI":
+    if st.get("constraints") is not None or constraints is not None:
+        st.pop("trial_args", None)               # (the one-call trial step names the unconstrained call)
+    st["constraints"] = constraints
+    if constraints is not None:
+        _sweep_sets_constrained(st, models, grids, constraints, task)
+    elif kind[0] == "EI":
         _lib.check(_lib.load().cbo_acq_sweep_sets(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
                                                   _lib.dptr(batch_cost), _lib.dptr(vals),
                                                   idxs.ctypes.data_as(_lib.c_int64_p)))
@@ -337,9 +350,89 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     for i in range(s):
         if not models[i].small:                  # the general path fitted it on the way (deferred refit)
             models[i].stale = False
+    if constraints is not None:
+        for i in range(s):                       # (a set with a larger model anywhere took the general path: all fitted)
+            mine = [models[i]] + [c.model for c in constraints[i]]
+            if any(not m.small for m in mine):
+                for m in mine:
+                    m.stale = False
     if raw:
         return None, [(float(vals[i]), int(idxs[i])) for i in range(s)]
     return winners_to_points(st, models, grids, current_global_best, task)
+
+
+def checked_set_constraints(constraints, n_sets, kind=("EI", None), raw=False):
+    """``find_next_y_points``' ``constraints`` checked on the host, before any device call: ``None`` when there is nothing
+    to constrain (``None`` given, or every set's list empty), else a list of ``n_sets`` lists of ``ProbabilityOfFeasibility``."""
+    import math
+    if constraints is None:
+        return None
+    from .constrained import MAX_CONSTRAINTS, ProbabilityOfFeasibility
+    constraints = [list(c) if c is not None else [] for c in constraints]
+    if len(constraints) != n_sets:
+        raise ValueError(f"constraints must have one entry per exploration set ({n_sets}), not {len(constraints)}")
+    if not any(constraints):
+        return None
+    if kind[0] != "EI":
+        raise ValueError("constraints multiply the causal EI: acquisition must be 'EI'")
+    if raw:
+        raise ValueError("constraints are not defined across several ranks (raw=True)")
+    for i, cons in enumerate(constraints):
+        if len(cons) > MAX_CONSTRAINTS:
+            raise ValueError(f"set {i}: at most {MAX_CONSTRAINTS} constraints, not {len(cons)}")
+        for c in cons:
+            if not isinstance(c, ProbabilityOfFeasibility):
+                raise ValueError(f"set {i}: a constraint must be a ProbabilityOfFeasibility, not {type(c).__name__}")
+            for what, v in (("max_value", c.max_value), ("jitter", c.jitter)):
+                try:
+                    ok = math.isfinite(float(v))
+                except (TypeError, ValueError):
+                    ok = False
+                if not ok:
+                    raise ValueError(f"set {i}: a constraint's {what} must be a finite number, not {v!r}")
+    return constraints
+
+
+def _sweep_sets_constrained(st, models, grids, constraints, task):
+    """The constrained form of ``find_next_y_points``' device call: the constraint models' candidate grids from the cache
+    entry ``st`` (rebuilt where a model object changed), then ``cbo_acq_sweep_sets_constrained`` into ``st``'s winners."""
+    import ctypes
+    from .. import _lib
+    from .causal_acquisition_functions import CandidateGrid
+    from .constrained import SENSE_CODE
+    kept = st.setdefault("con_grids", {})            # (set, position) -> (model, CandidateGrid or None when it is grids[i])
+    wanted = {(i, k): c.model for i, cons in enumerate(constraints) for k, c in enumerate(cons)}
+    for key in [k for k, (m, _) in kept.items() if wanted.get(k) is not m]:
+        grid = kept.pop(key)[1]
+        if grid is not None:
+            grid.close()
+    con_gps, con_cds, values, jitters, senses = [], [], [], [], []
+    for i, cons in enumerate(constraints):
+        by_model = {id(models[i]): grids[i]}         # one candidate set serves one model (and that model everywhere in the set)
+        for k, c in enumerate(cons):
+            if (i, k) not in kept:
+                grid = by_model.get(id(c.model))
+                own = grid is None
+                if own:
+                    grid = CandidateGrid(grids[i].points, c.model, index_offset=grids[i].index_offset)
+                kept[(i, k)] = (c.model, grid if own else None)
+                by_model[id(c.model)] = grid
+            else:
+                grid = kept[(i, k)][1]
+                if grid is None:
+                    grid = by_model[id(c.model)]
+                by_model.setdefault(id(c.model), grid)
+            if not (c.model._handle.value and grid._handle.value):
+                raise ValueError("find_next_y_points: a constraint's model or candidate grid has been closed")
+            con_gps.append(c.model._handle); con_cds.append(grid._handle)
+            values.append(float(c.max_value)); jitters.append(float(c.jitter)); senses.append(SENSE_CODE[c.sense])
+    n = len(con_gps)
+    n_con = (ctypes.c_int * len(models))(*[len(cons) for cons in constraints])
+    _lib.check(_lib.load().cbo_acq_sweep_sets_constrained(
+        len(models), st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0, _lib.dptr(st["batch_cost"]),
+        n_con, (ctypes.c_void_p * n)(*con_gps), (ctypes.c_void_p * n)(*con_cds), _lib.dptr(np.array(values)),
+        _lib.dptr(np.array(jitters)), (ctypes.c_int * n)(*senses), _lib.dptr(st["vals"]),
+        st["idxs"].ctypes.data_as(_lib.c_int64_p)))
 
 
 def winners_to_points(st, models, grids, current_global_best, task):
@@ -348,6 +441,7 @@ def winners_to_points(st, models, grids, current_global_best, task):
     only variable costs change the value -- through the acquisition class of the kind the entry records."""
     costs, batch_cost, vals, idxs = st["costs"], st["batch_cost"], st["vals"], st["idxs"]
     name, param = st.get("kind", ("EI", None))
+    constraints = st.get("constraints")
     xs, ys = [], []
     winners, values, batch = idxs.tolist(), vals.tolist(), batch_cost.tolist()
     for i in range(len(models)):
@@ -356,6 +450,10 @@ def winners_to_points(st, models, grids, current_global_best, task):
         point_cost = float(costs[i].evaluate(x_new))
         if point_cost == batch[i]:
             y = np.array(((values[i],),))
+        elif constraints is not None and constraints[i]:
+            from .constrained import AcquisitionProduct
+            ei = CausalExpectedImprovement(current_global_best, task, models[i])
+            y = (AcquisitionProduct([ei] + list(constraints[i])) / costs[i]).evaluate(x_new)
         else:
             y = _acquisition_for(name, models[i], current_global_best, task, None, param).sweep(x_new, cost=point_cost,
                                                                                                 want_acq=True)["acq"]

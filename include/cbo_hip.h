@@ -285,8 +285,8 @@ int cbo_acq_sweep_mes(cbo_gp *gp, cbo_cands *cands, int n_samples, const double 
  * one appended row after cbo_gp_append, the fp32 strip of fp32 models, the chunked substitution otherwise), one pair after
  * the other; the vectors stay in the candidates' own buffers, also with CBO_HIP_SWEEP_CACHE=0 (same bits either way).
  * Every set has the same m, candidate i of every set is the same intervention; a set may serve several pairs only with
- * the same model.  Out of scope: refitting in the same call (cbo_gp_fit_sweep) and the single launch of small sets
- * (cbo_acq_sweep_sets).  The models are only read.
+ * the same model.  Out of scope: refitting in the same call (cbo_gp_fit_sweep).  The single launch of small sets is
+ * cbo_acq_sweep_sets_constrained, below.  The models are only read.
  * CBO_ERR_INVALID: n_con outside 0..CBO_MAX_CONSTRAINTS (or 0 without an objective), only one of gp / cands NULL, a NULL
  * among the first n_con entries or a NULL array with n_con > 0, pairs on different contexts, sets whose m differ,
  * gp->d != cands->d in a pair, a causal model whose set carries no prior, one set with two models, a non-finite con_value
@@ -593,14 +593,41 @@ int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int 
  * cbo_acq_sweep_sets_kind + cbo_argmax_sets.
  * CBO_ERR_INVALID, before any model is touched: cbo_acq_sweep_sets' (cbo_trial_step's) argument checks, a kind outside 1..4,
  * a non-finite param, beta < 0, a non-finite y_best[i] for CBO_ACQ_PI, costs[i] <= 0 or NaN, a bad task for every kind but
- * CBO_ACQ_VAR.  Out of scope: max-value entropy search, constrained, batch and hyper-marginalised epilogues in the one
- * launch. */
+ * CBO_ACQ_VAR.  Out of scope: max-value entropy search, batch and hyper-marginalised epilogues in the one launch (the
+ * constrained one is cbo_acq_sweep_sets_constrained, below). */
 int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int kind, const double *y_best,
                             int task, double param, const double *costs, double *best_vals, int64_t *best_idxs);
 int cbo_trial_step_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
                         const double *X, const double *y, const double *prior_mean_X, const double *prior_var_X,
                         int kind, const double *y_best, int task, double param, const double *costs, double *best_vals,
                         int64_t *best_idxs, int *chosen_out);
+
+/* cbo_acq_sweep_sets for the constrained acquisition of cbo_acq_sweep_constrained: set i is an objective pair
+ * (gps[i], cands[i]) and n_con[i] constraint pairs, whose five con_* entries lie set-major in arrays of sum(n_con) entries
+ * (set 0's constraints, then set 1's, ...); the arrays may be NULL when every n_con[i] is 0.  Sets of one call may have
+ * different n_con.
+ * Routing, per set: when every one of its 1 + n_con[i] models is fp64 with at most 128 observations (and CBO_HIP_SMALL_SETS is
+ * on, and the call's widest such set has at most 65535 blocks of 64 candidates), the set is factored AND swept by one launch
+ * inside LDS (small_sets_con_kernel): a workgroup serves 64 candidates and walks the set's models in order, the running
+ * product in a register.  Those models need no fit (cbo_gp_upload_data suffices), and nothing of them or of their candidate
+ * sets is touched: not the factor, not the fitted flag, not the cached q / mu, not the kept solutions.  Every other set -- a
+ * larger or fp32 model anywhere in it, or a non-positive pivot in any of its models (jitchol's ladder) -- takes the general
+ * path inside the same call: cbo_gp_fit on each unfitted model, the objective first, then the constraints in order, then
+ * cbo_acq_sweep_constrained.
+ * Contract: for every set, best_vals[i] and best_idxs[i] are bit for bit what cbo_acq_sweep_constrained(gps[i], cands[i],
+ * y_best[i], task, ei_jitter, costs[i], n_con[i], <set i's slices>, NULL, NULL, NULL, &v, &idx) returns on freshly fitted
+ * twins of the models: the same tie rule (lowest index, NaN maximal, the objective set's index_offset), n_con[i] = 0 closing
+ * with cbo_acq_sweep's quotient, n_con[i] >= 1 multiplying left to right and closing with one IEEE division.
+ * CBO_ERR_INVALID, before any model is touched (what needs no handle is checked first): n_sets <= 0; a NULL y_best, costs,
+ * n_con, best_vals or best_idxs; a bad task; costs[i] <= 0 or NaN; an n_con[i] outside 0..CBO_MAX_CONSTRAINTS; a NULL con_*
+ * array while some n_con[i] > 0; a non-finite con_value or con_jitter; a sense other than CBO_CON_LE / CBO_CON_GE; then a
+ * NULL handle array or handle; models of different contexts; a model without data; within a set, candidate sets whose m
+ * differ, gp->d != cands->d in a pair, a causal model whose candidate set carries no prior, one candidate set used with two
+ * different models.  An objective is required (cbo_acq_sweep_constrained's form without one is not offered here). */
+int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
+                                   double ei_jitter, const double *costs, const int *n_con, cbo_gp *const *con_gps,
+                                   cbo_cands *const *con_cands, const double *con_value, const double *con_jitter,
+                                   const int *con_sense, double *best_vals, int64_t *best_idxs);
 
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
