@@ -2189,7 +2189,7 @@ extern "C" int cbo_gp_fit_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task
 // CBO.compute_best_acquisition_values (/root/reference/src/CBO.py:237-260) loops find_next_y_point over the S
 // exploration sets.  Sets whose model has at most 128 observations -- every model the reference itself builds
 // (10 + <= 40 points, src/ArgumentParser.py:18,25) -- are swept by ONE launch that factors and sweeps inside LDS
-// (kernels_chol.hip, small_sets_kernel): no per-set launch chain, no per-set synchronisation, one copy back.  Such a
+// (kernels_sets.hip, small_sets_kernel): no per-set launch chain, no per-set synchronisation, one copy back.  Such a
 // model need not be fitted: the launch works from its resident data (cbo_gp_upload_data is enough) and leaves its
 // fitted state alone.  A set whose factorisation meets a non-positive pivot there (jitchol's business), a larger
 // model, or an fp32 model takes the general path: cbo_gp_fit_sweep when the model is not fitted, cbo_acq_sweep
@@ -2271,6 +2271,31 @@ static void fill_small_model(cbo_small_set &st, const cbo_gp *g)
     st.stage = nullptr; st.stage_ls = nullptr; st.raw = g->raw; st.pv = g->X.pv;
 }
 
+// the candidate half: set k as prepare_cands has scaled it for model g, the prior closures for a causal model
+static void fill_small_cands(cbo_small_set &st, const cbo_gp *g, const cbo_cands *k)
+{
+    const bool causal = g->X.sv != nullptr;
+    st.cxs = k->P.xs; st.csq = k->P.sq; st.csv = causal ? k->P.sv : nullptr;
+    st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
+    st.cld = k->P.ld; st.m = k->m; st.index_offset = k->index_offset;
+}
+
+// a model the one-workgroup sweeps take: fp64, at most 128 observations (CBO_HIP_SMALL_SETS=0: none)
+static bool small_sweep_model(const cbo_gp *g) { return g->dtype == CBO_DTYPE_F64 && g->n_pad == kPadN && g->ctx->small_sets; }
+
+// the records of a one-launch sweep of the sets small[0..ns) into the caller's arrays; a set whose record reports a model
+// that is not positive definite as assembled is left for the general path (its jitchol ladder)
+static void harvest_small_sets(cbo_ctx *c, const std::vector<int> &small, double *best_vals, int64_t *best_idxs,
+                               std::vector<char> &done)
+{
+    for (size_t j = 0; j < small.size(); ++j) {
+        if (c->small_out[j].info != 0) continue;
+        best_vals[small[j]] = c->small_out[j].best_val;
+        best_idxs[small[j]] = c->small_out[j].best_idx;
+        done[(size_t)small[j]] = 1;
+    }
+}
+
 // descriptors, result records, status words and tickets for n_sets sets (at least 32), scratch and partial winners for
 // `blocks` workgroups per set
 static int ensure_small_buffers(cbo_ctx *c, int n_sets, int blocks)
@@ -2289,9 +2314,8 @@ static int ensure_small_buffers(cbo_ctx *c, int n_sets, int blocks)
 // staged_set >= 0 (cbo_trial_step): that set's new data sit in the context's staging buffer, its model's host-side state
 // is already the new one, and the one-launch path -- which the caller has checked the set takes -- prepares and stores them.
 // kind: kEiKind = the causal EI (small_sets_kernel, cbo_gp_fit_sweep / cbo_acq_sweep), else one of CBO_ACQ_* (DESIGN.md §4l:
-// small_sets_kind_kernel, cbo_gp_fit + cbo_acq_sweep_kind), ei_jitter then being the kind's parameter -- the caller has run
+// small_sets_kernel<kind>, cbo_gp_fit + cbo_acq_sweep_kind), ei_jitter then being the kind's parameter -- the caller has run
 // check_kind_args.
-constexpr int kEiKind = 0;
 static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
                            double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs, int staged_set,
                            int kind);
@@ -2346,7 +2370,7 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
     std::vector<int> small;
     int blocks = 1;
     for (int i = 0; i < n_sets; ++i) {
-        if (gps[i]->dtype == CBO_DTYPE_F64 && gps[i]->n_pad == kPadN && c->small_sets) {
+        if (small_sweep_model(gps[i])) {
             small.push_back(i);
             const int b = (int)((cands[i]->m + 63) / 64);
             if (b > blocks) blocks = b;
@@ -2361,16 +2385,13 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
             cbo_cands *k = cands[small[j]];
             rc = prepare_cands(g, k);
             if (rc != CBO_OK) return rc;
-            const bool causal = g->X.sv != nullptr;
             cbo_small_set &st = c->sets_host[j];
             fill_small_model(st, g);
             if (small[j] == staged_set) {
                 st.stage = c->stage;
                 st.stage_ls = g->h.ard ? g->ls_dev : nullptr;
             }
-            st.cxs = k->P.xs; st.csq = k->P.sq; st.csv = causal ? k->P.sv : nullptr;
-            st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
-            st.cld = k->P.ld; st.m = k->m; st.index_offset = k->index_offset;
+            fill_small_cands(st, g, k);
             // (only the EI and the probability of improvement read the caller's incumbent)
             st.task = task; st.y_best = (kind == kEiKind || kind == CBO_ACQ_PI) ? y_best[small[j]] : 0.0;
             st.ei_jitter = ei_jitter;
@@ -2378,25 +2399,15 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
         }
         const int ns = (int)small.size();
         auto launch = [&](int seq) -> int {
-            if (kind == kEiKind)
-                launch_small_sets(c->stream, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val, c->small_part_idx,
-                                  c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq);
-            else
-                launch_small_sets_kind(c->stream, kind, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val,
-                                       c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out,
-                                       seq);
+            launch_small_sets(c->stream, kind, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val,
+                              c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq);
             HIP_TRY(hipGetLastError());
             return CBO_OK;
         };
         rc = polled_launch(c, kind == kEiKind ? "cbo_acq_sweep_sets" : "cbo_acq_sweep_sets_kind", c->small_out.p, ns,
                            "multi-set sweep: no result record", launch);
         if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            if (c->small_out[j].info != 0) continue;        // not positive definite as assembled: the jitchol ladder below
-            best_vals[small[(size_t)j]] = c->small_out[j].best_val;
-            best_idxs[small[(size_t)j]] = c->small_out[j].best_idx;
-            done[(size_t)small[(size_t)j]] = 1;
-        }
+        harvest_small_sets(c, small, best_vals, best_idxs, done);
     }
     for (int i = 0; i < n_sets; ++i) {
         if (done[(size_t)i]) continue;
@@ -2476,12 +2487,11 @@ extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cb
     }
     cbo_ctx *c = gps[0]->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    auto small_model = [&](const cbo_gp *g) { return g->dtype == CBO_DTYPE_F64 && g->n_pad == kPadN && c->small_sets; };
     std::vector<int> small;
     int blocks = 1, n_pairs = 0, max_pairs = 1;
     for (int i = 0; i < n_sets; ++i) {
-        bool ok = small_model(gps[i]);
-        for (int64_t j = first[(size_t)i]; ok && j < first[(size_t)i + 1]; ++j) ok = small_model(con_gps[j]);
+        bool ok = small_sweep_model(gps[i]);
+        for (int64_t j = first[(size_t)i]; ok && j < first[(size_t)i + 1]; ++j) ok = small_sweep_model(con_gps[j]);
         if (!ok) continue;
         small.push_back(i);
         n_pairs += 1 + n_con[i];
@@ -2507,12 +2517,10 @@ extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cb
                 cbo_cands *k = a == 0 ? cands[i] : con_cands[cj];
                 rc = prepare_cands(g, k);
                 if (rc != CBO_OK) return rc;
-                const bool causal = g->X.sv != nullptr;
                 cbo_small_set &st = c->sets_host[p];
                 fill_small_model(st, g);
-                st.cxs = k->P.xs; st.csq = k->P.sq; st.csv = causal ? k->P.sv : nullptr;
-                st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
-                st.cld = k->P.ld; st.m = k->m; st.index_offset = cands[i]->index_offset;
+                fill_small_cands(st, g, k);
+                st.index_offset = cands[i]->index_offset;       // (the set's: the objective's candidates name the winner)
                 if (a == 0) { st.task = task; st.y_best = y_best[i]; st.ei_jitter = ei_jitter; }
                 else { st.task = con_sense[cj]; st.y_best = con_value[cj]; st.ei_jitter = con_jitter[cj]; }
                 st.cost = costs[i];
@@ -2527,12 +2535,7 @@ extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cb
         };
         rc = polled_launch(c, "cbo_acq_sweep_sets_constrained", c->small_out.p, ns, "multi-set sweep: no result record", launch);
         if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            if (c->small_out[j].info != 0) continue;        // some model not positive definite as assembled: the ladder below
-            best_vals[small[(size_t)j]] = c->small_out[j].best_val;
-            best_idxs[small[(size_t)j]] = c->small_out[j].best_idx;
-            done[(size_t)small[(size_t)j]] = 1;
-        }
+        harvest_small_sets(c, small, best_vals, best_idxs, done);
     }
     for (int i = 0; i < n_sets; ++i) {
         if (done[(size_t)i]) continue;
@@ -2618,7 +2621,7 @@ extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const
     cbo_ctx *c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const int64_t blocks64 = (k->m + 63) / 64;
-    if (g->dtype == CBO_DTYPE_F64 && g->n_pad == kPadN && c->small_sets && blocks64 <= 65535) {
+    if (small_sweep_model(g) && blocks64 <= 65535) {
         const int blocks = (int)blocks64;
         rc = ensure_small_buffers(c, 1, blocks > n_samples ? blocks : n_samples);
         if (rc == CBO_OK) rc = grow(c, c->hyper_host, (size_t)CBO_MAX_HYPER_SAMPLES * (CBO_MAX_DIM + 2));

@@ -261,7 +261,7 @@ void launch_gemm_update(hipStream_t s, const double *U, int64_t ldu, const doubl
                         int64_t ldc, int k0, int klen, int i0_begin, int i0_end, int64_t m_pad, bool upper_only,
                         const int *skip_if = nullptr);
 
-// One (model, candidate set) pair of a multi-set sweep of small models (kernels_chol.hip, small_sets_kernel): every
+// One (model, candidate set) pair of a multi-set sweep of small models (kernels_sets.hip, small_sets_kernel): every
 // pointer is device memory; filled on the host per call and uploaded as an array.
 struct cbo_small_set {
     const double *xs, *sq, *sv, *pm, *y;               // model: SoA points (ld), |x|^2, sqrt(v) or null, m(X) or null, targets
@@ -321,17 +321,22 @@ void launch_loo_identity_chunk(hipStream_t s, double *V, int64_t ldv, int64_t ro
 int loo_finish_blocks(int64_t n);
 void launch_loo_finish(hipStream_t s, const double *c, const double *alpha, const double *y, int64_t n, double *mean_out,
                        double *var_out, double *lpd_out, double *partial, double *sum_out);
+// The one-workgroup sweeps (small_sets_kernel, small_sets_con_kernel, hyper_avg_kernel) take two launches from this many
+// candidate blocks per model on.  Few blocks (the reference's 100-200 candidates): every workgroup factors its model
+// itself, ONE launch, no dependency between workgroups.  Many blocks (16k-candidate grids on 25 coral sets: 6400
+// workgroups): factoring the model 256 times over costs more than a second launch -- one workgroup per model factors,
+// then the sweep workgroups start from the factor.  profiles/hyper_avg_timing.json has both schedules of hyper_avg_kernel
+// at the three shapes of DESIGN.md §4j.
+constexpr int kSmallTwoPhaseFromBlocks = 12;
 // sets / out may be pinned host memory (device-mapped): the kernel then reads the descriptors and writes the results
 // across the host link itself and the call needs no copy operation (the host may poll out[].seq instead of
-// synchronising the stream); info and ticket (device, n_sets ints each) must be zero on entry and are zero again afterwards
-void launch_small_sets(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
+// synchronising the stream); info and ticket (device, n_sets ints each) must be zero on entry and are zero again afterwards.
+// kind (kernels_sets.hip, small_sets_kernel<KIND>): kEiKind = the causal EI, or the point-wise epilogue
+// CBO_ACQ_LCB / _PI / _VAR / _MPEI; the descriptors' ei_jitter then carries the kind's parameter, y_best PI's incumbent
+// (the plug-in EI forms its own inside the launch)
+constexpr int kEiKind = 0;
+void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
                        double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq);
-// the same launch with a point-wise epilogue (kernels_sets_kind.hip, small_sets_kind_kernel): kind
-// CBO_ACQ_LCB / _PI / _VAR / _MPEI; the descriptors' ei_jitter carries the kind's parameter, y_best PI's incumbent (the
-// plug-in EI forms its own inside the launch)
-void launch_small_sets_kind(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set,
-                            double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket,
-                            cbo_small_result *out, int seq);
 // the same launch with the constrained epilogue (kernels_sets_con.hip, small_sets_con_kernel): `pairs` holds
 // one descriptor per (model, candidate set) pair, a set's pairs consecutive with the objective first; a constraint's value,
 // jitter and sense ride in y_best, ei_jitter and task; pairs[s].pad_ = index of set s's first pair.  max_pairs = the most

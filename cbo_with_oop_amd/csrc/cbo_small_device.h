@@ -1,9 +1,15 @@
 // Device functions of the one-workgroup kernels, shared by the translation units that factor a block inside LDS
-// (kernels_chol.hip: the blocked factorisation's diagonal block, small_sets_kernel, small_lml_kernel; kernels_loo.hip:
-// small_loo_batch_kernel; kernels_hyper.hip: hyper_avg_kernel): the register Cholesky of a 16x16 tile, the decoupled-wave factorisation of a 128-row block,
-// the tile solve of a 128-row block for one wave's 16 columns, and the model side of a small model (points, K(X,X) +
-// diag, factor, inverses and z).  One definition, so every kernel that factors a small model produces the same bits.
+// (kernels_chol.hip: the blocked factorisation's diagonal block, small_lml_kernel; kernels_sets.hip: small_sets_kernel;
+// kernels_sets_con.hip: small_sets_con_kernel; kernels_loo.hip: small_loo_batch_kernel; kernels_hyper.hip:
+// hyper_avg_kernel): the register Cholesky of a 16x16 tile, the decoupled-wave factorisation of a 128-row block, the tile
+// solve of a 128-row block for one wave's 16 columns, the model side of a small model (points, K(X,X) + diag, factor,
+// inverses and z), and the stages of a one-workgroup sweep (a wave's candidates, K*, the solve with q and mu, the
+// workgroup's arg-max, the set's reduction).  One definition, so every kernel that factors or sweeps a small model
+// produces the same bits.  A function whose own arithmetic the compiler could contract says contract(off) itself, as
+// cbo_device.h's do; the translation units that build kernels from the sweep stages say it again for their own text.
 #pragma once
+
+#include <atomic>
 
 #include "cbo_device.h"
 
@@ -446,6 +452,19 @@ struct SmallShared {
 };
 static_assert(sizeof(SmallShared) <= 163840, "one workgroup per CU");
 
+// Opts a kernel whose dynamic LDS is SmallShared in to the whole CU's LDS, once per device: `opted` is the caller's static
+// mask of the devices done, one per kernel instantiation (several devices in one process each need it; a failed attempt
+// is repeated by the next call; the launch itself reports what is wrong if it never succeeds) -- the call costs a
+// microsecond of the forty a reference-scale trial takes.
+inline void small_lds_opt_in(const void *kernel, std::atomic<unsigned long long> &opted)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || !((opted.load(std::memory_order_relaxed) >> (dev & 63)) & 1ull)) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallShared)) == hipSuccess)
+            opted.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
+    }
+}
+
 constexpr int kSmallLd = kDiagLd;                              // scratch factor rows: [128][144], z in column 128
 constexpr int kSmallScratch = 128 * kSmallLd + 8 * 256;        // doubles per workgroup: factor rows + inverses
 
@@ -649,6 +668,96 @@ __device__ __forceinline__ void small_kstar_tiles(const SmallShared &sh, const c
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[t][r] = 0.0;
         }
+    }
+}
+
+// ---- the stages of a one-workgroup sweep, in the order a kernel runs them ---------------------------------------------
+// phases == 1 of a two-launch form: factor the model into the slot `fs`, nothing else
+__device__ __forceinline__ void small_factor_only(SmallShared &sh, const cbo_small_set &st, double *fs, int *info_word)
+{
+    double ivx[8][4], zrx[8][4];
+    small_model_factor(sh, st, (st.n + 15) / 16, fs, fs + 128 * kSmallLd, info_word, ivx, zrx, 1, true);
+}
+
+// Candidate c of the set as this lane's column: scaled coordinates, |x|^2, sqrt(v) and the prior closures (zeros for a
+// non-causal set).  Clamped: lanes beyond the set compute, nobody looks.  Fetched before the factorisation, used after it
+// (their latency is off the chain).
+__device__ __forceinline__ void small_fetch_cand(const cbo_small_set &st, int64_t c, double (&xc)[CBO_MAX_DIM], double &csq,
+                                                 double &csv, double &cpm_c, double &cpv_c)
+{
+    const int64_t cc = (c < st.m) ? c : st.m - 1;
+#pragma unroll
+    for (int k = 0; k < CBO_MAX_DIM; ++k) xc[k] = (k < st.d) ? st.cxs[(int64_t)k * st.cld + cc] : 0.0;
+    csq = st.csq[cc];
+    csv = st.csv ? st.csv[cc] : 0.0;
+    cpm_c = st.cpm ? st.cpm[cc] : 0.0;
+    cpv_c = st.cpv ? st.cpv[cc] : 0.0;
+}
+
+// K(X, X*) of one wave's 16 candidates, straight into the MFMA result layout: small_kstar_tiles<d> (d uniform)
+__device__ __forceinline__ void small_kstar_tiles_of(const SmallShared &sh, const cbo_small_set &st, int tiles,
+                                                     const double *xc, double csq, double csv, double inv_l2, int kq,
+                                                     d4 (&acc)[8])
+{
+    switch (st.d) {
+        case 1: small_kstar_tiles<1>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+        case 2: small_kstar_tiles<2>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+        case 3: small_kstar_tiles<3>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+        case 4: small_kstar_tiles<4>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+        case 5: small_kstar_tiles<5>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+        case 6: small_kstar_tiles<6>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+        case 7: small_kstar_tiles<7>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+        default: small_kstar_tiles<8>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
+    }
+}
+
+// V = L^-1 K* of one wave's 16 candidates, q = sum V^2, mu = V^T z: lane partials, then over the four lane groups (the strip
+// kernel's order).  The factor must be in LDS: the caller has waited (s_waitcnt vmcnt(0)) and synchronised.
+__device__ __forceinline__ void solve_q_mu(const SmallShared &sh, d4 (&acc)[8], const double (&iv)[8][4],
+                                           const double (&zr)[8][4], int tiles, int kq, int lc, double &qacc, double &macc)
+{
+#pragma clang fp contract(off)
+    qacc = 0.0;
+    macc = 0.0;
+    panel_solve_tiles(&sh.blk.S[kq][lc], acc, iv, tiles, [&](int s, const d4 &x) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            qacc = fma(x[r], x[r], qacc);
+            macc = fma(x[r], zr[s][r], macc);
+        }
+    });
+    qacc += __shfl_xor(qacc, 16);
+    qacc += __shfl_xor(qacc, 32);
+    macc += __shfl_xor(macc, 16);
+    macc += __shfl_xor(macc, 32);
+}
+
+// posterior_of's and the epilogues' scalars from a descriptor (the predictive variance includes the noise)
+__device__ __forceinline__ AcqParams small_acq_params(const cbo_small_set &st)
+{
+    AcqParams p;
+    p.variance = st.variance; p.noise_var = st.noise_var; p.y_best = st.y_best; p.ei_jitter = st.ei_jitter;
+    p.cost = st.cost; p.task = st.task; p.include_noise = 1; p.want_ei = 1;
+    return p;
+}
+
+// The workgroup's arg-max of the lanes' (bv, bi): the waves' shuffle trees, then thread 0 over the four waves -- whose
+// (bv, bi) are the workgroup's winner on return, which is where small_set_finish begins.  The waves' winners pass
+// through sh.sq / sh.sv.  Precondition: sh.sq and sh.sv are dead -- no wave reads the model's |x|^2 and sqrt(v) again
+// once it is here (their last readers are K* and the plug-in incumbent, before the solve); the first barrier below is
+// what keeps a fast wave from writing while a slow one is still at those reads.
+// (lane, wave: the caller's -- a second readfirstlane here cost the constrained kernel 3 % more instructions.)
+__device__ __forceinline__ void small_block_argmax(SmallShared &sh, int lane, int wave, double &bv, int64_t &bi)
+{
+    wave_argmax(bv, bi);
+    double *red_v = &sh.sq[0];
+    int64_t *red_i = reinterpret_cast<int64_t *>(&sh.sv[0]);
+    __syncthreads();
+    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (better(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
     }
 }
 

@@ -18,9 +18,8 @@
 //   3. syrk_kernel<64> / trsm_update_kernel   the bulk of  A[below, below] -= P^T P  on a second stream (fp64 MFMA),
 //                                 rhs -= P^T z  along with it
 // The bulk update carries the n^3/3 flops; steps 1-2 are the serial chain.
-// Also here: backsolve / forward-solve steps for single vectors, and the one-workgroup kernels for models of at most 128
-// observations (small_sets_kernel: factor + sweep of every exploration set of a trial; small_lml_kernel: likelihood and
-// gradients of one MLE iterate).
+// Also here: backsolve / forward-solve steps for single vectors, and the one-workgroup likelihood kernels for small models
+// (small_lml_kernel: likelihood and gradients of one MLE iterate).  The one-workgroup sweeps are in kernels_sets.hip.
 #include <hip/hip_ext.h>
 #include <climits>
 #include <atomic>
@@ -283,105 +282,6 @@ void launch_panel_trsm(hipStream_t s, double *A, int64_t lda, int r0, int col0, 
     if (n_cols <= 0) { if (done) hipEventRecord(done, s); return; }
     hipExtLaunchKernelGGL(panel_trsm_kernel, dim3((unsigned)(n_cols / kStrip)), dim3(256), sizeof(PanelShared), s, nullptr,
                           done, 0, A, lda, r0, col0, invDt, skip_if);
-}
-
-template <bool BYVAL>
-__global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
-                                                         double *scratch, int blocks_per_set,
-                                                         double *__restrict__ part_val, int64_t *__restrict__ part_idx,
-                                                         int *__restrict__ info, int *__restrict__ ticket,
-                                                         cbo_small_result *__restrict__ out, int seq, int phases)
-{
-    __shared__ int last_flag;
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    SmallShared &sh = *reinterpret_cast<SmallShared *>(smem_raw);
-    const int set = blockIdx.y, blk = blockIdx.x;
-    const cbo_small_set st = BYVAL ? byval.s[set] : sets[set];
-    const int slot = set * blocks_per_set + blk;
-    if (phases == 1) {                                            // one workgroup per set: factor it, nothing else
-        double ivx[8][4], zrx[8][4];
-        double *fs = scratch + (int64_t)(set * blocks_per_set) * kSmallScratch;
-        small_model_factor(sh, st, (st.n + 15) / 16, fs, fs + 128 * kSmallLd, &info[set], ivx, zrx, 1, true);
-        return;
-    }
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lc = lane & 15, kq = lane >> 4;
-    if ((int64_t)blk * 64 >= st.m) {                              // no candidates left for this workgroup
-        small_set_finish(-INFINITY, INT64_MAX, set, slot, blocks_per_set, part_val, part_idx, info, ticket, out, seq,
-                         &last_flag);
-        return;
-    }
-    const int tiles = (st.n + 15) / 16;
-    // phases 3: every workgroup factors the model itself, into its own scratch slot; phases 2: the set's slot 0 holds it
-    double *my = scratch + (int64_t)(phases == 2 ? set * blocks_per_set : slot) * kSmallScratch;
-    double *Us = my, *invs = my + 128 * kSmallLd;
-
-    // this wave's 16 candidates: fetched now, used after the factorisation (their latency is off the chain)
-    const int64_t c = (int64_t)blk * 64 + wave * 16 + lc;
-    const int64_t cc = (c < st.m) ? c : st.m - 1;                  // clamped: lanes beyond the set compute, nobody looks
-    double xc[CBO_MAX_DIM];
-#pragma unroll
-    for (int k = 0; k < CBO_MAX_DIM; ++k) xc[k] = (k < st.d) ? st.cxs[(int64_t)k * st.cld + cc] : 0.0;
-    const double csq = st.csq[cc], csv = st.csv ? st.csv[cc] : 0.0;
-    const double cpm_c = st.cpm ? st.cpm[cc] : 0.0, cpv_c = st.cpv ? st.cpv[cc] : 0.0;
-
-    double iv[8][4], zr[8][4];
-    small_model_factor(sh, st, tiles, Us, invs, &info[set], iv, zr, phases, true);
-    // ---- K(X, X*) of this wave's 16 candidates, straight into the result layout
-    const double inv_l2 = 1.0 / (st.lengthscale * st.lengthscale);
-    d4 acc[8];
-    switch (st.d) {
-        case 1: small_kstar_tiles<1>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 2: small_kstar_tiles<2>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 3: small_kstar_tiles<3>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 4: small_kstar_tiles<4>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 5: small_kstar_tiles<5>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 6: small_kstar_tiles<6>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 7: small_kstar_tiles<7>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        default: small_kstar_tiles<8>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // ---- V = L^-1 K*, q = sum V^2, mu = V^T z (lane partials, then over the four lane groups: the strip kernel's order)
-    double qacc = 0.0, macc = 0.0;
-    panel_solve_tiles(&sh.blk.S[kq][lc], acc, iv, tiles, [&](int s, const d4 &x) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            qacc = fma(x[r], x[r], qacc);
-            macc = fma(x[r], zr[s][r], macc);
-        }
-    });
-    qacc += __shfl_xor(qacc, 16);
-    qacc += __shfl_xor(qacc, 32);
-    macc += __shfl_xor(macc, 16);
-    macc += __shfl_xor(macc, 32);
-
-    // ---- epilogue and the workgroup's arg-max
-    AcqParams p;
-    p.variance = st.variance; p.noise_var = st.noise_var; p.y_best = st.y_best; p.ei_jitter = st.ei_jitter;
-    p.cost = st.cost; p.task = st.task; p.include_noise = 1; p.want_ei = 1;
-    double bv = -INFINITY;
-    int64_t bi = INT64_MAX;
-    if (kq == 0 && c < st.m) {
-        double mean, var;
-        posterior_of(qacc, macc, cpm_c, cpv_c, st.sv != nullptr, p, mean, var);
-        bv = acquisition_of(mean, var, p);
-        bi = c + st.index_offset;
-    }
-    wave_argmax(bv, bi);
-    double *red_v = &sh.sq[0];                         // free by now
-    int64_t *red_i = reinterpret_cast<int64_t *>(&sh.sv[0]);
-    __syncthreads();
-    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
-    }
-    small_set_finish(bv, bi, set, slot, blocks_per_set, part_val, part_idx, info, ticket, out, seq, &last_flag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -833,14 +733,9 @@ void launch_small_lml_batch(hipStream_t s, const cbo_small_set *sets, int n_mode
 {
     {
         static std::atomic<unsigned long long> opted[2];
-        int dev = 0;
         const bool byval = n_models <= kSmallByValue;
-        if (hipGetDevice(&dev) != hipSuccess || !((opted[byval].load(std::memory_order_relaxed) >> (dev & 63)) & 1ull)) {
-            const void *fn = byval ? reinterpret_cast<const void *>(small_lml_batch_kernel<true>)
-                                   : reinterpret_cast<const void *>(small_lml_batch_kernel<false>);
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallShared)) == hipSuccess)
-                opted[byval].fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-        }
+        small_lds_opt_in(byval ? reinterpret_cast<const void *>(small_lml_batch_kernel<true>)
+                               : reinterpret_cast<const void *>(small_lml_batch_kernel<false>), opted[byval]);
     }
     SmallSetArgs args{};
     if (n_models <= kSmallByValue) {
@@ -873,50 +768,6 @@ void launch_small_lml(hipStream_t s, const cbo_small_set &st, double *scratch, i
         default: CBO_LAUNCH_LML(8); break;
     }
 #undef CBO_LAUNCH_LML
-}
-
-size_t small_sets_scratch_doubles(int n_sets, int blocks_per_set) { return (size_t)n_sets * blocks_per_set * kSmallScratch; }
-
-void launch_small_sets(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
-                       double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq)
-{
-    // once per device and instantiation (several devices in one process each need it; a failed attempt is repeated by
-    // the next call; the launch itself reports what is wrong if it never succeeds) -- the call costs a microsecond of
-    // the forty a reference-scale trial takes
-    {
-        static std::atomic<unsigned long long> opted[2];
-        int dev = 0;
-        const bool byval = n_sets <= kSmallByValue;
-        if (hipGetDevice(&dev) != hipSuccess || !((opted[byval].load(std::memory_order_relaxed) >> (dev & 63)) & 1ull)) {
-            const void *fn = byval ? reinterpret_cast<const void *>(small_sets_kernel<true>)
-                                   : reinterpret_cast<const void *>(small_sets_kernel<false>);
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallShared)) == hipSuccess)
-                opted[byval].fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-        }
-    }
-    SmallSetArgs args{};
-    const dim3 grid((unsigned)blocks_per_set, (unsigned)n_sets);
-    // Few candidate blocks per set (the reference's 100-200 candidates): every workgroup factors its set's model itself,
-    // ONE launch, no dependency between workgroups.  Many blocks per set (16k-candidate grids on 25 coral sets: 6400
-    // workgroups): factoring the model 256 times over costs more than a second launch -- one workgroup per set factors,
-    // then the sweep workgroups start from the factor.
-    constexpr int kTwoPhaseFromBlocks = 12;
-    const bool two_phase = blocks_per_set >= kTwoPhaseFromBlocks;
-    auto launch = [&](const dim3 &g, int phases) {
-        if (n_sets <= kSmallByValue)
-            hipLaunchKernelGGL(small_sets_kernel<true>, g, dim3(256), sizeof(SmallShared), s, args, sets, scratch,
-                               blocks_per_set, part_val, part_idx, info, ticket, out, seq, phases);
-        else
-            hipLaunchKernelGGL(small_sets_kernel<false>, g, dim3(256), sizeof(SmallShared), s, args, sets, scratch,
-                               blocks_per_set, part_val, part_idx, info, ticket, out, seq, phases);
-    };
-    if (n_sets <= kSmallByValue) std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_sets);
-    if (two_phase) {
-        launch(dim3(1u, (unsigned)n_sets), 1);
-        launch(grid, 2);
-    } else {
-        launch(grid, 3);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -12,9 +12,9 @@
 //   phases 1: workgroup h factors sample h into scratch slot h and returns;  phases 2: the sweep reads factor h back.
 // The accumulate / finish kernels at the end serve the general path (larger, fp32 or jitter-needing models), whose
 // per-sample terms come from cbo_acq_sweep itself.
-#include <atomic>
-
 #include "cbo_small_device.h"
+
+#pragma clang fp contract(off)
 
 namespace cbo {
 
@@ -22,7 +22,6 @@ namespace cbo {
 __device__ __forceinline__ void hyper_point(const double *__restrict__ raw, int64_t i, int d, const double *ls, bool in,
                                             double (&x)[CBO_MAX_DIM], double &sum)
 {
-#pragma clang fp contract(off)
 #pragma unroll
     for (int k = 0; k < CBO_MAX_DIM; ++k) x[k] = 0.0;
     if (in) {
@@ -183,39 +182,16 @@ __global__ __launch_bounds__(256) void hyper_avg_kernel(const HyperArgs a, doubl
                 iv[s][kk] = (s < tiles) ? invs[s * 256 + (4 * kk + kq) * 16 + lc] : 0.0;
                 zr[s][kk] = (s < tiles) ? Us[(int64_t)(16 * s + kq + 4 * kk) * kSmallLd + 128] : 0.0;
             }
-        // ---- K(X, X*) of this wave's 16 candidates, straight into the result layout
         const double inv_l2 = 1.0 / (sth.lengthscale * sth.lengthscale);
         d4 acc[8];
-        switch (st.d) {
-            case 1: small_kstar_tiles<1>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-            case 2: small_kstar_tiles<2>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-            case 3: small_kstar_tiles<3>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-            case 4: small_kstar_tiles<4>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-            case 5: small_kstar_tiles<5>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-            case 6: small_kstar_tiles<6>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-            case 7: small_kstar_tiles<7>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-            default: small_kstar_tiles<8>(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        }
+        small_kstar_tiles_of(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
 
-        // ---- V = L^-1 K*, q = sum V^2, mu = V^T z (lane partials, then over the four lane groups: the strip kernel's order)
-        double qacc = 0.0, macc = 0.0;
-        panel_solve_tiles(&sh.blk.S[kq][lc], acc, iv, tiles, [&](int s, const d4 &x) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                qacc = fma(x[r], x[r], qacc);
-                macc = fma(x[r], zr[s][r], macc);
-            }
-        });
-        qacc += __shfl_xor(qacc, 16);
-        qacc += __shfl_xor(qacc, 32);
-        macc += __shfl_xor(macc, 16);
-        macc += __shfl_xor(macc, 32);
+        double qacc, macc;
+        solve_q_mu(sh, acc, iv, zr, tiles, kq, lc, qacc, macc);
 
-        AcqParams p;
-        p.variance = sth.variance; p.noise_var = sth.noise_var; p.y_best = st.y_best; p.ei_jitter = st.ei_jitter;
-        p.cost = st.cost; p.task = st.task; p.include_noise = 1; p.want_ei = 1;
+        const AcqParams p = small_acq_params(sth);                // (the sample's variance and noise, the model's EI scalars)
         if (kq == 0 && c < st.m) {
             double mean, var;
             posterior_of(qacc, macc, cpm_c, cpv_c, causal, p, mean, var);
@@ -231,16 +207,7 @@ __global__ __launch_bounds__(256) void hyper_avg_kernel(const HyperArgs a, doubl
         bi = c + st.index_offset;
         if (a.acq_out) a.acq_out[c] = bv;
     }
-    wave_argmax(bv, bi);
-    double *red_v = &sh.sq[0];                         // free by now
-    int64_t *red_i = reinterpret_cast<int64_t *>(&sh.sv[0]);
-    __syncthreads();
-    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
-    }
+    small_block_argmax(sh, lane, wave, bv, bi);
     small_set_finish(bv, bi, 0, blk, blocks, part_val, part_idx, info, ticket, out, seq, &last_flag);
 }
 
@@ -249,27 +216,17 @@ size_t hyper_avg_scratch_doubles(int blocks, int n_samples)
     return (size_t)(blocks > n_samples ? blocks : n_samples) * kSmallScratch;
 }
 
-// From this many candidate blocks on, the samples are factored once by a first launch of n_samples workgroups and the sweep
-// reads the factors back (phases 1 + 2); below, every workgroup factors every sample itself (phases 3).  The threshold is
-// small_sets_kernel's own; profiles/hyper_avg_timing.json has both schedules at the three shapes of DESIGN.md §4j.
-constexpr int kHyperTwoPhaseFromBlocks = 12;
-
+// schedule 0: from kSmallTwoPhaseFromBlocks candidate blocks on, the samples are factored once by a first launch of n_samples
+// workgroups and the sweep reads the factors back (phases 1 + 2); below, every workgroup factors every sample itself (phases 3)
 void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
                       int n_ls, double *acq_out, int blocks, int schedule, double *scratch, double *part_val,
                       int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq)
 {
-    {
-        static std::atomic<unsigned long long> opted;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || !((opted.load(std::memory_order_relaxed) >> (dev & 63)) & 1ull)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(hyper_avg_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallShared)) == hipSuccess)
-                opted.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-        }
-    }
+    static std::atomic<unsigned long long> opted{0};
+    small_lds_opt_in(reinterpret_cast<const void *>(hyper_avg_kernel), opted);
     HyperArgs a{};
     a.st = st; a.craw = craw; a.hyper = hyper; a.n_samples = n_samples; a.n_ls = n_ls; a.acq_out = acq_out;
-    const bool two_phase = schedule == 2 || (schedule != 1 && blocks >= kHyperTwoPhaseFromBlocks);
+    const bool two_phase = schedule == 2 || (schedule != 1 && blocks >= kSmallTwoPhaseFromBlocks);
     if (two_phase) {
         hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)n_samples), dim3(256), sizeof(SmallShared), s, a, scratch, blocks,
                            part_val, part_idx, info, ticket, out, seq, 1);

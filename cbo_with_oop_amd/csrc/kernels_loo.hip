@@ -122,14 +122,9 @@ void launch_small_loo_batch(hipStream_t s, const cbo_small_set *sets, int n_mode
 {
     {
         static std::atomic<unsigned long long> opted[2];
-        int dev = 0;
         const bool byval = n_models <= kSmallByValue;
-        if (hipGetDevice(&dev) != hipSuccess || !((opted[byval].load(std::memory_order_relaxed) >> (dev & 63)) & 1ull)) {
-            const void *fn = byval ? reinterpret_cast<const void *>(small_loo_batch_kernel<true>)
-                                   : reinterpret_cast<const void *>(small_loo_batch_kernel<false>);
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallShared)) == hipSuccess)
-                opted[byval].fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-        }
+        small_lds_opt_in(byval ? reinterpret_cast<const void *>(small_loo_batch_kernel<true>)
+                               : reinterpret_cast<const void *>(small_loo_batch_kernel<false>), opted[byval]);
     }
     SmallSetArgs args{};
     if (n_models <= kSmallByValue) {

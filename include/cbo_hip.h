@@ -582,7 +582,7 @@ int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int 
 /* cbo_acq_sweep_sets and cbo_trial_step for the point-wise acquisitions of cbo_acq_sweep_kind: kind is one
  * of CBO_ACQ_LCB | _PI | _VAR | _MPEI, param its parameter (beta; PI's jitter; not read; EI's jitter), y_best[i] is read by
  * CBO_ACQ_PI only (the array itself must be given).  Routing is cbo_acq_sweep_sets': fp64 models of at most 128 observations
- * are factored AND swept by one launch inside LDS (small_sets_kind_kernel: the EI launch's sequence with the kind's
+ * are factored AND swept by one launch inside LDS (small_sets_kernel<kind>: the EI launch's sequence with the kind's
  * epilogue; for CBO_ACQ_MPEI the workgroup first runs the model's own points through its factor for the plug-in incumbent)
  * -- they need no fit, and their fitted state and caches are left alone; larger models, fp32 models and sets whose
  * factorisation needs jitchol's jitter take the general path inside the same call: cbo_gp_fit if unfitted, then

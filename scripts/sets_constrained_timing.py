@@ -5,7 +5,7 @@ models:
 
   * cbo_acq_sweep_sets_constrained: one call for all sets and all their models;
   * the per-set sequence the call replaces: cbo_gp_fit on every model of the set, then cbo_acq_sweep_constrained, set by set;
-  * cbo_acq_sweep_sets (the causal EI: small_sets_kernel, which this feature does not touch) as the floor, in the rows
+  * cbo_acq_sweep_sets (the causal EI: small_sets_kernel of kernels_sets.hip, the same stages for one model) as the floor, in the rows
     without constraints.
 
 Every figure is the host's clock around one whole call (each call ends with its results on the host: the multi-set calls

@@ -1,10 +1,10 @@
-"""Timing of the point-wise acquisitions in the one-launch multi-set sweep (cbo_acq_sweep_sets_kind, kernels_sets_kind.hip) on
+"""Timing of the point-wise acquisitions in the one-launch multi-set sweep (cbo_acq_sweep_sets_kind, kernels_sets.hip) on
 one MI355X, at BASELINE config 1's shape -- 2 exploration sets x 200 candidates x 50 observations -- and at 6 and 25 sets of
 that shape, beside what it replaces and beside its floor, on the same box and the same models:
 
   * cbo_acq_sweep_sets_kind per kind (LCB, PI, VAR, MPEI): one call for all sets;
   * the per-set sequence the call replaces: cbo_gp_fit + cbo_acq_sweep_kind, set by set;
-  * cbo_acq_sweep_sets (the causal EI: small_sets_kernel, which this feature does not touch) as the floor.
+  * cbo_acq_sweep_sets (the causal EI: small_sets_kernel<kEiKind>, the same kernel with the EI epilogue) as the floor.
 
 Every figure is the host's clock around one whole call (each call ends with its results on the host: the multi-set calls
 poll their pinned result records, the per-set calls synchronise their stream): --warmup unrecorded calls per variant, then the

@@ -1901,6 +1901,40 @@ def test_sweep_sets_small_models_equal_the_per_set_path(hip):
         assert idx == int(f["best_idx"]), f["note"]
 
 
+def test_sweep_sets_on_both_sides_of_the_two_launch_split(hip):
+    """cbo_acq_sweep_sets with 13 candidate blocks per set (two launches: one workgroup per set factors, the sweep reads
+    the factor back) and, the first set's candidates cut to 700, with 11 (one launch: every workgroup factors): a
+    non-causal d = 1 model of 17 observations (one ragged tile) and a causal d = 3 model of 128 whose second workgroup
+    holds one live candidate.  Winners and values are cbo_gp_fit_sweep's on twin models, bit for bit."""
+    from cbo_with_oop_amd import CandidateGrid, CausalExpectedImprovement
+    from cbo_with_oop_amd.GaussianProcessFactory import HipGaussianProcess
+    rng = np.random.default_rng(13)
+    mean_f = lambda a: 0.3 * np.sin(a).sum(1, keepdims=True)                   # noqa: E731
+    var_f = lambda a: 0.05 + 0.02 * np.cos(a).sum(1, keepdims=True) ** 2       # noqa: E731
+    kws = [dict(noise_var=1e-3), dict(variance=1.3, lengthscale=0.9, noise_var=1e-3, mean_function=mean_f,
+                                      variance_adjustment=var_f)]
+    data, cand = [], []
+    for n, m, d in ((17, 800, 1), (128, 65, 3)):
+        X = rng.uniform(-2.0, 2.0, (n, d))
+        data.append((X, np.cos(X).sum(1, keepdims=True) + 0.05 * rng.standard_normal((n, 1))))
+        cand.append(rng.uniform(-2.5, 2.5, (m, d)))
+    y_best, costs = 0.2, [1.0, 3.0]
+    for m0 in (800, 700):
+        pts = [cand[0][:m0], cand[1]]
+        assert (max(len(p) for p in pts) + 63) // 64 == (13 if m0 == 800 else 11)
+        models = [HipGaussianProcess(X, y, fit=False, **kw) for (X, y), kw in zip(data, kws)]
+        grids = [CandidateGrid(p, m, index_offset=100 * i) for i, (p, m) in enumerate(zip(pts, models))]
+        got = _sweep_sets(models, grids, y_best, "min", costs)
+        assert all(m.stale for m in models)
+        twins = [HipGaussianProcess(X, y, fit=False, **kw) for (X, y), kw in zip(data, kws)]
+        want = []
+        for i, (p, t) in enumerate(zip(pts, twins)):
+            r = CausalExpectedImprovement(y_best, "min", t).sweep(CandidateGrid(p, t, index_offset=100 * i), cost=costs[i],
+                                                                  refit=True)
+            want.append((r["best_val"], r["best_idx"]))
+        assert got == want, (m0, got, want)
+
+
 def test_sweep_sets_twenty_five_sets_in_one_call(hip):
     """The coral graph's count of exploration sets (S = 25, src/graphs/impl/CoralGraph.py:162-175) in ONE call: more
     sets than travel as kernel arguments, so the descriptors are read from the pinned array; dimensions 1..3, ragged

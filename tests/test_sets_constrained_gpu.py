@@ -4,7 +4,7 @@ cbo_acq_sweep_sets_constrained (small_sets_con_kernel, kernels_sets_con.hip) and
 Every comparison is exact -- values as bit patterns (NaN equals NaN), indices equal -- and the reference is always the
 per-set cbo_acq_sweep_constrained on freshly FITTED twin models, never the code under test.  Equality is the contract: the
 launch runs kernel_value, the decoupled-wave block factorisation, the tile solve, posterior_of, acquisition_of and
-feasibility_of -- the general path's own device functions in the general path's summation orders -- model after model of a
+feasibility_of (the stages cbo_small_device.h shares with small_sets_kernel) -- the general path's own device functions in the general path's summation orders -- model after model of a
 set inside one workgroup, which is why the shapes walk n up and down and mix causal with plain models inside one set."""
 import ctypes
 import warnings

@@ -1,5 +1,5 @@
 """GPU tests of the point-wise acquisitions in the one-launch multi-set sweep and the agent:
-cbo_acq_sweep_sets_kind / cbo_trial_step_kind (small_sets_kind_kernel, kernels_sets_kind.hip) and the Python layer on top.
+cbo_acq_sweep_sets_kind / cbo_trial_step_kind (small_sets_kernel<KIND>, kernels_sets.hip) and the Python layer on top.
 
 Every comparison is exact -- values as bit patterns (NaN equals NaN), indices equal -- and the reference is always the
 per-set cbo_acq_sweep_kind (for the plug-in EI also cbo_acq_sweep at cbo_gp_plugin_incumbent) on freshly FITTED twin models,
