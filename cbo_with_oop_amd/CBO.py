@@ -49,6 +49,24 @@ def checked_path_constraints(constraints, kind=("EI", None)):
     return out
 
 
+def checked_path_hyper_samples(hyper_samples, kind=("EI", None), constraints=()):
+    """``CBOAcquisitionPath``'s ``hyper_samples`` checked on the host: ``None``, a positive int (at most 256) or a callable."""
+    from . import _lib
+    if hyper_samples is None:
+        return None
+    if kind[0] != "EI":
+        raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI'")
+    if constraints:
+        raise ValueError("the marginalised EI is not defined with constraints: constraints must be None")
+    if callable(hyper_samples):
+        return hyper_samples
+    if isinstance(hyper_samples, bool) or not isinstance(hyper_samples, (int, np.integer)) \
+            or not 1 <= hyper_samples <= _lib.MAX_HYPER_SAMPLES:
+        raise ValueError(f"hyper_samples must be an int in 1..{_lib.MAX_HYPER_SAMPLES} or a callable sampler(model, set_index), "
+                         f"not {hyper_samples!r}")
+    return int(hyper_samples)
+
+
 class CBOAcquisitionPath:
     """Holds exactly the state those methods read on the reference's ``CBO`` object: ``gp_type``,
     ``exploration_set``, ``costs``, ``task``, per-set data, spaces, prior closures and models.  ``acquisition`` (``"EI"``,
@@ -59,11 +77,15 @@ class CBOAcquisitionPath:
     ``">="``) with ``constraint_data_y`` (``constraint_data_y[s][c]`` is (n_s, 1): the values of node ``c`` at ``data_x[s]``)
     make every set's score ``EI * prod PoF / cost``: the path keeps ``constraint_models[s][c]`` --
     non-causal models from the factory on ``data_x[s]`` -- rebuilds them with the objectives and passes them on.  They need
-    ``acquisition="EI"`` and a single process."""
+    ``acquisition="EI"`` and a single process.
+    ``hyper_samples`` (a positive int H, or a callable ``sampler(model, set_index) -> (H, P)`` samples in GPy's parameter
+    order) makes every set's score the causal EI marginalised over hyper-parameter samples of its own model:
+    an int draws ``model.generate_hyperparameters_samples(H)`` with emukit's defaults.  The path keeps ``hyper_rows[s]`` and
+    redraws them whenever it rebuilds the set's model.  It needs ``acquisition="EI"``, no constraints and a single process."""
 
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
-                 acquisition_param=None, constraints=None, constraint_data_y=None):
+                 acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None):
         from .utils_functions.utils import sets_acquisition
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
@@ -77,6 +99,8 @@ class CBOAcquisitionPath:
         # (kept as given, like data_x / data_y: the caller appends to its lists between trials)
         self.constraint_data_y = constraint_data_y if self.constraints else None
         self.constraint_models = []
+        self.hyper_samples = checked_path_hyper_samples(hyper_samples, self._kind, self.constraints)
+        self.hyper_rows = [None] * len(exploration_set)
         self.gp_type = gp_type
         self.exploration_set = exploration_set
         self.es_size = len(exploration_set)
@@ -116,6 +140,18 @@ class CBOAcquisitionPath:
         if self.constraints:
             self.constraint_models = [[self._constraint_model(s, c) for c in range(len(self.constraints))]
                                       for s in range(self.es_size)]
+        for s in range(self.es_size):
+            self._draw_hyper_rows(s)
+
+    def _draw_hyper_rows(self, s):
+        """``hyper_rows[s]``: fresh samples for set s's model as the rows ``cbo_acq_sweep_sets_hyper`` takes."""
+        if self.hyper_samples is None:
+            return
+        from .utils_functions.integrated_hyper import _hyper_rows
+        model = self.models[s]
+        samples = (self.hyper_samples(model, s) if callable(self.hyper_samples)
+                   else model.generate_hyperparameters_samples(self.hyper_samples))
+        self.hyper_rows[s] = _hyper_rows(model, samples)
 
     def _constraint_model(self, s, c, fit=True):
         from .GaussianProcessFactory import GaussianProcessType
@@ -142,6 +178,7 @@ class CBOAcquisitionPath:
         if model is not None and model.mean_function is self.mean_functions[s] \
                 and model.variance_adjustment is self.var_functions[s]:
             model.rebuild(self.data_x[s], self.data_y[s], fit=fit)      # same handle: no allocation, no new grid
+            self._draw_hyper_rows(s)
             return
         self._call_cache.clear()
         old = self._grids.pop(s, None)
@@ -149,6 +186,7 @@ class CBOAcquisitionPath:
             old[1].close()
         self.models[s] = GPFactory.create(self.gp_type, self.data_x[s], self.data_y[s],
                                           [self.mean_functions[s], self.var_functions[s]], emukit_wrapper=True, fit=fit)
+        self._draw_hyper_rows(s)
 
     @property
     def comm(self):
@@ -213,10 +251,13 @@ class CBOAcquisitionPath:
         mode, world, rank = self.placement()
         if self.constraints and mode != "single":
             raise ValueError(f"constraints are scored by a single process: the placement is {mode!r}")
+        if self.hyper_samples is not None and mode != "single":
+            raise ValueError(f"the marginalised EI is scored by a single process: the placement is {mode!r}")
         if mode == "single":
             grids = [self.candidate_grid(s) for s in range(self.es_size)]
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
-                                      cache=self._call_cache, acquisition=self._kind, constraints=self.set_constraints())
+                                      cache=self._call_cache, acquisition=self._kind, constraints=self.set_constraints(),
+                                      hyper_samples=None if self.hyper_samples is None else list(self.hyper_rows))
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -278,14 +319,14 @@ class CBOAcquisitionPath:
         At the reference's model sizes the three calls' host glue costs as much as the one launch that serves them
         (``cbo_trial_step``, ``cbo_trial_step_kind`` for a point-wise ``acquisition``); anything the one call does not cover
         (several ranks, a model rebuilt with other prior closures or other hyper-parameters, the first trial,
-        constraints) takes the three calls."""
+        constraints, hyper-parameter samples) takes the three calls."""
         import ctypes
         from . import _lib
         from .utils_functions.utils import winners_to_points
         s = self.last_intervention
         st = self._call_cache.get("sweep_sets")
         model = self.models[s] if (s is not None and self.models) else None
-        fast = (st is not None and model is not None and not self.constraints
+        fast = (st is not None and model is not None and not self.constraints and self.hyper_samples is None
                 and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
                 and model._hyper_initial and st["cost_table"] is self.costs
@@ -379,7 +420,10 @@ class CBO(CBOAcquisitionPath):
     of set s to the (M, 1) values of the node -- by default ``compute_interventions`` on the graph's SEM with
     ``target_variable=node``.  A constrained node that is the target, or that some exploration set manipulates, raises
     ``ValueError``.  The incumbent stays the plain best observation (``find_current_global``), as in emukit's recipe; the
-    monitor records ``constraint_values`` and ``feasible`` per trial."""
+    monitor records ``constraint_values`` and ``feasible`` per trial.
+    ``hyper_samples`` (a positive int or a callable sampler, as for ``CBOAcquisitionPath``): ``intervene()`` scores every set
+    with the EI marginalised over hyper-parameter samples of its model; the closing ``optimize()`` of the
+    chosen set's model stays, as in the reference."""
 
     TARGET = "Y"
 
@@ -387,7 +431,7 @@ class CBO(CBOAcquisitionPath):
                  num_interventions=10, initial_num_obs_samples=100, causal_prior=False, num_trials=40, task="min",
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
-                 constraint_functions=None):
+                 constraint_functions=None, hyper_samples=None):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType
         from .graphs import _columns
@@ -429,6 +473,7 @@ class CBO(CBOAcquisitionPath):
         if len(data_x) != len(exploration):
             raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
         path_constraints = checked_path_constraints(path_constraints, sets_acquisition(acquisition, acquisition_param))
+        checked_path_hyper_samples(hyper_samples, sets_acquisition(acquisition, acquisition_param), path_constraints)
         sem = None
         if path_constraints and constraint_functions is None:
             from functools import partial
@@ -443,7 +488,7 @@ class CBO(CBOAcquisitionPath):
         super().__init__(gp_type, exploration, self.graph.get_cost_structure(type_cost), task, data_x, data_y,
                          [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None,
                          acquisition=acquisition, acquisition_param=acquisition_param, constraints=path_constraints,
-                         constraint_data_y=constraint_data_y)
+                         constraint_data_y=constraint_data_y, hyper_samples=hyper_samples)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions

@@ -129,8 +129,10 @@ struct cbo_ctx {
     PinnedBuf<cbo_small_lml_result> lml_batch_out;              // written by small_lml_batch_kernel
     PinnedBuf<cbo_small_loo_result> loo_out;                    // written by small_loo_batch_kernel
     int loo_route = 0;               // CBO_HIP_LOO_ROUTE: 1 = trailing-system chunks always, 2 = full-height chunks, else automatic
-    // cbo_acq_sweep_hyper: the samples as the kernel reads them (pinned), the general path's running sum [m_pad]
+    // cbo_acq_sweep_hyper, cbo_acq_sweep_sets_hyper: the samples as the kernel reads them (pinned, every set's rows one
+    // after the other), the general path's running sum [m_pad]
     PinnedBuf<double> hyper_host;
+    PinnedBuf<HyperSet> hyper_sets_host;                        // cbo_acq_sweep_sets_hyper: one descriptor per set
     GrowBuf<double> hyper_sum;
     int hyper_schedule = 0;          // CBO_HIP_HYPER_SCHEDULE: 1 = every workgroup factors every sample, 2 = two launches, else automatic
     GrowBuf<double> q, mu, mean, var, acq;                      // per candidate
@@ -2655,6 +2657,122 @@ extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const
         // a sample that is not positive definite as assembled: the jitchol ladder of the general path
     }
     return hyper_general_path(g, k, n_samples, n_ls, hyper, y_best, task, ei_jitter, cost, acq_out, best_val, best_idx);
+}
+
+// ---- the marginalised EI for every set of a trial (hyper_sets_kernel) ------------------------------------
+// sweep_sets_impl's routing with cbo_acq_sweep_hyper's two paths: the fp64 models of at most 128 observations are factored
+// and swept, sample after sample, by the workgroups of one launch (two from kSmallTwoPhaseFromBlocks blocks per set on, when
+// the slots fit); every other set -- and a set whose record reports a non-positive pivot at any sample -- takes
+// hyper_general_path, which restores its model.
+extern "C" int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
+                                        const double *const *hyper, const double *y_best, int task, double ei_jitter,
+                                        const double *costs, double *best_vals, int64_t *best_idxs)
+{
+    // what needs no handle first
+    if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
+    if (!n_samples || !hyper || !y_best || !costs || !best_vals || !best_idxs)
+        return fail(CBO_ERR_INVALID, "NULL argument: n_samples, hyper, y_best, costs, best_vals and best_idxs must be given");
+    if (task != CBO_TASK_MIN && task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
+    for (int i = 0; i < n_sets; ++i) {
+        if (n_samples[i] < 1 || n_samples[i] > CBO_MAX_HYPER_SAMPLES)
+            return fail(CBO_ERR_INVALID, "set " + std::to_string(i) + ": the number of hyper-parameter samples must be in 1.." +
+                                             std::to_string(CBO_MAX_HYPER_SAMPLES));
+        if (!hyper[i]) return fail(CBO_ERR_INVALID, "hyper of set " + std::to_string(i) + " is NULL");
+        if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive (set " + std::to_string(i) + ")");
+    }
+    // the handles, then the rows (whose length is the model's)
+    if (!gps || !cands) return fail(CBO_ERR_INVALID, "NULL argument: gps and cands must be given");
+    for (int i = 0; i < n_sets; ++i) {
+        const int rc = check_sweep_args(gps[i], cands[i], task);
+        if (rc != CBO_OK) return rc;
+        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
+        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
+    }
+    std::vector<int> n_ls((size_t)n_sets);
+    for (int i = 0; i < n_sets; ++i) {
+        const int L = n_ls[(size_t)i] = gps[i]->h.ard ? gps[i]->d : 1;
+        for (int h = 0; h < n_samples[i]; ++h) {
+            const double *row = hyper[i] + (size_t)h * (size_t)(L + 2);
+            const std::string where = "set " + std::to_string(i) + ", hyper row " + std::to_string(h);
+            for (int j = 0; j <= L; ++j)
+                if (!std::isfinite(row[j]) || !(row[j] > 0.0))
+                    return fail(CBO_ERR_INVALID, where + ": variance and lengthscales must be finite and positive");
+            if (!std::isfinite(row[1 + L]) || row[1 + L] < 0.0)
+                return fail(CBO_ERR_INVALID, where + ": noise_var must be finite and non-negative");
+        }
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int> small;
+    int blocks = 1;
+    int64_t blocks_max = 1;
+    size_t total = 0, doubles = 0;                              // samples and doubles of the small sets' rows
+    for (int i = 0; i < n_sets; ++i) {
+        if (!small_sweep_model(gps[i])) continue;
+        small.push_back(i);
+        const int64_t b = (cands[i]->m + 63) / 64;
+        if (b > blocks_max) blocks_max = b;
+        total += (size_t)n_samples[i];
+        doubles += (size_t)n_samples[i] * (size_t)(n_ls[(size_t)i] + 2);
+    }
+    std::vector<char> done((size_t)n_sets, 0);
+    if (!small.empty() && blocks_max <= 65535) {
+        blocks = (int)blocks_max;
+        const int ns = (int)small.size();
+        // two launches from kSmallTwoPhaseFromBlocks blocks per set on (CBO_HIP_HYPER_SCHEDULE=1 / =2: never / always) -- but
+        // only when one scratch slot per sample of the call fits the workspace limit; else every workgroup factors for itself
+        bool two_phase = c->hyper_schedule == 2 || (c->hyper_schedule != 1 && blocks >= kSmallTwoPhaseFromBlocks);
+        if (two_phase && sizeof(double) * hyper_sets_scratch_doubles(ns, blocks, (int)total, true) > c->max_ws_bytes)
+            two_phase = false;
+        int rc = ensure_small_buffers(c, ns, 1);                // records, status words, tickets
+        if (rc == CBO_OK) rc = grow(c, c->hyper_sets_host, ns < 32 ? (size_t)32 : (size_t)ns);
+        if (rc == CBO_OK) rc = grow(c, c->hyper_host, doubles);
+        if (rc == CBO_OK) rc = grow(c, c->small_scratch, hyper_sets_scratch_doubles(ns, blocks, (int)total, two_phase));
+        if (rc == CBO_OK) rc = grow(c, c->small_part_val, (size_t)ns * (size_t)blocks);
+        if (rc == CBO_OK) rc = grow(c, c->small_part_idx, (size_t)ns * (size_t)blocks);
+        if (rc != CBO_OK) return rc;
+        size_t at = 0;
+        int first = 0;
+        for (int j = 0; j < ns; ++j) {
+            const int i = small[(size_t)j];
+            const cbo_gp *g = gps[i];
+            const cbo_cands *k = cands[i];
+            const size_t len = (size_t)n_samples[i] * (size_t)(n_ls[(size_t)i] + 2);
+            std::memcpy(c->hyper_host.p + at, hyper[i], sizeof(double) * len);
+            const bool causal = g->X.sv != nullptr;
+            HyperSet &hs = c->hyper_sets_host[j];
+            hs = HyperSet{};
+            cbo_small_set &st = hs.a.st;
+            fill_small_model(st, g);
+            st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
+            st.m = k->m; st.index_offset = k->index_offset;
+            st.task = task; st.y_best = y_best[i]; st.ei_jitter = ei_jitter; st.cost = costs[i];
+            hs.a.craw = k->raw; hs.a.hyper = c->hyper_host.p + at; hs.a.n_samples = n_samples[i]; hs.a.n_ls = n_ls[(size_t)i];
+            hs.a.acq_out = nullptr;
+            hs.first = first;
+            at += len;
+            first += n_samples[i];
+        }
+        auto launch = [&](int seq) -> int {
+            launch_hyper_sets(c->stream, c->hyper_sets_host, ns, blocks, (int)total, two_phase, c->small_scratch,
+                              c->small_part_val, c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2,
+                              c->small_out, seq);
+            HIP_TRY(hipGetLastError());
+            return CBO_OK;
+        };
+        rc = polled_launch(c, "cbo_acq_sweep_sets_hyper", c->small_out.p, ns, "marginalised multi-set sweep: no result record",
+                           launch);
+        if (rc != CBO_OK) return rc;
+        harvest_small_sets(c, small, best_vals, best_idxs, done);
+    }
+    for (int i = 0; i < n_sets; ++i) {
+        if (done[(size_t)i]) continue;
+        // a larger or fp32 model, or a sample that is not positive definite as assembled: the general path, model restored
+        const int rc = hyper_general_path(gps[i], cands[i], n_samples[i], n_ls[(size_t)i], hyper[i], y_best[i], task, ei_jitter,
+                                          costs[i], nullptr, &best_vals[i], &best_idxs[i]);
+        if (rc != CBO_OK) return rc;
+    }
+    return CBO_OK;
 }
 
 // One reference-scale trial in ONE call (src/CBO.py:143-173, CBO.intervene): the model of the set that was intervened on

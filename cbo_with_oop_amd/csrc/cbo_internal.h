@@ -321,7 +321,7 @@ void launch_loo_identity_chunk(hipStream_t s, double *V, int64_t ldv, int64_t ro
 int loo_finish_blocks(int64_t n);
 void launch_loo_finish(hipStream_t s, const double *c, const double *alpha, const double *y, int64_t n, double *mean_out,
                        double *var_out, double *lpd_out, double *partial, double *sum_out);
-// The one-workgroup sweeps (small_sets_kernel, small_sets_con_kernel, hyper_avg_kernel) take two launches from this many
+// The one-workgroup sweeps (small_sets_kernel, small_sets_con_kernel, hyper_avg_kernel, hyper_sets_kernel) take two launches from this many
 // candidate blocks per model on.  Few blocks (the reference's 100-200 candidates): every workgroup factors its model
 // itself, ONE launch, no dependency between workgroups.  Many blocks (16k-candidate grids on 25 coral sets: 6400
 // workgroups): factoring the model 256 times over costs more than a second launch -- one workgroup per model factors,
@@ -356,6 +356,27 @@ size_t hyper_avg_scratch_doubles(int blocks, int n_samples);
 void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
                       int n_ls, double *acq_out, int blocks, int schedule, double *scratch, double *part_val,
                       int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq);
+// The multi-set form (hyper_sets_kernel).  One descriptor per set: hyper_avg_kernel's arguments (acq_out
+// null) and `first`, the sum of the n_samples of the sets before it -- the scratch slot of the set's sample 0 in the
+// two-launch form.  sets may be pinned host memory (read by the kernel directly beyond kSmallByValue sets).
+struct HyperArgs {
+    cbo_small_set st;                  // fill_small_model's descriptor + the candidates' prior closures, m, index_offset, EI's scalars
+    const double *craw;                // the candidates' raw AoS coordinates
+    const double *hyper;               // n_samples rows of (variance, lengthscale x n_ls, noise_var): pinned host memory
+    int n_samples, n_ls;
+    double *acq_out;                   // [m] device, or null
+};
+struct HyperSet {
+    HyperArgs a;
+    int first, pad_;
+};
+// scratch: hyper_sets_scratch_doubles(...); part_val / part_idx: n_sets * blocks_per_set entries; info, ticket (n_sets ints
+// each) zero on entry (zero again afterwards); one record out[s] (pinned) per set.  two_phase: a first launch of
+// total_samples workgroups factors every sample of every set once, the sweep reads the factors back.
+size_t hyper_sets_scratch_doubles(int n_sets, int blocks_per_set, int total_samples, bool two_phase);
+void launch_hyper_sets(hipStream_t s, const HyperSet *sets, int n_sets, int blocks_per_set, int total_samples, bool two_phase,
+                       double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out,
+                       int seq);
 // the general path: sum[i] = (first ? 0 : sum[i]) + acq[i] for i < m; then acq_out[i] = sum[i] / n_samples (acq_out may be
 // null) with arg-max partials per workgroup (n_blocks <= 2048) for launch_argmax_final
 void launch_hyper_accumulate(hipStream_t s, double *sum, const double *acq, int64_t m, bool first, int n_blocks);

@@ -1,7 +1,7 @@
 // Device functions of the one-workgroup kernels, shared by the translation units that factor a block inside LDS
 // (kernels_chol.hip: the blocked factorisation's diagonal block, small_lml_kernel; kernels_sets.hip: small_sets_kernel;
 // kernels_sets_con.hip: small_sets_con_kernel; kernels_loo.hip: small_loo_batch_kernel; kernels_hyper.hip:
-// hyper_avg_kernel): the register Cholesky of a 16x16 tile, the decoupled-wave factorisation of a 128-row block, the tile
+// hyper_avg_kernel, hyper_sets_kernel): the register Cholesky of a 16x16 tile, the decoupled-wave factorisation of a 128-row block, the tile
 // solve of a 128-row block for one wave's 16 columns, the model side of a small model (points, K(X,X) + diag, factor,
 // inverses and z), and the stages of a one-workgroup sweep (a wave's candidates, K*, the solve with q and mu, the
 // workgroup's arg-max, the set's reduction).  One definition, so every kernel that factors or sweeps a small model

@@ -10,8 +10,12 @@
 // prior closures; nothing resident is written.
 //   phases 3: every workgroup factors every sample itself (its own scratch slot, reused sample after sample);
 //   phases 1: workgroup h factors sample h into scratch slot h and returns;  phases 2: the sweep reads factor h back.
+// hyper_sets_kernel: the same for every exploration set of a trial in one launch, from the same device
+// functions -- workgroup (block, set) walks its own set's samples.
 // The accumulate / finish kernels at the end serve the general path (larger, fp32 or jitter-needing models), whose
 // per-sample terms come from cbo_acq_sweep itself.
+#include <cstring>
+
 #include "cbo_small_device.h"
 
 #pragma clang fp contract(off)
@@ -106,13 +110,117 @@ __device__ __forceinline__ void hyper_factor(SmallShared &sh, const cbo_small_se
     __syncthreads();
 }
 
-struct HyperArgs {
-    cbo_small_set st;                  // fill_small_model's descriptor + the candidates' prior closures, m, index_offset, EI's scalars
-    const double *craw;                // the candidates' raw AoS coordinates
-    const double *hyper;               // n_samples rows of (variance, lengthscale x n_ls, noise_var): pinned host memory
-    int n_samples, n_ls;
-    double *acq_out;                   // [m] device, or null
+struct HyperSetArgs { HyperSet s[kSmallByValue]; };             // by value up to kSmallByValue sets, as SmallSetArgs
+static_assert(sizeof(HyperSetArgs) <= 3072, "the descriptors by value and the other arguments fit the kernel arguments");
+
+// ---- the prologue, the per-sample body and the close of a marginalised sweep: hyper_avg_kernel (one model, one candidate
+// set) and hyper_sets_kernel (every set of a trial) are both built from these, so the arithmetic exists once
+// and the two kernels' results are equal by construction.
+
+// r = y - m(X) of this thread's row: it does not depend on the sample
+__device__ __forceinline__ double hyper_rhs(const cbo_small_set &st)
+{
+    const int tid = threadIdx.x;
+    double rhs = 0.0;
+    if (tid < st.n) {
+        const double yv = st.y[tid];
+        rhs = st.pm ? __dadd_rn(yv, -st.pm[tid]) : yv;
+    }
+    return rhs;
+}
+
+// phases 1 of a two-launch form: factor the sample `row` of the model into the scratch slot `fs`, nothing else
+__device__ __forceinline__ void hyper_factor_sample(SmallShared &sh, const cbo_small_set &st, const double *__restrict__ row,
+                                                    int n_ls, int tiles, double rhs, double *fs, int *info_word)
+{
+    const cbo_small_set sth = hyper_sample_set(st, row, n_ls);
+    hyper_model_points(sh, st, st.ard ? row + 1 : nullptr);
+    __syncthreads();
+    hyper_factor(sh, sth, tiles, rhs, fs, fs + 128 * kSmallLd, info_word);
+}
+
+// This lane's candidate of candidate block `blk` (clamped: lanes beyond the set compute, nobody looks) and the prior
+// closures at it, which do not depend on the sample either
+struct HyperLane {
+    int64_t c, cc;
+    double cpm_c, cpv_c, csv;
+    bool causal;
 };
+__device__ __forceinline__ HyperLane hyper_lane(const cbo_small_set &st, int blk, int wave, int lc)
+{
+    HyperLane L;
+    L.c = (int64_t)blk * 64 + wave * 16 + lc;
+    L.cc = (L.c < st.m) ? L.c : st.m - 1;
+    L.causal = st.sv != nullptr;
+    L.cpm_c = st.cpm ? st.cpm[L.cc] : 0.0;
+    L.cpv_c = st.cpv ? st.cpv[L.cc] : 0.0;
+    L.csv = L.causal ? sqrt(L.cpv_c) : 0.0;
+    return L;
+}
+
+// One sample: the points with the sample's lengthscales, the factor (factored here into `slot` when `factor`, else read from
+// `slot`, where a first launch left it), K*, the solve, and sum = sum + acquisition_of(...) on the lanes that own a candidate
+__device__ __forceinline__ void hyper_add_sample(SmallShared &sh, const cbo_small_set &st, const double *__restrict__ craw,
+                                                 const double *__restrict__ row, int n_ls, int tiles, double rhs, double *slot,
+                                                 bool factor, int *info_word, const HyperLane &L, int lane, int wave,
+                                                 double &sum)
+{
+    const int lc = lane & 15, kq = lane >> 4;
+    const double *ls = st.ard ? row + 1 : nullptr;
+    const cbo_small_set sth = hyper_sample_set(st, row, n_ls);
+    double *Us = slot, *invs = slot + 128 * kSmallLd;
+    double xc[CBO_MAX_DIM], csq;
+    hyper_point(craw, L.cc, st.d, ls, true, xc, csq);
+    __syncthreads();                                          // the previous sample's solve has read the block and the points
+    hyper_model_points(sh, st, ls);
+    __syncthreads();
+    if (factor) hyper_factor(sh, sth, tiles, rhs, Us, invs, info_word);
+    // ---- the factor back into LDS (rows of the factored tiles), inverses and z to registers
+    {
+        const unsigned s0 = lds_byte_address(&sh.blk.S[0][0]);
+        const int rows = 16 * tiles;
+        for (int p = wave; p < rows; p += 4)
+            glds16(Us + (int64_t)p * kSmallLd + lane * 2, __builtin_amdgcn_readfirstlane(s0 + 8u * (unsigned)(p * kDiagLd)));
+    }
+    double iv[8][4], zr[8][4];
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            iv[s][kk] = (s < tiles) ? invs[s * 256 + (4 * kk + kq) * 16 + lc] : 0.0;
+            zr[s][kk] = (s < tiles) ? Us[(int64_t)(16 * s + kq + 4 * kk) * kSmallLd + 128] : 0.0;
+        }
+    const double inv_l2 = 1.0 / (sth.lengthscale * sth.lengthscale);
+    d4 acc[8];
+    small_kstar_tiles_of(sh, sth, tiles, xc, csq, L.csv, inv_l2, kq, acc);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    double qacc, macc;
+    solve_q_mu(sh, acc, iv, zr, tiles, kq, lc, qacc, macc);
+
+    const AcqParams p = small_acq_params(sth);                // (the sample's variance and noise, the model's EI scalars)
+    if (kq == 0 && L.c < st.m) {
+        double mean, var;
+        posterior_of(qacc, macc, L.cpm_c, L.cpv_c, L.causal, p, mean, var);
+        sum = __dadd_rn(sum, acquisition_of(mean, var, p));
+    }
+}
+
+// The mean over the samples (one IEEE division) and the workgroup's arg-max of it: thread 0's (bv, bi) on return
+__device__ __forceinline__ void hyper_mean_argmax(SmallShared &sh, const cbo_small_set &st, double sum, int n_samples,
+                                                  double *acq_out, const HyperLane &L, int lane, int wave, double &bv,
+                                                  int64_t &bi)
+{
+    bv = -INFINITY;
+    bi = INT64_MAX;
+    if ((lane >> 4) == 0 && L.c < st.m) {
+        bv = __ddiv_rn(sum, (double)n_samples);
+        bi = L.c + st.index_offset;
+        if (acq_out) acq_out[L.c] = bv;
+    }
+    small_block_argmax(sh, lane, wave, bv, bi);
+}
 
 __global__ __launch_bounds__(256) void hyper_avg_kernel(const HyperArgs a, double *scratch, int blocks,
                                                         double *__restrict__ part_val, int64_t *__restrict__ part_idx,
@@ -126,89 +234,84 @@ __global__ __launch_bounds__(256) void hyper_avg_kernel(const HyperArgs a, doubl
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lc = lane & 15, kq = lane >> 4;
     const int blk = blockIdx.x;
     const int tiles = (st.n + 15) / 16;
     const int row_len = a.n_ls + 2;
-    // r = y - m(X) does not depend on the sample
-    double rhs = 0.0;
-    if (tid < st.n) {
-        const double yv = st.y[tid];
-        rhs = st.pm ? __dadd_rn(yv, -st.pm[tid]) : yv;
-    }
+    const double rhs = hyper_rhs(st);
     if (phases == 1) {                                            // workgroup h: factor sample h into slot h, nothing else
-        const double *row = a.hyper + (int64_t)blk * row_len;
-        const cbo_small_set sth = hyper_sample_set(st, row, a.n_ls);
-        double *fs = scratch + (int64_t)blk * kSmallScratch;
-        hyper_model_points(sh, st, st.ard ? row + 1 : nullptr);
-        __syncthreads();
-        hyper_factor(sh, sth, tiles, rhs, fs, fs + 128 * kSmallLd, &info[0]);
+        hyper_factor_sample(sh, st, a.hyper + (int64_t)blk * row_len, a.n_ls, tiles, rhs,
+                            scratch + (int64_t)blk * kSmallScratch, &info[0]);
         return;
     }
-
-    // this wave's 16 candidates (clamped: lanes beyond the set compute, nobody looks)
-    const int64_t c = (int64_t)blk * 64 + wave * 16 + lc;
-    const int64_t cc = (c < st.m) ? c : st.m - 1;
-    const bool causal = st.sv != nullptr;
-    const double cpm_c = st.cpm ? st.cpm[cc] : 0.0, cpv_c = st.cpv ? st.cpv[cc] : 0.0;
-    const double csv = causal ? sqrt(cpv_c) : 0.0;
-
+    const HyperLane L = hyper_lane(st, blk, wave, lane & 15);
     double sum = 0.0;
-    for (int h = 0; h < a.n_samples; ++h) {
-        const double *row = a.hyper + (int64_t)h * row_len;
-        const double *ls = st.ard ? row + 1 : nullptr;
-        const cbo_small_set sth = hyper_sample_set(st, row, a.n_ls);
+    for (int h = 0; h < a.n_samples; ++h)
         // phases 3: the workgroup's own slot, sample after sample; phases 2: slot h holds sample h's factor
-        double *my = scratch + (int64_t)(phases == 2 ? h : blk) * kSmallScratch;
-        double *Us = my, *invs = my + 128 * kSmallLd;
-        double xc[CBO_MAX_DIM], csq;
-        hyper_point(a.craw, cc, st.d, ls, true, xc, csq);
-        __syncthreads();                                          // the previous sample's solve has read the block and the points
-        hyper_model_points(sh, st, ls);
-        __syncthreads();
-        if (phases & 1) hyper_factor(sh, sth, tiles, rhs, Us, invs, &info[0]);
-        // ---- the factor back into LDS (rows of the factored tiles), inverses and z to registers
-        {
-            const unsigned s0 = lds_byte_address(&sh.blk.S[0][0]);
-            const int rows = 16 * tiles;
-            for (int p = wave; p < rows; p += 4)
-                glds16(Us + (int64_t)p * kSmallLd + lane * 2, __builtin_amdgcn_readfirstlane(s0 + 8u * (unsigned)(p * kDiagLd)));
-        }
-        double iv[8][4], zr[8][4];
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                iv[s][kk] = (s < tiles) ? invs[s * 256 + (4 * kk + kq) * 16 + lc] : 0.0;
-                zr[s][kk] = (s < tiles) ? Us[(int64_t)(16 * s + kq + 4 * kk) * kSmallLd + 128] : 0.0;
-            }
-        const double inv_l2 = 1.0 / (sth.lengthscale * sth.lengthscale);
-        d4 acc[8];
-        small_kstar_tiles_of(sh, sth, tiles, xc, csq, csv, inv_l2, kq, acc);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-
-        double qacc, macc;
-        solve_q_mu(sh, acc, iv, zr, tiles, kq, lc, qacc, macc);
-
-        const AcqParams p = small_acq_params(sth);                // (the sample's variance and noise, the model's EI scalars)
-        if (kq == 0 && c < st.m) {
-            double mean, var;
-            posterior_of(qacc, macc, cpm_c, cpv_c, causal, p, mean, var);
-            sum = __dadd_rn(sum, acquisition_of(mean, var, p));
-        }
-    }
-
-    // ---- the mean, and the workgroup's arg-max of it
-    double bv = -INFINITY;
-    int64_t bi = INT64_MAX;
-    if (kq == 0 && c < st.m) {
-        bv = __ddiv_rn(sum, (double)a.n_samples);
-        bi = c + st.index_offset;
-        if (a.acq_out) a.acq_out[c] = bv;
-    }
-    small_block_argmax(sh, lane, wave, bv, bi);
+        hyper_add_sample(sh, st, a.craw, a.hyper + (int64_t)h * row_len, a.n_ls, tiles, rhs,
+                         scratch + (int64_t)(phases == 2 ? h : blk) * kSmallScratch, (phases & 1) != 0, &info[0], L, lane, wave,
+                         sum);
+    double bv;
+    int64_t bi;
+    hyper_mean_argmax(sh, st, sum, a.n_samples, a.acq_out, L, lane, wave, bv, bi);
     small_set_finish(bv, bi, 0, blk, blocks, part_val, part_idx, info, ticket, out, seq, &last_flag);
+}
+
+// The multi-set form (cbo_acq_sweep_sets_hyper): workgroup (blk, set) serves 64 candidates of set `set` and
+// walks that set's own samples in index order.
+//   phases 3: grid (blocks_per_set, n_sets); every workgroup factors every sample of its set into its own scratch slot
+//             set * blocks_per_set + blk, reused sample after sample;
+//   phases 1: grid (sum of the sets' n_samples): workgroup first_s + h factors sample h of set s into slot first_s + h;
+//   phases 2: grid (blocks_per_set, n_sets): the sweep reads slot first_s + h back.
+// A workgroup beyond its set's own candidate blocks (a set narrower than the widest) reads nothing of the set and writes no
+// scratch: it only hands in the empty winner, as small_sets_kernel's does, so that the set's ticket counts blocks_per_set.
+template <bool BYVAL>
+__global__ __launch_bounds__(256) void hyper_sets_kernel(const HyperSetArgs byval, const HyperSet *__restrict__ sets,
+                                                         int n_sets, double *scratch, int blocks_per_set,
+                                                         double *__restrict__ part_val, int64_t *__restrict__ part_idx,
+                                                         int *__restrict__ info, int *__restrict__ ticket,
+                                                         cbo_small_result *__restrict__ out, int seq, int phases)
+{
+    __shared__ int last_flag;
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    SmallShared &sh = *reinterpret_cast<SmallShared *>(smem_raw);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (phases == 1) {
+        // the set whose samples hold slot blockIdx.x: the sets' first slots ascend (uniform scan, at most n_sets - 1 steps)
+        const int slot = blockIdx.x;
+        int set = 0;
+        while (set + 1 < n_sets && (BYVAL ? byval.s[set + 1].first : sets[set + 1].first) <= slot) ++set;
+        const HyperSet hs = BYVAL ? byval.s[set] : sets[set];
+        const cbo_small_set &st = hs.a.st;
+        const int h = slot - hs.first;
+        if (h >= hs.a.n_samples) return;
+        hyper_factor_sample(sh, st, hs.a.hyper + (int64_t)h * (hs.a.n_ls + 2), hs.a.n_ls, (st.n + 15) / 16, hyper_rhs(st),
+                            scratch + (int64_t)slot * kSmallScratch, &info[set]);
+        return;
+    }
+    const int set = blockIdx.y, blk = blockIdx.x;
+    const HyperSet hs = BYVAL ? byval.s[set] : sets[set];
+    const cbo_small_set &st = hs.a.st;
+    const int slot = set * blocks_per_set + blk;
+    if ((int64_t)blk * 64 >= st.m) {                              // no candidates left for this workgroup
+        small_set_finish(-INFINITY, INT64_MAX, set, slot, blocks_per_set, part_val, part_idx, info, ticket, out, seq,
+                         &last_flag);
+        return;
+    }
+    const int tiles = (st.n + 15) / 16;
+    const int row_len = hs.a.n_ls + 2;
+    const double rhs = hyper_rhs(st);
+    const HyperLane L = hyper_lane(st, blk, wave, lane & 15);
+    double sum = 0.0;
+    for (int h = 0; h < hs.a.n_samples; ++h)
+        hyper_add_sample(sh, st, hs.a.craw, hs.a.hyper + (int64_t)h * row_len, hs.a.n_ls, tiles, rhs,
+                         scratch + (int64_t)(phases == 2 ? hs.first + h : slot) * kSmallScratch, (phases & 1) != 0, &info[set],
+                         L, lane, wave, sum);
+    double bv;
+    int64_t bi;
+    hyper_mean_argmax(sh, st, sum, hs.a.n_samples, nullptr, L, lane, wave, bv, bi);
+    small_set_finish(bv, bi, set, slot, blocks_per_set, part_val, part_idx, info, ticket, out, seq, &last_flag);
 }
 
 size_t hyper_avg_scratch_doubles(int blocks, int n_samples)
@@ -235,6 +338,47 @@ void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw
     } else {
         hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, scratch, blocks,
                            part_val, part_idx, info, ticket, out, seq, 3);
+    }
+}
+
+// The two-launch form needs one scratch slot per sample of the call, the single launch one per workgroup
+size_t hyper_sets_scratch_doubles(int n_sets, int blocks_per_set, int total_samples, bool two_phase)
+{
+    return (two_phase ? (size_t)total_samples : (size_t)n_sets * (size_t)blocks_per_set) * kSmallScratch;
+}
+
+template <bool BYVAL>
+static void launch_hyper_sets_as(hipStream_t s, const HyperSetArgs &args, const HyperSet *sets, int n_sets, int blocks_per_set,
+                                 int total_samples, bool two_phase, double *scratch, double *part_val, int64_t *part_idx,
+                                 int *info, int *ticket, cbo_small_result *out, int seq)
+{
+    static std::atomic<unsigned long long> opted{0};
+    small_lds_opt_in(reinterpret_cast<const void *>(hyper_sets_kernel<BYVAL>), opted);
+    const dim3 grid((unsigned)blocks_per_set, (unsigned)n_sets);
+    auto launch = [&](const dim3 &g, int phases) {
+        hipLaunchKernelGGL((hyper_sets_kernel<BYVAL>), g, dim3(256), sizeof(SmallShared), s, args, sets, n_sets, scratch,
+                           blocks_per_set, part_val, part_idx, info, ticket, out, seq, phases);
+    };
+    if (two_phase) {
+        launch(dim3((unsigned)total_samples), 1);
+        launch(grid, 2);
+    } else {
+        launch(grid, 3);
+    }
+}
+
+void launch_hyper_sets(hipStream_t s, const HyperSet *sets, int n_sets, int blocks_per_set, int total_samples, bool two_phase,
+                       double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out,
+                       int seq)
+{
+    HyperSetArgs args{};
+    if (n_sets <= kSmallByValue) {
+        std::memcpy(args.s, sets, sizeof(HyperSet) * (size_t)n_sets);
+        launch_hyper_sets_as<true>(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, scratch, part_val,
+                                   part_idx, info, ticket, out, seq);
+    } else {
+        launch_hyper_sets_as<false>(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, scratch, part_val,
+                                    part_idx, info, ticket, out, seq);
     }
 }
 

@@ -279,7 +279,7 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
 
 
 def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
-                       acquisition="EI", acquisition_param=None, constraints=None):
+                       acquisition="EI", acquisition_param=None, hyper_samples=None, constraints=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -299,11 +299,19 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     points with the set's ``index_offset``, built once and kept in the cache entry while the model object stays the same.
     Non-empty constraints with another ``acquisition`` than ``"EI"`` or with ``raw=True``, a wrong length, more than 8
     constraints in a set and a non-finite ``max_value`` or ``jitter`` raise ``ValueError`` before any device call.  ``None``,
-    or every list empty, takes exactly today's calls."""
+    or every list empty, takes exactly today's calls.
+    ``hyper_samples`` (one entry per set, each an (H_s, P_s) array of hyper-parameter samples in GPy's parameter order -- a
+    model whose noise is fixed has no noise column -- or a positive int: every model then draws that many with
+    ``generate_hyperparameters_samples``): every set is scored with the causal EI marginalised over its own samples, over
+    the cost, in the same one call (``cbo_acq_sweep_sets_hyper``) -- per set what
+    ``find_next_y_point(hyper_samples=rows_s)`` returns.  A wrong length, a bad shape, more than 256 rows, non-finite or
+    non-positive entries, another ``acquisition`` than ``"EI"``, non-empty ``constraints`` and ``raw=True`` raise
+    ``ValueError`` before any device call.  ``None`` takes exactly today's calls."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition(acquisition, acquisition_param)
     constraints = checked_set_constraints(constraints, len(models), kind, raw)
+    hyper_rows = checked_set_hyper_samples(hyper_samples, models, kind, constraints, raw)
     if kind[0] != "EI" and task not in _lib.TASK_CODE:
         raise ValueError(f"task must be 'min' or 'max', not {task!r}")
     s = len(models)
@@ -336,7 +344,18 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     if st.get("constraints") is not None or constraints is not None:
         st.pop("trial_args", None)               # (the one-call trial step names the unconstrained call)
     st["constraints"] = constraints
-    if constraints is not None:
+    if st.get("hyper_rows") is not None or hyper_rows is not None:
+        st.pop("trial_args", None)               # (likewise: the one-call trial step names the plug-in call)
+    st["hyper_rows"] = hyper_rows
+    if hyper_rows is not None:
+        # (the entry keeps the row arrays and the pointer array alive; the rows change from trial to trial)
+        st["hyper_args"] = ((ctypes.c_int * s)(*[r.shape[0] for r in hyper_rows]),
+                            (ctypes.c_void_p * s)(*[r.ctypes.data for r in hyper_rows]))
+        _lib.check(_lib.load().cbo_acq_sweep_sets_hyper(s, st["gps"], st["cds"], st["hyper_args"][0], st["hyper_args"][1],
+                                                        _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
+                                                        _lib.dptr(batch_cost), _lib.dptr(vals),
+                                                        idxs.ctypes.data_as(_lib.c_int64_p)))
+    elif constraints is not None:
         _sweep_sets_constrained(st, models, grids, constraints, task)
     elif kind[0] == "EI":
         _lib.check(_lib.load().cbo_acq_sweep_sets(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
@@ -348,7 +367,9 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
                                                        _lib.dptr(batch_cost), _lib.dptr(vals),
                                                        idxs.ctypes.data_as(_lib.c_int64_p)))
     for i in range(s):
-        if not models[i].small:                  # the general path fitted it on the way (deferred refit)
+        # the general path fitted it on the way (deferred refit) -- the marginalised one restores a model instead: fitted
+        # again if it was, unfitted if it was not
+        if not models[i].small and hyper_rows is None:
             models[i].stale = False
     if constraints is not None:
         for i in range(s):                       # (a set with a larger model anywhere took the general path: all fitted)
@@ -359,6 +380,43 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     if raw:
         return None, [(float(vals[i]), int(idxs[i])) for i in range(s)]
     return winners_to_points(st, models, grids, current_global_best, task)
+
+
+def checked_set_hyper_samples(hyper_samples, models, kind=("EI", None), constraints=None, raw=False):
+    """``find_next_y_points``' ``hyper_samples`` checked on the host: ``None``, or per set the contiguous (H_s, 2 + L_s) rows
+    of ``cbo_acq_sweep_sets_hyper`` (``integrated_hyper._hyper_rows``: a fixed noise fills its own column).  Everything that
+    can be refused is refused before a model draws (an int) and before any device call."""
+    if hyper_samples is None:
+        return None
+    if kind[0] != "EI":
+        raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI'")
+    if constraints is not None:
+        raise ValueError("the marginalised EI is not defined with constraints: constraints must be None or empty")
+    if raw:
+        raise ValueError("the marginalised EI is not defined across several ranks (raw=True)")
+    from .. import _lib
+    from .integrated_hyper import _hyper_rows
+    if isinstance(hyper_samples, bool) or (isinstance(hyper_samples, (int, np.integer)) and hyper_samples < 1):
+        raise ValueError(f"hyper_samples must be a list of (H, P) arrays or a positive int, not {hyper_samples!r}")
+    if isinstance(hyper_samples, (int, np.integer)):
+        if hyper_samples > _lib.MAX_HYPER_SAMPLES:
+            raise ValueError(f"at most {_lib.MAX_HYPER_SAMPLES} samples, not {hyper_samples}")
+        hyper_samples = [m.generate_hyperparameters_samples(int(hyper_samples)) for m in models]
+    elif isinstance(hyper_samples, np.ndarray) or not hasattr(hyper_samples, "__len__"):
+        raise ValueError("hyper_samples must be a list with one (H, P) array per exploration set, or a positive int")
+    if len(hyper_samples) != len(models):
+        raise ValueError(f"hyper_samples must have one entry per exploration set ({len(models)}), not {len(hyper_samples)}")
+    rows = []
+    for i, (model, samples) in enumerate(zip(models, hyper_samples)):
+        try:
+            r = _hyper_rows(model, samples)
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"hyper_samples of set {i}: {exc}") from None
+        if not np.all(np.isfinite(r)) or not np.all(r[:, :-1] > 0.0) or not np.all(r[:, -1] >= 0.0):
+            raise ValueError(f"hyper_samples of set {i}: variances and lengthscales must be finite and positive, the noise "
+                             "variance finite and not negative")
+        rows.append(r)
+    return rows
 
 
 def checked_set_constraints(constraints, n_sets, kind=("EI", None), raw=False):
@@ -442,6 +500,7 @@ def winners_to_points(st, models, grids, current_global_best, task):
     costs, batch_cost, vals, idxs = st["costs"], st["batch_cost"], st["vals"], st["idxs"]
     name, param = st.get("kind", ("EI", None))
     constraints = st.get("constraints")
+    hyper_rows = st.get("hyper_rows")
     xs, ys = [], []
     winners, values, batch = idxs.tolist(), vals.tolist(), batch_cost.tolist()
     for i in range(len(models)):
@@ -450,6 +509,10 @@ def winners_to_points(st, models, grids, current_global_best, task):
         point_cost = float(costs[i].evaluate(x_new))
         if point_cost == batch[i]:
             y = np.array(((values[i],),))
+        elif hyper_rows is not None:
+            from .integrated_hyper import IntegratedHyperParameterAcquisition
+            generator = lambda mdl, c=costs[i]: CausalExpectedImprovement(current_global_best, task, mdl) / c   # noqa: E731
+            y = IntegratedHyperParameterAcquisition(models[i], generator, samples=hyper_rows[i]).evaluate(x_new)
         elif constraints is not None and constraints[i]:
             from .constrained import AcquisitionProduct
             ei = CausalExpectedImprovement(current_global_best, task, models[i])

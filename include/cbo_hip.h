@@ -593,8 +593,8 @@ int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int 
  * cbo_acq_sweep_sets_kind + cbo_argmax_sets.
  * CBO_ERR_INVALID, before any model is touched: cbo_acq_sweep_sets' (cbo_trial_step's) argument checks, a kind outside 1..4,
  * a non-finite param, beta < 0, a non-finite y_best[i] for CBO_ACQ_PI, costs[i] <= 0 or NaN, a bad task for every kind but
- * CBO_ACQ_VAR.  Out of scope: max-value entropy search, batch and hyper-marginalised epilogues in the one launch (the
- * constrained one is cbo_acq_sweep_sets_constrained, below). */
+ * CBO_ACQ_VAR.  Out of scope: max-value entropy search and batch epilogues in the one launch (the constrained one is
+ * cbo_acq_sweep_sets_constrained, the hyper-marginalised one cbo_acq_sweep_sets_hyper, below). */
 int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int kind, const double *y_best,
                             int task, double param, const double *costs, double *best_vals, int64_t *best_idxs);
 int cbo_trial_step_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
@@ -628,6 +628,30 @@ int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cbo_cands *co
                                    double ei_jitter, const double *costs, const int *n_con, cbo_gp *const *con_gps,
                                    cbo_cands *const *con_cands, const double *con_value, const double *con_jitter,
                                    const int *con_sense, double *best_vals, int64_t *best_idxs);
+
+/* cbo_acq_sweep_sets for the marginalised EI of cbo_acq_sweep_hyper: set i is (gps[i], cands[i]) with its
+ * own n_samples[i] in 1..CBO_MAX_HYPER_SAMPLES rows hyper[i] of (variance, lengthscale x L_i, noise_var), cbo_acq_sweep_hyper's
+ * row format (L_i = d if gps[i] is ard else 1).  Sets of one call may differ in n_samples, d, ARD and causal / plain.
+ * Contract: for every set, best_vals[i] and best_idxs[i] are bit for bit what cbo_acq_sweep_hyper(gps[i], cands[i],
+ * n_samples[i], hyper[i], y_best[i], task, ei_jitter, costs[i], NULL, &v, &idx) returns: the same sum in sample order, the
+ * same division, the same tie rule (lowest index, NaN maximal, index_offset applied).
+ * Routing is cbo_acq_sweep_sets': the fp64 models of at most 128 observations (CBO_HIP_SMALL_SETS on, the call's widest such
+ * set at most 65535 blocks of 64 candidates) are answered by ONE launch whose workgroups serve (one set, 64 candidates) and
+ * walk that set's samples (hyper_sets_kernel) -- two launches from 12 candidate blocks per set on when one scratch slot per
+ * sample of the call fits the workspace limit (CBO_HIP_WORKSPACE_MB); CBO_HIP_HYPER_SCHEDULE=1 / =2 forces the schedule,
+ * same bits either way.  Those models need no fit, nothing resident of them or of their candidate sets is read beyond raw
+ * points, targets and prior closures, and nothing is written: factor, fit stamp, cached q / mu and kept solutions stay, an
+ * unfitted model stays unfitted.  A larger or fp32 model, and a set one of whose samples met a non-positive pivot in the
+ * launch, takes cbo_acq_sweep_hyper's general path inside the same call, which restores the model as described there,
+ * without disturbing the other sets.
+ * CBO_ERR_INVALID, before any model is touched (what needs no handle is checked first): n_sets <= 0; a NULL n_samples, hyper,
+ * y_best, costs, best_vals or best_idxs; a bad task; an n_samples[i] out of range; a NULL hyper[i]; costs[i] <= 0 or NaN;
+ * then a NULL handle array or handle; models of different contexts; a model without data; gp->d != cands->d; a causal model
+ * whose candidate set carries no prior; a variance or lengthscale that is not finite and positive, a noise that is negative
+ * or not finite, in any row.  There is no CBO_ERR_NOT_FITTED. */
+int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
+                             const double *const *hyper, const double *y_best, int task, double ei_jitter,
+                             const double *costs, double *best_vals, int64_t *best_idxs);
 
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
