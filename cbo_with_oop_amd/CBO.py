@@ -72,7 +72,10 @@ class CBOAcquisitionPath:
     ``exploration_set``, ``costs``, ``task``, per-set data, spaces, prior closures and models.  ``acquisition`` (``"EI"``,
     the reference's, or ``"LCB" | "PI" | "MPEI" | "VAR"``) and ``acquisition_param`` (beta, default 1; the jitter of PI and
     MPEI, default 0) name what every exploration set is scored with (``find_next_y_points``); they are fixed
-    at construction.
+    at construction.  ``acquisition="MES"`` (``acquisition_param``: ``None`` or ``(num_samples, grid_size)``) scores every set
+    with emukit's max-value entropy search over the cost: two device calls per trial for all sets, the
+    Gumbel grids drawn from ``space_list``; it needs ``task="min"``, no constraints, no hyper-parameter samples and a single
+    process, and its ``trial_step`` takes the three-call route.
     ``constraints`` (a list of ``(name, sense, value[, jitter])``, at most 8, shared by all sets; ``sense`` ``"<="`` or
     ``">="``) with ``constraint_data_y`` (``constraint_data_y[s][c]`` is (n_s, 1): the values of node ``c`` at ``data_x[s]``)
     make every set's score ``EI * prod PoF / cost``: the path keeps ``constraint_models[s][c]`` --
@@ -86,11 +89,13 @@ class CBOAcquisitionPath:
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None):
-        from .utils_functions.utils import sets_acquisition
+        from .utils_functions.utils import sets_acquisition_or_default as sets_acquisition
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
         self._kind = sets_acquisition(acquisition, acquisition_param)
         self.acquisition, self.acquisition_param = acquisition, acquisition_param
+        if self._kind[0] == "MES" and task != "min":
+            raise ValueError("acquisition='MES' minimises: task must be 'min'")
         self.constraints = checked_path_constraints(constraints, self._kind)
         if self.constraints:
             if constraint_data_y is None or len(constraint_data_y) != len(exploration_set) \
@@ -253,11 +258,14 @@ class CBOAcquisitionPath:
             raise ValueError(f"constraints are scored by a single process: the placement is {mode!r}")
         if self.hyper_samples is not None and mode != "single":
             raise ValueError(f"the marginalised EI is scored by a single process: the placement is {mode!r}")
+        if self._kind[0] == "MES" and mode != "single":
+            raise ValueError(f"max-value entropy search is scored by a single process: the placement is {mode!r}")
         if mode == "single":
             grids = [self.candidate_grid(s) for s in range(self.es_size)]
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
                                       cache=self._call_cache, acquisition=self._kind, constraints=self.set_constraints(),
-                                      hyper_samples=None if self.hyper_samples is None else list(self.hyper_rows))
+                                      hyper_samples=None if self.hyper_samples is None else list(self.hyper_rows),
+                                      spaces=self.space_list if self._kind[0] == "MES" else None)
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -319,7 +327,8 @@ class CBOAcquisitionPath:
         At the reference's model sizes the three calls' host glue costs as much as the one launch that serves them
         (``cbo_trial_step``, ``cbo_trial_step_kind`` for a point-wise ``acquisition``); anything the one call does not cover
         (several ranks, a model rebuilt with other prior closures or other hyper-parameters, the first trial,
-        constraints, hyper-parameter samples) takes the three calls."""
+        constraints, hyper-parameter samples, max-value entropy search -- whose host draws its Gumbel samples between the
+        Gumbel fit and the scoring) takes the three calls."""
         import ctypes
         from . import _lib
         from .utils_functions.utils import winners_to_points
@@ -327,6 +336,7 @@ class CBOAcquisitionPath:
         st = self._call_cache.get("sweep_sets")
         model = self.models[s] if (s is not None and self.models) else None
         fast = (st is not None and model is not None and not self.constraints and self.hyper_samples is None
+                and self._kind[0] != "MES"
                 and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
                 and model._hyper_initial and st["cost_table"] is self.costs
@@ -414,7 +424,7 @@ class CBO(CBOAcquisitionPath):
     set's ``get_gp_name`` must name a graph GP; the constructor raises KeyError naming the first that does not.
     ``lockstep=False`` fits the graph GPs one after another (the reference's order; same models).
     ``acquisition`` / ``acquisition_param``: what ``intervene()`` scores the exploration sets with, as for
-    ``CBOAcquisitionPath`` (default: the reference's causal EI).
+    ``CBOAcquisitionPath`` (default: the reference's causal EI; ``"MES"`` needs ``task="min"``).
     ``constraints`` (``{"node": (sense, value[, jitter])}``): other nodes of the graph that must stay in range; every set is
     scored with ``EI * prod PoF / cost``.  ``constraint_functions[s][node]`` maps (M, d) intervention values
     of set s to the (M, 1) values of the node -- by default ``compute_interventions`` on the graph's SEM with
@@ -435,7 +445,7 @@ class CBO(CBOAcquisitionPath):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType
         from .graphs import _columns
-        from .utils_functions.utils import sets_acquisition
+        from .utils_functions.utils import sets_acquisition_or_default as sets_acquisition
         self.graph = graph() if isinstance(graph, type) else graph
         self.measurements = _columns(measurements)
         self.all_measurements = _columns(all_measurements)

@@ -158,6 +158,9 @@ SIGNATURES = {
                                                       c_double_p, c_int_p, c_double_p, c_int64_p]),
     "cbo_acq_sweep_sets_hyper": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_int_p, c_void_pp, c_double_p,
                                                 ctypes.c_int, ctypes.c_double, c_double_p, c_double_p, c_int64_p]),
+    "cbo_acq_sweep_sets_mes": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_int_p, c_void_pp, c_double_p, c_double_p,
+                                              c_int64_p]),
+    "cbo_gp_mes_gumbel_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_double_p]),
     "cbo_comm_gather_i64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_int64_p]),
     "cbo_comm_share_factor": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_int_p, ctypes.c_int,

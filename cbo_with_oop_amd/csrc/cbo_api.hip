@@ -134,6 +134,14 @@ struct cbo_ctx {
     PinnedBuf<double> hyper_host;
     PinnedBuf<HyperSet> hyper_sets_host;                        // cbo_acq_sweep_sets_hyper: one descriptor per set
     GrowBuf<double> hyper_sum;
+    // cbo_acq_sweep_sets_mes, cbo_gp_mes_gumbel_sets: one (offset, count) per set and the sets' Gumbel samples as the kernel
+    // reads them (pinned); the grids' mean / var workspace, every set's points one after the other; the bisections' table,
+    // quantiles and status words
+    PinnedBuf<cbo_small_aux> aux_host;
+    PinnedBuf<double> mes_host;
+    GrowBuf<double> gumbel_mean, gumbel_var, gumbel_out;
+    GrowBuf<int64_t> gumbel_status;
+    PinnedBuf<GumbelSet> gumbel_sets_host;
     int hyper_schedule = 0;          // CBO_HIP_HYPER_SCHEDULE: 1 = every workgroup factors every sample, 2 = two launches, else automatic
     GrowBuf<double> q, mu, mean, var, acq;                      // per candidate
     double *part_val = nullptr; int64_t *part_idx = nullptr;
@@ -2317,10 +2325,11 @@ static int ensure_small_buffers(cbo_ctx *c, int n_sets, int blocks)
 // is already the new one, and the one-launch path -- which the caller has checked the set takes -- prepares and stores them.
 // kind: kEiKind = the causal EI (small_sets_kernel, cbo_gp_fit_sweep / cbo_acq_sweep), else one of CBO_ACQ_* (DESIGN.md §4l:
 // small_sets_kernel<kind>, cbo_gp_fit + cbo_acq_sweep_kind), ei_jitter then being the kind's parameter -- the caller has run
-// check_kind_args.
+// check_kind_args.  kMesKind (small_sets_kernel<kMesKind>, cbo_gp_fit + cbo_acq_sweep_mes): set i scores
+// against mins[i][0..n_samples[i]); y_best is not read (it may be NULL), task is 'min' -- cbo_acq_sweep_sets_mes has checked.
 static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
                            double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs, int staged_set,
-                           int kind);
+                           int kind, const int *n_samples = nullptr, const double *const *mins = nullptr);
 
 extern "C" int cbo_acq_sweep_sets(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
                                   double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs)
@@ -2355,11 +2364,32 @@ extern "C" int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands
     return sweep_sets_impl(n_sets, gps, cands, y_best, task, param, costs, best_vals, best_idxs, -1, kind);
 }
 
+// cbo_acq_sweep_sets for max-value entropy search: cbo_acq_sweep_mes' checks of its scalars for every set,
+// before anything is touched, then sweep_sets_impl's routing
+extern "C" int cbo_acq_sweep_sets_mes(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
+                                      const double *const *mins, const double *costs, double *best_vals, int64_t *best_idxs)
+{
+    if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
+    if (!n_samples || !mins || !costs || !best_vals || !best_idxs)
+        return fail(CBO_ERR_INVALID, "NULL argument: n_samples, mins, costs, best_vals and best_idxs must be given");
+    for (int i = 0; i < n_sets; ++i) {
+        const std::string where = " (set " + std::to_string(i) + ")";
+        if (n_samples[i] <= 0 || n_samples[i] > kMesMaxSamples)
+            return fail(CBO_ERR_INVALID, "the number of Gumbel samples must be in 1.." + std::to_string(kMesMaxSamples) + where);
+        if (!mins[i]) return fail(CBO_ERR_INVALID, "NULL argument: mins" + where);
+        for (int k = 0; k < n_samples[i]; ++k)
+            if (!std::isfinite(mins[i][k])) return fail(CBO_ERR_INVALID, "the Gumbel samples must be finite" + where);
+        if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive" + where);
+    }
+    return sweep_sets_impl(n_sets, gps, cands, nullptr, CBO_TASK_MIN, 0.0, costs, best_vals, best_idxs, -1, kMesKind,
+                           n_samples, mins);
+}
+
 static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
                            double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs, int staged_set,
-                           int kind)
+                           int kind, const int *n_samples, const double *const *mins)
 {
-    if (n_sets <= 0 || !gps || !cands || !y_best || !costs || !best_vals || !best_idxs)
+    if (n_sets <= 0 || !gps || !cands || (!y_best && kind != kMesKind) || !costs || !best_vals || !best_idxs)
         return fail(CBO_ERR_INVALID, "bad argument");
     for (int i = 0; i < n_sets; ++i) {
         int rc = check_sweep_args(gps[i], cands[i], task);
@@ -2381,6 +2411,25 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
     std::vector<char> done((size_t)n_sets, 0);
     if (!small.empty() && blocks <= 65535) {
         int rc = ensure_small_buffers(c, (int)small.size(), blocks);
+        SmallAux aux;
+        if (rc == CBO_OK && kind == kMesKind) {
+            // the small sets' samples, one set after the other, and where each set's begin
+            size_t total = 0;
+            for (size_t j = 0; j < small.size(); ++j) total += (size_t)n_samples[small[j]];
+            rc = grow(c, c->aux_host, small.size() < 32 ? (size_t)32 : small.size());
+            if (rc == CBO_OK) rc = grow(c, c->mes_host, total);
+            if (rc == CBO_OK) {
+                size_t at = 0;
+                for (size_t j = 0; j < small.size(); ++j) {
+                    const size_t k = (size_t)n_samples[small[j]];
+                    std::memcpy(c->mes_host.p + at, mins[small[j]], sizeof(double) * k);
+                    c->aux_host[j] = cbo_small_aux{(int64_t)at, (int64_t)k};
+                    at += k;
+                }
+                aux.per_set = c->aux_host;
+                aux.data = c->mes_host;
+            }
+        }
         if (rc != CBO_OK) return rc;
         for (size_t j = 0; j < small.size(); ++j) {
             cbo_gp *g = gps[small[j]];
@@ -2402,11 +2451,13 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
         const int ns = (int)small.size();
         auto launch = [&](int seq) -> int {
             launch_small_sets(c->stream, kind, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val,
-                              c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq);
+                              c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq,
+                              aux);
             HIP_TRY(hipGetLastError());
             return CBO_OK;
         };
-        rc = polled_launch(c, kind == kEiKind ? "cbo_acq_sweep_sets" : "cbo_acq_sweep_sets_kind", c->small_out.p, ns,
+        rc = polled_launch(c, kind == kEiKind ? "cbo_acq_sweep_sets" : kind == kMesKind ? "cbo_acq_sweep_sets_mes"
+                                                                                         : "cbo_acq_sweep_sets_kind", c->small_out.p, ns,
                            "multi-set sweep: no result record", launch);
         if (rc != CBO_OK) return rc;
         harvest_small_sets(c, small, best_vals, best_idxs, done);
@@ -2414,7 +2465,12 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
     for (int i = 0; i < n_sets; ++i) {
         if (done[(size_t)i]) continue;
         int rc;
-        if (kind != kEiKind) {
+        if (kind == kMesKind) {
+            rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
+            if (rc == CBO_OK)
+                rc = cbo_acq_sweep_mes(gps[i], cands[i], n_samples[i], mins[i], costs[i], nullptr, nullptr, nullptr,
+                                       &best_vals[i], &best_idxs[i]);
+        } else if (kind != kEiKind) {
             rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
             if (rc == CBO_OK)
                 rc = cbo_acq_sweep_kind(gps[i], cands[i], kind, y_best[i], task, ei_jitter, costs[i], nullptr, nullptr,
@@ -3055,6 +3111,34 @@ extern "C" int cbo_acq_sweep_kind(cbo_gp *g, cbo_cands *k, int kind, double y_be
                       y_best_dev);
 }
 
+// What gumbel_quantiles_kernel left for one set: the single call's message for the first quantile that failed ("" = none),
+// and _fit_gumbel's parameters from the three quantiles -- shared by cbo_gp_mes_gumbel and cbo_gp_mes_gumbel_sets.
+static std::string gumbel_failure(const double *out5, const int64_t *status3)
+{
+    for (int j = 0; j < 3; ++j) {
+        char msg[160];
+        if (status3[j] == 1) {
+            std::snprintf(msg, sizeof msg, "Gumbel fit: f(a) and f(b) must have different signs (quantile %.2f on "
+                          "[%.17g, %.17g])", 0.25 * (j + 1), out5[3], out5[4]);
+            return msg;
+        }
+        if (status3[j] != 0) {
+            std::snprintf(msg, sizeof msg, "Gumbel fit: bisection of quantile %.2f failed to converge after 10000 "
+                          "iterations", 0.25 * (j + 1));
+            return msg;
+        }
+    }
+    return std::string();
+}
+static void gumbel_parameters(const double *out5, double *quantiles3, double *a_out, double *b_out)
+{
+    for (int j = 0; j < 3; ++j) quantiles3[j] = out5[j];
+    // _fit_gumbel: b = (q25 - q75) / (log(log(4/3)) - log(log(4))), a = q50 - b log(log(2))
+    const double b = (out5[0] - out5[2]) / (std::log(std::log(4.0 / 3.0)) - std::log(std::log(4.0)));
+    *b_out = b;
+    *a_out = out5[1] - b * std::log(std::log(2.0));
+}
+
 // emukit MaxValueEntropySearch.update_parameters' model.predict(grid) and _fit_gumbel: the grid's predictive mean and
 // variance (noise included) as cbo_gp_predict leaves them on the device, then the three bisections in one launch on them;
 // only the quantiles (and, when asked, the mean and variance) come back
@@ -3070,7 +3154,7 @@ extern "C" int cbo_gp_mes_gumbel(cbo_gp *g, int64_t m, const double *Xg, const d
     int rc = posterior_of_host_points(g, m, Xg, pm, pv, 1, &k);
     if (rc != CBO_OK) return rc;
     // part_val / part_idx: free device scratch between sweeps (2048 entries each)
-    launch_gumbel_quantiles(c->stream, c->mean, c->var, m, c->part_val, c->part_idx);
+    launch_gumbel_quantiles(c->stream, GumbelSet{c->mean, c->var, m}, nullptr, 1, c->part_val, c->part_idx);
     HIP_TRY(hipGetLastError());
     double out[5];
     int64_t status[3];
@@ -3079,24 +3163,132 @@ extern "C" int cbo_gp_mes_gumbel(cbo_gp *g, int64_t m, const double *Xg, const d
     rc = copy_posterior_out(c, k, nullptr, mean_out, var_out);
     if (rc != CBO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int j = 0; j < 3; ++j) {
-        char msg[160];
-        if (status[j] == 1) {
-            std::snprintf(msg, sizeof msg, "Gumbel fit: f(a) and f(b) must have different signs (quantile %.2f on "
-                          "[%.17g, %.17g])", 0.25 * (j + 1), out[3], out[4]);
-            return fail(CBO_ERR_INVALID, msg);
-        }
-        if (status[j] != 0) {
-            std::snprintf(msg, sizeof msg, "Gumbel fit: bisection of quantile %.2f failed to converge after 10000 "
-                          "iterations", 0.25 * (j + 1));
-            return fail(CBO_ERR_INVALID, msg);
-        }
+    const std::string err = gumbel_failure(out, status);
+    if (!err.empty()) return fail(CBO_ERR_INVALID, err);
+    gumbel_parameters(out, quantiles3, a_out, b_out);
+    if (c->profiling) c->timers.n_sweep += 1;
+    return CBO_OK;
+}
+
+// cbo_gp_mes_gumbel for every set of a trial: the grids of the fp64 models of at most 128 observations are
+// predicted by small_sets_kernel<kPredictKind> -- no fit; one launch, two from kSmallTwoPhaseFromBlocks blocks per set on --
+// into one mean / var workspace, every set's points one after the other; every other model is fitted if need be and
+// predicted by the general path into the same workspace; then ONE launch of the bisections for all sets and ONE
+// synchronisation.  A small model whose record reports a non-positive pivot is fitted and fitted a Gumbel as the single
+// call does it, afterwards.
+extern "C" int cbo_gp_mes_gumbel_sets(int n_sets, cbo_gp *const *gps, cbo_cands *const *grids, double *quantiles, double *a,
+                                      double *b)
+{
+    if (n_sets <= 0 || n_sets > 65535) return fail(CBO_ERR_INVALID, "n_sets must be in 1..65535");
+    if (!gps || !grids || !quantiles || !a || !b) return fail(CBO_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < n_sets; ++i) {
+        const int rc = check_sweep_args(gps[i], grids[i], CBO_TASK_MIN);
+        if (rc != CBO_OK) return rc;
+        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
+        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
+        if (grids[i]->m <= 0) return fail(CBO_ERR_INVALID, "the Gumbel grid of set " + std::to_string(i) + " is empty");
     }
-    for (int j = 0; j < 3; ++j) quantiles3[j] = out[j];
-    // _fit_gumbel: b = (q25 - q75) / (log(log(4/3)) - log(log(4))), a = q50 - b log(log(2))
-    const double b = (out[0] - out[2]) / (std::log(std::log(4.0 / 3.0)) - std::log(std::log(4.0)));
-    *b_out = b;
-    *a_out = out[1] - b * std::log(std::log(2.0));
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int64_t> off((size_t)n_sets);
+    int64_t total = 0;
+    for (int i = 0; i < n_sets; ++i) { off[(size_t)i] = total; total += grids[i]->m; }
+    if (2 * sizeof(double) * (size_t)total > c->max_ws_bytes)
+        return fail(CBO_ERR_UNSUPPORTED, "the Gumbel grids' mean / variance workspace (" + std::to_string(total) +
+                                             " points) exceeds the workspace limit: raise CBO_HIP_WORKSPACE_MB");
+    int rc = grow(c, c->gumbel_mean, (size_t)total);
+    if (rc == CBO_OK) rc = grow(c, c->gumbel_var, (size_t)total);
+    if (rc == CBO_OK) rc = grow(c, c->gumbel_out, 5 * (size_t)n_sets);
+    if (rc == CBO_OK) rc = grow(c, c->gumbel_status, 3 * (size_t)n_sets);
+    if (rc == CBO_OK) rc = grow(c, c->gumbel_sets_host, (size_t)n_sets);
+    if (rc != CBO_OK) return rc;
+    std::vector<int> small;
+    int64_t blocks_max = 1;
+    for (int i = 0; i < n_sets; ++i) {
+        if (!small_sweep_model(gps[i]) || (grids[i]->m + 63) / 64 > 65535) continue;
+        small.push_back(i);
+        const int64_t bl = (grids[i]->m + 63) / 64;
+        if (bl > blocks_max) blocks_max = bl;
+    }
+    // (1) the predict: the small models' grids in the one-workgroup launch ...
+    const int ns = (int)small.size();
+    int seq = 0;
+    if (ns > 0) {
+        const int blocks = (int)blocks_max;
+        rc = ensure_small_buffers(c, ns, blocks);
+        if (rc == CBO_OK) rc = grow(c, c->aux_host, ns < 32 ? (size_t)32 : (size_t)ns);
+        if (rc != CBO_OK) return rc;
+        for (int j = 0; j < ns; ++j) {
+            cbo_gp *g = gps[small[(size_t)j]];
+            cbo_cands *k = grids[small[(size_t)j]];
+            rc = prepare_cands(g, k);
+            if (rc != CBO_OK) return rc;
+            cbo_small_set &st = c->sets_host[j];
+            fill_small_model(st, g);
+            fill_small_cands(st, g, k);
+            st.task = CBO_TASK_MIN; st.y_best = 0.0; st.ei_jitter = 0.0; st.cost = 1.0;
+            c->aux_host[j] = cbo_small_aux{off[(size_t)small[(size_t)j]], 0};
+        }
+        SmallAux aux;
+        aux.per_set = c->aux_host;
+        aux.mean_out = c->gumbel_mean;
+        aux.var_out = c->gumbel_var;
+        if (++c->small_seq == 0) c->small_seq = 1;
+        seq = c->small_seq;
+        launch_small_sets(c->stream, kPredictKind, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val,
+                          c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq, aux);
+        HIP_TRY(hipGetLastError());
+    }
+    // ... every other model's on the general path, into the same workspace
+    std::vector<char> is_small((size_t)n_sets, 0);
+    for (int j = 0; j < ns; ++j) is_small[(size_t)small[(size_t)j]] = 1;
+    auto general_predict = [&](int i) -> int {
+        int r = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
+        if (r == CBO_OK) r = posterior_of_set(gps[i], grids[i], 1);
+        if (r != CBO_OK) return r;
+        const size_t bytes = sizeof(double) * (size_t)grids[i]->m;
+        HIP_TRY(hipMemcpyAsync(c->gumbel_mean + off[(size_t)i], c->mean, bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->gumbel_var + off[(size_t)i], c->var, bytes, hipMemcpyDeviceToDevice, c->stream));
+        return CBO_OK;
+    };
+    for (int i = 0; i < n_sets; ++i) {
+        if (is_small[(size_t)i]) continue;
+        rc = general_predict(i);
+        if (rc != CBO_OK) return rc;
+    }
+    // (2) the bisections of every set, then the call's one synchronisation
+    for (int i = 0; i < n_sets; ++i)
+        c->gumbel_sets_host[i] = GumbelSet{c->gumbel_mean + off[(size_t)i], c->gumbel_var + off[(size_t)i], grids[i]->m};
+    std::vector<double> out(5 * (size_t)n_sets);
+    std::vector<int64_t> status(3 * (size_t)n_sets);
+    auto bisect = [&](int first, int count) -> int {
+        launch_gumbel_quantiles(c->stream, GumbelSet{}, c->gumbel_sets_host + first, count, c->gumbel_out + 5 * first,
+                                c->gumbel_status + 3 * first);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out.data() + 5 * first, c->gumbel_out + 5 * first, sizeof(double) * 5 * (size_t)count,
+                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(status.data() + 3 * first, c->gumbel_status + 3 * first, sizeof(int64_t) * 3 * (size_t)count,
+                               hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return CBO_OK;
+    };
+    rc = bisect(0, n_sets);
+    if (rc != CBO_OK) return rc;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int j = 0; j < ns; ++j) {
+        if (c->small_out[j].seq != seq) return fail(CBO_ERR_HIP, "multi-set Gumbel fit: no result record");
+        if (c->small_out[j].info == 0) continue;
+        // not positive definite as assembled: the general path's jitchol ladder, and this set's bisections again
+        const int i = small[(size_t)j];
+        rc = general_predict(i);
+        if (rc == CBO_OK) rc = bisect(i, 1);
+        if (rc != CBO_OK) return rc;
+    }
+    for (int i = 0; i < n_sets; ++i) {
+        const std::string err = gumbel_failure(out.data() + 5 * i, status.data() + 3 * i);
+        if (!err.empty()) return fail(CBO_ERR_INVALID, "set " + std::to_string(i) + ": " + err);
+    }
+    for (int i = 0; i < n_sets; ++i) gumbel_parameters(out.data() + 5 * i, quantiles + 3 * i, a + i, b + i);
     if (c->profiling) c->timers.n_sweep += 1;
     return CBO_OK;
 }

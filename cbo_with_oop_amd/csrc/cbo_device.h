@@ -359,4 +359,47 @@ __device__ __forceinline__ double pointwise_of(double mean, double var, const Ac
     return fma(fma(-qv, p.cost, v), rc, qv);
 }
 
+// ---- max-value entropy search: the epilogue of mes_acq_kernel (kernels_mes.hip) and of small_sets_kernel<kMesKind>
+// (kernels_sets.hip) -- one definition, so the multi-set sweep returns cbo_acq_sweep_mes' bits.
+// One sample's term of emukit's evaluate: -gamma pdf(gamma) / (2 minus_cdf) - log(minus_cdf).  The density and cephes ndtr
+// share one exponential (ndtr_with_exp); 1 - ndtr(gamma) is formed as written, not as ndtr(-gamma).
+__device__ __forceinline__ double mes_term(double min_k, double mean, double fsd)
+{
+#pragma clang fp contract(off)
+    const double g = (min_k - mean) / fsd;                           // IEEE division, as numpy
+    const double e = exp_nonpositive(-(g * g) / 2.0);
+    const double pdf = e * 0.3989422804014327;                      // scipy _norm_pdf: exp(-x**2/2)/sqrt(2 pi), to an ulp
+    double mc = 1.0 - ndtr_with_exp(g, e);
+    mc = select_f64(mc < 1e-10, 1e-10, mc);                         // np.clip(minus_cdf, 1e-10, 1) (NaN stays NaN; mc <= 1)
+    return ((-g) * pdf) / (2.0 * mc) - log(mc);
+}
+
+// mean over the k samples in numpy's order for a row of an (M, K) array reduced along its last axis (np.mean(axis=1):
+// pairwise_sum): below 8 terms one running sum from 0; from 8 on, eight accumulators over the leading multiple of 8, combined
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the rest one by one; then / K
+// P: mins (an array or a pointer to the samples, wherever they live), k (uniform) and cost -- MesParams, or MesSetParams
+template <class P>
+__device__ __forceinline__ double mes_of(double mean, double var, const P &p)
+{
+#pragma clang fp contract(off)
+    double fsd = sqrt(var);                                          // IEEE square root (np.sqrt)
+    fsd = select_f64(fsd < 1e-10, 1e-10, fsd);                      // np.maximum(fsd, 1e-10); NaN stays NaN
+    const int full = p.k - p.k % 8;
+    double r[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int k = 0;
+    for (; k < full; k += 8) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + mes_term(p.mins[k + j], mean, fsd);
+    }
+    double s = (p.k < 8) ? 0.0 : ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; k < p.k; ++k) s = s + mes_term(p.mins[k], mean, fsd);
+    return (s / (double)p.k) / p.cost;
+}
+// the samples of one set of the multi-set sweep: in LDS, copied there from the call's table
+struct MesSetParams {
+    const double *mins;
+    int k;
+    double cost;
+};
+
 }  // namespace cbo

@@ -335,8 +335,26 @@ constexpr int kSmallTwoPhaseFromBlocks = 12;
 // CBO_ACQ_LCB / _PI / _VAR / _MPEI; the descriptors' ei_jitter then carries the kind's parameter, y_best PI's incumbent
 // (the plug-in EI forms its own inside the launch)
 constexpr int kEiKind = 0;
+// Two further kinds, internal (beyond CBO_ACQ_*), read what the descriptor has no room for through `aux`:
+//   kMesKind      max-value entropy search's epilogue (mes_of, so cbo_acq_sweep_mes' bits): set s scores against the
+//                 per_set[s].count (1..kMesMaxSamples) Gumbel samples data[per_set[s].off ...]; task is 'min';
+//   kPredictKind  no acquisition and no arg-max: the predictive mean and variance (noise included) of candidate c of set s
+//                 go to mean_out / var_out[per_set[s].off + c] (cbo_gp_mes_gumbel_sets' grids); the record carries the
+//                 status word alone.
+// per_set and data may be pinned host memory (device-mapped), like the descriptors.
+constexpr int kMesKind = 5;
+constexpr int kPredictKind = 6;
+struct cbo_small_aux {
+    int64_t off, count;
+};
+struct SmallAux {
+    const cbo_small_aux *per_set = nullptr;
+    const double *data = nullptr;
+    double *mean_out = nullptr, *var_out = nullptr;
+};
 void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
-                       double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq);
+                       double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
+                       const SmallAux &aux = SmallAux());
 // the same launch with the constrained epilogue (kernels_sets_con.hip, small_sets_con_kernel): `pairs` holds
 // one descriptor per (model, candidate set) pair, a set's pairs consecutive with the objective first; a constraint's value,
 // jitter and sense ride in y_best, ei_jitter and task; pairs[s].pad_ = index of set s's first pair.  max_pairs = the most
@@ -411,7 +429,14 @@ void launch_mes_acq(hipStream_t s, const double *q, const double *mu, const doub
 // The three bisections of emukit's _fit_gumbel (vals 0.25, 0.5, 0.75) on the predictive mean / variance of m grid points,
 // one workgroup each: out[0..3) the quantiles, out[3] = left, out[4] = right; status[j] = 0 converged, 1 the bracket does
 // not change sign (scipy's ValueError), 2 no convergence within maxiter (scipy's RuntimeError).
-void launch_gumbel_quantiles(hipStream_t s, const double *mean, const double *var, int64_t m, double *out, int64_t *status);
+// n_sets sets in one launch (a (3, n_sets) grid): set s reads its (mean, var, m) from table[s] (device-visible) and writes
+// out[5 s ..], status[3 s ..]; table == nullptr: one set, `one`, which travels in the kernel arguments.
+struct GumbelSet {
+    const double *mean, *var;
+    int64_t m;
+};
+void launch_gumbel_quantiles(hipStream_t s, const GumbelSet &one, const GumbelSet *table, int n_sets, double *out,
+                             int64_t *status);
 // ---- constrained acquisition (kernels_con.hip) ------------------------------------------------------------------
 // EI times probabilities of feasibility over a cost, from the q, mu of several (model, candidate set) pairs at once.  The
 // pointer table travels in the kernel arguments: model 0 is the objective when has_objective, every other one a constraint.

@@ -14,36 +14,7 @@
 
 namespace cbo {
 
-// One sample's term of emukit's evaluate: -gamma pdf(gamma) / (2 minus_cdf) - log(minus_cdf).  The density and cephes ndtr
-// share one exponential (ndtr_with_exp); 1 - ndtr(gamma) is formed as written, not as ndtr(-gamma).
-__device__ __forceinline__ double mes_term(double min_k, double mean, double fsd)
-{
-    const double g = (min_k - mean) / fsd;                           // IEEE division, as numpy
-    const double e = exp_nonpositive(-(g * g) / 2.0);
-    const double pdf = e * 0.3989422804014327;                      // scipy _norm_pdf: exp(-x**2/2)/sqrt(2 pi), to an ulp
-    double mc = 1.0 - ndtr_with_exp(g, e);
-    mc = select_f64(mc < 1e-10, 1e-10, mc);                         // np.clip(minus_cdf, 1e-10, 1) (NaN stays NaN; mc <= 1)
-    return ((-g) * pdf) / (2.0 * mc) - log(mc);
-}
-
-// mean over the k samples in numpy's order for a row of an (M, K) array reduced along its last axis (np.mean(axis=1):
-// pairwise_sum): below 8 terms one running sum from 0; from 8 on, eight accumulators over the leading multiple of 8, combined
-// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the rest one by one; then / K
-__device__ __forceinline__ double mes_of(double mean, double var, const MesParams &p)
-{
-    double fsd = sqrt(var);                                          // IEEE square root (np.sqrt)
-    fsd = select_f64(fsd < 1e-10, 1e-10, fsd);                      // np.maximum(fsd, 1e-10); NaN stays NaN
-    const int full = p.k - p.k % 8;
-    double r[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    int k = 0;
-    for (; k < full; k += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = r[j] + mes_term(p.mins[k + j], mean, fsd);
-    }
-    double s = (p.k < 8) ? 0.0 : ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; k < p.k; ++k) s = s + mes_term(p.mins[k], mean, fsd);
-    return (s / (double)p.k) / p.cost;
-}
+// (mes_term / mes_of, the epilogue, are cbo_device.h's: the multi-set sweep of kernels_sets.hip shares them)
 
 // acq_kernel's structure (kernels_acq.hip): two consecutive candidates per lane and iteration, the next iteration's operands
 // and the previous one's results issued together right behind the iteration's only wait.  Unlike the EI pass this one is
@@ -183,16 +154,24 @@ __device__ double gumbel_log_sum(const double *__restrict__ mean, const double *
     return t;
 }
 
-// One workgroup per quantile (val = 0.25, 0.5, 0.75).  left = min(fmean - 5 fsd), right = max(fmean + 5 fsd), then scipy's
+// One workgroup per quantile (val = 0.25, 0.5, 0.75) and set.  left = min(fmean - 5 fsd), right = max(fmean + 5 fsd), then scipy's
 // bisect (scipy/optimize/Zeros/bisect.c) with xtol = 2e-12, rtol = 4 eps, maxiter = 10000, on f(x) = probf(x) - val:
 //     fa = f(xa), fb = f(xb); fa fb > 0: error; fa == 0: xa; fb == 0: xb; dm = xb - xa;
 //     repeat: dm *= .5; xm = xa + dm; fm = f(xm); if fm fa >= 0: xa = xm; if fm == 0 or |dm| < xtol + rtol |xm|: xm
 // Every thread holds the whole state and takes the same decisions from the same sums: the control flow is uniform.
-__global__ __launch_bounds__(kGumbelThreads) void gumbel_quantiles_kernel(const double *__restrict__ mean,
-                                                                          const double *__restrict__ var, int64_t m,
+// blockIdx.y is the set: its (mean, var, m) come from table[blockIdx.y] -- or, for the single fit, from the kernel
+// arguments -- and its five doubles and three status words lie at out + 5 blockIdx.y, status + 3 blockIdx.y.
+__global__ __launch_bounds__(kGumbelThreads) void gumbel_quantiles_kernel(const GumbelSet one,
+                                                                          const GumbelSet *__restrict__ table,
                                                                           double *__restrict__ out,
                                                                           int64_t *__restrict__ status)
 {
+    const GumbelSet gs = table ? table[blockIdx.y] : one;             // (uniform)
+    const double *__restrict__ mean = gs.mean;
+    const double *__restrict__ var = gs.var;
+    const int64_t m = gs.m;
+    out += 5 * blockIdx.y;
+    status += 3 * blockIdx.y;
     __shared__ double part[2][kGumbelWaves];
     __shared__ double lr[2][kGumbelWaves];
     int buf = 0;
@@ -250,9 +229,11 @@ __global__ __launch_bounds__(kGumbelThreads) void gumbel_quantiles_kernel(const 
     }
 }
 
-void launch_gumbel_quantiles(hipStream_t s, const double *mean, const double *var, int64_t m, double *out, int64_t *status)
+void launch_gumbel_quantiles(hipStream_t s, const GumbelSet &one, const GumbelSet *table, int n_sets, double *out,
+                             int64_t *status)
 {
-    hipLaunchKernelGGL(gumbel_quantiles_kernel, dim3(3), dim3(kGumbelThreads), 0, s, mean, var, m, out, status);
+    hipLaunchKernelGGL(gumbel_quantiles_kernel, dim3(3, (unsigned)(table ? n_sets : 1)), dim3(kGumbelThreads), 0, s, one,
+                       table, out, status);
 }
 
 }  // namespace cbo

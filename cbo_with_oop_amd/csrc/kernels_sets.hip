@@ -18,6 +18,8 @@ namespace cbo {
 static_assert(sizeof(SmallShared) + 128 * sizeof(double) + 4 * sizeof(double) + 4 * sizeof(int) + sizeof(double) +
                       sizeof(int) <= 163840,
               "the workgroup's static LDS (plug-in means, their reduction, the ticket flag) beside SmallShared: one CU");
+static_assert(sizeof(SmallShared) + kMesMaxSamples * sizeof(double) + sizeof(int) <= 163840,
+              "the workgroup's static LDS (the set's Gumbel samples, the ticket flag) beside SmallShared: one CU");
 
 // The plug-in incumbent of the workgroup's model: min (task 'min') or max of the posterior means at the model's own n <= 128
 // points, NaN if any of them is.  The points are already in LDS in candidate layout (xs, sq, sv); they go through K*, the tile
@@ -88,6 +90,9 @@ __device__ __forceinline__ double small_plugin_incumbent(const SmallShared &sh, 
 
 // KIND: kEiKind, or CBO_ACQ_LCB, _PI, _VAR or _MPEI (compile time: one kind's arithmetic per instantiation).  For a point-wise
 // kind the descriptor's ei_jitter carries the kind's parameter (beta; PI's and the plug-in EI's jitter), y_best PI's incumbent.
+// kMesKind: max-value entropy search -- the set's Gumbel samples come from aux's table (fetched with the
+// candidates, ahead of the factorisation; parked in LDS behind K*'s barrier), the epilogue is mes_of.  kPredictKind: the
+// epilogue stores mean and variance at the set's offset in aux's workspace; no arg-max, the record carries the status word.
 // phases 3: every workgroup factors the model itself, into its own scratch slot; 1: one workgroup per set factors it into
 // the set's slot 0, nothing else; 2: the set's slot 0 holds the factor.
 template <int KIND, bool BYVAL>
@@ -95,7 +100,8 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
                                                          double *scratch, int blocks_per_set,
                                                          double *__restrict__ part_val, int64_t *__restrict__ part_idx,
                                                          int *__restrict__ info, int *__restrict__ ticket,
-                                                         cbo_small_result *__restrict__ out, int seq, int phases)
+                                                         cbo_small_result *__restrict__ out, int seq, int phases,
+                                                         const SmallAux aux)
 {
     __shared__ int last_flag;
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -124,6 +130,12 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
     const int64_t c = (int64_t)blk * 64 + wave * 16 + lc;
     double xc[CBO_MAX_DIM], csq, csv, cpm_c, cpv_c;
     small_fetch_cand(st, c, xc, csq, csv, cpm_c, cpv_c);
+    [[maybe_unused]] cbo_small_aux ax{};
+    [[maybe_unused]] double my_min = 0.0;                          // thread t < count: the set's sample t
+    if constexpr (KIND == kMesKind || KIND == kPredictKind) ax = aux.per_set[set];
+    if constexpr (KIND == kMesKind) {
+        if (tid < (int)ax.count) my_min = aux.data[ax.off + tid];
+    }
 
     double iv[8][4], zr[8][4];
     small_model_factor(sh, st, tiles, Us, invs, &info[set], iv, zr, phases, true);
@@ -142,6 +154,12 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
     const double inv_l2 = 1.0 / (st.lengthscale * st.lengthscale);
     d4 acc[8];
     small_kstar_tiles_of(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc);
+    [[maybe_unused]] double *mes_mins = nullptr;
+    if constexpr (KIND == kMesKind) {
+        __shared__ double mins_s[kMesMaxSamples];
+        if (tid < kMesMaxSamples) mins_s[tid] = my_min;
+        mes_mins = mins_s;
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -154,10 +172,21 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
     if (kq == 0 && c < st.m) {
         double mean, var;
         posterior_of(qacc, macc, cpm_c, cpv_c, st.sv != nullptr, p, mean, var);
-        bv = (KIND == kEiKind || KIND == CBO_ACQ_MPEI) ? acquisition_of(mean, var, p) : pointwise_of<KIND>(mean, var, p);
-        bi = c + st.index_offset;
+        if constexpr (KIND == kPredictKind) {
+            aux.mean_out[ax.off + c] = mean;
+            aux.var_out[ax.off + c] = var;
+        } else {
+            if constexpr (KIND == kMesKind) {
+                const MesSetParams mp{mes_mins, (int)ax.count, p.cost};
+                bv = mes_of(mean, var, mp);
+            } else {
+                bv = (KIND == kEiKind || KIND == CBO_ACQ_MPEI) ? acquisition_of(mean, var, p)
+                                                               : pointwise_of<KIND>(mean, var, p);
+            }
+            bi = c + st.index_offset;
+        }
     }
-    small_block_argmax(sh, lane, wave, bv, bi);
+    if constexpr (KIND != kPredictKind) small_block_argmax(sh, lane, wave, bv, bi);
     small_set_finish(bv, bi, set, slot, blocks_per_set, part_val, part_idx, info, ticket, out, seq, &last_flag);
 }
 
@@ -166,14 +195,14 @@ size_t small_sets_scratch_doubles(int n_sets, int blocks_per_set) { return (size
 template <int KIND, bool BYVAL>
 static void launch_small_sets_as(hipStream_t s, const SmallSetArgs &args, const cbo_small_set *sets, int n_sets,
                                  int blocks_per_set, double *scratch, double *part_val, int64_t *part_idx, int *info,
-                                 int *ticket, cbo_small_result *out, int seq)
+                                 int *ticket, cbo_small_result *out, int seq, const SmallAux &aux)
 {
     static std::atomic<unsigned long long> opted{0};
     small_lds_opt_in(reinterpret_cast<const void *>(small_sets_kernel<KIND, BYVAL>), opted);
     const dim3 grid((unsigned)blocks_per_set, (unsigned)n_sets);
     auto launch = [&](const dim3 &g, int phases) {
         hipLaunchKernelGGL((small_sets_kernel<KIND, BYVAL>), g, dim3(256), sizeof(SmallShared), s, args, sets, scratch,
-                           blocks_per_set, part_val, part_idx, info, ticket, out, seq, phases);
+                           blocks_per_set, part_val, part_idx, info, ticket, out, seq, phases, aux);
     };
     if (blocks_per_set >= kSmallTwoPhaseFromBlocks) {
         launch(dim3(1u, (unsigned)n_sets), 1);
@@ -184,21 +213,24 @@ static void launch_small_sets_as(hipStream_t s, const SmallSetArgs &args, const 
 }
 
 void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
-                       double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq)
+                       double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
+                       const SmallAux &aux)
 {
     SmallSetArgs args{};
     const bool byval = n_sets <= kSmallByValue;
     if (byval) std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_sets);
 #define CBO_LAUNCH_KIND(K)                                                                                              \
     (byval ? launch_small_sets_as<K, true>(s, args, sets, n_sets, blocks_per_set, scratch, part_val, part_idx, info,     \
-                                           ticket, out, seq)                                                            \
+                                           ticket, out, seq, aux)                                                       \
            : launch_small_sets_as<K, false>(s, args, sets, n_sets, blocks_per_set, scratch, part_val, part_idx, info,   \
-                                            ticket, out, seq))
+                                            ticket, out, seq, aux))
     switch (kind) {
         case CBO_ACQ_LCB: CBO_LAUNCH_KIND(CBO_ACQ_LCB); break;
         case CBO_ACQ_PI: CBO_LAUNCH_KIND(CBO_ACQ_PI); break;
         case CBO_ACQ_VAR: CBO_LAUNCH_KIND(CBO_ACQ_VAR); break;
         case CBO_ACQ_MPEI: CBO_LAUNCH_KIND(CBO_ACQ_MPEI); break;
+        case kMesKind: CBO_LAUNCH_KIND(kMesKind); break;
+        case kPredictKind: CBO_LAUNCH_KIND(kPredictKind); break;
         default: CBO_LAUNCH_KIND(kEiKind); break;
     }
 #undef CBO_LAUNCH_KIND

@@ -37,6 +37,47 @@ def gumbel_mins(num_samples, a, b):
     return np.log(-np.log(1 - u)) * b + a
 
 
+def mes_sets_parameters(models, spaces, num_samples=10, grid_size=5000):
+    """``MaxValueEntropySearch.update_parameters`` for every exploration set of a trial with ONE device call for all the
+    Gumbel fits (``cbo_gp_mes_gumbel_sets``).  Returns ``(gumbels, mins)``, one entry per set:
+    ``(q25, q50, q75, a, b)`` and the ``num_samples`` minima drawn from that Gumbel.
+
+    The draws on numpy's global generator come in a fixed order:
+      1. ``gumbel_grid(space_bounds(spaces[i]), grid_size, models[i].X)`` for the sets 0..S-1 in order;
+      2. the one ``cbo_gp_mes_gumbel_sets`` call (it draws nothing);
+      3. ``gumbel_mins(num_samples, a[i], b[i])`` for the sets 0..S-1 in order.
+    (Per-set ``update_parameters`` calls interleave grid and minima set by set: the same seed gives other numbers.)
+    The grids' ``CandidateGrid``s are built for this call and closed after it: their points change every trial.  Models of
+    at most 128 observations on the fp64 path need no fit; the others are fitted inside the call if they were not."""
+    from .utils import space_bounds
+    s = len(models)
+    if len(spaces) != s:
+        raise ValueError(f"spaces must have one entry per exploration set ({s}), not {len(spaces)}")
+    if not 0 < int(num_samples) <= MAX_SAMPLES:
+        raise ValueError(f"num_samples must be in 1..{MAX_SAMPLES}")
+    if int(grid_size) < 1:
+        raise ValueError("grid_size must be at least 1")
+    points = [gumbel_grid(space_bounds(spaces[i]), grid_size, models[i].X) for i in range(s)]
+    quantiles, a, b = np.empty((s, 3)), np.empty(s), np.empty(s)
+    grids = []
+    try:
+        for i in range(s):
+            grids.append(CandidateGrid(points[i], models[i]))
+        gps = (ctypes.c_void_p * s)(*[m._handle for m in models])
+        cds = (ctypes.c_void_p * s)(*[g._handle for g in grids])
+        _lib.check(_lib.load().cbo_gp_mes_gumbel_sets(s, gps, cds, _lib.dptr(quantiles), _lib.dptr(a), _lib.dptr(b)))
+    finally:
+        for g in grids:
+            g.close()
+    for m in models:
+        if not m.small:
+            m.stale = False             # (the general path fitted it on the way)
+    gumbels = [(float(quantiles[i, 0]), float(quantiles[i, 1]), float(quantiles[i, 2]), float(a[i]), float(b[i]))
+               for i in range(s)]
+    mins = [gumbel_mins(num_samples, a[i], b[i]) for i in range(s)]
+    return gumbels, mins
+
+
 class MaxValueEntropySearch:
     def __init__(self, model, space, num_samples=10, grid_size=5000):
         """emukit's signature.  ``space``: an emukit ParameterSpace or a list of (lo, hi), as ``space_bounds`` accepts.

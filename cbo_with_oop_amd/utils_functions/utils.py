@@ -234,15 +234,35 @@ def _acquisition_for(name, model, current_global_best, task, space, param=None):
 def sets_acquisition(acquisition="EI", acquisition_param=None):
     """(name, parameter) of the acquisition a multi-set sweep scores with, checked on the host before any device call:
     ``"EI"`` (no parameter: today's call, ``None``), ``"LCB"`` (beta, default 1, finite and not negative), ``"PI"`` and
-    ``"MPEI"`` (the jitter, default 0, finite), ``"VAR"`` (no parameter: 0 travels).  Anything else raises ``ValueError``.
+    ``"MPEI"`` (the jitter, default 0, finite), ``"VAR"`` (no parameter: 0 travels), ``"MES"`` with a pair of ints
+    ``(num_samples, grid_size)``, ``num_samples`` in 1..64, ``grid_size`` at least 1 (the parameter returned is that pair).
+    Anything else raises ``ValueError`` -- a bare ``"MES"`` too: this function never answered for it and has no default for
+    it; ``sets_acquisition_or_default`` -- what ``find_next_y_points``, ``CBOAcquisitionPath`` and ``CBO`` call -- puts
+    emukit's defaults (10 samples, a Gumbel grid of 5000) in the place of a ``None`` first.
     An answer of this function is accepted in the place of the name (and returned as it is)."""
     import math
     if type(acquisition) is tuple and acquisition_param is None and len(acquisition) == 2:
         name, param = acquisition                 # an earlier answer of this function (a path keeps its own): checked again
         sets_acquisition(name, None if name in ("EI", "VAR") else param)
         return acquisition
-    if not isinstance(acquisition, str) or acquisition not in ("EI",) + POINTWISE_ACQUISITIONS:
-        raise ValueError(f"acquisition must be 'EI', 'LCB', 'PI', 'MPEI' or 'VAR' in a multi-set sweep, not {acquisition!r}")
+    if not isinstance(acquisition, str) or acquisition not in ("EI", "MES") + POINTWISE_ACQUISITIONS:
+        raise ValueError("acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR' in a multi-set sweep, "
+                         f"not {acquisition!r}")
+    if acquisition == "MES":
+        if acquisition_param is None:
+            raise ValueError("acquisition must be 'EI', 'LCB', 'PI', 'MPEI' or 'VAR' -- or 'MES' with acquisition_param = "
+                             "(num_samples, grid_size) -- in a multi-set sweep")
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))      # noqa: E731
+        if not isinstance(acquisition_param, (tuple, list)) or len(acquisition_param) != 2 \
+                or not all(is_int(v) for v in acquisition_param):
+            raise ValueError("acquisition_param (num_samples, grid_size) must be a pair of ints, "
+                             f"not {acquisition_param!r}")
+        num_samples, grid_size = int(acquisition_param[0]), int(acquisition_param[1])
+        if not 1 <= num_samples <= 64:
+            raise ValueError(f"acquisition_param: num_samples must be in 1..64, not {num_samples}")
+        if grid_size < 1:
+            raise ValueError(f"acquisition_param: grid_size must be at least 1, not {grid_size}")
+        return "MES", (num_samples, grid_size)
     if acquisition == "EI":
         if acquisition_param is not None:
             raise ValueError("acquisition_param: the multi-set EI takes none (its jitter is the reference's 0)")
@@ -263,6 +283,17 @@ def sets_acquisition(acquisition="EI", acquisition_param=None):
     return acquisition, param
 
 
+MES_DEFAULTS = (10, 5000)          # emukit's MaxValueEntropySearch: num_samples, grid_size
+
+
+def sets_acquisition_or_default(acquisition="EI", acquisition_param=None):
+    """``sets_acquisition`` with emukit's defaults for ``"MES"`` where no parameter was given: what the callers that take
+    ``acquisition`` / ``acquisition_param`` from a user (``find_next_y_points``, ``CBOAcquisitionPath``, ``CBO``) call."""
+    if isinstance(acquisition, str) and acquisition == "MES" and acquisition_param is None:
+        acquisition_param = MES_DEFAULTS
+    return sets_acquisition(acquisition, acquisition_param)
+
+
 def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
     """``find_next_y_point(batch_size=B)``: (y (B,1), x (B,d)) of one ``sweep_batch``.  y[t] is the pick's acquisition over
     the point's own cost where variable costs make that differ from the batch's (utils.py:36): pick 0 by the single-point
@@ -279,7 +310,7 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
 
 
 def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
-                       acquisition="EI", acquisition_param=None, hyper_samples=None, constraints=None):
+                       acquisition="EI", acquisition_param=None, hyper_samples=None, spaces=None, constraints=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -306,10 +337,24 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     the cost, in the same one call (``cbo_acq_sweep_sets_hyper``) -- per set what
     ``find_next_y_point(hyper_samples=rows_s)`` returns.  A wrong length, a bad shape, more than 256 rows, non-finite or
     non-positive entries, another ``acquisition`` than ``"EI"``, non-empty ``constraints`` and ``raw=True`` raise
-    ``ValueError`` before any device call.  ``None`` takes exactly today's calls."""
+    ``ValueError`` before any device call.  ``None`` takes exactly today's calls.
+    ``acquisition="MES"`` with ``acquisition_param`` (``None``: 10 samples, a Gumbel grid of 5000; or ``(num_samples,
+    grid_size)``) and ``spaces`` (one entry per set, as ``space_bounds`` accepts): emukit's ``MaxValueEntropySearch(model,
+    space) / Cost`` for every set in two device calls -- ``max_value_entropy.mes_sets_parameters`` (every
+    set's Gumbel fit, ``cbo_gp_mes_gumbel_sets``; it draws from numpy's global generator in the order documented there),
+    then ``cbo_acq_sweep_sets_mes``.  ``task`` other than ``"min"``, missing ``spaces``, ``raw=True``, non-empty
+    ``constraints`` and ``hyper_samples`` raise ``ValueError`` before any device call."""
     import ctypes
     from .. import _lib
-    kind = sets_acquisition(acquisition, acquisition_param)
+    kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    if kind[0] == "MES":
+        if task != "min":
+            raise ValueError("acquisition='MES' minimises: task must be 'min'")
+        if spaces is None or not hasattr(spaces, "__len__") or len(spaces) != len(models):
+            raise ValueError(f"acquisition='MES' draws its Gumbel grids from the sets' spaces: spaces must have one entry per "
+                             f"exploration set ({len(models)})")
+        if raw:
+            raise ValueError("acquisition='MES' is not defined across several ranks (raw=True)")
     constraints = checked_set_constraints(constraints, len(models), kind, raw)
     hyper_rows = checked_set_hyper_samples(hyper_samples, models, kind, constraints, raw)
     if kind[0] != "EI" and task not in _lib.TASK_CODE:
@@ -357,6 +402,17 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
                                                         idxs.ctypes.data_as(_lib.c_int64_p)))
     elif constraints is not None:
         _sweep_sets_constrained(st, models, grids, constraints, task)
+    elif kind[0] == "MES":
+        from .max_value_entropy import mes_sets_parameters
+        st.pop("trial_args", None)               # (a trial step with MES takes the three-call route)
+        _, mins = mes_sets_parameters(models, spaces, kind[1][0], kind[1][1])
+        # (the entry keeps the sample arrays and the pointer array alive; winners_to_points re-evaluates against them)
+        st["mes_mins"] = [_lib.as_f64(m) for m in mins]
+        st["mes_args"] = ((ctypes.c_int * s)(*[m.shape[0] for m in st["mes_mins"]]),
+                          (ctypes.c_void_p * s)(*[m.ctypes.data for m in st["mes_mins"]]))
+        _lib.check(_lib.load().cbo_acq_sweep_sets_mes(s, st["gps"], st["cds"], st["mes_args"][0], st["mes_args"][1],
+                                                      _lib.dptr(batch_cost), _lib.dptr(vals),
+                                                      idxs.ctypes.data_as(_lib.c_int64_p)))
     elif kind[0] == "EI":
         _lib.check(_lib.load().cbo_acq_sweep_sets(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
                                                   _lib.dptr(batch_cost), _lib.dptr(vals),
@@ -517,6 +573,12 @@ def winners_to_points(st, models, grids, current_global_best, task):
             from .constrained import AcquisitionProduct
             ei = CausalExpectedImprovement(current_global_best, task, models[i])
             y = (AcquisitionProduct([ei] + list(constraints[i])) / costs[i]).evaluate(x_new)
+        elif name == "MES":
+            # the set's own draw: a fresh MaxValueEntropySearch would refit the Gumbel and draw again
+            from .max_value_entropy import MaxValueEntropySearch
+            mes = MaxValueEntropySearch(models[i], [(0.0, 1.0)] * x_new.shape[1], param[0], param[1])
+            mes.mins = st["mes_mins"][i]
+            y = mes.sweep(x_new, cost=point_cost, want_acq=True)["acq"]
         else:
             y = _acquisition_for(name, models[i], current_global_best, task, None, param).sweep(x_new, cost=point_cost,
                                                                                                 want_acq=True)["acq"]

@@ -593,8 +593,8 @@ int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int 
  * cbo_acq_sweep_sets_kind + cbo_argmax_sets.
  * CBO_ERR_INVALID, before any model is touched: cbo_acq_sweep_sets' (cbo_trial_step's) argument checks, a kind outside 1..4,
  * a non-finite param, beta < 0, a non-finite y_best[i] for CBO_ACQ_PI, costs[i] <= 0 or NaN, a bad task for every kind but
- * CBO_ACQ_VAR.  Out of scope: max-value entropy search and batch epilogues in the one launch (the constrained one is
- * cbo_acq_sweep_sets_constrained, the hyper-marginalised one cbo_acq_sweep_sets_hyper, below). */
+ * CBO_ACQ_VAR.  Out of scope: batch epilogues in the one launch (the constrained one is cbo_acq_sweep_sets_constrained,
+ * the hyper-marginalised one cbo_acq_sweep_sets_hyper, max-value entropy search cbo_acq_sweep_sets_mes, below). */
 int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int kind, const double *y_best,
                             int task, double param, const double *costs, double *best_vals, int64_t *best_idxs);
 int cbo_trial_step_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
@@ -652,6 +652,42 @@ int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cbo_cands *co
 int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
                              const double *const *hyper, const double *y_best, int task, double ei_jitter,
                              const double *costs, double *best_vals, int64_t *best_idxs);
+
+/* Max-value entropy search for every exploration set of a trial, in two calls with the host's draw of the
+ * Gumbel samples between them (mins = log(-log(1 - u)) * b + a, u from the caller's generator).
+ *
+ * cbo_acq_sweep_sets_mes, the scoring half: set i is (gps[i], cands[i]) scored against its own n_samples[i] (1..64) Gumbel
+ * samples mins[i] over costs[i].  Sets of one call may differ in n_samples, d, ARD and causal / plain.
+ * Contract: for every set, best_vals[i] and best_idxs[i] are bit for bit what cbo_acq_sweep_mes(gps[i], cands[i],
+ * n_samples[i], mins[i], costs[i], NULL, NULL, NULL, &v, &idx) returns on a fitted twin of the model: the same sum over the
+ * samples in numpy's order, the same tie rule (lowest index, NaN maximal, index_offset applied).
+ * Routing is cbo_acq_sweep_sets': fp64 models of at most 128 observations (CBO_HIP_SMALL_SETS on) are factored AND swept by
+ * one launch inside LDS (small_sets_kernel with cbo_acq_sweep_mes' epilogue; the sets' samples travel in one pinned table
+ * with an offset and a count per set) -- two launches from 12 candidate blocks per set on; they need no fit, and their
+ * fitted state and caches are left alone.  Larger models, fp32 models and sets whose factorisation needs jitchol's jitter
+ * take the general path inside the same call: cbo_gp_fit if unfitted, then cbo_acq_sweep_mes.
+ * CBO_ERR_INVALID, before any model is touched: n_sets <= 0; a NULL n_samples, mins, costs, best_vals or best_idxs; an
+ * n_samples[i] outside 1..64; a NULL or non-finite mins[i]; costs[i] <= 0 or NaN; then cbo_acq_sweep_sets' checks of the
+ * handles (NULL, contexts, a model without data, dimensions, a causal model whose candidates carry no prior).
+ *
+ * cbo_gp_mes_gumbel_sets, the Gumbel fit of every set in one call: grids[i] is a candidate set over set i's Gumbel grid
+ * (emukit stacks model.X on top of its uniform grid; the caller does; for a causal model the set carries the prior closures
+ * at the grid).  quantiles (n_sets x 3), a and b (n_sets each): for every set bit for bit what cbo_gp_mes_gumbel returns
+ * on a fitted twin for the same points.
+ * Two launches for all sets and one synchronisation: (1) the grids of the fp64 models of at most 128 observations are
+ * predicted, noise included, by the one-workgroup sweep's stages (small_sets_kernel storing mean and variance in the place of
+ * an acquisition; its factor-once first launch from 12 blocks per set on belongs to this step) into one device workspace of
+ * 2 sum(m_i) doubles -- those models need no fit and are only read; every other model is fitted if need be and predicted by
+ * the general path into the same workspace; (2) the bisections of all sets, three workgroups per set.  A small model that
+ * met a non-positive pivot is fitted (jitchol's ladder) and answered as cbo_gp_mes_gumbel answers, inside the same call.
+ * A set fails as the single call does (a bracket without a sign change, a bisection that does not converge): CBO_ERR_INVALID,
+ * the single call's message behind "set <i>: " for the first such set; the outputs are then unspecified.
+ * CBO_ERR_INVALID, before any model is touched: n_sets outside 1..65535, NULL arguments or handles, models of different
+ * contexts, a model without data, an empty grid, gp->d != grid->d, a causal model whose grid carries no prior.
+ * CBO_ERR_UNSUPPORTED (naming CBO_HIP_WORKSPACE_MB): the mean / variance workspace exceeds the workspace limit. */
+int cbo_acq_sweep_sets_mes(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
+                           const double *const *mins, const double *costs, double *best_vals, int64_t *best_idxs);
+int cbo_gp_mes_gumbel_sets(int n_sets, cbo_gp *const *gps, cbo_cands *const *grids, double *quantiles, double *a, double *b);
 
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,

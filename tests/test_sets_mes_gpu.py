@@ -1,0 +1,559 @@
+"""GPU tests of max-value entropy search in the one-launch multi-set sweep and the agent:
+cbo_acq_sweep_sets_mes (small_sets_kernel<kMesKind>, kernels_sets.hip), cbo_gp_mes_gumbel_sets (small_sets_kernel<kPredictKind>
+and the (3, n_sets) gumbel_quantiles_kernel, kernels_mes.hip) and the Python layer on top.
+
+Every comparison is exact -- values as bit patterns (NaN equals NaN), indices equal -- and the reference is always the
+per-set cbo_acq_sweep_mes / cbo_gp_mes_gumbel on freshly FITTED twin models, never the code under test.  Equality is the
+contract: the launch runs the general path's own device functions (kernel_value, the block factorisation, the tile solve,
+posterior_of, mes_of) in the general path's summation orders, and the bisections' sums keep their order whatever the grid.
+The single call itself is pinned to what it returned before its kernel became the one-set case of the multi-set launch
+(tests/golden/mes_gumbel_single.npz, tests/golden/make_mes_gumbel_fixture.py)."""
+import ctypes
+import os
+import subprocess
+import sys
+import warnings
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+INVALID, NOT_FITTED = -1, -5
+SAMPLE_COUNTS = [1, 7, 8, 9, 10, 16, 63, 64]      # numpy's pairwise order: below 8, 8, 8 + tail, two rounds, ..., the cap
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from cbo_with_oop_amd import _lib
+    assert _lib.device_count() > 0, "no GPU visible: -m gpu tests need an MI355X"
+    return _lib
+
+
+def gp(X, y, **kw):
+    from cbo_with_oop_amd.GaussianProcessFactory import HipGaussianProcess
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        return HipGaussianProcess(X, y, **kw)
+
+
+def mean_f(a):
+    return 0.3 * np.sin(a).sum(1, keepdims=True)
+
+
+def var_f(a):
+    return 0.05 + 0.02 * np.cos(a).sum(1, keepdims=True) ** 2
+
+
+class Pair:
+    """One exploration set twice: the model under test (never fitted) with its grid, and the fitted twin with its own."""
+
+    def __init__(self, n, m, d, causal=False, ard=False, offset=0, seed=0, kw=None, data=None, cand=None):
+        from cbo_with_oop_amd import CandidateGrid
+        rng = np.random.default_rng(1000 * n + 10 * m + d + seed)
+        X = rng.uniform(-2.0, 2.0, (n, d)) if data is None else data[0]
+        y = np.cos(X).sum(1, keepdims=True) + 0.05 * rng.standard_normal((n, 1)) if data is None else data[1]
+        pts = rng.uniform(-2.5, 2.5, (m, d)) if cand is None else cand
+        if kw is None:
+            kw = dict(variance=1.3, lengthscale=(0.7 + 0.2 * np.arange(d)) if ard else 0.9, ard=ard, noise_var=1e-3)
+            if causal:
+                kw.update(mean_function=mean_f, variance_adjustment=var_f)
+        self.causal = "mean_function" in kw
+        self.model, self.twin = gp(X, y, fit=False, **kw), gp(X, y, **kw)
+        self.points = pts
+        self.grid = CandidateGrid(pts, self.model, index_offset=offset)
+        self.twin_grid = CandidateGrid(pts, self.twin, index_offset=offset)
+
+    def close(self):
+        for o in (self.grid, self.twin_grid, self.model, self.twin):
+            o.close()
+
+
+def handles(objs):
+    return (ctypes.c_void_p * len(objs))(*[o._handle for o in objs])
+
+
+def single_gumbel(lib, twin, points):
+    """cbo_gp_mes_gumbel on a fitted twin: (rc, quantiles (3,), a, b)."""
+    pts = lib.as_f64(points)
+    pm = pv = None
+    if twin.causal:
+        pm = lib.as_f64(twin.mean_function(pts)).reshape(-1)
+        pv = lib.as_f64(twin.variance_adjustment(pts)).reshape(-1)
+    q = np.full(3, -7.0)
+    a, b = ctypes.c_double(-7.0), ctypes.c_double(-7.0)
+    twin.ensure_fitted()
+    rc = lib.load().cbo_gp_mes_gumbel(twin._handle, pts.shape[0], lib.dptr(pts), lib.dptr(pm), lib.dptr(pv), lib.dptr(q),
+                                      ctypes.byref(a), ctypes.byref(b), None, None)
+    return rc, q, a.value, b.value
+
+
+def mins_for(lib, pair, k, seed):
+    """k Gumbel samples for a set from the fitted twin's own Gumbel fit over the set's points -- with one value far below
+    and one far above the data (mean -+ 8 sd of the targets), so that 1 - ndtr meets its 1e-10 clip and ndtr's branches
+    diverge inside a wave."""
+    rc, _, a, b = single_gumbel(lib, pair.twin, np.vstack([pair.twin.X, pair.points]))
+    lib.check(rc)
+    u = np.random.default_rng(seed).random(k)
+    mins = np.log(-np.log(1 - u)) * b + a
+    y = pair.twin._y_flat
+    sd = float(np.std(y)) if y.size > 1 else 1.0
+    if k >= 2:
+        mins[0] = float(np.mean(y)) - 8.0 * sd
+        mins[-1] = float(np.mean(y)) + 8.0 * sd
+    assert np.all(np.isfinite(mins))
+    return np.ascontiguousarray(mins)
+
+
+def sweep_sets_mes(lib, models, grids, mins, costs, counts=None):
+    """cbo_acq_sweep_sets_mes: (rc, values, indices), the outputs pre-filled with a sentinel."""
+    s = len(models)
+    cs = np.ascontiguousarray(np.broadcast_to(np.asarray(costs, dtype=np.float64), (s,)))
+    ks = (ctypes.c_int * s)(*(counts if counts is not None else [len(m) for m in mins]))
+    ptrs = (ctypes.c_void_p * s)(*[None if m is None else m.ctypes.data for m in mins])
+    vals, idxs = np.full(s, -7.0), np.full(s, -7, dtype=np.int64)
+    rc = lib.load().cbo_acq_sweep_sets_mes(s, handles(models), handles(grids), ks, ptrs, lib.dptr(cs), lib.dptr(vals),
+                                           idxs.ctypes.data_as(lib.c_int64_p))
+    return rc, vals, idxs
+
+
+def per_set(lib, twins, twin_grids, mins, costs):
+    """The reference: cbo_acq_sweep_mes set by set on fitted twins."""
+    s = len(twins)
+    cs = np.broadcast_to(np.asarray(costs, float), (s,))
+    vals, idxs = np.empty(s), np.empty(s, dtype=np.int64)
+    for i, (g, grid) in enumerate(zip(twins, twin_grids)):
+        g.ensure_fitted()
+        bv, bi = ctypes.c_double(), ctypes.c_int64(-1)
+        lib.check(lib.load().cbo_acq_sweep_mes(g._handle, grid._handle, len(mins[i]), lib.dptr(mins[i]), float(cs[i]), None,
+                                               None, None, ctypes.byref(bv), ctypes.byref(bi)))
+        vals[i], idxs[i] = bv.value, bi.value
+    return vals, idxs
+
+
+def assert_same(got, want, what=""):
+    (gv, gi), (wv, wi) = got, want
+    print(what, "values", gv.tolist(), "reference", wv.tolist(), "indices", gi.tolist(), "reference", wi.tolist())
+    assert np.array_equal(gi, wi), (what, gi, wi)
+    assert np.array_equal(gv.view(np.uint64), wv.view(np.uint64)), (what, gv, wv)
+
+
+def check_call(lib, pairs, mins, costs, what=""):
+    rc, vals, idxs = sweep_sets_mes(lib, [p.model for p in pairs], [p.grid for p in pairs], mins, costs)
+    lib.check(rc)
+    assert_same((vals, idxs), per_set(lib, [p.twin for p in pairs], [p.twin_grid for p in pairs], mins, costs), what)
+    return vals, idxs
+
+
+def unfitted(lib, models):
+    out = np.empty(1)
+    return all(m.stale for m in models) and all(lib.load().cbo_gp_log_marginal(m._handle, lib.dptr(out)) == NOT_FITTED
+                                                for m in models)
+
+
+# ---- the kernel's edges ----------------------------------------------------------------------------------------------------
+# n: 16-row tile boundaries and the largest model the launch takes; m: 64 candidates per workgroup; 704 / 705 candidates: 11
+# and 12 workgroups per set, the two sides of the one- / two-launch split (the widest set of a call decides for the call)
+SHAPES = [dict(n=1, m=1, d=1), dict(n=15, m=63, d=2, causal=True), dict(n=16, m=64, d=3, offset=5000),
+          dict(n=17, m=65, d=8, ard=True), dict(n=50, m=200, d=1, causal=True), dict(n=128, m=704, d=2)]
+EXTRA = [dict(n=128, m=705, d=3, causal=True), dict(n=40, m=100, d=2, seed=1)]      # the two-launch side; an eighth set
+
+
+@pytest.fixture(scope="module")
+def zoo(lib):
+    pairs = [Pair(**kw) for kw in SHAPES + EXTRA]
+    mins = [mins_for(lib, p, k, seed=i) for i, (p, k) in enumerate(zip(pairs, SAMPLE_COUNTS))]
+    yield pairs, mins
+    for p in pairs:
+        p.close()
+
+
+def test_shapes_and_sample_counts(lib, zoo):
+    """One call over the six one-launch shapes and an eighth small set (one set of each K but 63: seven sets), then all
+    eight -- the 705-candidate set forces the two-launch form on every set of the call, and brings K = 63."""
+    pairs, mins = zoo
+    one = [0, 1, 2, 3, 4, 5, 7]
+    costs = 1.0 + np.arange(8) % 3
+    check_call(lib, [pairs[i] for i in one], [mins[i] for i in one], costs[one], "one launch")
+    check_call(lib, pairs, mins, costs, "two launches")
+    # every K at the widest one-launch shape and at the two-launch one
+    for k in SAMPLE_COUNTS:
+        ms = [mins_for(lib, pairs[5], k, seed=100 + k), mins_for(lib, pairs[4], k, seed=200 + k)]
+        check_call(lib, [pairs[5], pairs[4]], ms, [2.0, 1.0], f"K={k} one launch")
+        ms = [mins_for(lib, pairs[6], k, seed=300 + k), ms[1]]
+        check_call(lib, [pairs[6], pairs[4]], ms, [3.0, 1.0], f"K={k} two launches")
+    # the launch needs no fit and leaves the models alone
+    assert unfitted(lib, [p.model for p in pairs])
+
+
+def test_twenty_five_sets(lib):
+    """Beyond eight sets the descriptors are read from the pinned array; K mixed within the call."""
+    pairs = []
+    for sidx in range(25):
+        d = 1 + sidx % 3
+        pairs.append(Pair(8 + (7 * sidx) % 60, [150, 221, 210][d - 1] + sidx, d, causal=sidx % 4 == 1, seed=sidx))
+    mins = [mins_for(lib, p, SAMPLE_COUNTS[i % 8], seed=i) for i, p in enumerate(pairs)]
+    check_call(lib, pairs, mins, [1.0 + s % 3 for s in range(25)], "25 sets")
+    for p in pairs:
+        p.close()
+
+
+# ---- routing ---------------------------------------------------------------------------------------------------------------
+def mixed_pairs():
+    """n = 50 (the one launch), n = 129 and an fp32 model (the general path inside the same call)."""
+    rng = np.random.default_rng(3)
+    Xb = rng.uniform(-2, 2, (129, 3))
+    yb = np.cos(Xb).sum(1, keepdims=True)
+    cand = rng.uniform(-2.5, 2.5, (300, 3))
+    return [Pair(50, 200, 2, causal=True), Pair(129, 300, 3, kw=dict(noise_var=1e-3), data=(Xb, yb), cand=cand),
+            Pair(129, 300, 3, kw=dict(noise_var=1e-2, dtype="f32"), data=(Xb, yb), cand=cand)]
+
+
+def mixed_mins(pairs):
+    # (fixed numbers, the same in the child process: inside and outside the targets' range)
+    return [np.array([-1.5, 0.2, 1.0, -9.0, 9.0, 0.5, -0.3, 0.1, 0.0, -2.0]), np.array([0.5, -2.5, -20.0]), np.array([-1.0])]
+
+
+def child_mixed():
+    """(the child process of test_mixed_routing: the answers of the code under test)"""
+    from cbo_with_oop_amd import _lib
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        pairs = mixed_pairs()
+        rc, vals, idxs = sweep_sets_mes(_lib, [p.model for p in pairs], [p.grid for p in pairs], mixed_mins(pairs),
+                                        [2.0, 1.0, 3.0])
+        _lib.check(rc)
+        print("ANSWER", vals.view(np.uint64).tolist(), idxs.tolist())
+
+
+def test_mixed_routing(lib):
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        pairs = mixed_pairs()
+        mins = mixed_mins(pairs)
+        vals, idxs = check_call(lib, pairs, mins, [2.0, 1.0, 3.0], "mixed")
+    assert pairs[0].model.stale and unfitted(lib, [pairs[0].model])
+    out = np.empty(1)
+    assert lib.load().cbo_gp_log_marginal(pairs[1].model._handle, lib.dptr(out)) == 0        # the general path fitted it
+    # the same call with the one launch switched off (read when the context is created: a process of its own)
+    env = dict(os.environ, CBO_HIP_SMALL_SETS="0")
+    code = ("import sys; sys.path[:0] = [%r, %r]; import test_sets_mes_gpu as t; t.child_mixed()"
+            % (ROOT, os.path.join(ROOT, "tests")))
+    run = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stdout + run.stderr
+    lines = [ln for ln in run.stdout.splitlines() if ln.startswith("ANSWER ")]
+    assert lines == [f"ANSWER {vals.view(np.uint64).tolist()} {idxs.tolist()}"], (lines, vals, idxs)
+    for p in pairs:
+        p.close()
+
+
+def test_a_fitted_model_keeps_its_cached_solution(lib):
+    """A fitted small model with a swept grid: the launch reads neither and changes neither -- the next per-set sweep (from
+    the cached q, mu) returns what it returned before."""
+    p = Pair(40, 150, 2, causal=True)
+    mins = np.array([-1.0, 0.5, 0.1])
+    before = per_set(lib, [p.twin], [p.twin_grid], [mins], [2.0])
+    rc, vals, idxs = sweep_sets_mes(lib, [p.twin], [p.twin_grid], [mins], [2.0])
+    lib.check(rc)
+    assert_same((vals, idxs), before, "fitted model")
+    out = np.empty(1)
+    assert lib.load().cbo_gp_log_marginal(p.twin._handle, lib.dptr(out)) == 0
+    assert_same(per_set(lib, [p.twin], [p.twin_grid], [mins], [2.0]), before, "after the launch")
+    p.close()
+
+
+# ---- the Gumbel fit of every set ---------------------------------------------------------------------------------------------
+def gumbel_sets(lib, models, grids):
+    s = len(models)
+    q, a, b = np.full((s, 3), -7.0), np.full(s, -7.0), np.full(s, -7.0)
+    rc = lib.load().cbo_gp_mes_gumbel_sets(s, handles(models), handles(grids), lib.dptr(q), lib.dptr(a), lib.dptr(b))
+    return rc, q, a, b
+
+
+def gumbel_pairs(specs):
+    """(n, grid points beyond the model's own, d, causal) -> Pair whose grid is the model's points with those on top."""
+    pairs = []
+    for i, (n, extra, d, causal) in enumerate(specs):
+        rng = np.random.default_rng(77 + i)
+        X = rng.uniform(-2.0, 2.0, (n, d))
+        y = np.cos(X).sum(1, keepdims=True) + 0.05 * rng.standard_normal((n, 1))
+        pairs.append(Pair(n, n + extra, d, causal=causal, data=(X, y), cand=np.vstack([X, rng.uniform(-2.5, 2.5, (extra, d))])))
+    return pairs
+
+
+def assert_gumbel_same(lib, pairs, what):
+    rc, q, a, b = gumbel_sets(lib, [p.model for p in pairs], [p.grid for p in pairs])
+    lib.check(rc)
+    for i, p in enumerate(pairs):
+        rc1, q1, a1, b1 = single_gumbel(lib, p.twin, p.points)
+        lib.check(rc1)
+        print(what, "set", i, "quantiles", q[i].tolist(), "single", q1.tolist(), "a", a[i], a1, "b", b[i], b1)
+        assert np.array_equal(q[i].view(np.uint64), q1.view(np.uint64)), (what, i, q[i], q1)
+        assert np.float64(a[i]).tobytes() == np.float64(a1).tobytes() and np.float64(b[i]).tobytes() == np.float64(b1).tobytes()
+
+
+def test_gumbel_shapes(lib):
+    """Grid sizes of n plus {1, 63, 64, 65, 704 - n, 705 - n} and totals of 1023, 1024 and 1025 points (the stride of the
+    1024-thread sum), plain and causal, n in {1, 17, 50, 128}: one call over all (705 points: the factor-once first
+    launch), and the sets of at most 704 points in a call of their own (every workgroup factors its model)."""
+    specs = [(1, 1, 1, False), (17, 63, 2, True), (50, 64, 3, False), (128, 65, 2, True), (50, 704 - 50, 1, True),
+             (17, 704 - 17, 2, False), (128, 705 - 128, 3, True), (17, 1023 - 17, 1, False), (50, 1024 - 50, 2, True),
+             (1, 1025 - 1, 2, False)]
+    pairs = gumbel_pairs(specs)
+    assert_gumbel_same(lib, pairs, "all")
+    assert_gumbel_same(lib, pairs[:6], "one launch")
+    assert unfitted(lib, [p.model for p in pairs])
+    for p in pairs:
+        p.close()
+
+
+def test_gumbel_routing(lib):
+    """n = 129 and an fp32 model are fitted and predicted by the general path into the same workspace."""
+    rng = np.random.default_rng(5)
+    Xb = rng.uniform(-2, 2, (129, 2))
+    yb = np.cos(Xb).sum(1, keepdims=True)
+    cand = np.vstack([Xb, rng.uniform(-2.5, 2.5, (100, 2))])
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        pairs = gumbel_pairs([(50, 150, 2, True)]) + [Pair(129, 229, 2, kw=dict(noise_var=1e-3), data=(Xb, yb), cand=cand),
+                                                      Pair(129, 229, 2, kw=dict(noise_var=1e-2, dtype="f32"), data=(Xb, yb), cand=cand)]
+        assert_gumbel_same(lib, pairs, "mixed")
+    assert unfitted(lib, [pairs[0].model])
+    for p in pairs:
+        p.close()
+
+
+def test_single_gumbel_fit_has_not_moved(lib):
+    """cbo_gp_mes_gumbel against what it returned before the bisection kernel was generalised (recorded bit patterns)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_mes_gumbel_fixture as gen
+    finally:
+        sys.path.pop(0)
+    f = np.load(os.path.join(ROOT, "tests", "golden", "mes_gumbel_single.npz"), allow_pickle=False)
+    for i in range(int(f["n_cases"])):
+        inp = {k[len(f"c{i}_"):]: f[k] for k in f.files if k.startswith(f"c{i}_")}
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            model = gen.model_of(inp)
+        q, a, b = gen.single_fit(lib, model, inp)
+        print("case", i, q.tolist(), inp["quantiles"].tolist(), a, float(inp["a"]), b, float(inp["b"]))
+        assert np.array_equal(q.view(np.uint64), inp["quantiles"].view(np.uint64)), (i, q, inp["quantiles"])
+        assert np.float64(a).tobytes() == inp["a"].tobytes() and np.float64(b).tobytes() == inp["b"].tobytes()
+        model.close()
+
+
+def test_a_failing_set_fails_as_the_single_call_does(lib):
+    """A grid whose prior mean holds a NaN: no bracket, the bisection cannot converge -- an arithmetic outcome.  The call
+    returns the single call's code and its message behind the index of the set."""
+    rng = np.random.default_rng(9)
+    X = rng.uniform(-2.0, 2.0, (20, 2))
+    y = np.cos(X).sum(1, keepdims=True)
+    pts = np.vstack([X, rng.uniform(-2.5, 2.5, (30, 2))])
+    bad = pts[25].copy()
+
+    def mf(a):
+        out = mean_f(a)
+        out[np.all(a == bad[None, :], axis=1)] = np.nan
+        return out
+    kw = dict(variance=1.3, lengthscale=0.9, noise_var=1e-3, mean_function=mf, variance_adjustment=var_f)
+    healthy = gumbel_pairs([(30, 40, 2, False)])[0]
+    pair = Pair(20, 50, 2, kw=kw, data=(X, y), cand=pts)
+    rc1, _, _, _ = single_gumbel(lib, pair.twin, pts)
+    single_msg = lib.load().cbo_last_error().decode()
+    assert rc1 == INVALID and single_msg
+    rc, _, _, _ = gumbel_sets(lib, [healthy.model, pair.model], [healthy.grid, pair.grid])
+    msg = lib.load().cbo_last_error().decode()
+    print(rc, msg, "|", single_msg)
+    assert rc == rc1 and msg == "set 1: " + single_msg
+    # and the call works afterwards
+    assert_gumbel_same(lib, [healthy], "after the failure")
+    healthy.close(); pair.close()
+
+
+# ---- errors -----------------------------------------------------------------------------------------------------------------
+def test_invalid_arguments_leave_everything_untouched(lib):
+    L = lib.load()
+    pairs = [Pair(20, 100, 2, causal=True), Pair(33, 70, 2)]
+    models, grids = [p.model for p in pairs], [p.grid for p in pairs]
+    good = [np.array([-1.0, 0.2]), np.array([0.3])]
+
+    def refused(mins=good, costs=(1.0, 2.0), counts=None):
+        rc, vals, idxs = sweep_sets_mes(lib, models, grids, mins, costs, counts)
+        assert rc == INVALID and L.cbo_last_error(), (mins, costs, counts)
+        assert np.all(vals == -7.0) and np.all(idxs == -7) and unfitted(lib, models)
+
+    for counts in ([0, 1], [2, 65], [-1, 1]):
+        refused(mins=[np.zeros(70), np.zeros(70)], counts=counts)
+    refused(mins=[good[0], None], counts=[2, 1])
+    for bad in (np.nan, np.inf, -np.inf):
+        refused(mins=[good[0], np.array([bad])])
+        refused(mins=[np.array([0.1, bad]), good[1]])
+    for costs in ((0.0, 1.0), (1.0, -1.0), (1.0, np.nan)):
+        refused(costs=costs)
+    # cbo_acq_sweep_sets' own checks: n_sets, NULL arrays, a causal model whose candidates carry no prior, dimensions
+    vals, idxs, cs = np.full(2, -7.0), np.full(2, -7, dtype=np.int64), np.ones(2)
+    ks, ptrs = (ctypes.c_int * 2)(2, 1), (ctypes.c_void_p * 2)(good[0].ctypes.data, good[1].ctypes.data)
+    ok = (2, handles(models), handles(grids), ks, ptrs, lib.dptr(cs), lib.dptr(vals), idxs.ctypes.data_as(lib.c_int64_p))
+    for at, bad in ((0, 0), (0, -1), (1, None), (2, None), (3, None), (4, None), (5, None), (6, None), (7, None)):
+        args = list(ok)
+        args[at] = bad
+        assert L.cbo_acq_sweep_sets_mes(*args) == INVALID and unfitted(lib, models), at
+    assert np.all(vals == -7.0) and np.all(idxs == -7)
+    swapped = (2, handles(models), handles(grids[::-1])) + ok[3:]      # the causal model with the grid that has no prior
+    assert L.cbo_acq_sweep_sets_mes(*swapped) == INVALID and unfitted(lib, models)
+    other = Pair(10, 20, 3)
+    assert L.cbo_acq_sweep_sets_mes(2, handles(models), handles([grids[0], other.grid]), *ok[3:]) == INVALID
+    assert np.all(vals == -7.0) and np.all(idxs == -7) and unfitted(lib, models)
+    # the Gumbel fit: NULL arguments, a causal model whose grid carries no prior, dimensions
+    q, a, b = np.full((2, 3), -7.0), np.full(2, -7.0), np.full(2, -7.0)
+    ok = (2, handles(models), handles(grids), lib.dptr(q), lib.dptr(a), lib.dptr(b))
+    for at, bad in ((0, 0), (1, None), (2, None), (3, None), (4, None), (5, None)):
+        args = list(ok)
+        args[at] = bad
+        assert L.cbo_gp_mes_gumbel_sets(*args) == INVALID and unfitted(lib, models), at
+    assert L.cbo_gp_mes_gumbel_sets(2, handles(models), handles(grids[::-1]), *ok[3:]) == INVALID
+    assert L.cbo_gp_mes_gumbel_sets(2, handles(models), handles([grids[0], other.grid]), *ok[3:]) == INVALID
+    assert L.cbo_gp_mes_gumbel_sets(2, handles(models), (ctypes.c_void_p * 2)(grids[0]._handle, None), *ok[3:]) == INVALID
+    assert np.all(q == -7.0) and np.all(a == -7.0) and np.all(b == -7.0) and unfitted(lib, models)
+    # the refusals left the valid calls working
+    check_call(lib, pairs, good, (1.0, 2.0), "valid call")
+    other.close()
+    for p in pairs:
+        p.close()
+
+
+# ---- the Python path ----------------------------------------------------------------------------------------------------------------
+def replay(lib, twins, spaces, es, cost_table, num_samples, grid_size, grid_shape):
+    """The documented draw order by hand, on fitted twins: gumbel_grid per set, cbo_gp_mes_gumbel per twin, gumbel_mins per
+    set, cbo_acq_sweep_mes per twin; then utils.py:36's re-evaluation at the point's own cost.  Returns (xs, ys)."""
+    from cbo_with_oop_amd import CandidateGrid
+    from cbo_with_oop_amd.graphs import meshgrid_candidates
+    from cbo_with_oop_amd.utils_functions import Cost
+    from cbo_with_oop_amd.utils_functions.max_value_entropy import gumbel_grid, gumbel_mins
+    from cbo_with_oop_amd.utils_functions.utils import space_bounds
+    grids = [gumbel_grid(space_bounds(spaces[s]), grid_size, twins[s].X) for s in range(len(twins))]
+    fits = []
+    for s, twin in enumerate(twins):
+        rc, _, a, b = single_gumbel(lib, twin, grids[s])
+        lib.check(rc)
+        fits.append((a, b))
+    mins = [np.ascontiguousarray(gumbel_mins(num_samples, a, b)) for a, b in fits]
+    xs, ys = [], []
+    for s, twin in enumerate(twins):
+        cost = Cost(cost_table, es[s])
+        grid = CandidateGrid(meshgrid_candidates(space_bounds(spaces[s]), grid_shape), twin)
+        batch_cost = float(cost.evaluate(grid.points))
+        vals, idxs = per_set(lib, [twin], [grid], [mins[s]], [batch_cost])
+        x_new = grid.points[int(idxs[0])][None, :].copy()
+        point_cost = float(cost.evaluate(x_new))
+        if point_cost == batch_cost:
+            y = np.array([[vals[0]]])
+        else:
+            one = CandidateGrid(x_new, twin)
+            y = np.array([[per_set(lib, [twin], [one], [mins[s]], [point_cost])[0][0]]])
+            one.close()
+        xs.append(x_new); ys.append(y)
+        grid.close()
+    for t in twins:
+        t.close()
+    return xs, ys
+
+
+@pytest.mark.parametrize("type_cost", [1, 4])
+def test_find_next_y_points_is_the_hand_replay(lib, type_cost):
+    from cbo_with_oop_amd import CandidateGrid
+    from cbo_with_oop_amd.graphs import ToyGraph, meshgrid_candidates
+    from cbo_with_oop_amd.utils_functions import find_next_y_points
+    es = ToyGraph.get_exploration_set("MIS")
+    spaces = [ToyGraph.bounds(s) for s in es]
+    cost_table = ToyGraph.get_cost_structure(type_cost)
+    rng = np.random.default_rng(11)
+    data = [(rng.uniform(-5, 5, (12, 1)),), (rng.uniform(-5, 20, (15, 1)),)]
+    data = [(data[0][0], ToyGraph.target_do_x(data[0][0])), (data[1][0], ToyGraph.target_do_z(data[1][0]))]
+    kw_of = lambda s: dict(noise_var=1e-3, mean_function=mean_f, variance_adjustment=var_f) if s == 1 else dict(noise_var=1e-3)  # noqa: E731
+    models = [gp(x, y, fit=False, **kw_of(s)) for s, (x, y) in enumerate(data)]
+    grids = [CandidateGrid(meshgrid_candidates(spaces[s], [200]), models[s]) for s in range(2)]
+    np.random.seed(123)
+    a_x, a_y = find_next_y_points(models, 0.0, es, cost_table, "min", grids, acquisition="MES", acquisition_param=(10, 37),
+                                  spaces=spaces)
+    np.random.seed(123)
+    b_x, b_y = replay(lib, [gp(x, y, **kw_of(s)) for s, (x, y) in enumerate(data)], spaces, es, cost_table, 10, 37, [200])
+    print([y.tolist() for y in a_y], [y.tolist() for y in b_y])
+    assert all(np.array_equal(p, q) for p, q in zip(a_x, b_x))
+    assert all(np.array_equal(p.view(np.uint64), q.view(np.uint64)) for p, q in zip(a_y, b_y))
+    for o in grids + models:
+        o.close()
+
+
+def test_path_trial_steps_are_the_hand_replay(lib):
+    """CBOAcquisitionPath(acquisition="MES").trial_step over three trials on the toy graph with a fixed seed: each trial's
+    chosen set and points equal the hand replay (the three-call route: upload, the Gumbel fits, the scoring)."""
+    from cbo_with_oop_amd import CBOAcquisitionPath, GaussianProcessType
+    from cbo_with_oop_amd.graphs import ToyGraph
+    es = ToyGraph.get_exploration_set("MIS")
+    targets = [ToyGraph.target_do_x, ToyGraph.target_do_z]
+    spaces = [ToyGraph.bounds(s) for s in es]
+    cost_table = ToyGraph.get_cost_structure(1)
+    rng = np.random.default_rng(4)
+    xs = [rng.uniform(-5, 5, (12, 1)), rng.uniform(-5, 20, (12, 1))]
+    ys = [targets[0](xs[0]), targets[1](xs[1])]
+    path = CBOAcquisitionPath(GaussianProcessType.NON_CAUSAL_GP, es, cost_table, "min", xs, ys, spaces,
+                              grid_shapes=[[200], [200]], comm=None, acquisition="MES", acquisition_param=(10, 37))
+    path.update_all_gaussian_processes()
+    from cbo_with_oop_amd.GaussianProcessFactory import GaussianProcessFactory as GPFactory
+    twin_of = lambda x, y: GPFactory.create(GaussianProcessType.NON_CAUSAL_GP, x, y, [None, None], emukit_wrapper=True)  # noqa: E731
+    for trial in range(3):
+        best = min(float(ys[0].min()), float(ys[1].min()))
+        np.random.seed(1000 + trial)
+        a_x, a_y, (a_set, a_idx) = path.trial_step(best)
+        np.random.seed(1000 + trial)
+        b_x, b_y = replay(lib, [twin_of(x, y) for x, y in zip(xs, ys)], spaces, es, cost_table, 10, 37, [200])
+        b_idx = int(np.argmax([float(y[0, 0]) for y in b_y]))
+        print("trial", trial, [y.tolist() for y in a_y], [y.tolist() for y in b_y])
+        assert a_idx == b_idx and a_set == es[b_idx]
+        assert all(np.array_equal(p, q) for p, q in zip(a_x, b_x))
+        assert all(np.array_equal(p.view(np.uint64), q.view(np.uint64)) for p, q in zip(a_y, b_y))
+        assert "trial_args" not in path._call_cache["sweep_sets"]
+        xs[a_idx] = np.vstack([xs[a_idx], a_x[a_idx]])
+        ys[a_idx] = np.vstack([ys[a_idx], targets[a_idx](a_x[a_idx])])
+
+
+def test_agent_runs_with_max_value_entropy_search(lib):
+    """CBO(toy graph, acquisition="MES", num_trials=2).run(): one observation, one intervention scored by max-value entropy
+    search; finite values recorded.  task="max" with MES is refused at construction."""
+    from cbo_with_oop_amd.CBO import CBO
+    from cbo_with_oop_amd.graphs import ToyGraph
+    from cbo_with_oop_amd.utils_functions.graph_functions import sample_from_model
+
+    class Toy(ToyGraph):
+        """The toy graph with what an observe step needs: its manipulative variables and one graph GP per set."""
+        manipulative_variables = ("X", "Z")
+        _fit_dependencies = (("X",), ("Z",))
+        _fit_parameters = ([1.0, 1.0, 10.0, False], [1.0, 1.0, 10.0, False])
+
+    sem = Toy.define_sem()
+    rng = np.random.default_rng(11)
+    draws = [sample_from_model(sem, rng.standard_normal(len(sem))) for _ in range(60)]
+    obs = {v: np.array([r[v] for r in draws]) for v in draws[0] if not v.startswith("U")}
+    init = {k: v[:40] for k, v in obs.items()}
+    es = ToyGraph.get_exploration_set("MIS")
+    targets = [ToyGraph.target_do_x, ToyGraph.target_do_z]
+    xs = [rng.uniform(-5, 5, (6, 1)), rng.uniform(-5, 20, (6, 1))]
+    data = [(xs[s].copy(), targets[s](xs[s])) for s in range(2)]
+    common = dict(exploration_set=es, num_trials=2, initial_num_obs_samples=40, num_additional_observations=10,
+                  grid_shapes=[[64], [64]], target_functions=targets, acquisition="MES", acquisition_param=(10, 50))
+    with pytest.raises(ValueError):
+        CBO(Toy, init, obs, data, task="max", **common)
+    np.random.seed(9)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        agent = CBO(Toy, init, obs, data, **common)
+        mon = agent.run()
+    assert mon.type_trial == [0, 1] and mon.chosen[-1] is not None
+    assert agent._kind == ("MES", (10, 50))
+    print(mon.global_opt, mon.current_cost, mon.chosen)
+    assert np.all(np.isfinite(mon.global_opt)) and np.all(np.isfinite(mon.current_cost))
+    assert np.all(np.isfinite(np.asarray(mon.chosen[-1][1], dtype=np.float64)))
