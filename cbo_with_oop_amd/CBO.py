@@ -9,8 +9,8 @@ import numpy as np
 from .GaussianProcessFactory import GaussianProcessFactory as GPFactory
 from .graphs import meshgrid_candidates
 from .utils_functions.causal_acquisition_functions import CandidateGrid
-from .utils_functions.utils import (default_grid_shape, find_current_global, find_next_y_point, find_next_y_points,  # noqa: F401
-                                    space_bounds)
+from .utils_functions.utils import (checked_batch_size, default_grid_shape, find_current_global, find_next_y_point,  # noqa: F401
+                                    find_next_y_points, space_bounds)
 
 
 class _FixedCosts:
@@ -84,11 +84,16 @@ class CBOAcquisitionPath:
     ``hyper_samples`` (a positive int H, or a callable ``sampler(model, set_index) -> (H, P)`` samples in GPy's parameter
     order) makes every set's score the causal EI marginalised over hyper-parameter samples of its own model:
     an int draws ``model.generate_hyperparameters_samples(H)`` with emukit's defaults.  The path keeps ``hyper_rows[s]`` and
-    redraws them whenever it rebuilds the set's model.  It needs ``acquisition="EI"``, no constraints and a single process."""
+    redraws them whenever it rebuilds the set's model.  It needs ``acquisition="EI"``, no constraints and a single process.
+    ``batch_size`` (an int B in 1..64) with ``update_incumbent`` makes every set's answer a greedy batch of B Kriging-believer
+    picks in one device call (``find_next_y_points(batch_size=B)``): ``xs[s]`` is (B, d), ``ys[s]`` (B, 1); the
+    set is chosen by pick 0, as before.  It needs ``acquisition="EI"``, no constraints, no hyper-parameter samples and a
+    single process, and its ``trial_step`` takes the three-call route."""
 
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
-                 acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None):
+                 acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
+                 update_incumbent=False):
         from .utils_functions.utils import sets_acquisition_or_default as sets_acquisition
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
@@ -106,6 +111,8 @@ class CBOAcquisitionPath:
         self.constraint_models = []
         self.hyper_samples = checked_path_hyper_samples(hyper_samples, self._kind, self.constraints)
         self.hyper_rows = [None] * len(exploration_set)
+        self.batch_size = checked_batch_size(batch_size, self._kind, self.constraints, self.hyper_samples)
+        self.update_incumbent = bool(update_incumbent)
         self.gp_type = gp_type
         self.exploration_set = exploration_set
         self.es_size = len(exploration_set)
@@ -252,7 +259,8 @@ class CBOAcquisitionPath:
     def compute_best_acquisition_values(self, current_best):
         """CBO.py:237-260: the loop over the exploration sets, as ONE device call (``cbo_acq_sweep_sets``, or
         ``cbo_acq_sweep_sets_kind`` for the path's point-wise ``acquisition``); across several GPUs, this rank's share of
-        it and one arg-max exchange per set."""
+        it and one arg-max exchange per set.  With the path's ``batch_size`` B it is one ``cbo_acq_sweep_sets_batch`` call
+        (a single process only): ``xs[s]`` is (B, d) and ``ys[s]`` (B, 1), row 0 the single-point result."""
         mode, world, rank = self.placement()
         if self.constraints and mode != "single":
             raise ValueError(f"constraints are scored by a single process: the placement is {mode!r}")
@@ -260,12 +268,15 @@ class CBOAcquisitionPath:
             raise ValueError(f"the marginalised EI is scored by a single process: the placement is {mode!r}")
         if self._kind[0] == "MES" and mode != "single":
             raise ValueError(f"max-value entropy search is scored by a single process: the placement is {mode!r}")
+        if self.batch_size is not None and mode != "single":
+            raise ValueError(f"batch selection is scored by a single process: the placement is {mode!r}")
         if mode == "single":
             grids = [self.candidate_grid(s) for s in range(self.es_size)]
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
                                       cache=self._call_cache, acquisition=self._kind, constraints=self.set_constraints(),
                                       hyper_samples=None if self.hyper_samples is None else list(self.hyper_rows),
-                                      spaces=self.space_list if self._kind[0] == "MES" else None)
+                                      spaces=self.space_list if self._kind[0] == "MES" else None,
+                                      batch_size=self.batch_size, update_incumbent=self.update_incumbent)
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -327,8 +338,8 @@ class CBOAcquisitionPath:
         At the reference's model sizes the three calls' host glue costs as much as the one launch that serves them
         (``cbo_trial_step``, ``cbo_trial_step_kind`` for a point-wise ``acquisition``); anything the one call does not cover
         (several ranks, a model rebuilt with other prior closures or other hyper-parameters, the first trial,
-        constraints, hyper-parameter samples, max-value entropy search -- whose host draws its Gumbel samples between the
-        Gumbel fit and the scoring) takes the three calls."""
+        constraints, hyper-parameter samples, a batch, max-value entropy search -- whose host draws its Gumbel samples between
+        the Gumbel fit and the scoring) takes the three calls."""
         import ctypes
         from . import _lib
         from .utils_functions.utils import winners_to_points
@@ -336,7 +347,7 @@ class CBOAcquisitionPath:
         st = self._call_cache.get("sweep_sets")
         model = self.models[s] if (s is not None and self.models) else None
         fast = (st is not None and model is not None and not self.constraints and self.hyper_samples is None
-                and self._kind[0] != "MES"
+                and self._kind[0] != "MES" and self.batch_size is None
                 and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
                 and model._hyper_initial and st["cost_table"] is self.costs
@@ -433,7 +444,11 @@ class CBO(CBOAcquisitionPath):
     monitor records ``constraint_values`` and ``feasible`` per trial.
     ``hyper_samples`` (a positive int or a callable sampler, as for ``CBOAcquisitionPath``): ``intervene()`` scores every set
     with the EI marginalised over hyper-parameter samples of its model; the closing ``optimize()`` of the
-    chosen set's model stays, as in the reference."""
+    chosen set's model stays, as in the reference.
+    ``batch_size`` (an int B in 1..64) with ``update_incumbent``: ``intervene()`` runs the B interventions of a greedy batch on
+    the chosen set side by side: the monitor evaluates the B rows, appends them in order and records
+    ``chosen`` as ``(set, x (B, d))``; the trial's cost is the sum of the B interventions' costs.  ``None``: the reference's
+    one intervention per trial."""
 
     TARGET = "Y"
 
@@ -441,7 +456,7 @@ class CBO(CBOAcquisitionPath):
                  num_interventions=10, initial_num_obs_samples=100, causal_prior=False, num_trials=40, task="min",
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
-                 constraint_functions=None, hyper_samples=None):
+                 constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType
         from .graphs import _columns
@@ -484,6 +499,7 @@ class CBO(CBOAcquisitionPath):
             raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
         path_constraints = checked_path_constraints(path_constraints, sets_acquisition(acquisition, acquisition_param))
         checked_path_hyper_samples(hyper_samples, sets_acquisition(acquisition, acquisition_param), path_constraints)
+        checked_batch_size(batch_size, sets_acquisition(acquisition, acquisition_param), path_constraints, hyper_samples)
         sem = None
         if path_constraints and constraint_functions is None:
             from functools import partial
@@ -498,7 +514,8 @@ class CBO(CBOAcquisitionPath):
         super().__init__(gp_type, exploration, self.graph.get_cost_structure(type_cost), task, data_x, data_y,
                          [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None,
                          acquisition=acquisition, acquisition_param=acquisition_param, constraints=path_constraints,
-                         constraint_data_y=constraint_data_y, hyper_samples=hyper_samples)
+                         constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
+                         update_incumbent=update_incumbent)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions
@@ -538,7 +555,9 @@ class CBO(CBOAcquisitionPath):
         self.monitor.log_agent_performance()
 
     def intervene(self):
-        """src/CBO.py:143-173."""
+        """src/CBO.py:143-173.  With ``batch_size`` B the chosen set -- picked by the first value of each ``ys[s]``, as
+        always -- contributes its whole batch: ``compute_cost`` sums the B interventions' costs and the monitor evaluates and
+        appends the B rows in order (``_Monitor._log_batch``), then the set's model is optimised once."""
         self.monitor.log_agent_behaviour(act=True)
         current_best = self.current_best_solution(self.monitor.current_best_y)
         if self.monitor.agent_previously_observed() or not self.models:
@@ -579,10 +598,16 @@ class CBO(CBOAcquisitionPath):
         return {k: v[lo:lo + self.num_additional_observations] for k, v in self.all_measurements.items()}
 
     def compute_cost(self, intervention_set, intervention, acquisition_xs):
-        """src/CBO.py:279-291."""
+        """src/CBO.py:279-291; with a batch, the sum over the batch's interventions in order."""
         from .utils_functions.cost_functions import total_cost
-        x = {v: acquisition_xs[intervention][0, i] for i, v in enumerate(intervention_set)}
-        return total_cost(intervention_set, self.costs, x)
+        rows = np.asarray(acquisition_xs[intervention])
+        if self.batch_size is None:
+            x = {v: rows[0, i] for i, v in enumerate(intervention_set)}
+            return total_cost(intervention_set, self.costs, x)
+        cost = 0.
+        for row in rows:
+            cost += total_cost(intervention_set, self.costs, {v: row[i] for i, v in enumerate(intervention_set)})
+        return cost
 
 
 class _Monitor:
@@ -632,6 +657,8 @@ class _Monitor:
             self.feasible.append(None)
             return
         cbo = self.cbo
+        if getattr(cbo, "batch_size", None) is not None:
+            return self._log_batch(intervention_set, intervention, acquisition_xs, current_cost)
         x_new = np.asarray(acquisition_xs[intervention], dtype=np.float64).reshape(1, -1)
         y_new = np.asarray(cbo.target_functions[intervention](x_new), dtype=np.float64).reshape(1, 1)
         cbo.data_x[intervention] = np.vstack((cbo.data_x[intervention], x_new))
@@ -649,6 +676,28 @@ class _Monitor:
         name = cbo.intervention_names[intervention]
         self.current_best_x[name].append(float(x_new[0, 0]))
         self.current_best_y[name].append(float(y_new[0, 0]))
+        self.global_opt.append(float(find_current_global(self.current_best_y, cbo.intervention_names, cbo.task)))
+        self.cumulative_cost += current_cost
+        self.current_cost.append(self.cumulative_cost)
+        self.chosen.append((list(intervention_set), x_new.copy()))
+
+    def _log_batch(self, intervention_set, intervention, acquisition_xs, current_cost):
+        """A trial that ran a batch: the B rows evaluated, appended in order (one ``set_data``), every value in order into
+        the set's bests; ``chosen`` holds (set, x (B, d)).  (A batch needs no constraints: the agent refuses both.)"""
+        cbo = self.cbo
+        x_new = np.asarray(acquisition_xs[intervention], dtype=np.float64)
+        x_new = x_new.reshape(-1, x_new.shape[-1])
+        y_new = np.vstack([np.asarray(cbo.target_functions[intervention](row[None, :]), dtype=np.float64).reshape(1, 1)
+                           for row in x_new])
+        cbo.data_x[intervention] = np.vstack((cbo.data_x[intervention], x_new))
+        cbo.data_y[intervention] = np.vstack((cbo.data_y[intervention], y_new))
+        cbo.models[intervention].set_data(cbo.data_x[intervention], cbo.data_y[intervention])
+        self.constraint_values.append(None)
+        self.feasible.append(None)
+        name = cbo.intervention_names[intervention]
+        for t in range(x_new.shape[0]):
+            self.current_best_x[name].append(float(x_new[t, 0]))
+            self.current_best_y[name].append(float(y_new[t, 0]))
         self.global_opt.append(float(find_current_global(self.current_best_y, cbo.intervention_names, cbo.task)))
         self.cumulative_cost += current_cost
         self.current_cost.append(self.cumulative_cost)

@@ -22,6 +22,8 @@ ABI_VERSION = 5          # include/cbo_hip.h: CBO_HIP_ABI_VERSION
 MAX_DIM = 8              # CBO_MAX_DIM
 MAX_APPEND = 64          # CBO_MAX_APPEND
 MAX_HYPER_SAMPLES = 256  # CBO_MAX_HYPER_SAMPLES
+MAX_BATCH = 64  # CBO_MAX_BATCH
+SMALL_BATCH_MAX_CANDS = 1024  # kSmallBatchMaxCands: the widest set cbo_acq_sweep_sets_batch answers in its one launch
 CBO_OK = 0
 CBO_ERR_INVALID = -1
 CBO_ERR_HIP = -2
@@ -160,6 +162,8 @@ SIGNATURES = {
                                                 ctypes.c_int, ctypes.c_double, c_double_p, c_double_p, c_int64_p]),
     "cbo_acq_sweep_sets_mes": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_int_p, c_void_pp, c_double_p, c_double_p,
                                               c_int64_p]),
+    "cbo_acq_sweep_sets_batch": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, ctypes.c_int, ctypes.c_double,
+                                                c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_int64_p]),
     "cbo_gp_mes_gumbel_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_double_p]),
     "cbo_comm_gather_i64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_int64_p]),

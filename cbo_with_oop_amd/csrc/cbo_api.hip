@@ -165,6 +165,9 @@ struct cbo_ctx {
     // cbo_acq_sweep_batch: the fantasy rows [batch_size - 1][m_pad], the working copy of q, the pivot column [n_pad], the
     // slice sums of the pass over V [kBatchMaxSlices][m_pad], the pick's scalars, and the winners (pinned: written by kernels)
     GrowBuf<double> batch_W, batch_q, batch_col, batch_part;
+    // cbo_acq_sweep_sets_batch: every small set's V, W, q and mu (small_sets_batch_doubles), the winners [n_sets][batch_size]
+    GrowBuf<double> sets_batch_scratch;
+    PinnedBuf<double> sets_batch_h_vals; PinnedBuf<int64_t> sets_batch_h_idxs;
     GrowBuf<double> append_part;                       // block append: slice sums of the pass over V [slices][kp][m_pad]
     GrowBuf<BatchState> batch_state;
     PinnedBuf<double> batch_h_vals; PinnedBuf<int64_t> batch_h_idxs;
@@ -2481,6 +2484,108 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
         else
             rc = cbo_acq_sweep(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
                                &best_vals[i], &best_idxs[i]);
+        if (rc != CBO_OK) return rc;
+    }
+    return CBO_OK;
+}
+
+// ---- greedy batch selection for every set of a trial (kernels_sets_batch.hip) ---------------------------------
+// batch_size Kriging-believer picks per set, set-major in best_vals / best_idxs: per set cbo_acq_sweep_batch's bits on a
+// fitted twin.  sweep_sets_impl's routing plus one cap: an fp64 model of at most 128 observations whose set has at most
+// kSmallBatchMaxCands candidates takes ONE small_sets_batch_kernel launch (no fit, no model or candidate state touched);
+// every other set -- and a set whose status word reports a non-positive pivot -- takes cbo_gp_fit when it is not fitted,
+// then cbo_acq_sweep_batch.  batch_size == 1 is cbo_acq_sweep_sets.
+// the winners array and the sets' V / W / q / mu scratch of one call
+static int ensure_small_batch_buffers(cbo_ctx *c, int n_sets, int blocks, int batch_size)
+{
+    const size_t winners = (size_t)(n_sets < 32 ? 32 : n_sets) * (size_t)batch_size;
+    int rc = grow(c, c->sets_batch_scratch, small_sets_batch_doubles(n_sets, blocks, batch_size));
+    if (rc == CBO_OK) rc = grow(c, c->sets_batch_h_vals, winners, true);
+    if (rc == CBO_OK) rc = grow(c, c->sets_batch_h_idxs, winners, true);
+    return rc;
+}
+
+extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
+                                        double ei_jitter, const double *costs, int batch_size, int update_incumbent,
+                                        double *best_vals, int64_t *best_idxs)
+{
+    // what needs no handle first
+    if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
+    if (!y_best || !costs || !best_vals || !best_idxs)
+        return fail(CBO_ERR_INVALID, "NULL argument: y_best, costs, best_vals and best_idxs must be given");
+    if (task != CBO_TASK_MIN && task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
+    if (batch_size < 1 || batch_size > CBO_MAX_BATCH)
+        return fail(CBO_ERR_INVALID, "batch_size must be in 1.." + std::to_string(CBO_MAX_BATCH));
+    if (update_incumbent != 0 && update_incumbent != 1) return fail(CBO_ERR_INVALID, "update_incumbent must be 0 or 1");
+    for (int i = 0; i < n_sets; ++i) {
+        if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive (set " + std::to_string(i) + ")");
+        if (!std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite (set " + std::to_string(i) + ")");
+    }
+    if (!gps || !cands) return fail(CBO_ERR_INVALID, "NULL argument: gps and cands must be given");
+    for (int i = 0; i < n_sets; ++i) {
+        int rc = check_sweep_args(gps[i], cands[i], task);
+        if (rc != CBO_OK) return rc;
+        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
+        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
+        if (batch_size > cands[i]->m)
+            return fail(CBO_ERR_INVALID, "batch_size exceeds the number of candidates (set " + std::to_string(i) + ")");
+    }
+    if (batch_size == 1)
+        return sweep_sets_impl(n_sets, gps, cands, y_best, task, ei_jitter, costs, best_vals, best_idxs, -1, kEiKind);
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int> small;
+    int blocks = 1;
+    for (int i = 0; i < n_sets; ++i) {
+        if (small_sweep_model(gps[i]) && cands[i]->m <= kSmallBatchMaxCands) {
+            small.push_back(i);
+            const int b = (int)((cands[i]->m + 63) / 64);
+            if (b > blocks) blocks = b;
+        }
+    }
+    std::vector<char> done((size_t)n_sets, 0);
+    if (!small.empty()) {
+        const int ns = (int)small.size();
+        int rc = ensure_small_buffers(c, ns, blocks);
+        if (rc == CBO_OK) rc = ensure_small_batch_buffers(c, ns, blocks, batch_size);
+        if (rc != CBO_OK) return rc;
+        for (int j = 0; j < ns; ++j) {
+            cbo_gp *g = gps[small[(size_t)j]];
+            cbo_cands *k = cands[small[(size_t)j]];
+            rc = prepare_cands(g, k);
+            if (rc != CBO_OK) return rc;
+            cbo_small_set &st = c->sets_host[j];
+            fill_small_model(st, g);
+            fill_small_cands(st, g, k);
+            st.task = task; st.y_best = y_best[small[(size_t)j]]; st.ei_jitter = ei_jitter; st.cost = costs[small[(size_t)j]];
+        }
+        auto launch = [&](int seq) -> int {
+            launch_small_sets_batch(c->stream, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val, c->small_part_idx,
+                                    c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq,
+                                    c->sets_batch_scratch, batch_size, update_incumbent, c->sets_batch_h_vals,
+                                    c->sets_batch_h_idxs);
+            HIP_TRY(hipGetLastError());
+            return CBO_OK;
+        };
+        rc = polled_launch(c, "cbo_acq_sweep_sets_batch", c->small_out.p, ns, "multi-set batch sweep: no result record", launch);
+        if (rc != CBO_OK) return rc;
+        for (int j = 0; j < ns; ++j) {
+            if (c->small_out[j].info != 0) continue;            // not positive definite as assembled: the general path
+            const size_t i = (size_t)small[(size_t)j];
+            for (int t = 0; t < batch_size; ++t) {
+                best_vals[i * (size_t)batch_size + (size_t)t] = c->sets_batch_h_vals.p[(size_t)j * (size_t)batch_size + (size_t)t];
+                best_idxs[i * (size_t)batch_size + (size_t)t] = c->sets_batch_h_idxs.p[(size_t)j * (size_t)batch_size + (size_t)t];
+            }
+            done[i] = 1;
+        }
+    }
+    for (int i = 0; i < n_sets; ++i) {
+        if (done[(size_t)i]) continue;
+        int rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
+        if (rc == CBO_OK)
+            rc = cbo_acq_sweep_batch(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], batch_size, update_incumbent,
+                                     best_vals + (size_t)i * (size_t)batch_size, best_idxs + (size_t)i * (size_t)batch_size,
+                                     nullptr, nullptr, nullptr);
         if (rc != CBO_OK) return rc;
     }
     return CBO_OK;

@@ -402,4 +402,55 @@ struct MesSetParams {
     double cost;
 };
 
+// ---- greedy batch selection: the arithmetic of one further pick, shared by batch_pivot_kernel,
+// batch_partial_kernel and batch_final_kernel (kernels_batch.hip: cbo_acq_sweep_batch) and small_sets_batch_kernel
+// (kernels_sets_batch.hip: cbo_acq_sweep_sets_batch) -- one definition, so the one-launch form returns
+// cbo_acq_sweep_batch's bits.
+// d of the believed point p: cbo_gp_predict's clipped latent variance (posterior_of without the noise) plus Ky's diagonal term
+__device__ __forceinline__ double batch_believer_sd(double variance, double pv_p, bool causal, double q_p, double noise_var)
+{
+#pragma clang fp contract(off)
+    const double kss = causal ? (variance + pv_p) : variance;
+    double lat = kss - q_p;
+    lat = (lat < kGpyVarClip) ? kGpyVarClip : lat;
+    const double s2 = (lat + noise_var) + kGpyDiagJitter;
+    return sqrt(s2);
+}
+// min(model.Y) once the believed point is in the data (max for the 'max' task); a NaN mean leaves it alone
+__device__ __forceinline__ double batch_moved_incumbent(double yb, double mu_p, double pm_p, bool causal, int task)
+{
+#pragma clang fp contract(off)
+    double mean = mu_p;
+    if (causal) mean = mean + pm_p;
+    return (task == CBO_TASK_MIN ? (mean < yb) : (mean > yb)) ? mean : yb;
+}
+// one row of the pass over V: the column's chain s += V_ip V_ij
+__device__ __forceinline__ double batch_pass_step(double l, double v, double s) { return __fma_rn(l, v, s); }
+// W_tj of candidate j: slice(r) = the r-th slice sum of the pass, wrow(r) = W_rj of the earlier fantasy rows, wp[r] = W_rp
+template <int D, class Slice, class Wrow>
+__device__ __forceinline__ double batch_fantasy_weight(int slices, Slice slice, int rows, const double *wp, Wrow wrow,
+                                                       const double *xp, const double *xj, double sqp, double sqj,
+                                                       bool causal, double svp, double svj, double variance, double inv_l2,
+                                                       double d)
+{
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int r = 0; r < slices; ++r) s = __dadd_rn(s, slice(r));
+    double ws = 0.0;
+    for (int r = 0; r < rows; ++r) ws = __fma_rn(wp[r], wrow(r), ws);
+    double kv = kernel_value<D>(xp, xj, sqp, sqj, variance, inv_l2, false);
+    if (causal) kv = __dadd_rn(kv, __dmul_rn(svp, svj));
+    const double c = __dadd_rn(__dadd_rn(kv, -s), -ws);
+    return c / d;
+}
+__device__ __forceinline__ double batch_q_update(double w, double q) { return __fma_rn(w, w, q); }
+// row slices of the pass over V: one per 64 rows, kBatchMaxSlices at the most
+__host__ __device__ inline int batch_slice_count(int64_t n)
+{
+    const int64_t s = (n + 63) / 64;
+    return (int)(s < 1 ? 1 : (s > kBatchMaxSlices ? kBatchMaxSlices : s));
+}
+// rows of one slice of the pass: ceil(ceil(n / slices) / 8) * 8
+__host__ __device__ inline int batch_rows_per_slice(int64_t n, int slices) { return (int)(((n + slices - 1) / slices + 7) / 8 * 8); }
+
 }  // namespace cbo

@@ -355,6 +355,23 @@ struct SmallAux {
 void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
                        double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
                        const SmallAux &aux = SmallAux());
+// the same launch with the batch epilogue (kernels_sets_batch.hip, small_sets_batch_kernel): batch_size >= 2
+// Kriging-believer picks per set.  Sets of at most kSmallBatchMaxCands candidates: the set's V = L^-1 K* stays in global
+// scratch (1 MiB per set at the cap) and the call's widest set has at most 16 candidate blocks.  batch_scratch:
+// small_sets_batch_doubles(...) doubles (V [128][m_pad], W [batch_size - 1][m_pad], q and mu [m_pad] per set, m_pad =
+// 64 blocks_per_set); h_vals / h_idxs (pinned, device-mapped): n_sets x batch_size winners, set-major, complete when
+// the set's record is; everything else as launch_small_sets.
+constexpr int kSmallBatchMaxCands = 1024;
+struct SmallBatchArgs {
+    double *V, *W, *q, *mu;
+    double *h_vals; int64_t *h_idxs;
+    int64_t m_pad;
+    int batch_size, update_incumbent;
+};
+size_t small_sets_batch_doubles(int n_sets, int blocks_per_set, int batch_size);
+void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
+                             double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
+                             double *batch_scratch, int batch_size, int update_incumbent, double *h_vals, int64_t *h_idxs);
 // the same launch with the constrained epilogue (kernels_sets_con.hip, small_sets_con_kernel): `pairs` holds
 // one descriptor per (model, candidate set) pair, a set's pairs consecutive with the objective first; a constraint's value,
 // jitter and sense ride in y_best, ei_jitter and task; pairs[s].pad_ = index of set s's first pair.  max_pairs = the most

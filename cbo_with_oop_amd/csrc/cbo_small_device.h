@@ -1,6 +1,7 @@
 // Device functions of the one-workgroup kernels, shared by the translation units that factor a block inside LDS
 // (kernels_chol.hip: the blocked factorisation's diagonal block, small_lml_kernel; kernels_sets.hip: small_sets_kernel;
-// kernels_sets_con.hip: small_sets_con_kernel; kernels_loo.hip: small_loo_batch_kernel; kernels_hyper.hip:
+// kernels_sets_con.hip: small_sets_con_kernel; kernels_sets_batch.hip: small_sets_batch_kernel; kernels_loo.hip:
+// small_loo_batch_kernel; kernels_hyper.hip:
 // hyper_avg_kernel, hyper_sets_kernel): the register Cholesky of a 16x16 tile, the decoupled-wave factorisation of a 128-row block, the tile
 // solve of a 128-row block for one wave's 16 columns, the model side of a small model (points, K(X,X) + diag, factor,
 // inverses and z), and the stages of a one-workgroup sweep (a wave's candidates, K*, the solve with q and mu, the
@@ -713,13 +714,18 @@ __device__ __forceinline__ void small_kstar_tiles_of(const SmallShared &sh, cons
 
 // V = L^-1 K* of one wave's 16 candidates, q = sum V^2, mu = V^T z: lane partials, then over the four lane groups (the strip
 // kernel's order).  The factor must be in LDS: the caller has waited (s_waitcnt vmcnt(0)) and synchronised.
-__device__ __forceinline__ void solve_q_mu(const SmallShared &sh, d4 (&acc)[8], const double (&iv)[8][4],
-                                           const double (&zr)[8][4], int tiles, int kq, int lc, double &qacc, double &macc)
+// keep(s, x): tile s of V as panel_solve_tiles emits it (x[r] = V[16 s + kq + 4 r][this lane's candidate]), for a caller
+// that stores V (small_sets_batch_kernel); it takes no part in q and mu.
+template <class Keep>
+__device__ __forceinline__ void solve_q_mu_keep(const SmallShared &sh, d4 (&acc)[8], const double (&iv)[8][4],
+                                                const double (&zr)[8][4], int tiles, int kq, int lc, double &qacc,
+                                                double &macc, Keep keep)
 {
 #pragma clang fp contract(off)
     qacc = 0.0;
     macc = 0.0;
     panel_solve_tiles(&sh.blk.S[kq][lc], acc, iv, tiles, [&](int s, const d4 &x) {
+        keep(s, x);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             qacc = fma(x[r], x[r], qacc);
@@ -730,6 +736,11 @@ __device__ __forceinline__ void solve_q_mu(const SmallShared &sh, d4 (&acc)[8], 
     qacc += __shfl_xor(qacc, 32);
     macc += __shfl_xor(macc, 16);
     macc += __shfl_xor(macc, 32);
+}
+__device__ __forceinline__ void solve_q_mu(const SmallShared &sh, d4 (&acc)[8], const double (&iv)[8][4],
+                                           const double (&zr)[8][4], int tiles, int kq, int lc, double &qacc, double &macc)
+{
+    solve_q_mu_keep(sh, acc, iv, zr, tiles, kq, lc, qacc, macc, [](int, const d4 &) {});
 }
 
 // posterior_of's and the epilogues' scalars from a descriptor (the predictive variance includes the noise)
@@ -763,23 +774,37 @@ __device__ __forceinline__ void small_block_argmax(SmallShared &sh, int lane, in
 
 // The last workgroup of a set to finish (an atomic ticket) reduces the set's per-workgroup winners, hands the result
 // record to the host (pinned, device-mapped memory; `seq` is stored last, after a system-scope fence, so that the host
-// can poll it) and re-arms the set's status word and ticket for the next call.
-__device__ __forceinline__ void small_set_finish(double bv, int64_t bi, int set, int slot, int blocks_per_set,
+// can poll it) and re-arms the set's status word and ticket for the next call.  Three steps, so that a kernel whose last
+// arriver goes on working for the set (small_sets_batch_kernel) takes them one by one:
+// the workgroup's winner to its slot and the ticket; true (every thread) in the set's last workgroup to arrive.
+// PUBLISH: the workgroup has stored more than its winner for the last arriver to read (every storing wave has drained
+// vmcnt(0) ahead of a barrier): the ticket is an agent-scope release of all of it -- the fence, its own wait, the add.
+template <bool PUBLISH = false>
+__device__ __forceinline__ bool small_set_ticket(double bv, int64_t bi, int set, int slot, int blocks_per_set,
                                                  double *__restrict__ part_val, int64_t *__restrict__ part_idx,
-                                                 int *__restrict__ info, int *__restrict__ ticket,
-                                                 cbo_small_result *__restrict__ out, int seq, int *last_flag)
+                                                 int *__restrict__ ticket, int *last_flag)
 {
-    const int tid = threadIdx.x;
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         part_val[slot] = bv;
         part_idx[slot] = bi;
-        __threadfence();
+        if (PUBLISH) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else {
+            __threadfence();
+        }
         *last_flag = (atomicAdd(&ticket[set], 1) == blocks_per_set - 1) ? 1 : 0;
     }
     __syncthreads();
-    if (*last_flag == 0 || tid >= 64) return;
-    __threadfence();
-    const int status = (tid == 0) ? atomicAdd(&info[set], 0) : 0;       // (in flight with the loads below)
+    return *last_flag != 0;
+}
+// wave 0 of the last arriver: the set's winner and status word (thread 0's on return)
+__device__ __forceinline__ void small_set_reduce(int set, int blocks_per_set, const double *__restrict__ part_val,
+                                                 const int64_t *__restrict__ part_idx, int *__restrict__ info, double &bv,
+                                                 int64_t &bi, int &status)
+{
+    const int tid = threadIdx.x;
+    status = (tid == 0) ? atomicAdd(&info[set], 0) : 0;                 // (in flight with the loads below)
     bv = -INFINITY;
     bi = INT64_MAX;
     for (int b = tid; b < blocks_per_set; b += 64) {
@@ -788,15 +813,30 @@ __device__ __forceinline__ void small_set_finish(double bv, int64_t bi, int set,
         if (better(v, i, bv, bi)) { bv = v; bi = i; }
     }
     wave_argmax(bv, bi);
-    if (tid == 0) {
-        out[set].best_val = bv;
-        out[set].best_idx = bi;
-        out[set].info = status;
-        __threadfence_system();
-        *reinterpret_cast<volatile int *>(&out[set].seq) = seq;
-        info[set] = 0;
-        ticket[set] = 0;
-    }
+}
+// thread 0 of the last arriver: the record, then the set's words re-armed
+__device__ __forceinline__ void small_set_record(double bv, int64_t bi, int status, int set, int *__restrict__ info,
+                                                 int *__restrict__ ticket, cbo_small_result *__restrict__ out, int seq)
+{
+    out[set].best_val = bv;
+    out[set].best_idx = bi;
+    out[set].info = status;
+    __threadfence_system();
+    *reinterpret_cast<volatile int *>(&out[set].seq) = seq;
+    info[set] = 0;
+    ticket[set] = 0;
+}
+__device__ __forceinline__ void small_set_finish(double bv, int64_t bi, int set, int slot, int blocks_per_set,
+                                                 double *__restrict__ part_val, int64_t *__restrict__ part_idx,
+                                                 int *__restrict__ info, int *__restrict__ ticket,
+                                                 cbo_small_result *__restrict__ out, int seq, int *last_flag)
+{
+    if (!small_set_ticket(bv, bi, set, slot, blocks_per_set, part_val, part_idx, ticket, last_flag) || threadIdx.x >= 64)
+        return;
+    __threadfence();
+    int status;
+    small_set_reduce(set, blocks_per_set, part_val, part_idx, info, bv, bi, status);
+    if (threadIdx.x == 0) small_set_record(bv, bi, status, set, info, ticket, out, seq);
 }
 
 // Up to kSmallByValue descriptors travel as kernel arguments (no read across the host link before the first

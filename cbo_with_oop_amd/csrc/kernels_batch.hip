@@ -38,23 +38,13 @@ __global__ __launch_bounds__(256) void batch_pivot_kernel(BatchPivotArgs a)
     }
     if (threadIdx.x == 65) {
         const bool causal = a.pv != nullptr;
-        // cbo_gp_predict's clipped latent variance (posterior_of without the noise) plus Ky's diagonal term
-        const double kss = causal ? (a.variance + a.pv[p]) : a.variance;
-        double lat = kss - a.q[p];
-        lat = (lat < kGpyVarClip) ? kGpyVarClip : lat;
-        const double s2 = (lat + a.noise_var) + kGpyDiagJitter;
-        st->d = sqrt(s2);
+        st->d = batch_believer_sd(a.variance, causal ? a.pv[p] : 0.0, causal, a.q[p], a.noise_var);
         for (int k = 0; k < CBO_MAX_DIM; ++k) st->x[k] = (k < a.dims) ? a.xs[(int64_t)k * a.ldx + p] : 0.0;
         st->sq = a.sq[p];
         st->sv = (causal && a.sv) ? a.sv[p] : 0.0;
         st->p = p;
-        if (a.update_incumbent) {
-            double mean = a.mu[p];
-            if (causal) mean = mean + a.pm[p];
-            const double yb = st->y_best;
-            // min(model.Y) once the believed point is in the data (max for the 'max' task); a NaN mean leaves it alone
-            if (a.task == CBO_TASK_MIN ? (mean < yb) : (mean > yb)) st->y_best = mean;
-        }
+        if (a.update_incumbent)
+            st->y_best = batch_moved_incumbent(st->y_best, a.mu[p], causal ? a.pm[p] : 0.0, causal, a.task);
     }
 }
 
@@ -102,15 +92,15 @@ __global__ __launch_bounds__(256) void batch_partial_kernel(const double *__rest
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const double l = ls[t + u];
-                    s[0] = __fma_rn(l, v[u][0], s[0]);
-                    s[1] = __fma_rn(l, v[u][1], s[1]);
+                    s[0] = batch_pass_step(l, v[u][0], s[0]);
+                    s[1] = batch_pass_step(l, v[u][1], s[1]);
                 }
             }
             for (; t < cnt; ++t) {
                 const d2 v = *reinterpret_cast<const d2 *>(vp + (int64_t)t * ldv);
                 const double l = ls[t];
-                s[0] = __fma_rn(l, v[0], s[0]);
-                s[1] = __fma_rn(l, v[1], s[1]);
+                s[0] = batch_pass_step(l, v[0], s[0]);
+                s[1] = batch_pass_step(l, v[1], s[1]);
             }
         }
     }
@@ -127,29 +117,21 @@ __global__ __launch_bounds__(256) void batch_final_kernel(BatchFinalArgs a)
     double *wrow = a.W + (int64_t)(a.t - 1) * a.m_pad;
     if (j >= a.m) { wrow[j] = 0.0; return; }
     const BatchState *st = a.state;
-    double s = 0.0;
-    for (int r = 0; r < a.slices; ++r) s = __dadd_rn(s, a.partial[(int64_t)r * a.m_pad + j]);
-    double ws = 0.0;
-    for (int r = 0; r < a.t - 1; ++r) ws = __fma_rn(st->wp[r], a.W[(int64_t)r * a.m_pad + j], ws);
     double xp[D], xj[D];
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         xp[k] = st->x[k];
         xj[k] = a.xs[(int64_t)k * a.ldx + j];
     }
-    double kv = kernel_value<D>(xp, xj, st->sq, a.sq[j], a.variance, a.inv_l2, false);
-    if (a.sv) kv = __dadd_rn(kv, __dmul_rn(st->sv, a.sv[j]));
-    const double c = __dadd_rn(__dadd_rn(kv, -s), -ws);
-    const double w = c / st->d;
+    const double w = batch_fantasy_weight<D>(
+        a.slices, [&](int r) { return a.partial[(int64_t)r * a.m_pad + j]; }, a.t - 1, st->wp,
+        [&](int r) { return a.W[(int64_t)r * a.m_pad + j]; }, xp, xj, st->sq, a.sq[j], a.sv != nullptr, st->sv,
+        a.sv ? a.sv[j] : 0.0, a.variance, a.inv_l2, st->d);
     wrow[j] = w;
-    a.q[j] = __fma_rn(w, w, a.q[j]);
+    a.q[j] = batch_q_update(w, a.q[j]);
 }
 
-int batch_slices(int64_t n)
-{
-    const int64_t s = (n + 63) / 64;
-    return (int)(s < 1 ? 1 : (s > kBatchMaxSlices ? kBatchMaxSlices : s));
-}
+int batch_slices(int64_t n) { return batch_slice_count(n); }
 
 void launch_batch_state_init(hipStream_t s, BatchState *st, double y_best)
 {
@@ -167,7 +149,7 @@ void launch_batch_pick(hipStream_t s, const BatchPivotArgs &pa, BatchFinalArgs f
     const int64_t n = pa.n;
     hipLaunchKernelGGL(batch_pivot_kernel, dim3((unsigned)(n > 0 ? (n + 255) / 256 : 1)), dim3(256), 0, s, pa);
     const int slices = batch_slices(n);
-    const int rows_per_slice = (int)(((n + slices - 1) / slices + 7) / 8 * 8);
+    const int rows_per_slice = batch_rows_per_slice(n, slices);
     if (n > 0)
         hipLaunchKernelGGL(batch_partial_kernel, dim3((unsigned)((pa.m_pad + 511) / 512), (unsigned)slices), dim3(256), 0, s,
                            pa.V, pa.ldv, n, rows_per_slice, col, pa.m_pad, partial);

@@ -310,7 +310,8 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
 
 
 def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
-                       acquisition="EI", acquisition_param=None, hyper_samples=None, spaces=None, constraints=None):
+                       acquisition="EI", acquisition_param=None, hyper_samples=None, spaces=None, batch_size=None,
+                       update_incumbent=False, constraints=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -343,10 +344,19 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     space) / Cost`` for every set in two device calls -- ``max_value_entropy.mes_sets_parameters`` (every
     set's Gumbel fit, ``cbo_gp_mes_gumbel_sets``; it draws from numpy's global generator in the order documented there),
     then ``cbo_acq_sweep_sets_mes``.  ``task`` other than ``"min"``, missing ``spaces``, ``raw=True``, non-empty
-    ``constraints`` and ``hyper_samples`` raise ``ValueError`` before any device call."""
+    ``constraints`` and ``hyper_samples`` raise ``ValueError`` before any device call.
+    ``batch_size`` (a positive int B, at most 64 and at most every grid's size) with ``update_incumbent``: greedy batch
+    selection for every set in ONE device call (``cbo_acq_sweep_sets_batch``) -- per set what
+    ``find_next_y_point(batch_size=B)`` returns: ``xs[s]`` is (B, d), ``ys[s]`` (B, 1), row 0 the single-point result.  Under
+    variable costs ``ys[s][0]`` is today's re-evaluation and the later picks are rescaled from the batch cost to the point's
+    own.  Another ``acquisition`` than ``"EI"``, non-empty ``constraints``, ``hyper_samples`` and ``raw=True`` raise
+    ``ValueError`` before any device call.  ``None`` takes exactly today's calls."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    batch_size = checked_batch_size(batch_size, kind, constraints, hyper_samples, raw)
+    if batch_size is not None and task not in _lib.TASK_CODE:
+        raise ValueError(f"task must be 'min' or 'max', not {task!r}")
     if kind[0] == "MES":
         if task != "min":
             raise ValueError("acquisition='MES' minimises: task must be 'min'")
@@ -392,6 +402,11 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     if st.get("hyper_rows") is not None or hyper_rows is not None:
         st.pop("trial_args", None)               # (likewise: the one-call trial step names the plug-in call)
     st["hyper_rows"] = hyper_rows
+    if st.get("batch_size") != batch_size:
+        st.pop("trial_args", None)               # (a batch takes the three-call route; back at None the call is made anew)
+    st["batch_size"] = batch_size
+    if batch_size is not None:
+        return _sweep_sets_batch(st, models, grids, current_global_best, task, batch_size, bool(update_incumbent))
     if hyper_rows is not None:
         # (the entry keeps the row arrays and the pointer array alive; the rows change from trial to trial)
         st["hyper_args"] = ((ctypes.c_int * s)(*[r.shape[0] for r in hyper_rows]),
@@ -436,6 +451,65 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     if raw:
         return None, [(float(vals[i]), int(idxs[i])) for i in range(s)]
     return winners_to_points(st, models, grids, current_global_best, task)
+
+
+def checked_batch_size(batch_size, kind=("EI", None), constraints=None, hyper_samples=None, raw=False):
+    """``batch_size`` of a multi-set sweep, a path or an agent, checked on the host before any device call: ``None``, or
+    an int in 1..64 -- with the causal EI, no (non-empty) constraints, no hyper-parameter samples and a single rank."""
+    if batch_size is None:
+        return None
+    from .. import _lib
+    if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError(f"batch_size must be a positive int, not {batch_size!r}")
+    if batch_size > _lib.MAX_BATCH:
+        raise ValueError(f"batch_size must be at most {_lib.MAX_BATCH}, not {batch_size}")
+    if kind[0] != "EI":
+        raise ValueError("batch selection believes the causal EI's model: acquisition must be 'EI'")
+    if constraints is not None and any(constraints):
+        raise ValueError("batch selection is not defined for constrained acquisitions: constraints must be None or empty")
+    if hyper_samples is not None:
+        raise ValueError("batch selection is not defined for the marginalised EI: hyper_samples must be None")
+    if raw:
+        raise ValueError("batch selection is not defined across several ranks (raw=True)")
+    return int(batch_size)
+
+
+def _sweep_sets_batch(st, models, grids, current_global_best, task, batch_size, update_incumbent):
+    """The batch form of ``find_next_y_points``' device call: one ``cbo_acq_sweep_sets_batch``, its set-major winners as
+    (B, d) points and (B, 1) values per set (``_next_y_points_batch``'s treatment of variable costs)."""
+    from .. import _lib
+    s = len(models)
+    for i in range(s):
+        if batch_size > grids[i].points.shape[0]:
+            raise ValueError(f"batch_size {batch_size} exceeds the {grids[i].points.shape[0]} candidates of set {i}")
+    vals, idxs = np.empty(s * batch_size), np.empty(s * batch_size, dtype=np.int64)
+    _lib.check(_lib.load().cbo_acq_sweep_sets_batch(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
+                                                    _lib.dptr(st["batch_cost"]), batch_size, int(update_incumbent),
+                                                    _lib.dptr(vals), idxs.ctypes.data_as(_lib.c_int64_p)))
+    vals, idxs = vals.reshape(s, batch_size), idxs.reshape(s, batch_size)
+    st["vals"][:], st["idxs"][:] = vals[:, 0], idxs[:, 0]
+    xs, ys = [], []
+    for i in range(s):
+        # The library's static routing, mirrored: a set the one launch does not take was fitted by the general path inside
+        # the call -- a larger or fp32 model always; a grid above the cap only when batch_size > 1 (a batch of one is
+        # cbo_acq_sweep_sets' route, which takes a small model whatever its grid and does not fit it).  The library has no
+        # query for "fitted": a small set that fell to the general path at run time (a non-positive pivot in the launch,
+        # CBO_HIP_SMALL_SETS=0) is fitted too but stays ``stale`` here, which costs one redundant refit later, never a
+        # wrong answer.
+        if not models[i].small or (batch_size > 1 and grids[i].points.shape[0] > _lib.SMALL_BATCH_MAX_CANDS):
+            models[i].stale = False
+        x_new = grids[i].points[idxs[i] - grids[i].index_offset].copy()
+        y = vals[i].reshape(-1, 1).copy()
+        batch_cost = float(st["batch_cost"][i])
+        for t in range(batch_size):
+            point_cost = float(st["costs"][i].evaluate(x_new[t:t + 1]))
+            if point_cost != batch_cost:
+                y[t, 0] = (CausalExpectedImprovement(current_global_best, task, models[i]).sweep(
+                    x_new[t:t + 1], cost=point_cost, want_acq=True)["acq"][0, 0] if t == 0
+                           else y[t, 0] * batch_cost / point_cost)
+        xs.append(x_new)
+        ys.append(y)
+    return xs, ys
 
 
 def checked_set_hyper_samples(hyper_samples, models, kind=("EI", None), constraints=None, raw=False):

@@ -593,8 +593,9 @@ int cbo_trial_step(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int 
  * cbo_acq_sweep_sets_kind + cbo_argmax_sets.
  * CBO_ERR_INVALID, before any model is touched: cbo_acq_sweep_sets' (cbo_trial_step's) argument checks, a kind outside 1..4,
  * a non-finite param, beta < 0, a non-finite y_best[i] for CBO_ACQ_PI, costs[i] <= 0 or NaN, a bad task for every kind but
- * CBO_ACQ_VAR.  Out of scope: batch epilogues in the one launch (the constrained one is cbo_acq_sweep_sets_constrained,
- * the hyper-marginalised one cbo_acq_sweep_sets_hyper, max-value entropy search cbo_acq_sweep_sets_mes, below). */
+ * CBO_ACQ_VAR.  The other epilogues of the one launch are calls of their own, below: the constrained one is
+ * cbo_acq_sweep_sets_constrained, the hyper-marginalised one cbo_acq_sweep_sets_hyper, max-value entropy search
+ * cbo_acq_sweep_sets_mes, greedy batch selection cbo_acq_sweep_sets_batch. */
 int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int kind, const double *y_best,
                             int task, double param, const double *costs, double *best_vals, int64_t *best_idxs);
 int cbo_trial_step_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int refit_set, int64_t n,
@@ -688,6 +689,28 @@ int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cands *const *c
 int cbo_acq_sweep_sets_mes(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
                            const double *const *mins, const double *costs, double *best_vals, int64_t *best_idxs);
 int cbo_gp_mes_gumbel_sets(int n_sets, cbo_gp *const *gps, cbo_cands *const *grids, double *quantiles, double *a, double *b);
+
+/* cbo_acq_sweep_sets for greedy batch selection: batch_size Kriging-believer picks (cbo_acq_sweep_batch,
+ * §4g) for every exploration set of a trial.  best_vals and best_idxs hold n_sets x batch_size entries, set-major: pick t of
+ * set i is at [i * batch_size + t].
+ * Contract: for every set i the batch_size (value, index) pairs are bit for bit those of cbo_acq_sweep_batch(gps[i],
+ * cands[i], y_best[i], task, ei_jitter, costs[i], batch_size, update_incumbent, ...) on a fitted twin of the model: its
+ * formulas, clip, tie rule (lowest index, NaN maximal, index_offset applied), 'max'-task sign and update_incumbent
+ * semantics; a pick may repeat a point.  Pick 0 is cbo_acq_sweep_sets' result; batch_size == 1 IS cbo_acq_sweep_sets.
+ * Routing is cbo_acq_sweep_sets' plus one cap: an fp64 model of at most 128 observations (CBO_HIP_SMALL_SETS on) whose set
+ * has at most 1024 candidates is answered by ONE launch (small_sets_batch_kernel; two from 12 candidate blocks per set on):
+ * the workgroups of a set leave V = L^-1 K*, q and mu in global scratch and the last of them to arrive runs the further
+ * picks.  Those models need no fit, and nothing of them or of their candidate sets is touched: fitted flag, factor, cached
+ * q / mu, kept V and stamps stay; an unfitted model is still unfitted afterwards.  Every other set -- a larger or fp32 model,
+ * more than 1024 candidates, a non-positive pivot in the launch -- takes cbo_gp_fit if unfitted, then cbo_acq_sweep_batch,
+ * inside the same call.
+ * CBO_ERR_INVALID, before any model is touched (what needs no handle is checked first): n_sets <= 0; a NULL y_best, costs,
+ * best_vals or best_idxs; a bad task; batch_size outside 1..CBO_MAX_BATCH; update_incumbent other than 0 / 1; costs[i] <= 0
+ * or NaN; a non-finite y_best[i]; then cbo_acq_sweep_sets' checks of the handles and batch_size above a set's number of
+ * candidates. */
+int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
+                             double ei_jitter, const double *costs, int batch_size, int update_incumbent,
+                             double *best_vals, int64_t *best_idxs);
 
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
