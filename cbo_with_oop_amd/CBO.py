@@ -88,13 +88,17 @@ class CBOAcquisitionPath:
     ``batch_size`` (an int B in 1..64) with ``update_incumbent`` makes every set's answer a greedy batch of B Kriging-believer
     picks in one device call (``find_next_y_points(batch_size=B)``): ``xs[s]`` is (B, d), ``ys[s]`` (B, 1); the
     set is chosen by pick 0, as before.  It needs ``acquisition="EI"``, no constraints, no hyper-parameter samples and a
+    single process, and its ``trial_step`` takes the three-call route.
+    ``refine=True`` adds the reference's second stage (``find_next_y_points(refine=True)``): every set's
+    winner is refined by L-BFGS inside the set's box from ``space_list``, all sets in one further device call, and kept only
+    if it is not lower.  It needs ``"EI"`` or a point-wise kind, no constraints, no hyper-parameter samples, no batch and a
     single process, and its ``trial_step`` takes the three-call route."""
 
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
-                 update_incumbent=False):
-        from .utils_functions.utils import sets_acquisition_or_default as sets_acquisition
+                 update_incumbent=False, refine=False):
+        from .utils_functions.utils import checked_refine, sets_acquisition_or_default as sets_acquisition
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
         self._kind = sets_acquisition(acquisition, acquisition_param)
@@ -113,6 +117,8 @@ class CBOAcquisitionPath:
         self.hyper_rows = [None] * len(exploration_set)
         self.batch_size = checked_batch_size(batch_size, self._kind, self.constraints, self.hyper_samples)
         self.update_incumbent = bool(update_incumbent)
+        self.refine = checked_refine(refine, self._kind, self.constraints, self.hyper_samples, self.batch_size, False,
+                                     space_list, len(exploration_set))
         self.gp_type = gp_type
         self.exploration_set = exploration_set
         self.es_size = len(exploration_set)
@@ -270,13 +276,16 @@ class CBOAcquisitionPath:
             raise ValueError(f"max-value entropy search is scored by a single process: the placement is {mode!r}")
         if self.batch_size is not None and mode != "single":
             raise ValueError(f"batch selection is scored by a single process: the placement is {mode!r}")
+        if self.refine and mode != "single":
+            raise ValueError(f"gradient refinement is run by a single process: the placement is {mode!r}")
         if mode == "single":
             grids = [self.candidate_grid(s) for s in range(self.es_size)]
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
                                       cache=self._call_cache, acquisition=self._kind, constraints=self.set_constraints(),
                                       hyper_samples=None if self.hyper_samples is None else list(self.hyper_rows),
-                                      spaces=self.space_list if self._kind[0] == "MES" else None,
-                                      batch_size=self.batch_size, update_incumbent=self.update_incumbent)
+                                      spaces=self.space_list if (self._kind[0] == "MES" or self.refine) else None,
+                                      batch_size=self.batch_size, update_incumbent=self.update_incumbent,
+                                      refine=self.refine)
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -347,7 +356,7 @@ class CBOAcquisitionPath:
         st = self._call_cache.get("sweep_sets")
         model = self.models[s] if (s is not None and self.models) else None
         fast = (st is not None and model is not None and not self.constraints and self.hyper_samples is None
-                and self._kind[0] != "MES" and self.batch_size is None
+                and self._kind[0] != "MES" and self.batch_size is None and not self.refine
                 and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
                 and model._hyper_initial and st["cost_table"] is self.costs
@@ -448,7 +457,9 @@ class CBO(CBOAcquisitionPath):
     ``batch_size`` (an int B in 1..64) with ``update_incumbent``: ``intervene()`` runs the B interventions of a greedy batch on
     the chosen set side by side: the monitor evaluates the B rows, appends them in order and records
     ``chosen`` as ``(set, x (B, d))``; the trial's cost is the sum of the B interventions' costs.  ``None``: the reference's
-    one intervention per trial."""
+    one intervention per trial.
+    ``refine=True``: every set's winner is refined by L-BFGS inside the set's interventional ranges before the set is chosen
+    (``CBOAcquisitionPath(refine=True)``) -- the reference's continuous optimum instead of a grid point."""
 
     TARGET = "Y"
 
@@ -456,11 +467,11 @@ class CBO(CBOAcquisitionPath):
                  num_interventions=10, initial_num_obs_samples=100, causal_prior=False, num_trials=40, task="min",
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
-                 constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False):
+                 constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType
         from .graphs import _columns
-        from .utils_functions.utils import sets_acquisition_or_default as sets_acquisition
+        from .utils_functions.utils import checked_refine, sets_acquisition_or_default as sets_acquisition
         self.graph = graph() if isinstance(graph, type) else graph
         self.measurements = _columns(measurements)
         self.all_measurements = _columns(all_measurements)
@@ -500,6 +511,8 @@ class CBO(CBOAcquisitionPath):
         path_constraints = checked_path_constraints(path_constraints, sets_acquisition(acquisition, acquisition_param))
         checked_path_hyper_samples(hyper_samples, sets_acquisition(acquisition, acquisition_param), path_constraints)
         checked_batch_size(batch_size, sets_acquisition(acquisition, acquisition_param), path_constraints, hyper_samples)
+        checked_refine(refine, sets_acquisition(acquisition, acquisition_param), path_constraints, hyper_samples, batch_size,
+                       False, [self.graph.bounds(s) for s in exploration], len(exploration))
         sem = None
         if path_constraints and constraint_functions is None:
             from functools import partial
@@ -515,7 +528,7 @@ class CBO(CBOAcquisitionPath):
                          [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None,
                          acquisition=acquisition, acquisition_param=acquisition_param, constraints=path_constraints,
                          constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
-                         update_incumbent=update_incumbent)
+                         update_incumbent=update_incumbent, refine=refine)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions

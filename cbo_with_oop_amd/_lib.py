@@ -37,6 +37,12 @@ CBO_ERR_COMM = -8
 TASK_CODE = {"min": 0, "max": 1}
 DTYPE_CODE = {"f64": 0, "f32": 1}
 ACQ_KIND_CODE = {"LCB": 1, "PI": 2, "VAR": 3, "MPEI": 4}      # CBO_ACQ_LCB, _PI, _VAR, _MPEI
+REFINE_KIND_CODE = dict(ACQ_KIND_CODE, EI=0)                  # cbo_acq_refine_sets: 0 = the causal Expected Improvement
+REFINE_MAX_STARTS = 64       # CBO_REFINE_MAX_STARTS
+REFINE_ROUNDS_LIMIT = 1000   # CBO_REFINE_ROUNDS_LIMIT
+REFINE_PGTOL, REFINE_FTOL, REFINE_STEP, REFINE_MAX_ROUNDS, REFINE_NAN_START, REFINE_DECLINED = range(6)   # CBO_REFINE_*
+REFINE_STATUS_NAME = {REFINE_PGTOL: "pgtol", REFINE_FTOL: "ftol", REFINE_STEP: "step", REFINE_MAX_ROUNDS: "max_rounds",
+                      REFINE_NAN_START: "nan_start", REFINE_DECLINED: "declined"}
 
 
 class CboTimers(ctypes.Structure):
@@ -60,6 +66,12 @@ class CboSemSpec(ctypes.Structure):
                 ("term_begin", ctypes.c_int * (SEM_MAX_NODES + 1)), ("term_parent", ctypes.c_int * SEM_MAX_TERMS),
                 ("term_fn", ctypes.c_int * SEM_MAX_TERMS), ("term_a", ctypes.c_double * SEM_MAX_TERMS),
                 ("term_c", ctypes.c_double * SEM_MAX_TERMS)]
+
+
+class CboRefineSet(ctypes.Structure):
+    """struct cbo_refine_set of include/cbo_hip.h."""
+    _fields_ = [("k", ctypes.c_int), ("starts", c_double_p), ("lo", c_double_p), ("hi", c_double_p),
+                ("cost_fix", c_double_p), ("cost_variable", c_int_p)]
 
 
 class CboHipError(RuntimeError):
@@ -164,6 +176,9 @@ SIGNATURES = {
                                               c_int64_p]),
     "cbo_acq_sweep_sets_batch": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, ctypes.c_int, ctypes.c_double,
                                                 c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_int64_p]),
+    "cbo_acq_refine_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), ctypes.c_int, c_double_p,
+                                           ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                           c_int_p, c_int_p]),
     "cbo_gp_mes_gumbel_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_double_p]),
     "cbo_comm_gather_i64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_int64_p]),

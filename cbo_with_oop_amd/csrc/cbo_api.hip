@@ -168,6 +168,12 @@ struct cbo_ctx {
     // cbo_acq_sweep_sets_batch: every small set's V, W, q and mu (small_sets_batch_doubles), the winners [n_sets][batch_size]
     GrowBuf<double> sets_batch_scratch;
     PinnedBuf<double> sets_batch_h_vals; PinnedBuf<int64_t> sets_batch_h_idxs;
+    // cbo_acq_refine_sets: the sets' search descriptors, starts and results as the kernel reads and writes them (pinned),
+    // one status word per set
+    PinnedBuf<cbo_small_refine> refine_host;
+    PinnedBuf<double> refine_starts, refine_x, refine_grad, refine_val;
+    PinnedBuf<int> refine_rounds, refine_status;
+    GrowBuf<int> refine_info;
     GrowBuf<double> append_part;                       // block append: slice sums of the pass over V [slices][kp][m_pad]
     GrowBuf<BatchState> batch_state;
     PinnedBuf<double> batch_h_vals; PinnedBuf<int64_t> batch_h_idxs;
@@ -2587,6 +2593,131 @@ extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cand
                                      best_vals + (size_t)i * (size_t)batch_size, best_idxs + (size_t)i * (size_t)batch_size,
                                      nullptr, nullptr, nullptr);
         if (rc != CBO_OK) return rc;
+    }
+    return CBO_OK;
+}
+
+// ---- gradient refinement of every set's starts (kernels_sets_refine.hip) -----------------------------------
+// One launch for every set the kernel takes (small_sweep_model, no prior); the others are declined here, their status
+// entries alone written.  The models are only read.
+extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int kind, const double *y_best,
+                                   int task, double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
+                                   int *rounds_out, int *status_out)
+{
+    if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
+    if (!gps || !sets || !y_best || !x_out || !val_out || !grad_out || !rounds_out || !status_out)
+        return fail(CBO_ERR_INVALID, "NULL argument");
+    if (max_rounds < 0 || max_rounds > CBO_REFINE_ROUNDS_LIMIT)
+        return fail(CBO_ERR_INVALID, "max_rounds must be in 0.." + std::to_string(CBO_REFINE_ROUNDS_LIMIT));
+    if (kind != kEiKind) {
+        std::vector<double> ones((size_t)n_sets, 1.0);
+        const int rc = check_kind_args(n_sets, kind, y_best, &task, &param, ones.data());
+        if (rc != CBO_OK) return rc;
+    } else {
+        if (task != CBO_TASK_MIN && task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
+        if (!std::isfinite(param)) return fail(CBO_ERR_INVALID, "the jitter must be finite");
+    }
+    for (int i = 0; i < n_sets; ++i) {
+        const std::string where = " (set " + std::to_string(i) + ")";
+        const cbo_refine_set &rs = sets[i];
+        if (!gps[i]) return fail(CBO_ERR_INVALID, "NULL gp" + where);
+        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
+        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data" + where);
+        if (rs.k < 1 || rs.k > CBO_REFINE_MAX_STARTS)
+            return fail(CBO_ERR_INVALID, "the number of starts must be in 1.." + std::to_string(CBO_REFINE_MAX_STARTS) + where);
+        if (!rs.starts || !rs.lo || !rs.hi || !rs.cost_fix || !rs.cost_variable)
+            return fail(CBO_ERR_INVALID, "NULL argument: starts, lo, hi, cost_fix and cost_variable must be given" + where);
+        const int d = gps[i]->d;
+        double fix_sum = 0.0;
+        for (int k = 0; k < d; ++k) {
+            if (!std::isfinite(rs.lo[k]) || !std::isfinite(rs.hi[k])) return fail(CBO_ERR_INVALID, "the bounds must be finite" + where);
+            if (rs.lo[k] > rs.hi[k]) return fail(CBO_ERR_INVALID, "a lower bound exceeds its upper bound" + where);
+            if (!std::isfinite(rs.cost_fix[k])) return fail(CBO_ERR_INVALID, "the fixed costs must be finite" + where);
+            if (rs.cost_variable[k] != 0 && rs.cost_variable[k] != 1)
+                return fail(CBO_ERR_INVALID, "cost_variable must be 0 or 1" + where);
+            fix_sum += rs.cost_fix[k];
+        }
+        if (!(fix_sum > 0.0)) return fail(CBO_ERR_INVALID, "the fixed costs must sum to a positive cost" + where);
+        for (int64_t e = 0; e < (int64_t)rs.k * d; ++e)
+            if (!std::isfinite(rs.starts[e])) return fail(CBO_ERR_INVALID, "the starts must be finite" + where);
+        if (kind == kEiKind && !std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite" + where);
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    // where each set's rows begin in the caller's arrays; which sets the launch takes
+    std::vector<int64_t> row_off((size_t)n_sets);
+    std::vector<int> out_off((size_t)n_sets), small;
+    int64_t rows = 0;
+    int outs = 0, blocks = 1;
+    for (int i = 0; i < n_sets; ++i) {
+        row_off[(size_t)i] = rows;
+        out_off[(size_t)i] = outs;
+        rows += (int64_t)sets[i].k * gps[i]->d;
+        outs += sets[i].k;
+        if (small_sweep_model(gps[i]) && gps[i]->X.sv == nullptr) {
+            small.push_back(i);
+            const int per = small_refine_starts_per_block(gps[i]->d);
+            const int b = (sets[i].k + per - 1) / per;
+            if (b > blocks) blocks = b;
+        } else {
+            for (int s = 0; s < sets[i].k; ++s) status_out[outs - sets[i].k + s] = CBO_REFINE_DECLINED;
+        }
+    }
+    if (small.empty()) return CBO_OK;
+    const int ns = (int)small.size();
+    int rc = ensure_small_buffers(c, ns, blocks);
+    const size_t cap = ns < 32 ? (size_t)32 : (size_t)ns;
+    if (rc == CBO_OK) rc = grow(c, c->refine_host, cap);
+    if (rc == CBO_OK) rc = grow(c, c->refine_info, cap);
+    if (rc == CBO_OK) rc = grow(c, c->refine_starts, (size_t)rows);
+    if (rc == CBO_OK) rc = grow(c, c->refine_x, (size_t)rows);
+    if (rc == CBO_OK) rc = grow(c, c->refine_grad, (size_t)rows);
+    if (rc == CBO_OK) rc = grow(c, c->refine_val, (size_t)outs);
+    if (rc == CBO_OK) rc = grow(c, c->refine_rounds, (size_t)outs);
+    if (rc == CBO_OK) rc = grow(c, c->refine_status, (size_t)outs);
+    if (rc != CBO_OK) return rc;
+    for (int j = 0; j < ns; ++j) {
+        const int i = small[(size_t)j];
+        const cbo_gp *g = gps[i];
+        cbo_small_set &st = c->sets_host[j];
+        fill_small_model(st, g);
+        st.cxs = st.csq = st.csv = st.cpm = st.cpv = nullptr;
+        st.cld = 0; st.m = 0; st.index_offset = 0;
+        st.task = task; st.y_best = (kind == kEiKind || kind == CBO_ACQ_PI) ? y_best[i] : 0.0;
+        st.ei_jitter = param;
+        st.cost = 1.0;                                         // (the kernel prices every point itself)
+        cbo_small_refine &rf = c->refine_host[j];
+        std::memset(&rf, 0, sizeof(rf));
+        for (int k = 0; k < g->d; ++k) {
+            rf.lo[k] = sets[i].lo[k]; rf.hi[k] = sets[i].hi[k];
+            rf.fix[k] = sets[i].cost_fix[k]; rf.variable[k] = sets[i].cost_variable[k];
+            rf.ls[k] = g->h.ard ? g->ls[(size_t)k] : 1.0;
+        }
+        rf.row_off = row_off[(size_t)i]; rf.out_off = out_off[(size_t)i];
+        rf.k = sets[i].k; rf.ard = g->h.ard;
+        std::memcpy(c->refine_starts.p + rf.row_off, sets[i].starts, sizeof(double) * (size_t)rf.k * (size_t)g->d);
+        for (int s = 0; s < rf.k; ++s) c->refine_status[rf.out_off + s] = CBO_REFINE_DECLINED;
+    }
+    HIP_TRY(hipMemsetAsync(c->refine_info, 0, sizeof(int) * (size_t)ns, c->stream));
+    launch_small_sets_refine(c->stream, kind, c->sets_host, c->refine_host, c->refine_starts, ns, blocks, c->small_scratch,
+                             c->refine_info, max_rounds, c->refine_x, c->refine_val, c->refine_grad, c->refine_rounds,
+                             c->refine_status);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int j = 0; j < ns; ++j) {
+        const int i = small[(size_t)j];
+        const cbo_small_refine &rf = c->refine_host[j];
+        const int d = gps[i]->d;
+        bool declined = false;
+        for (int s = 0; s < rf.k; ++s) declined = declined || c->refine_status[rf.out_off + s] == CBO_REFINE_DECLINED;
+        for (int s = 0; s < rf.k; ++s) {
+            status_out[rf.out_off + s] = declined ? CBO_REFINE_DECLINED : c->refine_status[rf.out_off + s];
+            if (declined) continue;
+            rounds_out[rf.out_off + s] = c->refine_rounds[rf.out_off + s];
+            val_out[rf.out_off + s] = c->refine_val[rf.out_off + s];
+            std::memcpy(x_out + rf.row_off + (int64_t)s * d, c->refine_x.p + rf.row_off + (int64_t)s * d, sizeof(double) * (size_t)d);
+            std::memcpy(grad_out + rf.row_off + (int64_t)s * d, c->refine_grad.p + rf.row_off + (int64_t)s * d, sizeof(double) * (size_t)d);
+        }
     }
     return CBO_OK;
 }

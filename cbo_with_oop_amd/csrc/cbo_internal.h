@@ -355,6 +355,25 @@ struct SmallAux {
 void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
                        double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
                        const SmallAux &aux = SmallAux());
+// ---- gradient refinement of every set's starts in one launch (kernels_sets_refine.hip) ----------------------
+// What a set's searches need beside the model's descriptor (pinned, device-mapped: read by the kernel directly): the box,
+// the cost c(x) = sum_k (fix[k] + (variable[k] ? |x_k| : 0)), the per-dimension lengthscales of an ARD model (the moving
+// point is scaled as prep_points_kernel scales a candidate), the number of starts and where the set's rows begin in the
+// call's starts / x_out / grad_out (row_off, in doubles) and in val_out / rounds_out / status_out (out_off).
+struct cbo_small_refine {
+    double lo[CBO_MAX_DIM], hi[CBO_MAX_DIM], fix[CBO_MAX_DIM], ls[CBO_MAX_DIM];
+    int variable[CBO_MAX_DIM];
+    int64_t row_off;
+    int k, out_off, ard, pad_;
+};
+int small_refine_starts_per_block(int d);              // 4 floor(16 / (1 + d)): a start fills 1 + d of a wave's 16 columns
+// sets / refs / starts and the five outputs may be pinned host memory; scratch: small_sets_scratch_doubles(n_sets,
+// blocks_per_set); info: n_sets ints, zero on entry, a set's word non-zero afterwards when its factorisation met a
+// non-positive pivot (the kernel then wrote CBO_REFINE_DECLINED for the set's starts and nothing else).  kind: kEiKind or
+// CBO_ACQ_*, the descriptors' scalars as for launch_small_sets; descriptors carry no candidates.  max_rounds <= 1000.
+void launch_small_sets_refine(hipStream_t s, int kind, const cbo_small_set *sets, const cbo_small_refine *refs,
+                              const double *starts, int n_sets, int blocks_per_set, double *scratch, int *info, int max_rounds,
+                              double *x_out, double *val_out, double *grad_out, int *rounds_out, int *status_out);
 // the same launch with the batch epilogue (kernels_sets_batch.hip, small_sets_batch_kernel): batch_size >= 2
 // Kriging-believer picks per set.  Sets of at most kSmallBatchMaxCands candidates: the set's V = L^-1 K* stays in global
 // scratch (1 MiB per set at the cap) and the call's widest set has at most 16 candidate blocks.  batch_scratch:

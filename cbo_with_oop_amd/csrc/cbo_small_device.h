@@ -752,6 +752,74 @@ __device__ __forceinline__ AcqParams small_acq_params(const cbo_small_set &st)
     return p;
 }
 
+// The plug-in incumbent of the workgroup's model (small_sets_kernel<CBO_ACQ_MPEI>, small_sets_refine_kernel<CBO_ACQ_MPEI>): min (task 'min') or max of the posterior means at the model's own n <= 128
+// points, NaN if any of them is.  The points are already in LDS in candidate layout (xs, sq, sv); they go through K*, the tile
+// solve and posterior_of (noise included) as candidates do, one 16-point tile per wave and round (two rounds at most), and
+// the means through plugin_incumbent_kernel's reduction, operation for operation (kernels_pointwise.hip: lane i holds
+// point i, the waves' shuffle tree, then thread 0 over the waves), so that even a tie between zeros of either sign falls as it
+// does there.  The factor must be in LDS (the caller has waited and synchronised); every thread returns the incumbent.
+// `fresh`: the set's new data are still in the staging buffer (a trial step's one-launch form): the prior closures at the
+// points are read from there, since the resident copies are being written by the set's first workgroup meanwhile.
+__device__ __forceinline__ double small_plugin_incumbent(const SmallShared &sh, const cbo_small_set &st, int tiles,
+                                                         const double (&iv)[8][4], const double (&zr)[8][4],
+                                                         const AcqParams &p, bool fresh, double *mean_s, double *red_v,
+                                                         int *red_n, double *out_s)
+{
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lc = lane & 15, kq = lane >> 4;
+    const bool causal = st.sv != nullptr;
+    const double *pmsrc = !causal ? nullptr : fresh ? st.stage + (int64_t)st.n * st.d + st.n : st.pm;
+    const double *pvsrc = !causal ? nullptr : fresh ? st.stage + (int64_t)st.n * st.d + 2 * (int64_t)st.n : st.pv;
+    const double inv_l2 = 1.0 / (st.lengthscale * st.lengthscale);
+    for (int t = wave; t < tiles; t += 4) {                        // (uniform per wave)
+        const int row = 16 * t + lc;
+        const int rr = (row < st.n) ? row : st.n - 1;              // clamped: lanes beyond the model compute, nobody looks
+        double xc[CBO_MAX_DIM];
+#pragma unroll
+        for (int k = 0; k < CBO_MAX_DIM; ++k) xc[k] = (k < st.d) ? sh.xs[k][rr] : 0.0;
+        const double csq = sh.sq[rr], csv = sh.sv[rr];
+        const double pm_c = pmsrc ? pmsrc[rr] : 0.0, pv_c = pvsrc ? pvsrc[rr] : 0.0;
+        d4 acc[8];
+        small_kstar_tiles_of(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc);
+        double qacc, macc;
+        solve_q_mu(sh, acc, iv, zr, tiles, kq, lc, qacc, macc);
+        if (kq == 0 && row < st.n) {
+            double mean, var;
+            posterior_of(qacc, macc, pm_c, pv_c, causal, p, mean, var);
+            mean_s[row] = mean;
+        }
+    }
+    __syncthreads();
+    const bool is_min = st.task == CBO_TASK_MIN;                   // (uniform)
+    double best = is_min ? INFINITY : -INFINITY;
+    int nan = 0;
+    if (tid < st.n) {
+        const double v = mean_s[tid];
+        nan |= isnan(v) ? 1 : 0;
+        if (is_min ? v < best : v > best) best = v;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_down(best, off);
+        nan |= __shfl_down(nan, off);
+        if (is_min ? ov < best : ov > best) best = ov;
+    }
+    if (lane == 0) { red_v[wave] = best; red_n[wave] = nan; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) {
+            nan |= red_n[w];
+            if (is_min ? red_v[w] < best : red_v[w] > best) best = red_v[w];
+        }
+        *out_s = nan ? __builtin_nan("") : best;
+    }
+    __syncthreads();
+    return *out_s;
+}
+
 // The workgroup's arg-max of the lanes' (bv, bi): the waves' shuffle trees, then thread 0 over the four waves -- whose
 // (bv, bi) are the workgroup's winner on return, which is where small_set_finish begins.  The waves' winners pass
 // through sh.sq / sh.sv.  Precondition: sh.sq and sh.sv are dead -- no wave reads the model's |x|^2 and sqrt(v) again

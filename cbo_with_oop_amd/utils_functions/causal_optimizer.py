@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .. import _lib
 from ..graphs import meshgrid_candidates
 from .causal_acquisition_functions import CandidateGrid
 
@@ -75,12 +76,17 @@ class CausalGradientAcquisitionOptimizer:
         return lockstep_lbfgs(lambda X: _values_and_gradients(acquisition, X), np.asarray(x0, dtype=np.float64), lo, hi,
                               max_rounds=max_rounds, history=history)
 
-    def optimize(self, acquisition, context=None, refine=False, num_starts=1):
+    def optimize(self, acquisition, context=None, refine=False, num_starts=1, device=False):
         """(x_max (1,d), acquisition value at x_max (1,1)) -- emukit ``AcquisitionOptimizerBase.optimize``.
         ``acquisition`` is ``CausalExpectedImprovement(...) / Cost(...)`` (an ``AcquisitionQuotient``) or a bare
         ``CausalExpectedImprovement``.  ``refine=True`` adds the reference's gradient stage: from the best grid point
         with scipy's L-BFGS-B (``num_starts=1``, what the reference does with its best anchor), or from the
-        ``num_starts`` best grid points at once (``refine_batched``)."""
+        ``num_starts`` best grid points at once (``refine_batched``).  ``device=True`` (with ``refine=True``) runs the
+        searches from the ``num_starts`` best grid points inside one device launch (``refine_sets``) and
+        raises ``ValueError`` when the set is not eligible for it: a causal, large or fp32 model, a cost that is not the
+        graphs' own, an acquisition the launch does not know.  The default is today's path."""
+        if device and not refine:
+            raise ValueError("device=True selects the device form of the refinement: refine must be True")
         if (refine or self.anchors == "uniform") and not has_gradients(acquisition):
             raise ValueError(f"{type(_numerator(acquisition)).__name__} has no gradients: it cannot be refined with "
                              "L-BFGS (use refine=False and anchors='grid')")
@@ -97,7 +103,23 @@ class CausalGradientAcquisitionOptimizer:
         res = acquisition.sweep(grid, want_acq=k > 1)
         x = pts[res["best_idx"]][None, :].copy()
         fx = np.array([[res["best_val"]]])
-        if refine and k == 1:
+        if refine and device:
+            kind, model, y_best, task, cost = _device_refinable(acquisition)
+            if k > 1:
+                acq = np.asarray(res["acq"], dtype=np.float64).reshape(-1)
+                top = np.argpartition(-acq, k - 1)[:k]
+                starts = pts[top[np.argsort(-acq[top], kind="stable")]]
+            else:
+                starts = x
+            (xs, fs, status), = refine_sets([model], [starts], [self.bounds], y_best, task, [cost], kind=kind,
+                                            host_fallback=False)
+            if status[0] == _lib.REFINE_DECLINED:
+                raise ValueError("device=True: the device launch declined the set (its model is not positive definite "
+                                 "without jitter, or the one-workgroup kernels are switched off with CBO_HIP_SMALL_SETS=0)")
+            best = int(np.argmax(fs))
+            if fs[best] >= fx[0, 0]:
+                x, fx = xs[best][None, :].copy(), np.array([[fs[best]]])
+        elif refine and k == 1:
             xr, fr = self.refine(acquisition, x)
             if fr[0, 0] >= fx[0, 0]:
                 x, fx = xr, fr
@@ -217,3 +239,179 @@ def lockstep_lbfgs(fun, x0, lo, hi, max_rounds=200, history=8, pgtol=1e-5, ftol=
                 done[i] = True
     return X, -F
 
+
+
+def cost_structure(cost):
+    """``(fix (d,), variable (d,) int32)`` of a ``Cost`` whose every function, for its own evaluated set, is a
+    ``functools.partial`` of ``graphs.cost`` with both parameters bound -- what ``get_cost_structure`` builds, for all four
+    cost types -- so that a one-row cost is ``(fix_0 + variable_0 |x_0|) + (fix_1 + ...) + ...`` from 0; ``None`` for anything
+    else (a lambda, another callable, keyword arguments): such a cost can only be evaluated in Python."""
+    import functools
+    from ..graphs import cost as graph_cost
+    fix, variable = [], []
+    for name in getattr(cost, "evaluated_set", ()):
+        f = getattr(cost, "costs_functions", {}).get(name)
+        if not isinstance(f, functools.partial) or f.func is not graph_cost or len(f.args) != 2 or f.keywords:
+            return None
+        fixed, var = f.args
+        if isinstance(fixed, (bool, np.bool_)) or not isinstance(fixed, (int, float, np.integer, np.floating)):
+            return None
+        if not np.isfinite(float(fixed)):
+            return None
+        fix.append(float(fixed))
+        variable.append(1 if var is True else 0)          # (graphs.cost adds the variable part for ``True`` alone)
+    if not fix:
+        return None
+    return np.array(fix, dtype=np.float64), np.array(variable, dtype=np.int32)
+
+
+def one_row_cost(fix, variable, x):
+    """``Cost.evaluate`` of the one-row batch ``x`` ((d,)) from ``cost_structure``'s pair, bit for bit: the terms added
+    from 0 in the evaluated set's order -- the arithmetic of the device launch."""
+    c = 0.0
+    for f, v, xi in zip(fix, variable, x):
+        c = c + (f + abs(float(xi)) if v else f)
+    return c
+
+
+def _device_refinable(acquisition):
+    """(kind, model, y_best, task, Cost) of an acquisition ``optimize(device=True)`` can hand to ``refine_sets``;
+    ``ValueError`` says why another cannot."""
+    from .causal_acquisition_functions import CausalExpectedImprovement
+    from . import pointwise_acquisitions as pw
+    from .cost_functions import Cost
+    num, cost = getattr(acquisition, "numerator", None), getattr(acquisition, "denominator", None)
+    if num is None or not isinstance(cost, Cost):
+        raise ValueError("device=True refines acquisition / Cost(...): the acquisition must be such a quotient")
+    if type(num) is CausalExpectedImprovement:
+        kind = ("EI", None)
+        if num.jitter != 0.0:
+            kind = ("EI", float(num.jitter))
+        y_best, task = float(np.asarray(num.current_global_min, dtype=np.float64).reshape(-1)[0]), num.task
+    elif isinstance(num, pw._PointwiseAcquisition) and num.kind in _lib.ACQ_KIND_CODE:
+        y_best, task, param = num._scalars()
+        kind = (num.kind, param)
+    else:
+        raise ValueError(f"device=True: {type(num).__name__} is not an acquisition the device launch refines")
+    why = _not_eligible(num.model, cost)
+    if why:
+        raise ValueError(f"device=True: {why}")
+    return kind, num.model, y_best, task, cost
+
+
+def _not_eligible(model, cost):
+    """Why the device launch does not take this (model, Cost), or None when it does."""
+    if getattr(model, "causal", False):
+        return "a causal model's prior closures are Python: they cannot be evaluated at a moving point on the device"
+    if not getattr(model, "small", False):
+        return "the model has more than 128 observations or is fp32"
+    if cost_structure(cost) is None:
+        return "the cost is not a table of functools.partial(graphs.cost, fix, variable)"
+    return None
+
+
+def _acquisition_of_kind(kind, model, current_global_best, task, cost):
+    from .causal_acquisition_functions import CausalExpectedImprovement
+    from .utils import _acquisition_for
+    if kind[0] == "EI":
+        return CausalExpectedImprovement(current_global_best, task, model, 0.0 if kind[1] is None else kind[1]) / cost
+    return _acquisition_for(kind[0], model, current_global_best, task, None, None if kind[0] == "VAR" else kind[1]) / cost
+
+
+def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=("EI", None), max_rounds=200,
+                host_fallback=True):
+    """The reference's second stage (causal_optimizer.py:59-65) for every exploration set at once: from every row of
+    ``starts[s]`` ((k_s, d_s), 1 <= k_s <= 64) a projected L-BFGS ascent of ``acquisition / Cost`` inside ``bounds[s]``
+    (``lockstep_lbfgs``'s iteration), returning per set ``(points (k_s, d_s), values (k_s,), status (k_s,) int)``.
+    Eligible sets -- a non-causal fp64 model of at most 128 observations whose ``costs[s]`` ``cost_structure`` recognises --
+    advance inside ONE device launch (``cbo_acq_refine_sets``, DESIGN.md §4q: the model factored in LDS once, every round's
+    value and gradient from one tile solve); ``status`` is the launch's reason for stopping (``_lib.REFINE_*``).  Every
+    other set, and a set the launch declined, goes through ``refine_batched`` inside the same call: its points and values
+    are that method's own and its status entries are ``_lib.REFINE_DECLINED``.
+    ``kind`` is ``sets_acquisition``'s pair: ``("EI", None)``, ``("LCB", beta)``, ``("PI", jitter)``, ``("MPEI", jitter)``,
+    ``("VAR", 0.0)`` -- it is checked and completed by ``sets_acquisition`` here, so a ``None`` parameter means the kind's
+    default (beta 1, jitter 0) on both routes; ``("EI", jitter)`` with a finite jitter is accepted too (what
+    ``optimize(device=True)`` passes for a jittered EI) and reaches both routes.  Models are only read by the launch; the
+    host route fits a model that is not.  ``host_fallback=False``: a set the launch does not take is not refined at all --
+    its points are its starts, its values NaN, its status ``_lib.REFINE_DECLINED``."""
+    import ctypes
+    import math
+    from .utils import sets_acquisition
+    if not (isinstance(kind, tuple) and len(kind) == 2):
+        raise ValueError(f"refine_sets: kind must be a (name, parameter) pair, not {kind!r}")
+    if kind[0] == "MES":
+        raise ValueError("refine_sets: acquisition must be 'EI', 'LCB', 'PI', 'MPEI' or 'VAR', not 'MES'")
+    if kind[0] == "EI" and kind[1] is not None:
+        if isinstance(kind[1], bool) or not isinstance(kind[1], (int, float, np.integer, np.floating)) \
+                or not math.isfinite(float(kind[1])):
+            raise ValueError(f"refine_sets: the EI's jitter must be a finite number, not {kind[1]!r}")
+        kind = ("EI", float(kind[1]))
+    else:
+        kind = sets_acquisition(kind[0], None if kind[0] in ("EI", "VAR") else kind[1])
+    s = len(models)
+    if not (len(starts) == len(bounds) == len(costs) == s) or s == 0:
+        raise ValueError("refine_sets: models, starts, bounds and costs must have one entry per exploration set")
+    if task not in _lib.TASK_CODE:
+        raise ValueError(f"task must be 'min' or 'max', not {task!r}")
+    max_rounds = int(max_rounds)
+    if not 0 <= max_rounds <= _lib.REFINE_ROUNDS_LIMIT:
+        raise ValueError(f"max_rounds must be in 0..{_lib.REFINE_ROUNDS_LIMIT}, not {max_rounds}")
+    y_best = float(np.asarray(current_global_best, dtype=np.float64).reshape(-1)[0])
+    param = 0.0 if kind[1] is None else float(kind[1])
+    X0, los, his = [], [], []
+    for i in range(s):
+        x0 = _lib.as_f64(starts[i])
+        d = models[i].input_dim
+        if x0.ndim != 2 or x0.shape[1] != d or not 1 <= x0.shape[0] <= _lib.REFINE_MAX_STARTS:
+            raise ValueError(f"refine_sets: starts of set {i} must be (k, {d}) with 1 <= k <= {_lib.REFINE_MAX_STARTS}, "
+                             f"not {x0.shape}")
+        lo = np.array([b[0] for b in bounds[i]], dtype=np.float64)
+        hi = np.array([b[1] for b in bounds[i]], dtype=np.float64)
+        if lo.shape != (d,) or not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo <= hi)):
+            raise ValueError(f"refine_sets: bounds of set {i} must be {d} finite (lo, hi) pairs with lo <= hi")
+        if not np.all(np.isfinite(x0)):
+            raise ValueError(f"refine_sets: starts of set {i} must be finite")
+        X0.append(x0); los.append(lo); his.append(hi)
+    out = [None] * s
+    dev = [i for i in range(s) if _not_eligible(models[i], costs[i]) is None]
+    if dev:
+        n = len(dev)
+        structs = [cost_structure(costs[i]) for i in dev]
+        for i, (fix, _) in zip(dev, structs):
+            if not fix.sum() > 0.0:
+                raise ValueError(f"refine_sets: the fixed costs of set {i} must sum to a positive cost")
+        sets = (_lib.CboRefineSet * n)()
+        for j, i in enumerate(dev):
+            fix, variable = structs[j]
+            sets[j].k = X0[i].shape[0]
+            sets[j].starts = X0[i].ctypes.data_as(_lib.c_double_p)
+            sets[j].lo = los[i].ctypes.data_as(_lib.c_double_p)
+            sets[j].hi = his[i].ctypes.data_as(_lib.c_double_p)
+            sets[j].cost_fix = fix.ctypes.data_as(_lib.c_double_p)
+            sets[j].cost_variable = variable.ctypes.data_as(_lib.c_int_p)
+        rows = sum(X0[i].size for i in dev)
+        total = sum(X0[i].shape[0] for i in dev)
+        x_out, g_out, v_out = np.zeros(rows), np.zeros(rows), np.zeros(total)
+        rounds, status = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32)
+        gps = (ctypes.c_void_p * n)(*[models[i]._handle for i in dev])
+        yb = np.full(n, y_best)
+        _lib.check(_lib.load().cbo_acq_refine_sets(
+            n, gps, sets, _lib.REFINE_KIND_CODE[kind[0]], _lib.dptr(yb), _lib.TASK_CODE[task], param, max_rounds,
+            _lib.dptr(x_out), _lib.dptr(v_out), _lib.dptr(g_out), rounds.ctypes.data_as(_lib.c_int_p),
+            status.ctypes.data_as(_lib.c_int_p)))
+        r0 = o0 = 0
+        for i in dev:
+            k, d = X0[i].shape
+            if status[o0] != _lib.REFINE_DECLINED:
+                out[i] = (x_out[r0:r0 + k * d].reshape(k, d).copy(), v_out[o0:o0 + k].copy(), status[o0:o0 + k].copy())
+            r0 += k * d
+            o0 += k
+    for i in range(s):
+        if out[i] is None and not host_fallback:
+            out[i] = (X0[i].copy(), np.full(X0[i].shape[0], np.nan), np.full(X0[i].shape[0], _lib.REFINE_DECLINED, dtype=np.int32))
+        if out[i] is None:
+            acq = _acquisition_of_kind(kind, models[i], current_global_best, task, costs[i])
+            x, f = CausalGradientAcquisitionOptimizer(list(zip(los[i].tolist(), his[i].tolist()))).refine_batched(
+                acq, X0[i], max_rounds=max_rounds)
+            out[i] = (x, f, np.full(X0[i].shape[0], _lib.REFINE_DECLINED, dtype=np.int32))
+    return out

@@ -311,7 +311,7 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
 
 def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
                        acquisition="EI", acquisition_param=None, hyper_samples=None, spaces=None, batch_size=None,
-                       update_incumbent=False, constraints=None):
+                       update_incumbent=False, refine=False, constraints=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -350,10 +350,17 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     ``find_next_y_point(batch_size=B)`` returns: ``xs[s]`` is (B, d), ``ys[s]`` (B, 1), row 0 the single-point result.  Under
     variable costs ``ys[s][0]`` is today's re-evaluation and the later picks are rescaled from the batch cost to the point's
     own.  Another ``acquisition`` than ``"EI"``, non-empty ``constraints``, ``hyper_samples`` and ``raw=True`` raise
-    ``ValueError`` before any device call.  ``None`` takes exactly today's calls."""
+    ``ValueError`` before any device call.  ``None`` takes exactly today's calls.
+    ``refine=True`` with ``spaces`` (one entry per set): the reference's second stage (causal_optimizer.py:59-65) -- every
+    set's winner is the start of an L-BFGS ascent inside the set's box, all of them in one further device call
+    (``causal_optimizer.refine_sets``; sets the launch does not take go through ``refine_batched``).  The
+    refined point replaces the winner only if its value, priced at its own cost, is not lower.  ``refine=True`` with
+    ``"MES"``, non-empty ``constraints``, ``hyper_samples``, ``batch_size`` or ``raw=True``, or without ``spaces``, raises
+    ``ValueError`` before any device call.  ``False`` takes exactly today's calls."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    checked_refine(refine, kind, constraints, hyper_samples, batch_size, raw, spaces, len(models))
     batch_size = checked_batch_size(batch_size, kind, constraints, hyper_samples, raw)
     if batch_size is not None and task not in _lib.TASK_CODE:
         raise ValueError(f"task must be 'min' or 'max', not {task!r}")
@@ -450,7 +457,45 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
                     m.stale = False
     if raw:
         return None, [(float(vals[i]), int(idxs[i])) for i in range(s)]
-    return winners_to_points(st, models, grids, current_global_best, task)
+    xs, ys = winners_to_points(st, models, grids, current_global_best, task)
+    if refine:
+        xs, ys = refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind)
+    return xs, ys
+
+
+def checked_refine(refine, kind, constraints=None, hyper_samples=None, batch_size=None, raw=False, spaces=None, n_sets=None):
+    """``refine`` of a multi-set sweep, a path or an agent, checked on the host before any device call: gradient refinement
+    is defined for the causal EI and the point-wise kinds alone, one winner per set, on a single rank, and needs the sets'
+    boxes."""
+    if not refine:
+        return False
+    if kind[0] == "MES":
+        raise ValueError("refine=True: max-value entropy search has no gradients")
+    if constraints is not None and any(constraints):
+        raise ValueError("refine=True is not defined for constrained acquisitions: constraints must be None or empty")
+    if hyper_samples is not None:
+        raise ValueError("refine=True is not defined for the marginalised EI: hyper_samples must be None")
+    if batch_size is not None:
+        raise ValueError("refine=True is not defined for batches: batch_size must be None")
+    if raw:
+        raise ValueError("refine=True is not defined across several ranks (raw=True)")
+    if spaces is None or not hasattr(spaces, "__len__") or (n_sets is not None and len(spaces) != n_sets):
+        raise ValueError("refine=True searches inside the sets' boxes: spaces must have one entry per exploration set"
+                         + ("" if n_sets is None else f" ({n_sets})"))
+    return True
+
+
+def refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind):
+    """``find_next_y_points(refine=True)``'s second stage: every set's winner refined by ``refine_sets``; the refined point
+    replaces it only if its value -- over the point's own cost, as ``winners_to_points`` prices the winner -- is not lower."""
+    from .causal_optimizer import refine_sets
+    res = refine_sets(models, xs, [space_bounds(sp) for sp in spaces], current_global_best, task, costs, kind=kind)
+    xs, ys = list(xs), list(ys)
+    for i, (pts, vals, _) in enumerate(res):
+        best = int(np.argmax(vals))
+        if vals[best] >= ys[i][0, 0]:
+            xs[i], ys[i] = pts[best][None, :].copy(), np.array([[vals[best]]])
+    return xs, ys
 
 
 def checked_batch_size(batch_size, kind=("EI", None), constraints=None, hyper_samples=None, raw=False):

@@ -712,6 +712,37 @@ int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cands *const *c
                              double ei_jitter, const double *costs, int batch_size, int update_incumbent,
                              double *best_vals, int64_t *best_idxs);
 
+/* The second stage of the reference's optimiser for every exploration set of a trial: from each of set
+ * i's k starts a box-constrained L-BFGS ascent of acquisition / cost -- lockstep_lbfgs of utils_functions/causal_optimizer.py,
+ * restated in csrc/refine_search.h -- and every search of every set advances inside ONE launch (small_sets_refine_kernel):
+ * the set's model is factored in LDS once per workgroup and stays there for all rounds.
+ * kind: 0 = the causal Expected Improvement (y_best[i] the incumbent, param the jitter), or CBO_ACQ_LCB | _PI | _VAR | _MPEI
+ * with param as for cbo_acq_sweep_sets_kind.  The cost of a point is c(x) = (fix_0 + variable_0 |x_0|) + (fix_1 + ...) + ...
+ * accumulated from 0 in that order; value = acquisition / c(x), gradient = d acquisition / c(x) (the reference's zero cost
+ * gradient).  The value reported at a point is, bit for bit, what cbo_acq_sweep_sets (_kind) returns for a one-point grid
+ * at that point with costs[i] = c(x).
+ * Outputs, concatenated in set order: x_out and grad_out sum(k) rows, row-major with each set's own d; val_out, rounds_out
+ * and status_out sum(k) entries.  status_out: why the search ended (CBO_REFINE_*).  max_rounds = 0 evaluates value and
+ * gradient at the starts (clipped to the box) and returns them.
+ * A set whose model has a prior (a causal model), more than 128 observations, or fp32 data, or whose factorisation meets a
+ * non-positive pivot in the launch, is DECLINED: status_out = CBO_REFINE_DECLINED for all its starts, its other output
+ * rows are not written.  Models are only read: fitted state, caches and kept solutions stay as they were; no fit needed.
+ * CBO_ERR_INVALID before any launch: n_sets <= 0, NULL arguments, k outside 1..CBO_REFINE_MAX_STARTS, lo > hi, non-finite
+ * bounds or starts, a fixed-cost sum that is not positive, a variable flag other than 0 / 1, an unknown kind (and
+ * cbo_acq_sweep_sets_kind's checks of param and y_best), a bad task, max_rounds outside 0..CBO_REFINE_ROUNDS_LIMIT (emukit's maxfun). */
+#define CBO_REFINE_MAX_STARTS 64
+#define CBO_REFINE_ROUNDS_LIMIT 1000
+enum { CBO_REFINE_PGTOL = 0, CBO_REFINE_FTOL = 1, CBO_REFINE_STEP = 2, CBO_REFINE_MAX_ROUNDS = 3,
+       CBO_REFINE_NAN_START = 4, CBO_REFINE_DECLINED = 5 };
+typedef struct cbo_refine_set {
+    int k; const double *starts;                        /* k x d, row-major */
+    const double *lo, *hi;                              /* d */
+    const double *cost_fix; const int *cost_variable;   /* d */
+} cbo_refine_set;
+int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int kind, const double *y_best,
+                        int task, double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
+                        int *rounds_out, int *status_out);
+
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
                        const double *prior_var_s, double y_best, int task, double ei_jitter,
