@@ -2242,11 +2242,17 @@ static bool poll_until(Pred done, double budget_us)
 // A record that has not arrived then is the error `missing`; the caller reads the records after this call's fence.
 // CBO_HIP_TRACE_SLOW=1: a call that takes more than a millisecond says on stderr where the time went (a value above 1 is
 // the threshold in microseconds instead).
+// the sequence number of the context's next one-workgroup launch (never 0: the records are zero between calls)
+static int next_small_seq(cbo_ctx *c)
+{
+    if (++c->small_seq == 0) c->small_seq = 1;
+    return c->small_seq;
+}
+
 template <class Rec, class Launch>
 static int polled_launch(cbo_ctx *c, const char *name, const Rec *out, int n, const char *missing, Launch launch)
 {
-    if (++c->small_seq == 0) c->small_seq = 1;
-    const int seq = c->small_seq;
+    const int seq = next_small_seq(c);
     static const bool trace_slow = std::getenv("CBO_HIP_TRACE_SLOW") != nullptr;
     static const double trace_over_us = trace_slow && std::atof(std::getenv("CBO_HIP_TRACE_SLOW")) > 1.0
                                             ? std::atof(std::getenv("CBO_HIP_TRACE_SLOW")) : 1000.0;
@@ -2302,19 +2308,6 @@ static void fill_small_cands(cbo_small_set &st, const cbo_gp *g, const cbo_cands
 // a model the one-workgroup sweeps take: fp64, at most 128 observations (CBO_HIP_SMALL_SETS=0: none)
 static bool small_sweep_model(const cbo_gp *g) { return g->dtype == CBO_DTYPE_F64 && g->n_pad == kPadN && g->ctx->small_sets; }
 
-// the records of a one-launch sweep of the sets small[0..ns) into the caller's arrays; a set whose record reports a model
-// that is not positive definite as assembled is left for the general path (its jitchol ladder)
-static void harvest_small_sets(cbo_ctx *c, const std::vector<int> &small, double *best_vals, int64_t *best_idxs,
-                               std::vector<char> &done)
-{
-    for (size_t j = 0; j < small.size(); ++j) {
-        if (c->small_out[j].info != 0) continue;
-        best_vals[small[j]] = c->small_out[j].best_val;
-        best_idxs[small[j]] = c->small_out[j].best_idx;
-        done[(size_t)small[j]] = 1;
-    }
-}
-
 // descriptors, result records, status words and tickets for n_sets sets (at least 32), scratch and partial winners for
 // `blocks` workgroups per set
 static int ensure_small_buffers(cbo_ctx *c, int n_sets, int blocks)
@@ -2328,6 +2321,126 @@ static int ensure_small_buffers(cbo_ctx *c, int n_sets, int blocks)
     if (rc == CBO_OK) rc = grow(c, c->small_part_val, parts);
     if (rc == CBO_OK) rc = grow(c, c->small_part_idx, parts);
     return rc;
+}
+
+// ---- the routing policy of the one-workgroup kernels, written once ---------------------------------------
+// (1) the handles of a multi-set call: every (gp, cands) passes check_sweep_args, lives on first's context and -- unless the
+// caller is about to give it data (cbo_trial_step's refit_set) -- holds data.  `what`: "sets" or "models", for the message.
+static int check_set_handle(const cbo_gp *g, const cbo_cands *k, int task, const cbo_gp *first, const char *what = "sets",
+                            bool needs_data = true)
+{
+    const int rc = check_sweep_args(g, k, task);
+    if (rc != CBO_OK) return rc;
+    if (g->ctx != first->ctx) return fail(CBO_ERR_INVALID, std::string("all ") + what + " must live on one context");
+    if (needs_data && (g->n <= 0 || g->n_pad <= 0)) return fail(CBO_ERR_INVALID, "a gp holds no data");
+    return CBO_OK;
+}
+static int check_set_handles(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int task)
+{
+    for (int i = 0; i < n_sets; ++i) {
+        const int rc = check_set_handle(gps[i], cands[i], task, gps[0]);
+        if (rc != CBO_OK) return rc;
+    }
+    return CBO_OK;
+}
+// ... and of a call that takes models alone (the likelihood and leave-one-out batches)
+static int check_model_handles(int n_models, cbo_gp *const *gps)
+{
+    for (int i = 0; i < n_models; ++i) {
+        if (!gps[i]) return fail(CBO_ERR_INVALID, "NULL gp");
+        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all models must live on one context");
+    }
+    return CBO_OK;
+}
+
+// (2) which items the one launch takes -- those `eligible` accepts, in index order -- and how many workgroups the widest of
+// them needs.  A grid dimension holds 65535 workgroups: a wider item sends the WHOLE call to the general path (a call that
+// wants only that item sent there says so in `eligible`).
+constexpr int64_t kMaxGridBlocks = 65535;
+static int64_t cand_blocks(const cbo_cands *k) { return (k->m + 63) / 64; }     // 64 candidates per workgroup
+template <class Eligible, class Blocks>
+static int partition_small(int n_items, Eligible eligible, Blocks blocks_of, std::vector<int> &small)
+{
+    int64_t widest = 1;
+    for (int i = 0; i < n_items; ++i) {
+        if (!eligible(i)) continue;
+        small.push_back(i);
+        const int64_t b = blocks_of(i);
+        if (b > widest) widest = b;
+    }
+    if (widest > kMaxGridBlocks) small.clear();
+    return (int)widest;
+}
+
+// (3) the descriptor of one (model, candidate set) pair with the acquisition's scalars.  staged (cbo_trial_step): the
+// model's new data sit in the context's staging buffer and the launch prepares and stores them.
+static int fill_small_set(cbo_small_set &st, cbo_gp *g, cbo_cands *k, int task, double y_best, double ei_jitter, double cost,
+                          bool staged = false)
+{
+    const int rc = prepare_cands(g, k);
+    if (rc != CBO_OK) return rc;
+    fill_small_model(st, g);
+    if (staged) {
+        st.stage = g->ctx->stage;
+        st.stage_ls = g->h.ard ? g->ls_dev : nullptr;
+    }
+    fill_small_cands(st, g, k);
+    st.task = task; st.y_best = y_best; st.ei_jitter = ei_jitter; st.cost = cost;
+    return CBO_OK;
+}
+// ... and of the marginalised EI, whose kernels scale the raw candidates per sample themselves
+static void fill_hyper_set(cbo_small_set &st, const cbo_gp *g, const cbo_cands *k, int task, double y_best, double ei_jitter,
+                           double cost)
+{
+    const bool causal = g->X.sv != nullptr;
+    fill_small_model(st, g);
+    st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
+    st.m = k->m; st.index_offset = k->index_offset;
+    st.task = task; st.y_best = y_best; st.ei_jitter = ei_jitter; st.cost = cost;
+}
+
+// (4) the context buffers of one launch (ensure_small_buffers has sized them); the tickets are the upper half of small_info
+static SmallLaunch small_launch(cbo_ctx *c, int seq)
+{
+    return SmallLaunch{c->small_scratch, c->small_part_val, c->small_part_idx, c->small_info,
+                       c->small_info + c->small_info.cap / 2, c->small_out, seq};
+}
+
+// (5) run and fall back.  When the launch takes any item: prepare() sizes the call's buffers and fills the descriptors of
+// small[0..ns), launch(L) queues the kernel on the buffers L, its records -- records.p[0..ns), pinned -- are polled, and
+// harvest(j, i) reads record j, which answers item i = small[j].  An item whose record reports a model that is not positive
+// definite as assembled (info != 0: jitchol's business) joins the items the launch did not take: general(i), in index
+// order -- which is "fit if not fitted, then the single-model call" (ensure_fitted: the jitchol ladder lives in cbo_gp_fit).
+static int ensure_fitted(cbo_gp *g) { return g->fitted ? CBO_OK : cbo_gp_fit(g, nullptr, nullptr); }
+template <class Records, class Prepare, class Launch, class Harvest, class General>
+static int run_small_or_general(cbo_ctx *c, const char *name, const char *missing, int n_items, const std::vector<int> &small,
+                                const Records &records, Prepare prepare, Launch launch, Harvest harvest, General general)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<char> done((size_t)n_items, 0);
+    if (!small.empty()) {
+        int rc = prepare();
+        if (rc != CBO_OK) return rc;
+        const auto *out = records.p;
+        rc = polled_launch(c, name, out, (int)small.size(), missing, [&](int seq) -> int {
+            launch(small_launch(c, seq));
+            HIP_TRY(hipGetLastError());
+            return CBO_OK;
+        });
+        if (rc != CBO_OK) return rc;
+        for (size_t j = 0; j < small.size(); ++j) {
+            if (out[j].info != 0) continue;
+            rc = harvest((int)j, small[j]);
+            if (rc != CBO_OK) return rc;
+            done[(size_t)small[j]] = 1;
+        }
+    }
+    for (int i = 0; i < n_items; ++i) {
+        if (done[(size_t)i]) continue;
+        const int rc = general(i);
+        if (rc != CBO_OK) return rc;
+    }
+    return CBO_OK;
 }
 
 // staged_set >= 0 (cbo_trial_step): that set's new data sit in the context's staging buffer, its model's host-side state
@@ -2394,105 +2507,75 @@ extern "C" int cbo_acq_sweep_sets_mes(int n_sets, cbo_gp *const *gps, cbo_cands 
                            n_samples, mins);
 }
 
+// the record of a one-launch sweep is the set's winner
+static int harvest_winner(const cbo_ctx *c, int j, int i, double *best_vals, int64_t *best_idxs)
+{
+    best_vals[i] = c->small_out[j].best_val;
+    best_idxs[i] = c->small_out[j].best_idx;
+    return CBO_OK;
+}
+
 static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
                            double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs, int staged_set,
                            int kind, const int *n_samples, const double *const *mins)
 {
     if (n_sets <= 0 || !gps || !cands || (!y_best && kind != kMesKind) || !costs || !best_vals || !best_idxs)
         return fail(CBO_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n_sets; ++i) {
-        int rc = check_sweep_args(gps[i], cands[i], task);
-        if (rc != CBO_OK) return rc;
-        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
-        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
-    }
+    int rc = check_set_handles(n_sets, gps, cands, task);
+    if (rc != CBO_OK) return rc;
     cbo_ctx *c = gps[0]->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     std::vector<int> small;
-    int blocks = 1;
-    for (int i = 0; i < n_sets; ++i) {
-        if (small_sweep_model(gps[i])) {
-            small.push_back(i);
-            const int b = (int)((cands[i]->m + 63) / 64);
-            if (b > blocks) blocks = b;
-        }
-    }
-    std::vector<char> done((size_t)n_sets, 0);
-    if (!small.empty() && blocks <= 65535) {
-        int rc = ensure_small_buffers(c, (int)small.size(), blocks);
-        SmallAux aux;
+    const int blocks = partition_small(n_sets, [&](int i) { return small_sweep_model(gps[i]); },
+                                       [&](int i) { return cand_blocks(cands[i]); }, small);
+    const int ns = (int)small.size();
+    SmallAux aux;
+    auto prepare = [&]() -> int {
+        int rc = ensure_small_buffers(c, ns, blocks);
         if (rc == CBO_OK && kind == kMesKind) {
             // the small sets' samples, one set after the other, and where each set's begin
             size_t total = 0;
-            for (size_t j = 0; j < small.size(); ++j) total += (size_t)n_samples[small[j]];
-            rc = grow(c, c->aux_host, small.size() < 32 ? (size_t)32 : small.size());
+            for (int j = 0; j < ns; ++j) total += (size_t)n_samples[small[(size_t)j]];
+            rc = grow(c, c->aux_host, ns < 32 ? (size_t)32 : (size_t)ns);
             if (rc == CBO_OK) rc = grow(c, c->mes_host, total);
-            if (rc == CBO_OK) {
-                size_t at = 0;
-                for (size_t j = 0; j < small.size(); ++j) {
-                    const size_t k = (size_t)n_samples[small[j]];
-                    std::memcpy(c->mes_host.p + at, mins[small[j]], sizeof(double) * k);
-                    c->aux_host[j] = cbo_small_aux{(int64_t)at, (int64_t)k};
-                    at += k;
-                }
-                aux.per_set = c->aux_host;
-                aux.data = c->mes_host;
-            }
-        }
-        if (rc != CBO_OK) return rc;
-        for (size_t j = 0; j < small.size(); ++j) {
-            cbo_gp *g = gps[small[j]];
-            cbo_cands *k = cands[small[j]];
-            rc = prepare_cands(g, k);
             if (rc != CBO_OK) return rc;
-            cbo_small_set &st = c->sets_host[j];
-            fill_small_model(st, g);
-            if (small[j] == staged_set) {
-                st.stage = c->stage;
-                st.stage_ls = g->h.ard ? g->ls_dev : nullptr;
+            size_t at = 0;
+            for (int j = 0; j < ns; ++j) {
+                const size_t k = (size_t)n_samples[small[(size_t)j]];
+                std::memcpy(c->mes_host.p + at, mins[small[(size_t)j]], sizeof(double) * k);
+                c->aux_host[j] = cbo_small_aux{(int64_t)at, (int64_t)k};
+                at += k;
             }
-            fill_small_cands(st, g, k);
-            // (only the EI and the probability of improvement read the caller's incumbent)
-            st.task = task; st.y_best = (kind == kEiKind || kind == CBO_ACQ_PI) ? y_best[small[j]] : 0.0;
-            st.ei_jitter = ei_jitter;
-            st.cost = costs[small[j]];
+            aux.per_set = c->aux_host;
+            aux.data = c->mes_host;
         }
-        const int ns = (int)small.size();
-        auto launch = [&](int seq) -> int {
-            launch_small_sets(c->stream, kind, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val,
-                              c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq,
-                              aux);
-            HIP_TRY(hipGetLastError());
-            return CBO_OK;
-        };
-        rc = polled_launch(c, kind == kEiKind ? "cbo_acq_sweep_sets" : kind == kMesKind ? "cbo_acq_sweep_sets_mes"
-                                                                                         : "cbo_acq_sweep_sets_kind", c->small_out.p, ns,
-                           "multi-set sweep: no result record", launch);
+        for (int j = 0; rc == CBO_OK && j < ns; ++j) {
+            const int i = small[(size_t)j];
+            // (only the EI and the probability of improvement read the caller's incumbent)
+            const double incumbent = (kind == kEiKind || kind == CBO_ACQ_PI) ? y_best[i] : 0.0;
+            rc = fill_small_set(c->sets_host[j], gps[i], cands[i], task, incumbent, ei_jitter, costs[i], i == staged_set);
+        }
+        return rc;
+    };
+    auto general = [&](int i) -> int {
+        if (kind == kEiKind && !gps[i]->fitted)
+            return cbo_gp_fit_sweep(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
+                                    &best_vals[i], &best_idxs[i], nullptr, nullptr);
+        const int rc = ensure_fitted(gps[i]);
         if (rc != CBO_OK) return rc;
-        harvest_small_sets(c, small, best_vals, best_idxs, done);
-    }
-    for (int i = 0; i < n_sets; ++i) {
-        if (done[(size_t)i]) continue;
-        int rc;
-        if (kind == kMesKind) {
-            rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
-            if (rc == CBO_OK)
-                rc = cbo_acq_sweep_mes(gps[i], cands[i], n_samples[i], mins[i], costs[i], nullptr, nullptr, nullptr,
-                                       &best_vals[i], &best_idxs[i]);
-        } else if (kind != kEiKind) {
-            rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
-            if (rc == CBO_OK)
-                rc = cbo_acq_sweep_kind(gps[i], cands[i], kind, y_best[i], task, ei_jitter, costs[i], nullptr, nullptr,
-                                        nullptr, &best_vals[i], &best_idxs[i]);
-        } else if (!gps[i]->fitted)
-            rc = cbo_gp_fit_sweep(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
-                                  &best_vals[i], &best_idxs[i], nullptr, nullptr);
-        else
-            rc = cbo_acq_sweep(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
-                               &best_vals[i], &best_idxs[i]);
-        if (rc != CBO_OK) return rc;
-    }
-    return CBO_OK;
+        if (kind == kMesKind)
+            return cbo_acq_sweep_mes(gps[i], cands[i], n_samples[i], mins[i], costs[i], nullptr, nullptr, nullptr, &best_vals[i],
+                                     &best_idxs[i]);
+        if (kind != kEiKind)
+            return cbo_acq_sweep_kind(gps[i], cands[i], kind, y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
+                                      &best_vals[i], &best_idxs[i]);
+        return cbo_acq_sweep(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr, &best_vals[i],
+                             &best_idxs[i]);
+    };
+    return run_small_or_general(
+        c, kind == kEiKind ? "cbo_acq_sweep_sets" : kind == kMesKind ? "cbo_acq_sweep_sets_mes" : "cbo_acq_sweep_sets_kind",
+        "multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
+        [&](const SmallLaunch &L) { launch_small_sets(c->stream, kind, c->sets_host, ns, blocks, L, aux); },
+        [&](int j, int i) { return harvest_winner(c, j, i, best_vals, best_idxs); }, general);
 }
 
 // ---- greedy batch selection for every set of a trial (kernels_sets_batch.hip) ---------------------------------
@@ -2529,77 +2612,53 @@ extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cand
     }
     if (!gps || !cands) return fail(CBO_ERR_INVALID, "NULL argument: gps and cands must be given");
     for (int i = 0; i < n_sets; ++i) {
-        int rc = check_sweep_args(gps[i], cands[i], task);
+        const int rc = check_set_handle(gps[i], cands[i], task, gps[0]);
         if (rc != CBO_OK) return rc;
-        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
-        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
         if (batch_size > cands[i]->m)
             return fail(CBO_ERR_INVALID, "batch_size exceeds the number of candidates (set " + std::to_string(i) + ")");
     }
     if (batch_size == 1)
         return sweep_sets_impl(n_sets, gps, cands, y_best, task, ei_jitter, costs, best_vals, best_idxs, -1, kEiKind);
     cbo_ctx *c = gps[0]->ctx;
-    HIP_TRY(hipSetDevice(c->device));
+    const size_t B = (size_t)batch_size;
     std::vector<int> small;
-    int blocks = 1;
-    for (int i = 0; i < n_sets; ++i) {
-        if (small_sweep_model(gps[i]) && cands[i]->m <= kSmallBatchMaxCands) {
-            small.push_back(i);
-            const int b = (int)((cands[i]->m + 63) / 64);
-            if (b > blocks) blocks = b;
-        }
-    }
-    std::vector<char> done((size_t)n_sets, 0);
-    if (!small.empty()) {
-        const int ns = (int)small.size();
+    const int blocks = partition_small(
+        n_sets, [&](int i) { return small_sweep_model(gps[i]) && cands[i]->m <= kSmallBatchMaxCands; },
+        [&](int i) { return cand_blocks(cands[i]); }, small);
+    const int ns = (int)small.size();
+    auto prepare = [&]() -> int {
         int rc = ensure_small_buffers(c, ns, blocks);
         if (rc == CBO_OK) rc = ensure_small_batch_buffers(c, ns, blocks, batch_size);
-        if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            cbo_gp *g = gps[small[(size_t)j]];
-            cbo_cands *k = cands[small[(size_t)j]];
-            rc = prepare_cands(g, k);
-            if (rc != CBO_OK) return rc;
-            cbo_small_set &st = c->sets_host[j];
-            fill_small_model(st, g);
-            fill_small_cands(st, g, k);
-            st.task = task; st.y_best = y_best[small[(size_t)j]]; st.ei_jitter = ei_jitter; st.cost = costs[small[(size_t)j]];
+        for (int j = 0; rc == CBO_OK && j < ns; ++j) {
+            const int i = small[(size_t)j];
+            rc = fill_small_set(c->sets_host[j], gps[i], cands[i], task, y_best[i], ei_jitter, costs[i]);
         }
-        auto launch = [&](int seq) -> int {
-            launch_small_sets_batch(c->stream, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val, c->small_part_idx,
-                                    c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq,
-                                    c->sets_batch_scratch, batch_size, update_incumbent, c->sets_batch_h_vals,
-                                    c->sets_batch_h_idxs);
-            HIP_TRY(hipGetLastError());
+        return rc;
+    };
+    return run_small_or_general(
+        c, "cbo_acq_sweep_sets_batch", "multi-set batch sweep: no result record", n_sets, small, c->small_out, prepare,
+        [&](const SmallLaunch &L) {
+            launch_small_sets_batch(c->stream, c->sets_host, ns, blocks, L, c->sets_batch_scratch, batch_size, update_incumbent,
+                                    c->sets_batch_h_vals, c->sets_batch_h_idxs);
+        },
+        [&](int j, int i) {                                      // the set's winners, complete when its record is
+            std::memcpy(best_vals + (size_t)i * B, c->sets_batch_h_vals.p + (size_t)j * B, sizeof(double) * B);
+            std::memcpy(best_idxs + (size_t)i * B, c->sets_batch_h_idxs.p + (size_t)j * B, sizeof(int64_t) * B);
             return CBO_OK;
-        };
-        rc = polled_launch(c, "cbo_acq_sweep_sets_batch", c->small_out.p, ns, "multi-set batch sweep: no result record", launch);
-        if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            if (c->small_out[j].info != 0) continue;            // not positive definite as assembled: the general path
-            const size_t i = (size_t)small[(size_t)j];
-            for (int t = 0; t < batch_size; ++t) {
-                best_vals[i * (size_t)batch_size + (size_t)t] = c->sets_batch_h_vals.p[(size_t)j * (size_t)batch_size + (size_t)t];
-                best_idxs[i * (size_t)batch_size + (size_t)t] = c->sets_batch_h_idxs.p[(size_t)j * (size_t)batch_size + (size_t)t];
-            }
-            done[i] = 1;
-        }
-    }
-    for (int i = 0; i < n_sets; ++i) {
-        if (done[(size_t)i]) continue;
-        int rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
-        if (rc == CBO_OK)
-            rc = cbo_acq_sweep_batch(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], batch_size, update_incumbent,
-                                     best_vals + (size_t)i * (size_t)batch_size, best_idxs + (size_t)i * (size_t)batch_size,
-                                     nullptr, nullptr, nullptr);
-        if (rc != CBO_OK) return rc;
-    }
-    return CBO_OK;
+        },
+        [&](int i) -> int {
+            const int rc = ensure_fitted(gps[i]);
+            if (rc != CBO_OK) return rc;
+            return cbo_acq_sweep_batch(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], batch_size, update_incumbent,
+                                       best_vals + (size_t)i * B, best_idxs + (size_t)i * B, nullptr, nullptr, nullptr);
+        });
 }
 
 // ---- gradient refinement of every set's starts (kernels_sets_refine.hip) -----------------------------------
 // One launch for every set the kernel takes (small_sweep_model, no prior); the others are declined here, their status
-// entries alone written.  The models are only read.
+// entries alone written.  The models are only read.  Of the routing policy this call shares the partition alone: it has no
+// general path (a set the launch declines is declined), and its outputs come back behind a memset of the status words and a
+// stream synchronisation, not through polled records.
 extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int kind, const double *y_best,
                                    int task, double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
                                    int *rounds_out, int *status_out)
@@ -2648,23 +2707,24 @@ extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_ref
     std::vector<int64_t> row_off((size_t)n_sets);
     std::vector<int> out_off((size_t)n_sets), small;
     int64_t rows = 0;
-    int outs = 0, blocks = 1;
+    int outs = 0;
     for (int i = 0; i < n_sets; ++i) {
         row_off[(size_t)i] = rows;
         out_off[(size_t)i] = outs;
         rows += (int64_t)sets[i].k * gps[i]->d;
         outs += sets[i].k;
-        if (small_sweep_model(gps[i]) && gps[i]->X.sv == nullptr) {
-            small.push_back(i);
-            const int per = small_refine_starts_per_block(gps[i]->d);
-            const int b = (sets[i].k + per - 1) / per;
-            if (b > blocks) blocks = b;
-        } else {
-            for (int s = 0; s < sets[i].k; ++s) status_out[outs - sets[i].k + s] = CBO_REFINE_DECLINED;
-        }
+    }
+    const int blocks = partition_small(n_sets, [&](int i) { return small_sweep_model(gps[i]) && gps[i]->X.sv == nullptr; },
+                                       [&](int i) {
+                                           const int per = small_refine_starts_per_block(gps[i]->d);
+                                           return (int64_t)((sets[i].k + per - 1) / per);
+                                       }, small);
+    const int ns = (int)small.size();
+    for (int i = 0, j = 0; i < n_sets; ++i) {
+        if (j < ns && small[(size_t)j] == i) ++j;
+        else std::fill_n(status_out + out_off[(size_t)i], sets[i].k, (int)CBO_REFINE_DECLINED);
     }
     if (small.empty()) return CBO_OK;
-    const int ns = (int)small.size();
     int rc = ensure_small_buffers(c, ns, blocks);
     const size_t cap = ns < 32 ? (size_t)32 : (size_t)ns;
     if (rc == CBO_OK) rc = grow(c, c->refine_host, cap);
@@ -2769,10 +2829,8 @@ extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cb
         sg[nm] = gps[i]; sk[nm] = cands[i]; ++nm;
         for (int64_t j = first[(size_t)i]; j < first[(size_t)i + 1]; ++j, ++nm) { sg[nm] = con_gps[j]; sk[nm] = con_cands[j]; }
         for (int a = 0; a < nm; ++a) {
-            const int rc = check_sweep_args(sg[a], sk[a], task);
+            const int rc = check_set_handle(sg[a], sk[a], task, gps[0], "models");
             if (rc != CBO_OK) return rc;
-            if (sg[a]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all models must live on one context");
-            if (sg[a]->n <= 0 || sg[a]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
             if (sk[a]->m != sk[0]->m) return fail(CBO_ERR_INVALID, "the candidate sets of a set differ in size");
             for (int b = 0; b < a; ++b)
                 if (sk[b] == sk[a] && sg[b] != sg[a])
@@ -2780,22 +2838,19 @@ extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cb
         }
     }
     cbo_ctx *c = gps[0]->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     std::vector<int> small;
-    int blocks = 1, n_pairs = 0, max_pairs = 1;
-    for (int i = 0; i < n_sets; ++i) {
+    const int blocks = partition_small(n_sets, [&](int i) {          // every model of the set
         bool ok = small_sweep_model(gps[i]);
         for (int64_t j = first[(size_t)i]; ok && j < first[(size_t)i + 1]; ++j) ok = small_sweep_model(con_gps[j]);
-        if (!ok) continue;
-        small.push_back(i);
+        return ok;
+    }, [&](int i) { return cand_blocks(cands[i]); }, small);
+    const int ns = (int)small.size();
+    int n_pairs = 0, max_pairs = 1;
+    for (int i : small) {
         n_pairs += 1 + n_con[i];
         if (1 + n_con[i] > max_pairs) max_pairs = 1 + n_con[i];
-        const int b = (int)((cands[i]->m + 63) / 64);
-        if (b > blocks) blocks = b;
     }
-    std::vector<char> done((size_t)n_sets, 0);
-    if (!small.empty() && blocks <= 65535) {
-        const int ns = (int)small.size();
+    auto prepare = [&]() -> int {
         // descriptors for every pair; status words, tickets, records, scratch and partial winners per set
         int rc = ensure_small_buffers(c, n_pairs, 1);
         if (rc == CBO_OK) rc = ensure_small_buffers(c, ns, blocks);
@@ -2807,45 +2862,33 @@ extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cb
             first_pair[(size_t)j] = p;
             for (int a = 0; a <= n_con[i]; ++a, ++p) {
                 const int64_t cj = first[(size_t)i] + a - 1;
-                cbo_gp *g = a == 0 ? gps[i] : con_gps[cj];
-                cbo_cands *k = a == 0 ? cands[i] : con_cands[cj];
-                rc = prepare_cands(g, k);
-                if (rc != CBO_OK) return rc;
                 cbo_small_set &st = c->sets_host[p];
-                fill_small_model(st, g);
-                fill_small_cands(st, g, k);
+                // (a constraint's sense, value and jitter ride in task, y_best and ei_jitter)
+                rc = a == 0 ? fill_small_set(st, gps[i], cands[i], task, y_best[i], ei_jitter, costs[i])
+                            : fill_small_set(st, con_gps[cj], con_cands[cj], con_sense[cj], con_value[cj], con_jitter[cj],
+                                             costs[i]);
+                if (rc != CBO_OK) return rc;
                 st.index_offset = cands[i]->index_offset;       // (the set's: the objective's candidates name the winner)
-                if (a == 0) { st.task = task; st.y_best = y_best[i]; st.ei_jitter = ei_jitter; }
-                else { st.task = con_sense[cj]; st.y_best = con_value[cj]; st.ei_jitter = con_jitter[cj]; }
-                st.cost = costs[i];
             }
         }
         for (int j = 0; j < ns; ++j) c->sets_host[j].pad_ = first_pair[(size_t)j];      // the table: set j's first pair
-        auto launch = [&](int seq) -> int {
-            launch_small_sets_con(c->stream, c->sets_host, n_pairs, ns, max_pairs, blocks, c->small_scratch, c->small_part_val,
-                                  c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq);
-            HIP_TRY(hipGetLastError());
-            return CBO_OK;
-        };
-        rc = polled_launch(c, "cbo_acq_sweep_sets_constrained", c->small_out.p, ns, "multi-set sweep: no result record", launch);
-        if (rc != CBO_OK) return rc;
-        harvest_small_sets(c, small, best_vals, best_idxs, done);
-    }
-    for (int i = 0; i < n_sets; ++i) {
-        if (done[(size_t)i]) continue;
-        const int64_t f = first[(size_t)i];
-        int rc = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
-        for (int64_t j = f; rc == CBO_OK && j < first[(size_t)i + 1]; ++j)
-            if (!con_gps[j]->fitted) rc = cbo_gp_fit(con_gps[j], nullptr, nullptr);
-        if (rc == CBO_OK)
-            rc = cbo_acq_sweep_constrained(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], n_con[i],
-                                           n_con[i] ? con_gps + f : nullptr, n_con[i] ? con_cands + f : nullptr,
-                                           n_con[i] ? con_value + f : nullptr, n_con[i] ? con_jitter + f : nullptr,
-                                           n_con[i] ? con_sense + f : nullptr, nullptr, nullptr, nullptr, &best_vals[i],
-                                           &best_idxs[i]);
-        if (rc != CBO_OK) return rc;
-    }
-    return CBO_OK;
+        return CBO_OK;
+    };
+    return run_small_or_general(
+        c, "cbo_acq_sweep_sets_constrained", "multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
+        [&](const SmallLaunch &L) { launch_small_sets_con(c->stream, c->sets_host, n_pairs, ns, max_pairs, blocks, L); },
+        [&](int j, int i) { return harvest_winner(c, j, i, best_vals, best_idxs); },
+        [&](int i) -> int {
+            const int64_t f = first[(size_t)i];
+            int rc = ensure_fitted(gps[i]);
+            for (int64_t j = f; rc == CBO_OK && j < first[(size_t)i + 1]; ++j) rc = ensure_fitted(con_gps[j]);
+            if (rc != CBO_OK) return rc;
+            return cbo_acq_sweep_constrained(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], n_con[i],
+                                             n_con[i] ? con_gps + f : nullptr, n_con[i] ? con_cands + f : nullptr,
+                                             n_con[i] ? con_value + f : nullptr, n_con[i] ? con_jitter + f : nullptr,
+                                             n_con[i] ? con_sense + f : nullptr, nullptr, nullptr, nullptr, &best_vals[i],
+                                             &best_idxs[i]);
+        });
 }
 
 // ---- the causal EI marginalised over hyper-parameter samples (kernels_hyper.hip) -------------------------
@@ -2912,26 +2955,22 @@ extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const
         if (!std::isfinite(row[1 + n_ls]) || row[1 + n_ls] < 0.0)
             return fail(CBO_ERR_INVALID, "hyper row " + std::to_string(h) + ": noise_var must be finite and non-negative");
     }
+    // The one-item case of the routing policy, written out: run_small_or_general's two vectors would be this call's only
+    // heap allocations.
     cbo_ctx *c = g->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    const int64_t blocks64 = (k->m + 63) / 64;
-    if (small_sweep_model(g) && blocks64 <= 65535) {
-        const int blocks = (int)blocks64;
+    if (small_sweep_model(g) && cand_blocks(k) <= kMaxGridBlocks) {
+        const int blocks = (int)cand_blocks(k);
         rc = ensure_small_buffers(c, 1, blocks > n_samples ? blocks : n_samples);
         if (rc == CBO_OK) rc = grow(c, c->hyper_host, (size_t)CBO_MAX_HYPER_SAMPLES * (CBO_MAX_DIM + 2));
         if (rc == CBO_OK && acq_out) rc = grow_vectors(c, k->m_pad);
         if (rc != CBO_OK) return rc;
         std::memcpy(c->hyper_host.p, hyper, sizeof(double) * (size_t)n_samples * (size_t)row_len);
-        const bool causal = g->X.sv != nullptr;
         cbo_small_set st{};
-        fill_small_model(st, g);
-        st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
-        st.m = k->m; st.index_offset = k->index_offset;
-        st.task = task; st.y_best = y_best; st.ei_jitter = ei_jitter; st.cost = cost;
+        fill_hyper_set(st, g, k, task, y_best, ei_jitter, cost);
         auto launch = [&](int seq) -> int {
             launch_hyper_avg(c->stream, st, k->raw, c->hyper_host, n_samples, n_ls, acq_out ? c->acq.p : nullptr, blocks,
-                             c->hyper_schedule, c->small_scratch, c->small_part_val, c->small_part_idx, c->small_info,
-                             c->small_info + c->small_info.cap / 2, c->small_out, seq);
+                             c->hyper_schedule, small_launch(c, seq));
             HIP_TRY(hipGetLastError());
             return CBO_OK;
         };
@@ -2974,12 +3013,8 @@ extern "C" int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cand
     }
     // the handles, then the rows (whose length is the model's)
     if (!gps || !cands) return fail(CBO_ERR_INVALID, "NULL argument: gps and cands must be given");
-    for (int i = 0; i < n_sets; ++i) {
-        const int rc = check_sweep_args(gps[i], cands[i], task);
-        if (rc != CBO_OK) return rc;
-        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
-        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
-    }
+    int rc = check_set_handles(n_sets, gps, cands, task);
+    if (rc != CBO_OK) return rc;
     std::vector<int> n_ls((size_t)n_sets);
     for (int i = 0; i < n_sets; ++i) {
         const int L = n_ls[(size_t)i] = gps[i]->h.ard ? gps[i]->d : 1;
@@ -2994,28 +3029,21 @@ extern "C" int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cand
         }
     }
     cbo_ctx *c = gps[0]->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     std::vector<int> small;
-    int blocks = 1;
-    int64_t blocks_max = 1;
+    const int blocks = partition_small(n_sets, [&](int i) { return small_sweep_model(gps[i]); },
+                                       [&](int i) { return cand_blocks(cands[i]); }, small);
+    const int ns = (int)small.size();
     size_t total = 0, doubles = 0;                              // samples and doubles of the small sets' rows
-    for (int i = 0; i < n_sets; ++i) {
-        if (!small_sweep_model(gps[i])) continue;
-        small.push_back(i);
-        const int64_t b = (cands[i]->m + 63) / 64;
-        if (b > blocks_max) blocks_max = b;
+    for (int i : small) {
         total += (size_t)n_samples[i];
         doubles += (size_t)n_samples[i] * (size_t)(n_ls[(size_t)i] + 2);
     }
-    std::vector<char> done((size_t)n_sets, 0);
-    if (!small.empty() && blocks_max <= 65535) {
-        blocks = (int)blocks_max;
-        const int ns = (int)small.size();
-        // two launches from kSmallTwoPhaseFromBlocks blocks per set on (CBO_HIP_HYPER_SCHEDULE=1 / =2: never / always) -- but
-        // only when one scratch slot per sample of the call fits the workspace limit; else every workgroup factors for itself
-        bool two_phase = c->hyper_schedule == 2 || (c->hyper_schedule != 1 && blocks >= kSmallTwoPhaseFromBlocks);
-        if (two_phase && sizeof(double) * hyper_sets_scratch_doubles(ns, blocks, (int)total, true) > c->max_ws_bytes)
-            two_phase = false;
+    // two launches from kSmallTwoPhaseFromBlocks blocks per set on (CBO_HIP_HYPER_SCHEDULE=1 / =2: never / always) -- but
+    // only when one scratch slot per sample of the call fits the workspace limit; else every workgroup factors for itself
+    bool two_phase = c->hyper_schedule == 2 || (c->hyper_schedule != 1 && blocks >= kSmallTwoPhaseFromBlocks);
+    if (two_phase && sizeof(double) * hyper_sets_scratch_doubles(ns, blocks, (int)total, true) > c->max_ws_bytes)
+        two_phase = false;
+    auto prepare = [&]() -> int {
         int rc = ensure_small_buffers(c, ns, 1);                // records, status words, tickets
         if (rc == CBO_OK) rc = grow(c, c->hyper_sets_host, ns < 32 ? (size_t)32 : (size_t)ns);
         if (rc == CBO_OK) rc = grow(c, c->hyper_host, doubles);
@@ -3027,44 +3055,28 @@ extern "C" int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cand
         int first = 0;
         for (int j = 0; j < ns; ++j) {
             const int i = small[(size_t)j];
-            const cbo_gp *g = gps[i];
-            const cbo_cands *k = cands[i];
             const size_t len = (size_t)n_samples[i] * (size_t)(n_ls[(size_t)i] + 2);
             std::memcpy(c->hyper_host.p + at, hyper[i], sizeof(double) * len);
-            const bool causal = g->X.sv != nullptr;
             HyperSet &hs = c->hyper_sets_host[j];
             hs = HyperSet{};
-            cbo_small_set &st = hs.a.st;
-            fill_small_model(st, g);
-            st.cpm = causal ? k->pm : nullptr; st.cpv = causal ? k->pv : nullptr;
-            st.m = k->m; st.index_offset = k->index_offset;
-            st.task = task; st.y_best = y_best[i]; st.ei_jitter = ei_jitter; st.cost = costs[i];
-            hs.a.craw = k->raw; hs.a.hyper = c->hyper_host.p + at; hs.a.n_samples = n_samples[i]; hs.a.n_ls = n_ls[(size_t)i];
-            hs.a.acq_out = nullptr;
+            fill_hyper_set(hs.a.st, gps[i], cands[i], task, y_best[i], ei_jitter, costs[i]);
+            hs.a.craw = cands[i]->raw; hs.a.hyper = c->hyper_host.p + at; hs.a.n_samples = n_samples[i];
+            hs.a.n_ls = n_ls[(size_t)i]; hs.a.acq_out = nullptr;
             hs.first = first;
             at += len;
             first += n_samples[i];
         }
-        auto launch = [&](int seq) -> int {
-            launch_hyper_sets(c->stream, c->hyper_sets_host, ns, blocks, (int)total, two_phase, c->small_scratch,
-                              c->small_part_val, c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2,
-                              c->small_out, seq);
-            HIP_TRY(hipGetLastError());
-            return CBO_OK;
-        };
-        rc = polled_launch(c, "cbo_acq_sweep_sets_hyper", c->small_out.p, ns, "marginalised multi-set sweep: no result record",
-                           launch);
-        if (rc != CBO_OK) return rc;
-        harvest_small_sets(c, small, best_vals, best_idxs, done);
-    }
-    for (int i = 0; i < n_sets; ++i) {
-        if (done[(size_t)i]) continue;
+        return CBO_OK;
+    };
+    return run_small_or_general(
+        c, "cbo_acq_sweep_sets_hyper", "marginalised multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
+        [&](const SmallLaunch &L) { launch_hyper_sets(c->stream, c->hyper_sets_host, ns, blocks, (int)total, two_phase, L); },
+        [&](int j, int i) { return harvest_winner(c, j, i, best_vals, best_idxs); },
         // a larger or fp32 model, or a sample that is not positive definite as assembled: the general path, model restored
-        const int rc = hyper_general_path(gps[i], cands[i], n_samples[i], n_ls[(size_t)i], hyper[i], y_best[i], task, ei_jitter,
-                                          costs[i], nullptr, &best_vals[i], &best_idxs[i]);
-        if (rc != CBO_OK) return rc;
-    }
-    return CBO_OK;
+        [&](int i) {
+            return hyper_general_path(gps[i], cands[i], n_samples[i], n_ls[(size_t)i], hyper[i], y_best[i], task, ei_jitter,
+                                      costs[i], nullptr, &best_vals[i], &best_idxs[i]);
+        });
 }
 
 // One reference-scale trial in ONE call (src/CBO.py:143-173, CBO.intervene): the model of the set that was intervened on
@@ -3122,11 +3134,9 @@ static int trial_step_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
                     sizeof(double) * (size_t)(n * g->d + n + (pv ? 2 * n : 0)) <= kStageBytes;
         // (everything the sweep would refuse is refused BEFORE the model's host-side state moves to the new data)
         for (int i = 0; i < n_sets; ++i) {
-            const int rc = check_sweep_args(gps[i], cands[i], task);
+            const int rc = check_set_handle(gps[i], cands[i], task, g, "sets", i != refit_set);   // (its data are on their way)
             if (rc != CBO_OK) return rc;
-            if (gps[i]->ctx != c) return fail(CBO_ERR_INVALID, "all sets must live on one context");
-            if (i != refit_set && (gps[i]->n <= 0 || gps[i]->n_pad <= 0)) return fail(CBO_ERR_INVALID, "a gp holds no data");
-            if (gps[i]->dtype == CBO_DTYPE_F64 && gps[i]->n_pad == kPadN && (cands[i]->m + 63) / 64 > 65535) fuse = false;
+            if (gps[i]->dtype == CBO_DTYPE_F64 && gps[i]->n_pad == kPadN && cand_blocks(cands[i]) > kMaxGridBlocks) fuse = false;
             // the same model in two sets: the other copy's workgroups would read the resident arrays while the staged set's
             // first workgroup rewrites them in the same launch -- the plain upload first, then the sweep
             if (i != refit_set && gps[i] == g) fuse = false;
@@ -3418,10 +3428,8 @@ extern "C" int cbo_gp_mes_gumbel_sets(int n_sets, cbo_gp *const *gps, cbo_cands 
     if (n_sets <= 0 || n_sets > 65535) return fail(CBO_ERR_INVALID, "n_sets must be in 1..65535");
     if (!gps || !grids || !quantiles || !a || !b) return fail(CBO_ERR_INVALID, "NULL argument");
     for (int i = 0; i < n_sets; ++i) {
-        const int rc = check_sweep_args(gps[i], grids[i], CBO_TASK_MIN);
+        const int rc = check_set_handle(gps[i], grids[i], CBO_TASK_MIN, gps[0]);
         if (rc != CBO_OK) return rc;
-        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
-        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data");
         if (grids[i]->m <= 0) return fail(CBO_ERR_INVALID, "the Gumbel grid of set " + std::to_string(i) + " is empty");
     }
     cbo_ctx *c = gps[0]->ctx;
@@ -3438,48 +3446,38 @@ extern "C" int cbo_gp_mes_gumbel_sets(int n_sets, cbo_gp *const *gps, cbo_cands 
     if (rc == CBO_OK) rc = grow(c, c->gumbel_status, 3 * (size_t)n_sets);
     if (rc == CBO_OK) rc = grow(c, c->gumbel_sets_host, (size_t)n_sets);
     if (rc != CBO_OK) return rc;
+    // Of the routing policy this call shares the partition, the descriptors and the launch buffers.  Its records are not
+    // polled: they are read behind the synchronisation of stage (2), so the launch is no polled launch and only takes its
+    // sequence number where those take theirs.  (A grid too wide for the launch sends that set alone to the general path.)
     std::vector<int> small;
-    int64_t blocks_max = 1;
-    for (int i = 0; i < n_sets; ++i) {
-        if (!small_sweep_model(gps[i]) || (grids[i]->m + 63) / 64 > 65535) continue;
-        small.push_back(i);
-        const int64_t bl = (grids[i]->m + 63) / 64;
-        if (bl > blocks_max) blocks_max = bl;
-    }
+    const int blocks = partition_small(
+        n_sets, [&](int i) { return small_sweep_model(gps[i]) && cand_blocks(grids[i]) <= kMaxGridBlocks; },
+        [&](int i) { return cand_blocks(grids[i]); }, small);
     // (1) the predict: the small models' grids in the one-workgroup launch ...
     const int ns = (int)small.size();
     int seq = 0;
     if (ns > 0) {
-        const int blocks = (int)blocks_max;
         rc = ensure_small_buffers(c, ns, blocks);
         if (rc == CBO_OK) rc = grow(c, c->aux_host, ns < 32 ? (size_t)32 : (size_t)ns);
-        if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            cbo_gp *g = gps[small[(size_t)j]];
-            cbo_cands *k = grids[small[(size_t)j]];
-            rc = prepare_cands(g, k);
-            if (rc != CBO_OK) return rc;
-            cbo_small_set &st = c->sets_host[j];
-            fill_small_model(st, g);
-            fill_small_cands(st, g, k);
-            st.task = CBO_TASK_MIN; st.y_best = 0.0; st.ei_jitter = 0.0; st.cost = 1.0;
-            c->aux_host[j] = cbo_small_aux{off[(size_t)small[(size_t)j]], 0};
+        for (int j = 0; rc == CBO_OK && j < ns; ++j) {
+            const int i = small[(size_t)j];
+            rc = fill_small_set(c->sets_host[j], gps[i], grids[i], CBO_TASK_MIN, 0.0, 0.0, 1.0);
+            c->aux_host[j] = cbo_small_aux{off[(size_t)i], 0};
         }
+        if (rc != CBO_OK) return rc;
         SmallAux aux;
         aux.per_set = c->aux_host;
         aux.mean_out = c->gumbel_mean;
         aux.var_out = c->gumbel_var;
-        if (++c->small_seq == 0) c->small_seq = 1;
-        seq = c->small_seq;
-        launch_small_sets(c->stream, kPredictKind, c->sets_host, ns, blocks, c->small_scratch, c->small_part_val,
-                          c->small_part_idx, c->small_info, c->small_info + c->small_info.cap / 2, c->small_out, seq, aux);
+        seq = next_small_seq(c);
+        launch_small_sets(c->stream, kPredictKind, c->sets_host, ns, blocks, small_launch(c, seq), aux);
         HIP_TRY(hipGetLastError());
     }
     // ... every other model's on the general path, into the same workspace
     std::vector<char> is_small((size_t)n_sets, 0);
     for (int j = 0; j < ns; ++j) is_small[(size_t)small[(size_t)j]] = 1;
     auto general_predict = [&](int i) -> int {
-        int r = gps[i]->fitted ? CBO_OK : cbo_gp_fit(gps[i], nullptr, nullptr);
+        int r = ensure_fitted(gps[i]);
         if (r == CBO_OK) r = posterior_of_set(gps[i], grids[i], 1);
         if (r != CBO_OK) return r;
         const size_t bytes = sizeof(double) * (size_t)grids[i]->m;
@@ -3887,61 +3885,53 @@ extern "C" int cbo_gp_lml_gradients_batch(int n_models, cbo_gp *const *gps, doub
                                           double *dnoise, int *status)
 {
     if (n_models <= 0 || !gps || !lml || !dvar || !dls || !dnoise || !status) return fail(CBO_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n_models; ++i) {
-        if (!gps[i]) return fail(CBO_ERR_INVALID, "NULL gp");
-        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all models must live on one context");
-    }
+    int rc = check_model_handles(n_models, gps);
+    if (rc != CBO_OK) return rc;
     cbo_ctx *c = gps[0]->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<int> small, rest;
+    std::vector<int> small;
     bool any_mid = false;
-    for (int i = 0; i < n_models; ++i) {
+    partition_small(n_models, [&](int i) {
         const bool mid = mid_lml_eligible(gps[i]);
         any_mid = any_mid || mid;
-        (small_lml_eligible(gps[i]) || mid ? small : rest).push_back(i);
-    }
+        return small_lml_eligible(gps[i]) || mid;
+    }, [](int) { return (int64_t)1; }, small);
     const int ns = (int)small.size();
-    if (ns > 0) {
-        // descriptors + status words, and a scratch slot per model: factor + L^-1 (n <= 128), or the two-block slab
-        const size_t stride = any_mid ? mid_lml_scratch_doubles() : small_lml_scratch_doubles();
+    // a scratch slot per model: factor + L^-1 (n <= 128), or the two-block slab
+    const size_t stride = any_mid ? mid_lml_scratch_doubles() : small_lml_scratch_doubles();
+    auto prepare = [&]() -> int {
         const size_t per_block = small_sets_scratch_doubles(1, 1);
-        const int blocks = (int)((stride + per_block - 1) / per_block);
-        int rc = ensure_small_buffers(c, ns, blocks);
+        int rc = ensure_small_buffers(c, ns, (int)((stride + per_block - 1) / per_block));
         if (rc != CBO_OK) return rc;
         if ((size_t)ns * stride > c->small_scratch.cap)
             return fail(CBO_ERR_INVALID, "likelihood batch: scratch smaller than expected");
         rc = grow(c, c->lml_batch_out, ns < 32 ? 32 : (size_t)ns, true);
-        if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            cbo_small_set st{};
-            fill_small_model(st, gps[small[(size_t)j]]);
-            c->sets_host[j] = st;
+        for (int j = 0; rc == CBO_OK && j < ns; ++j) {
+            c->sets_host[j] = cbo_small_set{};
+            fill_small_model(c->sets_host[j], gps[small[(size_t)j]]);
         }
-        cbo_small_lml_result *out = c->lml_batch_out;
-        auto launch = [&](int seq) -> int {
-            launch_small_lml_batch(c->stream, c->sets_host, ns, c->small_scratch, (int64_t)stride, c->small_info, out, seq);
-            return hipGetLastError() != hipSuccess ? fail(CBO_ERR_HIP, "small_lml_batch_kernel launch") : CBO_OK;
-        };
-        rc = polled_launch(c, "cbo_gp_lml_gradients_batch", out, ns, "likelihood batch kernel: no result record", launch);
-        if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            const int i = small[(size_t)j];
-            if (out[j].info != 0) { rest.push_back(i); continue; }
-            const double *t = out[j].terms;
-            lml_outputs(gps[i], t, t[1 + CBO_MAX_DIM], t[1 + CBO_MAX_DIM + 1], t[1 + CBO_MAX_DIM + 2],
-                        t[1 + CBO_MAX_DIM + 3], &lml[i], &dvar[i], &dls[(size_t)i * CBO_MAX_DIM], &dnoise[i]);
+        return rc;
+    };
+    return run_small_or_general(
+        c, "cbo_gp_lml_gradients_batch", "likelihood batch kernel: no result record", n_models, small, c->lml_batch_out, prepare,
+        [&](const SmallLaunch &L) {
+            launch_small_lml_batch(c->stream, c->sets_host, ns, L.scratch, (int64_t)stride, L.info, c->lml_batch_out, L.seq);
+        },
+        [&](int j, int i) {
+            const double *t = c->lml_batch_out[j].terms;
+            lml_outputs(gps[i], t, t[1 + CBO_MAX_DIM], t[1 + CBO_MAX_DIM + 1], t[1 + CBO_MAX_DIM + 2], t[1 + CBO_MAX_DIM + 3],
+                        &lml[i], &dvar[i], &dls[(size_t)i * CBO_MAX_DIM], &dnoise[i]);
             status[i] = CBO_OK;
-        }
-    }
-    for (int i : rest) {
-        int rc = CBO_OK;
-        if (mid_lml_eligible(gps[i]) && !gps[i]->fitted) rc = cbo_gp_fit(gps[i], nullptr, nullptr);   // (jitchol ladder)
-        if (rc == CBO_OK)
-            rc = general_lml_gradients(gps[i], &lml[i], &dvar[i], &dls[(size_t)i * CBO_MAX_DIM], &dnoise[i]);
-        if (rc == CBO_ERR_HIP) return rc;               // the device is in trouble: no per-model answer means anything
-        status[i] = rc;
-    }
-    return CBO_OK;
+            return CBO_OK;
+        },
+        // an error is the model's status, not the call's -- unless the device is in trouble: no per-model answer means anything
+        [&](int i) -> int {
+            int rc = CBO_OK;
+            if (mid_lml_eligible(gps[i]) && !gps[i]->fitted) rc = cbo_gp_fit(gps[i], nullptr, nullptr);   // (jitchol ladder)
+            if (rc == CBO_OK)
+                rc = general_lml_gradients(gps[i], &lml[i], &dvar[i], &dls[(size_t)i * CBO_MAX_DIM], &dnoise[i]);
+            status[i] = rc;
+            return rc == CBO_ERR_HIP ? rc : CBO_OK;
+        });
 }
 
 static int general_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out, double *dlengthscale_out,
@@ -4064,58 +4054,49 @@ extern "C" int cbo_gp_loo(cbo_gp *g, double *mean_out, double *var_out, double *
 extern "C" int cbo_gp_loo_batch(int n_models, cbo_gp *const *gps, double *sum_lpd, double *lpd_cat, int *status)
 {
     if (n_models <= 0 || !gps || !sum_lpd || !status) return fail(CBO_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n_models; ++i) {
-        if (!gps[i]) return fail(CBO_ERR_INVALID, "NULL gp");
-        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all models must live on one context");
-    }
+    int rc = check_model_handles(n_models, gps);
+    if (rc != CBO_OK) return rc;
     cbo_ctx *c = gps[0]->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<int> small, rest;
+    std::vector<int> small;
     std::vector<int64_t> offset((size_t)n_models);
     int64_t total = 0;
     for (int i = 0; i < n_models; ++i) {
         offset[(size_t)i] = total;
         total += gps[i]->n;
-        (small_lml_eligible(gps[i]) ? small : rest).push_back(i);
     }
+    partition_small(n_models, [&](int i) { return small_lml_eligible(gps[i]); }, [](int) { return (int64_t)1; }, small);
     const int ns = (int)small.size();
-    if (ns > 0) {
+    auto prepare = [&]() -> int {
         int rc = ensure_small_buffers(c, ns, 1);
         if (rc != CBO_OK) return rc;
         if ((size_t)ns * small_loo_scratch_doubles() > c->small_scratch.cap)
             return fail(CBO_ERR_INVALID, "leave-one-out batch: scratch smaller than expected");
         rc = grow(c, c->loo_out, ns < 32 ? 32 : (size_t)ns, true);
-        if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            cbo_small_set st{};
-            fill_small_model(st, gps[small[(size_t)j]]);
-            c->sets_host[j] = st;
+        for (int j = 0; rc == CBO_OK && j < ns; ++j) {
+            c->sets_host[j] = cbo_small_set{};
+            fill_small_model(c->sets_host[j], gps[small[(size_t)j]]);
         }
-        cbo_small_loo_result *out = c->loo_out;
-        auto launch = [&](int seq) -> int {
-            launch_small_loo_batch(c->stream, c->sets_host, ns, c->small_scratch, c->small_info, out, seq);
-            return hipGetLastError() != hipSuccess ? fail(CBO_ERR_HIP, "small_loo_batch_kernel launch") : CBO_OK;
-        };
-        rc = polled_launch(c, "cbo_gp_loo_batch", out, ns, "leave-one-out batch kernel: no result record", launch);
-        if (rc != CBO_OK) return rc;
-        for (int j = 0; j < ns; ++j) {
-            const int i = small[(size_t)j];
-            if (out[j].info != 0) { rest.push_back(i); continue; }
-            sum_lpd[i] = out[j].sum;
-            if (lpd_cat) std::memcpy(lpd_cat + offset[(size_t)i], out[j].lpd, sizeof(double) * (size_t)gps[i]->n);
+        return rc;
+    };
+    return run_small_or_general(
+        c, "cbo_gp_loo_batch", "leave-one-out batch kernel: no result record", n_models, small, c->loo_out, prepare,
+        [&](const SmallLaunch &L) { launch_small_loo_batch(c->stream, c->sets_host, ns, L.scratch, L.info, c->loo_out, L.seq); },
+        [&](int j, int i) {
+            sum_lpd[i] = c->loo_out[j].sum;
+            if (lpd_cat) std::memcpy(lpd_cat + offset[(size_t)i], c->loo_out[j].lpd, sizeof(double) * (size_t)gps[i]->n);
             status[i] = CBO_OK;
-        }
-    }
-    for (int i : rest) {
-        cbo_gp *g = gps[i];
-        int rc = CBO_OK;
-        if (!g->fitted && g->n_pad == kPadN) rc = cbo_gp_fit(g, nullptr, nullptr);   // (jitchol ladder)
-        if (rc == CBO_OK && !g->fitted) rc = fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
-        if (rc == CBO_OK) rc = general_loo(g, nullptr, nullptr, lpd_cat ? lpd_cat + offset[(size_t)i] : nullptr, &sum_lpd[i]);
-        if (rc == CBO_ERR_HIP) return rc;               // the device is in trouble: no per-model answer means anything
-        status[i] = rc;
-    }
-    return CBO_OK;
+            return CBO_OK;
+        },
+        // an error is the model's status, not the call's -- unless the device is in trouble: no per-model answer means anything
+        [&](int i) -> int {
+            cbo_gp *g = gps[i];
+            int rc = CBO_OK;
+            if (!g->fitted && g->n_pad == kPadN) rc = cbo_gp_fit(g, nullptr, nullptr);   // (jitchol ladder)
+            if (rc == CBO_OK && !g->fitted) rc = fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+            if (rc == CBO_OK) rc = general_loo(g, nullptr, nullptr, lpd_cat ? lpd_cat + offset[(size_t)i] : nullptr, &sum_lpd[i]);
+            status[i] = rc;
+            return rc == CBO_ERR_HIP ? rc : CBO_OK;
+        });
 }
 
 // the reversed factor of the backward substitution (kernels_kmat.hip), once per fit

@@ -352,8 +352,17 @@ struct SmallAux {
     const double *data = nullptr;
     double *mean_out = nullptr, *var_out = nullptr;
 };
-void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
-                       double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
+// What every launch of these kernels takes from its context beside the descriptors: scratch and partial winners per
+// workgroup, one status word, one ticket and one (pinned) record per set, and the call's sequence number, which closes a
+// record.  The host wrappers below take it whole and unpack it into the kernels' parameter lists.
+struct SmallLaunch {
+    double *scratch, *part_val;
+    int64_t *part_idx;
+    int *info, *ticket;
+    cbo_small_result *out;
+    int seq;
+};
+void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, const SmallLaunch &L,
                        const SmallAux &aux = SmallAux());
 // ---- gradient refinement of every set's starts in one launch (kernels_sets_refine.hip) ----------------------
 // What a set's searches need beside the model's descriptor (pinned, device-mapped: read by the kernel directly): the box,
@@ -388,8 +397,7 @@ struct SmallBatchArgs {
     int batch_size, update_incumbent;
 };
 size_t small_sets_batch_doubles(int n_sets, int blocks_per_set, int batch_size);
-void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
-                             double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
+void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, const SmallLaunch &L,
                              double *batch_scratch, int batch_size, int update_incumbent, double *h_vals, int64_t *h_idxs);
 // the same launch with the constrained epilogue (kernels_sets_con.hip, small_sets_con_kernel): `pairs` holds
 // one descriptor per (model, candidate set) pair, a set's pairs consecutive with the objective first; a constraint's value,
@@ -397,8 +405,7 @@ void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_set
 // pairs of one set (<= 1 + CBO_MAX_CONSTRAINTS).  scratch, part_val, part_idx: n_sets * blocks_per_set slots; info, ticket,
 // out: one per SET, as above
 void launch_small_sets_con(hipStream_t s, const cbo_small_set *pairs, int n_pairs, int n_sets, int max_pairs,
-                           int blocks_per_set, double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket,
-                           cbo_small_result *out, int seq);
+                           int blocks_per_set, const SmallLaunch &L);
 
 // ---- hyper-parameter-marginalised EI (kernels_hyper.hip) ----------------------------------------------
 // One launch (schedule 1) or two (2; 0 = by the number of candidate blocks) for a model of at most 128 observations: st is
@@ -408,8 +415,7 @@ void launch_small_sets_con(hipStream_t s, const cbo_small_set *pairs, int n_pair
 // zero on entry (zero again afterwards); the record out[0] (pinned) carries the winner and the status word.
 size_t hyper_avg_scratch_doubles(int blocks, int n_samples);
 void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
-                      int n_ls, double *acq_out, int blocks, int schedule, double *scratch, double *part_val,
-                      int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq);
+                      int n_ls, double *acq_out, int blocks, int schedule, const SmallLaunch &L);
 // The multi-set form (hyper_sets_kernel).  One descriptor per set: hyper_avg_kernel's arguments (acq_out
 // null) and `first`, the sum of the n_samples of the sets before it -- the scratch slot of the set's sample 0 in the
 // two-launch form.  sets may be pinned host memory (read by the kernel directly beyond kSmallByValue sets).
@@ -429,8 +435,7 @@ struct HyperSet {
 // total_samples workgroups factors every sample of every set once, the sweep reads the factors back.
 size_t hyper_sets_scratch_doubles(int n_sets, int blocks_per_set, int total_samples, bool two_phase);
 void launch_hyper_sets(hipStream_t s, const HyperSet *sets, int n_sets, int blocks_per_set, int total_samples, bool two_phase,
-                       double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out,
-                       int seq);
+                       const SmallLaunch &L);
 // the general path: sum[i] = (first ? 0 : sum[i]) + acq[i] for i < m; then acq_out[i] = sum[i] / n_samples (acq_out may be
 // null) with arg-max partials per workgroup (n_blocks <= 2048) for launch_argmax_final
 void launch_hyper_accumulate(hipStream_t s, double *sum, const double *acq, int64_t m, bool first, int n_blocks);

@@ -322,8 +322,7 @@ size_t hyper_avg_scratch_doubles(int blocks, int n_samples)
 // schedule 0: from kSmallTwoPhaseFromBlocks candidate blocks on, the samples are factored once by a first launch of n_samples
 // workgroups and the sweep reads the factors back (phases 1 + 2); below, every workgroup factors every sample itself (phases 3)
 void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
-                      int n_ls, double *acq_out, int blocks, int schedule, double *scratch, double *part_val,
-                      int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq)
+                      int n_ls, double *acq_out, int blocks, int schedule, const SmallLaunch &L)
 {
     static std::atomic<unsigned long long> opted{0};
     small_lds_opt_in(reinterpret_cast<const void *>(hyper_avg_kernel), opted);
@@ -331,13 +330,13 @@ void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw
     a.st = st; a.craw = craw; a.hyper = hyper; a.n_samples = n_samples; a.n_ls = n_ls; a.acq_out = acq_out;
     const bool two_phase = schedule == 2 || (schedule != 1 && blocks >= kSmallTwoPhaseFromBlocks);
     if (two_phase) {
-        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)n_samples), dim3(256), sizeof(SmallShared), s, a, scratch, blocks,
-                           part_val, part_idx, info, ticket, out, seq, 1);
-        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, scratch, blocks,
-                           part_val, part_idx, info, ticket, out, seq, 2);
+        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)n_samples), dim3(256), sizeof(SmallShared), s, a, L.scratch, blocks,
+                           L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 1);
+        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, L.scratch, blocks,
+                           L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 2);
     } else {
-        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, scratch, blocks,
-                           part_val, part_idx, info, ticket, out, seq, 3);
+        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, L.scratch, blocks,
+                           L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 3);
     }
 }
 
@@ -368,17 +367,16 @@ static void launch_hyper_sets_as(hipStream_t s, const HyperSetArgs &args, const 
 }
 
 void launch_hyper_sets(hipStream_t s, const HyperSet *sets, int n_sets, int blocks_per_set, int total_samples, bool two_phase,
-                       double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out,
-                       int seq)
+                       const SmallLaunch &L)
 {
     HyperSetArgs args{};
     if (n_sets <= kSmallByValue) {
         std::memcpy(args.s, sets, sizeof(HyperSet) * (size_t)n_sets);
-        launch_hyper_sets_as<true>(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, scratch, part_val,
-                                   part_idx, info, ticket, out, seq);
+        launch_hyper_sets_as<true>(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, L.scratch, L.part_val,
+                                   L.part_idx, L.info, L.ticket, L.out, L.seq);
     } else {
-        launch_hyper_sets_as<false>(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, scratch, part_val,
-                                    part_idx, info, ticket, out, seq);
+        launch_hyper_sets_as<false>(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, L.scratch, L.part_val,
+                                    L.part_idx, L.info, L.ticket, L.out, L.seq);
     }
 }
 

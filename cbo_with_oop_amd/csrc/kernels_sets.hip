@@ -145,18 +145,17 @@ static void launch_small_sets_as(hipStream_t s, const SmallSetArgs &args, const 
     }
 }
 
-void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
-                       double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
+void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n_sets, int blocks_per_set, const SmallLaunch &L,
                        const SmallAux &aux)
 {
     SmallSetArgs args{};
     const bool byval = n_sets <= kSmallByValue;
     if (byval) std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_sets);
 #define CBO_LAUNCH_KIND(K)                                                                                              \
-    (byval ? launch_small_sets_as<K, true>(s, args, sets, n_sets, blocks_per_set, scratch, part_val, part_idx, info,     \
-                                           ticket, out, seq, aux)                                                       \
-           : launch_small_sets_as<K, false>(s, args, sets, n_sets, blocks_per_set, scratch, part_val, part_idx, info,   \
-                                            ticket, out, seq, aux))
+    (byval ? launch_small_sets_as<K, true>(s, args, sets, n_sets, blocks_per_set, L.scratch, L.part_val, L.part_idx,     \
+                                           L.info, L.ticket, L.out, L.seq, aux)                                         \
+           : launch_small_sets_as<K, false>(s, args, sets, n_sets, blocks_per_set, L.scratch, L.part_val, L.part_idx,   \
+                                            L.info, L.ticket, L.out, L.seq, aux))
     switch (kind) {
         case CBO_ACQ_LCB: CBO_LAUNCH_KIND(CBO_ACQ_LCB); break;
         case CBO_ACQ_PI: CBO_LAUNCH_KIND(CBO_ACQ_PI); break;

@@ -264,8 +264,7 @@ static void launch_small_sets_batch_as(hipStream_t s, const SmallSetArgs &args, 
     }
 }
 
-void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, double *scratch,
-                             double *part_val, int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq,
+void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, const SmallLaunch &L,
                              double *batch_scratch, int batch_size, int update_incumbent, double *h_vals, int64_t *h_idxs)
 {
     SmallBatchArgs ba;
@@ -281,11 +280,11 @@ void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_set
     const bool byval = n_sets <= kSmallByValue;
     if (byval) std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_sets);
     if (byval)
-        launch_small_sets_batch_as<true>(s, args, sets, n_sets, blocks_per_set, scratch, part_val, part_idx, info, ticket, out,
-                                         seq, ba);
+        launch_small_sets_batch_as<true>(s, args, sets, n_sets, blocks_per_set, L.scratch, L.part_val, L.part_idx, L.info,
+                                         L.ticket, L.out, L.seq, ba);
     else
-        launch_small_sets_batch_as<false>(s, args, sets, n_sets, blocks_per_set, scratch, part_val, part_idx, info, ticket,
-                                          out, seq, ba);
+        launch_small_sets_batch_as<false>(s, args, sets, n_sets, blocks_per_set, L.scratch, L.part_val, L.part_idx, L.info,
+                                          L.ticket, L.out, L.seq, ba);
 }
 
 }  // namespace cbo

@@ -138,17 +138,16 @@ static void launch_small_sets_con_as(hipStream_t s, const SmallSetArgs &args, co
 
 // launch_small_sets for the constrained epilogue (cbo_internal.h)
 void launch_small_sets_con(hipStream_t s, const cbo_small_set *pairs, int n_pairs, int n_sets, int max_pairs,
-                           int blocks_per_set, double *scratch, double *part_val, int64_t *part_idx, int *info, int *ticket,
-                           cbo_small_result *out, int seq)
+                           int blocks_per_set, const SmallLaunch &L)
 {
     SmallSetArgs args{};
     if (n_pairs <= kSmallByValue) {
         std::memcpy(args.s, pairs, sizeof(cbo_small_set) * (size_t)n_pairs);
-        launch_small_sets_con_as<true>(s, args, pairs, n_pairs, n_sets, max_pairs, blocks_per_set, scratch, part_val, part_idx,
-                                       info, ticket, out, seq);
+        launch_small_sets_con_as<true>(s, args, pairs, n_pairs, n_sets, max_pairs, blocks_per_set, L.scratch, L.part_val,
+                                       L.part_idx, L.info, L.ticket, L.out, L.seq);
     } else {
-        launch_small_sets_con_as<false>(s, args, pairs, n_pairs, n_sets, max_pairs, blocks_per_set, scratch, part_val,
-                                        part_idx, info, ticket, out, seq);
+        launch_small_sets_con_as<false>(s, args, pairs, n_pairs, n_sets, max_pairs, blocks_per_set, L.scratch, L.part_val,
+                                        L.part_idx, L.info, L.ticket, L.out, L.seq);
     }
 }
 

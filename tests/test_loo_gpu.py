@@ -197,6 +197,40 @@ def test_unfitted_large_model_in_a_batch_disturbs_nobody(lib):
         m.close()
 
 
+def test_a_model_the_batch_launch_declines_takes_the_general_path_between_its_neighbours(lib):
+    """The jitter fixture (duplicate rows under a negative noise: the launch's pivot at the duplicate is about -2e-9, far
+    below rounding, so it declines there) between two ordinary small models: the batch fits it with the jitchol ladder and
+    answers with cbo_gp_loo's bits on a fitted twin; the neighbours stay unfitted and get their one-model batches' bits; the
+    same call again and the neighbours alone right after return the same bits."""
+    so = lib.load()
+    fj, fo = load_fixture("jitter_ladder"), load_fixture("graph_ard_d4")
+    ladder, twin = _fixture_model(fj, None, False), _fixture_model(fj, None, True)
+    models = [_fixture_model(fo, 17, False), ladder, _fixture_model(fo, 25, False)]
+    n = fj["X"].shape[0]
+    lpd_twin, total_twin = np.zeros(n), ctypes.c_double(0.0)
+    lib.check(so.cbo_gp_loo(twin._handle, None, None, lib.dptr(lpd_twin), ctypes.byref(total_twin)))
+    alone = [_loo_batch(lib, [models[i]]) for i in (0, 2)]
+    out, tries = np.empty(1), ctypes.c_int(-1)
+    for attempt in ("the call", "the same call again"):
+        rc, sums, lpds, status = _loo_batch(lib, models)
+        print(attempt, "sums", sums.tolist(), "twin", total_twin.value, "status", status.tolist())
+        assert rc == lib.CBO_OK and np.all(status == lib.CBO_OK)
+        assert sums[1] == total_twin.value and np.array_equal(lpds[1].view(np.uint64), lpd_twin.view(np.uint64))
+        for i, (_, sums1, lpds1, _) in zip((0, 2), alone):
+            assert sums1[0] == sums[i] and np.array_equal(lpds1[0].view(np.uint64), lpds[i].view(np.uint64)), (attempt, i)
+        assert so.cbo_gp_log_marginal(ladder._handle, lib.dptr(out)) == lib.CBO_OK         # the general path fitted it ...
+        assert so.cbo_gp_jitter(ladder._handle, ctypes.byref(tries), None) == lib.CBO_OK and tries.value >= 1   # ... by the ladder
+        for i in (0, 2):
+            assert so.cbo_gp_log_marginal(models[i]._handle, lib.dptr(out)) == lib.CBO_ERR_NOT_FITTED
+    rc, sums, lpds, status = _loo_batch(lib, models[::2])
+    assert rc == lib.CBO_OK and np.all(status == lib.CBO_OK)
+    for j, (_, sums1, lpds1, _) in enumerate(alone):
+        assert sums1[0] == sums[j] and np.array_equal(lpds1[0].view(np.uint64), lpds[j].view(np.uint64)), j
+    assert twin.jitter_tries >= 1                                                          # the premise: the fixture needs it
+    for m in models + [twin]:
+        m.close()
+
+
 def test_end_to_end_against_models_fitted_without_the_point(lib):
     """Independent of the restatement: the device's own prediction of y_i from a model fitted on the other 299 points.
     cbo_gp_predict adds the noise to its variance but not the 1e-8 GPy adds to the diagonal of Ky, which the LOO variance --

@@ -140,6 +140,39 @@ def test_models_and_candidates_are_left_as_they_were_and_two_calls_agree(lib, ke
     grid.close(); fitted.close(); unfitted.close()
 
 
+def test_a_set_the_launch_declines_takes_the_general_path_between_its_neighbours(lib):
+    """The jitter fixture (duplicate rows under a negative noise: the launch's pivot at the duplicate is about -2e-9, far
+    below rounding, so it declines there) between two ordinary small sets: every set's picks are cbo_acq_sweep_batch's on a
+    fitted twin; the declined set's model was fitted by the general path, with jitter, the neighbours' were not; the same
+    call again and a call of the neighbours alone return the same bits."""
+    ladder, ladder_grid, f = fixture_model("jitter_ladder", fit=False)
+    twin, twin_grid, _ = fixture_model("jitter_ladder", fit=True)
+    first, last = Pair(n=17, m=65, d=1), Pair(n=25, m=70, d=1, causal=True)
+    models, grids = [first.model, ladder, last.model], [first.grid, ladder_grid, last.grid]
+    twins, twin_grids = [first.twin, twin, last.twin], [first.twin_grid, twin_grid, last.twin_grid]
+    y_best, costs = [-0.1, float(f["y_best"]), 0.2], [2.0, 1.0, 3.0]
+    out, tries = np.empty(1), ctypes.c_int(-1)
+    for update in (0, 1):
+        rc, vals, idxs = sets_batch(lib, models, grids, y_best, "min", 3, costs, update)
+        lib.check(rc)
+        want = per_set_batch(lib, twins, twin_grids, y_best, "min", 3, costs, update)
+        assert_same((vals, idxs), want, f"ladder between neighbours, update={update}")
+        assert lib.load().cbo_gp_log_marginal(ladder._handle, lib.dptr(out)) == 0          # the general path fitted it ...
+        assert lib.load().cbo_gp_jitter(ladder._handle, ctypes.byref(tries), None) == 0 and tries.value >= 1   # ... by the ladder
+        for p in (first, last):
+            assert lib.load().cbo_gp_log_marginal(p.model._handle, lib.dptr(out)) == NOT_FITTED
+        rc, vals2, idxs2 = sets_batch(lib, models, grids, y_best, "min", 3, costs, update)
+        lib.check(rc)
+        assert_same((vals2, idxs2), (vals, idxs), "the same call again")
+        rc, vals3, idxs3 = sets_batch(lib, models[::2], grids[::2], y_best[::2], "min", 3, costs[::2], update)
+        lib.check(rc)
+        assert_same((vals3, idxs3), (want[0][::2], want[1][::2]), "the neighbours alone, right after")
+    assert twin.jitter_tries >= 1                                                          # the premise: the fixture needs it
+    for o in (ladder_grid, twin_grid, ladder, twin):
+        o.close()
+    first.close(); last.close()
+
+
 def test_the_picks_are_the_restatements_under_the_single_set_calls_bar(lib):
     B = 5
     cases = [fixture_model(name, fit=False) for name in ("causal_d2", "complete_bo_d3")]

@@ -17,7 +17,7 @@ import warnings
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, load_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -201,19 +201,39 @@ def test_twenty_five_sets(lib):
 
 
 # ---- routing ---------------------------------------------------------------------------------------------------------------
+def ladder_pair():
+    """The jitter fixture: duplicate rows under a negative noise -- the launch's pivot at the duplicate is about -2e-9, far
+    below rounding, so the launch declines the set and the general path's jitchol ladder takes over."""
+    f = load_fixture("jitter_ladder")
+    kw = dict(variance=float(f["variance"]), lengthscale=f["lengthscale_arg"], noise_var=float(f["noise_var"]))
+    return Pair(len(f["X"]), len(f["Xs"]), 1, kw=kw, data=(f["X"], f["y"]), cand=f["Xs"])
+
+
+def fitted_with_jitter(lib, model):
+    out, tries = np.empty(1), ctypes.c_int(-1)
+    return (lib.load().cbo_gp_log_marginal(model._handle, lib.dptr(out)) == 0
+            and lib.load().cbo_gp_jitter(model._handle, ctypes.byref(tries), None) == 0 and tries.value >= 1)
+
+
+MIXED_COSTS = [2.0, 3.0, 1.0, 2.0, 1.0, 3.0]
+
+
 def mixed_pairs():
-    """n = 50 (the one launch), n = 129 and an fp32 model (the general path inside the same call)."""
+    """n = 50 (the one launch); the jitter fixture between two ordinary small sets (it declines in the launch and takes the
+    general path, they do not); n = 129 and an fp32 model (the general path inside the same call)."""
     rng = np.random.default_rng(3)
     Xb = rng.uniform(-2, 2, (129, 3))
     yb = np.cos(Xb).sum(1, keepdims=True)
     cand = rng.uniform(-2.5, 2.5, (300, 3))
-    return [Pair(50, 200, 2, causal=True), Pair(129, 300, 3, kw=dict(noise_var=1e-3), data=(Xb, yb), cand=cand),
+    return [Pair(50, 200, 2, causal=True), Pair(17, 65, 1), ladder_pair(), Pair(25, 70, 2, causal=True),
+            Pair(129, 300, 3, kw=dict(noise_var=1e-3), data=(Xb, yb), cand=cand),
             Pair(129, 300, 3, kw=dict(noise_var=1e-2, dtype="f32"), data=(Xb, yb), cand=cand)]
 
 
 def mixed_mins(pairs):
     # (fixed numbers, the same in the child process: inside and outside the targets' range)
-    return [np.array([-1.5, 0.2, 1.0, -9.0, 9.0, 0.5, -0.3, 0.1, 0.0, -2.0]), np.array([0.5, -2.5, -20.0]), np.array([-1.0])]
+    return [np.array([-1.5, 0.2, 1.0, -9.0, 9.0, 0.5, -0.3, 0.1, 0.0, -2.0]), np.array([0.3, -1.2]),
+            np.array([-1.0, 0.4, -3.0, 0.0]), np.array([0.1]), np.array([0.5, -2.5, -20.0]), np.array([-1.0])]
 
 
 def child_mixed():
@@ -223,7 +243,7 @@ def child_mixed():
         warnings.simplefilter("ignore", RuntimeWarning)
         pairs = mixed_pairs()
         rc, vals, idxs = sweep_sets_mes(_lib, [p.model for p in pairs], [p.grid for p in pairs], mixed_mins(pairs),
-                                        [2.0, 1.0, 3.0])
+                                        MIXED_COSTS)
         _lib.check(rc)
         print("ANSWER", vals.view(np.uint64).tolist(), idxs.tolist())
 
@@ -233,10 +253,19 @@ def test_mixed_routing(lib):
         warnings.simplefilter("ignore", RuntimeWarning)
         pairs = mixed_pairs()
         mins = mixed_mins(pairs)
-        vals, idxs = check_call(lib, pairs, mins, [2.0, 1.0, 3.0], "mixed")
-    assert pairs[0].model.stale and unfitted(lib, [pairs[0].model])
+        vals, idxs = check_call(lib, pairs, mins, MIXED_COSTS, "mixed")
+    small = [0, 1, 3]
+    assert all(pairs[i].model.stale for i in small) and unfitted(lib, [pairs[i].model for i in small])
+    assert fitted_with_jitter(lib, pairs[2].model)                         # declined in the launch: the general path's ladder
     out = np.empty(1)
-    assert lib.load().cbo_gp_log_marginal(pairs[1].model._handle, lib.dptr(out)) == 0        # the general path fitted it
+    assert lib.load().cbo_gp_log_marginal(pairs[4].model._handle, lib.dptr(out)) == 0        # the general path fitted it
+    # the same call again: the same bits; the declined set's two neighbours alone right after: their single-set bits
+    rc, vals2, idxs2 = sweep_sets_mes(lib, [p.model for p in pairs], [p.grid for p in pairs], mins, MIXED_COSTS)
+    lib.check(rc)
+    assert_same((vals2, idxs2), (vals, idxs), "the same call again")
+    near = [1, 3]
+    check_call(lib, [pairs[i] for i in near], [mins[i] for i in near], [MIXED_COSTS[i] for i in near], "the neighbours alone")
+    assert unfitted(lib, [pairs[i].model for i in small])
     # the same call with the one launch switched off (read when the context is created: a process of its own)
     env = dict(os.environ, CBO_HIP_SMALL_SETS="0")
     code = ("import sys; sys.path[:0] = [%r, %r]; import test_sets_mes_gpu as t; t.child_mixed()"
@@ -310,17 +339,24 @@ def test_gumbel_shapes(lib):
 
 
 def test_gumbel_routing(lib):
-    """n = 129 and an fp32 model are fitted and predicted by the general path into the same workspace."""
+    """n = 129 and an fp32 model are fitted and predicted by the general path into the same workspace; so is the jitter
+    fixture, which declines in the launch between two ordinary small sets that do not."""
     rng = np.random.default_rng(5)
     Xb = rng.uniform(-2, 2, (129, 2))
     yb = np.cos(Xb).sum(1, keepdims=True)
     cand = np.vstack([Xb, rng.uniform(-2.5, 2.5, (100, 2))])
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)
-        pairs = gumbel_pairs([(50, 150, 2, True)]) + [Pair(129, 229, 2, kw=dict(noise_var=1e-3), data=(Xb, yb), cand=cand),
-                                                      Pair(129, 229, 2, kw=dict(noise_var=1e-2, dtype="f32"), data=(Xb, yb), cand=cand)]
+        pairs = (gumbel_pairs([(50, 150, 2, True), (17, 48, 1, False)]) + [ladder_pair()] + gumbel_pairs([(25, 45, 2, True)])
+                 + [Pair(129, 229, 2, kw=dict(noise_var=1e-3), data=(Xb, yb), cand=cand),
+                    Pair(129, 229, 2, kw=dict(noise_var=1e-2, dtype="f32"), data=(Xb, yb), cand=cand)])
         assert_gumbel_same(lib, pairs, "mixed")
-    assert unfitted(lib, [pairs[0].model])
+        small = [pairs[i].model for i in (0, 1, 3)]
+        assert unfitted(lib, small)
+        assert fitted_with_jitter(lib, pairs[2].model)                     # declined in the launch: the general path's ladder
+        assert_gumbel_same(lib, pairs, "the same call again")
+        assert_gumbel_same(lib, [pairs[1], pairs[3]], "the neighbours alone, right after")
+        assert unfitted(lib, small)
     for p in pairs:
         p.close()
 

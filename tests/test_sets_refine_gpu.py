@@ -437,6 +437,49 @@ def test_a_mixed_list_declines_what_the_kernel_cannot_take(lib, zoo):
     causal.model.close(); large.model.close()
 
 
+def test_a_set_that_declines_in_the_launch_is_declined_between_its_neighbours(lib, zoo):
+    """The jitter fixture (duplicate rows under a negative noise: the launch's pivot at the duplicate is about -2e-9, far
+    below rounding, so it declines there) between two ordinary small sets.  This call has no general path: every start of
+    the declined set comes back CBO_REFINE_DECLINED with its other entries untouched, no model is fitted, the neighbours'
+    outputs are their own calls' bit for bit; the same call again and the neighbours alone right after give the same bits."""
+    from cbo_with_oop_amd.GaussianProcessFactory import HipGaussianProcess
+    f = load_fixture("jitter_ladder")
+
+    class Holder:
+        pass
+    ladder = Holder()
+    ladder.model = HipGaussianProcess(f["X"], f["y"], fit=False, variance=float(f["variance"]),
+                                      lengthscale=f["lengthscale_arg"], noise_var=float(f["noise_var"]))
+    ladder.lo, ladder.hi, ladder.y_best, ladder.d = np.array([-1.0]), np.array([1.0]), float(f["y_best"]), 1
+    first, last = zoo["n10 d1"], zoo["n16 d2"]
+    cases = [first, ladder, last]
+    starts = [first.points(4), np.ascontiguousarray(f["Xs"][::21]), last.points(4)]
+    costs = [costs_of(c, i == 2) for i, c in enumerate(cases)]
+    alone = []
+    for i in (0, 2):
+        rc, (res,) = refine_call(lib, [cases[i]], [starts[i]], [costs[i]], sentinel=-77.0)
+        lib.check(rc)
+        alone.append(res)
+    same = lambda a, b: all(np.array_equal(np.ascontiguousarray(u).view(np.uint8), np.ascontiguousarray(v).view(np.uint8))  # noqa: E731
+                            for u, v in zip(a, b))
+    out = np.empty(1)
+    for attempt in ("the call", "the same call again"):
+        rc, res = refine_call(lib, cases, starts, costs, sentinel=-77.0)
+        lib.check(rc)
+        x, val, grad, rounds, status = res[1]
+        print(attempt, "ladder status", status.tolist(), "neighbours", res[0][4].tolist(), res[2][4].tolist())
+        assert np.all(status == lib.REFINE_DECLINED)
+        assert np.all(x == -77.0) and np.all(val == -77.0) and np.all(grad == -77.0) and np.all(rounds == -77)
+        assert same(res[0], alone[0]) and same(res[2], alone[1]), attempt
+        assert np.all(res[0][4] != lib.REFINE_DECLINED) and np.all(res[2][4] != lib.REFINE_DECLINED)
+        for c in cases:                                             # the models are only read: nobody was fitted
+            assert lib.load().cbo_gp_log_marginal(c.model._handle, lib.dptr(out)) == NOT_FITTED
+    rc, res = refine_call(lib, cases[::2], starts[::2], costs[::2], sentinel=-77.0)
+    lib.check(rc)
+    assert same(res[0], alone[0]) and same(res[1], alone[1]), "the neighbours alone, right after"
+    ladder.model.close()
+
+
 def test_refine_sets_completes_the_kind_and_can_leave_the_host_route_out(lib, zoo):
     """A ``None`` parameter is the kind's default (beta 1) on the device as it is on the host; ``host_fallback=False`` leaves
     a set the launch does not take unrefined; ``optimize(device=True)`` carries a jittered EI's jitter to the launch."""
