@@ -67,6 +67,16 @@ def checked_path_hyper_samples(hyper_samples, kind=("EI", None), constraints=())
     return int(hyper_samples)
 
 
+def checked_hyper_sampler(hyper_sampler, hyper_samples):
+    """``hyper_sampler`` checked on the host: ``"host"`` (the per-model host chain) or ``"device"`` (every chain in one
+    launch); a callable ``hyper_samples`` is its own sampler and takes ``"host"`` alone."""
+    if hyper_sampler not in ("host", "device"):
+        raise ValueError(f"hyper_sampler must be 'host' or 'device', not {hyper_sampler!r}")
+    if hyper_sampler == "device" and callable(hyper_samples):
+        raise ValueError("hyper_sampler='device' draws the samples itself: hyper_samples must be an int, not a callable")
+    return hyper_sampler
+
+
 class CBOAcquisitionPath:
     """Holds exactly the state those methods read on the reference's ``CBO`` object: ``gp_type``,
     ``exploration_set``, ``costs``, ``task``, per-set data, spaces, prior closures and models.  ``acquisition`` (``"EI"``,
@@ -85,6 +95,9 @@ class CBOAcquisitionPath:
     order) makes every set's score the causal EI marginalised over hyper-parameter samples of its own model:
     an int draws ``model.generate_hyperparameters_samples(H)`` with emukit's defaults.  The path keeps ``hyper_rows[s]`` and
     redraws them whenever it rebuilds the set's model.  It needs ``acquisition="EI"``, no constraints and a single process.
+    ``hyper_sampler="device"`` (with an int ``hyper_samples``) draws them by the one-launch HMC: every set's
+    rows in one ``cbo_gp_hmc_sets`` call after ``update_all_gaussian_processes``, the rebuilt set's in a one-model call;
+    ``"host"`` (default) is the per-model host chain.
     ``batch_size`` (an int B in 1..64) with ``update_incumbent`` makes every set's answer a greedy batch of B Kriging-believer
     picks in one device call (``find_next_y_points(batch_size=B)``): ``xs[s]`` is (B, d), ``ys[s]`` (B, 1); the
     set is chosen by pick 0, as before.  It needs ``acquisition="EI"``, no constraints, no hyper-parameter samples and a
@@ -97,7 +110,7 @@ class CBOAcquisitionPath:
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
-                 update_incumbent=False, refine=False):
+                 update_incumbent=False, refine=False, hyper_sampler="host"):
         from .utils_functions.utils import checked_refine, sets_acquisition_or_default as sets_acquisition
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
@@ -114,6 +127,7 @@ class CBOAcquisitionPath:
         self.constraint_data_y = constraint_data_y if self.constraints else None
         self.constraint_models = []
         self.hyper_samples = checked_path_hyper_samples(hyper_samples, self._kind, self.constraints)
+        self.hyper_sampler = checked_hyper_sampler(hyper_sampler, self.hyper_samples)
         self.hyper_rows = [None] * len(exploration_set)
         self.batch_size = checked_batch_size(batch_size, self._kind, self.constraints, self.hyper_samples)
         self.update_incumbent = bool(update_incumbent)
@@ -158,6 +172,13 @@ class CBOAcquisitionPath:
         if self.constraints:
             self.constraint_models = [[self._constraint_model(s, c) for c in range(len(self.constraints))]
                                       for s in range(self.es_size)]
+        if self.hyper_samples is not None and self.hyper_sampler == "device":
+            # every set's chain in one launch
+            from .GaussianProcessFactory import generate_hyperparameters_samples_together
+            from .utils_functions.integrated_hyper import _hyper_rows
+            drawn = generate_hyperparameters_samples_together(self.models, self.hyper_samples)
+            self.hyper_rows = [_hyper_rows(model, samples) for model, samples in zip(self.models, drawn)]
+            return
         for s in range(self.es_size):
             self._draw_hyper_rows(s)
 
@@ -167,8 +188,12 @@ class CBOAcquisitionPath:
             return
         from .utils_functions.integrated_hyper import _hyper_rows
         model = self.models[s]
-        samples = (self.hyper_samples(model, s) if callable(self.hyper_samples)
-                   else model.generate_hyperparameters_samples(self.hyper_samples))
+        if callable(self.hyper_samples):
+            samples = self.hyper_samples(model, s)
+        elif self.hyper_sampler == "device":
+            samples = model.generate_hyperparameters_samples(self.hyper_samples, sampler="device")
+        else:
+            samples = model.generate_hyperparameters_samples(self.hyper_samples)
         self.hyper_rows[s] = _hyper_rows(model, samples)
 
     def _constraint_model(self, s, c, fit=True):
@@ -453,7 +478,8 @@ class CBO(CBOAcquisitionPath):
     monitor records ``constraint_values`` and ``feasible`` per trial.
     ``hyper_samples`` (a positive int or a callable sampler, as for ``CBOAcquisitionPath``): ``intervene()`` scores every set
     with the EI marginalised over hyper-parameter samples of its model; the closing ``optimize()`` of the
-    chosen set's model stays, as in the reference.
+    chosen set's model stays, as in the reference.  ``hyper_sampler="device"`` draws them by the one-launch HMC (DESIGN.md
+    §4s), as for ``CBOAcquisitionPath``.
     ``batch_size`` (an int B in 1..64) with ``update_incumbent``: ``intervene()`` runs the B interventions of a greedy batch on
     the chosen set side by side: the monitor evaluates the B rows, appends them in order and records
     ``chosen`` as ``(set, x (B, d))``; the trial's cost is the sum of the B interventions' costs.  ``None``: the reference's
@@ -467,7 +493,8 @@ class CBO(CBOAcquisitionPath):
                  num_interventions=10, initial_num_obs_samples=100, causal_prior=False, num_trials=40, task="min",
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
-                 constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False):
+                 constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False,
+                 hyper_sampler="host"):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType
         from .graphs import _columns
@@ -510,6 +537,7 @@ class CBO(CBOAcquisitionPath):
             raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
         path_constraints = checked_path_constraints(path_constraints, sets_acquisition(acquisition, acquisition_param))
         checked_path_hyper_samples(hyper_samples, sets_acquisition(acquisition, acquisition_param), path_constraints)
+        checked_hyper_sampler(hyper_sampler, hyper_samples)
         checked_batch_size(batch_size, sets_acquisition(acquisition, acquisition_param), path_constraints, hyper_samples)
         checked_refine(refine, sets_acquisition(acquisition, acquisition_param), path_constraints, hyper_samples, batch_size,
                        False, [self.graph.bounds(s) for s in exploration], len(exploration))
@@ -528,7 +556,7 @@ class CBO(CBOAcquisitionPath):
                          [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None,
                          acquisition=acquisition, acquisition_param=acquisition_param, constraints=path_constraints,
                          constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
-                         update_incumbent=update_incumbent, refine=refine)
+                         update_incumbent=update_incumbent, refine=refine, hyper_sampler=hyper_sampler)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions

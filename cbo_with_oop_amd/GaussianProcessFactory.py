@@ -550,15 +550,22 @@ class HipGaussianProcess:
         return _optimizer_finish(self, theta0, x_opt, f_opt, info, transform)
 
     def generate_hyperparameters_samples(self, n_samples=20, n_burnin=100, subsample_interval=10, step_size=1e-1,
-                                         leapfrog_steps=20):
+                                         leapfrog_steps=20, sampler="host"):
         """emukit ``GPyModelWrapper.generate_hyperparameters_samples``: ``optimize()``, a multiplicative 1 % perturbation of
         the parameters (``theta * (1 + 0.01 * np.random.randn(P))``, numpy's global generator), GPy's HMC over the
         Logexp-transformed parameters (``integrated_hyper.hmc_sample`` on this model's ``_objective``) for
         ``n_burnin + n_samples * subsample_interval`` samples, and ``samples[n_burnin::subsample_interval]``: an
         (n_samples, P) array of (variance, lengthscale(s), noise variance) rows -- without the noise column for a model whose
         noise is fixed.  The model is LEFT AT THE CHAIN'S LAST STATE, unfitted (``stale``): the next use refits it there.
+        ``sampler="device"``: the same draws from the generator, the chain inside one device launch
+        (``generate_hyperparameters_samples_together([self], ...)``); ``"host"`` is the chain described above.
         emukit and GPy are not installed here: restated from memory, parity unpinned."""
         from .utils_functions.integrated_hyper import hmc_sample
+        if sampler not in ("host", "device"):
+            raise ValueError(f"sampler must be 'host' or 'device', not {sampler!r}")
+        if sampler == "device":
+            return generate_hyperparameters_samples_together([self], n_samples, n_burnin, subsample_interval, step_size,
+                                                             leapfrog_steps)[0]
         self.optimize()
         theta0, _ = _optimizer_start(self, "logexp")
         theta0 = theta0 * (1.0 + 0.01 * np.random.randn(theta0.size))
@@ -729,6 +736,81 @@ def optimize_together(models, max_iters=1000, transform="logexp"):
     finals = evaluate(list(range(len(models))), [x for x, _, _ in runs])
     return [_optimizer_finish(m, theta0, x_opt, f_final[0], info, transform)
             for m, (theta0, _), (x_opt, _, info), f_final in zip(models, starts, runs, finals)]
+
+
+def hmc_chains_device(models, theta0s, draws, hmc_iters, stepsize):
+    """One ``cbo_gp_hmc_sets`` call: model k's chain from ``theta0s[k]`` with the handed-in ``draws[k]`` = (momenta,
+    uniforms).  Returns per model dict(status, rows, accept, theta, lml, grad): rows (num_samples, P), the accept flags, and
+    the chain's last state -- everything but ``status`` is meaningless unless it is ``_lib.HMC_OK``.  The models are only
+    read."""
+    k = len(models)
+    lib = _lib.load()
+    handles = (ctypes.c_void_p * k)(*[m._handle for m in models])
+    chains = (_lib.CboHmcChain * k)()
+    status = np.full(k, -1, dtype=np.int32)
+    out = []
+    for j, (m, theta0, (momenta, uniforms)) in enumerate(zip(models, theta0s, draws)):
+        theta0 = np.ascontiguousarray(theta0, dtype=np.float64).reshape(-1)
+        momenta = np.ascontiguousarray(momenta, dtype=np.float64)
+        uniforms = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
+        num, size = uniforms.size, theta0.size
+        if momenta.shape != (num, size):
+            raise ValueError(f"momenta of model {j} must be ({num}, {size}), not {momenta.shape}")
+        o = dict(status=-1, rows=np.zeros((num, size)), accept=np.zeros(num, dtype=np.int32), theta=np.zeros(size),
+                 lml=np.zeros(1), grad=np.zeros(size), _keep=(theta0, momenta, uniforms))
+        ch = chains[j]
+        ch.n_params, ch.sample_noise, ch.num_samples, ch.hmc_iters = size, 0 if m.fix_noise else 1, num, int(hmc_iters)
+        ch.stepsize = float(stepsize)
+        ch.theta0, ch.momenta, ch.uniforms = _lib.dptr(theta0), _lib.dptr(momenta), _lib.dptr(uniforms)
+        ch.rows_out, ch.accept_out = _lib.dptr(o["rows"]), o["accept"].ctypes.data_as(_lib.c_int_p)
+        ch.final_theta, ch.final_lml, ch.final_grad = _lib.dptr(o["theta"]), _lib.dptr(o["lml"]), _lib.dptr(o["grad"])
+        out.append(o)
+    _lib.check(lib.cbo_gp_hmc_sets(k, handles, chains, status.ctypes.data_as(_lib.c_int_p)))
+    for o, st in zip(out, status):
+        o["status"] = int(st)
+        o["lml"] = float(o["lml"][0])
+        o["accept"] = o["accept"].astype(bool)
+        del o["_keep"]
+    return out
+
+
+def generate_hyperparameters_samples_together(models, n_samples=20, n_burnin=100, subsample_interval=10, step_size=1e-1,
+                                              leapfrog_steps=20, host_fallback=True):
+    """``[m.generate_hyperparameters_samples(...) for m in models]`` with every model's HMC chain inside ONE device launch
+    (``cbo_gp_hmc_sets``): ``optimize_together(models)``; then per model, in order, the 1 % perturbation
+    (``randn(P)``) and the chain's draws (``hmc_draws``) -- the generator is consumed exactly as by the per-model sequence,
+    ``optimize`` draws nothing --; then the one call.  A model the call declined (more than 128 observations, fp32), or
+    whose chain met a Ky that is not positive definite as assembled, is repeated on the host by ``hmc_sample_from_draws``
+    on its ``_objective`` with the same draws (``host_fallback=False``: RuntimeError instead).  Returns per model
+    ``samples[n_burnin::subsample_interval]``; every model is left at its chain's last state, unfitted (``stale``)."""
+    from .utils_functions.integrated_hyper import hmc_draws, hmc_sample_from_draws
+    models = list(models)
+    if not models:
+        return []
+    optimize_together(models)
+    num = int(n_burnin) + int(n_samples) * int(subsample_interval)
+    theta0s, draws = [], []
+    for m in models:
+        theta0, _ = _optimizer_start(m, "logexp")
+        theta0s.append(theta0 * (1.0 + 0.01 * np.random.randn(theta0.size)))
+        draws.append(hmc_draws(theta0.size, num))
+    answers = hmc_chains_device(models, theta0s, draws, int(leapfrog_steps), float(step_size))
+    if not host_fallback:
+        for j, a in enumerate(answers):
+            if a["status"] != _lib.HMC_OK:
+                why = "was declined" if a["status"] == _lib.HMC_DECLINED else \
+                    "met a Ky that is not positive definite as assembled"
+                raise RuntimeError(f"the device chain of model {j} {why} and host_fallback is off")
+    results = []
+    for m, theta0, (momenta, uniforms), a in zip(models, theta0s, draws, answers):
+        if a["status"] == _lib.HMC_OK:
+            samples = a["rows"]
+        else:
+            samples, _, _ = hmc_sample_from_draws(lambda x, m=m: m._objective(x, "logexp"), theta0, momenta, uniforms,
+                                                  int(leapfrog_steps), float(step_size))
+        _objective_set(m, samples[-1], fit=False)            # (the chain's last state: the last row, accepted or not)
+        results.append(samples[int(n_burnin)::int(subsample_interval)])
+    return results
 
 
 class GaussianProcessFactory:

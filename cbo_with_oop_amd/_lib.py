@@ -41,6 +41,10 @@ REFINE_KIND_CODE = dict(ACQ_KIND_CODE, EI=0)                  # cbo_acq_refine_s
 REFINE_MAX_STARTS = 64       # CBO_REFINE_MAX_STARTS
 REFINE_ROUNDS_LIMIT = 1000   # CBO_REFINE_ROUNDS_LIMIT
 REFINE_PGTOL, REFINE_FTOL, REFINE_STEP, REFINE_MAX_ROUNDS, REFINE_NAN_START, REFINE_DECLINED = range(6)   # CBO_REFINE_*
+HMC_MAX_PARAMS = MAX_DIM + 2   # CBO_HMC_MAX_PARAMS
+HMC_MAX_SAMPLES = 4096         # CBO_HMC_MAX_SAMPLES
+HMC_MAX_EVALS = 262144         # CBO_HMC_MAX_EVALS: the cap on num_samples * hmc_iters
+HMC_OK, HMC_NOT_PD, HMC_DECLINED = range(3)   # CBO_HMC_*
 REFINE_STATUS_NAME = {REFINE_PGTOL: "pgtol", REFINE_FTOL: "ftol", REFINE_STEP: "step", REFINE_MAX_ROUNDS: "max_rounds",
                       REFINE_NAN_START: "nan_start", REFINE_DECLINED: "declined"}
 
@@ -72,6 +76,14 @@ class CboRefineSet(ctypes.Structure):
     """struct cbo_refine_set of include/cbo_hip.h."""
     _fields_ = [("k", ctypes.c_int), ("starts", c_double_p), ("lo", c_double_p), ("hi", c_double_p),
                 ("cost_fix", c_double_p), ("cost_variable", c_int_p)]
+
+
+class CboHmcChain(ctypes.Structure):
+    """struct cbo_hmc_chain of include/cbo_hip.h."""
+    _fields_ = [("n_params", ctypes.c_int), ("sample_noise", ctypes.c_int), ("num_samples", ctypes.c_int),
+                ("hmc_iters", ctypes.c_int), ("stepsize", ctypes.c_double), ("theta0", c_double_p), ("momenta", c_double_p),
+                ("uniforms", c_double_p), ("rows_out", c_double_p), ("accept_out", c_int_p), ("final_theta", c_double_p),
+                ("final_lml", c_double_p), ("final_grad", c_double_p)]
 
 
 class CboHipError(RuntimeError):
@@ -179,6 +191,7 @@ SIGNATURES = {
     "cbo_acq_refine_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), ctypes.c_int, c_double_p,
                                            ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                            c_int_p, c_int_p]),
+    "cbo_gp_hmc_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboHmcChain), c_int_p]),
     "cbo_gp_mes_gumbel_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_double_p]),
     "cbo_comm_gather_i64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_int64_p]),

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cbo_internal.h"
+#include "lml_outputs.h"
 #include "schedule_tuner.h"
 
 using namespace cbo;
@@ -174,6 +175,11 @@ struct cbo_ctx {
     PinnedBuf<double> refine_starts, refine_x, refine_grad, refine_val;
     PinnedBuf<int> refine_rounds, refine_status;
     GrowBuf<int> refine_info;
+    // cbo_gp_hmc_sets: the chains' descriptors and draws as the kernel reads them, rows, accept flags, final states and
+    // status words as it writes them (all pinned)
+    PinnedBuf<cbo_small_hmc> hmc_host;
+    PinnedBuf<double> hmc_draws, hmc_rows, hmc_final;
+    PinnedBuf<int> hmc_accept, hmc_status;
     GrowBuf<double> append_part;                       // block append: slice sums of the pass over V [slices][kp][m_pad]
     GrowBuf<BatchState> batch_state;
     PinnedBuf<double> batch_h_vals; PinnedBuf<int64_t> batch_h_idxs;
@@ -3809,16 +3815,8 @@ extern "C" int cbo_gp_log_marginal(cbo_gp *g, double *lml_out)
 static void lml_outputs(const cbo_gp *g, const double *grad_sums, double zz, double logdet, double aa, double tr_w,
                         double *lml_out, double *dvariance_out, double *dlengthscale_out, double *dnoise_out)
 {
-    *dvariance_out = 0.5 * grad_sums[0] / g->h.variance;
-    if (g->h.ard) {
-        for (int k = 0; k < g->d; ++k) dlengthscale_out[k] = 0.5 * grad_sums[1 + k] / g->ls[(size_t)k];
-    } else {
-        double sum = 0.0;
-        for (int k = 0; k < g->d; ++k) sum += grad_sums[1 + k];
-        dlengthscale_out[0] = 0.5 * sum / g->h.lengthscale;
-    }
-    *dnoise_out = 0.5 * (aa - tr_w);
-    if (lml_out) *lml_out = 0.5 * (-(double)g->n * 1.8378770664093453 - 2.0 * logdet - zz);
+    lml_outputs_of(g->h.variance, g->h.ard != 0, g->h.ard ? g->ls.data() : &g->h.lengthscale, g->d, (long long)g->n, grad_sums, zz,
+                   logdet, aa, tr_w, lml_out, dvariance_out, dlengthscale_out, dnoise_out);
 }
 
 // the one-launch form of small_lml_gradients applies to this model
@@ -3932,6 +3930,118 @@ extern "C" int cbo_gp_lml_gradients_batch(int n_models, cbo_gp *const *gps, doub
             status[i] = rc;
             return rc == CBO_ERR_HIP ? rc : CBO_OK;
         });
+}
+
+// ---- every model's HMC chain over its hyper-parameters (kernels_hmc.hip) ------------------------------------
+// One launch for every model small_lml_gradients would take; the others are declined here, their status alone written.  The
+// models are only read.  Of the routing policy (§4r) this call uses partition_small, ensure_small_buffers and
+// fill_small_model: like cbo_acq_refine_sets it has no general path inside the call (a chain the launch cannot finish is
+// the caller's to repeat), and its outputs come back behind one stream synchronisation, not through polled records.
+extern "C" int cbo_gp_hmc_sets(int n_models, cbo_gp *const *gps, const cbo_hmc_chain *chains, int *status_out)
+{
+    if (n_models <= 0) return fail(CBO_ERR_INVALID, "n_models must be positive");
+    if (!gps || !chains || !status_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    int rc = check_model_handles(n_models, gps);
+    if (rc != CBO_OK) return rc;
+    for (int i = 0; i < n_models; ++i) {
+        const std::string where = " (model " + std::to_string(i) + ")";
+        const cbo_hmc_chain &ch = chains[i];
+        const cbo_gp *g = gps[i];
+        if (!ch.theta0 || !ch.momenta || !ch.uniforms || !ch.rows_out || !ch.accept_out || !ch.final_theta || !ch.final_lml ||
+            !ch.final_grad)
+            return fail(CBO_ERR_INVALID, "NULL argument: theta0, the draws and the outputs must be given" + where);
+        if (ch.num_samples < 1 || ch.num_samples > CBO_HMC_MAX_SAMPLES)
+            return fail(CBO_ERR_INVALID, "num_samples must be in 1.." + std::to_string(CBO_HMC_MAX_SAMPLES) + where);
+        if (ch.hmc_iters < 0) return fail(CBO_ERR_INVALID, "hmc_iters must not be negative" + where);
+        if ((int64_t)ch.num_samples * ch.hmc_iters > CBO_HMC_MAX_EVALS)
+            return fail(CBO_ERR_INVALID, "num_samples * hmc_iters must not exceed " + std::to_string(CBO_HMC_MAX_EVALS) + where);
+        if (!std::isfinite(ch.stepsize) || !(ch.stepsize > 0.0))
+            return fail(CBO_ERR_INVALID, "the stepsize must be finite and positive" + where);
+        if (ch.sample_noise != 0 && ch.sample_noise != 1) return fail(CBO_ERR_INVALID, "sample_noise must be 0 or 1" + where);
+        const int n_ls = g->h.ard ? g->d : 1;
+        if (ch.n_params != 1 + n_ls + ch.sample_noise)
+            return fail(CBO_ERR_INVALID, "n_params must be " + std::to_string(1 + n_ls + ch.sample_noise) +
+                                             " (variance, the lengthscale(s), the noise variance when it is sampled)" + where);
+        for (int k = 0; k < ch.n_params; ++k)
+            if (!std::isfinite(ch.theta0[k]) || !(ch.theta0[k] > 0.0))
+                return fail(CBO_ERR_INVALID, "theta0 must be finite and positive" + where);
+        for (int64_t e = 0; e < (int64_t)ch.num_samples * ch.n_params; ++e)
+            if (!std::isfinite(ch.momenta[e])) return fail(CBO_ERR_INVALID, "the momenta must be finite" + where);
+        for (int e = 0; e < ch.num_samples; ++e)
+            if (!std::isfinite(ch.uniforms[e])) return fail(CBO_ERR_INVALID, "the uniforms must be finite" + where);
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int> small;
+    partition_small(n_models, [&](int i) { return small_lml_eligible(gps[i]); }, [](int) { return (int64_t)1; }, small);
+    const int ns = (int)small.size();
+    for (int i = 0, j = 0; i < n_models; ++i) {
+        if (j < ns && small[(size_t)j] == i) ++j;
+        else status_out[i] = CBO_HMC_DECLINED;
+    }
+    if (small.empty()) return CBO_OK;
+    // where each chain's draws, rows and flags begin in the call's arrays
+    int64_t draws = 0, rows = 0, flags = 0;
+    for (int j = 0; j < ns; ++j) {
+        const cbo_hmc_chain &ch = chains[small[(size_t)j]];
+        draws += (int64_t)ch.num_samples * (ch.n_params + 1);
+        rows += (int64_t)ch.num_samples * ch.n_params;
+        flags += ch.num_samples;
+    }
+    // a scratch slot per model: factor + L^-1
+    const size_t stride = small_lml_scratch_doubles(), per_block = small_sets_scratch_doubles(1, 1);
+    const size_t cap = ns < 32 ? (size_t)32 : (size_t)ns;
+    constexpr int kFinal = 2 * CBO_HMC_MAX_PARAMS + 1;
+    rc = ensure_small_buffers(c, ns, (int)((stride + per_block - 1) / per_block));
+    if (rc == CBO_OK && (size_t)ns * stride > c->small_scratch.cap)
+        rc = fail(CBO_ERR_INVALID, "HMC chains: scratch smaller than expected");
+    if (rc == CBO_OK) rc = grow(c, c->hmc_host, cap);
+    if (rc == CBO_OK) rc = grow(c, c->hmc_draws, (size_t)draws);
+    if (rc == CBO_OK) rc = grow(c, c->hmc_rows, (size_t)rows);
+    if (rc == CBO_OK) rc = grow(c, c->hmc_accept, (size_t)flags);
+    if (rc == CBO_OK) rc = grow(c, c->hmc_final, cap * (size_t)kFinal);
+    if (rc == CBO_OK) rc = grow(c, c->hmc_status, cap);
+    if (rc != CBO_OK) return rc;
+    draws = rows = flags = 0;
+    for (int j = 0; j < ns; ++j) {
+        const int i = small[(size_t)j];
+        const cbo_hmc_chain &ch = chains[i];
+        c->sets_host[j] = cbo_small_set{};
+        fill_small_model(c->sets_host[j], gps[i]);
+        cbo_small_hmc &hm = c->hmc_host[j];
+        std::memset(&hm, 0, sizeof(hm));
+        std::memcpy(hm.theta0, ch.theta0, sizeof(double) * (size_t)ch.n_params);
+        hm.stepsize = ch.stepsize;
+        hm.draw_off = draws; hm.row_off = rows; hm.acc_off = flags;
+        hm.n_params = ch.n_params; hm.n_ls = gps[i]->h.ard ? gps[i]->d : 1; hm.sample_noise = ch.sample_noise;
+        hm.num_samples = ch.num_samples; hm.hmc_iters = ch.hmc_iters;
+        const size_t np = (size_t)ch.num_samples * (size_t)ch.n_params;
+        std::memcpy(c->hmc_draws.p + draws, ch.momenta, sizeof(double) * np);
+        std::memcpy(c->hmc_draws.p + draws + np, ch.uniforms, sizeof(double) * (size_t)ch.num_samples);
+        c->hmc_status[j] = CBO_HMC_DECLINED;                   // (a launch that never ran answers nothing)
+        draws += (int64_t)np + ch.num_samples; rows += (int64_t)np; flags += ch.num_samples;
+    }
+    launch_hmc_sets(c->stream, c->sets_host, c->hmc_host, c->hmc_draws, ns, c->small_scratch, (int64_t)stride, c->small_info,
+                    c->hmc_rows, c->hmc_accept, c->hmc_final, c->hmc_status);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int j = 0; j < ns; ++j) {
+        const int i = small[(size_t)j];
+        const cbo_hmc_chain &ch = chains[i];
+        const cbo_small_hmc &hm = c->hmc_host[j];
+        if (c->hmc_status[j] == CBO_HMC_DECLINED) return fail(CBO_ERR_HIP, "HMC kernel: no status for a model it was given");
+        status_out[i] = c->hmc_status[j];
+        if (status_out[i] != CBO_HMC_OK) continue;
+        const size_t np = (size_t)ch.num_samples * (size_t)ch.n_params;
+        std::memcpy(ch.rows_out, c->hmc_rows.p + hm.row_off, sizeof(double) * np);
+        std::memcpy(ch.accept_out, c->hmc_accept.p + hm.acc_off, sizeof(int) * (size_t)ch.num_samples);
+        const double *fin = c->hmc_final.p + (size_t)j * kFinal;
+        std::memcpy(ch.final_theta, fin, sizeof(double) * (size_t)ch.n_params);
+        *ch.final_lml = fin[CBO_HMC_MAX_PARAMS];
+        std::memcpy(ch.final_grad, fin + CBO_HMC_MAX_PARAMS + 1, sizeof(double) * (size_t)ch.n_params);
+    }
+    return CBO_OK;
 }
 
 static int general_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out, double *dlengthscale_out,

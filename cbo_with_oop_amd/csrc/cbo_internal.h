@@ -383,6 +383,23 @@ int small_refine_starts_per_block(int d);              // 4 floor(16 / (1 + d)):
 void launch_small_sets_refine(hipStream_t s, int kind, const cbo_small_set *sets, const cbo_small_refine *refs,
                               const double *starts, int n_sets, int blocks_per_set, double *scratch, int *info, int max_rounds,
                               double *x_out, double *val_out, double *grad_out, int *rounds_out, int *status_out);
+// ---- every model's HMC chain over its hyper-parameters in one launch (kernels_hmc.hip) -----------------------
+// What a model's chain needs beside the model's descriptor (pinned, device-mapped: read by the kernel directly): the start,
+// the chain's shape, and where its draws (n_params x num_samples momenta, then num_samples uniforms) and its rows / accept
+// flags begin in the call's arrays.  n_params = 1 + n_ls + sample_noise.
+struct cbo_small_hmc {
+    double theta0[CBO_HMC_MAX_PARAMS];
+    double stepsize;
+    int64_t draw_off, row_off, acc_off;
+    int n_params, n_ls, sample_noise, num_samples, hmc_iters, pad_;
+};
+// sets / chains / draws and the four outputs may be pinned host memory; scratch: `stride` >= small_lml_scratch_doubles()
+// doubles per model; info: n_models ints, zero on entry and zero again afterwards.  final_out: per model theta
+// [CBO_HMC_MAX_PARAMS], lml, dlml / dtheta [CBO_HMC_MAX_PARAMS]; status_out: CBO_HMC_OK or CBO_HMC_NOT_PD per model (a
+// chain that met a non-positive pivot wrote rows up to there and no final state).
+void launch_hmc_sets(hipStream_t s, const cbo_small_set *sets, const cbo_small_hmc *chains, const double *draws, int n_models,
+                     double *scratch, int64_t stride, int *info, double *rows_out, int *accept_out, double *final_out,
+                     int *status_out);
 // the same launch with the batch epilogue (kernels_sets_batch.hip, small_sets_batch_kernel): batch_size >= 2
 // Kriging-believer picks per set.  Sets of at most kSmallBatchMaxCands candidates: the set's V = L^-1 K* stays in global
 // scratch (1 MiB per set at the cap) and the call's widest set has at most 16 candidate blocks.  batch_scratch:

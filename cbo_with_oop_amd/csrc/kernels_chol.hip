@@ -26,7 +26,7 @@
 #include <cstring>
 #include <vector>
 
-#include "cbo_small_device.h"
+#include "cbo_small_lml_device.h"
 
 namespace cbo {
 
@@ -301,109 +301,17 @@ __device__ __forceinline__ void small_lml_body(SmallShared &sh, double *alpha_s,
                                                cbo_small_lml_result *__restrict__ out, int seq)
 {
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lc = lane & 15, kq = lane >> 4;
-    const int tiles = (st.n + 15) / 16, rows = 16 * tiles;
+    const int tiles = (st.n + 15) / 16;
     double *Us = scratch, *invs = scratch + 128 * kSmallLd, *Vg = scratch + kSmallScratch;
     double iv[8][4], zr[8][4];
     small_model_factor(sh, st, tiles, Us, invs, info, iv, zr);
     if (tid < 128) alpha_s[tid] = 0.0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-
-    // ---- V = L^-1: column tile ct of the identity through the tile solve; alpha and diag(Ky^-1) fall out
-    double trw = 0.0;
-    for (int ct = wave; ct < tiles; ct += 4) {
-        d4 acc[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][r] = (t == ct && kq + 4 * r == lc) ? 1.0 : 0.0;
-        double qacc = 0.0, macc = 0.0;
-        double *Vc = Vg + 16 * ct + lc;
-        panel_solve_tiles(&sh.blk.S[kq][lc], acc, iv, tiles, [&](int s2, const d4 &x) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                Vc[(int64_t)(16 * s2 + kq + 4 * r) * kSmallLd] = x[r];
-                qacc = fma(x[r], x[r], qacc);
-                macc = fma(x[r], zr[s2][r], macc);
-            }
-        });
-        qacc += __shfl_xor(qacc, 16);
-        qacc += __shfl_xor(qacc, 32);
-        macc += __shfl_xor(macc, 16);
-        macc += __shfl_xor(macc, 32);
-        const int col = 16 * ct + lc;
-        if (kq == 0 && col < st.n) {
-            alpha_s[col] = macc;
-            trw += qacc;
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // ---- gradient sums over the upper tile pairs, one pair per wave at a time
-    const double inv_l2 = st.ard ? 1.0 : 1.0 / (st.lengthscale * st.lengthscale);
-    double sum[1 + D];
-#pragma unroll
-    for (int k = 0; k <= D; ++k) sum[k] = 0.0;
-    int pair = 0;
-    for (int ti = 0; ti < tiles; ++ti)
-        for (int tj = ti; tj < tiles; ++tj, ++pair) {
-            if ((pair & 3) != wave) continue;                       // uniform per wave
-            d4 w = {0.0, 0.0, 0.0, 0.0}, w2 = {0.0, 0.0, 0.0, 0.0};
-            const double *Va = Vg + 16 * ti + lc, *Vb = Vg + 16 * tj + lc;
-            // V is lower triangular: rows above tile tj contribute nothing to column tile tj
-            for (int k0 = 16 * tj; k0 < rows; k0 += 8) {
-                w = MFMA_F64(Va[(int64_t)(k0 + kq) * kSmallLd], Vb[(int64_t)(k0 + kq) * kSmallLd], w);
-                w2 = MFMA_F64(Va[(int64_t)(k0 + 4 + kq) * kSmallLd], Vb[(int64_t)(k0 + 4 + kq) * kSmallLd], w2);
-            }
-            w += w2;
-            const int gj = 16 * tj + lc;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gi = 16 * ti + kq + 4 * r;
-                if (gi >= st.n || gj >= st.n || gj < gi) continue;
-                double r2 = 0.0, d2k[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const double df = sh.xs[k][gi] - sh.xs[k][gj];
-                    d2k[k] = df * df * inv_l2;
-                    r2 += d2k[k];
-                }
-                const double kv = st.variance * exp_nonpositive(-0.5 * r2);
-                const double m = (gi == gj ? 1.0 : 2.0) * (alpha_s[gi] * alpha_s[gj] - w[r]);
-                const double mk = m * kv;
-                sum[0] += mk + m * (sh.sv[gi] * sh.sv[gj]);
-#pragma unroll
-                for (int k = 0; k < D; ++k) sum[1 + k] = fma(mk, d2k[k], sum[1 + k]);
-            }
-        }
-    // ---- z^T z, sum log diag(U), alpha^T alpha, tr(Ky^-1); everything reduced over the workgroup
-    double terms[kSmallLmlTerms];
-#pragma unroll
-    for (int k = 0; k < kSmallLmlTerms; ++k) terms[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k <= D; ++k) terms[k] = sum[k];
-    if (tid < st.n) {
-        const double zi = Us[(int64_t)tid * kSmallLd + 128];
-        terms[1 + CBO_MAX_DIM + 0] = zi * zi;
-        terms[1 + CBO_MAX_DIM + 1] = log(sh.blk.S[tid][tid]);
-        terms[1 + CBO_MAX_DIM + 2] = alpha_s[tid] * alpha_s[tid];
-    }
-    terms[1 + CBO_MAX_DIM + 3] = trw;
-#pragma unroll
-    for (int k = 0; k < kSmallLmlTerms; ++k) {
-        double v = terms[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
+    small_lml_after_factor<D>(sh, alpha_s, red, st, Us, Vg, iv, zr);
     if (tid == 0) {
 #pragma unroll
-        for (int k = 0; k < kSmallLmlTerms; ++k) out->terms[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+        for (int k = 0; k < kSmallLmlTerms; ++k) out->terms[k] = small_lml_term(red, k);
         out->info = atomicAdd(info, 0);
         __threadfence_system();
         *reinterpret_cast<volatile int *>(&out->seq) = seq;

@@ -1,0 +1,168 @@
+// Every model's HMC chain over its hyper-parameters in one launch for gfx950: hmc_sets_kernel, the sampler
+// behind emukit's GPyModelWrapper.generate_hyperparameters_samples for every exploration set of a trial.  One workgroup of
+// 256 threads runs one model's whole chain; no workgroup waits for another.  Per position of the chain:
+//   thread 0 has left theta(x) in LDS (the chain's state, hmc_chain.h), so every lane works from the same doubles;
+//   the model's points are prepared from its RAW coordinates with theta's lengthscales, K(X,X) + (noise + 1e-8) I is
+//   assembled and factored inside LDS (hyper_sample_set / hyper_model_points / hyper_factor, as hyper_avg_kernel does for a
+//   hyper-parameter sample);
+//   the stages behind the factor of small_lml_kernel follow (small_lml_after_factor: L^-1 through the tile solve, alpha,
+//   diag(Ky^-1), the gradient sums over the upper tile pairs, the workgroup reduction), the sums staying in LDS;
+//   thread 0 turns them into the likelihood and its gradients with the host's own arithmetic (lml_outputs.h) and advances
+//   the chain (hmc_feed): two multiply-adds per parameter between two evaluations.
+// The likelihood at a position is therefore what cbo_gp_lml_gradients answers for the model at those hyper-parameters.
+// A position whose Ky is not positive definite as assembled ends the chain with CBO_HMC_NOT_PD (jitchol's ladder lives on
+// the host: the caller repeats the chain there).  Nothing resident is written but the workgroup's scratch slot.
+// Every loop is bounded: the positions by 1 + num_samples * hmc_iters, the chain's own loops by num_samples and P.
+#include <cstring>
+
+#include "cbo_small_lml_device.h"
+#include "hmc_chain.h"
+#include "lml_outputs.h"
+
+namespace cbo {
+
+static_assert(sizeof(SmallShared) + 4 * kSmallLmlTerms * sizeof(double) + sizeof(HmcChain) + kHmcMaxParams * sizeof(double)
+                  <= 163840,
+              "the workgroup's static LDS (the reduction's partial sums, the chain's state, the published theta) beside "
+              "SmallShared: one CU");
+static_assert(kHmcMaxParams == CBO_MAX_DIM + 2, "variance, one lengthscale per dimension, noise variance");
+
+// the factor of the scratch slot back into LDS (rows of the factored tiles; the solve reads nothing else), its tile
+// inverses and z into registers: small_model_factor's closing steps.  Ends with loads in flight: the caller waits.
+__device__ __forceinline__ void hmc_factor_to_lds(SmallShared &sh, const double *Us, const double *invs, int tiles,
+                                                  double (&iv)[8][4], double (&zr)[8][4])
+{
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lc = lane & 15, kq = lane >> 4;
+    const unsigned s0 = lds_byte_address(&sh.blk.S[0][0]);
+    const int rows = 16 * tiles;
+    for (int p = wave; p < rows; p += 4)
+        glds16(Us + (int64_t)p * kSmallLd + lane * 2, __builtin_amdgcn_readfirstlane(s0 + 8u * (unsigned)(p * kDiagLd)));
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            iv[s][kk] = (s < tiles) ? invs[s * 256 + (4 * kk + kq) * 16 + lc] : 0.0;
+            zr[s][kk] = (s < tiles) ? Us[(int64_t)(16 * s + kq + 4 * kk) * kSmallLd + 128] : 0.0;
+        }
+}
+
+template <bool BYVAL>
+__global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
+                                                       const cbo_small_hmc *__restrict__ chains,
+                                                       const double *__restrict__ draws, double *scratch, int64_t stride,
+                                                       int *__restrict__ info, double *__restrict__ rows_out,
+                                                       int *__restrict__ accept_out, double *__restrict__ final_out,
+                                                       int *__restrict__ status_out)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    SmallShared &sh = *reinterpret_cast<SmallShared *>(smem_raw);
+    __shared__ double red[4][kSmallLmlTerms];
+    __shared__ HmcChain chain;
+    __shared__ double theta_row[kHmcMaxParams];
+    const int b = blockIdx.x;
+    const cbo_small_set st = BYVAL ? byval.s[b] : sets[b];
+    const cbo_small_hmc &hm = chains[b];
+    const int tid = threadIdx.x;
+    const int tiles = (st.n + 15) / 16;
+    const int n_ls = hm.n_ls, P = hm.n_params, sample_noise = hm.sample_noise;
+    const int num_samples = hm.num_samples, hmc_iters = hm.hmc_iters;
+    double *Us = scratch + (int64_t)b * stride, *invs = Us + 128 * kSmallLd, *Vg = Us + kSmallScratch;
+    double *alpha_s = sh.sq;                                      // (|x|^2 is the assembly's alone: free behind the factor)
+    const double *momenta = draws + hm.draw_off, *uniforms = momenta + (int64_t)num_samples * P;
+    double *rows = rows_out + hm.row_off;
+    int *accepts = accept_out + hm.acc_off;
+    const double rhs = hyper_rhs(st);
+
+    // theta(x) of the chain's position for every lane: a model whose noise is fixed keeps its own in the row's last place
+    auto publish = [&]() {
+        for (int k = 0; k < kHmcMaxParams; ++k) theta_row[k] = (k < P) ? chain.th[k] : 0.0;
+        if (!sample_noise) theta_row[1 + n_ls] = st.noise_var;
+    };
+    if (tid == 0) {
+        hmc_begin(chain, P, hm.theta0, num_samples, hmc_iters, hm.stepsize);
+        publish();
+    }
+    __syncthreads();
+
+    const int64_t positions = 1 + (int64_t)num_samples * hmc_iters;
+    for (int64_t pos = 0; pos < positions; ++pos) {
+        // ---- theta as a hyper-parameter sample's row (variance, lengthscale x n_ls, noise variance): thread 0 left it in LDS
+        const double *row = theta_row;
+        const cbo_small_set sth = hyper_sample_set(st, row, n_ls);
+        hyper_model_points(sh, st, st.ard ? row + 1 : nullptr);
+        __syncthreads();
+        hyper_factor(sh, sth, tiles, rhs, Us, invs, &info[b]);
+        // not positive definite as assembled: jitchol's business, the chain stops here
+        if (__hip_atomic_load(&info[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+            __syncthreads();                                      // (everybody has read the word)
+            if (tid == 0) {
+                status_out[b] = CBO_HMC_NOT_PD;
+                __hip_atomic_store(&info[b], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            return;
+        }
+        double iv[8][4], zr[8][4];
+        hmc_factor_to_lds(sh, Us, invs, tiles, iv, zr);
+        if (tid < 128) alpha_s[tid] = 0.0;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        switch (st.d) {
+            case 1: small_lml_after_factor<1>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
+            case 2: small_lml_after_factor<2>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
+            case 3: small_lml_after_factor<3>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
+            case 4: small_lml_after_factor<4>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
+            case 5: small_lml_after_factor<5>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
+            case 6: small_lml_after_factor<6>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
+            case 7: small_lml_after_factor<7>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
+            default: small_lml_after_factor<8>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
+        }
+        // ---- the likelihood and its gradients by the host's arithmetic, one step of the chain
+        if (tid == 0) {
+            double t[kSmallLmlTerms];
+#pragma unroll
+            for (int k = 0; k < kSmallLmlTerms; ++k) t[k] = small_lml_term(red, k);
+            double lml, dl[kHmcMaxParams], dnoise;
+            lml_outputs_of(row[0], st.ard != 0, row + 1, st.d, st.n, t, t[1 + CBO_MAX_DIM], t[1 + CBO_MAX_DIM + 1],
+                           t[1 + CBO_MAX_DIM + 2], t[1 + CBO_MAX_DIM + 3], &lml, &dl[0], &dl[1], &dnoise);
+            if (sample_noise) dl[1 + n_ls] = dnoise;
+            hmc_feed(chain, lml, dl, momenta, uniforms, rows, accepts);
+            publish();
+        }
+        __syncthreads();
+        if (chain.done) break;                                    // (uniform: everybody reads the same word)
+    }
+
+    if (tid == 0) {
+        double *fin = final_out + (int64_t)b * (2 * kHmcMaxParams + 1);
+        for (int k = 0; k < P; ++k) {
+            fin[k] = chain.th[k];
+            fin[kHmcMaxParams + 1 + k] = chain.dl[k];
+        }
+        fin[kHmcMaxParams] = -chain.f;
+        status_out[b] = CBO_HMC_OK;
+    }
+}
+
+void launch_hmc_sets(hipStream_t s, const cbo_small_set *sets, const cbo_small_hmc *chains, const double *draws, int n_models,
+                     double *scratch, int64_t stride, int *info, double *rows_out, int *accept_out, double *final_out,
+                     int *status_out)
+{
+    static std::atomic<unsigned long long> opted[2] = {{0}, {0}};
+    const bool byval = n_models <= kSmallByValue;
+    small_lds_opt_in(byval ? reinterpret_cast<const void *>(hmc_sets_kernel<true>)
+                           : reinterpret_cast<const void *>(hmc_sets_kernel<false>), opted[byval]);
+    SmallSetArgs args{};
+    if (byval) {
+        std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_models);
+        hipLaunchKernelGGL(hmc_sets_kernel<true>, dim3((unsigned)n_models), dim3(256), sizeof(SmallShared), s, args, sets,
+                           chains, draws, scratch, stride, info, rows_out, accept_out, final_out, status_out);
+    } else {
+        hipLaunchKernelGGL(hmc_sets_kernel<false>, dim3((unsigned)n_models), dim3(256), sizeof(SmallShared), s, args, sets,
+                           chains, draws, scratch, stride, info, rows_out, accept_out, final_out, status_out);
+    }
+}
+
+}  // namespace cbo

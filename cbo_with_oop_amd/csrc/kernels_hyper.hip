@@ -16,99 +16,11 @@
 // per-sample terms come from cbo_acq_sweep itself.
 #include <cstring>
 
-#include "cbo_small_device.h"
+#include "cbo_small_lml_device.h"
 
 #pragma clang fp contract(off)
 
 namespace cbo {
-
-// One point from AoS raw coordinates: x[k] = raw[k] / ls[k] (ARD; ls null: unscaled), |x|^2 in prep_points_kernel's order
-__device__ __forceinline__ void hyper_point(const double *__restrict__ raw, int64_t i, int d, const double *ls, bool in,
-                                            double (&x)[CBO_MAX_DIM], double &sum)
-{
-#pragma unroll
-    for (int k = 0; k < CBO_MAX_DIM; ++k) x[k] = 0.0;
-    if (in) {
-#pragma unroll
-        for (int k = 0; k < CBO_MAX_DIM; ++k)
-            if (k < d) {
-                double v = raw[i * d + k];
-                if (ls) v = v / ls[k];
-                x[k] = v;
-            }
-    }
-    if (d == 8) {
-        double r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = __dmul_rn(x[k], x[k]);
-        sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                        __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-    } else {
-        sum = 0.0;
-#pragma unroll
-        for (int k = 0; k < CBO_MAX_DIM; ++k)
-            if (k < d) sum = __dadd_rn(sum, __dmul_rn(x[k], x[k]));
-    }
-}
-
-// The descriptor of sample h: the model's with the sample's variance, lengthscale and noise in the place of its own
-__device__ __forceinline__ cbo_small_set hyper_sample_set(const cbo_small_set &st, const double *__restrict__ row, int n_ls)
-{
-    cbo_small_set sh = st;
-    sh.variance = row[0];
-    sh.lengthscale = st.ard ? 1.0 : row[1];
-    sh.noise_var = row[1 + n_ls];
-    sh.diag_add = __dadd_rn(sh.noise_var, kGpyDiagJitter);             // Ky = K + (noise + 1e-8) I
-    return sh;
-}
-
-// The model's points of sample h into LDS (threads 0..127), as the resident copies of a model with that sample's
-// lengthscales hold them.  The caller synchronises.
-__device__ __forceinline__ void hyper_model_points(SmallShared &sh, const cbo_small_set &st, const double *ls)
-{
-    const int tid = threadIdx.x;
-    if (tid < 128) {
-        const bool in = tid < st.n;
-        double x[CBO_MAX_DIM], sum;
-        hyper_point(st.raw, tid, st.d, ls, in, x, sum);
-#pragma unroll
-        for (int k = 0; k < CBO_MAX_DIM; ++k)
-            if (k < st.d) sh.xs[k][tid] = x[k];
-        sh.sq[tid] = sum;
-        sh.sv[tid] = (in && st.sv) ? sqrt(st.pv[tid]) : 0.0;
-    }
-}
-
-// K(X,X) + diag and the rhs into the block, the factorisation of the `tiles` real tiles into the scratch slot (Us, invs):
-// small_model_factor's steps between its point loads and its read-back, on points that are already in LDS
-__device__ __forceinline__ void hyper_factor(SmallShared &sh, const cbo_small_set &st, int tiles, double rhs, double *Us,
-                                             double *invs, int *info_word)
-{
-    const int tid = threadIdx.x;
-    switch (st.d) {
-        case 1: small_assemble<1>(sh, st, tiles); break;
-        case 2: small_assemble<2>(sh, st, tiles); break;
-        case 3: small_assemble<3>(sh, st, tiles); break;
-        case 4: small_assemble<4>(sh, st, tiles); break;
-        case 5: small_assemble<5>(sh, st, tiles); break;
-        case 6: small_assemble<6>(sh, st, tiles); break;
-        case 7: small_assemble<7>(sh, st, tiles); break;
-        default: small_assemble<8>(sh, st, tiles); break;
-    }
-    const int rows = 16 * tiles;
-    for (int r = tid >> 4; r < rows; r += 16)
-        for (int c = rows + (tid & 15); c < kDiagLd; c += 16) {
-            if (c == 128 && r < st.n) continue;                                                // (the rhs: below)
-            sh.blk.S[r][c] = 0.0;
-        }
-    if (tid < st.n) sh.blk.S[tid][128] = rhs;                                                  // r = y - m(X)
-    __syncthreads();
-    diag128_factor_in_lds(sh.blk, Us, kSmallLd, 0, 128, invs, info_word, nullptr, tiles, nullptr,
-                          (st.n - 16 * (tiles - 1) + 3) / 4);
-    // (ends with a barrier.)  Every wave's stores of factor rows / inverses / z are complete before anyone re-reads them
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-}
 
 struct HyperSetArgs { HyperSet s[kSmallByValue]; };             // by value up to kSmallByValue sets, as SmallSetArgs
 static_assert(sizeof(HyperSetArgs) <= 3072, "the descriptors by value and the other arguments fit the kernel arguments");
@@ -116,28 +28,6 @@ static_assert(sizeof(HyperSetArgs) <= 3072, "the descriptors by value and the ot
 // ---- the prologue, the per-sample body and the close of a marginalised sweep: hyper_avg_kernel (one model, one candidate
 // set) and hyper_sets_kernel (every set of a trial) are both built from these, so the arithmetic exists once
 // and the two kernels' results are equal by construction.
-
-// r = y - m(X) of this thread's row: it does not depend on the sample
-__device__ __forceinline__ double hyper_rhs(const cbo_small_set &st)
-{
-    const int tid = threadIdx.x;
-    double rhs = 0.0;
-    if (tid < st.n) {
-        const double yv = st.y[tid];
-        rhs = st.pm ? __dadd_rn(yv, -st.pm[tid]) : yv;
-    }
-    return rhs;
-}
-
-// phases 1 of a two-launch form: factor the sample `row` of the model into the scratch slot `fs`, nothing else
-__device__ __forceinline__ void hyper_factor_sample(SmallShared &sh, const cbo_small_set &st, const double *__restrict__ row,
-                                                    int n_ls, int tiles, double rhs, double *fs, int *info_word)
-{
-    const cbo_small_set sth = hyper_sample_set(st, row, n_ls);
-    hyper_model_points(sh, st, st.ard ? row + 1 : nullptr);
-    __syncthreads();
-    hyper_factor(sh, sth, tiles, rhs, fs, fs + 128 * kSmallLd, info_word);
-}
 
 // This lane's candidate of candidate block `blk` (clamped: lanes beyond the set compute, nobody looks) and the prior
 // closures at it, which do not depend on the sample either

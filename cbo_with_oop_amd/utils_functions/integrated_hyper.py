@@ -60,6 +60,65 @@ def hmc_sample(objective_and_grad, theta0, num_samples, hmc_iters, stepsize):
     return params
 
 
+def hmc_draws(size, num_samples):
+    """The random numbers ``hmc_sample`` consumes for a chain of ``num_samples`` samples over ``size`` parameters, drawn from
+    numpy's global generator in its own order -- per sample one ``np.random.multivariate_normal(zeros, I)``, then one
+    ``np.random.rand()``; the chain's course never changes what is drawn.  Returns (momenta (num_samples, size), uniforms
+    (num_samples,))."""
+    size, num_samples = int(size), int(num_samples)
+    identity = np.eye(size)
+    momenta = np.empty((num_samples, size))
+    uniforms = np.empty(num_samples)
+    for i in range(num_samples):
+        momenta[i] = np.random.multivariate_normal(np.zeros(size), identity)
+        uniforms[i] = np.random.rand()
+    return momenta, uniforms
+
+
+def hmc_sample_from_draws(objective_and_grad, theta0, momenta, uniforms, hmc_iters, stepsize):
+    """``hmc_sample``'s arithmetic with the draws handed in (``hmc_draws``): the same chain, bit for bit, without touching
+    the generator -- the host form of the chain ``cbo_gp_hmc_sets`` runs on the device (csrc/hmc_chain.h), and the fallback
+    for a chain the device declined.  Returns (rows (num_samples, P), accept flags (num_samples,) bool, accept
+    probabilities k (num_samples,))."""
+    x = np.array(logexp_finv(np.asarray(theta0, dtype=np.float64)), dtype=np.float64).reshape(-1)
+    size = x.size
+    momenta = np.asarray(momenta, dtype=np.float64).reshape(-1, size)
+    uniforms = np.asarray(uniforms, dtype=np.float64).reshape(-1)
+    num_samples = uniforms.size
+    if momenta.shape[0] != num_samples:
+        raise ValueError("momenta must hold one row per uniform")
+    params = np.empty((num_samples, size))
+    accepted = np.zeros(num_samples, dtype=bool)
+    ks = np.empty(num_samples)
+    f, g = objective_and_grad(x)
+    g = np.asarray(g, dtype=np.float64)
+
+    def hamiltonian(fx, p):
+        return fx + size * np.log(2 * np.pi) / 2.0 + np.dot(p, p) / 2.0
+
+    for i in range(num_samples):
+        p = momenta[i].copy()
+        h_old = hamiltonian(f, p)
+        x_old, f_old, g_old = x.copy(), f, g
+        params[i] = logexp_f(x)
+        with np.errstate(over="ignore", invalid="ignore"):
+            for _ in range(int(hmc_iters)):
+                p = p + (-stepsize / 2.0) * g
+                x = x + stepsize * p
+                f, g = objective_and_grad(x)
+                g = np.asarray(g, dtype=np.float64)
+                p = p + (-stepsize / 2.0) * g
+            h_new = hamiltonian(f, p)
+            k = 1.0 if h_old > h_new else np.exp(h_old - h_new)
+        ks[i] = k
+        if uniforms[i] < k:
+            params[i] = logexp_f(x)
+            accepted[i] = True
+        else:
+            x, f, g = x_old, f_old, g_old
+    return params, accepted, ks
+
+
 def _hyper_rows(model, samples):
     """(H, 2 + L) rows of (variance, lengthscale x L, noise variance) for ``cbo_acq_sweep_hyper`` from (H, P) samples in
     GPy's parameter order; a model whose noise is fixed has no noise column (P = 1 + L): its own noise fills it."""
@@ -80,10 +139,14 @@ def _hyper_rows(model, samples):
 class IntegratedHyperParameterAcquisition:
     """emukit's ``IntegratedHyperParameterAcquisition`` for the causal EI: its signature plus ``samples``, an (H, P) array
     that skips the sampler.  ``acquisition_generator(model)`` must return a ``CausalExpectedImprovement`` or that over a
-    ``Cost``; the average over the samples runs on the device, the model is not touched when it is small."""
+    ``Cost``; the average over the samples runs on the device, the model is not touched when it is small.
+    ``sampler="device"`` draws the samples by the one-launch HMC; ``"host"`` (default) is the host chain."""
 
     def __init__(self, model, acquisition_generator, n_samples=10, n_burnin=100, subsample_interval=10, step_size=1e-1,
-                 leapfrog_steps=20, samples=None):
+                 leapfrog_steps=20, samples=None, sampler="host"):
+        if sampler not in ("host", "device"):
+            raise ValueError(f"sampler must be 'host' or 'device', not {sampler!r}")
+        self.sampler = sampler
         self.model = model
         self.acquisition_generator = acquisition_generator
         acquisition = acquisition_generator(model)
@@ -110,7 +173,8 @@ class IntegratedHyperParameterAcquisition:
     def update_parameters(self):
         """Redraw the samples (emukit: ``model.generate_hyperparameters_samples(...)``)."""
         self.samples = _hyper_rows(self.model, self.model.generate_hyperparameters_samples(
-            self.n_samples, self.n_burnin, self.subsample_interval, self.step_size, self.leapfrog_steps))
+            self.n_samples, self.n_burnin, self.subsample_interval, self.step_size, self.leapfrog_steps,
+            **({} if self.sampler == "host" else {"sampler": self.sampler})))
 
     def sweep(self, candidates, cost=None, want_acq=False):
         """dict(best_val, best_idx, acq, mean, var) as ``CausalExpectedImprovement.sweep`` returns it (mean and var are

@@ -743,6 +743,43 @@ int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *se
                         int task, double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
                         int *rounds_out, int *status_out);
 
+/* Hyper-parameter posterior samples of every model by HMC in ONE launch: GPy's inference.mcmc.HMC with the
+ * unit mass matrix over the Logexp-transformed parameters -- integrated_hyper.hmc_sample, restated in csrc/hmc_chain.h -- one
+ * chain per model, every chain inside hmc_sets_kernel: a workgroup factors its model at each position of its chain from
+ * the raw coordinates and evaluates the log marginal likelihood and its gradients there, with cbo_gp_lml_gradients'
+ * arithmetic.  The random numbers are the caller's: per sample one momentum (n_params standard normals) and one uniform.
+ * Per model: theta0 (n_params positive values: variance, the lengthscale(s), and the noise variance when sample_noise = 1; a
+ * model whose noise is fixed has sample_noise = 0 and keeps its own), num_samples, hmc_iters leapfrog steps of stepsize.
+ * Outputs per model: rows_out (num_samples x n_params, theta at each sample's start, overwritten by the proposal when it
+ * is accepted), accept_out (num_samples flags), and the chain's last state: final_theta, final_lml, final_grad (n_params;
+ * d lml / d theta) -- the likelihood and gradients cbo_gp_lml_gradients returns for the model at final_theta, bit for bit.
+ * status_out[i]: CBO_HMC_OK; CBO_HMC_NOT_PD -- a position's Ky was not positive definite as assembled (the launch cannot
+ * walk jitchol's ladder): the chain stopped, its outputs mean nothing, the caller repeats it on the host with the same draws;
+ * CBO_HMC_DECLINED -- the model is not one the launch takes (more than 128 observations, fp32 data, CBO_HIP_SMALL_SETS=0):
+ * nothing else is written for it.  Models are only read: hyper-parameters, fitted state, caches and kept solutions stay as
+ * they were; no fit needed.
+ * CBO_ERR_INVALID before any device work: n_models <= 0, NULL arguments or handles, models of different contexts,
+ * num_samples outside 1..CBO_HMC_MAX_SAMPLES, hmc_iters < 0, num_samples * hmc_iters above CBO_HMC_MAX_EVALS, a stepsize or
+ * theta0 that is not finite and positive, sample_noise other than 0 / 1, n_params other than 1 + (ARD ? d : 1) +
+ * sample_noise, non-finite draws.
+ * CBO_HMC_MAX_SAMPLES: 4096 samples of 10 parameters are 320 KiB of draws and as much of rows per model, in pinned memory --
+ * twenty times emukit's default chain (100 burn-in + 10 x 10).  CBO_HMC_MAX_EVALS: one launch evaluates the likelihood
+ * 1 + num_samples * hmc_iters times per model, one after the other, at tens of microseconds each: 2^18 keeps the longest
+ * launch to some seconds (emukit's default chain has 4000). */
+#define CBO_HMC_MAX_PARAMS (CBO_MAX_DIM + 2)
+#define CBO_HMC_MAX_SAMPLES 4096
+#define CBO_HMC_MAX_EVALS 262144
+enum { CBO_HMC_OK = 0, CBO_HMC_NOT_PD = 1, CBO_HMC_DECLINED = 2 };
+typedef struct cbo_hmc_chain {
+    int n_params, sample_noise, num_samples, hmc_iters;
+    double stepsize;
+    const double *theta0;                               /* n_params */
+    const double *momenta, *uniforms;                   /* num_samples x n_params, num_samples */
+    double *rows_out; int *accept_out;                  /* num_samples x n_params, num_samples */
+    double *final_theta, *final_lml, *final_grad;       /* n_params, 1, n_params */
+} cbo_hmc_chain;
+int cbo_gp_hmc_sets(int n_models, cbo_gp *const *gps, const cbo_hmc_chain *chains, int *status_out);
+
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
                        const double *prior_var_s, double y_best, int task, double ei_jitter,
