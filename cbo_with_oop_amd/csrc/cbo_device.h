@@ -95,6 +95,30 @@ __device__ __forceinline__ double exp_nonpositive(double x)
     p = horner(p, r, 1.0);
     return select_f64(x <= -745.2, 0.0, ldexp(p, (int)k));           // underflow; a NaN argument has made p NaN
 }
+// |x|^2 of one point of d coordinates (x[k] = 0 for k >= d), the squared norm every kernel-matrix element's r^2 is formed
+// from.  d < 8: the chain rn(x0^2), then fma(xk, xk, s) -- the chain kernel_value's dot product takes, so r^2(x, x) is an
+// exact zero.  d = 8: numpy's 8-way pairwise tree, ((p01 + p23) + (p45 + p67)), over the pairs p01 = fma(x1, x1, rn(x0^2)),
+// p23 = fma(x3, x3, rn(x2^2)), ...  Every fused step is WRITTEN as an fma: __dmul_rn and __dadd_rn are plain * and + to the
+// compiler, and a product next to a sum is contracted or not, and on either operand, as the compiler sees fit; a product
+// that feeds an explicit fma, and a sum of two fmas, leave it nothing to choose.  tests/test_dims_gpu.py pins the order: two
+// live coordinates in the slots (2k, 2k + 1) of an 8-column problem give the two-column problem's bits, in slots of two
+// different pairs rn(rn(a^2) + rn(b^2)).
+__device__ __forceinline__ double squared_norm(const double (&x)[CBO_MAX_DIM], int d)
+{
+    if (d == 8) {
+        const double p01 = __fma_rn(x[1], x[1], __dmul_rn(x[0], x[0]));
+        const double p23 = __fma_rn(x[3], x[3], __dmul_rn(x[2], x[2]));
+        const double p45 = __fma_rn(x[5], x[5], __dmul_rn(x[4], x[4]));
+        const double p67 = __fma_rn(x[7], x[7], __dmul_rn(x[6], x[6]));
+        return __dadd_rn(__dadd_rn(p01, p23), __dadd_rn(p45, p67));
+    }
+    double s = __dmul_rn(x[0], x[0]);
+#pragma unroll
+    for (int k = 1; k < CBO_MAX_DIM; ++k)
+        if (k < d) s = __fma_rn(x[k], x[k], s);
+    return s;
+}
+
 // One kernel-matrix element, GPy operation order (Stationary._unscaled_dist: GEMM-trick squared distance from the
 // same |x|^2 sums, clip at 0; RBF.K_of_r), restating /root/reference/src/utils_functions/causal_kernels.py:45-62
 // without the rank-1 causal term (added by the caller).

@@ -552,19 +552,7 @@ __device__ __forceinline__ void small_model_factor(SmallShared &sh, const cbo_sm
                     }
                 if (st.sv) pvi = st.stage[(int64_t)st.n * st.d + 2 * st.n + tid];
             }
-            double sum;
-            if (st.d == 8) {
-                double r[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) r[k] = __dmul_rn(x[k], x[k]);
-                sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                                __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-            } else {
-                sum = 0.0;
-#pragma unroll
-                for (int k = 0; k < CBO_MAX_DIM; ++k)
-                    if (k < st.d) sum = __dadd_rn(sum, __dmul_rn(x[k], x[k]));
-            }
+            const double sum = squared_norm(x, st.d);
             const double svi = (in && st.sv) ? sqrt(pvi) : 0.0;
 #pragma unroll
             for (int k = 0; k < CBO_MAX_DIM; ++k)

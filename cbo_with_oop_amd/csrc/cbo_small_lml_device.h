@@ -24,18 +24,7 @@ __device__ __forceinline__ void hyper_point(const double *__restrict__ raw, int6
                 x[k] = v;
             }
     }
-    if (d == 8) {
-        double r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = __dmul_rn(x[k], x[k]);
-        sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                        __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-    } else {
-        sum = 0.0;
-#pragma unroll
-        for (int k = 0; k < CBO_MAX_DIM; ++k)
-            if (k < d) sum = __dadd_rn(sum, __dmul_rn(x[k], x[k]));
-    }
+    sum = squared_norm(x, d);
 }
 
 // The descriptor of sample h: the model's with the sample's variance, lengthscale and noise in the place of its own

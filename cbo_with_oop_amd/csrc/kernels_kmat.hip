@@ -19,8 +19,8 @@
 namespace cbo {
 
 // ------------------------------------------------------------------------------------------------
-// AoS -> SoA, optional per-dimension scaling (GPy ARD: X / lengthscale), squared norms exactly as
-// numpy's np.sum(np.square(X), 1) forms them (sequential for d < 8, the 8-way pairwise tree at d = 8).
+// AoS -> SoA, optional per-dimension scaling (GPy ARD: X / lengthscale), squared norms in the order numpy's
+// np.sum(np.square(X), 1) takes (sequential for d < 8, the 8-way pairwise tree at d = 8): squared_norm of cbo_device.h.
 __global__ __launch_bounds__(256) void prep_points_kernel(const double *__restrict__ raw, int64_t n, int d,
                                                           const double *__restrict__ ls,
                                                           const double *__restrict__ pv,
@@ -44,19 +44,7 @@ __global__ __launch_bounds__(256) void prep_points_kernel(const double *__restri
 #pragma unroll
     for (int k = 0; k < CBO_MAX_DIM; ++k)
         if (k < d) xs[(int64_t)k * ld + i] = x[k];
-    double s;
-    if (d == 8) {
-        double r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = __dmul_rn(x[k], x[k]);
-        s = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                      __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-    } else {
-        s = 0.0;
-#pragma unroll
-        for (int k = 0; k < CBO_MAX_DIM; ++k)
-            if (k < d) s = __dadd_rn(s, __dmul_rn(x[k], x[k]));
-    }
+    const double s = squared_norm(x, d);
     sq[i] = s;
     if (sv) sv[i] = (i < n && pv) ? sqrt(pv[i]) : 0.0;
 }
@@ -96,19 +84,7 @@ __global__ __launch_bounds__(256) void prep_points_staged_kernel(const double *_
 #pragma unroll
     for (int k = 0; k < CBO_MAX_DIM; ++k)
         if (k < d) xs[(int64_t)k * ld + i] = x[k];
-    double s;
-    if (d == 8) {
-        double r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = __dmul_rn(x[k], x[k]);
-        s = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                      __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-    } else {
-        s = 0.0;
-#pragma unroll
-        for (int k = 0; k < CBO_MAX_DIM; ++k)
-            if (k < d) s = __dadd_rn(s, __dmul_rn(x[k], x[k]));
-    }
+    const double s = squared_norm(x, d);
     sq[i] = s;
     if (sv) sv[i] = (i < n && has_prior) ? sqrt(pvi) : 0.0;
 }

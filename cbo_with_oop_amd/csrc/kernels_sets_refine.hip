@@ -148,19 +148,7 @@ __global__ __launch_bounds__(256) void small_sets_refine_kernel(const SmallSetAr
         double xc[CBO_MAX_DIM];
 #pragma unroll
         for (int k = 0; k < CBO_MAX_DIM; ++k) xc[k] = (k < d) ? (rf.ard ? xt[k] / scale[k] : xt[k]) : 0.0;
-        double csq;
-        if (d == 8) {
-            double r[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) r[k] = __dmul_rn(xc[k], xc[k]);
-            csq = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                            __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-        } else {
-            csq = 0.0;
-#pragma unroll
-            for (int k = 0; k < CBO_MAX_DIM; ++k)
-                if (k < d) csq = __dadd_rn(csq, __dmul_rn(xc[k], xc[k]));
-        }
+        const double csq = squared_norm(xc, d);
         double xcj = xc[0];
 #pragma unroll
         for (int k = 1; k < CBO_MAX_DIM; ++k) xcj = (k == jm) ? xc[k] : xcj;
