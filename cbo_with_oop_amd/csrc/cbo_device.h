@@ -119,6 +119,30 @@ __device__ __forceinline__ double squared_norm(const double (&x)[CBO_MAX_DIM], i
     return s;
 }
 
+// CBO_FOR_DIM(d, statement): the one place a runtime dimension d picks its instantiation of a `template <int D>` kernel or
+// device function.  The statement is compiled once per dimension with D a constant, e.g.
+//     CBO_FOR_DIM(st.d, small_assemble<D>(sh, st, tiles));
+// Every case comes from CBO_FOR_DIM_CASE(N, ...), which writes N once, as the label and as D, so a label cannot launch
+// another dimension's code.  d is validated to [1, CBO_MAX_DIM] where it enters (cbo_gp_create, cbo_cands_create), so
+// `default:` can only mean CBO_MAX_DIM.
+// A macro and not a generic lambda (for_dim(d, [&](auto D) { ... })): the macro expands to the plain switch, and the device
+// code is the hand-written switch's line for line.  The lambda's by-reference capture costs stack in device code --
+// hmc_sets_kernel went from 32 to 64 bytes of private segment, from 4 to 14 spilled VGPRs, the file from 8 to 28 scratch
+// instructions.
+static_assert(CBO_MAX_DIM == 8, "CBO_FOR_DIM lists the cases 1..7 and the default: extend the list with the limit");
+#define CBO_FOR_DIM_CASE(N, ...) case N: { constexpr int D = N; __VA_ARGS__; } break;
+#define CBO_FOR_DIM(d, ...)                                                                                             \
+    switch (d) {                                                                                                        \
+        CBO_FOR_DIM_CASE(1, __VA_ARGS__)                                                                                \
+        CBO_FOR_DIM_CASE(2, __VA_ARGS__)                                                                                \
+        CBO_FOR_DIM_CASE(3, __VA_ARGS__)                                                                                \
+        CBO_FOR_DIM_CASE(4, __VA_ARGS__)                                                                                \
+        CBO_FOR_DIM_CASE(5, __VA_ARGS__)                                                                                \
+        CBO_FOR_DIM_CASE(6, __VA_ARGS__)                                                                                \
+        CBO_FOR_DIM_CASE(7, __VA_ARGS__)                                                                                \
+        default: { constexpr int D = CBO_MAX_DIM; __VA_ARGS__; } break;                                                 \
+    }
+
 // One kernel-matrix element, GPy operation order (Stationary._unscaled_dist: GEMM-trick squared distance from the
 // same |x|^2 sums, clip at 0; RBF.K_of_r), restating /root/reference/src/utils_functions/causal_kernels.py:45-62
 // without the rank-1 causal term (added by the caller).

@@ -585,16 +585,7 @@ __device__ __forceinline__ void small_model_factor(SmallShared &sh, const cbo_sm
     }
     __syncthreads();
     if (phases & 1) {
-    switch (st.d) {
-        case 1: small_assemble<1>(sh, st, tiles); break;
-        case 2: small_assemble<2>(sh, st, tiles); break;
-        case 3: small_assemble<3>(sh, st, tiles); break;
-        case 4: small_assemble<4>(sh, st, tiles); break;
-        case 5: small_assemble<5>(sh, st, tiles); break;
-        case 6: small_assemble<6>(sh, st, tiles); break;
-        case 7: small_assemble<7>(sh, st, tiles); break;
-        default: small_assemble<8>(sh, st, tiles); break;
-    }
+    CBO_FOR_DIM(st.d, small_assemble<D>(sh, st, tiles));
     {
         const int rows = 16 * tiles;
         for (int r = tid >> 4; r < rows; r += 16)
@@ -688,16 +679,7 @@ __device__ __forceinline__ void small_kstar_tiles_of(const SmallShared &sh, cons
                                                      const double *xc, double csq, double csv, double inv_l2, int kq,
                                                      d4 (&acc)[8])
 {
-    switch (st.d) {
-        case 1: small_kstar_tiles<1>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 2: small_kstar_tiles<2>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 3: small_kstar_tiles<3>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 4: small_kstar_tiles<4>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 5: small_kstar_tiles<5>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 6: small_kstar_tiles<6>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        case 7: small_kstar_tiles<7>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-        default: small_kstar_tiles<8>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc); break;
-    }
+    CBO_FOR_DIM(st.d, small_kstar_tiles<D>(sh, st, tiles, xc, csq, csv, inv_l2, kq, acc));
 }
 
 // V = L^-1 K* of one wave's 16 candidates, q = sum V^2, mu = V^T z: lane partials, then over the four lane groups (the strip

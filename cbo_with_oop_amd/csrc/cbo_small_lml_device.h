@@ -61,16 +61,7 @@ __device__ __forceinline__ void hyper_factor(SmallShared &sh, const cbo_small_se
                                              double *invs, int *info_word)
 {
     const int tid = threadIdx.x;
-    switch (st.d) {
-        case 1: small_assemble<1>(sh, st, tiles); break;
-        case 2: small_assemble<2>(sh, st, tiles); break;
-        case 3: small_assemble<3>(sh, st, tiles); break;
-        case 4: small_assemble<4>(sh, st, tiles); break;
-        case 5: small_assemble<5>(sh, st, tiles); break;
-        case 6: small_assemble<6>(sh, st, tiles); break;
-        case 7: small_assemble<7>(sh, st, tiles); break;
-        default: small_assemble<8>(sh, st, tiles); break;
-    }
+    CBO_FOR_DIM(st.d, small_assemble<D>(sh, st, tiles));
     const int rows = 16 * tiles;
     for (int r = tid >> 4; r < rows; r += 16)
         for (int c = rows + (tid & 15); c < kDiagLd; c += 16) {

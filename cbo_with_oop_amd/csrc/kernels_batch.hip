@@ -156,16 +156,7 @@ void launch_batch_pick(hipStream_t s, const BatchPivotArgs &pa, BatchFinalArgs f
     fa.slices = n > 0 ? slices : 0;
     fa.partial = partial;
     const dim3 grid((unsigned)((pa.m_pad + 255) / 256));
-    switch (pa.dims) {
-        case 1: hipLaunchKernelGGL(batch_final_kernel<1>, grid, dim3(256), 0, s, fa); break;
-        case 2: hipLaunchKernelGGL(batch_final_kernel<2>, grid, dim3(256), 0, s, fa); break;
-        case 3: hipLaunchKernelGGL(batch_final_kernel<3>, grid, dim3(256), 0, s, fa); break;
-        case 4: hipLaunchKernelGGL(batch_final_kernel<4>, grid, dim3(256), 0, s, fa); break;
-        case 5: hipLaunchKernelGGL(batch_final_kernel<5>, grid, dim3(256), 0, s, fa); break;
-        case 6: hipLaunchKernelGGL(batch_final_kernel<6>, grid, dim3(256), 0, s, fa); break;
-        case 7: hipLaunchKernelGGL(batch_final_kernel<7>, grid, dim3(256), 0, s, fa); break;
-        default: hipLaunchKernelGGL(batch_final_kernel<8>, grid, dim3(256), 0, s, fa); break;
-    }
+    CBO_FOR_DIM(pa.dims, hipLaunchKernelGGL(batch_final_kernel<D>, grid, dim3(256), 0, s, fa));
 }
 
 }  // namespace cbo

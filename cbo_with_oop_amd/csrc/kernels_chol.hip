@@ -612,28 +612,10 @@ __global__ __launch_bounds__(256) void small_lml_batch_kernel(const SmallSetArgs
     const cbo_small_set st = BYVAL ? byval.s[b] : sets[b];
     double *my = scratch + (int64_t)b * stride;
     if (st.n > 128) {                                               // 128 < n <= 256: the two-block form
-        switch (st.d) {
-            case 1: mid_lml_body<1>(sh, red, st, my, &info[b], &out[b], seq); break;
-            case 2: mid_lml_body<2>(sh, red, st, my, &info[b], &out[b], seq); break;
-            case 3: mid_lml_body<3>(sh, red, st, my, &info[b], &out[b], seq); break;
-            case 4: mid_lml_body<4>(sh, red, st, my, &info[b], &out[b], seq); break;
-            case 5: mid_lml_body<5>(sh, red, st, my, &info[b], &out[b], seq); break;
-            case 6: mid_lml_body<6>(sh, red, st, my, &info[b], &out[b], seq); break;
-            case 7: mid_lml_body<7>(sh, red, st, my, &info[b], &out[b], seq); break;
-            default: mid_lml_body<8>(sh, red, st, my, &info[b], &out[b], seq); break;
-        }
+        CBO_FOR_DIM(st.d, mid_lml_body<D>(sh, red, st, my, &info[b], &out[b], seq));
         return;
     }
-    switch (st.d) {
-        case 1: small_lml_body<1>(sh, alpha_s, red, st, my, &info[b], &out[b], seq); break;
-        case 2: small_lml_body<2>(sh, alpha_s, red, st, my, &info[b], &out[b], seq); break;
-        case 3: small_lml_body<3>(sh, alpha_s, red, st, my, &info[b], &out[b], seq); break;
-        case 4: small_lml_body<4>(sh, alpha_s, red, st, my, &info[b], &out[b], seq); break;
-        case 5: small_lml_body<5>(sh, alpha_s, red, st, my, &info[b], &out[b], seq); break;
-        case 6: small_lml_body<6>(sh, alpha_s, red, st, my, &info[b], &out[b], seq); break;
-        case 7: small_lml_body<7>(sh, alpha_s, red, st, my, &info[b], &out[b], seq); break;
-        default: small_lml_body<8>(sh, alpha_s, red, st, my, &info[b], &out[b], seq); break;
-    }
+    CBO_FOR_DIM(st.d, small_lml_body<D>(sh, alpha_s, red, st, my, &info[b], &out[b], seq));
 }
 
 void launch_small_lml_batch(hipStream_t s, const cbo_small_set *sets, int n_models, double *scratch, int64_t stride,
@@ -658,24 +640,11 @@ void launch_small_lml_batch(hipStream_t s, const cbo_small_set *sets, int n_mode
 
 void launch_small_lml(hipStream_t s, const cbo_small_set &st, double *scratch, int *info, cbo_small_lml_result *out, int seq)
 {
-#define CBO_LAUNCH_LML(D)                                                                                              \
-    do {                                                                                                               \
-        hipFuncSetAttribute(reinterpret_cast<const void *>(small_lml_kernel<D>),                                       \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallShared));                     \
-        hipLaunchKernelGGL(small_lml_kernel<D>, dim3(1), dim3(256), sizeof(SmallShared), s, st, scratch, info, out,    \
-                           seq);                                                                                       \
-    } while (0)
-    switch (st.d) {
-        case 1: CBO_LAUNCH_LML(1); break;
-        case 2: CBO_LAUNCH_LML(2); break;
-        case 3: CBO_LAUNCH_LML(3); break;
-        case 4: CBO_LAUNCH_LML(4); break;
-        case 5: CBO_LAUNCH_LML(5); break;
-        case 6: CBO_LAUNCH_LML(6); break;
-        case 7: CBO_LAUNCH_LML(7); break;
-        default: CBO_LAUNCH_LML(8); break;
-    }
-#undef CBO_LAUNCH_LML
+    CBO_FOR_DIM(st.d,
+                hipFuncSetAttribute(reinterpret_cast<const void *>(small_lml_kernel<D>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallShared));
+                hipLaunchKernelGGL(small_lml_kernel<D>, dim3(1), dim3(256), sizeof(SmallShared), s, st, scratch, info, out,
+                                   seq));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -109,16 +109,7 @@ __global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval,
         if (tid < 128) alpha_s[tid] = 0.0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        switch (st.d) {
-            case 1: small_lml_after_factor<1>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
-            case 2: small_lml_after_factor<2>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
-            case 3: small_lml_after_factor<3>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
-            case 4: small_lml_after_factor<4>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
-            case 5: small_lml_after_factor<5>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
-            case 6: small_lml_after_factor<6>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
-            case 7: small_lml_after_factor<7>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
-            default: small_lml_after_factor<8>(sh, alpha_s, red, sth, Us, Vg, iv, zr); break;
-        }
+        CBO_FOR_DIM(st.d, small_lml_after_factor<D>(sh, alpha_s, red, sth, Us, Vg, iv, zr));
         // ---- the likelihood and its gradients by the host's arithmetic, one step of the chain
         if (tid == 0) {
             double t[kSmallLmlTerms];

@@ -366,16 +366,7 @@ __global__ __launch_bounds__(256) void factor_padding_kernel(double *A, int64_t 
 template <bool SYM>
 static void launch_cov_d(hipStream_t s, int d, const CovArgs &a, dim3 grid)
 {
-    switch (d) {
-        case 1: hipLaunchKernelGGL((cov_tile_kernel<1, SYM>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((cov_tile_kernel<2, SYM>), grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((cov_tile_kernel<3, SYM>), grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((cov_tile_kernel<4, SYM>), grid, dim3(256), 0, s, a); break;
-        case 5: hipLaunchKernelGGL((cov_tile_kernel<5, SYM>), grid, dim3(256), 0, s, a); break;
-        case 6: hipLaunchKernelGGL((cov_tile_kernel<6, SYM>), grid, dim3(256), 0, s, a); break;
-        case 7: hipLaunchKernelGGL((cov_tile_kernel<7, SYM>), grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((cov_tile_kernel<8, SYM>), grid, dim3(256), 0, s, a); break;
-    }
+    CBO_FOR_DIM(d, hipLaunchKernelGGL((cov_tile_kernel<D, SYM>), grid, dim3(256), 0, s, a));
 }
 
 void launch_cov_tiles(hipStream_t s, int d, bool sym, CovArgs a)
@@ -395,16 +386,7 @@ void launch_ivr_tiles(hipStream_t s, int d, IvrArgs a)
 {
     const dim3 grid((unsigned)((a.p + kTile - 1) / kTile), (unsigned)((a.m + kTile - 1) / kTile));
     a.n_k = (int)round_up(a.n_k, kTileKB);
-    switch (d) {
-        case 1: hipLaunchKernelGGL(ivr_tile_kernel<1>, grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL(ivr_tile_kernel<2>, grid, dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL(ivr_tile_kernel<3>, grid, dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL(ivr_tile_kernel<4>, grid, dim3(256), 0, s, a); break;
-        case 5: hipLaunchKernelGGL(ivr_tile_kernel<5>, grid, dim3(256), 0, s, a); break;
-        case 6: hipLaunchKernelGGL(ivr_tile_kernel<6>, grid, dim3(256), 0, s, a); break;
-        case 7: hipLaunchKernelGGL(ivr_tile_kernel<7>, grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(ivr_tile_kernel<8>, grid, dim3(256), 0, s, a); break;
-    }
+    CBO_FOR_DIM(d, hipLaunchKernelGGL(ivr_tile_kernel<D>, grid, dim3(256), 0, s, a));
 }
 
 void launch_samples_tiles(hipStream_t st, SampArgs a)

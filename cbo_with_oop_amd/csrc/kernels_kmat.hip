@@ -245,16 +245,7 @@ static void launch_kmat_d(hipStream_t s, const KmatArgs &a, dim3 grid)
 
 static void launch_kmat(hipStream_t s, int d, const KmatArgs &a, dim3 grid)
 {
-    switch (d) {
-        case 1: launch_kmat_d<1>(s, a, grid); break;
-        case 2: launch_kmat_d<2>(s, a, grid); break;
-        case 3: launch_kmat_d<3>(s, a, grid); break;
-        case 4: launch_kmat_d<4>(s, a, grid); break;
-        case 5: launch_kmat_d<5>(s, a, grid); break;
-        case 6: launch_kmat_d<6>(s, a, grid); break;
-        case 7: launch_kmat_d<7>(s, a, grid); break;
-        default: launch_kmat_d<8>(s, a, grid); break;
-    }
+    CBO_FOR_DIM(d, launch_kmat_d<D>(s, a, grid));
 }
 
 void launch_kxx(hipStream_t s, const PointSet &X, const KernelHyper &h, double diag_add, double jitter, double *A,
@@ -489,20 +480,8 @@ void launch_lml_grad(hipStream_t s, const PointSet &X, const KernelHyper &h, con
     const int nt = (int)(n_pad / 64);
     const dim3 grid(nt, nt);
     const double inv_l2 = h.ard ? 1.0 : 1.0 / (h.lengthscale * h.lengthscale);
-#define CBO_LAUNCH_GRAD(D)                                                                                     \
-    hipLaunchKernelGGL(lml_grad_tile_kernel<D>, grid, dim3(256), 0, s, X.xs, X.ld, X.n, alpha, negW, ldw, h.variance, \
-                       inv_l2, X.sv, partial)
-    switch (X.d) {
-        case 1: CBO_LAUNCH_GRAD(1); break;
-        case 2: CBO_LAUNCH_GRAD(2); break;
-        case 3: CBO_LAUNCH_GRAD(3); break;
-        case 4: CBO_LAUNCH_GRAD(4); break;
-        case 5: CBO_LAUNCH_GRAD(5); break;
-        case 6: CBO_LAUNCH_GRAD(6); break;
-        case 7: CBO_LAUNCH_GRAD(7); break;
-        default: CBO_LAUNCH_GRAD(8); break;
-    }
-#undef CBO_LAUNCH_GRAD
+    CBO_FOR_DIM(X.d, hipLaunchKernelGGL(lml_grad_tile_kernel<D>, grid, dim3(256), 0, s, X.xs, X.ld, X.n, alpha, negW, ldw,
+                                        h.variance, inv_l2, X.sv, partial));
     hipLaunchKernelGGL(lml_grad_final_kernel, dim3(1), dim3(16), 0, s, partial, nt * nt, 1 + X.d, out);
 }
 

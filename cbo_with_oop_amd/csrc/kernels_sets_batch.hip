@@ -225,16 +225,7 @@ __global__ __launch_bounds__(256) void small_sets_batch_kernel(const SmallSetArg
     status = bs.status;
     __syncthreads();
     if (status == 0) {                                            // (uniform) else: the general path, from the host
-        switch (st.d) {
-            case 1: small_batch_picks<1>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0); break;
-            case 2: small_batch_picks<2>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0); break;
-            case 3: small_batch_picks<3>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0); break;
-            case 4: small_batch_picks<4>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0); break;
-            case 5: small_batch_picks<5>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0); break;
-            case 6: small_batch_picks<6>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0); break;
-            case 7: small_batch_picks<7>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0); break;
-            default: small_batch_picks<8>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0); break;
-        }
+        CBO_FOR_DIM(st.d, small_batch_picks<D>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0));
     }
     if (tid == 0) small_set_record(v0, i0, status, set, info, ticket, out, seq);   // (after thread 0's winners)
 }

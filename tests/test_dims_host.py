@@ -1,5 +1,6 @@
 """Host side of the dimension tests (no GPU): the zero-extension premise of tests/dims_support.py on the numpy
-oracle, the placements' coverage, and a scan of the hand-written ``switch (d)`` launchers in csrc.
+oracle, the placements' coverage, and a scan of csrc's dimension dispatch: the one macro CBO_FOR_DIM, its uses, and the
+``case N:`` lines that remain.
 
 The oracle's BLAS may associate a dot product differently for another column count, so the oracle is compared at the
 rtol tests/test_parity_gpu.py::test_ragged_sizes_and_dims applies (1e-7 mean, 1e-6 variance), not bit for bit; the
@@ -92,23 +93,71 @@ def test_embedding_premise_on_the_oracle(emb, variant):
 CASE = re.compile(r"^\s*case\s+(\d+)\s*:(.*)$")
 TEMPLATE_ARG = re.compile(r"<\s*(\d+)\s*[,>]")
 MACRO_ARG = re.compile(r"\b[A-Z][A-Z0-9_]*\(\s*(\d+)\s*\)")
+D_ARG = re.compile(r"<\s*D\s*[,>]|\b[A-Z][A-Z0-9_]*\(\s*D\s*[,)]")
+COMMENT = re.compile(r"//[^\n]*|/\*.*?\*/", re.S)
+DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(CBO_FOR_DIM(?:_CASE)?)\((?:[^\n]*\\\n)*[^\n]*\n", re.M)
+
+
+def csrc_sources():
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))):
+        with open(path) as f:
+            yield os.path.basename(path), f.read()
+
+
+def dispatch_uses(text):
+    """(line, dimension expression, body) of every CBO_FOR_DIM(...) call in a text without comments and definitions"""
+    for hit in re.finditer(r"\bCBO_FOR_DIM\(", text):
+        depth, comma, at = 1, None, hit.end()
+        while depth:
+            c = text[at]
+            depth += (c == "(") - (c == ")")
+            if c == "," and depth == 1 and comma is None:
+                comma = at
+            at += 1
+        assert comma is not None, text[hit.start():at]
+        yield text.count("\n", 0, hit.start()) + 1, text[hit.end():comma].strip(), text[comma + 1:at - 1]
 
 
 def test_every_case_label_launches_its_own_instantiation():
-    """``case N:`` followed on the same line by a template argument list or an upper-case macro call whose first
-    argument is a literal: that literal is N.  A ``case 6:`` that launches ``<5>`` fails here before it reaches a GPU."""
-    checked, wrong = 0, []
-    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))):
-        with open(path) as f:
-            for no, line in enumerate(f, 1):
-                hit = CASE.match(line)
-                if not hit:
-                    continue
-                args = TEMPLATE_ARG.findall(hit.group(2)) + MACRO_ARG.findall(hit.group(2))
-                if not args:
-                    continue
-                checked += 1
-                if any(int(a) != int(hit.group(1)) for a in args):
-                    wrong.append(f"{os.path.basename(path)}:{no}: {line.strip()}")
+    """A dimension launched with another dimension's instantiation fails here before it reaches a GPU.
+
+    ``case N:`` followed on the same line by a template argument list or an upper-case macro call whose first argument is
+    a literal: that literal is N.  Only kernels_append.hip's two tile-count tables still have such lines; every dimension
+    goes through CBO_FOR_DIM (cbo_device.h), whose helper writes N once, as the label and as D.  The macro is defined
+    once, its helper is invoked for 1..7, each once, the default binds CBO_MAX_DIM, and every use instantiates with D and
+    with no literal."""
+    checked, wrong = {}, []
+    for name, text in csrc_sources():
+        for no, line in enumerate(text.splitlines(), 1):
+            hit = CASE.match(line)
+            if not hit:
+                continue
+            args = TEMPLATE_ARG.findall(hit.group(2)) + MACRO_ARG.findall(hit.group(2))
+            if not args:
+                continue
+            checked[name] = checked.get(name, 0) + 1
+            if any(int(a) != int(hit.group(1)) for a in args):
+                wrong.append(f"{name}:{no}: {line.strip()}")
     assert not wrong, "\n".join(wrong)
-    assert checked >= 90, checked          # the scan still sees the launchers (97 lines when this was written)
+    assert checked == {"kernels_append.hip": 6}, checked     # (switch (kp / 16): a tile count, not a dimension)
+
+    defines, uses = {}, []
+    for name, text in csrc_sources():
+        text = COMMENT.sub("", text)
+        for hit in DEFINE.finditer(text):
+            defines.setdefault(hit.group(1), []).append(hit.group(0))
+        rest = DEFINE.sub(lambda m: "\n" * m.group(0).count("\n"), text)       # (line numbers stay)
+        uses += [(f"{name}:{no}", d, body) for no, d, body in dispatch_uses(rest)]
+    assert {k: len(v) for k, v in defines.items()} == {"CBO_FOR_DIM": 1, "CBO_FOR_DIM_CASE": 1}, defines
+    helper = " ".join(defines["CBO_FOR_DIM_CASE"][0].replace("\\\n", " ").split())
+    assert helper == "#define CBO_FOR_DIM_CASE(N, ...) case N: { constexpr int D = N; __VA_ARGS__; } break;", helper
+    macro = " ".join(defines["CBO_FOR_DIM"][0].replace("\\\n", " ").split())
+    cases = "".join(f" CBO_FOR_DIM_CASE({n}, __VA_ARGS__)" for n in range(1, 8))
+    assert macro == ("#define CBO_FOR_DIM(d, ...) switch (d) {" + cases +
+                     " default: { constexpr int D = CBO_MAX_DIM; __VA_ARGS__; } break; }"), macro
+
+    assert len(uses) >= 13, [u[0] for u in uses]
+    for where, d, body in uses:
+        assert d, where
+        assert D_ARG.search(body), f"{where}: the body does not instantiate with D: {body.strip()}"
+        assert not (TEMPLATE_ARG.search(body) or MACRO_ARG.search(body)), f"{where}: a literal instantiation: {body.strip()}"
