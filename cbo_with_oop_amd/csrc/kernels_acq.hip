@@ -10,18 +10,16 @@
 //   numpy.argmax)                             /root/reference/src/utils_functions/causal_optimizer.py:52-55
 // HBM-bound and tiny next to the TRSM: 2-4 doubles in, up to 3 out per candidate.  The arg-max is a
 // wavefront shuffle reduction, one partial per workgroup, then one 256-thread finishing block.
-#include "cbo_device.h"
+#include "acq_pass.h"
 
 #pragma clang fp contract(off)
 
 namespace cbo {
 
-// Two consecutive candidates per lane and iteration (16-byte loads and stores), the next iteration's operands requested
-// before this one's arithmetic: with one candidate per lane and the load at the top of the loop body the pass was bound by
-// memory LATENCY -- 32 KB in flight per CU -- and ran at 0.29 of the HBM roofline whatever the arithmetic cost (round 5: halving
-// the transcendental work changed nothing until the loads were decoupled).
+// The EI pass: acq_pass (acq_pass.h; its comments say why the loop has the shape it has) scored by acquisition_of.
 // CAUSAL: the candidates carry a prior mean / variance; MV: mean and / or variance are written out (the plain sweep asks for
-// neither: 24 registers less, one more wave per SIMD)
+// neither: 24 registers less, one more wave per SIMD).  p.want_ei == 0 (uniform) is cbo_gp_predict's form: the posterior
+// alone, no scoring, no arg-max.
 template <bool CAUSAL, bool MV>
 __global__ __launch_bounds__(256) void acq_kernel(const double *__restrict__ q, const double *__restrict__ mu,
                                                   const double *__restrict__ pm, const double *__restrict__ pv,
@@ -33,105 +31,14 @@ __global__ __launch_bounds__(256) void acq_kernel(const double *__restrict__ q, 
     double bv = -INFINITY;
     int64_t bi = kNoIndex;
     if (p.y_best_dev) p.y_best = *p.y_best_dev;                  // (uniform) cbo_acq_sweep_batch: the incumbent lives on the device
-    constexpr bool causal = CAUSAL;
     if (!MV) { mean_out = nullptr; var_out = nullptr; }
-    const int64_t stride = 2 * (int64_t)gridDim.x * blockDim.x;
-    // the workgroup's first candidate of an iteration is uniform (scalar registers), the lane's share of the address a constant
-    // 16 tid bytes: every load and store is "scalar base + 32-bit lane offset" and the loop advances scalars only
-    int64_t cu = 2 * (int64_t)blockIdx.x * blockDim.x;
-    const unsigned lane2 = 2 * threadIdx.x;
-    const int64_t span = 2 * (int64_t)blockDim.x;
-    // operands of the pair at cu + lane2 (the second of an odd tail: a copy of the first, never stored)
-    auto fetch = [&](int64_t base, d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2) __attribute__((always_inline)) {
-        if (base + span <= m) {                                  // (uniform) every lane has its two candidates
-            q2 = *reinterpret_cast<const d2 *>(q + base + lane2);
-            mu2 = *reinterpret_cast<const d2 *>(mu + base + lane2);
-            if (causal) {
-                pm2 = *reinterpret_cast<const d2 *>(pm + base + lane2);
-                pv2 = *reinterpret_cast<const d2 *>(pv + base + lane2);
-            }
-            return;
-        }
-        const int64_t at = base + lane2;
-        if (at + 1 < m) {
-            q2 = *reinterpret_cast<const d2 *>(q + at);
-            mu2 = *reinterpret_cast<const d2 *>(mu + at);
-            if (causal) {
-                pm2 = *reinterpret_cast<const d2 *>(pm + at);
-                pv2 = *reinterpret_cast<const d2 *>(pv + at);
-            }
-        } else if (at < m) {
-            q2 = d2{q[at], q[at]};
-            mu2 = d2{mu[at], mu[at]};
-            if (causal) {
-                pm2 = d2{pm[at], pm[at]};
-                pv2 = d2{pv[at], pv[at]};
-            }
-        }
+    // (one candidate after the other: the two in lockstep -- shared coefficients, independent chains -- needed selects
+    // where this takes branches, 190 instead of 160 vector instructions per candidate, and 14 more registers: 113 us
+    // against 107 at 2^24 candidates, profiles/r05_ei_pass_ab.txt)
+    auto score = [&](d2 mean2, d2 var2) {
+        return d2{acquisition_of(mean2[0], var2[0], p), acquisition_of(mean2[1], var2[1], p)};
     };
-    auto store = [&](int64_t base, const d2 &mean2, const d2 &var2, const d2 &acq2) __attribute__((always_inline)) {
-        const int64_t c = base + lane2;
-        if (base + span <= m) {                                  // (uniform)
-            if (mean_out) *reinterpret_cast<d2 *>(mean_out + base + lane2) = mean2;
-            if (var_out) *reinterpret_cast<d2 *>(var_out + base + lane2) = var2;
-            if (p.want_ei && acq_out) *reinterpret_cast<d2 *>(acq_out + base + lane2) = acq2;
-        } else if (c + 1 < m) {
-            if (mean_out) *reinterpret_cast<d2 *>(mean_out + c) = mean2;
-            if (var_out) *reinterpret_cast<d2 *>(var_out + c) = var2;
-            if (p.want_ei && acq_out) *reinterpret_cast<d2 *>(acq_out + c) = acq2;
-        } else if (c < m) {
-            if (mean_out) mean_out[c] = mean2[0];
-            if (var_out) var_out[c] = var2[0];
-            if (p.want_ei && acq_out) acq_out[c] = acq2[0];
-        }
-    };
-    // Every memory operation of an iteration is issued in one place, right behind the iteration's only wait: the operands of
-    // the NEXT iteration and the results of the PREVIOUS one.  Loads and stores share one counter on gfx9 and the compiler
-    // waits for zero whenever both kinds are pending -- with the stores at the end of the body and the loads at its top (the
-    // form this loop had until round 5) that wait sat right behind the freshly issued prefetch and took its whole latency,
-    // every iteration, plus the stores': the pass ran at "memory floor + arithmetic" (77 + 48 us at 2^24 candidates) instead
-    // of the larger of the two.  Now whatever the wait covers was issued a whole iteration of arithmetic earlier.
-    d2 qn = {0.0, 0.0}, mun = {0.0, 0.0}, pmn = {0.0, 0.0}, pvn = {0.0, 0.0};
-    d2 mean_done = {0.0, 0.0}, var_done = {0.0, 0.0}, acq_done = {0.0, 0.0};
-    fetch(cu, qn, mun, pmn, pvn);
-    for (int64_t done = -1; cu < m; done = cu, cu += stride) {
-        d2 q2 = qn, mu2 = mun, pm2 = pmn, pv2 = pvn;
-        // (the operands are in their registers before anything below is issued; nothing memory moves across this line)
-        asm volatile("" : "+v"(q2), "+v"(mu2), "+v"(pm2), "+v"(pv2) : : "memory");
-        if (done >= 0) store(done, mean_done, var_done, acq_done);
-        fetch(cu + stride, qn, mun, pmn, pvn);
-        const bool full = cu + span <= m;                        // uniform
-        const int64_t c = cu + lane2;
-        const bool one = full || c < m, two = full || c + 1 < m;
-        d2 mean2, var2, acq2 = {0.0, 0.0};
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            double mean, var;
-            posterior_of(q2[e], mu2[e], causal ? pm2[e] : 0.0, causal ? pv2[e] : 0.0, causal, p, mean, var);
-            mean2[e] = mean;
-            var2[e] = var;
-        }
-        if (p.want_ei) {
-            // (one candidate after the other: the two in lockstep -- shared coefficients, independent chains -- needed selects
-            // where this takes branches, 190 instead of 160 vector instructions per candidate, and 14 more registers: 113 us
-            // against 107 at 2^24 candidates, profiles/r05_ei_pass_ab.txt)
-            acq2[0] = acquisition_of(mean2[0], var2[0], p);
-            acq2[1] = acquisition_of(mean2[1], var2[1], p);
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const double acq = acq2[e];
-                const int64_t gi = c + e + index_offset;
-                // (a candidate below the lane's best cannot win: better() is only asked when it is not -- one compare on the
-                // usual path instead of better()'s NaN classification of both sides)
-                if ((e == 0 ? one : two) && !(acq < bv) && better(acq, gi, bv, bi)) { bv = acq; bi = gi; }
-            }
-        }
-        mean_done = mean2;
-        var_done = var2;
-        acq_done = acq2;
-    }
-    // (cu has run past m by whole strides: the last iteration's results, if there was one)
-    if (cu - stride >= 2 * (int64_t)blockIdx.x * blockDim.x) store(cu - stride, mean_done, var_done, acq_done);
+    acq_pass<CAUSAL>(q, mu, pm, pv, m, p, p.want_ei != 0, mean_out, var_out, acq_out, index_offset, score, bv, bi);
     if (p.want_ei) block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
 }
 

@@ -11,7 +11,7 @@
 // acq_kernel forms them (kernels_acq.hip); the EI term is that kernel's acquisition_of at cost 1.
 // HBM-bound like the EI pass: 2 doubles in per model and candidate (4 for a causal one), nothing out but the workgroup's
 // arg-max partial unless per-candidate outputs are asked for.
-#include "cbo_device.h"
+#include "acq_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -19,12 +19,11 @@ namespace cbo {
 
 // (one constraint's term: feasibility_of, cbo_device.h -- shared with the probability of improvement, kernels_pointwise.hip)
 
-// acq_kernel's structure (kernels_acq.hip; its comments say why): two consecutive candidates per lane and step (16-byte
-// loads and stores), addresses "scalar base + 32-bit lane offset", and every memory operation of a step issued in one place
-// right behind the step's only wait.  A step here is ONE model's term of one pair of candidates: the operands it prefetches
-// are the next model's (the first model's of the workgroup's next pair after the last), the result it stores the previous
-// step's -- so the registers hold two models' operands whatever the number of models, and the loop over the models has a
-// uniform trip count with the table in the kernel arguments (scalar loads).
+// acq_pass's discipline (acq_pass.h; its comments say why) with its fetch_pair / store_pair, but a loop of its own: a step
+// here is ONE model's term of one pair of candidates.  The operands it prefetches are the next model's (the first model's
+// of the workgroup's next pair after the last), the result it stores the previous step's -- so the registers hold two
+// models' operands whatever the number of models, and the loop over the models has a uniform trip count with the table in
+// the kernel arguments (scalar loads).
 // CAUSAL: some model's candidates carry a prior mean / variance (the others skip those loads: uniform); OUT: per-candidate
 // results are written (acq, and each model's own term where its `out` is set).  The common call asks for neither.
 template <bool CAUSAL, bool OUT>
@@ -36,46 +35,13 @@ __global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64
     int64_t bi = kNoIndex;
     if (!OUT) acq_out = nullptr;
     const int nm = p.n_models;
-    const int64_t stride = 2 * (int64_t)gridDim.x * blockDim.x;
-    int64_t cu = 2 * (int64_t)blockIdx.x * blockDim.x;
+    const int64_t stride = 2 * (int64_t)gridDim.x * kPassThreads;
+    int64_t cu = 2 * (int64_t)blockIdx.x * kPassThreads;
     const unsigned lane2 = 2 * threadIdx.x;
-    const int64_t span = 2 * (int64_t)blockDim.x;
-    // operands of the pair at base + lane2 for one model (the second of an odd tail: a copy of the first, never stored)
+    const int64_t span = 2 * kPassThreads;
+    // one model's operands; whether it carries a prior is decided per model (uniform)
     auto fetch = [&](const ConModel &md, int64_t base, d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2) __attribute__((always_inline)) {
-        const double *__restrict__ q = md.q, *__restrict__ mu = md.mu, *__restrict__ pm = md.pm, *__restrict__ pv = md.pv;
-        const bool causal = CAUSAL && pv != nullptr;             // (uniform)
-        if (base + span <= m) {                                  // (uniform) every lane has its two candidates
-            q2 = *reinterpret_cast<const d2 *>(q + base + lane2);
-            mu2 = *reinterpret_cast<const d2 *>(mu + base + lane2);
-            if (causal) {
-                pm2 = *reinterpret_cast<const d2 *>(pm + base + lane2);
-                pv2 = *reinterpret_cast<const d2 *>(pv + base + lane2);
-            }
-            return;
-        }
-        const int64_t at = base + lane2;
-        if (at + 1 < m) {
-            q2 = *reinterpret_cast<const d2 *>(q + at);
-            mu2 = *reinterpret_cast<const d2 *>(mu + at);
-            if (causal) {
-                pm2 = *reinterpret_cast<const d2 *>(pm + at);
-                pv2 = *reinterpret_cast<const d2 *>(pv + at);
-            }
-        } else if (at < m) {
-            q2 = d2{q[at], q[at]};
-            mu2 = d2{mu[at], mu[at]};
-            if (causal) {
-                pm2 = d2{pm[at], pm[at]};
-                pv2 = d2{pv[at], pv[at]};
-            }
-        }
-    };
-    auto store = [&](double *__restrict__ dst, int64_t base, const d2 &v) __attribute__((always_inline)) {
-        if (!dst) return;                                        // (uniform)
-        const int64_t c = base + lane2;
-        if (base + span <= m) *reinterpret_cast<d2 *>(dst + base + lane2) = v;       // (uniform)
-        else if (c + 1 < m) *reinterpret_cast<d2 *>(dst + c) = v;
-        else if (c < m) dst[c] = v[0];
+        fetch_pair(md.q, md.mu, md.pm, md.pv, CAUSAL && md.pv != nullptr, m, base, q2, mu2, pm2, pv2);
     };
     AcqParams ap;                                                // the fields posterior_of / acquisition_of read, per model
     ap.y_best = p.y_best; ap.ei_jitter = p.ei_jitter; ap.cost = 1.0;
@@ -94,12 +60,10 @@ __global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64
         for (int k = 0; k < nm; ++k) {
             const ConModel &md = p.mdl[k];
             d2 q2 = qn, mu2 = mun, pm2 = pmn, pv2 = pvn;
-            // (the operands are in their registers before anything below is issued; nothing memory moves across this line)
-            if (CAUSAL) asm volatile("" : "+v"(q2), "+v"(mu2), "+v"(pm2), "+v"(pv2) : : "memory");
-            else asm volatile("" : "+v"(q2), "+v"(mu2) : : "memory");
+            operand_fence<CAUSAL>(q2, mu2, pm2, pv2);
             if (OUT) {
-                store(term_dst, term_base, term_done);
-                if (acq_base >= 0) store(acq_out, acq_base, acq_done);
+                store_pair<1>({term_dst}, {term_done}, m, term_base);
+                if (acq_base >= 0) store_pair<1>({acq_out}, {acq_done}, m, acq_base);
                 acq_base = -1;
             }
             const bool last = k + 1 == nm;
@@ -140,17 +104,13 @@ __global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64
             acc[0] = acc[0] / p.cost;                            // IEEE division (emukit's Quotient is numpy's)
             acc[1] = acc[1] / p.cost;
         }
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const double acq = acc[e];
-            const int64_t gi = c + e + index_offset;
-            if ((e == 0 ? one : two) && !(acq < bv) && better(acq, gi, bv, bi)) { bv = acq; bi = gi; }
-        }
+        lane_argmax(one, acc[0], c + index_offset, bv, bi);
+        lane_argmax(two, acc[1], c + 1 + index_offset, bv, bi);
         if (OUT) { acq_done = acc; acq_base = cu; }
     }
     if (OUT) {
-        store(term_dst, term_base, term_done);
-        if (acq_base >= 0) store(acq_out, acq_base, acq_done);
+        store_pair<1>({term_dst}, {term_done}, m, term_base);
+        if (acq_base >= 0) store_pair<1>({acq_out}, {acq_done}, m, acq_base);
     }
     block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
 }

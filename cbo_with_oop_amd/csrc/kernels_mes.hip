@@ -8,7 +8,7 @@
 //   update_parameters():  _fit_gumbel's three scipy.optimize.bisect calls on
 //                         probf(x) = 1 - exp(sum_i log_ndtr(-(x - fmean_i) / fsd_i))
 // mean and variance come from q = sum V^2, mu = V^T z exactly as acq_kernel forms them (kernels_acq.hip).
-#include "cbo_device.h"
+#include "acq_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -16,10 +16,9 @@ namespace cbo {
 
 // (mes_term / mes_of, the epilogue, are cbo_device.h's: the multi-set sweep of kernels_sets.hip shares them)
 
-// acq_kernel's structure (kernels_acq.hip): two consecutive candidates per lane and iteration, the next iteration's operands
-// and the previous one's results issued together right behind the iteration's only wait.  Unlike the EI pass this one is
-// bound by fp64 arithmetic (about a hundred vector instructions per sample), not by HBM; the two candidates of a lane are
-// scored one after the other (one copy of the sample loop).
+// acq_pass (acq_pass.h) scored by mes_of.  Unlike the EI pass this one is bound by fp64 arithmetic (about a hundred vector
+// instructions per sample), not by HBM; the two candidates of a lane are scored one after the other (one copy of the sample
+// loop).
 template <bool CAUSAL, bool MV>
 __global__ __launch_bounds__(256) void mes_acq_kernel(const double *__restrict__ q, const double *__restrict__ mu,
                                                       const double *__restrict__ pm, const double *__restrict__ pv,
@@ -30,93 +29,20 @@ __global__ __launch_bounds__(256) void mes_acq_kernel(const double *__restrict__
 {
     double bv = -INFINITY;
     int64_t bi = kNoIndex;
-    constexpr bool causal = CAUSAL;
     if (!MV) { mean_out = nullptr; var_out = nullptr; }
     AcqParams ap;                                                    // the posterior epilogue's fields of the EI pass
     ap.variance = p.variance; ap.noise_var = p.noise_var; ap.y_best = 0.0; ap.ei_jitter = 0.0; ap.cost = 1.0;
     ap.task = CBO_TASK_MIN; ap.include_noise = 1; ap.want_ei = 0;
-    const int64_t stride = 2 * (int64_t)gridDim.x * blockDim.x;
-    int64_t cu = 2 * (int64_t)blockIdx.x * blockDim.x;
-    const unsigned lane2 = 2 * threadIdx.x;
-    const int64_t span = 2 * (int64_t)blockDim.x;
-    auto fetch = [&](int64_t base, d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2) __attribute__((always_inline)) {
-        if (base + span <= m) {                                      // (uniform) every lane has its two candidates
-            q2 = *reinterpret_cast<const d2 *>(q + base + lane2);
-            mu2 = *reinterpret_cast<const d2 *>(mu + base + lane2);
-            if (causal) {
-                pm2 = *reinterpret_cast<const d2 *>(pm + base + lane2);
-                pv2 = *reinterpret_cast<const d2 *>(pv + base + lane2);
-            }
-            return;
-        }
-        const int64_t at = base + lane2;
-        if (at + 1 < m) {
-            q2 = *reinterpret_cast<const d2 *>(q + at);
-            mu2 = *reinterpret_cast<const d2 *>(mu + at);
-            if (causal) {
-                pm2 = *reinterpret_cast<const d2 *>(pm + at);
-                pv2 = *reinterpret_cast<const d2 *>(pv + at);
-            }
-        } else if (at < m) {
-            q2 = d2{q[at], q[at]};
-            mu2 = d2{mu[at], mu[at]};
-            if (causal) {
-                pm2 = d2{pm[at], pm[at]};
-                pv2 = d2{pv[at], pv[at]};
-            }
-        }
-    };
-    auto store = [&](int64_t base, const d2 &mean2, const d2 &var2, const d2 &acq2) __attribute__((always_inline)) {
-        const int64_t c = base + lane2;
-        if (base + span <= m) {                                      // (uniform)
-            if (mean_out) *reinterpret_cast<d2 *>(mean_out + base + lane2) = mean2;
-            if (var_out) *reinterpret_cast<d2 *>(var_out + base + lane2) = var2;
-            if (acq_out) *reinterpret_cast<d2 *>(acq_out + base + lane2) = acq2;
-        } else if (c + 1 < m) {
-            if (mean_out) *reinterpret_cast<d2 *>(mean_out + c) = mean2;
-            if (var_out) *reinterpret_cast<d2 *>(var_out + c) = var2;
-            if (acq_out) *reinterpret_cast<d2 *>(acq_out + c) = acq2;
-        } else if (c < m) {
-            if (mean_out) mean_out[c] = mean2[0];
-            if (var_out) var_out[c] = var2[0];
-            if (acq_out) acq_out[c] = acq2[0];
-        }
-    };
-    d2 qn = {0.0, 0.0}, mun = {0.0, 0.0}, pmn = {0.0, 0.0}, pvn = {0.0, 0.0};
-    d2 mean_done = {0.0, 0.0}, var_done = {0.0, 0.0}, acq_done = {0.0, 0.0};
-    fetch(cu, qn, mun, pmn, pvn);
-    for (int64_t done = -1; cu < m; done = cu, cu += stride) {
-        d2 q2 = qn, mu2 = mun, pm2 = pmn, pv2 = pvn;
-        asm volatile("" : "+v"(q2), "+v"(mu2), "+v"(pm2), "+v"(pv2) : : "memory");
-        if (done >= 0) store(done, mean_done, var_done, acq_done);
-        fetch(cu + stride, qn, mun, pmn, pvn);
-        const bool full = cu + span <= m;                            // uniform
-        const int64_t c = cu + lane2;
-        const bool one = full || c < m, two = full || c + 1 < m;
-        d2 mean2, var2, acq2;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            double mean, var;
-            posterior_of(q2[e], mu2[e], causal ? pm2[e] : 0.0, causal ? pv2[e] : 0.0, causal, ap, mean, var);
-            mean2[e] = mean;
-            var2[e] = var;
-        }
+    auto score = [&](d2 mean2, d2 var2) {
+        d2 acq2;
 #pragma unroll 1
         for (int e = 0; e < 2; ++e) {
             const double v = mes_of(e ? mean2[1] : mean2[0], e ? var2[1] : var2[0], p);
             if (e) acq2[1] = v; else acq2[0] = v;
         }
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const double acq = acq2[e];
-            const int64_t gi = c + e + index_offset;
-            if ((e == 0 ? one : two) && !(acq < bv) && better(acq, gi, bv, bi)) { bv = acq; bi = gi; }
-        }
-        mean_done = mean2;
-        var_done = var2;
-        acq_done = acq2;
-    }
-    if (cu - stride >= 2 * (int64_t)blockIdx.x * blockDim.x) store(cu - stride, mean_done, var_done, acq_done);
+        return acq2;
+    };
+    acq_pass<CAUSAL>(q, mu, pm, pv, m, ap, true, mean_out, var_out, acq_out, index_offset, score, bv, bi);
     block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
 }
 
