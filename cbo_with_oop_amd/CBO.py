@@ -105,13 +105,15 @@ class CBOAcquisitionPath:
     ``refine=True`` adds the reference's second stage (``find_next_y_points(refine=True)``): every set's
     winner is refined by L-BFGS inside the set's box from ``space_list``, all sets in one further device call, and kept only
     if it is not lower.  It needs ``"EI"`` or a point-wise kind, no constraints, no hyper-parameter samples, no batch and a
-    single process, and its ``trial_step`` takes the three-call route."""
+    single process, and its ``trial_step`` takes the three-call route.  ``device_prior=True`` (with ``refine=True``) lets
+    causal sets into that device call through a device-resident do-calculus prior."""
 
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
-                 update_incumbent=False, refine=False, hyper_sampler="host"):
-        from .utils_functions.utils import checked_refine, sets_acquisition_or_default as sets_acquisition
+                 update_incumbent=False, refine=False, hyper_sampler="host", device_prior=False):
+        from .utils_functions.utils import checked_device_prior, checked_refine, sets_acquisition_or_default as sets_acquisition
+        self.device_prior = checked_device_prior(device_prior, refine)
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
         self._kind = sets_acquisition(acquisition, acquisition_param)
@@ -310,7 +312,7 @@ class CBOAcquisitionPath:
                                       hyper_samples=None if self.hyper_samples is None else list(self.hyper_rows),
                                       spaces=self.space_list if (self._kind[0] == "MES" or self.refine) else None,
                                       batch_size=self.batch_size, update_incumbent=self.update_incumbent,
-                                      refine=self.refine)
+                                      refine=self.refine, device_prior=self.device_prior)
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -485,7 +487,9 @@ class CBO(CBOAcquisitionPath):
     ``chosen`` as ``(set, x (B, d))``; the trial's cost is the sum of the B interventions' costs.  ``None``: the reference's
     one intervention per trial.
     ``refine=True``: every set's winner is refined by L-BFGS inside the set's interventional ranges before the set is chosen
-    (``CBOAcquisitionPath(refine=True)``) -- the reference's continuous optimum instead of a grid point."""
+    (``CBOAcquisitionPath(refine=True)``) -- the reference's continuous optimum instead of a grid point.
+    ``device_prior=True`` (with ``refine=True`` and ``causal_prior=True``): the causal sets are refined inside the device launch,
+    their do-calculus priors evaluated there, instead of on the host route."""
 
     TARGET = "Y"
 
@@ -494,7 +498,7 @@ class CBO(CBOAcquisitionPath):
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
                  constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False,
-                 hyper_sampler="host"):
+                 hyper_sampler="host", device_prior=False):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType
         from .graphs import _columns
@@ -541,6 +545,8 @@ class CBO(CBOAcquisitionPath):
         checked_batch_size(batch_size, sets_acquisition(acquisition, acquisition_param), path_constraints, hyper_samples)
         checked_refine(refine, sets_acquisition(acquisition, acquisition_param), path_constraints, hyper_samples, batch_size,
                        False, [self.graph.bounds(s) for s in exploration], len(exploration))
+        if device_prior and not refine:
+            raise ValueError("device_prior=True puts causal sets into the refinement's device launch: refine must be True")
         sem = None
         if path_constraints and constraint_functions is None:
             from functools import partial
@@ -556,7 +562,8 @@ class CBO(CBOAcquisitionPath):
                          [self.graph.bounds(s) for s in exploration], grid_shapes=grid_shapes, comm=None,
                          acquisition=acquisition, acquisition_param=acquisition_param, constraints=path_constraints,
                          constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
-                         update_incumbent=update_incumbent, refine=refine, hyper_sampler=hyper_sampler)
+                         update_incumbent=update_incumbent, refine=refine, hyper_sampler=hyper_sampler,
+                         device_prior=device_prior)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions

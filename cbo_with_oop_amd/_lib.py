@@ -41,6 +41,7 @@ REFINE_KIND_CODE = dict(ACQ_KIND_CODE, EI=0)                  # cbo_acq_refine_s
 REFINE_MAX_STARTS = 64       # CBO_REFINE_MAX_STARTS
 REFINE_ROUNDS_LIMIT = 1000   # CBO_REFINE_ROUNDS_LIMIT
 REFINE_PGTOL, REFINE_FTOL, REFINE_STEP, REFINE_MAX_ROUNDS, REFINE_NAN_START, REFINE_DECLINED = range(6)   # CBO_REFINE_*
+DO_PRIOR_MAX_N = 1024        # CBO_DO_PRIOR_MAX_N
 HMC_MAX_PARAMS = MAX_DIM + 2   # CBO_HMC_MAX_PARAMS
 HMC_MAX_SAMPLES = 4096         # CBO_HMC_MAX_SAMPLES
 HMC_MAX_EVALS = 262144         # CBO_HMC_MAX_EVALS: the cap on num_samples * hmc_iters
@@ -191,6 +192,12 @@ SIGNATURES = {
     "cbo_acq_refine_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), ctypes.c_int, c_double_p,
                                            ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                            c_int_p, c_int_p]),
+    "cbo_acq_refine_sets_prior": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), c_void_pp, ctypes.c_int,
+                                                 c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p,
+                                                 c_double_p, c_int_p, c_int_p]),
+    "cbo_do_prior_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int, c_int_p, c_void_pp]),
+    "cbo_do_prior_destroy": (None, [ctypes.c_void_p]),
+    "cbo_do_prior_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_hmc_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboHmcChain), c_int_p]),
     "cbo_gp_mes_gumbel_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_double_p]),

@@ -2660,14 +2660,25 @@ extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cand
         });
 }
 
+// a device-resident do-calculus prior (cbo_do_prior_create, below)
+struct cbo_do_prior {
+    cbo_ctx *ctx = nullptr;
+    DoPriorView h{};                 // the view as the host filled it
+    double *mem = nullptr;           // w | M | xi, one allocation
+    DoPriorView *view = nullptr;     // the same view on the device
+};
+
 // ---- gradient refinement of every set's starts (kernels_sets_refine.hip) -----------------------------------
 // One launch for every set the kernel takes (small_sweep_model, no prior); the others are declined here, their status
 // entries alone written.  The models are only read.  Of the routing policy this call shares the partition alone: it has no
 // general path (a set the launch declines is declined), and its outputs come back behind a memset of the status words and a
 // stream synchronisation, not through polled records.
-extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int kind, const double *y_best,
-                                   int task, double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
-                                   int *rounds_out, int *status_out)
+// priors: NULL, or per set NULL or the do-calculus prior of the set's causal model -- such a set joins the
+// kernel's causal instantiation: the sets without a prior come first in the descriptor arrays and go to one launch, the
+// sets with one to a second launch on the same stream.
+static int refine_sets_impl(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, const cbo_do_prior *const *priors,
+                            int kind, const double *y_best, int task, double param, int max_rounds, double *x_out,
+                            double *val_out, double *grad_out, int *rounds_out, int *status_out)
 {
     if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
     if (!gps || !sets || !y_best || !x_out || !val_out || !grad_out || !rounds_out || !status_out)
@@ -2706,9 +2717,18 @@ extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_ref
         for (int64_t e = 0; e < (int64_t)rs.k * d; ++e)
             if (!std::isfinite(rs.starts[e])) return fail(CBO_ERR_INVALID, "the starts must be finite" + where);
         if (kind == kEiKind && !std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite" + where);
+        if (priors && priors[i]) {
+            if (priors[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "a prior lives on another context" + where);
+            if (gps[i]->X.sv == nullptr)
+                return fail(CBO_ERR_INVALID, "a do-calculus prior was given for a model without a prior of its own" + where);
+            if (priors[i]->h.n_iv != d)
+                return fail(CBO_ERR_INVALID, "the prior's n_iv (" + std::to_string(priors[i]->h.n_iv) +
+                                                 ") differs from the model's d (" + std::to_string(d) + ")" + where);
+        }
     }
     cbo_ctx *c = gps[0]->ctx;
     HIP_TRY(hipSetDevice(c->device));
+    auto prior_of = [&](int i) -> const cbo_do_prior * { return priors ? priors[i] : nullptr; };
     // where each set's rows begin in the caller's arrays; which sets the launch takes
     std::vector<int64_t> row_off((size_t)n_sets);
     std::vector<int> out_off((size_t)n_sets), small;
@@ -2720,7 +2740,9 @@ extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_ref
         rows += (int64_t)sets[i].k * gps[i]->d;
         outs += sets[i].k;
     }
-    const int blocks = partition_small(n_sets, [&](int i) { return small_sweep_model(gps[i]) && gps[i]->X.sv == nullptr; },
+    const int blocks = partition_small(n_sets, [&](int i) {
+                                           return small_sweep_model(gps[i]) && (gps[i]->X.sv == nullptr || prior_of(i) != nullptr);
+                                       },
                                        [&](int i) {
                                            const int per = small_refine_starts_per_block(gps[i]->d);
                                            return (int64_t)((sets[i].k + per - 1) / per);
@@ -2742,6 +2764,10 @@ extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_ref
     if (rc == CBO_OK) rc = grow(c, c->refine_rounds, (size_t)outs);
     if (rc == CBO_OK) rc = grow(c, c->refine_status, (size_t)outs);
     if (rc != CBO_OK) return rc;
+    // the launch's order: the sets without a prior, then the sets with one (each group in the caller's order)
+    std::stable_partition(small.begin(), small.end(), [&](int i) { return prior_of(i) == nullptr; });
+    int n_plain = 0;
+    while (n_plain < ns && prior_of(small[(size_t)n_plain]) == nullptr) ++n_plain;
     for (int j = 0; j < ns; ++j) {
         const int i = small[(size_t)j];
         const cbo_gp *g = gps[i];
@@ -2761,13 +2787,20 @@ extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_ref
         }
         rf.row_off = row_off[(size_t)i]; rf.out_off = out_off[(size_t)i];
         rf.k = sets[i].k; rf.ard = g->h.ard;
+        rf.prior = prior_of(i) ? prior_of(i)->view : nullptr;
         std::memcpy(c->refine_starts.p + rf.row_off, sets[i].starts, sizeof(double) * (size_t)rf.k * (size_t)g->d);
         for (int s = 0; s < rf.k; ++s) c->refine_status[rf.out_off + s] = CBO_REFINE_DECLINED;
     }
     HIP_TRY(hipMemsetAsync(c->refine_info, 0, sizeof(int) * (size_t)ns, c->stream));
-    launch_small_sets_refine(c->stream, kind, c->sets_host, c->refine_host, c->refine_starts, ns, blocks, c->small_scratch,
-                             c->refine_info, max_rounds, c->refine_x, c->refine_val, c->refine_grad, c->refine_rounds,
-                             c->refine_status);
+    if (n_plain > 0)
+        launch_small_sets_refine(c->stream, kind, false, c->sets_host, c->refine_host, c->refine_starts, n_plain, blocks,
+                                 c->small_scratch, c->refine_info, max_rounds, c->refine_x, c->refine_val, c->refine_grad,
+                                 c->refine_rounds, c->refine_status);
+    if (ns > n_plain)
+        launch_small_sets_refine(c->stream, kind, true, c->sets_host.p + n_plain, c->refine_host.p + n_plain, c->refine_starts,
+                                 ns - n_plain, blocks, c->small_scratch.p + small_sets_scratch_doubles(n_plain, blocks),
+                                 c->refine_info.p + n_plain, max_rounds, c->refine_x, c->refine_val, c->refine_grad,
+                                 c->refine_rounds, c->refine_status);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int j = 0; j < ns; ++j) {
@@ -2786,6 +2819,23 @@ extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_ref
         }
     }
     return CBO_OK;
+}
+
+extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int kind, const double *y_best,
+                                   int task, double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
+                                   int *rounds_out, int *status_out)
+{
+    return refine_sets_impl(n_sets, gps, sets, nullptr, kind, y_best, task, param, max_rounds, x_out, val_out, grad_out,
+                            rounds_out, status_out);
+}
+
+extern "C" int cbo_acq_refine_sets_prior(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets,
+                                         const cbo_do_prior *const *priors, int kind, const double *y_best, int task,
+                                         double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
+                                         int *rounds_out, int *status_out)
+{
+    return refine_sets_impl(n_sets, gps, sets, priors, kind, y_best, task, param, max_rounds, x_out, val_out, grad_out,
+                            rounds_out, status_out);
 }
 
 // ---- constrained acquisition for every set of a trial (kernels_sets_con.hip) ------------------------------
@@ -4331,6 +4381,143 @@ extern "C" int cbo_gp_predict_do(cbo_gp *g, int64_t m, int64_t n_obs, const doub
     rc = posterior_of_set(g, k, include_noise);
     if (rc != CBO_OK) return rc;
     return group_means_out(c, m, n_obs, mean_out, var_out);
+}
+
+// ---- the device-resident do-calculus prior (kernels_do_prior.hip) ----------------------------------------
+// Preparation, once per handle: W = L^-1 from the identity right-hand sides through the strip kernel (as cbo_gp_loo has it)
+// in the V workspace, b in the W workspace (k-major, V's leading dimension), Ky^-1 = W^T W and b^T b on the joint
+// posterior's tile loop with the element-wise product as the second product's epilogue, w from b's column means and alpha.
+extern "C" int cbo_do_prior_create(cbo_gp *g, int64_t n_obs, const double *observed, int n_iv, const int *iv_index,
+                                   cbo_do_prior **out)
+{
+    if (!g || !observed || !iv_index || !out) return fail(CBO_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (n_obs <= 0) return fail(CBO_ERR_INVALID, "n_obs must be positive");
+    if (n_iv <= 0 || n_iv > CBO_MAX_DIM) return fail(CBO_ERR_INVALID, "n_iv must be in 1.." + std::to_string(CBO_MAX_DIM));
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    int n_col = 0;
+    for (int j = 0; j < g->d; ++j) {
+        if (iv_index[j] >= n_iv) return fail(CBO_ERR_INVALID, "intervened_index refers to a column values does not have");
+        n_col += iv_index[j] >= 0 ? 1 : 0;
+    }
+    if (n_col == 0) return fail(CBO_ERR_INVALID, "no column is intervened");
+    if (g->dtype != CBO_DTYPE_F64) return fail(CBO_ERR_UNSUPPORTED, "do-calculus prior: an fp32 graph gp is not supported");
+    if (g->X.sv != nullptr)
+        return fail(CBO_ERR_UNSUPPORTED, "do-calculus prior: a causal graph gp (it has a prior of its own) is not supported");
+    if (g->n > kDoPriorMaxN)
+        return fail(CBO_ERR_UNSUPPORTED, "do-calculus prior: the graph gp has " + std::to_string(g->n) + " rows, more than CBO_DO_PRIOR_MAX_N = " +
+                                             std::to_string(kDoPriorMaxN));
+    if (g->tries != 0 || g->jitter != 0.0)
+        return fail(CBO_ERR_UNSUPPORTED, "do-calculus prior: the graph gp needed jitchol's jitter");
+    const double sn = g->noise_var + kGpyDiagJitter;
+    if (!(sn / ((double)g->n * g->h.variance + sn) >= 0x1p-26))
+        return fail(CBO_ERR_UNSUPPORTED, "do-calculus prior: the clip rule -- sn / (n_g sigma^2 + sn) is below 2^-26 (noise too "
+                                         "small for the factored variance to stay clear of GPy's clip)");
+    cbo_ctx *c = g->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_alpha(g);
+    if (rc != CBO_OK) return rc;
+    const int64_t n_pad = g->n_pad, rows_pad = round_up(n_obs, 16);
+    int64_t chunk = 0, ldv = 0;
+    rc = ensure_workspaces(c, n_pad, n_pad, &chunk, &ldv);
+    if (rc != CBO_OK) return rc;
+    if (chunk < n_pad) return fail(CBO_ERR_UNSUPPORTED, "do-calculus prior: the workspace (CBO_HIP_WORKSPACE_MB) does not hold L^-1");
+    rc = grow(c, c->W, (size_t)rows_pad * (size_t)ldv);
+    if (rc == CBO_OK) rc = grow(c, c->export_buf, (size_t)(n_obs * g->d));
+    if (rc != CBO_OK) return rc;
+
+    cbo_do_prior *p = new cbo_do_prior();
+    p->ctx = c;
+    const size_t doubles = (size_t)n_pad + (size_t)n_pad * (size_t)n_pad + (size_t)n_col * (size_t)n_pad;
+    auto bail = [&](int code) {
+        if (p->mem) (void)hipFree(p->mem);
+        if (p->view) (void)hipFree(p->view);
+        delete p;
+        return code;
+    };
+#define PRIOR_TRY(expr)                                                                                     \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) {                                                                             \
+            (void)hipGetLastError();                                                                        \
+            return bail(fail(CBO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)));              \
+        }                                                                                                   \
+    } while (0)
+    PRIOR_TRY(hipMalloc(&p->mem, sizeof(double) * doubles));
+    PRIOR_TRY(hipMalloc(&p->view, sizeof(DoPriorView)));
+    double *w = p->mem, *M = w + n_pad, *xi = M + (size_t)n_pad * (size_t)n_pad;
+    DoPriorView &h = p->h;
+    h.w = w; h.M = M; h.xi = xi; h.ldm = n_pad; h.ldx = n_pad;
+    h.inv_l2 = 1.0 / (g->h.lengthscale * g->h.lengthscale);
+    h.vmax = g->h.variance + g->noise_var;
+    h.n = (int)g->n; h.n_col = n_col; h.n_iv = n_iv; h.ard = g->h.ard;
+    DoPriorRowsArgs ra{};
+    ra.obs = c->export_buf; ra.xs = g->X.xs; ra.b = c->W;
+    ra.n_obs = n_obs; ra.rows_pad = rows_pad; ra.ldb = ldv; ra.ldx = g->X.ld;
+    ra.inv_l2 = h.inv_l2; ra.n = (int)g->n; ra.d = g->d; ra.ard = g->h.ard;
+    for (int k = 0; k < CBO_MAX_DIM; ++k) { h.ls[k] = 1.0; h.src[k] = 0; ra.ls[k] = 1.0; ra.col[k] = 0; }
+    for (int j = 0, ki = 0, kf = 0; j < g->d; ++j) {
+        const double l = g->h.ard ? g->ls[(size_t)j] : 1.0;
+        if (iv_index[j] >= 0) {
+            h.ls[ki] = l; h.src[ki] = iv_index[j];
+            PRIOR_TRY(hipMemcpyAsync(xi + (size_t)ki * (size_t)n_pad, g->X.xs + (int64_t)j * g->X.ld, sizeof(double) * (size_t)g->n,
+                                     hipMemcpyDeviceToDevice, c->stream));
+            ++ki;
+        } else {
+            ra.ls[kf] = l; ra.col[kf] = j;
+            ++kf;
+        }
+        ra.n_free = kf;
+    }
+    PRIOR_TRY(hipMemcpyAsync(c->export_buf, observed, sizeof(double) * (size_t)(n_obs * g->d), hipMemcpyHostToDevice, c->stream));
+    PRIOR_TRY(hipMemcpyAsync(p->view, &h, sizeof(DoPriorView), hipMemcpyHostToDevice, c->stream));
+    // W = L^-1: the identity through the strip kernel
+    launch_loo_identity_chunk(c->stream, c->V, ldv, n_pad, n_pad, 0);
+    launch_trsm_strips(c->stream, g->A, g->lda, g->invDt, c->V, ldv, n_pad, n_pad, nullptr, nullptr, nullptr);
+    launch_do_prior_rows(c->stream, ra);
+    launch_do_prior_weights(c->stream, c->W, ldv, n_obs, g->alpha, g->h.variance, (int)g->n, w);
+    GramArgs ga{};
+    ga.A = c->V; ga.lda = ldv; ga.n_k = (int)n_pad; ga.prev = nullptr; ga.out = M; ga.ldo = n_pad; ga.n = (int)g->n;
+    ga.divisor = 1.0; ga.scale = 1.0;
+    launch_gram_tiles(c->stream, ga);
+    ga.A = c->W; ga.n_k = (int)rows_pad; ga.prev = M; ga.divisor = (double)n_obs;
+    ga.scale = (g->h.variance * g->h.variance);
+    launch_gram_tiles(c->stream, ga);
+    PRIOR_TRY(hipGetLastError());
+    PRIOR_TRY(hipStreamSynchronize(c->stream));                // (`observed` and the view are the caller's / this frame's)
+#undef PRIOR_TRY
+    *out = p;
+    return CBO_OK;
+}
+
+extern "C" void cbo_do_prior_destroy(cbo_do_prior *p)
+{
+    if (!p) return;
+    hipSetDevice(p->ctx->device);
+    hipStreamSynchronize(p->ctx->stream);
+    hipFree(p->mem);
+    hipFree(p->view);
+    delete p;
+}
+
+extern "C" int cbo_do_prior_eval(const cbo_do_prior *p, int64_t m, const double *values, double *mean_out, double *var_out)
+{
+    if (!p || !values || !mean_out || !var_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (m <= 0) return fail(CBO_ERR_INVALID, "m must be positive");
+    cbo_ctx *c = p->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int n_iv = p->h.n_iv;
+    const size_t scratch = (size_t)do_prior_eval_blocks(m) * (size_t)kDoPriorMaxN;
+    int rc = grow(c, c->export_buf, (size_t)m * (size_t)n_iv + 2 * (size_t)m + scratch);
+    if (rc != CBO_OK) return rc;
+    double *d_val = c->export_buf, *d_mean = d_val + (size_t)m * (size_t)n_iv, *d_var = d_mean + m, *d_scr = d_var + m;
+    HIP_TRY(hipMemcpyAsync(d_val, values, sizeof(double) * (size_t)m * (size_t)n_iv, hipMemcpyHostToDevice, c->stream));
+    launch_do_prior_eval(c->stream, p->view, d_val, m, d_scr, d_mean, d_var);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(mean_out, d_mean, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(var_out, d_var, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CBO_OK;
 }
 
 // ---- tiny host-side reductions -------------------------------------------------------------------

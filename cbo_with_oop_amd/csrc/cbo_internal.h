@@ -374,15 +374,62 @@ struct cbo_small_refine {
     int variable[CBO_MAX_DIM];
     int64_t row_off;
     int k, out_off, ard, pad_;
+    const struct DoPriorView *prior;   // the do-calculus prior of a causal set on the device, else nullptr
 };
 int small_refine_starts_per_block(int d);              // 4 floor(16 / (1 + d)): a start fills 1 + d of a wave's 16 columns
 // sets / refs / starts and the five outputs may be pinned host memory; scratch: small_sets_scratch_doubles(n_sets,
 // blocks_per_set); info: n_sets ints, zero on entry, a set's word non-zero afterwards when its factorisation met a
 // non-positive pivot (the kernel then wrote CBO_REFINE_DECLINED for the set's starts and nothing else).  kind: kEiKind or
 // CBO_ACQ_*, the descriptors' scalars as for launch_small_sets; descriptors carry no candidates.  max_rounds <= 1000.
-void launch_small_sets_refine(hipStream_t s, int kind, const cbo_small_set *sets, const cbo_small_refine *refs,
+// prior: every set of the list carries one (refs[].prior) and its model is causal -- the kernel's causal instantiation;
+// false: none does.
+void launch_small_sets_refine(hipStream_t s, int kind, bool prior, const cbo_small_set *sets, const cbo_small_refine *refs,
                               const double *starts, int n_sets, int blocks_per_set, double *scratch, int *info, int max_rounds,
                               double *x_out, double *val_out, double *grad_out, int *rounds_out, int *status_out);
+// ---- the device-resident do-calculus prior (kernels_do_prior.hip, do_prior_device.h) ------------------------
+constexpr int kDoPriorMaxN = CBO_DO_PRIOR_MAX_N;   // rows of a graph GP a handle takes
+constexpr int kDoPriorGroup = 256;                 // lanes that evaluate one point together: a whole workgroup
+// What a handle keeps on the device (every pointer device memory owned by the handle).  M is symmetric to the bit, so
+// column r of it is read as row r: lanes walk the rows of M side by side.
+struct DoPriorView {
+    const double *w;                // [n]       sigma^2 alpha_i mean_r b_ri
+    const double *M;                // [n][ldm]  sigma^4 (Ky^-1 o b^T b / N_obs)
+    const double *xi;               // [n_col][ldx] the intervened columns of X_g, scaled as the kernels scale points
+    int64_t ldm, ldx;
+    double ls[CBO_MAX_DIM];         // lengthscale of intervened column k (ARD), else 1
+    double inv_l2, vmax;            // 1 / l^2 (1 for ARD); sigma^2 + sigma_n^2
+    int src[CBO_MAX_DIM];           // the column of `values` that intervened column k takes
+    int n, n_col, n_iv, ard;
+};
+// b[r][i] = exp(-1/2 sum over the n_free columns c = col[k] that are NOT intervened of ((obs[r][c] - X_g[i][c]) / l_c)^2) for
+// r < n_obs, i < n, zero elsewhere in [rows_pad][ldb]: k-major, the layout V has.  obs: raw (n_obs, d) on the device; xs:
+// the graph GP's scaled SoA points; ls[k]: lengthscale of column col[k] (ARD; the observed value is scaled as a point is).
+struct DoPriorRowsArgs {
+    const double *obs, *xs; double *b;
+    int64_t n_obs, rows_pad, ldb, ldx;
+    double ls[CBO_MAX_DIM], inv_l2;
+    int col[CBO_MAX_DIM];
+    int n, d, n_free, ard;
+};
+void launch_do_prior_rows(hipStream_t s, const DoPriorRowsArgs &a);
+// w[i] = (variance alpha[i]) (sum_r b[r][i] / n_obs), r ascending, i < n
+void launch_do_prior_weights(hipStream_t s, const double *b, int64_t ldb, int64_t n_obs, const double *alpha, double variance,
+                             int n, double *w);
+// Gram products on kernels_joint.hip's tile loop: out[i][j] = sum_{k < n_k} A[k][i] A[k][j] for i, j < n (row-major, ldo) --
+// or, with prev given (it may be out), (prev[i][j] (that sum / divisor)) scale, the element-wise product's epilogue.  A is
+// k-major [n_k rounded up to 16][lda] with at least round_up(n, 128) readable columns.
+struct GramArgs {
+    const double *A; int64_t lda; int n_k;
+    const double *prev; double *out; int64_t ldo;
+    int n;
+    double divisor, scale;
+};
+void launch_gram_tiles(hipStream_t s, GramArgs a);
+// (m, v) of m points (values: m x view->n_iv on the device) by do_prior_at, one point per workgroup and turn; scratch:
+// do_prior_eval_blocks(m) * kDoPriorMaxN doubles
+int do_prior_eval_blocks(int64_t m);
+void launch_do_prior_eval(hipStream_t s, const DoPriorView *view, const double *values, int64_t m, double *scratch,
+                          double *mean_out, double *var_out);
 // ---- every model's HMC chain over its hyper-parameters in one launch (kernels_hmc.hip) -----------------------
 // What a model's chain needs beside the model's descriptor (pinned, device-mapped: read by the kernel directly): the start,
 // the chain's shape, and where its draws (n_params x num_samples momenta, then num_samples uniforms) and its rows / accept

@@ -2,6 +2,7 @@
 //
 //     cov_tile_kernel:     C[i][j] = K(X1_i, X2_j) - sum_k V1[k][i] V2[k][j]
 //     samples_tile_kernel: F[i][j] = mu[i] + sum_{k <= i} U[k][i] Z[k][j]
+//     gram_tile_kernel:    G[i][j] = sum_k A[k][i] A[k][j]  (the do-calculus prior's two Gram products)
 //
 // with V = L^-1 K(X, .) (the sweep's solution, resident), U^T U = Sigma + jitter I (U[k][i] = L[i][k]), Z = normals^T.
 //
@@ -293,6 +294,41 @@ __global__ __launch_bounds__(256, 2) void ivr_tile_kernel(IvrArgs a)
     }
 }
 
+// gram_tile_kernel (cbo_do_prior_create): G = A^T A of one k-major operand on the same main loop, both for
+// Ky^-1 = W^T W (W = L^-1) and for b^T b; with `prev` the epilogue forms the element-wise product of the two,
+// (prev[i][j] (G[i][j] / divisor)) scale, in place.  Element (i, j) and element (j, i) are the same products summed in the
+// same order: the result is symmetric to the bit.
+__global__ __launch_bounds__(256, 2) void gram_tile_kernel(GramArgs a)
+{
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    __shared__ __align__(16) double lds[2 * kTileStage];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wr = wave >> 1, wc = wave & 1;
+    const int lc = lane & 15, kq = lane >> 4;
+    const int64_t i0 = (int64_t)ti * kTile, j0 = (int64_t)tj * kTile;
+
+    d4 acc[4][4];
+    tile_mainloop<false>(a.A + i0 + 2 * lane, a.lda, a.A + j0 + 2 * lane, a.lda, a.n_k / kTileKB, acc, lds);
+
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t gi = i0 + wr * 64 + bi * 16 + kq + 4 * r;
+            if (gi >= a.n) continue;
+#pragma unroll
+            for (int bj = 0; bj < 4; ++bj) {
+                const int64_t gj = j0 + wc * 64 + bj * 16 + lc;
+                if (gj >= a.n) continue;
+                double v = acc[bi][bj][r];
+                if (a.prev) v = __dmul_rn(__dmul_rn(a.prev[gi * a.ldo + gj], __ddiv_rn(v, a.divisor)), a.scale);
+                a.out[gi * a.ldo + gj] = v;
+            }
+        }
+}
+
 __global__ __launch_bounds__(256, 2) void samples_tile_kernel(SampArgs a)
 {
     const int t = blockIdx.x;
@@ -387,6 +423,13 @@ void launch_ivr_tiles(hipStream_t s, int d, IvrArgs a)
     const dim3 grid((unsigned)((a.p + kTile - 1) / kTile), (unsigned)((a.m + kTile - 1) / kTile));
     a.n_k = (int)round_up(a.n_k, kTileKB);
     CBO_FOR_DIM(d, hipLaunchKernelGGL(ivr_tile_kernel<D>, grid, dim3(256), 0, s, a));
+}
+
+void launch_gram_tiles(hipStream_t s, GramArgs a)
+{
+    const unsigned nt = (unsigned)((a.n + kTile - 1) / kTile);
+    a.n_k = (int)round_up(a.n_k, kTileKB);
+    hipLaunchKernelGGL(gram_tile_kernel, dim3(nt, nt), dim3(256), 0, s, a);
 }
 
 void launch_samples_tiles(hipStream_t st, SampArgs a)

@@ -14,17 +14,29 @@
 // Column 0 is a candidate's arithmetic to the bit (prep_points_kernel's scaling and |x|^2, small_kstar, the tile solve,
 // posterior_of, acquisition_of / pointwise_of<KIND>): the value reported at a point is what the multi-set sweep returns for
 // a one-point grid there.
+//
+// Causal sets (PRIOR).  A set whose model is a CausalRBF GP carries a do-calculus prior (DoPriorView): every
+// round, before the columns are formed, the whole workgroup evaluates (m, v) at the trial point of each of its running
+// starts with do_prior_at, one start after another (the owners pass their points and take the pair back through the
+// workgroup's global scratch, whose factor rows are free once the factor is in LDS).  Column 0 is then the causal k* with
+// sqrt(v) -- prep_points_kernel's sv of a candidate --, the derivative columns stay the stationary part's (GPy's
+// predictive_gradients differentiates nothing else), posterior_of takes (m, v), and d var / d x_j = -2 V_0.V_j holds with the
+// causal V_0.  The plug-in incumbent uses the model's stored priors at its own inputs, as the sweep does.  PRIOR is a
+// template flag: the instantiations without it are the kernels they were.
 #include <cstring>
 
 #include "cbo_small_device.h"
+#include "do_prior_device.h"
 #include "refine_search.h"
 
 #pragma clang fp contract(off)
 
 namespace cbo {
 
-static_assert(sizeof(SmallShared) + 128 * sizeof(double) + 4 * sizeof(double) + 4 * sizeof(int) + sizeof(double) <= 163840,
-              "the workgroup's static LDS (plug-in means and their reduction) beside SmallShared: one CU");
+static_assert(sizeof(SmallShared) + 128 * sizeof(double) + 4 * sizeof(double) + 4 * sizeof(int) + sizeof(double) +
+                      2 * (kDoPriorGroup / 64) * sizeof(double) + 256 <= 163840,
+              "the workgroup's static LDS (plug-in means and their reduction, the prior's reduction, and the 256 bytes the "
+              "resource report shows for every kind beside them) beside SmallShared: one CU");
 // The curvature rings of a workgroup's searches live in the block's lower-left quadrant (rows 64..127, columns 0..63): the
 // factor is upper triangular and the tile solve reads nothing below the diagonal tiles.  One row = one ring.
 static_assert(2 * 4 * (16 / 2) <= 64 && kRefineHistory * CBO_MAX_DIM <= 64, "one ring per row of the lower-left quadrant");
@@ -65,7 +77,12 @@ __device__ __forceinline__ double value_and_coefficients(double mean, double var
     }
 }
 
-template <int KIND, bool BYVAL>
+// the exchange area of the causal instantiations in the workgroup's scratch: a(x), then per start of the workgroup
+// [x (CBO_MAX_DIM) | running | m | v]
+constexpr int kPriorSlot = 16;
+static_assert(kDoPriorMaxN + 32 * kPriorSlot <= 128 * kSmallLd, "a(x) and the starts' slots fit the scratch factor rows");
+
+template <int KIND, bool BYVAL, bool PRIOR>
 __global__ __launch_bounds__(256) void small_sets_refine_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
                                                                 const cbo_small_refine *__restrict__ refs,
                                                                 const double *__restrict__ starts, double *scratch,
@@ -143,7 +160,36 @@ __global__ __launch_bounds__(256) void small_sets_refine_kernel(const SmallSetAr
     for (int k = 1; k < CBO_MAX_DIM; ++k) scale_j = (k == jm) ? scale[k] : scale_j;
     const double wj = rf.ard ? 1.0 / scale_j : inv_l2;
 
+    [[maybe_unused]] __shared__ double prior_red[2 * kDoPriorGroup / 64];
     for (int it = 0; it <= max_rounds; ++it) {                    // the start's own evaluation, then at most max_rounds rounds
+        // ---- a causal set: (m, v) at the trial point of every running start, the whole workgroup per start
+        double pm_c = 0.0, pv_c = 0.0;
+        if constexpr (PRIOR) {
+            double *pa = my, *px = my + kDoPriorMaxN;
+            if (owner) {
+#pragma unroll
+                for (int k = 0; k < CBO_MAX_DIM; ++k) px[slot * kPriorSlot + k] = xt[k];
+                px[slot * kPriorSlot + CBO_MAX_DIM] = refine_done(rs) ? 0.0 : 1.0;
+            }
+            __syncthreads();
+            const int here = (k_starts - blk * per_block < per_block) ? k_starts - blk * per_block : per_block;
+            const DoPriorView pview = *rf.prior;
+            for (int s = 0; s < here; ++s) {                      // (uniform, as is the flag: every thread reads one word)
+                if (px[s * kPriorSlot + CBO_MAX_DIM] == 0.0) continue;
+                double xv[CBO_MAX_DIM];
+#pragma unroll
+                for (int k = 0; k < CBO_MAX_DIM; ++k) xv[k] = (k < d) ? px[s * kPriorSlot + k] : 0.0;
+                double m_s, v_s;
+                do_prior_at<kDoPriorGroup>(pview, xv, pa, prior_red, tid, m_s, v_s);
+                if (tid == 0) {
+                    px[s * kPriorSlot + CBO_MAX_DIM + 1] = m_s;
+                    px[s * kPriorSlot + CBO_MAX_DIM + 2] = v_s;
+                }
+            }
+            __syncthreads();
+            pm_c = px[slot * kPriorSlot + CBO_MAX_DIM + 1];
+            pv_c = px[slot * kPriorSlot + CBO_MAX_DIM + 2];
+        }
         // ---- the moving point as a candidate: prep_points_kernel's arithmetic
         double xc[CBO_MAX_DIM];
 #pragma unroll
@@ -155,7 +201,7 @@ __global__ __launch_bounds__(256) void small_sets_refine_kernel(const SmallSetAr
 
         // ---- K* and its derivative columns, straight into the MFMA result layout
         d4 acc[8];
-        small_kstar_tiles_of(sh, st, tiles, xc, csq, 0.0, inv_l2, kq, acc);
+        small_kstar_tiles_of(sh, st, tiles, xc, csq, (PRIOR && j == 0) ? sqrt(pv_c) : 0.0, inv_l2, kq, acc);
         if (j > 0) {
 #pragma unroll
             for (int t = 0; t < 8; ++t)
@@ -186,7 +232,7 @@ __global__ __launch_bounds__(256) void small_sets_refine_kernel(const SmallSetAr
         // ---- the start's lane: posterior, acquisition over the point's cost, gradient, one step of the search
         if (owner) {
             double mean, var;
-            posterior_of(qacc, macc, 0.0, 0.0, false, p, mean, var);
+            posterior_of(qacc, macc, pm_c, pv_c, PRIOR, p, mean, var);
             double cost = 0.0;
 #pragma unroll
             for (int k = 0; k < CBO_MAX_DIM; ++k)
@@ -219,32 +265,33 @@ __global__ __launch_bounds__(256) void small_sets_refine_kernel(const SmallSetAr
     }
 }
 
-template <int KIND, bool BYVAL>
+template <int KIND, bool BYVAL, bool PRIOR>
 static void launch_refine_as(hipStream_t s, const SmallSetArgs &args, const cbo_small_set *sets, const cbo_small_refine *refs,
                              const double *starts, int n_sets, int blocks_per_set, double *scratch, int *info, int max_rounds,
                              double *x_out, double *val_out, double *grad_out, int *rounds_out, int *status_out)
 {
     static std::atomic<unsigned long long> opted{0};
-    small_lds_opt_in(reinterpret_cast<const void *>(small_sets_refine_kernel<KIND, BYVAL>), opted);
-    hipLaunchKernelGGL((small_sets_refine_kernel<KIND, BYVAL>), dim3((unsigned)blocks_per_set, (unsigned)n_sets), dim3(256),
+    small_lds_opt_in(reinterpret_cast<const void *>(small_sets_refine_kernel<KIND, BYVAL, PRIOR>), opted);
+    hipLaunchKernelGGL((small_sets_refine_kernel<KIND, BYVAL, PRIOR>), dim3((unsigned)blocks_per_set, (unsigned)n_sets), dim3(256),
                        sizeof(SmallShared), s, args, sets, refs, starts, scratch, blocks_per_set, info, max_rounds, x_out,
                        val_out, grad_out, rounds_out, status_out);
 }
 
 int small_refine_starts_per_block(int d) { return 4 * (16 / (1 + d)); }
 
-void launch_small_sets_refine(hipStream_t s, int kind, const cbo_small_set *sets, const cbo_small_refine *refs,
+void launch_small_sets_refine(hipStream_t s, int kind, bool prior, const cbo_small_set *sets, const cbo_small_refine *refs,
                               const double *starts, int n_sets, int blocks_per_set, double *scratch, int *info, int max_rounds,
                               double *x_out, double *val_out, double *grad_out, int *rounds_out, int *status_out)
 {
     SmallSetArgs args{};
     const bool byval = n_sets <= kSmallByValue;
     if (byval) std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_sets);
+#define CBO_LAUNCH_AS(K, B, P)                                                                                          \
+    launch_refine_as<K, B, P>(s, args, sets, refs, starts, n_sets, blocks_per_set, scratch, info, max_rounds, x_out, val_out, \
+                              grad_out, rounds_out, status_out)
 #define CBO_LAUNCH_KIND(K)                                                                                              \
-    (byval ? launch_refine_as<K, true>(s, args, sets, refs, starts, n_sets, blocks_per_set, scratch, info, max_rounds,   \
-                                       x_out, val_out, grad_out, rounds_out, status_out)                                \
-           : launch_refine_as<K, false>(s, args, sets, refs, starts, n_sets, blocks_per_set, scratch, info, max_rounds,  \
-                                        x_out, val_out, grad_out, rounds_out, status_out))
+    (prior ? (byval ? CBO_LAUNCH_AS(K, true, true) : CBO_LAUNCH_AS(K, false, true))                                     \
+           : (byval ? CBO_LAUNCH_AS(K, true, false) : CBO_LAUNCH_AS(K, false, false)))
     switch (kind) {
         case CBO_ACQ_LCB: CBO_LAUNCH_KIND(CBO_ACQ_LCB); break;
         case CBO_ACQ_PI: CBO_LAUNCH_KIND(CBO_ACQ_PI); break;
@@ -253,6 +300,7 @@ void launch_small_sets_refine(hipStream_t s, int kind, const cbo_small_set *sets
         default: CBO_LAUNCH_KIND(kEiKind); break;
     }
 #undef CBO_LAUNCH_KIND
+#undef CBO_LAUNCH_AS
 }
 
 }  // namespace cbo

@@ -76,7 +76,7 @@ class CausalGradientAcquisitionOptimizer:
         return lockstep_lbfgs(lambda X: _values_and_gradients(acquisition, X), np.asarray(x0, dtype=np.float64), lo, hi,
                               max_rounds=max_rounds, history=history)
 
-    def optimize(self, acquisition, context=None, refine=False, num_starts=1, device=False):
+    def optimize(self, acquisition, context=None, refine=False, num_starts=1, device=False, device_prior=False):
         """(x_max (1,d), acquisition value at x_max (1,1)) -- emukit ``AcquisitionOptimizerBase.optimize``.
         ``acquisition`` is ``CausalExpectedImprovement(...) / Cost(...)`` (an ``AcquisitionQuotient``) or a bare
         ``CausalExpectedImprovement``.  ``refine=True`` adds the reference's gradient stage: from the best grid point
@@ -84,7 +84,13 @@ class CausalGradientAcquisitionOptimizer:
         ``num_starts`` best grid points at once (``refine_batched``).  ``device=True`` (with ``refine=True``) runs the
         searches from the ``num_starts`` best grid points inside one device launch (``refine_sets``) and
         raises ``ValueError`` when the set is not eligible for it: a causal, large or fp32 model, a cost that is not the
-        graphs' own, an acquisition the launch does not know.  The default is today's path."""
+        graphs' own, an acquisition the launch does not know.  ``device_prior=True`` (with ``refine=True`` and
+        ``device=True``) lets a causal set into the launch through a device-resident do-calculus prior (``DoPrior``, DESIGN.md
+        §4u) when ``prior_spec`` recognises its closures.  The default is today's path."""
+        if device_prior and not refine:
+            raise ValueError("device_prior=True selects the device form of a causal set's refinement: refine must be True")
+        if device_prior and not device:
+            raise ValueError("device_prior=True belongs to the device form of the refinement: device must be True")
         if device and not refine:
             raise ValueError("device=True selects the device form of the refinement: refine must be True")
         if (refine or self.anchors == "uniform") and not has_gradients(acquisition):
@@ -104,7 +110,7 @@ class CausalGradientAcquisitionOptimizer:
         x = pts[res["best_idx"]][None, :].copy()
         fx = np.array([[res["best_val"]]])
         if refine and device:
-            kind, model, y_best, task, cost = _device_refinable(acquisition)
+            kind, model, y_best, task, cost = _device_refinable(acquisition, device_prior)
             if k > 1:
                 acq = np.asarray(res["acq"], dtype=np.float64).reshape(-1)
                 top = np.argpartition(-acq, k - 1)[:k]
@@ -112,7 +118,7 @@ class CausalGradientAcquisitionOptimizer:
             else:
                 starts = x
             (xs, fs, status), = refine_sets([model], [starts], [self.bounds], y_best, task, [cost], kind=kind,
-                                            host_fallback=False)
+                                            host_fallback=False, device_prior=device_prior)
             if status[0] == _lib.REFINE_DECLINED:
                 raise ValueError("device=True: the device launch declined the set (its model is not positive definite "
                                  "without jitter, or the one-workgroup kernels are switched off with CBO_HIP_SMALL_SETS=0)")
@@ -274,7 +280,7 @@ def one_row_cost(fix, variable, x):
     return c
 
 
-def _device_refinable(acquisition):
+def _device_refinable(acquisition, device_prior=False):
     """(kind, model, y_best, task, Cost) of an acquisition ``optimize(device=True)`` can hand to ``refine_sets``;
     ``ValueError`` says why another cannot."""
     from .causal_acquisition_functions import CausalExpectedImprovement
@@ -293,16 +299,21 @@ def _device_refinable(acquisition):
         kind = (num.kind, param)
     else:
         raise ValueError(f"device=True: {type(num).__name__} is not an acquisition the device launch refines")
-    why = _not_eligible(num.model, cost)
+    why = _not_eligible(num.model, cost, device_prior)
     if why:
         raise ValueError(f"device=True: {why}")
     return kind, num.model, y_best, task, cost
 
 
-def _not_eligible(model, cost):
-    """Why the device launch does not take this (model, Cost), or None when it does."""
+def _not_eligible(model, cost, device_prior=False):
+    """Why the device launch does not take this (model, Cost), or None when it does.  ``device_prior``: a causal model whose
+    closures ``prior_spec`` recognises is taken (its ``DoPrior`` has yet to be created: that can still decline it)."""
     if getattr(model, "causal", False):
-        return "a causal model's prior closures are Python: they cannot be evaluated at a moving point on the device"
+        if not device_prior:
+            return "a causal model's prior closures are Python: they cannot be evaluated at a moving point on the device"
+        from ..DoCalculus import prior_spec
+        if prior_spec(model) is None:
+            return "the causal model's prior closures are not the do-calculus closures of DoCalculus.py"
     if not getattr(model, "small", False):
         return "the model has more than 128 observations or is fp32"
     if cost_structure(cost) is None:
@@ -318,8 +329,50 @@ def _acquisition_of_kind(kind, model, current_global_best, task, cost):
     return _acquisition_for(kind[0], model, current_global_best, task, None, None if kind[0] == "VAR" else kind[1]) / cost
 
 
+def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, task, param, max_rounds, out):
+    """``refine_sets``' one library call for the sets ``dev`` (``priors``: the ``DoPrior`` of each causal one): fills ``out[i]``
+    of every set the launch took."""
+    import ctypes
+    if not dev:
+        return
+    n = len(dev)
+    structs = [cost_structure(costs[i]) for i in dev]
+    for i, (fix, _) in zip(dev, structs):
+        if not fix.sum() > 0.0:
+            raise ValueError(f"refine_sets: the fixed costs of set {i} must sum to a positive cost")
+    sets = (_lib.CboRefineSet * n)()
+    for j, i in enumerate(dev):
+        fix, variable = structs[j]
+        sets[j].k = X0[i].shape[0]
+        sets[j].starts = X0[i].ctypes.data_as(_lib.c_double_p)
+        sets[j].lo = los[i].ctypes.data_as(_lib.c_double_p)
+        sets[j].hi = his[i].ctypes.data_as(_lib.c_double_p)
+        sets[j].cost_fix = fix.ctypes.data_as(_lib.c_double_p)
+        sets[j].cost_variable = variable.ctypes.data_as(_lib.c_int_p)
+    rows = sum(X0[i].size for i in dev)
+    total = sum(X0[i].shape[0] for i in dev)
+    x_out, g_out, v_out = np.zeros(rows), np.zeros(rows), np.zeros(total)
+    rounds, status = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32)
+    gps = (ctypes.c_void_p * n)(*[models[i]._handle for i in dev])
+    yb = np.full(n, y_best)
+    outs = (_lib.REFINE_KIND_CODE[kind[0]], _lib.dptr(yb), _lib.TASK_CODE[task], param, max_rounds, _lib.dptr(x_out),
+            _lib.dptr(v_out), _lib.dptr(g_out), rounds.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p))
+    if priors:
+        handles = (ctypes.c_void_p * n)(*[priors[i]._handle if i in priors else None for i in dev])
+        _lib.check(_lib.load().cbo_acq_refine_sets_prior(n, gps, sets, handles, *outs))
+    else:
+        _lib.check(_lib.load().cbo_acq_refine_sets(n, gps, sets, *outs))
+    r0 = o0 = 0
+    for i in dev:
+        k, d = X0[i].shape
+        if status[o0] != _lib.REFINE_DECLINED:
+            out[i] = (x_out[r0:r0 + k * d].reshape(k, d).copy(), v_out[o0:o0 + k].copy(), status[o0:o0 + k].copy())
+        r0 += k * d
+        o0 += k
+
+
 def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=("EI", None), max_rounds=200,
-                host_fallback=True):
+                host_fallback=True, device_prior=False):
     """The reference's second stage (causal_optimizer.py:59-65) for every exploration set at once: from every row of
     ``starts[s]`` ((k_s, d_s), 1 <= k_s <= 64) a projected L-BFGS ascent of ``acquisition / Cost`` inside ``bounds[s]``
     (``lockstep_lbfgs``'s iteration), returning per set ``(points (k_s, d_s), values (k_s,), status (k_s,) int)``.
@@ -333,7 +386,11 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
     default (beta 1, jitter 0) on both routes; ``("EI", jitter)`` with a finite jitter is accepted too (what
     ``optimize(device=True)`` passes for a jittered EI) and reaches both routes.  Models are only read by the launch; the
     host route fits a model that is not.  ``host_fallback=False``: a set the launch does not take is not refined at all --
-    its points are its starts, its values NaN, its status ``_lib.REFINE_DECLINED``."""
+    its points are its starts, its values NaN, its status ``_lib.REFINE_DECLINED``.
+    ``device_prior=True``: a causal set is eligible too when ``prior_spec`` recognises its closures, its model
+    is small and fp64, ``cost_structure`` recognises its cost and a ``DoPrior`` of its graph GP can be created
+    (``cbo_acq_refine_sets_prior``); the priors are built for this call and closed after it.  A causal set that misses one of
+    these takes today's route.  The default does exactly what it did."""
     import ctypes
     import math
     from .utils import sets_acquisition
@@ -373,39 +430,27 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
             raise ValueError(f"refine_sets: starts of set {i} must be finite")
         X0.append(x0); los.append(lo); his.append(hi)
     out = [None] * s
-    dev = [i for i in range(s) if _not_eligible(models[i], costs[i]) is None]
-    if dev:
-        n = len(dev)
-        structs = [cost_structure(costs[i]) for i in dev]
-        for i, (fix, _) in zip(dev, structs):
-            if not fix.sum() > 0.0:
-                raise ValueError(f"refine_sets: the fixed costs of set {i} must sum to a positive cost")
-        sets = (_lib.CboRefineSet * n)()
-        for j, i in enumerate(dev):
-            fix, variable = structs[j]
-            sets[j].k = X0[i].shape[0]
-            sets[j].starts = X0[i].ctypes.data_as(_lib.c_double_p)
-            sets[j].lo = los[i].ctypes.data_as(_lib.c_double_p)
-            sets[j].hi = his[i].ctypes.data_as(_lib.c_double_p)
-            sets[j].cost_fix = fix.ctypes.data_as(_lib.c_double_p)
-            sets[j].cost_variable = variable.ctypes.data_as(_lib.c_int_p)
-        rows = sum(X0[i].size for i in dev)
-        total = sum(X0[i].shape[0] for i in dev)
-        x_out, g_out, v_out = np.zeros(rows), np.zeros(rows), np.zeros(total)
-        rounds, status = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32)
-        gps = (ctypes.c_void_p * n)(*[models[i]._handle for i in dev])
-        yb = np.full(n, y_best)
-        _lib.check(_lib.load().cbo_acq_refine_sets(
-            n, gps, sets, _lib.REFINE_KIND_CODE[kind[0]], _lib.dptr(yb), _lib.TASK_CODE[task], param, max_rounds,
-            _lib.dptr(x_out), _lib.dptr(v_out), _lib.dptr(g_out), rounds.ctypes.data_as(_lib.c_int_p),
-            status.ctypes.data_as(_lib.c_int_p)))
-        r0 = o0 = 0
-        for i in dev:
-            k, d = X0[i].shape
-            if status[o0] != _lib.REFINE_DECLINED:
-                out[i] = (x_out[r0:r0 + k * d].reshape(k, d).copy(), v_out[o0:o0 + k].copy(), status[o0:o0 + k].copy())
-            r0 += k * d
-            o0 += k
+    dev = [i for i in range(s) if _not_eligible(models[i], costs[i], device_prior) is None]
+    priors = {}
+    if device_prior:
+        from ..DoCalculus import DoPrior, prior_spec
+        for i in list(dev):
+            if not getattr(models[i], "causal", False):
+                continue
+            try:
+                priors[i] = DoPrior(*prior_spec(models[i]))
+                if priors[i].n_iv != models[i].input_dim:
+                    raise ValueError("the prior's value columns are not the model's inputs")
+            except (_lib.CboHipError, ValueError):
+                if i in priors:
+                    priors.pop(i).close()
+                dev.remove(i)                  # (unsupported graph GP: today's route)
+    try:
+        _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, task, param, max_rounds, out)
+    finally:
+        for p in priors.values():
+            p.close()
+
     for i in range(s):
         if out[i] is None and not host_fallback:
             out[i] = (X0[i].copy(), np.full(X0[i].shape[0], np.nan), np.full(X0[i].shape[0], _lib.REFINE_DECLINED, dtype=np.int32))

@@ -311,7 +311,7 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
 
 def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
                        acquisition="EI", acquisition_param=None, hyper_samples=None, spaces=None, batch_size=None,
-                       update_incumbent=False, refine=False, constraints=None):
+                       update_incumbent=False, refine=False, device_prior=False, constraints=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -356,10 +356,14 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     (``causal_optimizer.refine_sets``; sets the launch does not take go through ``refine_batched``).  The
     refined point replaces the winner only if its value, priced at its own cost, is not lower.  ``refine=True`` with
     ``"MES"``, non-empty ``constraints``, ``hyper_samples``, ``batch_size`` or ``raw=True``, or without ``spaces``, raises
-    ``ValueError`` before any device call.  ``False`` takes exactly today's calls."""
+    ``ValueError`` before any device call.  ``False`` takes exactly today's calls.
+    ``device_prior=True`` (with ``refine=True``; ``ValueError`` without): a causal set whose prior closures are the do-calculus
+    closures joins the refinement's device launch through a device-resident prior (``refine_sets(device_prior=True)``,
+    DESIGN.md §4u) instead of ``refine_batched``.  ``False`` takes exactly today's calls."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    checked_device_prior(device_prior, refine)
     checked_refine(refine, kind, constraints, hyper_samples, batch_size, raw, spaces, len(models))
     batch_size = checked_batch_size(batch_size, kind, constraints, hyper_samples, raw)
     if batch_size is not None and task not in _lib.TASK_CODE:
@@ -459,8 +463,15 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
         return None, [(float(vals[i]), int(idxs[i])) for i in range(s)]
     xs, ys = winners_to_points(st, models, grids, current_global_best, task)
     if refine:
-        xs, ys = refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind)
+        xs, ys = refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind, device_prior)
     return xs, ys
+
+
+def checked_device_prior(device_prior, refine):
+    """``device_prior`` of a multi-set sweep, a path or an agent: it selects how causal sets are REFINED."""
+    if device_prior and not refine:
+        raise ValueError("device_prior=True puts causal sets into the refinement's device launch: refine must be True")
+    return bool(device_prior)
 
 
 def checked_refine(refine, kind, constraints=None, hyper_samples=None, batch_size=None, raw=False, spaces=None, n_sets=None):
@@ -485,11 +496,12 @@ def checked_refine(refine, kind, constraints=None, hyper_samples=None, batch_siz
     return True
 
 
-def refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind):
+def refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind, device_prior=False):
     """``find_next_y_points(refine=True)``'s second stage: every set's winner refined by ``refine_sets``; the refined point
     replaces it only if its value -- over the point's own cost, as ``winners_to_points`` prices the winner -- is not lower."""
     from .causal_optimizer import refine_sets
-    res = refine_sets(models, xs, [space_bounds(sp) for sp in spaces], current_global_best, task, costs, kind=kind)
+    res = refine_sets(models, xs, [space_bounds(sp) for sp in spaces], current_global_best, task, costs, kind=kind,
+                      device_prior=device_prior)
     xs, ys = list(xs), list(ys)
     for i, (pts, vals, _) in enumerate(res):
         best = int(np.argmax(vals))

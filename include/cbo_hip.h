@@ -743,6 +743,46 @@ int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *se
                         int task, double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
                         int *rounds_out, int *status_out);
 
+/* The do-calculus prior of an RBF graph GP as a device-resident handle (src/DoCalculus.py:34-89).  With the
+ * graph GP's inputs X_g, the observed rows O (n_obs x d_in) and the intervened columns I,
+ *     a_i(x) = exp(-1/2 sum_{c in I} ((x_c - X_g[i,c]) / l_c)^2),      b_ri = the same over c not in I at O_rc,
+ *     m(x) = sum_i w_i a_i(x),  w_i = sigma^2 alpha_i mean_r b_ri;      v(x) = (sigma^2 + sigma_n^2) - a(x)^T M a(x),
+ *     M = sigma^4 (Ky^-1 o b^T b / n_obs)
+ * are cbo_gp_predict_do's row means (noise included) at O(n_g^2) per point instead of O(n_obs n_g^2).
+ * cbo_do_prior_create snapshots w, M, the intervened columns of X_g (scaled as the kernels scale points), their lengthscales
+ * and sigma^2 + sigma_n^2 from the fitted model: the handle owns its device memory and does not refer to the model
+ * afterwards -- rebuild it when the graph GP changes.  intervened_index: cbo_gp_predict_do's iv_index (d_in entries, -1 = not
+ * intervened, else the column of `values`).  The model is only read (its alpha is materialised as a prediction would).
+ * Every element of w and M is one fixed-order sum: two creations give the same bits.
+ * CBO_ERR_UNSUPPORTED, the reason in cbo_last_error(): an fp32 graph GP; a causal graph GP (it has a prior of its own); more
+ * than CBO_DO_PRIOR_MAX_N rows; a graph GP that needed jitchol's jitter; a model whose latent variance the factored form cannot
+ * keep above GPy's 1e-15 clip with margin -- sn / (n_g sigma^2 + sn) < 2^-26 with sn = sigma_n^2 + 1e-8 (the factored form has
+ * no per-row clip; the bound is the least latent variance over sigma^2, kept above sqrt(eps)).
+ * CBO_ERR_INVALID: NULL arguments, n_obs <= 0, n_iv outside 1..CBO_MAX_DIM, an index >= n_iv, no intervened column;
+ * CBO_ERR_NOT_FITTED: the model is not fitted.
+ * cbo_do_prior_eval: m(x) and v(x) at the m rows of `values` (m x n_iv); what it returns at a point is, bit for bit, what
+ * cbo_acq_refine_sets_prior uses there (one device function, the same lane group). */
+#define CBO_DO_PRIOR_MAX_N 1024
+typedef struct cbo_do_prior cbo_do_prior;
+int cbo_do_prior_create(cbo_gp *graph_gp, int64_t n_obs, const double *observed /* n_obs x d_in */, int n_iv,
+                        const int *intervened_index /* d_in */, cbo_do_prior **out);
+void cbo_do_prior_destroy(cbo_do_prior *prior);
+int cbo_do_prior_eval(const cbo_do_prior *prior, int64_t m, const double *values /* m x n_iv */, double *mean_out /* m */,
+                      double *var_out /* m */);
+
+/* cbo_acq_refine_sets with causal sets inside the launch: priors[i] is NULL or the do-calculus prior of set
+ * i's causal model (priors itself may be NULL: cbo_acq_refine_sets, which is this call with every prior NULL).  Every round
+ * the workgroup evaluates (m, v) at the trial point of each of its running starts (do_prior_at); column 0 is the causal k*
+ * with sqrt(v), the derivative columns are the stationary part's (GPy's predictive_gradients differentiates nothing else)
+ * and the posterior takes (m, v).  The value at a point is, bit for bit, cbo_acq_sweep_sets (_kind) on a one-point grid there
+ * whose prior arrays are cbo_do_prior_eval's.  A causal model with a NULL prior is DECLINED as before.  Sets with and without
+ * a prior go to two launches on the call's stream.
+ * CBO_ERR_INVALID before any launch, beside cbo_acq_refine_sets': a prior given for a model without one of its own; a prior
+ * whose n_iv differs from the model's d; a prior of another context. */
+int cbo_acq_refine_sets_prior(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, const cbo_do_prior *const *priors,
+                              int kind, const double *y_best, int task, double param, int max_rounds, double *x_out,
+                              double *val_out, double *grad_out, int *rounds_out, int *status_out);
+
 /* Hyper-parameter posterior samples of every model by HMC in ONE launch: GPy's inference.mcmc.HMC with the
  * unit mass matrix over the Logexp-transformed parameters -- integrated_hyper.hmc_sample, restated in csrc/hmc_chain.h -- one
  * chain per model, every chain inside hmc_sets_kernel: a workgroup factors its model at each position of its chain from
