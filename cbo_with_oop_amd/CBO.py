@@ -106,13 +106,19 @@ class CBOAcquisitionPath:
     winner is refined by L-BFGS inside the set's box from ``space_list``, all sets in one further device call, and kept only
     if it is not lower.  It needs ``"EI"`` or a point-wise kind, no constraints, no hyper-parameter samples, no batch and a
     single process, and its ``trial_step`` takes the three-call route.  ``device_prior=True`` (with ``refine=True``) lets
-    causal sets into that device call through a device-resident do-calculus prior."""
+    causal sets into that device call through a device-resident do-calculus prior.
+    ``mle_optimizer="device"`` (with ``mle_restarts`` starts per model, 1..16) runs the hyper-parameter MLEs this path
+    starts -- the one in front of the device HMC -- as one-launch searches; ``"host"`` (default) is scipy's
+    L-BFGS-B, unchanged."""
 
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
-                 update_incumbent=False, refine=False, hyper_sampler="host", device_prior=False):
+                 update_incumbent=False, refine=False, hyper_sampler="host", device_prior=False, mle_optimizer="host",
+                 mle_restarts=1):
+        from .GaussianProcessFactory import checked_mle_optimizer
         from .utils_functions.utils import checked_device_prior, checked_refine, sets_acquisition_or_default as sets_acquisition
+        self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
         self.device_prior = checked_device_prior(device_prior, refine)
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
@@ -178,7 +184,8 @@ class CBOAcquisitionPath:
             # every set's chain in one launch
             from .GaussianProcessFactory import generate_hyperparameters_samples_together
             from .utils_functions.integrated_hyper import _hyper_rows
-            drawn = generate_hyperparameters_samples_together(self.models, self.hyper_samples)
+            drawn = generate_hyperparameters_samples_together(self.models, self.hyper_samples, optimizer=self.mle_optimizer,
+                                                              num_restarts=self.mle_restarts)
             self.hyper_rows = [_hyper_rows(model, samples) for model, samples in zip(self.models, drawn)]
             return
         for s in range(self.es_size):
@@ -489,7 +496,11 @@ class CBO(CBOAcquisitionPath):
     ``refine=True``: every set's winner is refined by L-BFGS inside the set's interventional ranges before the set is chosen
     (``CBOAcquisitionPath(refine=True)``) -- the reference's continuous optimum instead of a grid point.
     ``device_prior=True`` (with ``refine=True`` and ``causal_prior=True``): the causal sets are refined inside the device launch,
-    their do-calculus priors evaluated there, instead of on the host route."""
+    their do-calculus priors evaluated there, instead of on the host route.
+    ``mle_optimizer="device"`` (with ``mle_restarts`` starts per model, 1..16): every hyper-parameter MLE of the agent -- the
+    graph GPs of ``run()``'s first fit and of ``observe()``, and the closing ``optimize()`` of ``intervene()``, the chosen
+    set's constraint models included, in one call -- is a one-launch device search (DESIGN.md §4v) instead of scipy's
+    L-BFGS-B with a device call per evaluation; ``"host"`` (default) changes nothing."""
 
     TARGET = "Y"
 
@@ -498,9 +509,10 @@ class CBO(CBOAcquisitionPath):
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
                  constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False,
-                 hyper_sampler="host", device_prior=False):
+                 hyper_sampler="host", device_prior=False, mle_optimizer="host", mle_restarts=1):
         from .DoCalculus import DoCalculus
-        from .GaussianProcessFactory import GaussianProcessType
+        from .GaussianProcessFactory import GaussianProcessType, checked_mle_optimizer
+        checked_mle_optimizer(mle_optimizer, mle_restarts)
         from .graphs import _columns
         from .utils_functions.utils import checked_refine, sets_acquisition_or_default as sets_acquisition
         self.graph = graph() if isinstance(graph, type) else graph
@@ -563,7 +575,7 @@ class CBO(CBOAcquisitionPath):
                          acquisition=acquisition, acquisition_param=acquisition_param, constraints=path_constraints,
                          constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
                          update_incumbent=update_incumbent, refine=refine, hyper_sampler=hyper_sampler,
-                         device_prior=device_prior)
+                         device_prior=device_prior, mle_optimizer=mle_optimizer, mle_restarts=mle_restarts)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions
@@ -580,7 +592,7 @@ class CBO(CBOAcquisitionPath):
         """Fit the graph GPs, observe once, intervene once, then ``num_trials - 2`` epsilon-greedy trials
         (``numpy.random.uniform(0., 1.) < epsilon``: observe, else intervene)."""
         from numpy.random import uniform
-        self.graph_gps = self.graph.fit_all_gaussian_processes(self.measurements, lockstep=self.lockstep)
+        self.graph_gps = self.graph.fit_all_gaussian_processes(self.measurements, lockstep=self.lockstep, **self._mle_kwargs())
         self.observe()
         self.intervene()
         self.monitor.start()
@@ -598,7 +610,7 @@ class CBO(CBOAcquisitionPath):
         self.monitor.log_agent_behaviour(act=False)
         new = self.get_new_observation()
         self.measurements = {k: np.vstack([v, new[k]]) for k, v in self.measurements.items()}
-        self.graph_gps = self.graph.fit_all_gaussian_processes(self.measurements, lockstep=self.lockstep)
+        self.graph_gps = self.graph.fit_all_gaussian_processes(self.measurements, lockstep=self.lockstep, **self._mle_kwargs())
         self.mean_functions, self.var_functions = self.do_calculus.update_all_do_functions(self.graph_gps)
         self.monitor.log_agent_performance()
 
@@ -616,9 +628,19 @@ class CBO(CBOAcquisitionPath):
         intervention_set, intervention = self.select_next_intervention(ys)
         cost = self.compute_cost(intervention_set, intervention, xs)
         self.monitor.log_agent_performance(intervention_set, intervention, xs, cost)
-        self.models[intervention].optimize()
-        for model in (self.constraint_models[intervention] if self.constraints else ()):
+        closing = [self.models[intervention]] + list(self.constraint_models[intervention] if self.constraints else ())
+        if self.mle_optimizer == "device":
+            from .GaussianProcessFactory import optimize_together
+            optimize_together(closing, optimizer="device", num_restarts=self.mle_restarts)
+            return
+        for model in closing:
             model.optimize()
+
+    def _mle_kwargs(self):
+        """What ``fit_all_gaussian_processes`` is told beside the reference's arguments: nothing on the default route."""
+        if self.mle_optimizer == "host":
+            return {}
+        return {"optimizer": self.mle_optimizer, "num_restarts": self.mle_restarts}
 
     @property
     def epsilon(self):

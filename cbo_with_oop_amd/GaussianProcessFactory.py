@@ -532,7 +532,7 @@ class HipGaussianProcess:
             return 1e25, np.zeros_like(x)
         return _objective_value(self, theta, self._last_lml, dv, dls, dn, transform)
 
-    def optimize(self, max_iters=1000, transform="logexp", **kwargs):
+    def optimize(self, max_iters=1000, transform="logexp", optimizer="host", **kwargs):
         """Hyper-parameter MLE (emukit ``GPyModelWrapper.optimize`` -> GPy ``optimize_restarts(1, robust=True)`` -- one run from
         the current parameters, nothing drawn --, src/CBO.py:173; ``gp.optimize()`` in src/utils_functions/utils.py:44):
         maximise the log marginal likelihood over kernel variance, lengthscale(s) and -- unless fixed, as for graph-level
@@ -541,13 +541,26 @@ class HipGaussianProcess:
         parameters from ``x0 = finv(theta0)``, the model left at the routine's ``x_opt``.  Every evaluation is a device
         refit plus the device likelihood and its analytic gradients.  ``transform="log"`` is rounds 1-4's parametrisation
         (theta = exp(x), same stationary point, another path to it).  GPy is not installed here: the trajectory is GPy's
-        by construction, not by comparison (parity unpinned)."""
+        by construction, not by comparison (parity unpinned).
+        ``optimizer="device"``: the whole search inside one device launch (``optimize_together([self], ...,
+        optimizer="device")``, DESIGN.md §4v: ``lockstep_lbfgs``' iteration, not scipy's); ``"host"`` is the run described
+        above, unchanged."""
         from scipy.optimize import fmin_l_bfgs_b
+        if checked_mle_optimizer(optimizer) == "device":
+            return optimize_together([self], max_iters, transform, optimizer="device")[0]
         theta0, x0 = _optimizer_start(self, transform)
         x_opt, f_opt, info = fmin_l_bfgs_b(lambda x: self._objective(x, transform), x0, maxfun=int(max_iters),
                                            maxiter=int(max_iters))
         f_opt = self._objective(x_opt, transform)[0]          # opt_lbfgsb: f_opt = f_fp(x_opt)[0]; the model sits at x_opt
         return _optimizer_finish(self, theta0, x_opt, f_opt, info, transform)
+
+    def optimize_restarts(self, num_restarts=10, max_iters=1000, optimizer="device", **kwargs):
+        """GPy ``model.optimize_restarts(num_restarts)``: the MLE from the current parameters and from ``num_restarts - 1``
+        randomised starts (``mle_restart_starts``: paramz ``randomize()``, a standard normal in the Logexp space, numpy's
+        global generator), the model left at the best end point.  Every start is one workgroup of ONE device launch
+        (DESIGN.md §4v); ``optimizer="host"`` would be ``num_restarts`` optimiser runs one after another and is not offered
+        (ValueError for more than one start).  Returns the ``optimization_result``; its ``runs`` hold every start's record."""
+        return optimize_together([self], max_iters, "logexp", optimizer=optimizer, num_restarts=num_restarts)[0]
 
     def generate_hyperparameters_samples(self, n_samples=20, n_burnin=100, subsample_interval=10, step_size=1e-1,
                                          leapfrog_steps=20, sampler="host"):
@@ -702,15 +715,139 @@ def lml_gradients_batch(models):
     return out
 
 
-def optimize_together(models, max_iters=1000, transform="logexp"):
+def checked_mle_optimizer(optimizer, num_restarts=1):
+    """``optimizer`` (``"host"``: scipy's L-BFGS-B with one device call per evaluation; ``"device"``: the one-launch search,
+    DESIGN.md §4v) and ``num_restarts`` (1..``_lib.MLE_MAX_STARTS``; more than one start on the device alone) checked on
+    the host, before any device call.  Returns ``optimizer``."""
+    if optimizer not in ("host", "device"):
+        raise ValueError(f"optimizer must be 'host' or 'device', not {optimizer!r}")
+    if isinstance(num_restarts, bool) or not isinstance(num_restarts, (int, np.integer)) \
+            or not 1 <= num_restarts <= _lib.MLE_MAX_STARTS:
+        raise ValueError(f"num_restarts must be an int in 1..{_lib.MLE_MAX_STARTS}, not {num_restarts!r}")
+    if optimizer == "host" and num_restarts > 1:
+        raise ValueError("restarts are run by the device launch: num_restarts > 1 needs optimizer='device'")
+    return optimizer
+
+
+def mle_restart_starts(P, num_restarts):
+    """The randomised starts of ``optimize_restarts``: ``num_restarts - 1`` rows ``x = np.random.randn(P)`` in the Logexp
+    space (paramz ``randomize()``: a standard normal for every transformed parameter), one ``randn(P)`` call per row from
+    numpy's global generator; (num_restarts - 1, P).  One start draws nothing."""
+    return np.array([np.random.randn(P) for _ in range(int(num_restarts) - 1)], dtype=np.float64).reshape(-1, P)
+
+
+def mle_best_run(lmls, statuses):
+    """The run GPy's ``argmin(f_opt)`` keeps: the highest final ``lml`` among the runs that have one (neither ``NAN_START``
+    nor ``NOT_PD``, and not NaN), the lowest index on ties; None when no run has."""
+    best = None
+    for j, (v, st) in enumerate(zip(lmls, statuses)):
+        if st in (_lib.REFINE_NAN_START, _lib.MLE_NOT_PD, _lib.MLE_DECLINED) or v != v:
+            continue
+        if best is None or v > lmls[best]:
+            best = j
+    return best
+
+
+def mle_runs_device(models, theta0s, max_rounds):
+    """One ``cbo_gp_mle_sets`` call: model k's searches from the rows of ``theta0s[k]`` ((n_starts, P) parameters).  Returns
+    per model dict(declined, status (n_starts,), rounds, theta (n_starts, P), lml, grad): every run's reason for stopping
+    (``_lib.REFINE_*`` or ``_lib.MLE_NOT_PD``), rounds and end point with the likelihood and its gradients there --
+    meaningless for a ``NOT_PD`` run and for a declined model.  The models are only read."""
+    k = len(models)
+    lib = _lib.load()
+    handles = (ctypes.c_void_p * k)(*[m._handle for m in models])
+    runs = (_lib.CboMleRun * k)()
+    model_status = np.full(k, -1, dtype=np.int32)
+    out, keep = [], []
+    for j, (m, theta0) in enumerate(zip(models, theta0s)):
+        theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+        if theta0.ndim == 1:
+            theta0 = theta0[None]
+        starts, size = theta0.shape
+        o = dict(declined=False, status=np.full(starts, -1, dtype=np.int32), rounds=np.zeros(starts, dtype=np.int32),
+                 theta=np.full((starts, size), np.nan), lml=np.full(starts, np.nan), grad=np.full((starts, size), np.nan))
+        r = runs[j]
+        r.n_params, r.fit_noise, r.n_starts, r.max_rounds = size, 0 if m.fix_noise else 1, starts, int(max_rounds)
+        r.theta0 = _lib.dptr(theta0)
+        r.theta_out, r.lml_out, r.grad_out = _lib.dptr(o["theta"]), _lib.dptr(o["lml"]), _lib.dptr(o["grad"])
+        r.status_out, r.rounds_out = o["status"].ctypes.data_as(_lib.c_int_p), o["rounds"].ctypes.data_as(_lib.c_int_p)
+        out.append(o)
+        keep.append(theta0)
+    _lib.check(lib.cbo_gp_mle_sets(k, handles, runs, model_status.ctypes.data_as(_lib.c_int_p)))
+    for o, st in zip(out, model_status):
+        o["declined"] = int(st) == _lib.MLE_DECLINED
+    return out
+
+
+def _optimize_on_device(models, max_iters, num_restarts, host_fallback):
+    """``optimize_together``'s device route: the results, None where the model has to take the host route."""
+    from scipy.optimize import OptimizeResult
+    max_rounds = min(int(max_iters), _lib.MLE_MAX_ROUNDS)
+    theta0s = []
+    for m in models:                                           # (the draws: per model, in model order, before the call)
+        theta0, _ = _optimizer_start(m, "logexp")
+        extra = mle_restart_starts(theta0.size, num_restarts)
+        theta0s.append(np.vstack([theta0[None], logexp_f(extra)]) if extra.size else theta0[None])
+    answers = mle_runs_device(models, theta0s, max_rounds)
+    results = [None] * len(models)
+    for j, (m, a) in enumerate(zip(models, answers)):
+        back = a["declined"] or int(a["status"][0]) == _lib.MLE_NOT_PD
+        if back:
+            if not host_fallback:
+                why = "was declined" if a["declined"] else "starts at a Ky that is not positive definite as assembled"
+                raise RuntimeError(f"the device search of model {j} {why} and host_fallback is off")
+            continue
+        status = [int(v) for v in a["status"]]
+        runs = [dict(theta0=theta0s[j][i].copy(), theta=a["theta"][i].copy(), lml=float(a["lml"][i]), grad=a["grad"][i].copy(),
+                     rounds=int(a["rounds"][i]), status=status[i], message=_lib.MLE_STATUS_NAME.get(status[i], "?"))
+                for i in range(len(status))]
+        best = mle_best_run(a["lml"], status)
+        won = runs[0 if best is None else best]
+        if best is not None:                                   # (every run failed: the model keeps its parameters)
+            _objective_set(m, won["theta"], fit=False)
+            m._last_lml = won["lml"]
+        theta = won["theta"]
+        res = OptimizeResult(x=logexp_finv(theta), fun=-won["lml"], jac=-(won["grad"] * logexp_gradfactor(theta)),
+                             nit=won["rounds"], nfev=1 + won["rounds"], status=won["status"], message=won["message"],
+                             success=best is not None and won["status"] in (_lib.REFINE_PGTOL, _lib.REFINE_FTOL),
+                             transform="logexp", optimizer="device", best_run=best, runs=runs)
+        m.optimization_result = res
+        results[j] = res
+    return results
+
+
+def optimize_together(models, max_iters=1000, transform="logexp", optimizer="host", num_restarts=1, host_fallback=True):
     """``[m.optimize(max_iters, transform) for m in models]`` with the models' L-BFGS-B runs in lockstep: every round
     evaluates the likelihood and gradients of all models that asked for a value in ONE device call
     (``lml_gradients_batch``).  A model of at most 128 observations follows the trajectory ``optimize`` gives it alone,
     bit for bit, and ends with the same result record; one of 128 < n <= 256 is evaluated by the two-block form without
     a fit (``optimize`` alone refits it and takes the general path): the same likelihood and gradients to rounding.
-    Returns the results (``optimization_result`` of each model)."""
+    Returns the results (``optimization_result`` of each model).
+    ``optimizer="device"``: ONE ``cbo_gp_mle_sets`` call runs every model's whole search -- and, with
+    ``num_restarts`` > 1, its searches from ``num_restarts - 1`` randomised starts beside the current parameters
+    (``mle_restart_starts``, drawn per model in model order before the call) -- at most ``min(max_iters, 4096)`` rounds
+    each.  The iteration is ``causal_optimizer.lockstep_lbfgs``', not scipy's: the same stationary points, another
+    trajectory.  Per model the best run wins (highest final likelihood, lowest index on ties, a NaN never wins: GPy's
+    ``argmin(f_opt)``); the model is set to its parameters, unfitted (``stale``), and its ``optimization_result`` carries
+    ``x``, ``fun``, ``jac``, ``nit``, ``status`` / ``message`` (why the winner's search ended, ``_lib.REFINE_*``),
+    ``transform="logexp"``, ``optimizer="device"`` and every start's record under ``runs``.  A model whose every run ended
+    at a non-finite start keeps its parameters.  A model the call declined (more than 128 observations, fp32,
+    ``CBO_HIP_SMALL_SETS=0``) or whose own start has a Ky that is not positive definite as assembled goes through the
+    lockstep route described above inside the same call (``host_fallback=False``: RuntimeError instead).
+    ``transform="log"`` with ``"device"``, and ``num_restarts`` > 1 with ``"host"``, raise ValueError."""
     from .utils_functions.lockstep_lbfgsb import lockstep_fmin_l_bfgs_b
     models = list(models)
+    checked_mle_optimizer(optimizer, num_restarts)
+    if optimizer == "device":
+        if transform != "logexp":
+            raise ValueError("optimizer='device' searches the Logexp-transformed parameters: transform must be 'logexp'")
+        if not models:
+            return []
+        results = _optimize_on_device(models, max_iters, int(num_restarts), host_fallback)
+        rest = [j for j, r in enumerate(results) if r is None]
+        for j, r in zip(rest, optimize_together([models[j] for j in rest], max_iters, transform) if rest else []):
+            results[j] = r
+        return results
     starts = [_optimizer_start(m, transform) for m in models]
 
     def evaluate(ks, xs):
@@ -775,19 +912,25 @@ def hmc_chains_device(models, theta0s, draws, hmc_iters, stepsize):
 
 
 def generate_hyperparameters_samples_together(models, n_samples=20, n_burnin=100, subsample_interval=10, step_size=1e-1,
-                                              leapfrog_steps=20, host_fallback=True):
+                                              leapfrog_steps=20, host_fallback=True, optimizer="host", num_restarts=1):
     """``[m.generate_hyperparameters_samples(...) for m in models]`` with every model's HMC chain inside ONE device launch
     (``cbo_gp_hmc_sets``): ``optimize_together(models)``; then per model, in order, the 1 % perturbation
     (``randn(P)``) and the chain's draws (``hmc_draws``) -- the generator is consumed exactly as by the per-model sequence,
     ``optimize`` draws nothing --; then the one call.  A model the call declined (more than 128 observations, fp32), or
     whose chain met a Ky that is not positive definite as assembled, is repeated on the host by ``hmc_sample_from_draws``
     on its ``_objective`` with the same draws (``host_fallback=False``: RuntimeError instead).  Returns per model
-    ``samples[n_burnin::subsample_interval]``; every model is left at its chain's last state, unfitted (``stale``)."""
+    ``samples[n_burnin::subsample_interval]``; every model is left at its chain's last state, unfitted (``stale``).
+    ``optimizer`` / ``num_restarts`` go to ``optimize_together`` (``"device"``: the MLE in one launch too; its
+    restarts are drawn before the chains' numbers)."""
     from .utils_functions.integrated_hyper import hmc_draws, hmc_sample_from_draws
     models = list(models)
     if not models:
         return []
-    optimize_together(models)
+    checked_mle_optimizer(optimizer, num_restarts)
+    if optimizer == "device":
+        optimize_together(models, optimizer=optimizer, num_restarts=num_restarts, host_fallback=host_fallback)
+    else:
+        optimize_together(models)
     num = int(n_burnin) + int(n_samples) * int(subsample_interval)
     theta0s, draws = [], []
     for m in models:

@@ -46,8 +46,12 @@ HMC_MAX_PARAMS = MAX_DIM + 2   # CBO_HMC_MAX_PARAMS
 HMC_MAX_SAMPLES = 4096         # CBO_HMC_MAX_SAMPLES
 HMC_MAX_EVALS = 262144         # CBO_HMC_MAX_EVALS: the cap on num_samples * hmc_iters
 HMC_OK, HMC_NOT_PD, HMC_DECLINED = range(3)   # CBO_HMC_*
+MLE_MAX_STARTS = 16            # CBO_MLE_MAX_STARTS
+MLE_MAX_ROUNDS = 4096          # CBO_MLE_MAX_ROUNDS
+MLE_DECLINED, MLE_NOT_PD = REFINE_DECLINED, 6   # CBO_MLE_*: beside the CBO_REFINE_* reasons a run's search ended for
 REFINE_STATUS_NAME = {REFINE_PGTOL: "pgtol", REFINE_FTOL: "ftol", REFINE_STEP: "step", REFINE_MAX_ROUNDS: "max_rounds",
                       REFINE_NAN_START: "nan_start", REFINE_DECLINED: "declined"}
+MLE_STATUS_NAME = {**REFINE_STATUS_NAME, MLE_NOT_PD: "not_pd"}
 
 
 class CboTimers(ctypes.Structure):
@@ -85,6 +89,13 @@ class CboHmcChain(ctypes.Structure):
                 ("hmc_iters", ctypes.c_int), ("stepsize", ctypes.c_double), ("theta0", c_double_p), ("momenta", c_double_p),
                 ("uniforms", c_double_p), ("rows_out", c_double_p), ("accept_out", c_int_p), ("final_theta", c_double_p),
                 ("final_lml", c_double_p), ("final_grad", c_double_p)]
+
+
+class CboMleRun(ctypes.Structure):
+    """struct cbo_mle_run of include/cbo_hip.h."""
+    _fields_ = [("n_params", ctypes.c_int), ("fit_noise", ctypes.c_int), ("n_starts", ctypes.c_int),
+                ("max_rounds", ctypes.c_int), ("theta0", c_double_p), ("theta_out", c_double_p), ("lml_out", c_double_p),
+                ("grad_out", c_double_p), ("status_out", c_int_p), ("rounds_out", c_int_p)]
 
 
 class CboHipError(RuntimeError):
@@ -199,6 +210,7 @@ SIGNATURES = {
     "cbo_do_prior_destroy": (None, [ctypes.c_void_p]),
     "cbo_do_prior_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_hmc_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboHmcChain), c_int_p]),
+    "cbo_gp_mle_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboMleRun), c_int_p]),
     "cbo_gp_mes_gumbel_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_double_p]),
     "cbo_comm_gather_i64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_int64_p]),

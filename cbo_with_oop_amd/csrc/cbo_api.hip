@@ -180,6 +180,12 @@ struct cbo_ctx {
     PinnedBuf<cbo_small_hmc> hmc_host;
     PinnedBuf<double> hmc_draws, hmc_rows, hmc_final;
     PinnedBuf<int> hmc_accept, hmc_status;
+    // cbo_gp_mle_sets: the runs' descriptors as the kernel reads them, final states, status words and rounds as it writes
+    // them (all pinned); the runs' rings of curvature pairs (device)
+    PinnedBuf<cbo_small_mle> mle_host;
+    PinnedBuf<double> mle_final;
+    PinnedBuf<int> mle_status, mle_rounds;
+    GrowBuf<double> mle_rings;
     GrowBuf<double> append_part;                       // block append: slice sums of the pass over V [slices][kp][m_pad]
     GrowBuf<BatchState> batch_state;
     PinnedBuf<double> batch_h_vals; PinnedBuf<int64_t> batch_h_idxs;
@@ -4090,6 +4096,98 @@ extern "C" int cbo_gp_hmc_sets(int n_models, cbo_gp *const *gps, const cbo_hmc_c
         std::memcpy(ch.final_theta, fin, sizeof(double) * (size_t)ch.n_params);
         *ch.final_lml = fin[CBO_HMC_MAX_PARAMS];
         std::memcpy(ch.final_grad, fin + CBO_HMC_MAX_PARAMS + 1, sizeof(double) * (size_t)ch.n_params);
+    }
+    return CBO_OK;
+}
+
+// ---- every model's hyper-parameter MLE (kernels_mle.hip) -----------------------------------------------------
+// cbo_gp_hmc_sets' skeleton with one workgroup, scratch slot and info word per RUN (a (model, start) pair) instead of per
+// model: the models small_lml_gradients would take go into one launch, the others are declined here, their status alone
+// written.  The models are only read; the call returns every run and chooses none.
+extern "C" int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_run *runs, int *model_status_out)
+{
+    if (n_models <= 0) return fail(CBO_ERR_INVALID, "n_models must be positive");
+    if (!gps || !runs || !model_status_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    int rc = check_model_handles(n_models, gps);
+    if (rc != CBO_OK) return rc;
+    for (int i = 0; i < n_models; ++i) {
+        const std::string where = " (model " + std::to_string(i) + ")";
+        const cbo_mle_run &r = runs[i];
+        const cbo_gp *g = gps[i];
+        if (!r.theta0 || !r.theta_out || !r.lml_out || !r.grad_out || !r.status_out || !r.rounds_out)
+            return fail(CBO_ERR_INVALID, "NULL argument: theta0 and the outputs must be given" + where);
+        if (r.n_starts < 1 || r.n_starts > CBO_MLE_MAX_STARTS)
+            return fail(CBO_ERR_INVALID, "n_starts must be in 1.." + std::to_string(CBO_MLE_MAX_STARTS) + where);
+        if (r.max_rounds < 0 || r.max_rounds > CBO_MLE_MAX_ROUNDS)
+            return fail(CBO_ERR_INVALID, "max_rounds must be in 0.." + std::to_string(CBO_MLE_MAX_ROUNDS) + where);
+        if (r.fit_noise != 0 && r.fit_noise != 1) return fail(CBO_ERR_INVALID, "fit_noise must be 0 or 1" + where);
+        const int n_ls = g->h.ard ? g->d : 1;
+        if (r.n_params != 1 + n_ls + r.fit_noise)
+            return fail(CBO_ERR_INVALID, "n_params must be " + std::to_string(1 + n_ls + r.fit_noise) +
+                                             " (variance, the lengthscale(s), the noise variance when it is fitted)" + where);
+        for (int k = 0; k < r.n_starts * r.n_params; ++k)
+            if (!std::isfinite(r.theta0[k]) || !(r.theta0[k] > 0.0))
+                return fail(CBO_ERR_INVALID, "theta0 must be finite and positive" + where);
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int> small;
+    partition_small(n_models, [&](int i) { return small_lml_eligible(gps[i]); }, [](int) { return (int64_t)1; }, small);
+    const int ns = (int)small.size();
+    int64_t total = 0;
+    for (int i = 0, j = 0; i < n_models; ++i) {
+        if (j < ns && small[(size_t)j] == i) { ++j; total += runs[i].n_starts; model_status_out[i] = CBO_OK; }
+        else model_status_out[i] = CBO_MLE_DECLINED;
+    }
+    if (small.empty()) return CBO_OK;
+    if (total > kMaxGridBlocks) return fail(CBO_ERR_INVALID, "more than 65535 runs in one call");
+    const int nr = (int)total;
+    // a scratch slot (factor + L^-1), an info word and a ring slot per run
+    const size_t stride = small_lml_scratch_doubles(), per_block = small_sets_scratch_doubles(1, 1);
+    const size_t cap = nr < 32 ? (size_t)32 : (size_t)nr;
+    constexpr int kFinal = 2 * CBO_HMC_MAX_PARAMS + 1;
+    rc = ensure_small_buffers(c, nr, (int)((stride + per_block - 1) / per_block));
+    if (rc == CBO_OK && (size_t)nr * stride > c->small_scratch.cap)
+        rc = fail(CBO_ERR_INVALID, "MLE runs: scratch smaller than expected");
+    if (rc == CBO_OK) rc = grow(c, c->mle_host, cap);
+    if (rc == CBO_OK) rc = grow(c, c->mle_final, cap * (size_t)kFinal);
+    if (rc == CBO_OK) rc = grow(c, c->mle_status, cap);
+    if (rc == CBO_OK) rc = grow(c, c->mle_rounds, cap);
+    if (rc == CBO_OK) rc = grow(c, c->mle_rings, cap * (size_t)kMleRingDoubles);
+    if (rc != CBO_OK) return rc;
+    constexpr int kNoStatus = -2;                               // (a launch that never ran answers nothing)
+    for (int j = 0, q = 0; j < ns; ++j) {
+        const int i = small[(size_t)j];
+        const cbo_mle_run &r = runs[i];
+        c->sets_host[j] = cbo_small_set{};
+        fill_small_model(c->sets_host[j], gps[i]);
+        for (int s = 0; s < r.n_starts; ++s, ++q) {
+            cbo_small_mle &rn = c->mle_host[q];
+            std::memset(&rn, 0, sizeof(rn));
+            std::memcpy(rn.theta0, r.theta0 + (size_t)s * (size_t)r.n_params, sizeof(double) * (size_t)r.n_params);
+            rn.model = j; rn.n_params = r.n_params; rn.n_ls = gps[i]->h.ard ? gps[i]->d : 1; rn.fit_noise = r.fit_noise;
+            rn.max_rounds = r.max_rounds;
+            c->mle_status[q] = kNoStatus;
+        }
+    }
+    launch_mle_sets(c->stream, c->sets_host, ns, c->mle_host, nr, c->small_scratch, (int64_t)stride, c->small_info, c->mle_rings,
+                    c->mle_final, c->mle_status, c->mle_rounds);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int j = 0, q = 0; j < ns; ++j) {
+        const cbo_mle_run &r = runs[small[(size_t)j]];
+        const size_t P = (size_t)r.n_params;
+        for (int s = 0; s < r.n_starts; ++s, ++q) {
+            if (c->mle_status[q] == kNoStatus) return fail(CBO_ERR_HIP, "MLE kernel: no status for a run it was given");
+            r.status_out[s] = c->mle_status[q];
+            r.rounds_out[s] = c->mle_rounds[q];
+            if (r.status_out[s] == CBO_MLE_NOT_PD) continue;
+            const double *fin = c->mle_final.p + (size_t)q * kFinal;
+            std::memcpy(r.theta_out + (size_t)s * P, fin, sizeof(double) * P);
+            r.lml_out[s] = fin[CBO_HMC_MAX_PARAMS];
+            std::memcpy(r.grad_out + (size_t)s * P, fin + CBO_HMC_MAX_PARAMS + 1, sizeof(double) * P);
+        }
     }
     return CBO_OK;
 }

@@ -447,6 +447,23 @@ struct cbo_small_hmc {
 void launch_hmc_sets(hipStream_t s, const cbo_small_set *sets, const cbo_small_hmc *chains, const double *draws, int n_models,
                      double *scratch, int64_t stride, int *info, double *rows_out, int *accept_out, double *final_out,
                      int *status_out);
+// ---- every model's hyper-parameter MLE in one launch (kernels_mle.hip) --------------------------------------
+// One RUN of the launch: a (model, start) pair -- the index of the model's descriptor, the start and the search's shape
+// (pinned, device-mapped: read by the kernel directly).  n_params = 1 + n_ls + fit_noise.
+struct cbo_small_mle {
+    double theta0[CBO_HMC_MAX_PARAMS];
+    int model, n_params, n_ls, fit_noise, max_rounds, pad_;
+};
+// a run's two rings of curvature pairs (mle_search.h): S then Y, 8 pairs x CBO_HMC_MAX_PARAMS doubles each
+constexpr int kMleRingDoubles = 2 * 8 * CBO_HMC_MAX_PARAMS;
+// One workgroup per run.  sets (n_models descriptors) / runs and the three outputs may be pinned host memory; scratch:
+// `stride` >= small_lml_scratch_doubles() doubles per RUN; info: n_runs ints, zero on entry and zero again afterwards; rings
+// (device): kMleRingDoubles doubles per run.  final_out: per run theta [CBO_HMC_MAX_PARAMS], lml, dlml / dtheta
+// [CBO_HMC_MAX_PARAMS] at the search's end point; status_out: CBO_REFINE_PGTOL .. CBO_REFINE_NAN_START, or CBO_MLE_NOT_PD
+// (the start's Ky is not positive definite as assembled: no final state); rounds_out: the rounds taken.
+void launch_mle_sets(hipStream_t s, const cbo_small_set *sets, int n_models, const cbo_small_mle *runs, int n_runs,
+                     double *scratch, int64_t stride, int *info, double *rings, double *final_out, int *status_out,
+                     int *rounds_out);
 // the same launch with the batch epilogue (kernels_sets_batch.hip, small_sets_batch_kernel): batch_size >= 2
 // Kriging-believer picks per set.  Sets of at most kSmallBatchMaxCands candidates: the set's V = L^-1 K* stays in global
 // scratch (1 MiB per set at the cap) and the call's widest set has at most 16 candidate blocks.  batch_scratch:

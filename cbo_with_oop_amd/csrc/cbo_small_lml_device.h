@@ -1,11 +1,12 @@
 // Device functions shared by the kernels that factor a small model (at most 128 observations) at hyper-parameters OTHER
 // than its own, from its raw coordinates, and by those that turn such a factor into the log marginal likelihood and its
 // gradients: hyper_avg_kernel / hyper_sets_kernel (kernels_hyper.hip), small_lml_kernel / small_lml_batch_kernel
-// (kernels_chol.hip) and hmc_sets_kernel (kernels_hmc.hip).  Each function exists once, so the kernels built from them
+// (kernels_chol.hip), hmc_sets_kernel (kernels_hmc.hip) and mle_sets_kernel (kernels_mle.hip).  Each function exists once, so the kernels built from them
 // agree bit for bit.
 #pragma once
 
 #include "cbo_small_device.h"
+#include "lml_outputs.h"
 
 namespace cbo {
 
@@ -213,6 +214,67 @@ __device__ __forceinline__ void small_lml_after_factor(SmallShared &sh, double *
 __device__ __forceinline__ double small_lml_term(const double (*red)[kSmallLmlTerms], int k)
 {
     return (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+}
+
+// the factor of the scratch slot back into LDS (rows of the factored tiles; the solve reads nothing else), its tile
+// inverses and z into registers: small_model_factor's closing steps.  Ends with loads in flight: the caller waits.
+__device__ __forceinline__ void hmc_factor_to_lds(SmallShared &sh, const double *Us, const double *invs, int tiles,
+                                                  double (&iv)[8][4], double (&zr)[8][4])
+{
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lc = lane & 15, kq = lane >> 4;
+    const unsigned s0 = lds_byte_address(&sh.blk.S[0][0]);
+    const int rows = 16 * tiles;
+    for (int p = wave; p < rows; p += 4)
+        glds16(Us + (int64_t)p * kSmallLd + lane * 2, __builtin_amdgcn_readfirstlane(s0 + 8u * (unsigned)(p * kDiagLd)));
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            iv[s][kk] = (s < tiles) ? invs[s * 256 + (4 * kk + kq) * 16 + lc] : 0.0;
+            zr[s][kk] = (s < tiles) ? Us[(int64_t)(16 * s + kq + 4 * kk) * kSmallLd + 128] : 0.0;
+        }
+}
+
+// The likelihood of the model st at the hyper-parameter row `row` (variance, lengthscale x n_ls, noise variance; in LDS, the
+// same doubles for every lane) from its RAW coordinates, inside one resident workgroup: what hmc_sets_kernel does per
+// position of a chain and mle_sets_kernel per evaluation of a search.  The points are prepared with the row's lengthscales,
+// K(X,X) + (noise + 1e-8) I is assembled and factored inside LDS into the scratch slot (Us, invs), and the stages behind the
+// factor leave the four waves' partial sums in red (small_lml_after_factor), behind a barrier.  Returns false -- to every
+// thread alike, with nothing behind the factor done and the info word still set: the caller clears it -- when Ky is not
+// positive definite as assembled.  alpha_s: 128 doubles of LDS that are free behind the factor.
+__device__ __forceinline__ bool small_lml_sums_at(SmallShared &sh, double *alpha_s, double (*red)[kSmallLmlTerms],
+                                                  const cbo_small_set &st, const double *row, int n_ls, int tiles, double rhs,
+                                                  double *Us, double *invs, double *Vg, int *info_word)
+{
+    const int tid = threadIdx.x;
+    const cbo_small_set sth = hyper_sample_set(st, row, n_ls);
+    hyper_model_points(sh, st, st.ard ? row + 1 : nullptr);
+    __syncthreads();
+    hyper_factor(sh, sth, tiles, rhs, Us, invs, info_word);
+    if (__hip_atomic_load(info_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
+    double iv[8][4], zr[8][4];
+    hmc_factor_to_lds(sh, Us, invs, tiles, iv, zr);
+    if (tid < 128) alpha_s[tid] = 0.0;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    CBO_FOR_DIM(st.d, small_lml_after_factor<D>(sh, alpha_s, red, sth, Us, Vg, iv, zr));
+    return true;
+}
+
+// ... and, on ONE thread behind that barrier, the likelihood and its gradients with respect to the row's entries by the
+// host's arithmetic (lml_outputs.h): dl[0] variance, dl[1 ..] the lengthscale(s), *dnoise the noise variance
+__device__ __forceinline__ void small_lml_outputs_at(const cbo_small_set &st, const double *row,
+                                                     const double (*red)[kSmallLmlTerms], double *lml, double *dl,
+                                                     double *dnoise)
+{
+    double t[kSmallLmlTerms];
+#pragma unroll
+    for (int k = 0; k < kSmallLmlTerms; ++k) t[k] = small_lml_term(red, k);
+    lml_outputs_of(row[0], st.ard != 0, row + 1, st.d, st.n, t, t[1 + CBO_MAX_DIM], t[1 + CBO_MAX_DIM + 1],
+                   t[1 + CBO_MAX_DIM + 2], t[1 + CBO_MAX_DIM + 3], lml, &dl[0], &dl[1], dnoise);
 }
 
 }  // namespace cbo

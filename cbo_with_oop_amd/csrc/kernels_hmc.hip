@@ -6,7 +6,8 @@
 //   assembled and factored inside LDS (hyper_sample_set / hyper_model_points / hyper_factor, as hyper_avg_kernel does for a
 //   hyper-parameter sample);
 //   the stages behind the factor of small_lml_kernel follow (small_lml_after_factor: L^-1 through the tile solve, alpha,
-//   diag(Ky^-1), the gradient sums over the upper tile pairs, the workgroup reduction), the sums staying in LDS;
+//   diag(Ky^-1), the gradient sums over the upper tile pairs, the workgroup reduction), the sums staying in LDS -- all of
+//   it one device function, small_lml_sums_at (cbo_small_lml_device.h), which mle_sets_kernel calls per evaluation too;
 //   thread 0 turns them into the likelihood and its gradients with the host's own arithmetic (lml_outputs.h) and advances
 //   the chain (hmc_feed): two multiply-adds per parameter between two evaluations.
 // The likelihood at a position is therefore what cbo_gp_lml_gradients answers for the model at those hyper-parameters.
@@ -26,28 +27,6 @@ static_assert(sizeof(SmallShared) + 4 * kSmallLmlTerms * sizeof(double) + sizeof
               "the workgroup's static LDS (the reduction's partial sums, the chain's state, the published theta) beside "
               "SmallShared: one CU");
 static_assert(kHmcMaxParams == CBO_MAX_DIM + 2, "variance, one lengthscale per dimension, noise variance");
-
-// the factor of the scratch slot back into LDS (rows of the factored tiles; the solve reads nothing else), its tile
-// inverses and z into registers: small_model_factor's closing steps.  Ends with loads in flight: the caller waits.
-__device__ __forceinline__ void hmc_factor_to_lds(SmallShared &sh, const double *Us, const double *invs, int tiles,
-                                                  double (&iv)[8][4], double (&zr)[8][4])
-{
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lc = lane & 15, kq = lane >> 4;
-    const unsigned s0 = lds_byte_address(&sh.blk.S[0][0]);
-    const int rows = 16 * tiles;
-    for (int p = wave; p < rows; p += 4)
-        glds16(Us + (int64_t)p * kSmallLd + lane * 2, __builtin_amdgcn_readfirstlane(s0 + 8u * (unsigned)(p * kDiagLd)));
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            iv[s][kk] = (s < tiles) ? invs[s * 256 + (4 * kk + kq) * 16 + lc] : 0.0;
-            zr[s][kk] = (s < tiles) ? Us[(int64_t)(16 * s + kq + 4 * kk) * kSmallLd + 128] : 0.0;
-        }
-}
 
 template <bool BYVAL>
 __global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
@@ -91,12 +70,8 @@ __global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval,
     for (int64_t pos = 0; pos < positions; ++pos) {
         // ---- theta as a hyper-parameter sample's row (variance, lengthscale x n_ls, noise variance): thread 0 left it in LDS
         const double *row = theta_row;
-        const cbo_small_set sth = hyper_sample_set(st, row, n_ls);
-        hyper_model_points(sh, st, st.ard ? row + 1 : nullptr);
-        __syncthreads();
-        hyper_factor(sh, sth, tiles, rhs, Us, invs, &info[b]);
         // not positive definite as assembled: jitchol's business, the chain stops here
-        if (__hip_atomic_load(&info[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+        if (!small_lml_sums_at(sh, alpha_s, red, st, row, n_ls, tiles, rhs, Us, invs, Vg, &info[b])) {
             __syncthreads();                                      // (everybody has read the word)
             if (tid == 0) {
                 status_out[b] = CBO_HMC_NOT_PD;
@@ -104,20 +79,10 @@ __global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval,
             }
             return;
         }
-        double iv[8][4], zr[8][4];
-        hmc_factor_to_lds(sh, Us, invs, tiles, iv, zr);
-        if (tid < 128) alpha_s[tid] = 0.0;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        CBO_FOR_DIM(st.d, small_lml_after_factor<D>(sh, alpha_s, red, sth, Us, Vg, iv, zr));
         // ---- the likelihood and its gradients by the host's arithmetic, one step of the chain
         if (tid == 0) {
-            double t[kSmallLmlTerms];
-#pragma unroll
-            for (int k = 0; k < kSmallLmlTerms; ++k) t[k] = small_lml_term(red, k);
             double lml, dl[kHmcMaxParams], dnoise;
-            lml_outputs_of(row[0], st.ard != 0, row + 1, st.d, st.n, t, t[1 + CBO_MAX_DIM], t[1 + CBO_MAX_DIM + 1],
-                           t[1 + CBO_MAX_DIM + 2], t[1 + CBO_MAX_DIM + 3], &lml, &dl[0], &dl[1], &dnoise);
+            small_lml_outputs_at(st, row, red, &lml, dl, &dnoise);
             if (sample_noise) dl[1 + n_ls] = dnoise;
             hmc_feed(chain, lml, dl, momenta, uniforms, rows, accepts);
             publish();

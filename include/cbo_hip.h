@@ -820,6 +820,38 @@ typedef struct cbo_hmc_chain {
 } cbo_hmc_chain;
 int cbo_gp_hmc_sets(int n_models, cbo_gp *const *gps, const cbo_hmc_chain *chains, int *status_out);
 
+/* Hyper-parameter MLE of every model by L-BFGS in ONE launch: causal_optimizer.lockstep_lbfgs without a box
+ * over the Logexp-transformed parameters -- restated in csrc/mle_search.h -- one search per RUN, a run being one (model,
+ * start) pair, every run inside mle_sets_kernel: a workgroup factors its model at each trial point of its search from the
+ * raw coordinates and evaluates the log marginal likelihood and its gradients there, with cbo_gp_lml_gradients' arithmetic.
+ * The iteration is lockstep_lbfgs', not scipy's L-BFGS-B (setulb): same stationary points, another path to them.
+ * Per model: n_starts rows of theta0 (n_params positive values each: variance, the lengthscale(s), and the noise variance
+ * when fit_noise = 1; a model whose noise is fixed has fit_noise = 0 and keeps its own), at most max_rounds rounds per run
+ * (max_rounds = 0 evaluates the starts and moves nothing).  Outputs per run s of the model: status_out[s] -- why the search
+ * ended, CBO_REFINE_PGTOL / FTOL / STEP / MAX_ROUNDS / NAN_START, or CBO_MLE_NOT_PD: the START's Ky was not positive definite
+ * as assembled (the launch cannot walk jitchol's ladder), nothing else of the run means anything and the caller repeats the
+ * model on the host; a TRIAL point of that kind counts as a failed step, as a non-finite value does --, rounds_out[s],
+ * theta_out (row s: the end point), lml_out[s] and grad_out (row s: d lml / d theta) there -- the likelihood and gradients
+ * cbo_gp_lml_gradients returns for the model at that theta, bit for bit.  The call does not choose among a model's runs.
+ * model_status_out[i]: CBO_OK, or CBO_MLE_DECLINED -- the model is not one the launch takes (more than 128 observations,
+ * fp32 data, CBO_HIP_SMALL_SETS=0): nothing else is written for it.  Models are only read: hyper-parameters, fitted state,
+ * caches and kept solutions stay as they were; no fit needed.
+ * CBO_ERR_INVALID before any device work: n_models <= 0, NULL arguments, handles or per-model pointers, models of different
+ * contexts, fit_noise other than 0 / 1, n_params other than 1 + (ARD ? d : 1) + fit_noise, n_starts outside
+ * 1..CBO_MLE_MAX_STARTS, max_rounds outside 0..CBO_MLE_MAX_ROUNDS, a theta0 entry that is not finite and positive, more than
+ * 65535 runs in all. */
+#define CBO_MLE_MAX_STARTS 16
+#define CBO_MLE_MAX_ROUNDS 4096
+#define CBO_MLE_DECLINED CBO_REFINE_DECLINED
+#define CBO_MLE_NOT_PD 6
+typedef struct cbo_mle_run {            /* one model: n_starts runs */
+    int n_params, fit_noise, n_starts, max_rounds;
+    const double *theta0;               /* n_starts x n_params, row 0 = the model's own start */
+    double *theta_out, *lml_out, *grad_out;   /* n_starts x n_params, n_starts, n_starts x n_params */
+    int *status_out, *rounds_out;       /* n_starts */
+} cbo_mle_run;
+int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_run *runs, int *model_status_out);
+
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
                        const double *prior_var_s, double y_best, int task, double ei_jitter,
