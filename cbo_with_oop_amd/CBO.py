@@ -109,17 +109,23 @@ class CBOAcquisitionPath:
     causal sets into that device call through a device-resident do-calculus prior.
     ``mle_optimizer="device"`` (with ``mle_restarts`` starts per model, 1..16) runs the hyper-parameter MLEs this path
     starts -- the one in front of the device HMC -- as one-launch searches; ``"host"`` (default) is scipy's
-    L-BFGS-B, unchanged."""
+    L-BFGS-B, unchanged.
+    ``hyper_priors`` (a dict ``"variance"`` / ``"lengthscale"`` / ``"noise_var"`` -> a prior of ``utils_functions.priors``):
+    every exploration-set model carries these priors whenever it is built or rebuilt (``HipGaussianProcess.set_prior``,
+    DESIGN.md §4w), so the MLEs and the HMC of this path work on the log posterior; ``None`` (default) sets none."""
 
     def __init__(self, gp_type, exploration_set, costs, task, data_x, data_y, space_list, mean_functions=None,
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
                  update_incumbent=False, refine=False, hyper_sampler="host", device_prior=False, mle_optimizer="host",
-                 mle_restarts=1):
+                 mle_restarts=1, hyper_priors=None):
         from .GaussianProcessFactory import checked_mle_optimizer
+        from .utils_functions.priors import checked_priors
         from .utils_functions.utils import checked_device_prior, checked_refine, sets_acquisition_or_default as sets_acquisition
         self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
         self.device_prior = checked_device_prior(device_prior, refine)
+        # priors on every exploration-set model's hyper-parameters (name -> prior), or None: today's behaviour
+        self.hyper_priors = checked_priors(hyper_priors) or None
         # what every exploration set is scored with: "EI" (the reference's) or a point-wise kind with its parameter
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
         self._kind = sets_acquisition(acquisition, acquisition_param)
@@ -174,7 +180,7 @@ class CBOAcquisitionPath:
         self._grids.clear()
         self.models = [
             GPFactory.create(self.gp_type, self.data_x[s], self.data_y[s],
-                             [self.mean_functions[s], self.var_functions[s]], emukit_wrapper=True)
+                             [self.mean_functions[s], self.var_functions[s]], emukit_wrapper=True, priors=self.hyper_priors)
             for s in range(self.es_size)
         ]
         if self.constraints:
@@ -237,7 +243,8 @@ class CBOAcquisitionPath:
         if old is not None:
             old[1].close()
         self.models[s] = GPFactory.create(self.gp_type, self.data_x[s], self.data_y[s],
-                                          [self.mean_functions[s], self.var_functions[s]], emukit_wrapper=True, fit=fit)
+                                          [self.mean_functions[s], self.var_functions[s]], emukit_wrapper=True, fit=fit,
+                                          priors=self.hyper_priors)
         self._draw_hyper_rows(s)
 
     @property
@@ -500,7 +507,10 @@ class CBO(CBOAcquisitionPath):
     ``mle_optimizer="device"`` (with ``mle_restarts`` starts per model, 1..16): every hyper-parameter MLE of the agent -- the
     graph GPs of ``run()``'s first fit and of ``observe()``, and the closing ``optimize()`` of ``intervene()``, the chosen
     set's constraint models included, in one call -- is a one-launch device search (DESIGN.md §4v) instead of scipy's
-    L-BFGS-B with a device call per evaluation; ``"host"`` (default) changes nothing."""
+    L-BFGS-B with a device call per evaluation; ``"host"`` (default) changes nothing.
+    ``hyper_priors`` (a dict ``"variance"`` / ``"lengthscale"`` / ``"noise_var"`` -> a prior of ``utils_functions.priors``):
+    priors on the hyper-parameters of every exploration-set model, applied whenever one is built or rebuilt (DESIGN.md §4w);
+    the graph-level GPs take none.  ``None`` (default): no priors, today's behaviour to the bit."""
 
     TARGET = "Y"
 
@@ -509,10 +519,12 @@ class CBO(CBOAcquisitionPath):
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
                  constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False,
-                 hyper_sampler="host", device_prior=False, mle_optimizer="host", mle_restarts=1):
+                 hyper_sampler="host", device_prior=False, mle_optimizer="host", mle_restarts=1, hyper_priors=None):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType, checked_mle_optimizer
         checked_mle_optimizer(mle_optimizer, mle_restarts)
+        from .utils_functions.priors import checked_priors
+        checked_priors(hyper_priors)                           # (on the host, before any device call)
         from .graphs import _columns
         from .utils_functions.utils import checked_refine, sets_acquisition_or_default as sets_acquisition
         self.graph = graph() if isinstance(graph, type) else graph
@@ -575,7 +587,8 @@ class CBO(CBOAcquisitionPath):
                          acquisition=acquisition, acquisition_param=acquisition_param, constraints=path_constraints,
                          constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
                          update_incumbent=update_incumbent, refine=refine, hyper_sampler=hyper_sampler,
-                         device_prior=device_prior, mle_optimizer=mle_optimizer, mle_restarts=mle_restarts)
+                         device_prior=device_prior, mle_optimizer=mle_optimizer, mle_restarts=mle_restarts,
+                         hyper_priors=hyper_priors)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions

@@ -118,6 +118,7 @@ class HipGaussianProcess:
         # explicitly (causal_kernels.py:53-55)
         self.zero_diag = (not self.causal) if zero_diag is None else bool(zero_diag)
         self._handle = ctypes.c_void_p()
+        self._priors = {}          # name -> utils_functions.priors.Prior (set_prior); the device handle holds the descriptors
         self._set_arrays(x, y)
         pm, pv = self._prior(self.X)
         _lib.check(self._lib.cbo_gp_create(
@@ -491,6 +492,51 @@ class HipGaussianProcess:
         self._last_lml = lml.value
         return dv.value, dls, dn.value
 
+    # -- priors on the hyper-parameters (GPy set_prior) ---------------------------------
+    @property
+    def priors(self):
+        """The priors as a dict name -> prior (``"variance"``, ``"lengthscale"``, ``"noise_var"``), a copy."""
+        return dict(self._priors)
+
+    def _upload_priors(self, priors):
+        from .utils_functions.priors import checked_priors, per_parameter
+        priors = checked_priors(priors, self.fix_noise)
+        row = per_parameter(priors, self.lengthscale.size)
+        desc = (_lib.CboHyperPrior * len(row))(*[p.descriptor() if p is not None else _lib.CboHyperPrior() for p in row])
+        _lib.check(self._lib.cbo_gp_set_priors(self._handle, len(row), desc))
+        self._priors = priors
+
+    def set_prior(self, name, prior):
+        """GPy ``model.<parameter>.set_prior(prior)``: ``name`` is ``"variance"``, ``"lengthscale"`` (one prior covers every
+        ARD lengthscale) or ``"noise_var"`` (ValueError for a model whose noise is fixed); ``prior`` a ``Gaussian``,
+        ``LogGaussian``, ``Gamma`` or ``InverseGamma`` of ``utils_functions.priors``.  The priors are state of the model:
+        ``set_data``, ``rebuild``, ``append``, ``set_hyperparameters`` and fits keep them.  From here on ``optimize`` (host
+        and device), ``optimize_restarts`` and the HMC work on the log posterior (``objective_function``)."""
+        self._upload_priors({**self._priors, name: prior})
+
+    def unset_priors(self, name=None):
+        """GPy ``unset_priors``: drop the prior on ``name``, or every prior.  A model without priors takes the code paths
+        and gives the bits of one that never had any."""
+        from .utils_functions.priors import PARAMETER_NAMES
+        if name is not None and name not in PARAMETER_NAMES:
+            raise ValueError(f"a prior goes on one of {PARAMETER_NAMES}, not {name!r}")
+        self._upload_priors({} if name is None else {k: v for k, v in self._priors.items() if k != name})
+
+    def log_prior(self):
+        """GPy ``model.log_prior()``: the sum of the priors' log densities at the current parameters plus the Logexp
+        log-Jacobian of every parameter that has a prior, evaluated on the device (``cbo_gp_log_prior_batch``); 0.0
+        without priors."""
+        return log_prior_batch([self])[0][0]
+
+    def log_prior_gradients(self):
+        """Its gradient with respect to (variance, lengthscale(s), noise variance) -- without the noise entry for a model
+        whose noise is fixed; zeros without priors."""
+        return log_prior_batch([self])[0][1]
+
+    def objective_function(self):
+        """GPy ``model.objective_function()``: ``-log_likelihood() - log_prior()``."""
+        return -self.log_likelihood() - self.log_prior()
+
     def _loo(self, want_mean=False, want_var=False, want_lpd=False):
         """``cbo_gp_loo`` of the fitted model: (mean, var, lpd, sum of lpd), None where not asked for."""
         self.ensure_fitted()
@@ -520,7 +566,10 @@ class HipGaussianProcess:
     def _objective(self, x, transform="log"):
         """(negative log marginal likelihood, its gradient with respect to x) at theta(x) = [variance, lengthscale(s),
         (noise)]: ``transform="logexp"``: theta = log(1 + exp(x)), paramz's ``Model._objective_grads`` with
-        ``_transform_gradients`` (gradient times 1 - exp(-theta)); ``"log"``: theta = exp(x)."""
+        ``_transform_gradients`` (gradient times 1 - exp(-theta)); ``"log"``: theta = exp(x).  A model with priors: the
+        negative log POSTERIOR -- the log prior and its gradient (one more device call) are added to the likelihood's before
+        the sign and the transform, as the device kernels add them; ``"logexp"`` only (ValueError otherwise)."""
+        _check_prior_transform(self, transform)
         x = np.asarray(x, dtype=np.float64)
         theta = logexp_f(x) if transform == "logexp" else np.exp(x)
         try:
@@ -530,7 +579,8 @@ class HipGaussianProcess:
             # paramz hands the optimiser inf and the clipped gradient of the last good point (and gives up after ten such
             # evaluations in a row); a large finite value keeps scipy's line search defined and is rejected the same way
             return 1e25, np.zeros_like(x)
-        return _objective_value(self, theta, self._last_lml, dv, dls, dn, transform)
+        prior = log_prior_batch([self])[0] if _has_priors(self) else None
+        return _objective_value(self, theta, self._last_lml, dv, dls, dn, transform, prior)
 
     def optimize(self, max_iters=1000, transform="logexp", optimizer="host", **kwargs):
         """Hyper-parameter MLE (emukit ``GPyModelWrapper.optimize`` -> GPy ``optimize_restarts(1, robust=True)`` -- one run from
@@ -559,7 +609,9 @@ class HipGaussianProcess:
         randomised starts (``mle_restart_starts``: paramz ``randomize()``, a standard normal in the Logexp space, numpy's
         global generator), the model left at the best end point.  Every start is one workgroup of ONE device launch
         (DESIGN.md §4v); ``optimizer="host"`` would be ``num_restarts`` optimiser runs one after another and is not offered
-        (ValueError for more than one start).  Returns the ``optimization_result``; its ``runs`` hold every start's record."""
+        (ValueError for more than one start).  Returns the ``optimization_result``; its ``runs`` hold every start's record.
+        A model with priors (``set_prior``): a parameter that has one is drawn from it, as paramz does, and the best end point
+        is the one with the highest log posterior (every run's ``lml`` then includes the log prior)."""
         return optimize_together([self], max_iters, "logexp", optimizer=optimizer, num_restarts=num_restarts)[0]
 
     def generate_hyperparameters_samples(self, n_samples=20, n_burnin=100, subsample_interval=10, step_size=1e-1,
@@ -651,9 +703,48 @@ def _batched(model):
     return model.dtype == "f64" and model.X.shape[0] <= 256
 
 
-def _objective_value(model, theta, lml, dv, dls, dn, transform):
-    """(-lml, -gradient with respect to x) from the likelihood and its gradients at theta(x)."""
+def _has_priors(model):
+    """The model carries at least one prior (a stand-in without the attribute carries none)."""
+    return bool(getattr(model, "_priors", None))
+
+
+def _check_prior_transform(model, transform):
+    if transform != "logexp" and _has_priors(model):
+        raise ValueError("a model with priors is optimised over the Logexp-transformed parameters (the log prior carries "
+                         "that constraint's Jacobian): transform must be 'logexp'")
+
+
+def log_prior_batch(models, thetas=None):
+    """``(log_prior, its gradient with respect to theta)`` of many models in one device call (``cbo_gp_log_prior_batch``:
+    one lane per model evaluates csrc/hyper_prior.h).  ``thetas[k]``: the row (variance, lengthscale(s), and the noise
+    variance unless the model's noise is fixed) to evaluate model k at, None -- or ``thetas=None`` for all -- for its own
+    parameters.  The gradient has the row's entries.  A model without priors answers (0.0, zeros)."""
+    k = len(models)
+    lib = _lib.load()
+    handles = (ctypes.c_void_p * k)(*[m._handle for m in models])
+    rows, ptrs = [], (_lib.c_double_p * k)()
+    for j, m in enumerate(models):
+        t = None if thetas is None or thetas[j] is None else np.asarray(thetas[j], dtype=np.float64).reshape(-1)
+        if t is not None:
+            t = np.ascontiguousarray(np.append(t, m.noise_var) if m.fix_noise else t)
+            if t.size != 2 + m.lengthscale.size:
+                raise ValueError(f"theta of model {j} must have {2 + m.lengthscale.size - int(m.fix_noise)} entries")
+            ptrs[j] = ctypes.cast(_lib.dptr(t), _lib.c_double_p)
+        rows.append(t)
+    lp, grad = np.zeros(k), np.zeros((k, _lib.HMC_MAX_PARAMS))
+    status = np.zeros(k, dtype=np.int32)
+    _lib.check(lib.cbo_gp_log_prior_batch(k, handles, ptrs, _lib.dptr(lp), _lib.dptr(grad),
+                                          status.ctypes.data_as(_lib.c_int_p)))
+    return [(float(lp[j]), grad[j, :1 + m.lengthscale.size + (0 if m.fix_noise else 1)].copy())
+            for j, m in enumerate(models)]
+
+
+def _objective_value(model, theta, lml, dv, dls, dn, transform, prior=None):
+    """(-lml, -gradient with respect to x) from the likelihood and its gradients at theta(x); ``prior`` = (log prior, its
+    gradient with respect to theta): added first, so the pair is the negative log posterior's."""
     g = np.asarray([dv, *dls] + ([] if model.fix_noise else [dn]), dtype=np.float64)
+    if prior is not None:
+        lml, g = lml + prior[0], g + prior[1]
     g = g * (logexp_gradfactor(theta) if transform == "logexp" else theta)
     return -lml, -g
 
@@ -662,6 +753,7 @@ def _optimizer_start(model, transform):
     """(theta0, x0) of ``optimize``."""
     if transform not in ("logexp", "log"):
         raise ValueError("transform must be 'logexp' (GPy / paramz) or 'log'")
+    _check_prior_transform(model, transform)
     theta0 = [model.variance, *model.lengthscale]
     if not model.fix_noise:
         theta0.append(model.noise_var)
@@ -729,11 +821,31 @@ def checked_mle_optimizer(optimizer, num_restarts=1):
     return optimizer
 
 
-def mle_restart_starts(P, num_restarts):
+def mle_restart_starts(P, num_restarts, priors=None, fit_noise=True):
     """The randomised starts of ``optimize_restarts``: ``num_restarts - 1`` rows ``x = np.random.randn(P)`` in the Logexp
     space (paramz ``randomize()``: a standard normal for every transformed parameter), one ``randn(P)`` call per row from
-    numpy's global generator; (num_restarts - 1, P).  One start draws nothing."""
-    return np.array([np.random.randn(P) for _ in range(int(num_restarts) - 1)], dtype=np.float64).reshape(-1, P)
+    numpy's global generator; (num_restarts - 1, P).  One start draws nothing.
+    ``priors`` (a dict name -> prior, as ``HipGaussianProcess.priors``): paramz draws a parameter that has a prior FROM the
+    prior.  Per row, after its ``randn(P)``: in the order variance, lengthscale, noise variance, one ``prior.rvs(size)`` per
+    parameter that has a prior (size = the number of lengthscales, P - 1 - ``fit_noise``, for that one, else 1; the noise
+    only when ``fit_noise``: the row's last entry) replaces those entries of theta = ``logexp_f(x)`` -- the row keeps
+    ``x = logexp_finv(drawn)`` there.  A drawn value that is not positive and finite -- possible under a Gaussian prior --
+    keeps the ``randn`` entry: ``cbo_gp_mle_sets`` refuses such starts (a deviation from paramz, which would hand it to
+    the model).  Without priors nothing changes, the generator's consumption included."""
+    rows = []
+    n_ls = int(P) - 1 - int(bool(fit_noise))
+    slots = (("variance", 0, 1), ("lengthscale", 1, n_ls)) + ((("noise_var", 1 + n_ls, 1),) if fit_noise else ())
+    for _ in range(int(num_restarts) - 1):
+        x = np.random.randn(P)
+        for name, lo, size in slots if priors else ():
+            if name not in priors:
+                continue
+            drawn = np.asarray(priors[name].rvs(size), dtype=np.float64).reshape(-1)
+            ok = np.isfinite(drawn) & (drawn > 0.0)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                x[lo:lo + size] = np.where(ok, logexp_finv(np.where(ok, drawn, 1.0)), x[lo:lo + size])
+        rows.append(x)
+    return np.array(rows, dtype=np.float64).reshape(-1, P)
 
 
 def mle_best_run(lmls, statuses):
@@ -786,7 +898,7 @@ def _optimize_on_device(models, max_iters, num_restarts, host_fallback):
     theta0s = []
     for m in models:                                           # (the draws: per model, in model order, before the call)
         theta0, _ = _optimizer_start(m, "logexp")
-        extra = mle_restart_starts(theta0.size, num_restarts)
+        extra = mle_restart_starts(theta0.size, num_restarts, getattr(m, "_priors", None) or None, not m.fix_noise)
         theta0s.append(np.vstack([theta0[None], logexp_f(extra)]) if extra.size else theta0[None])
     answers = mle_runs_device(models, theta0s, max_rounds)
     results = [None] * len(models)
@@ -834,7 +946,11 @@ def optimize_together(models, max_iters=1000, transform="logexp", optimizer="hos
     at a non-finite start keeps its parameters.  A model the call declined (more than 128 observations, fp32,
     ``CBO_HIP_SMALL_SETS=0``) or whose own start has a Ky that is not positive definite as assembled goes through the
     lockstep route described above inside the same call (``host_fallback=False``: RuntimeError instead).
-    ``transform="log"`` with ``"device"``, and ``num_restarts`` > 1 with ``"host"``, raise ValueError."""
+    ``transform="log"`` with ``"device"``, and ``num_restarts`` > 1 with ``"host"``, raise ValueError.
+    Models with priors (``set_prior``): both routes minimise ``-log_likelihood - log_prior`` -- the device
+    launch adds the prior inside the kernel, the host route through one ``log_prior_batch`` call per round for all models --
+    ``fun`` is that objective, the restarts draw such parameters from their priors, and ``transform="log"`` raises
+    ValueError."""
     from .utils_functions.lockstep_lbfgsb import lockstep_fmin_l_bfgs_b
     models = list(models)
     checked_mle_optimizer(optimizer, num_restarts)
@@ -864,8 +980,12 @@ def optimize_together(models, max_iters=1000, transform="logexp", optimizer="hos
                 continue
             batch.append((j, k, x, theta))
         answers = lml_gradients_batch([models[k] for _, k, _, _ in batch])
-        for (j, k, x, theta), a in zip(batch, answers):
-            values[j] = (1e25, np.zeros_like(x)) if a is None else _objective_value(models[k], theta, *a, transform)
+        # the models sit at their thetas: one more call for every model's log prior (none without priors)
+        priors = log_prior_batch([models[k] for _, k, _, _ in batch]) if any(_has_priors(models[k]) for _, k, _, _ in batch) \
+            else [None] * len(batch)
+        for (j, k, x, theta), a, pr in zip(batch, answers, priors):
+            pr = pr if _has_priors(models[k]) else None
+            values[j] = (1e25, np.zeros_like(x)) if a is None else _objective_value(models[k], theta, *a, transform, pr)
         return values
 
     runs = lockstep_fmin_l_bfgs_b(evaluate, [x0 for _, x0 in starts], maxfun=int(max_iters), maxiter=int(max_iters))
@@ -960,10 +1080,11 @@ class GaussianProcessFactory:
     """src/GaussianProcessFactory.py:18-73, same static methods."""
 
     @staticmethod
-    def create(gp_type, x, y, parameters=None, emukit_wrapper=False, fit=True, dtype=None):
+    def create(gp_type, x, y, parameters=None, emukit_wrapper=False, fit=True, dtype=None, priors=None):
         """``fit=False`` (not in the reference) builds the model without fitting it; the first acquisition sweep
         then refits and sweeps in one overlapped call.  ``dtype="f32"`` (not in the reference either; default from
-        ``CBO_HIP_DTYPE``, else "f64") selects the fp32 sweep."""
+        ``CBO_HIP_DTYPE``, else "f64") selects the fp32 sweep.  ``priors`` (a dict name -> prior, not in the reference:
+        its models have none) are set on the new model (``HipGaussianProcess.set_prior``)."""
         gp_functions = {
             GaussianProcessType.GRAPH_GP: GaussianProcessFactory.create_graph_gp,
             GaussianProcessType.CAUSAL_GP: GaussianProcessFactory.create_causal_gp,
@@ -971,7 +1092,10 @@ class GaussianProcessFactory:
         }
         # emukit_wrapper only selected the wrapper class in the reference; HipGaussianProcess answers
         # both interfaces, so the flag changes nothing here.
-        return gp_functions[gp_type](x, y, parameters, fit=fit, dtype=dtype)
+        model = gp_functions[gp_type](x, y, parameters, fit=fit, dtype=dtype)
+        for name, prior in (priors or {}).items():
+            model.set_prior(name, prior)
+        return model
 
     @staticmethod
     def create_graph_gp(x, y, parameters, fit=True, dtype=None):

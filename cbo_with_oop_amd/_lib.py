@@ -52,6 +52,7 @@ MLE_DECLINED, MLE_NOT_PD = REFINE_DECLINED, 6   # CBO_MLE_*: beside the CBO_REFI
 REFINE_STATUS_NAME = {REFINE_PGTOL: "pgtol", REFINE_FTOL: "ftol", REFINE_STEP: "step", REFINE_MAX_ROUNDS: "max_rounds",
                       REFINE_NAN_START: "nan_start", REFINE_DECLINED: "declined"}
 MLE_STATUS_NAME = {**REFINE_STATUS_NAME, MLE_NOT_PD: "not_pd"}
+PRIOR_NONE, PRIOR_GAUSSIAN, PRIOR_LOGGAUSSIAN, PRIOR_GAMMA, PRIOR_INVGAMMA = range(5)   # CBO_PRIOR_*
 
 
 class CboTimers(ctypes.Structure):
@@ -96,6 +97,12 @@ class CboMleRun(ctypes.Structure):
     _fields_ = [("n_params", ctypes.c_int), ("fit_noise", ctypes.c_int), ("n_starts", ctypes.c_int),
                 ("max_rounds", ctypes.c_int), ("theta0", c_double_p), ("theta_out", c_double_p), ("lml_out", c_double_p),
                 ("grad_out", c_double_p), ("status_out", c_int_p), ("rounds_out", c_int_p)]
+
+
+class CboHyperPrior(ctypes.Structure):
+    """struct cbo_hyper_prior of include/cbo_hip.h."""
+    _fields_ = [("kind", ctypes.c_int), ("pad_", ctypes.c_int), ("p0", ctypes.c_double), ("p1", ctypes.c_double),
+                ("constant", ctypes.c_double)]
 
 
 class CboHipError(RuntimeError):
@@ -211,6 +218,10 @@ SIGNATURES = {
     "cbo_do_prior_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_hmc_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboHmcChain), c_int_p]),
     "cbo_gp_mle_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboMleRun), c_int_p]),
+    "cbo_gp_set_priors": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(CboHyperPrior)]),
+    "cbo_gp_get_priors": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(CboHyperPrior)]),
+    "cbo_gp_log_prior_batch": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(c_double_p), c_double_p, c_double_p,
+                                              c_int_p]),
     "cbo_gp_mes_gumbel_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_double_p]),
     "cbo_comm_gather_i64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_int64_p]),

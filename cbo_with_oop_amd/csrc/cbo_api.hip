@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cbo_internal.h"
+#include "hyper_prior.h"
 #include "lml_outputs.h"
 #include "schedule_tuner.h"
 
@@ -186,6 +187,7 @@ struct cbo_ctx {
     PinnedBuf<double> mle_final;
     PinnedBuf<int> mle_status, mle_rounds;
     GrowBuf<double> mle_rings;
+    PinnedBuf<cbo_prior_item> prior_host;              // cbo_gp_log_prior_batch: one item per model, read and written by the kernel
     GrowBuf<double> append_part;                       // block append: slice sums of the pass over V [slices][kp][m_pad]
     GrowBuf<BatchState> batch_state;
     PinnedBuf<double> batch_h_vals; PinnedBuf<int64_t> batch_h_idxs;
@@ -245,6 +247,9 @@ struct cbo_gp {
     int64_t n32 = 0, ldu32 = 0;
     float *Uf = nullptr, *invF = nullptr;
     uint64_t f32_stamp = 0;          // fit stamp the copies belong to
+    // cbo_gp_set_priors: one descriptor per parameter (variance, lengthscale(s), noise variance), or empty -- no priors.
+    // Nothing but cbo_gp_set_priors writes it: data, hyper-parameters and fits leave it alone.
+    std::vector<cbo_hyper_prior> priors;
 };
 
 struct cbo_cands {
@@ -3988,6 +3993,112 @@ extern "C" int cbo_gp_lml_gradients_batch(int n_models, cbo_gp *const *gps, doub
         });
 }
 
+// ---- priors on the hyper-parameters (hyper_prior.h, kernels_prior.hip) ---------------------------------------
+static int prior_params(const cbo_gp *g) { return 2 + (g->h.ard ? g->d : 1); }
+
+extern "C" int cbo_gp_set_priors(cbo_gp *g, int n_params, const cbo_hyper_prior *priors)
+{
+    if (!g) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (n_params != prior_params(g))
+        return fail(CBO_ERR_INVALID, "n_params must be " + std::to_string(prior_params(g)) +
+                                         " (variance, the lengthscale(s), the noise variance)");
+    bool any = false;
+    for (int k = 0; priors && k < n_params; ++k) {
+        const cbo_hyper_prior &p = priors[k];
+        const std::string where = " (parameter " + std::to_string(k) + ")";
+        if (p.kind == CBO_PRIOR_NONE) continue;
+        if (p.kind != CBO_PRIOR_GAUSSIAN && p.kind != CBO_PRIOR_LOGGAUSSIAN && p.kind != CBO_PRIOR_GAMMA &&
+            p.kind != CBO_PRIOR_INVGAMMA)
+            return fail(CBO_ERR_INVALID, "unknown prior kind " + std::to_string(p.kind) + where);
+        if (!std::isfinite(p.p0) || !std::isfinite(p.p1)) return fail(CBO_ERR_INVALID, "a prior's parameters must be finite" + where);
+        if (!std::isfinite(p.constant)) return fail(CBO_ERR_INVALID, "a prior's constant must be finite" + where);
+        const bool normal = p.kind == CBO_PRIOR_GAUSSIAN || p.kind == CBO_PRIOR_LOGGAUSSIAN;
+        if (normal && !(p.p1 > 0.0)) return fail(CBO_ERR_INVALID, "sigma must be positive" + where);
+        if (!normal && !(p.p0 > 0.0)) return fail(CBO_ERR_INVALID, "a must be positive" + where);
+        if (!normal && !(p.p1 > 0.0)) return fail(CBO_ERR_INVALID, "b must be positive" + where);
+        any = true;
+    }
+    g->priors.clear();
+    if (any) {
+        g->priors.assign(priors, priors + n_params);
+        for (cbo_hyper_prior &p : g->priors) {
+            p.pad_ = 0;
+            if (p.kind == CBO_PRIOR_NONE) p.p0 = p.p1 = p.constant = 0.0;
+        }
+    }
+    return CBO_OK;
+}
+
+extern "C" int cbo_gp_get_priors(const cbo_gp *g, int n_params, cbo_hyper_prior *priors_out)
+{
+    if (!g || !priors_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (n_params != prior_params(g))
+        return fail(CBO_ERR_INVALID, "n_params must be " + std::to_string(prior_params(g)) +
+                                         " (variance, the lengthscale(s), the noise variance)");
+    for (int k = 0; k < n_params; ++k) priors_out[k] = g->priors.empty() ? cbo_hyper_prior{} : g->priors[(size_t)k];
+    return CBO_OK;
+}
+
+// The first n_params descriptors of a model's priors into a run's descriptor (the rest stay NONE); how many are priors.
+static int copy_run_priors(const cbo_gp *g, int n_params, cbo_hyper_prior *out)
+{
+    if (g->priors.empty()) return 0;
+    for (int k = 0; k < n_params; ++k) out[k] = g->priors[(size_t)k];
+    return hyper_prior_count(out, n_params);
+}
+
+extern "C" int cbo_gp_log_prior_batch(int n_models, cbo_gp *const *gps, const double *const *thetas, double *lp_out,
+                                      double *grad_out, int *status)
+{
+    if (n_models <= 0 || !gps || !lp_out || !grad_out || !status) return fail(CBO_ERR_INVALID, "bad argument");
+    int rc = check_model_handles(n_models, gps);
+    if (rc != CBO_OK) return rc;
+    for (int i = 0; i < n_models; ++i) {
+        const double *t = thetas ? thetas[i] : nullptr;
+        for (int k = 0; t && k < prior_params(gps[i]); ++k)
+            if (!std::isfinite(t[k])) return fail(CBO_ERR_INVALID, "theta must be finite (model " + std::to_string(i) + ")");
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    bool any = false;
+    for (int i = 0; i < n_models; ++i) any = any || !gps[i]->priors.empty();
+    for (int i = 0; i < n_models; ++i) {
+        lp_out[i] = 0.0;
+        status[i] = CBO_OK;
+        for (int k = 0; k < CBO_HMC_MAX_PARAMS; ++k) grad_out[(size_t)i * CBO_HMC_MAX_PARAMS + (size_t)k] = 0.0;
+    }
+    if (!any) return CBO_OK;                                    // (nothing to evaluate: 0 and zeros)
+    rc = grow(c, c->prior_host, n_models < 32 ? (size_t)32 : (size_t)n_models);
+    if (rc != CBO_OK) return rc;
+    for (int i = 0; i < n_models; ++i) {
+        const cbo_gp *g = gps[i];
+        cbo_prior_item &it = c->prior_host[i];
+        std::memset(&it, 0, sizeof(it));
+        const int P = prior_params(g), n_ls = P - 2;
+        it.n_params = g->priors.empty() ? 0 : P;
+        copy_run_priors(g, P, it.priors);
+        const double *t = thetas ? thetas[i] : nullptr;
+        if (t) {
+            std::memcpy(it.theta, t, sizeof(double) * (size_t)P);
+        } else {
+            it.theta[0] = g->h.variance;
+            for (int k = 0; k < n_ls; ++k) it.theta[1 + k] = g->ls[(size_t)k];
+            it.theta[1 + n_ls] = g->noise_var;
+        }
+    }
+    launch_log_prior(c->stream, c->prior_host, n_models);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int i = 0; i < n_models; ++i) {
+        const cbo_prior_item &it = c->prior_host[i];
+        if (!it.done) return fail(CBO_ERR_HIP, "log prior kernel: no answer for a model it was given");
+        lp_out[i] = it.lp;
+        std::memcpy(grad_out + (size_t)i * CBO_HMC_MAX_PARAMS, it.dlp, sizeof(double) * CBO_HMC_MAX_PARAMS);
+    }
+    return CBO_OK;
+}
+
 // ---- every model's HMC chain over its hyper-parameters (kernels_hmc.hip) ------------------------------------
 // One launch for every model small_lml_gradients would take; the others are declined here, their status alone written.  The
 // models are only read.  Of the routing policy (§4r) this call uses partition_small, ensure_small_buffers and
@@ -4071,6 +4182,7 @@ extern "C" int cbo_gp_hmc_sets(int n_models, cbo_gp *const *gps, const cbo_hmc_c
         hm.draw_off = draws; hm.row_off = rows; hm.acc_off = flags;
         hm.n_params = ch.n_params; hm.n_ls = gps[i]->h.ard ? gps[i]->d : 1; hm.sample_noise = ch.sample_noise;
         hm.num_samples = ch.num_samples; hm.hmc_iters = ch.hmc_iters;
+        hm.n_prior = copy_run_priors(gps[i], ch.n_params, hm.priors);
         const size_t np = (size_t)ch.num_samples * (size_t)ch.n_params;
         std::memcpy(c->hmc_draws.p + draws, ch.momenta, sizeof(double) * np);
         std::memcpy(c->hmc_draws.p + draws + np, ch.uniforms, sizeof(double) * (size_t)ch.num_samples);
@@ -4167,6 +4279,7 @@ extern "C" int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_r
             std::memcpy(rn.theta0, r.theta0 + (size_t)s * (size_t)r.n_params, sizeof(double) * (size_t)r.n_params);
             rn.model = j; rn.n_params = r.n_params; rn.n_ls = gps[i]->h.ard ? gps[i]->d : 1; rn.fit_noise = r.fit_noise;
             rn.max_rounds = r.max_rounds;
+            rn.n_prior = copy_run_priors(gps[i], r.n_params, rn.priors);
             c->mle_status[q] = kNoStatus;
         }
     }

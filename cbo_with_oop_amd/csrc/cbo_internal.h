@@ -438,7 +438,9 @@ struct cbo_small_hmc {
     double theta0[CBO_HMC_MAX_PARAMS];
     double stepsize;
     int64_t draw_off, row_off, acc_off;
-    int n_params, n_ls, sample_noise, num_samples, hmc_iters, pad_;
+    int n_params, n_ls, sample_noise, num_samples, hmc_iters;
+    int n_prior;                                   // how many of priors[0..n_params) are not NONE; 0: the stage is skipped
+    cbo_hyper_prior priors[CBO_HMC_MAX_PARAMS];    // the model's priors in the row's order (hyper_prior.h)
 };
 // sets / chains / draws and the four outputs may be pinned host memory; scratch: `stride` >= small_lml_scratch_doubles()
 // doubles per model; info: n_models ints, zero on entry and zero again afterwards.  final_out: per model theta
@@ -452,7 +454,9 @@ void launch_hmc_sets(hipStream_t s, const cbo_small_set *sets, const cbo_small_h
 // (pinned, device-mapped: read by the kernel directly).  n_params = 1 + n_ls + fit_noise.
 struct cbo_small_mle {
     double theta0[CBO_HMC_MAX_PARAMS];
-    int model, n_params, n_ls, fit_noise, max_rounds, pad_;
+    int model, n_params, n_ls, fit_noise, max_rounds;
+    int n_prior;                                   // how many of priors[0..n_params) are not NONE; 0: the stage is skipped
+    cbo_hyper_prior priors[CBO_HMC_MAX_PARAMS];    // the model's priors in the row's order (hyper_prior.h)
 };
 // a run's two rings of curvature pairs (mle_search.h): S then Y, 8 pairs x CBO_HMC_MAX_PARAMS doubles each
 constexpr int kMleRingDoubles = 2 * 8 * CBO_HMC_MAX_PARAMS;
@@ -464,6 +468,16 @@ constexpr int kMleRingDoubles = 2 * 8 * CBO_HMC_MAX_PARAMS;
 void launch_mle_sets(hipStream_t s, const cbo_small_set *sets, int n_models, const cbo_small_mle *runs, int n_runs,
                      double *scratch, int64_t stride, int *info, double *rings, double *final_out, int *status_out,
                      int *rounds_out);
+// ---- the hyper-parameters' log prior of many models in one launch (kernels_prior.hip) -------------------------
+// One lane per model: hyper_prior_at over the model's n_params entries at theta.  items (pinned, device-mapped) are read and
+// written by the kernel directly; the caller synchronises the stream before it reads lp / dlp.
+struct cbo_prior_item {
+    cbo_hyper_prior priors[CBO_HMC_MAX_PARAMS];
+    double theta[CBO_HMC_MAX_PARAMS];
+    double lp, dlp[CBO_HMC_MAX_PARAMS];
+    int n_params, done;                            // done: 0 on entry, 1 once lp / dlp are written
+};
+void launch_log_prior(hipStream_t s, cbo_prior_item *items, int n_models);
 // the same launch with the batch epilogue (kernels_sets_batch.hip, small_sets_batch_kernel): batch_size >= 2
 // Kriging-believer picks per set.  Sets of at most kSmallBatchMaxCands candidates: the set's V = L^-1 K* stays in global
 // scratch (1 MiB per set at the cap) and the call's widest set has at most 16 candidate blocks.  batch_scratch:

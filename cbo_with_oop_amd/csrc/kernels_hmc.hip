@@ -11,6 +11,8 @@
 //   thread 0 turns them into the likelihood and its gradients with the host's own arithmetic (lml_outputs.h) and advances
 //   the chain (hmc_feed): two multiply-adds per parameter between two evaluations.
 // The likelihood at a position is therefore what cbo_gp_lml_gradients answers for the model at those hyper-parameters.
+// A chain whose model has priors (cbo_gp_set_priors): thread 0 adds the log prior and its gradient at theta
+// (hyper_prior_at, hyper_prior.h) to that pair, one IEEE addition each, before hmc_feed -- the chain samples the posterior.
 // A position whose Ky is not positive definite as assembled ends the chain with CBO_HMC_NOT_PD (jitchol's ladder lives on
 // the host: the caller repeats the chain there).  Nothing resident is written but the workgroup's scratch slot.
 // Every loop is bounded: the positions by 1 + num_samples * hmc_iters, the chain's own loops by num_samples and P.
@@ -18,17 +20,20 @@
 
 #include "cbo_small_lml_device.h"
 #include "hmc_chain.h"
+#include "hyper_prior.h"
 #include "lml_outputs.h"
 
 namespace cbo {
 
 static_assert(sizeof(SmallShared) + 4 * kSmallLmlTerms * sizeof(double) + sizeof(HmcChain) + kHmcMaxParams * sizeof(double)
-                  <= 163840,
-              "the workgroup's static LDS (the reduction's partial sums, the chain's state, the published theta) beside "
-              "SmallShared: one CU");
+                  + kHmcMaxParams * (sizeof(cbo_hyper_prior) + sizeof(double)) <= 163840,
+              "the workgroup's static LDS (the reduction's partial sums, the chain's state, the published theta, the priors "
+              "and their gradient) beside SmallShared: one CU");
 static_assert(kHmcMaxParams == CBO_MAX_DIM + 2, "variance, one lengthscale per dimension, noise variance");
 
-template <bool BYVAL>
+// PRIOR: some run of the launch has a prior (hyper_prior.h).  The instantiation without is the kernel as it
+// was before priors existed: a launch without priors runs that code and gives those bits.
+template <bool BYVAL, bool PRIOR>
 __global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
                                                        const cbo_small_hmc *__restrict__ chains,
                                                        const double *__restrict__ draws, double *scratch, int64_t stride,
@@ -41,13 +46,15 @@ __global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval,
     __shared__ double red[4][kSmallLmlTerms];
     __shared__ HmcChain chain;
     __shared__ double theta_row[kHmcMaxParams];
+    __shared__ cbo_hyper_prior priors[kHmcMaxParams];             // thread 0's alone, filled when the chain has a prior
+    __shared__ double prior_grad[kHmcMaxParams];                       // ... and d log prior / d theta at the evaluated row
     const int b = blockIdx.x;
     const cbo_small_set st = BYVAL ? byval.s[b] : sets[b];
     const cbo_small_hmc &hm = chains[b];
     const int tid = threadIdx.x;
     const int tiles = (st.n + 15) / 16;
     const int n_ls = hm.n_ls, P = hm.n_params, sample_noise = hm.sample_noise;
-    const int num_samples = hm.num_samples, hmc_iters = hm.hmc_iters;
+    const int num_samples = hm.num_samples, hmc_iters = hm.hmc_iters, n_prior = hm.n_prior;
     double *Us = scratch + (int64_t)b * stride, *invs = Us + 128 * kSmallLd, *Vg = Us + kSmallScratch;
     double *alpha_s = sh.sq;                                      // (|x|^2 is the assembly's alone: free behind the factor)
     const double *momenta = draws + hm.draw_off, *uniforms = momenta + (int64_t)num_samples * P;
@@ -62,6 +69,8 @@ __global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval,
     };
     if (tid == 0) {
         hmc_begin(chain, P, hm.theta0, num_samples, hmc_iters, hm.stepsize);
+        if (PRIOR && n_prior > 0)
+            for (int k = 0; k < P; ++k) priors[k] = hm.priors[k];
         publish();
     }
     __syncthreads();
@@ -84,6 +93,14 @@ __global__ __launch_bounds__(256) void hmc_sets_kernel(const SmallSetArgs byval,
             double lml, dl[kHmcMaxParams], dnoise;
             small_lml_outputs_at(st, row, red, &lml, dl, &dnoise);
             if (sample_noise) dl[1 + n_ls] = dnoise;
+            if (PRIOR && n_prior > 0) {                           // (a chain without priors: no stage, no + 0.0)
+                double lp;
+                hyper_prior_at(priors, P, row, &lp, prior_grad);
+                lml = lml + lp;                                   // the log posterior and its gradient: one IEEE addition each
+#pragma unroll
+                for (int k = 0; k < kHmcMaxParams; ++k)
+                    if (k < P) dl[k] = dl[k] + prior_grad[k];
+            }
             hmc_feed(chain, lml, dl, momenta, uniforms, rows, accepts);
             publish();
         }
@@ -106,19 +123,19 @@ void launch_hmc_sets(hipStream_t s, const cbo_small_set *sets, const cbo_small_h
                      double *scratch, int64_t stride, int *info, double *rows_out, int *accept_out, double *final_out,
                      int *status_out)
 {
-    static std::atomic<unsigned long long> opted[2] = {{0}, {0}};
+    static std::atomic<unsigned long long> opted[2][2] = {{{0}, {0}}, {{0}, {0}}};
     const bool byval = n_models <= kSmallByValue;
-    small_lds_opt_in(byval ? reinterpret_cast<const void *>(hmc_sets_kernel<true>)
-                           : reinterpret_cast<const void *>(hmc_sets_kernel<false>), opted[byval]);
+    bool prior = false;
+    for (int j = 0; j < n_models; ++j) prior = prior || chains[j].n_prior > 0;
     SmallSetArgs args{};
-    if (byval) {
-        std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_models);
-        hipLaunchKernelGGL(hmc_sets_kernel<true>, dim3((unsigned)n_models), dim3(256), sizeof(SmallShared), s, args, sets,
-                           chains, draws, scratch, stride, info, rows_out, accept_out, final_out, status_out);
-    } else {
-        hipLaunchKernelGGL(hmc_sets_kernel<false>, dim3((unsigned)n_models), dim3(256), sizeof(SmallShared), s, args, sets,
-                           chains, draws, scratch, stride, info, rows_out, accept_out, final_out, status_out);
-    }
+    if (byval) std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_models);
+    auto launch = [&](auto kernel) {
+        small_lds_opt_in(reinterpret_cast<const void *>(kernel), opted[byval][prior]);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n_models), dim3(256), sizeof(SmallShared), s, args,
+                           sets, chains, draws, scratch, stride, info, rows_out, accept_out, final_out, status_out);
+    };
+    if (byval) prior ? launch(hmc_sets_kernel<true, true>) : launch(hmc_sets_kernel<true, false>);
+    else prior ? launch(hmc_sets_kernel<false, true>) : launch(hmc_sets_kernel<false, false>);
 }
 
 }  // namespace cbo

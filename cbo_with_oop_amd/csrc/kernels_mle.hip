@@ -8,6 +8,8 @@
 //   thread 0 turns them into the likelihood and its gradients with the host's own arithmetic (lml_outputs.h) and advances
 //   the search (mle_feed).
 // The likelihood at a trial point is therefore what cbo_gp_lml_gradients answers for the model at those hyper-parameters.
+// A run whose model has priors (cbo_gp_set_priors): thread 0 adds the log prior and its gradient at theta
+// (hyper_prior_at, hyper_prior.h) to that pair, one IEEE addition each, before mle_feed -- the search maximises the posterior.
 // A TRIAL point whose Ky is not positive definite as assembled is fed as a non-finite value: an Armijo failure, the step
 // halves (what _objective's 1e25 does to scipy); the info word is cleared.  At the START it ends the run with
 // CBO_MLE_NOT_PD (jitchol's ladder lives on the host: the caller repeats that model there).
@@ -17,17 +19,20 @@
 #include <cstring>
 
 #include "cbo_small_lml_device.h"
+#include "hyper_prior.h"
 #include "mle_search.h"
 
 namespace cbo {
 
 static_assert(sizeof(SmallShared) + 4 * kSmallLmlTerms * sizeof(double) + sizeof(MleSearch) + kMleMaxParams * sizeof(double)
-                  <= 163840,
-              "the workgroup's static LDS (the reduction's partial sums, the search's state, the published theta) beside "
-              "SmallShared: one CU");
+                  + kMleMaxParams * (sizeof(cbo_hyper_prior) + sizeof(double)) <= 163840,
+              "the workgroup's static LDS (the reduction's partial sums, the search's state, the published theta, the priors "
+              "and their gradient) beside SmallShared: one CU");
 static_assert(kMleMaxParams == CBO_MAX_DIM + 2, "variance, one lengthscale per dimension, noise variance");
 
-template <bool BYVAL>
+// PRIOR: some run of the launch has a prior (hyper_prior.h).  The instantiation without is the kernel as it
+// was before priors existed: a launch without priors runs that code and gives those bits.
+template <bool BYVAL, bool PRIOR>
 __global__ __launch_bounds__(256) void mle_sets_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
                                                        const cbo_small_mle *__restrict__ runs, double *scratch, int64_t stride,
                                                        int *__restrict__ info, double *__restrict__ rings,
@@ -39,12 +44,15 @@ __global__ __launch_bounds__(256) void mle_sets_kernel(const SmallSetArgs byval,
     __shared__ double red[4][kSmallLmlTerms];
     __shared__ MleSearch search;
     __shared__ double theta_row[kMleMaxParams];
+    __shared__ cbo_hyper_prior priors[kMleMaxParams];             // thread 0's alone, filled when the run has a prior
+    __shared__ double prior_grad[kMleMaxParams];                       // ... and d log prior / d theta at the evaluated row
     const int b = blockIdx.x;
     const cbo_small_mle &rn = runs[b];
     const cbo_small_set st = BYVAL ? byval.s[rn.model] : sets[rn.model];
     const int tid = threadIdx.x;
     const int tiles = (st.n + 15) / 16;
     const int n_ls = rn.n_ls, P = rn.n_params, fit_noise = rn.fit_noise, max_rounds = rn.max_rounds;
+    const int n_prior = rn.n_prior;
     double *Us = scratch + (int64_t)b * stride, *invs = Us + 128 * kSmallLd, *Vg = Us + kSmallScratch;
     double *alpha_s = sh.sq;                                      // (|x|^2 is the assembly's alone: free behind the factor)
     double *ring = rings + (int64_t)b * kMleRingDoubles;
@@ -57,6 +65,8 @@ __global__ __launch_bounds__(256) void mle_sets_kernel(const SmallSetArgs byval,
     };
     if (tid == 0) {
         mle_begin(search, P, rn.theta0, ring, ring + kRefineHistory * kMleMaxParams);
+        if (PRIOR && n_prior > 0)
+            for (int k = 0; k < P; ++k) priors[k] = rn.priors[k];
         publish();
     }
     __syncthreads();
@@ -82,6 +92,14 @@ __global__ __launch_bounds__(256) void mle_sets_kernel(const SmallSetArgs byval,
             if (pd) {
                 small_lml_outputs_at(st, row, red, &lml, dl, &dnoise);
                 if (fit_noise) dl[1 + n_ls] = dnoise;
+                if (PRIOR && n_prior > 0) {                           // (a run without priors: no stage, no + 0.0)
+                    double lp;
+                    hyper_prior_at(priors, P, row, &lp, prior_grad);
+                    lml = lml + lp;                                   // the log posterior and its gradient: one IEEE addition each
+#pragma unroll
+                    for (int k = 0; k < kMleMaxParams; ++k)
+                        if (k < P) dl[k] = dl[k] + prior_grad[k];
+                }
             }
             mle_feed(search, lml, dl, max_rounds);
             publish();
@@ -106,19 +124,19 @@ void launch_mle_sets(hipStream_t s, const cbo_small_set *sets, int n_models, con
                      double *scratch, int64_t stride, int *info, double *rings, double *final_out, int *status_out,
                      int *rounds_out)
 {
-    static std::atomic<unsigned long long> opted[2] = {{0}, {0}};
+    static std::atomic<unsigned long long> opted[2][2] = {{{0}, {0}}, {{0}, {0}}};
     const bool byval = n_models <= kSmallByValue;
-    small_lds_opt_in(byval ? reinterpret_cast<const void *>(mle_sets_kernel<true>)
-                           : reinterpret_cast<const void *>(mle_sets_kernel<false>), opted[byval]);
+    bool prior = false;
+    for (int j = 0; j < n_runs; ++j) prior = prior || runs[j].n_prior > 0;
     SmallSetArgs args{};
-    if (byval) {
-        std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_models);
-        hipLaunchKernelGGL(mle_sets_kernel<true>, dim3((unsigned)n_runs), dim3(256), sizeof(SmallShared), s, args, sets, runs,
-                           scratch, stride, info, rings, final_out, status_out, rounds_out);
-    } else {
-        hipLaunchKernelGGL(mle_sets_kernel<false>, dim3((unsigned)n_runs), dim3(256), sizeof(SmallShared), s, args, sets, runs,
-                           scratch, stride, info, rings, final_out, status_out, rounds_out);
-    }
+    if (byval) std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_models);
+    auto launch = [&](auto kernel) {
+        small_lds_opt_in(reinterpret_cast<const void *>(kernel), opted[byval][prior]);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n_runs), dim3(256), sizeof(SmallShared), s, args,
+                           sets, runs, scratch, stride, info, rings, final_out, status_out, rounds_out);
+    };
+    if (byval) prior ? launch(mle_sets_kernel<true, true>) : launch(mle_sets_kernel<true, false>);
+    else prior ? launch(mle_sets_kernel<false, true>) : launch(mle_sets_kernel<false, false>);
 }
 
 }  // namespace cbo

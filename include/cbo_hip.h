@@ -852,6 +852,43 @@ typedef struct cbo_mle_run {            /* one model: n_starts runs */
 } cbo_mle_run;
 int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_run *runs, int *model_status_out);
 
+/* Priors on the hyper-parameters: GPy's set_prior with priors.Gaussian / LogGaussian / Gamma /
+ * InverseGamma, restated in csrc/hyper_prior.h (from memory, parity with GPy unpinned).  Priors are state of the model
+ * handle: cbo_gp_set_data / _upload_data / _append / _append_block / _set_hyper and every fit keep them.  One descriptor per
+ * parameter in the row order of cbo_gp_hmc_sets and cbo_gp_mle_sets: variance, the lengthscale(s) (ARD ? d : 1), the noise
+ * variance; n_params = 2 + (ARD ? d : 1), the noise slot always present.  kind CBO_PRIOR_NONE: the parameter has no prior.
+ * (p0, p1) = (mu, sigma) for GAUSSIAN and LOGGAUSSIAN, (a, b) for GAMMA and INVGAMMA (b the rate, resp. the scale);
+ * `constant` is the density's constant, computed by the caller: -log(2 pi sigma^2) / 2, resp. a log(b) - lgamma(a) (the
+ * device never calls lgamma).  The log prior is the sum of the densities at theta plus, for every parameter that has a
+ * prior, the log-Jacobian of its Logexp constraint, log(expm1(theta)) - theta (0 above 36), as GPy's log_prior() adds it.
+ * cbo_gp_set_priors: priors == NULL, or every kind NONE, clears the priors.  CBO_ERR_INVALID, before any device work and
+ * with the reason in cbo_last_error(): a NULL handle, n_params other than 2 + (ARD ? d : 1), an unknown kind, a parameter
+ * or constant that is not finite, sigma <= 0, a <= 0 or b <= 0.  cbo_gp_get_priors writes the n_params descriptors (all
+ * NONE for a model without priors).
+ * With priors set, cbo_gp_hmc_sets and cbo_gp_mle_sets sample and maximise the log POSTERIOR: at every position / trial
+ * point the log prior and its gradient (hyper_prior_at over the run's n_params entries -- a prior on the noise variance
+ * takes part only when the noise is sampled / fitted) are added to the likelihood and its gradients, one IEEE addition each,
+ * before the chain / search sees them; final_lml, final_grad, lml_out and grad_out then hold the log posterior and its
+ * gradient with respect to theta (the negated objective, GPy's -f_opt): fl(lml + lp), fl(dl[k] + dlp[k]) with lml, dl what
+ * cbo_gp_lml_gradients and lp, dlp what cbo_gp_log_prior_batch answer there, bit for bit.  A model without priors skips the
+ * stage (no + 0.0) and gives the bits it gave before priors existed; a call in which no model has priors launches the
+ * kernel without the stage. */
+enum { CBO_PRIOR_NONE = 0, CBO_PRIOR_GAUSSIAN = 1, CBO_PRIOR_LOGGAUSSIAN = 2, CBO_PRIOR_GAMMA = 3, CBO_PRIOR_INVGAMMA = 4 };
+typedef struct cbo_hyper_prior {
+    int kind, pad_;
+    double p0, p1, constant;
+} cbo_hyper_prior;
+int cbo_gp_set_priors(cbo_gp *gp, int n_params, const cbo_hyper_prior *priors);
+int cbo_gp_get_priors(const cbo_gp *gp, int n_params, cbo_hyper_prior *priors_out);
+/* The log prior and its gradient with respect to theta of many models in ONE tiny launch, one lane per model, by
+ * hyper_prior_at ON THE DEVICE (its log / expm1 are the ones the searches use, so what they add can be checked bit for
+ * bit).  thetas[i]: 2 + (ARD ? d : 1) values (variance, lengthscale(s), noise variance), or NULL -- the model's own
+ * parameters; thetas == NULL: every model's own.  lp_out: n_models; grad_out: n_models x CBO_HMC_MAX_PARAMS, zeros behind
+ * the model's entries; status[i] = CBO_OK.  A model without priors answers 0 and zeros.  The models are only read.
+ * CBO_ERR_INVALID: n_models <= 0, NULL arguments or handles, models of different contexts, a theta that is not finite. */
+int cbo_gp_log_prior_batch(int n_models, cbo_gp *const *gps, const double *const *thetas, double *lp_out, double *grad_out,
+                           int *status);
+
 /* Host-buffer convenience form of the same call (uploads Xs first). */
 int cbo_acq_sweep_host(cbo_gp *gp, int64_t m, const double *Xs, const double *prior_mean_s,
                        const double *prior_var_s, double y_best, int task, double ei_jitter,
