@@ -85,7 +85,10 @@ class CBOAcquisitionPath:
     at construction.  ``acquisition="MES"`` (``acquisition_param``: ``None`` or ``(num_samples, grid_size)``) scores every set
     with emukit's max-value entropy search over the cost: two device calls per trial for all sets, the
     Gumbel grids drawn from ``space_list``; it needs ``task="min"``, no constraints, no hyper-parameter samples and a single
-    process, and its ``trial_step`` takes the three-call route.
+    process, and its ``trial_step`` takes the three-call route.  ``acquisition="LOGEI"`` (``acquisition_param``: the jitter,
+    default 0) scores every set with the logarithm of the causal EI minus the logarithm of the cost, computed without
+    underflow: where the EI of every candidate is an exact 0.0 the sets still rank; no constraints, no
+    hyper-parameter samples, no batch, no ``device_prior``, a single process, and ``trial_step`` takes the three-call route.
     ``constraints`` (a list of ``(name, sense, value[, jitter])``, at most 8, shared by all sets; ``sense`` ``"<="`` or
     ``">="``) with ``constraint_data_y`` (``constraint_data_y[s][c]`` is (n_s, 1): the values of node ``c`` at ``data_x[s]``)
     make every set's score ``EI * prod PoF / cost``: the path keeps ``constraint_models[s][c]`` --
@@ -121,7 +124,8 @@ class CBOAcquisitionPath:
                  mle_restarts=1, hyper_priors=None):
         from .GaussianProcessFactory import checked_mle_optimizer
         from .utils_functions.priors import checked_priors
-        from .utils_functions.utils import checked_device_prior, checked_refine, sets_acquisition_or_default as sets_acquisition
+        from .utils_functions.utils import (checked_device_prior, checked_log_ei, checked_refine,
+                                            sets_acquisition_or_default as sets_acquisition)
         self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
         self.device_prior = checked_device_prior(device_prior, refine)
         # priors on every exploration-set model's hyper-parameters (name -> prior), or None: today's behaviour
@@ -130,6 +134,7 @@ class CBOAcquisitionPath:
         # (``find_next_y_points``); fixed at construction and checked here, before any device call
         self._kind = sets_acquisition(acquisition, acquisition_param)
         self.acquisition, self.acquisition_param = acquisition, acquisition_param
+        checked_log_ei(self._kind, self.device_prior)
         if self._kind[0] == "MES" and task != "min":
             raise ValueError("acquisition='MES' minimises: task must be 'min'")
         self.constraints = checked_path_constraints(constraints, self._kind)
@@ -319,6 +324,8 @@ class CBOAcquisitionPath:
             raise ValueError(f"batch selection is scored by a single process: the placement is {mode!r}")
         if self.refine and mode != "single":
             raise ValueError(f"gradient refinement is run by a single process: the placement is {mode!r}")
+        if self._kind[0] == "LOGEI" and mode != "single":
+            raise ValueError(f"the log Expected Improvement is scored by a single process: the placement is {mode!r}")
         if mode == "single":
             grids = [self.candidate_grid(s) for s in range(self.es_size)]
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
@@ -397,7 +404,7 @@ class CBOAcquisitionPath:
         st = self._call_cache.get("sweep_sets")
         model = self.models[s] if (s is not None and self.models) else None
         fast = (st is not None and model is not None and not self.constraints and self.hyper_samples is None
-                and self._kind[0] != "MES" and self.batch_size is None and not self.refine
+                and self._kind[0] not in ("MES", "LOGEI") and self.batch_size is None and not self.refine
                 and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
                 and model._hyper_initial and st["cost_table"] is self.costs
@@ -571,6 +578,8 @@ class CBO(CBOAcquisitionPath):
                        False, [self.graph.bounds(s) for s in exploration], len(exploration))
         if device_prior and not refine:
             raise ValueError("device_prior=True puts causal sets into the refinement's device launch: refine must be True")
+        from .utils_functions.utils import checked_log_ei
+        checked_log_ei(sets_acquisition(acquisition, acquisition_param), device_prior)
         sem = None
         if path_constraints and constraint_functions is None:
             from functools import partial

@@ -38,6 +38,7 @@ TASK_CODE = {"min": 0, "max": 1}
 DTYPE_CODE = {"f64": 0, "f32": 1}
 ACQ_KIND_CODE = {"LCB": 1, "PI": 2, "VAR": 3, "MPEI": 4}      # CBO_ACQ_LCB, _PI, _VAR, _MPEI
 REFINE_KIND_CODE = dict(ACQ_KIND_CODE, EI=0)                  # cbo_acq_refine_sets: 0 = the causal Expected Improvement
+LOGEI = "LOGEI"              # the log Expected Improvement: entry points of its own (cbo_acq_*_logei), no kind code -- routed by name
 REFINE_MAX_STARTS = 64       # CBO_REFINE_MAX_STARTS
 REFINE_ROUNDS_LIMIT = 1000   # CBO_REFINE_ROUNDS_LIMIT
 REFINE_PGTOL, REFINE_FTOL, REFINE_STEP, REFINE_MAX_ROUNDS, REFINE_NAN_START, REFINE_DECLINED = range(6)   # CBO_REFINE_*
@@ -158,6 +159,13 @@ SIGNATURES = {
     "cbo_acq_sweep_kind": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                           ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
                                           c_int64_p]),
+    "cbo_acq_sweep_logei": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                           ctypes.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_int64_p]),
+    "cbo_acq_sweep_sets_logei": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, ctypes.c_int, ctypes.c_double,
+                                                c_double_p, c_double_p, c_int64_p]),
+    "cbo_acq_refine_sets_logei": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), c_double_p,
+                                                 ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p,
+                                                 c_double_p, c_int_p, c_int_p]),
     "cbo_gp_plugin_incumbent": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p]),
     "cbo_gp_set_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_double_p, ctypes.c_double]),
     "cbo_gp_log_marginal": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),

@@ -1421,7 +1421,7 @@ static int copy_posterior_out(cbo_ctx *c, const cbo_cands *k, double *acq_out, d
 }
 
 // mes: max-value entropy search's epilogue (mes_acq_kernel) in the place of EI's; y_best, task and ei_jitter are then unused
-// kind: CBO_ACQ_LCB / _PI / _VAR: pointwise_acq_kernel in the place of EI's, ei_jitter being the kind's parameter; 0 and
+// kind: CBO_ACQ_LCB / _PI / _VAR / kLogEiKind: pointwise_acq_kernel in the place of EI's, ei_jitter being the kind's parameter; 0 and
 // CBO_ACQ_MPEI: EI -- with y_best_dev, its incumbent is read from there (device memory) and y_best is unused
 static int enqueue_finish(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost, double *acq_out,
                           double *mean_out, double *var_out, const double *q_src, const double *mu_src,
@@ -1441,7 +1441,7 @@ static int enqueue_finish(cbo_gp *g, cbo_cands *k, double y_best, int task, doub
             launch_mes_acq(c->stream, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, *mes,
                            mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr,
                            c->part_val, c->part_idx, k->index_offset, nb);
-        else if (kind == CBO_ACQ_LCB || kind == CBO_ACQ_PI || kind == CBO_ACQ_VAR)
+        else if (kind == CBO_ACQ_LCB || kind == CBO_ACQ_PI || kind == CBO_ACQ_VAR || kind == kLogEiKind)
             launch_pointwise_acq(c->stream, kind, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, p,
                                  mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr,
                                  c->part_val, c->part_idx, k->index_offset, nb);
@@ -2478,9 +2478,12 @@ extern "C" int cbo_acq_sweep_sets(int n_sets, cbo_gp *const *gps, cbo_cands *con
 
 // cbo_acq_sweep_kind's checks of its scalars for every set of a multi-set call, before anything is touched; what the kind
 // does not read is put to cbo_acq_sweep_kind's neutral values (the model variance reads neither task nor parameter)
-static int check_kind_args(int n_sets, int kind, const double *y_best, int *task, double *param, const double *costs)
+// logei: the caller is one of the log-EI entry points, whose kind is kLogEiKind (no public kind code names it: every other
+// caller keeps refusing it) -- the jitter and the incumbent are checked as the probability of improvement's are
+static int check_kind_args(int n_sets, int kind, const double *y_best, int *task, double *param, const double *costs,
+                           bool logei = false)
 {
-    if (kind != CBO_ACQ_LCB && kind != CBO_ACQ_PI && kind != CBO_ACQ_VAR && kind != CBO_ACQ_MPEI)
+    if (!(logei && kind == kLogEiKind) && kind != CBO_ACQ_LCB && kind != CBO_ACQ_PI && kind != CBO_ACQ_VAR && kind != CBO_ACQ_MPEI)
         return fail(CBO_ERR_INVALID, "kind must be CBO_ACQ_LCB, CBO_ACQ_PI, CBO_ACQ_VAR or CBO_ACQ_MPEI");
     if (n_sets <= 0 || !y_best || !costs) return fail(CBO_ERR_INVALID, "bad argument");
     if (kind == CBO_ACQ_VAR) { *task = CBO_TASK_MIN; *param = 0.0; }
@@ -2488,7 +2491,8 @@ static int check_kind_args(int n_sets, int kind, const double *y_best, int *task
     if (!std::isfinite(*param)) return fail(CBO_ERR_INVALID, "param (beta / jitter) must be finite");
     if (kind == CBO_ACQ_LCB && *param < 0.0) return fail(CBO_ERR_INVALID, "beta must not be negative");
     for (int i = 0; i < n_sets; ++i) {
-        if (kind == CBO_ACQ_PI && !std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite");
+        if ((kind == CBO_ACQ_PI || kind == kLogEiKind) && !std::isfinite(y_best[i]))
+            return fail(CBO_ERR_INVALID, "y_best must be finite");
         if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
     }
     return CBO_OK;
@@ -2501,6 +2505,16 @@ extern "C" int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands
     const int rc = check_kind_args(n_sets, kind, y_best, &task, &param, costs);
     if (rc != CBO_OK) return rc;
     return sweep_sets_impl(n_sets, gps, cands, y_best, task, param, costs, best_vals, best_idxs, -1, kind);
+}
+
+// cbo_acq_sweep_sets_kind for the log Expected Improvement: the same checks, the same routing, the epilogue
+// log_ei_of -- per set cbo_acq_sweep_logei's bits on a fitted twin
+extern "C" int cbo_acq_sweep_sets_logei(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
+                                        double jitter, const double *costs, double *best_vals, int64_t *best_idxs)
+{
+    const int rc = check_kind_args(n_sets, kLogEiKind, y_best, &task, &jitter, costs, true);
+    if (rc != CBO_OK) return rc;
+    return sweep_sets_impl(n_sets, gps, cands, y_best, task, jitter, costs, best_vals, best_idxs, -1, kLogEiKind);
 }
 
 // cbo_acq_sweep_sets for max-value entropy search: cbo_acq_sweep_mes' checks of its scalars for every set,
@@ -2567,8 +2581,8 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
         }
         for (int j = 0; rc == CBO_OK && j < ns; ++j) {
             const int i = small[(size_t)j];
-            // (only the EI and the probability of improvement read the caller's incumbent)
-            const double incumbent = (kind == kEiKind || kind == CBO_ACQ_PI) ? y_best[i] : 0.0;
+            // (only the EI, its logarithm and the probability of improvement read the caller's incumbent)
+            const double incumbent = (kind == kEiKind || kind == CBO_ACQ_PI || kind == kLogEiKind) ? y_best[i] : 0.0;
             rc = fill_small_set(c->sets_host[j], gps[i], cands[i], task, incumbent, ei_jitter, costs[i], i == staged_set);
         }
         return rc;
@@ -2582,6 +2596,9 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
         if (kind == kMesKind)
             return cbo_acq_sweep_mes(gps[i], cands[i], n_samples[i], mins[i], costs[i], nullptr, nullptr, nullptr, &best_vals[i],
                                      &best_idxs[i]);
+        if (kind == kLogEiKind)
+            return cbo_acq_sweep_logei(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
+                                       &best_vals[i], &best_idxs[i]);
         if (kind != kEiKind)
             return cbo_acq_sweep_kind(gps[i], cands[i], kind, y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
                                       &best_vals[i], &best_idxs[i]);
@@ -2589,7 +2606,8 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
                              &best_idxs[i]);
     };
     return run_small_or_general(
-        c, kind == kEiKind ? "cbo_acq_sweep_sets" : kind == kMesKind ? "cbo_acq_sweep_sets_mes" : "cbo_acq_sweep_sets_kind",
+        c, kind == kEiKind ? "cbo_acq_sweep_sets" : kind == kMesKind ? "cbo_acq_sweep_sets_mes"
+           : kind == kLogEiKind ? "cbo_acq_sweep_sets_logei" : "cbo_acq_sweep_sets_kind",
         "multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
         [&](const SmallLaunch &L) { launch_small_sets(c->stream, kind, c->sets_host, ns, blocks, L, aux); },
         [&](int j, int i) { return harvest_winner(c, j, i, best_vals, best_idxs); }, general);
@@ -2689,7 +2707,7 @@ struct cbo_do_prior {
 // sets with one to a second launch on the same stream.
 static int refine_sets_impl(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, const cbo_do_prior *const *priors,
                             int kind, const double *y_best, int task, double param, int max_rounds, double *x_out,
-                            double *val_out, double *grad_out, int *rounds_out, int *status_out)
+                            double *val_out, double *grad_out, int *rounds_out, int *status_out, bool logei = false)
 {
     if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
     if (!gps || !sets || !y_best || !x_out || !val_out || !grad_out || !rounds_out || !status_out)
@@ -2698,7 +2716,7 @@ static int refine_sets_impl(int n_sets, cbo_gp *const *gps, const cbo_refine_set
         return fail(CBO_ERR_INVALID, "max_rounds must be in 0.." + std::to_string(CBO_REFINE_ROUNDS_LIMIT));
     if (kind != kEiKind) {
         std::vector<double> ones((size_t)n_sets, 1.0);
-        const int rc = check_kind_args(n_sets, kind, y_best, &task, &param, ones.data());
+        const int rc = check_kind_args(n_sets, kind, y_best, &task, &param, ones.data(), logei);
         if (rc != CBO_OK) return rc;
     } else {
         if (task != CBO_TASK_MIN && task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
@@ -2786,7 +2804,7 @@ static int refine_sets_impl(int n_sets, cbo_gp *const *gps, const cbo_refine_set
         fill_small_model(st, g);
         st.cxs = st.csq = st.csv = st.cpm = st.cpv = nullptr;
         st.cld = 0; st.m = 0; st.index_offset = 0;
-        st.task = task; st.y_best = (kind == kEiKind || kind == CBO_ACQ_PI) ? y_best[i] : 0.0;
+        st.task = task; st.y_best = (kind == kEiKind || kind == CBO_ACQ_PI || kind == kLogEiKind) ? y_best[i] : 0.0;
         st.ei_jitter = param;
         st.cost = 1.0;                                         // (the kernel prices every point itself)
         cbo_small_refine &rf = c->refine_host[j];
@@ -2838,6 +2856,22 @@ extern "C" int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_ref
 {
     return refine_sets_impl(n_sets, gps, sets, nullptr, kind, y_best, task, param, max_rounds, x_out, val_out, grad_out,
                             rounds_out, status_out);
+}
+
+// ... for the log Expected Improvement: value log EI(x) - log c(x), gradient d log EI (the cost's gradient is
+// the reference's zero).  A causal set is declined: the causal instantiation of this kind is not built.
+extern "C" int cbo_acq_refine_sets_logei(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, const double *y_best,
+                                         int task, double jitter, int max_rounds, double *x_out, double *val_out,
+                                         double *grad_out, int *rounds_out, int *status_out)
+{
+    // (the scalars first, as the sweeps of this kind check them: before a handle is looked at)
+    if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
+    if (!y_best) return fail(CBO_ERR_INVALID, "NULL argument: y_best");
+    const std::vector<double> ones((size_t)n_sets, 1.0);
+    const int rc = check_kind_args(n_sets, kLogEiKind, y_best, &task, &jitter, ones.data(), true);
+    if (rc != CBO_OK) return rc;
+    return refine_sets_impl(n_sets, gps, sets, nullptr, kLogEiKind, y_best, task, jitter, max_rounds, x_out, val_out, grad_out,
+                            rounds_out, status_out, true);
 }
 
 extern "C" int cbo_acq_refine_sets_prior(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets,
@@ -3422,6 +3456,20 @@ extern "C" int cbo_acq_sweep_kind(cbo_gp *g, cbo_cands *k, int kind, double y_be
     }
     return sweep_impl(g, k, y_best, task, param, cost, acq_out, mean_out, var_out, best_val, best_idx, nullptr, kind,
                       y_best_dev);
+}
+
+// The log Expected Improvement over a cost: cbo_acq_sweep_kind's path with log_ei_of's epilogue --
+// acq = log EI - log cost, finite and strictly ordered where the EI itself underflows to 0; mean and var are
+// cbo_acq_sweep_kind's bits.  The scalars are checked first (check_kind_args, as the multi-set call checks them), then the handles.
+extern "C" int cbo_acq_sweep_logei(cbo_gp *g, cbo_cands *k, double y_best, int task, double jitter, double cost,
+                                   double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx)
+{
+    int rc = check_kind_args(1, kLogEiKind, &y_best, &task, &jitter, &cost, true);
+    if (rc != CBO_OK) return rc;
+    rc = check_sweep_args(g, k, task);
+    if (rc != CBO_OK) return rc;
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    return sweep_impl(g, k, y_best, task, jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, nullptr, kLogEiKind);
 }
 
 // What gumbel_quantiles_kernel left for one set: the single call's message for the first quantile that failed ("" = none),

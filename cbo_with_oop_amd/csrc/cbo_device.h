@@ -407,6 +407,99 @@ __device__ __forceinline__ double pointwise_of(double mean, double var, const Ac
     return fma(fma(-qv, p.cost, v), rc, qv);
 }
 
+// ---- log Expected Improvement (Ament et al. 2023, "Unexpected improvements to expected improvement"):
+// the epilogue of pointwise_acq_kernel<kLogEiKind>, small_sets_kernel<kLogEiKind> and small_sets_refine_kernel<kLogEiKind>
+// -- one definition, so the three return each other's bits.
+// log h(u), h(u) = phi(u) + u Phi(u), without underflow, in three ranges (w = sqrt(pi / 2) |u| erfcx(-u / sqrt 2) = 1 - h / phi):
+//   u > -1            log(phi + u Phi), the density's exponential shared with cephes ndtr (ndtr_with_exp)
+//   -30 < u <= -1     -u^2 / 2 - log sqrt(2 pi) + log1mexp(log w),  log1mexp(x) = log(-expm1(x)) above -ln 2, else log1p(-exp(x));
+//                     erfcx from cephes erfc's rational functions without their exponential (P / Q below 8, R / S beyond;
+//                     exp(y^2) (1 - erf y) below 1, as log_ndtr has it)
+//   u <= -30          -u^2 / 2 - log sqrt(2 pi) - 2 log|u| + log1p(S),  S = -3 / u^2 + 15 / u^4 - 105 / u^6 + ... (eight terms:
+//                     the ninth is 2e-18 at |u| = 30) -- 1 - w cancels to nothing from |u| ~ 1e3 on, the series does not
+// GRAD: the gradient's coefficients too, A = Phi / h and B = phi / h (d log h / du = A, and d logEI = (-A d mean + B d sd) / sd):
+// the plain ratios above -1; below, B = 1 / (1 - w) or u^2 / (1 + S) -- exp(-u^2 / 2) cancels analytically -- and
+// A = sqrt(pi / 2) erfcx(-u / sqrt 2) B.
+// A NaN argument takes the last range and comes out NaN.  IEEE divisions and the device library's log / log1p / expm1 / exp.
+template <bool GRAD>
+__device__ __forceinline__ double log_h_of(double u, double &A, double &B)
+{
+#pragma clang fp contract(off)
+    const double SQRTH = 7.07106781186547524401E-1, LOG_SQRT_2PI = 0.918938533204672741780, SQRT_HALF_PI = 1.25331413731550025121,
+                 LOG_SQRT_HALF_PI = 0.225791352644727432363, LN2 = 0.693147180559945309417;
+    double r;
+    if (u > -1.0) {
+        const double e = exp_nonpositive(-(u * u) / 2.0);
+        const double pdf = e * 0.3989422804014327;
+        const double cdf = ndtr_with_exp(u, e);
+        const double h = fma(u, cdf, pdf);
+        r = log(h);
+        if (GRAD) { A = cdf / h; B = pdf / h; }
+    } else {
+        const double y = -u * SQRTH;                                   // >= 1 / sqrt 2 (or NaN)
+        double erfcx;
+        if (y < 1.0) {
+            erfcx = exp(y * y) * (1.0 - cephes_erf_small(y));
+        } else {
+            double p, q;
+            if (y < 8.0) cephes_erfc_pq(y, p, q);
+            else cephes_erfc_rs(y, p, q);
+            erfcx = p / q;
+        }
+        const double head = -(u * u) / 2.0 - LOG_SQRT_2PI;
+        if (u > -30.0) {
+            const double x = log(erfcx * -u) + LOG_SQRT_HALF_PI;        // log w < 0
+            const bool near = x > -LN2;
+            const double w = exp(x);
+            const double one_minus_w = near ? -expm1(x) : 1.0 - w;
+            r = head + (near ? log(one_minus_w) : log1p(-w));
+            if (GRAD) B = 1.0 / one_minus_w;
+        } else {
+            const double u2 = u * u, t = 1.0 / u2;
+            double S = 34459425.0;
+            S = fma(S, t, -2027025.0);
+            S = fma(S, t, 135135.0);
+            S = fma(S, t, -10395.0);
+            S = fma(S, t, 945.0);
+            S = fma(S, t, -105.0);
+            S = fma(S, t, 15.0);
+            S = fma(S, t, -3.0);
+            S = S * t;
+            r = (head - 2.0 * log(-u)) + log1p(S);
+            if (GRAD) B = u2 / (1.0 + S);
+        }
+        if (GRAD) A = SQRT_HALF_PI * erfcx * B;
+    }
+    return r;
+}
+// The standardised improvement of one candidate, s and the quotient formed as acquisition_of forms them.  Task 'max' is the
+// MIRROR, u = ((mean - jitter) - y_best) / s: not the logarithm of acquisition_of's -EI (the reference's quirk), which has none.
+__device__ __forceinline__ double log_ei_u(double mean, double var, const AcqParams &p, double &s)
+{
+#pragma clang fp contract(off)
+    double rs;
+    bool special;
+    sqrt_and_reciprocal(var, s, rs, special);
+    const double a = (p.task == CBO_TASK_MIN) ? p.y_best - (mean + p.ei_jitter) : (mean - p.ei_jitter) - p.y_best;   // (uniform)
+    double u = a * rs;
+    u = fma(fma(-u, s, a), rs, u);
+    if (__builtin_expect(special, 0)) u = a / s;                    // (a zero or infinite variance: the IEEE quotient)
+    return u;
+}
+// log EI - log cost of one candidate: log h(u) + log s - log_cost.  log_cost = log(p.cost) is uniform: the callers form it
+// once, ahead of their candidate loop.  A NaN mean or variance gives NaN.
+__device__ __forceinline__ double log_ei_of(double mean, double var, const AcqParams &p, double log_cost)
+{
+#pragma clang fp contract(off)
+    double s, A, B;
+    const double u = log_ei_u(mean, var, p, s);
+    return (log_h_of<false>(u, A, B) + log(s)) - log_cost;
+}
+__device__ __forceinline__ double log_ei_of(double mean, double var, const AcqParams &p)
+{
+    return log_ei_of(mean, var, p, log(p.cost));
+}
+
 // ---- max-value entropy search: the epilogue of mes_acq_kernel (kernels_mes.hip) and of small_sets_kernel<kMesKind>
 // (kernels_sets.hip) -- one definition, so the multi-set sweep returns cbo_acq_sweep_mes' bits.
 // One sample's term of emukit's evaluate: -gamma pdf(gamma) / (2 minus_cdf) - log(minus_cdf).  The density and cephes ndtr

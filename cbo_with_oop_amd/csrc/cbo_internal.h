@@ -344,6 +344,10 @@ constexpr int kEiKind = 0;
 // per_set and data may be pinned host memory (device-mapped), like the descriptors.
 constexpr int kMesKind = 5;
 constexpr int kPredictKind = 6;
+// ... and one that reads nothing more than the EI does: log Expected Improvement, log_ei_of's epilogue --
+// log EI - log cost, task 'max' mirrored; ei_jitter is the jitter, y_best the incumbent.  Internal: the public kind codes
+// (CBO_ACQ_*) do not name it, the entry points cbo_acq_sweep_logei / _sweep_sets_logei / _refine_sets_logei do.
+constexpr int kLogEiKind = 7;
 struct cbo_small_aux {
     int64_t off, count;
 };

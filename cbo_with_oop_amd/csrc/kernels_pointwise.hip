@@ -22,8 +22,9 @@ namespace cbo {
 // (pointwise_of, one candidate's value over the cost, lives in cbo_device.h: the one-launch multi-set sweep shares it.)
 
 // acq_pass (acq_pass.h) scored by pointwise_of<KIND>.
-// KIND: CBO_ACQ_LCB, CBO_ACQ_PI or CBO_ACQ_VAR (compile time: one kind's arithmetic per instantiation); CAUSAL: the
-// candidates carry a prior mean / variance; MV: mean and / or variance are written out.
+// KIND: CBO_ACQ_LCB, CBO_ACQ_PI or CBO_ACQ_VAR (compile time: one kind's arithmetic per instantiation), or kLogEiKind: the
+// pass scored by log_ei_of, log EI - log cost; CAUSAL: the candidates carry a prior mean / variance; MV: mean
+// and / or variance are written out.
 template <int KIND, bool CAUSAL, bool MV>
 __global__ __launch_bounds__(256) void pointwise_acq_kernel(const double *__restrict__ q, const double *__restrict__ mu,
                                                             const double *__restrict__ pm, const double *__restrict__ pv,
@@ -35,8 +36,12 @@ __global__ __launch_bounds__(256) void pointwise_acq_kernel(const double *__rest
     double bv = -INFINITY;
     int64_t bi = kNoIndex;
     if (!MV) { mean_out = nullptr; var_out = nullptr; }
+    [[maybe_unused]] const double log_cost = (KIND == kLogEiKind) ? log(p.cost) : 0.0;      // (uniform: once per launch)
     auto score = [&](d2 mean2, d2 var2) {
-        return d2{pointwise_of<KIND>(mean2[0], var2[0], p), pointwise_of<KIND>(mean2[1], var2[1], p)};
+        if constexpr (KIND == kLogEiKind)
+            return d2{log_ei_of(mean2[0], var2[0], p, log_cost), log_ei_of(mean2[1], var2[1], p, log_cost)};
+        else
+            return d2{pointwise_of<KIND>(mean2[0], var2[0], p), pointwise_of<KIND>(mean2[1], var2[1], p)};
     };
     acq_pass<CAUSAL>(q, mu, pm, pv, m, p, true, mean_out, var_out, acq_out, index_offset, score, bv, bi);
     block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
@@ -59,7 +64,8 @@ void launch_pointwise_acq(hipStream_t s, int kind, const double *q, const double
                           double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks)
 {
     auto launch = kind == CBO_ACQ_LCB ? launch_pointwise_kind<CBO_ACQ_LCB>
-                  : kind == CBO_ACQ_PI ? launch_pointwise_kind<CBO_ACQ_PI> : launch_pointwise_kind<CBO_ACQ_VAR>;
+                  : kind == CBO_ACQ_PI ? launch_pointwise_kind<CBO_ACQ_PI>
+                  : kind == kLogEiKind ? launch_pointwise_kind<kLogEiKind> : launch_pointwise_kind<CBO_ACQ_VAR>;
     launch(s, q, mu, pm, pv, m, p, mean_out, var_out, acq_out, part_val, part_idx, index_offset, n_blocks);
 }
 

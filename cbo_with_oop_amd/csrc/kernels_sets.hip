@@ -26,6 +26,7 @@ static_assert(sizeof(SmallShared) + kMesMaxSamples * sizeof(double) + sizeof(int
 // kMesKind: max-value entropy search -- the set's Gumbel samples come from aux's table (fetched with the
 // candidates, ahead of the factorisation; parked in LDS behind K*'s barrier), the epilogue is mes_of.  kPredictKind: the
 // epilogue stores mean and variance at the set's offset in aux's workspace; no arg-max, the record carries the status word.
+// kLogEiKind: the epilogue is log_ei_of, log EI - log cost -- cbo_acq_sweep_logei's bits; nothing from aux.
 // phases 3: every workgroup factors the model itself, into its own scratch slot; 1: one workgroup per set factors it into
 // the set's slot 0, nothing else; 2: the set's slot 0 holds the factor.
 template <int KIND, bool BYVAL>
@@ -113,8 +114,11 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
                 const MesSetParams mp{mes_mins, (int)ax.count, p.cost};
                 bv = mes_of(mean, var, mp);
             } else {
-                bv = (KIND == kEiKind || KIND == CBO_ACQ_MPEI) ? acquisition_of(mean, var, p)
-                                                               : pointwise_of<KIND>(mean, var, p);
+                if constexpr (KIND == kLogEiKind)
+                    bv = log_ei_of(mean, var, p);
+                else
+                    bv = (KIND == kEiKind || KIND == CBO_ACQ_MPEI) ? acquisition_of(mean, var, p)
+                                                                   : pointwise_of<KIND>(mean, var, p);
             }
             bi = c + st.index_offset;
         }
@@ -163,6 +167,7 @@ void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n
         case CBO_ACQ_MPEI: CBO_LAUNCH_KIND(CBO_ACQ_MPEI); break;
         case kMesKind: CBO_LAUNCH_KIND(kMesKind); break;
         case kPredictKind: CBO_LAUNCH_KIND(kPredictKind); break;
+        case kLogEiKind: CBO_LAUNCH_KIND(kLogEiKind); break;
         default: CBO_LAUNCH_KIND(kEiKind); break;
     }
 #undef CBO_LAUNCH_KIND

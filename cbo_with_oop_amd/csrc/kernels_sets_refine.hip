@@ -43,7 +43,29 @@ static_assert(2 * 4 * (16 / 2) <= 64 && kRefineHistory * CBO_MAX_DIM <= 64, "one
 
 // The acquisition over the cost and the two coefficients of its gradient, d value = (a d mean + b d sd) / cost, from
 // (mean, var) as the host classes form them (CausalExpectedImprovement.evaluate_with_gradients; pointwise_acquisitions.py).
-// The value is the sweep's own (acquisition_of / pointwise_of<KIND>); the coefficients repeat its intermediate steps.
+// The value is the sweep's own (acquisition_of / pointwise_of<KIND> / log_ei_of); the coefficients repeat its intermediate steps.
+// kLogEiKind: the value is log EI - log cost and (a, b) are the coefficients of d logEI itself -- not over the cost.
+
+// log EI - log cost, s, and the coefficients of d logEI = (-A d mean + B d sd) / s, d mean's sign flipped for 'max'
+// (log_h_of<true>).  The value is log_ei_of's, operation for operation.
+// A function of its own, NOT inlined: only the one lane that runs a start's search calls it, once per round.  Inlined, its
+// three ranges (the device library's log / log1p / expm1 / exp among them) cost the kernel -- which sits at 256 VGPRs --
+// 50 spilled VGPRs and 164 bytes of scratch per lane; as a call it costs none (256 VGPRs, 239 AGPRs, no scratch: the figures
+// of the LCB and VAR instantiations).
+struct LogEiTerms {
+    double value, s, a, b;
+};
+__device__ __attribute__((noinline)) LogEiTerms log_ei_value_and_coefficients(double mean, double var, double y_best,
+                                                                              double jitter, int task, double cost)
+{
+    AcqParams p{};
+    p.y_best = y_best; p.ei_jitter = jitter; p.task = task; p.cost = cost;
+    double s, A, B;
+    const double u = log_ei_u(mean, var, p, s);
+    const double log_h = log_h_of<true>(u, A, B);
+    return LogEiTerms{(log_h + log(s)) - log(cost), s, ((task == CBO_TASK_MIN) ? -A : A) / s, B / s};
+}
+
 template <int KIND>
 __device__ __forceinline__ double value_and_coefficients(double mean, double var, const AcqParams &p, double &s, double &a,
                                                          double &b)
@@ -66,6 +88,13 @@ __device__ __forceinline__ double value_and_coefficients(double mean, double var
             b = sign * pdf;
             return acquisition_of(mean, var, p);
         }
+    } else if constexpr (KIND == kLogEiKind) {
+        // (the caller does NOT divide this kind by the cost: the cost's gradient is the reference's zero)
+        const LogEiTerms t = log_ei_value_and_coefficients(mean, var, p.y_best, p.ei_jitter, p.task, p.cost);
+        s = t.s;
+        a = t.a;
+        b = t.b;
+        return t.value;
     } else if constexpr (KIND == CBO_ACQ_LCB) {
         a = -sign;
         b = p.ei_jitter;
@@ -242,7 +271,10 @@ __global__ __launch_bounds__(256) void small_sets_refine_kernel(const SmallSetAr
             const double value = value_and_coefficients<KIND>(mean, var, p, s, a, b);
             double grad[CBO_MAX_DIM];
 #pragma unroll
-            for (int k = 0; k < CBO_MAX_DIM; ++k) grad[k] = (a * dmean[k] + b * (dvar[k] / (2.0 * s))) / cost;
+            for (int k = 0; k < CBO_MAX_DIM; ++k) {
+                grad[k] = a * dmean[k] + b * (dvar[k] / (2.0 * s));
+                if constexpr (KIND != kLogEiKind) grad[k] = grad[k] / cost;
+            }
             refine_feed(rs, lo, hi, value, grad, max_rounds);
         }
         // the next trial point to every lane of the start's columns; the workgroup goes on while one of its searches does
@@ -297,6 +329,8 @@ void launch_small_sets_refine(hipStream_t s, int kind, bool prior, const cbo_sma
         case CBO_ACQ_PI: CBO_LAUNCH_KIND(CBO_ACQ_PI); break;
         case CBO_ACQ_VAR: CBO_LAUNCH_KIND(CBO_ACQ_VAR); break;
         case CBO_ACQ_MPEI: CBO_LAUNCH_KIND(CBO_ACQ_MPEI); break;
+        // (log EI: plain sets alone -- the causal instantiation is not built, refine_sets_impl declines such a set)
+        case kLogEiKind: byval ? CBO_LAUNCH_AS(kLogEiKind, true, false) : CBO_LAUNCH_AS(kLogEiKind, false, false); break;
         default: CBO_LAUNCH_KIND(kEiKind); break;
     }
 #undef CBO_LAUNCH_KIND

@@ -8,8 +8,9 @@ from .greedy_batch import GreedyBatchPointCalculator  # noqa: F401
 from .integrated_hyper import IntegratedHyperParameterAcquisition, hmc_sample  # noqa: F401
 from .integrated_variance import IntegratedVarianceReduction  # noqa: F401
 from .max_value_entropy import MaxValueEntropySearch  # noqa: F401
-from .pointwise_acquisitions import (CausalMeanPluginExpectedImprovement, CausalNegativeLowerConfidenceBound,  # noqa: F401
-                                     CausalProbabilityOfImprovement, ModelVariance)
+from .pointwise_acquisitions import (CausalLogExpectedImprovement, CausalMeanPluginExpectedImprovement,  # noqa: F401
+                                     CausalNegativeLowerConfidenceBound, CausalProbabilityOfImprovement,
+                                     LogAcquisitionQuotient, ModelVariance)
 from .utils import (compute_coverage, find_current_global, find_next_y_point, find_next_y_points,  # noqa: F401
                     fit_gaussian_process, fit_gaussian_processes, update_hull)
 from .graph_functions import (AdditiveSEM, Term, compute_interventions, get_parameter_space, intervene_dict,  # noqa: F401

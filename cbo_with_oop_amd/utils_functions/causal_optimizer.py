@@ -167,6 +167,8 @@ def _values_and_gradients(acquisition, X):
         return f[:, 0], df
     f, df = num.evaluate_with_gradients(X)
     c = np.array([float(acquisition.denominator.evaluate(X[i:i + 1])) for i in range(X.shape[0])])
+    if getattr(acquisition, "is_log", False):         # (LogAcquisitionQuotient: the logarithm of the quotient)
+        return f[:, 0] - np.log(c), df
     return f[:, 0] / c, df / c[:, None]
 
 
@@ -294,7 +296,7 @@ def _device_refinable(acquisition, device_prior=False):
         if num.jitter != 0.0:
             kind = ("EI", float(num.jitter))
         y_best, task = float(np.asarray(num.current_global_min, dtype=np.float64).reshape(-1)[0]), num.task
-    elif isinstance(num, pw._PointwiseAcquisition) and num.kind in _lib.ACQ_KIND_CODE:
+    elif isinstance(num, pw._PointwiseAcquisition) and (num.kind in _lib.ACQ_KIND_CODE or num.kind == _lib.LOGEI):
         y_best, task, param = num._scalars()
         kind = (num.kind, param)
     else:
@@ -355,9 +357,17 @@ def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, ta
     rounds, status = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32)
     gps = (ctypes.c_void_p * n)(*[models[i]._handle for i in dev])
     yb = np.full(n, y_best)
-    outs = (_lib.REFINE_KIND_CODE[kind[0]], _lib.dptr(yb), _lib.TASK_CODE[task], param, max_rounds, _lib.dptr(x_out),
-            _lib.dptr(v_out), _lib.dptr(g_out), rounds.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p))
-    if priors:
+    if kind[0] == _lib.LOGEI:                        # (no kind code: an entry point of its own; refine_sets has refused priors)
+        _lib.check(_lib.load().cbo_acq_refine_sets_logei(
+            n, gps, sets, _lib.dptr(yb), _lib.TASK_CODE[task], param, max_rounds, _lib.dptr(x_out), _lib.dptr(v_out),
+            _lib.dptr(g_out), rounds.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p)))
+        outs = None
+    else:
+        outs = (_lib.REFINE_KIND_CODE[kind[0]], _lib.dptr(yb), _lib.TASK_CODE[task], param, max_rounds, _lib.dptr(x_out),
+                _lib.dptr(v_out), _lib.dptr(g_out), rounds.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p))
+    if outs is None:
+        pass
+    elif priors:
         handles = (ctypes.c_void_p * n)(*[priors[i]._handle if i in priors else None for i in dev])
         _lib.check(_lib.load().cbo_acq_refine_sets_prior(n, gps, sets, handles, *outs))
     else:
@@ -390,10 +400,12 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
     ``device_prior=True``: a causal set is eligible too when ``prior_spec`` recognises its closures, its model
     is small and fp64, ``cost_structure`` recognises its cost and a ``DoPrior`` of its graph GP can be created
     (``cbo_acq_refine_sets_prior``); the priors are built for this call and closed after it.  A causal set that misses one of
-    these takes today's route.  The default does exactly what it did."""
+    these takes today's route.  The default does exactly what it did.
+    ``kind=("LOGEI", jitter)``: value ``log EI - log cost``, gradient ``d log EI``, through
+    ``cbo_acq_refine_sets_logei``; a causal set takes the host route, and ``device_prior=True`` raises ``ValueError``."""
     import ctypes
     import math
-    from .utils import sets_acquisition
+    from .utils import checked_log_ei, sets_acquisition
     if not (isinstance(kind, tuple) and len(kind) == 2):
         raise ValueError(f"refine_sets: kind must be a (name, parameter) pair, not {kind!r}")
     if kind[0] == "MES":
@@ -405,6 +417,7 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
         kind = ("EI", float(kind[1]))
     else:
         kind = sets_acquisition(kind[0], None if kind[0] in ("EI", "VAR") else kind[1])
+    checked_log_ei(kind, device_prior)
     s = len(models)
     if not (len(starts) == len(bounds) == len(costs) == s) or s == 0:
         raise ValueError("refine_sets: models, starts, bounds and costs must have one entry per exploration set")

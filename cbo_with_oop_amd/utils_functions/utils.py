@@ -139,6 +139,9 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     ``ModelVariance`` -- over the cost, on the grid or with ``anchors="uniform"`` (they have gradients).  ``"MPEI"`` and
     ``"VAR"`` do not use ``current_global_best``, ``"VAR"`` does not use ``task``.  Together with ``constraints``,
     ``batch_size`` or ``hyper_samples`` they raise those branches' ``ValueError``.
+    ``acquisition="LOGEI"``: the logarithm of the causal EI, computed without underflow, minus the logarithm of the cost
+    (``CausalLogExpectedImprovement / Cost``), on the grid or with ``anchors="uniform"``; together with
+    ``constraints``, ``batch_size`` or ``hyper_samples`` it raises those branches' ``ValueError``.
     ``hyper_samples`` (an (H, P) array of hyper-parameter samples, or an int: that many drawn by the model's HMC with the
     defaults): the grid is scored with the EI marginalised over the samples, over the cost, in one device call
     (integrated_hyper.py, ``cbo_acq_sweep_hyper``); together with ``acquisition="MES"``, ``constraints``, ``batch_size`` or
@@ -164,7 +167,7 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
             raise ValueError("batch selection is not defined for constrained acquisitions: constraints must be None")
         if anchors != "grid":
             raise ValueError("batch selection picks from the grid: anchors must be 'grid'")
-    if acquisition not in ("EI", "MES") + POINTWISE_ACQUISITIONS:
+    if acquisition not in ("EI", "MES", LOG_EI) + POINTWISE_ACQUISITIONS:
         raise ValueError(f"acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR', not {acquisition!r}")
     if acquisition == "MES":
         if task != "min":
@@ -224,6 +227,7 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
 
 
 POINTWISE_ACQUISITIONS = ("LCB", "PI", "MPEI", "VAR")
+LOG_EI = "LOGEI"      # the log Expected Improvement: a name of its own, routed to the cbo_acq_*_logei calls
 
 
 def _acquisition_for(name, model, current_global_best, task, space, param=None):
@@ -232,6 +236,9 @@ def _acquisition_for(name, model, current_global_best, task, space, param=None):
     if name == "MES":
         from .max_value_entropy import MaxValueEntropySearch
         return MaxValueEntropySearch(model, space)
+    if name == LOG_EI:
+        from .pointwise_acquisitions import CausalLogExpectedImprovement
+        return CausalLogExpectedImprovement(current_global_best, task, model, 0.0 if param is None else param)
     if name in POINTWISE_ACQUISITIONS:
         from . import pointwise_acquisitions as pw
         extra = () if param is None else (param,)
@@ -248,7 +255,8 @@ def _acquisition_for(name, model, current_global_best, task, space, param=None):
 def sets_acquisition(acquisition="EI", acquisition_param=None):
     """(name, parameter) of the acquisition a multi-set sweep scores with, checked on the host before any device call:
     ``"EI"`` (no parameter: today's call, ``None``), ``"LCB"`` (beta, default 1, finite and not negative), ``"PI"`` and
-    ``"MPEI"`` (the jitter, default 0, finite), ``"VAR"`` (no parameter: 0 travels), ``"MES"`` with a pair of ints
+    ``"MPEI"`` (the jitter, default 0, finite), ``"LOGEI"`` (the log Expected Improvement of DESIGN.md §4x: the jitter, as
+    PI's), ``"VAR"`` (no parameter: 0 travels), ``"MES"`` with a pair of ints
     ``(num_samples, grid_size)``, ``num_samples`` in 1..64, ``grid_size`` at least 1 (the parameter returned is that pair).
     Anything else raises ``ValueError`` -- a bare ``"MES"`` too: this function never answered for it and has no default for
     it; ``sets_acquisition_or_default`` -- what ``find_next_y_points``, ``CBOAcquisitionPath`` and ``CBO`` call -- puts
@@ -259,7 +267,7 @@ def sets_acquisition(acquisition="EI", acquisition_param=None):
         name, param = acquisition                 # an earlier answer of this function (a path keeps its own): checked again
         sets_acquisition(name, None if name in ("EI", "VAR") else param)
         return acquisition
-    if not isinstance(acquisition, str) or acquisition not in ("EI", "MES") + POINTWISE_ACQUISITIONS:
+    if not isinstance(acquisition, str) or acquisition not in ("EI", "MES", LOG_EI) + POINTWISE_ACQUISITIONS:
         raise ValueError("acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR' in a multi-set sweep, "
                          f"not {acquisition!r}")
     if acquisition == "MES":
@@ -373,11 +381,17 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     ``ValueError`` before any device call.  ``False`` takes exactly today's calls.
     ``device_prior=True`` (with ``refine=True``; ``ValueError`` without): a causal set whose prior closures are the do-calculus
     closures joins the refinement's device launch through a device-resident prior (``refine_sets(device_prior=True)``,
-    DESIGN.md §4u) instead of ``refine_batched``.  ``False`` takes exactly today's calls."""
+    DESIGN.md §4u) instead of ``refine_batched``.  ``False`` takes exactly today's calls.
+    ``acquisition="LOGEI"`` with ``acquisition_param`` (the jitter, default 0): the log Expected Improvement minus the
+    logarithm of the cost for every set in the same one call (``cbo_acq_sweep_sets_logei``) -- per set what
+    ``find_next_y_point(acquisition="LOGEI")`` returns -- and, with ``refine=True``, refined by ``cbo_acq_refine_sets_logei``
+    (causal sets through the host route).  Together with non-empty ``constraints``, ``hyper_samples``, ``batch_size``,
+    ``device_prior=True`` or ``raw=True`` it raises ``ValueError`` before any device call."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
     checked_device_prior(device_prior, refine)
+    checked_log_ei(kind, device_prior, raw)
     checked_refine(refine, kind, constraints, hyper_samples, batch_size, raw, spaces, len(models))
     batch_size = checked_batch_size(batch_size, kind, constraints, hyper_samples, raw)
     if batch_size is not None and task not in _lib.TASK_CODE:
@@ -453,6 +467,11 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
         _lib.check(_lib.load().cbo_acq_sweep_sets_mes(s, st["gps"], st["cds"], st["mes_args"][0], st["mes_args"][1],
                                                       _lib.dptr(batch_cost), _lib.dptr(vals),
                                                       idxs.ctypes.data_as(_lib.c_int64_p)))
+    elif kind[0] == LOG_EI:
+        st.pop("trial_args", None)               # (a trial step with the log EI takes the three-call route)
+        _lib.check(_lib.load().cbo_acq_sweep_sets_logei(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task],
+                                                        kind[1], _lib.dptr(batch_cost), _lib.dptr(vals),
+                                                        idxs.ctypes.data_as(_lib.c_int64_p)))
     elif kind[0] == "EI":
         _lib.check(_lib.load().cbo_acq_sweep_sets(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
                                                   _lib.dptr(batch_cost), _lib.dptr(vals),
@@ -486,6 +505,18 @@ def checked_device_prior(device_prior, refine):
     if device_prior and not refine:
         raise ValueError("device_prior=True puts causal sets into the refinement's device launch: refine must be True")
     return bool(device_prior)
+
+
+def checked_log_ei(kind, device_prior=False, raw=False):
+    """What the log Expected Improvement does not combine with beyond what the other checks refuse for every kind but the
+    EI (constraints, hyper-parameter samples, batches): a device-resident prior in the refinement (the kernel's causal
+    instantiation of this kind is not built) and several ranks (their exchange rescales values by a cost ratio)."""
+    if kind[0] != LOG_EI:
+        return
+    if device_prior:
+        raise ValueError("acquisition='LOGEI' refines causal sets through the host route: device_prior must be False")
+    if raw:
+        raise ValueError("acquisition='LOGEI' is not defined across several ranks (raw=True)")
 
 
 def checked_refine(refine, kind, constraints=None, hyper_samples=None, batch_size=None, raw=False, spaces=None, n_sets=None):

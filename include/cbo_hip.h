@@ -370,6 +370,23 @@ int cbo_acq_sweep_kind(cbo_gp *gp, cbo_cands *cands, int kind, double y_best, in
                        double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx);
 int cbo_gp_plugin_incumbent(cbo_gp *gp, int task, double *incumbent_out);
 
+/* log Expected Improvement over a cost (Ament et al. 2023, "Unexpected improvements to expected
+ * improvement"): cbo_acq_sweep_kind's argument list without kind, param being the jitter.
+ *     acq = log h(u) + log s - log cost,   h(u) = phi(u) + u Phi(u),   s = sqrt(var),
+ *     u = (y_best - (mean + jitter)) / s for task 'min',   u = ((mean - jitter) - y_best) / s for task 'max'
+ * computed without underflow (three ranges of u; finite and correct down to u = -3e7), so that candidates whose EI is an
+ * exact 0.0 in double precision -- u < -38.6: most of a grid once a model with noise 1e-10 has a few dozen observations --
+ * keep a strict order and a gradient.  Wherever EI is representable the arg-max is cbo_acq_sweep's.  Task 'max' is the MIRROR
+ * of 'min' (the improvement of a maximiser): it is NOT the logarithm of cbo_acq_sweep's 'max' value, which is the reference's
+ * negative -EI and has none.  mean_out / var_out are cbo_acq_sweep_kind's bits; s and the quotient u are formed as
+ * cbo_acq_sweep forms them; the tie rule, the outputs that may be NULL and the route to q, mu are cbo_acq_sweep_kind's.  A NaN
+ * mean or variance gives NaN.  The multi-set and refinement forms are cbo_acq_sweep_sets_logei and cbo_acq_refine_sets_logei,
+ * below; a one-call trial step, the constrained, hyper-marginalised, plug-in and batch forms are out of scope.
+ * CBO_ERR_INVALID, scalars first: a bad task, a non-finite jitter or y_best, cost <= 0 or NaN; then cbo_acq_sweep's argument
+ * checks.  Unfitted model: CBO_ERR_NOT_FITTED. */
+int cbo_acq_sweep_logei(cbo_gp *gp, cbo_cands *cands, double y_best, int task, double jitter, double cost,
+                        double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
@@ -603,6 +620,15 @@ int cbo_trial_step_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands,
                         int kind, const double *y_best, int task, double param, const double *costs, double *best_vals,
                         int64_t *best_idxs, int *chosen_out);
 
+/* cbo_acq_sweep_sets_kind for the log Expected Improvement of cbo_acq_sweep_logei: its argument list without
+ * kind, param being the jitter; y_best[i] is set i's incumbent.  Routing is cbo_acq_sweep_sets_kind's (small_sets_kernel with
+ * log_ei_of's epilogue; larger and fp32 models: cbo_gp_fit if unfitted, then cbo_acq_sweep_logei, inside the same call), and
+ * so is the contract: per set, bit for bit, what cbo_acq_sweep_logei returns on a fitted twin; models the one launch takes are
+ * left untouched.  CBO_ERR_INVALID, before any model is touched: a bad task, a non-finite jitter or y_best[i], costs[i] <= 0
+ * or NaN, and cbo_acq_sweep_sets' argument checks. */
+int cbo_acq_sweep_sets_logei(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
+                             double jitter, const double *costs, double *best_vals, int64_t *best_idxs);
+
 /* cbo_acq_sweep_sets for the constrained acquisition of cbo_acq_sweep_constrained: set i is an objective pair
  * (gps[i], cands[i]) and n_con[i] constraint pairs, whose five con_* entries lie set-major in arrays of sum(n_con) entries
  * (set 0's constraints, then set 1's, ...); the arrays may be NULL when every n_con[i] is 0.  Sets of one call may have
@@ -742,6 +768,16 @@ typedef struct cbo_refine_set {
 int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int kind, const double *y_best,
                         int task, double param, int max_rounds, double *x_out, double *val_out, double *grad_out,
                         int *rounds_out, int *status_out);
+/* cbo_acq_refine_sets for the log Expected Improvement: its argument list without kind, param being the
+ * jitter.  value = log EI(x) - log c(x) and gradient = d log EI(x) -- NOT divided by the cost: the logarithm of a quotient with
+ * the reference's zero cost gradient.  The value reported at a point is, bit for bit, what cbo_acq_sweep_sets_logei returns
+ * for a one-point grid there with costs[i] = c(x).  A start where the EI and its gradient are exact zeros (kind 0 ends there
+ * with CBO_REFINE_PGTOL after 0 rounds) has a finite value and a gradient here.  A causal set is DECLINED, as it is by
+ * cbo_acq_refine_sets (the causal instantiation of this kind is out of scope), as are larger and fp32 models.
+ * CBO_ERR_INVALID: cbo_acq_refine_sets' checks, a non-finite jitter or y_best[i]. */
+int cbo_acq_refine_sets_logei(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, const double *y_best, int task,
+                              double jitter, int max_rounds, double *x_out, double *val_out, double *grad_out,
+                              int *rounds_out, int *status_out);
 
 /* The do-calculus prior of an RBF graph GP as a device-resident handle (src/DoCalculus.py:34-89).  With the
  * graph GP's inputs X_g, the observed rows O (n_obs x d_in) and the intervened columns I,
