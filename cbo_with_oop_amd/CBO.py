@@ -89,6 +89,11 @@ class CBOAcquisitionPath:
     default 0) scores every set with the logarithm of the causal EI minus the logarithm of the cost, computed without
     underflow: where the EI of every candidate is an exact 0.0 the sets still rank; no constraints, no
     hyper-parameter samples, no batch, no ``device_prior``, a single process, and ``trial_step`` takes the three-call route.
+    ``cost_mode="pointwise"`` (with ``"EI"`` or ``"LOGEI"``) scores every candidate over its OWN cost,
+    ``EI(x) / c(x)``, where the default ``"batch"`` divides a whole grid by one scalar (the reference's quirk): the value
+    reported for a set is the winner's own, ``refine=True`` climbs with the cost's own gradient, and ``trial_step`` takes the
+    three-call route; no constraints, hyper-parameter samples, batch or ``device_prior``, a single process, and a cost table
+    ``cost_structure`` recognises.
     ``constraints`` (a list of ``(name, sense, value[, jitter])``, at most 8, shared by all sets; ``sense`` ``"<="`` or
     ``">="``) with ``constraint_data_y`` (``constraint_data_y[s][c]`` is (n_s, 1): the values of node ``c`` at ``data_x[s]``)
     make every set's score ``EI * prod PoF / cost``: the path keeps ``constraint_models[s][c]`` --
@@ -121,10 +126,10 @@ class CBOAcquisitionPath:
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
                  update_incumbent=False, refine=False, hyper_sampler="host", device_prior=False, mle_optimizer="host",
-                 mle_restarts=1, hyper_priors=None):
+                 mle_restarts=1, hyper_priors=None, cost_mode="batch"):
         from .GaussianProcessFactory import checked_mle_optimizer
         from .utils_functions.priors import checked_priors
-        from .utils_functions.utils import (checked_device_prior, checked_log_ei, checked_refine,
+        from .utils_functions.utils import (checked_device_prior, checked_log_ei, checked_pointwise_cost, checked_refine,
                                             sets_acquisition_or_default as sets_acquisition)
         self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
         self.device_prior = checked_device_prior(device_prior, refine)
@@ -152,6 +157,13 @@ class CBOAcquisitionPath:
         self.update_incumbent = bool(update_incumbent)
         self.refine = checked_refine(refine, self._kind, self.constraints, self.hyper_samples, self.batch_size, False,
                                      space_list, len(exploration_set))
+        # "batch": the reference's one scalar per grid; "pointwise" (DESIGN.md §4y): every candidate over its own cost
+        self.cost_mode = "pointwise" if checked_pointwise_cost(cost_mode, self._kind, self.constraints, self.hyper_samples,
+                                                               self.batch_size, self.device_prior) else "batch"
+        if self.cost_mode == "pointwise":
+            from .utils_functions.cost_functions import PointwiseCost
+            for es in exploration_set:
+                PointwiseCost(costs, es)                     # (a cost cost_structure does not recognise: ValueError here)
         self.gp_type = gp_type
         self.exploration_set = exploration_set
         self.es_size = len(exploration_set)
@@ -326,6 +338,8 @@ class CBOAcquisitionPath:
             raise ValueError(f"gradient refinement is run by a single process: the placement is {mode!r}")
         if self._kind[0] == "LOGEI" and mode != "single":
             raise ValueError(f"the log Expected Improvement is scored by a single process: the placement is {mode!r}")
+        if self.cost_mode == "pointwise" and mode != "single":
+            raise ValueError(f"cost_mode='pointwise' is scored by a single process: the placement is {mode!r}")
         if mode == "single":
             grids = [self.candidate_grid(s) for s in range(self.es_size)]
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
@@ -333,7 +347,7 @@ class CBOAcquisitionPath:
                                       hyper_samples=None if self.hyper_samples is None else list(self.hyper_rows),
                                       spaces=self.space_list if (self._kind[0] == "MES" or self.refine) else None,
                                       batch_size=self.batch_size, update_incumbent=self.update_incumbent,
-                                      refine=self.refine, device_prior=self.device_prior)
+                                      refine=self.refine, device_prior=self.device_prior, cost_mode=self.cost_mode)
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -405,6 +419,7 @@ class CBOAcquisitionPath:
         model = self.models[s] if (s is not None and self.models) else None
         fast = (st is not None and model is not None and not self.constraints and self.hyper_samples is None
                 and self._kind[0] not in ("MES", "LOGEI") and self.batch_size is None and not self.refine
+                and self.cost_mode == "batch"
                 and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
                 and model._hyper_initial and st["cost_table"] is self.costs
@@ -526,7 +541,8 @@ class CBO(CBOAcquisitionPath):
                  num_additional_observations=20, type_cost=1, name_index=0, target_functions=None, grid_shapes=None,
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
                  constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False,
-                 hyper_sampler="host", device_prior=False, mle_optimizer="host", mle_restarts=1, hyper_priors=None):
+                 hyper_sampler="host", device_prior=False, mle_optimizer="host", mle_restarts=1, hyper_priors=None,
+                 cost_mode="batch"):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType, checked_mle_optimizer
         checked_mle_optimizer(mle_optimizer, mle_restarts)
@@ -580,6 +596,9 @@ class CBO(CBOAcquisitionPath):
             raise ValueError("device_prior=True puts causal sets into the refinement's device launch: refine must be True")
         from .utils_functions.utils import checked_log_ei
         checked_log_ei(sets_acquisition(acquisition, acquisition_param), device_prior)
+        from .utils_functions.utils import checked_pointwise_cost
+        checked_pointwise_cost(cost_mode, sets_acquisition(acquisition, acquisition_param), path_constraints, hyper_samples,
+                               batch_size, device_prior)
         sem = None
         if path_constraints and constraint_functions is None:
             from functools import partial
@@ -597,7 +616,7 @@ class CBO(CBOAcquisitionPath):
                          constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
                          update_incumbent=update_incumbent, refine=refine, hyper_sampler=hyper_sampler,
                          device_prior=device_prior, mle_optimizer=mle_optimizer, mle_restarts=mle_restarts,
-                         hyper_priors=hyper_priors)
+                         hyper_priors=hyper_priors, cost_mode=cost_mode)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions

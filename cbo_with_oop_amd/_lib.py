@@ -189,6 +189,17 @@ SIGNATURES = {
                                         c_double_p, ctypes.c_int64, c_void_pp]),
     "cbo_cands_destroy": (None, [ctypes.c_void_p]),
     "cbo_cands_keep_solution": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    # per-candidate intervention costs
+    "cbo_cands_set_cost": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_int_p]),
+    "cbo_cands_get_cost": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
+    "cbo_cands_clear_cost": (ctypes.c_int, [ctypes.c_void_p]),
+    "cbo_acq_sweep_pointcost": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                               ctypes.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_int64_p]),
+    "cbo_acq_sweep_sets_pointcost": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, ctypes.c_int, c_double_p, ctypes.c_int,
+                                                    ctypes.c_double, c_double_p, c_int64_p]),
+    "cbo_acq_refine_sets_pointcost": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), ctypes.c_int,
+                                                     c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p,
+                                                     c_double_p, c_double_p, c_int_p, c_int_p]),
     "cbo_gp_append": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                      c_int_p]),
     "cbo_gp_append_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,

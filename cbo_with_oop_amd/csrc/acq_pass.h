@@ -15,10 +15,13 @@ constexpr int kPassThreads = 256;
 // never stored); nothing is read at or beyond m, and where there is nothing to read the registers keep their values.
 // The workgroup's first candidate, base, is uniform (scalar registers) and the lane's share of the address a constant 16 tid
 // bytes: every access is "scalar base + 32-bit lane offset".  causal: pm and pv are read too (uniform; a constant where the
-// kernel knows it at compile time).
+// kernel knows it at compile time).  COST (compile time): a fifth stream, the candidates' own costs, into
+// *c2 -- fetched beside the others under the same tail decision; without it cost and c2 are not looked at.
+template <bool COST = false>
 __device__ __forceinline__ void fetch_pair(const double *__restrict__ q, const double *__restrict__ mu,
                                            const double *__restrict__ pm, const double *__restrict__ pv, bool causal,
-                                           int64_t m, int64_t base, d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2)
+                                           int64_t m, int64_t base, d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2,
+                                           const double *__restrict__ cost = nullptr, d2 *c2 = nullptr)
 {
     const unsigned lane2 = 2 * threadIdx.x;
     constexpr int64_t span = 2 * kPassThreads;
@@ -29,6 +32,7 @@ __device__ __forceinline__ void fetch_pair(const double *__restrict__ q, const d
             pm2 = *reinterpret_cast<const d2 *>(pm + base + lane2);
             pv2 = *reinterpret_cast<const d2 *>(pv + base + lane2);
         }
+        if constexpr (COST) *c2 = *reinterpret_cast<const d2 *>(cost + base + lane2);
         return;
     }
     const int64_t at = base + lane2;
@@ -39,6 +43,7 @@ __device__ __forceinline__ void fetch_pair(const double *__restrict__ q, const d
             pm2 = *reinterpret_cast<const d2 *>(pm + at);
             pv2 = *reinterpret_cast<const d2 *>(pv + at);
         }
+        if constexpr (COST) *c2 = *reinterpret_cast<const d2 *>(cost + at);
     } else if (at < m) {
         q2 = d2{q[at], q[at]};
         mu2 = d2{mu[at], mu[at]};
@@ -46,6 +51,7 @@ __device__ __forceinline__ void fetch_pair(const double *__restrict__ q, const d
             pm2 = d2{pm[at], pm[at]};
             pv2 = d2{pv[at], pv[at]};
         }
+        if constexpr (COST) *c2 = d2{cost[at], cost[at]};
     }
 }
 
@@ -73,10 +79,15 @@ __device__ __forceinline__ void store_pair(double *const (&dst)[N], const d2 (&v
 }
 
 // The operands of a step are in their registers before anything behind this line is issued; nothing memory moves across it.
-// Only what was loaded is named: a model without a prior has no pm2 / pv2 to hold back.
-template <bool CAUSAL>
-__device__ __forceinline__ void operand_fence(d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2)
+// Only what was loaded is named: a model without a prior has no pm2 / pv2 to hold back, a pass without COST no c2.
+template <bool CAUSAL, bool COST = false>
+__device__ __forceinline__ void operand_fence(d2 &q2, d2 &mu2, d2 &pm2, d2 &pv2, d2 *c2 = nullptr)
 {
+    if constexpr (COST) {
+        if (CAUSAL) asm volatile("" : "+v"(q2), "+v"(mu2), "+v"(pm2), "+v"(pv2), "+v"(*c2) : : "memory");
+        else asm volatile("" : "+v"(q2), "+v"(mu2), "+v"(*c2) : : "memory");
+        return;
+    }
     if (CAUSAL) asm volatile("" : "+v"(q2), "+v"(mu2), "+v"(pm2), "+v"(pv2) : : "memory");
     else asm volatile("" : "+v"(q2), "+v"(mu2) : : "memory");
 }
@@ -106,12 +117,14 @@ __device__ __forceinline__ void lane_argmax(bool valid, double acq, int64_t gi, 
 // CAUSAL: the candidates carry a prior mean / variance.  p: what posterior_of reads.  scored (uniform; a constant in every
 // kernel but acq_kernel): false leaves the posterior alone -- no scoring, no arg-max, acq_out ignored.  score: the
 // epilogue's own part, (d2 mean2, d2 var2) -> the pair's acquisition values; it takes the pair BY VALUE (see `store` below).
-template <bool CAUSAL, class Score>
+// COST (compile time): `cost` holds one cost per candidate, the pair's travels with the other operands and
+// score is (d2 mean2, d2 var2, d2 cost2).  Without it the pass is what it was: cost is not looked at.
+template <bool CAUSAL, class Score, bool COST = false>
 __device__ __forceinline__ void acq_pass(const double *__restrict__ q, const double *__restrict__ mu,
                                          const double *__restrict__ pm, const double *__restrict__ pv, int64_t m,
                                          const AcqParams &p, bool scored, double *__restrict__ mean_out,
                                          double *__restrict__ var_out, double *__restrict__ acq_out, int64_t index_offset,
-                                         Score score, double &bv, int64_t &bi)
+                                         Score score, double &bv, int64_t &bi, const double *__restrict__ cost = nullptr)
 {
     if (!scored) acq_out = nullptr;
     const int64_t stride = 2 * (int64_t)gridDim.x * kPassThreads, span = 2 * (int64_t)kPassThreads;
@@ -126,12 +139,14 @@ __device__ __forceinline__ void acq_pass(const double *__restrict__ q, const dou
     };
     d2 qn = {0.0, 0.0}, mun = {0.0, 0.0}, pmn = {0.0, 0.0}, pvn = {0.0, 0.0};
     d2 mean_done = {0.0, 0.0}, var_done = {0.0, 0.0}, acq_done = {0.0, 0.0};
-    fetch_pair(q, mu, pm, pv, CAUSAL, m, cu, qn, mun, pmn, pvn);
+    [[maybe_unused]] d2 cn = {0.0, 0.0};
+    fetch_pair<COST>(q, mu, pm, pv, CAUSAL, m, cu, qn, mun, pmn, pvn, cost, &cn);
     for (int64_t done = -1; cu < m; done = cu, cu += stride) {
         d2 q2 = qn, mu2 = mun, pm2 = pmn, pv2 = pvn;
-        operand_fence<CAUSAL>(q2, mu2, pm2, pv2);
+        [[maybe_unused]] d2 c2 = cn;
+        operand_fence<CAUSAL, COST>(q2, mu2, pm2, pv2, &c2);
         if (done >= 0) store(done, mean_done, var_done, acq_done);
-        fetch_pair(q, mu, pm, pv, CAUSAL, m, cu + stride, qn, mun, pmn, pvn);
+        fetch_pair<COST>(q, mu, pm, pv, CAUSAL, m, cu + stride, qn, mun, pmn, pvn, cost, &cn);
         const bool full = cu + span <= m;                        // uniform
         const int64_t c = cu + lane2;
         d2 mean2, var2, acq2 = {0.0, 0.0};                       // (acq2: dead wherever scored is a constant)
@@ -143,7 +158,8 @@ __device__ __forceinline__ void acq_pass(const double *__restrict__ q, const dou
             var2[e] = var;
         }
         if (scored) {
-            acq2 = score(mean2, var2);
+            if constexpr (COST) acq2 = score(mean2, var2, c2);
+            else acq2 = score(mean2, var2);
             lane_argmax(full || c < m, acq2[0], c + index_offset, bv, bi);
             lane_argmax(full || c + 1 < m, acq2[1], c + 1 + index_offset, bv, bi);
         }

@@ -140,6 +140,7 @@ struct cbo_ctx {
     // reads them (pinned); the grids' mean / var workspace, every set's points one after the other; the bisections' table,
     // quantiles and status words
     PinnedBuf<cbo_small_aux> aux_host;
+    PinnedBuf<const double *> cost_ptrs_host;                   // cbo_acq_sweep_sets_pointcost: every small set's cost vector
     PinnedBuf<double> mes_host;
     GrowBuf<double> gumbel_mean, gumbel_var, gumbel_out;
     GrowBuf<int64_t> gumbel_status;
@@ -275,6 +276,11 @@ struct cbo_cands {
     int64_t v_ld = 0, v_rows_cap = 0, v_rows = 0;
     uint64_t v_stamp = 0;
     double *partial = nullptr;       // [64][m_pad] slice sums of the row update
+    // cbo_cands_set_cost: c(x_j) of every raw point under the table it was formed from; has_cost falls
+    // wherever the raw points are replaced (cands_describe: only the context's scratch sets are ever refilled)
+    GrowBuf<double> cost;
+    CostTable cost_table{};
+    bool has_cost = false;
 };
 
 // b to at least n elements (nothing happens when they fit): an old buffer is freed only after the queued work that may
@@ -1045,7 +1051,7 @@ static int cands_reserve(cbo_cands *k, int64_t m, int d, bool prior)
         const int cd = d > k->cap_d ? d : k->cap_d;
         const bool cp = prior || k->cap_prior;
         hipFree(k->raw); hipFree(k->P.xs); hipFree(k->P.sq); hipFree(k->P.sv); hipFree(k->pm); hipFree(k->pv);
-        k->q.release(); k->mu.release();
+        k->q.release(); k->mu.release(); k->cost.release();
         k->raw = k->P.xs = k->P.sq = k->P.sv = k->pm = k->pv = nullptr;
         k->cap_m_pad = 0; k->cap_d = 0; k->cap_prior = false; k->fit_stamp = 0;
         hipError_t e = hipMalloc(&k->raw, sizeof(double) * cap * cd);
@@ -1070,6 +1076,19 @@ static void cands_describe(cbo_cands *k, int64_t m, int d, bool prior, int64_t i
     k->has_prior = prior;
     k->prepared_for = nullptr; k->prepared_ls.clear();
     k->fit_stamp = 0; k->v_stamp = 0;
+    k->has_cost = false;                               // (the raw points are about to change)
+}
+
+// the set's cost vector from its raw points and its cost table (queued)
+static int cands_form_cost(cbo_cands *k)
+{
+    cbo_ctx *c = k->ctx;
+    const int rc = grow(c, k->cost, (size_t)k->cap_m_pad);
+    if (rc != CBO_OK) return rc;
+    launch_cands_cost(c->stream, k->raw, k->m, k->d, k->cost_table, k->cost);
+    HIP_TRY(hipGetLastError());
+    k->has_cost = true;
+    return CBO_OK;
 }
 
 // (re)fill a candidate set from host arrays
@@ -1168,6 +1187,51 @@ static int cands_cache_vectors(cbo_cands *k)
     int rc = grow(k->ctx, k->q, (size_t)k->cap_m_pad);
     if (rc == CBO_OK) rc = grow(k->ctx, k->mu, (size_t)k->cap_m_pad);
     return rc;
+}
+
+// ---- per-candidate intervention costs -------------------------------------------------------------------
+// cbo_acq_refine_sets' checks of a cost table: finite fixed costs, flags 0 or 1, a fixed-cost sum above 0 -- so c(x) > 0
+static int check_cost_table(int d, const double *fix, const int *variable, const std::string &where = "")
+{
+    double fix_sum = 0.0;
+    for (int k = 0; k < d; ++k) {
+        if (!std::isfinite(fix[k])) return fail(CBO_ERR_INVALID, "the fixed costs must be finite" + where);
+        if (variable[k] != 0 && variable[k] != 1) return fail(CBO_ERR_INVALID, "cost_variable must be 0 or 1" + where);
+        fix_sum += fix[k];
+    }
+    if (!(fix_sum > 0.0)) return fail(CBO_ERR_INVALID, "the fixed costs must sum to a positive cost" + where);
+    return CBO_OK;
+}
+
+extern "C" int cbo_cands_set_cost(cbo_cands *k, const double *fix, const int *variable)
+{
+    if (!k || !fix || !variable) return fail(CBO_ERR_INVALID, "NULL argument: cands, fix and variable must be given");
+    int rc = check_cost_table(k->d, fix, variable);
+    if (rc != CBO_OK) return rc;
+    HIP_TRY(hipSetDevice(k->ctx->device));
+    k->cost_table = CostTable{};
+    for (int j = 0; j < k->d; ++j) { k->cost_table.fix[j] = fix[j]; k->cost_table.variable[j] = variable[j]; }
+    rc = cands_form_cost(k);
+    if (rc != CBO_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(k->ctx->stream));
+    return CBO_OK;
+}
+
+extern "C" int cbo_cands_get_cost(const cbo_cands *k, double *out)
+{
+    if (!k || !out) return fail(CBO_ERR_INVALID, "NULL argument: cands and out must be given");
+    if (!k->has_cost) return fail(CBO_ERR_INVALID, "the candidate set has no cost vector (cbo_cands_set_cost)");
+    HIP_TRY(hipSetDevice(k->ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, k->cost.p, sizeof(double) * k->m, hipMemcpyDeviceToHost, k->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(k->ctx->stream));
+    return CBO_OK;
+}
+
+extern "C" int cbo_cands_clear_cost(cbo_cands *k)
+{
+    if (!k) return fail(CBO_ERR_INVALID, "NULL argument: cands");
+    k->has_cost = false;
+    return CBO_OK;
 }
 
 extern "C" void cbo_cands_destroy(cbo_cands *k)
@@ -1421,7 +1485,8 @@ static int copy_posterior_out(cbo_ctx *c, const cbo_cands *k, double *acq_out, d
 }
 
 // mes: max-value entropy search's epilogue (mes_acq_kernel) in the place of EI's; y_best, task and ei_jitter are then unused
-// kind: CBO_ACQ_LCB / _PI / _VAR / kLogEiKind: pointwise_acq_kernel in the place of EI's, ei_jitter being the kind's parameter; 0 and
+// kind: CBO_ACQ_LCB / _PI / _VAR / kLogEiKind: pointwise_acq_kernel in the place of EI's, ei_jitter being the kind's parameter;
+// kEiPointKind / kLogEiPointKind: pointcost_acq_kernel over the set's cost vector (the caller has checked it has one); 0 and
 // CBO_ACQ_MPEI: EI -- with y_best_dev, its incumbent is read from there (device memory) and y_best is unused
 static int enqueue_finish(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost, double *acq_out,
                           double *mean_out, double *var_out, const double *q_src, const double *mu_src,
@@ -1441,6 +1506,11 @@ static int enqueue_finish(cbo_gp *g, cbo_cands *k, double y_best, int task, doub
             launch_mes_acq(c->stream, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, *mes,
                            mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr,
                            c->part_val, c->part_idx, k->index_offset, nb);
+        else if (kind == kEiPointKind || kind == kLogEiPointKind)   // (cost is 1: every candidate is priced at k->cost)
+            launch_pointcost_acq(c->stream, kind == kLogEiPointKind, q_src, mu_src, causal ? k->pm : nullptr,
+                                 causal ? k->pv : nullptr, k->cost, k->m, p, mean_out ? c->mean : nullptr,
+                                 var_out ? c->var : nullptr, acq_out ? c->acq : nullptr, c->part_val, c->part_idx,
+                                 k->index_offset, nb);
         else if (kind == CBO_ACQ_LCB || kind == CBO_ACQ_PI || kind == CBO_ACQ_VAR || kind == kLogEiKind)
             launch_pointwise_acq(c->stream, kind, q_src, mu_src, causal ? k->pm : nullptr, causal ? k->pv : nullptr, k->m, p,
                                  mean_out ? c->mean : nullptr, var_out ? c->var : nullptr, acq_out ? c->acq : nullptr,
@@ -2498,6 +2568,21 @@ static int check_kind_args(int n_sets, int kind, const double *y_best, int *task
     return CBO_OK;
 }
 
+// the scalar checks of the *_pointcost entry points: cbo_acq_sweep_logei's, and the set's cost vector
+static int check_pointcost_args(int n_sets, int log_form, const double *y_best, int *task, double *jitter)
+{
+    if (log_form != 0 && log_form != 1) return fail(CBO_ERR_INVALID, "log_form must be 0 or 1");
+    if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
+    if (!y_best) return fail(CBO_ERR_INVALID, "NULL argument: y_best");
+    const std::vector<double> ones((size_t)n_sets, 1.0);
+    return check_kind_args(n_sets, kLogEiKind, y_best, task, jitter, ones.data(), true);
+}
+static int check_has_cost(const cbo_cands *k, const std::string &where = "")
+{
+    if (!k->has_cost) return fail(CBO_ERR_INVALID, "the candidate set has no cost vector (cbo_cands_set_cost)" + where);
+    return CBO_OK;
+}
+
 extern "C" int cbo_acq_sweep_sets_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int kind,
                                        const double *y_best, int task, double param, const double *costs,
                                        double *best_vals, int64_t *best_idxs)
@@ -2515,6 +2600,26 @@ extern "C" int cbo_acq_sweep_sets_logei(int n_sets, cbo_gp *const *gps, cbo_cand
     const int rc = check_kind_args(n_sets, kLogEiKind, y_best, &task, &jitter, costs, true);
     if (rc != CBO_OK) return rc;
     return sweep_sets_impl(n_sets, gps, cands, y_best, task, jitter, costs, best_vals, best_idxs, -1, kLogEiKind);
+}
+
+// cbo_acq_sweep_sets with every candidate priced at its own cost: the same routing, the epilogues of
+// kEiPointKind / kLogEiPointKind -- per set cbo_acq_sweep_pointcost's bits on a fitted twin
+extern "C" int cbo_acq_sweep_sets_pointcost(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int log_form,
+                                            const double *y_best, int task, double jitter, double *best_vals,
+                                            int64_t *best_idxs)
+{
+    int rc = check_pointcost_args(n_sets, log_form, y_best, &task, &jitter);
+    if (rc != CBO_OK) return rc;
+    if (!gps || !cands || !best_vals || !best_idxs) return fail(CBO_ERR_INVALID, "bad argument");
+    rc = check_set_handles(n_sets, gps, cands, task);
+    if (rc != CBO_OK) return rc;
+    for (int i = 0; i < n_sets; ++i) {
+        rc = check_has_cost(cands[i], " (set " + std::to_string(i) + ")");
+        if (rc != CBO_OK) return rc;
+    }
+    const std::vector<double> ones((size_t)n_sets, 1.0);
+    return sweep_sets_impl(n_sets, gps, cands, y_best, task, jitter, ones.data(), best_vals, best_idxs, -1,
+                           log_form ? kLogEiPointKind : kEiPointKind);
 }
 
 // cbo_acq_sweep_sets for max-value entropy search: cbo_acq_sweep_mes' checks of its scalars for every set,
@@ -2579,10 +2684,17 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
             aux.per_set = c->aux_host;
             aux.data = c->mes_host;
         }
+        if (rc == CBO_OK && (kind == kEiPointKind || kind == kLogEiPointKind)) {
+            rc = grow(c, c->cost_ptrs_host, ns < 32 ? (size_t)32 : (size_t)ns);
+            if (rc != CBO_OK) return rc;
+            for (int j = 0; j < ns; ++j) c->cost_ptrs_host[j] = cands[small[(size_t)j]]->cost.p;
+            aux.cost = c->cost_ptrs_host;
+        }
         for (int j = 0; rc == CBO_OK && j < ns; ++j) {
             const int i = small[(size_t)j];
             // (only the EI, its logarithm and the probability of improvement read the caller's incumbent)
-            const double incumbent = (kind == kEiKind || kind == CBO_ACQ_PI || kind == kLogEiKind) ? y_best[i] : 0.0;
+            const double incumbent = (kind == kEiKind || kind == CBO_ACQ_PI || kind == kLogEiKind || kind == kEiPointKind ||
+                                      kind == kLogEiPointKind) ? y_best[i] : 0.0;
             rc = fill_small_set(c->sets_host[j], gps[i], cands[i], task, incumbent, ei_jitter, costs[i], i == staged_set);
         }
         return rc;
@@ -2596,6 +2708,9 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
         if (kind == kMesKind)
             return cbo_acq_sweep_mes(gps[i], cands[i], n_samples[i], mins[i], costs[i], nullptr, nullptr, nullptr, &best_vals[i],
                                      &best_idxs[i]);
+        if (kind == kEiPointKind || kind == kLogEiPointKind)
+            return cbo_acq_sweep_pointcost(gps[i], cands[i], kind == kLogEiPointKind, y_best[i], task, ei_jitter, nullptr,
+                                           nullptr, nullptr, &best_vals[i], &best_idxs[i]);
         if (kind == kLogEiKind)
             return cbo_acq_sweep_logei(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], nullptr, nullptr, nullptr,
                                        &best_vals[i], &best_idxs[i]);
@@ -2607,7 +2722,8 @@ static int sweep_sets_impl(int n_sets, cbo_gp *const *gps, cbo_cands *const *can
     };
     return run_small_or_general(
         c, kind == kEiKind ? "cbo_acq_sweep_sets" : kind == kMesKind ? "cbo_acq_sweep_sets_mes"
-           : kind == kLogEiKind ? "cbo_acq_sweep_sets_logei" : "cbo_acq_sweep_sets_kind",
+           : kind == kLogEiKind ? "cbo_acq_sweep_sets_logei"
+           : (kind == kEiPointKind || kind == kLogEiPointKind) ? "cbo_acq_sweep_sets_pointcost" : "cbo_acq_sweep_sets_kind",
         "multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
         [&](const SmallLaunch &L) { launch_small_sets(c->stream, kind, c->sets_host, ns, blocks, L, aux); },
         [&](int j, int i) { return harvest_winner(c, j, i, best_vals, best_idxs); }, general);
@@ -2707,8 +2823,11 @@ struct cbo_do_prior {
 // sets with one to a second launch on the same stream.
 static int refine_sets_impl(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, const cbo_do_prior *const *priors,
                             int kind, const double *y_best, int task, double param, int max_rounds, double *x_out,
-                            double *val_out, double *grad_out, int *rounds_out, int *status_out, bool logei = false)
+                            double *val_out, double *grad_out, int *rounds_out, int *status_out, bool logei = false,
+                            bool pointcost = false)
 {
+    // pointcost (kind is kEiKind or kLogEiKind): the kernel's instantiation with the cost's own derivative
+    const int launch_kind = pointcost ? (kind == kLogEiKind ? kLogEiPointKind : kEiPointKind) : kind;
     if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
     if (!gps || !sets || !y_best || !x_out || !val_out || !grad_out || !rounds_out || !status_out)
         return fail(CBO_ERR_INVALID, "NULL argument");
@@ -2822,7 +2941,7 @@ static int refine_sets_impl(int n_sets, cbo_gp *const *gps, const cbo_refine_set
     }
     HIP_TRY(hipMemsetAsync(c->refine_info, 0, sizeof(int) * (size_t)ns, c->stream));
     if (n_plain > 0)
-        launch_small_sets_refine(c->stream, kind, false, c->sets_host, c->refine_host, c->refine_starts, n_plain, blocks,
+        launch_small_sets_refine(c->stream, launch_kind, false, c->sets_host, c->refine_host, c->refine_starts, n_plain, blocks,
                                  c->small_scratch, c->refine_info, max_rounds, c->refine_x, c->refine_val, c->refine_grad,
                                  c->refine_rounds, c->refine_status);
     if (ns > n_plain)
@@ -2872,6 +2991,18 @@ extern "C" int cbo_acq_refine_sets_logei(int n_sets, cbo_gp *const *gps, const c
     if (rc != CBO_OK) return rc;
     return refine_sets_impl(n_sets, gps, sets, nullptr, kLogEiKind, y_best, task, jitter, max_rounds, x_out, val_out, grad_out,
                             rounds_out, status_out, true);
+}
+
+// ... with the gradient of EI / c or log EI - log c itself: the same values, d c / d x_k = variable_k sign(x_k)
+// in the quotient rule.  Causal sets are declined (priors are not taken), as are larger and fp32 models.
+extern "C" int cbo_acq_refine_sets_pointcost(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int log_form,
+                                             const double *y_best, int task, double jitter, int max_rounds, double *x_out,
+                                             double *val_out, double *grad_out, int *rounds_out, int *status_out)
+{
+    const int rc = check_pointcost_args(n_sets, log_form, y_best, &task, &jitter);
+    if (rc != CBO_OK) return rc;
+    return refine_sets_impl(n_sets, gps, sets, nullptr, log_form ? kLogEiKind : kEiKind, y_best, task, jitter, max_rounds, x_out,
+                            val_out, grad_out, rounds_out, status_out, log_form != 0, true);
 }
 
 extern "C" int cbo_acq_refine_sets_prior(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets,
@@ -3470,6 +3601,23 @@ extern "C" int cbo_acq_sweep_logei(cbo_gp *g, cbo_cands *k, double y_best, int t
     if (rc != CBO_OK) return rc;
     if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
     return sweep_impl(g, k, y_best, task, jitter, cost, acq_out, mean_out, var_out, best_val, best_idx, nullptr, kLogEiKind);
+}
+
+// The Expected Improvement, or its logarithm, of every candidate over the candidate's OWN cost: cost[j] of
+// cbo_cands_set_cost.  cbo_acq_sweep_logei's scalar checks first, then the handles, then the cost vector.
+extern "C" int cbo_acq_sweep_pointcost(cbo_gp *g, cbo_cands *k, int log_form, double y_best, int task, double jitter,
+                                       double *acq_out, double *mean_out, double *var_out, double *best_val,
+                                       int64_t *best_idx)
+{
+    int rc = check_pointcost_args(1, log_form, &y_best, &task, &jitter);
+    if (rc != CBO_OK) return rc;
+    rc = check_sweep_args(g, k, task);
+    if (rc != CBO_OK) return rc;
+    rc = check_has_cost(k);
+    if (rc != CBO_OK) return rc;
+    if (!g->fitted) return fail(CBO_ERR_NOT_FITTED, "gp is not fitted");
+    return sweep_impl(g, k, y_best, task, jitter, 1.0, acq_out, mean_out, var_out, best_val, best_idx, nullptr,
+                      log_form ? kLogEiPointKind : kEiPointKind);
 }
 
 // What gumbel_quantiles_kernel left for one set: the single call's message for the first quantile that failed ("" = none),

@@ -348,6 +348,12 @@ constexpr int kPredictKind = 6;
 // log EI - log cost, task 'max' mirrored; ei_jitter is the jitter, y_best the incumbent.  Internal: the public kind codes
 // (CBO_ACQ_*) do not name it, the entry points cbo_acq_sweep_logei / _sweep_sets_logei / _refine_sets_logei do.
 constexpr int kLogEiKind = 7;
+// ... and two that price every candidate at its own cost: set s reads cost[c] from aux's cost[s], the cost
+// vector of its candidate set (cbo_cands_set_cost); the descriptor's cost is 1.  kEiPointKind: acquisition_of at cost 1 over
+// cost[c], the IEEE quotient; kLogEiPointKind: log_ei_of with log(cost[c]).  Internal, reached through the *_pointcost entry
+// points alone; in the refinement kernel they also select the gradient with the cost's own derivative.
+constexpr int kEiPointKind = 8;
+constexpr int kLogEiPointKind = 9;
 struct cbo_small_aux {
     int64_t off, count;
 };
@@ -355,6 +361,7 @@ struct SmallAux {
     const cbo_small_aux *per_set = nullptr;
     const double *data = nullptr;
     double *mean_out = nullptr, *var_out = nullptr;
+    const double *const *cost = nullptr;               // per set (pinned, device-mapped): its candidates' cost vector
 };
 // What every launch of these kernels takes from its context beside the descriptors: scratch and partial winners per
 // workgroup, one status word, one ticket and one (pinned) record per set, and the call's sequence number, which closes a
@@ -605,6 +612,19 @@ void launch_constrained_acq(hipStream_t s, const ConParams &p, int64_t m, double
 void launch_pointwise_acq(hipStream_t s, int kind, const double *q, const double *mu, const double *pm, const double *pv,
                           int64_t m, const AcqParams &p, double *mean_out, double *var_out, double *acq_out,
                           double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks);
+// ---- per-candidate intervention costs (kernels_pointwise.hip) -----------------------------------------
+// The reference's cost table of one exploration set, c(x) = sum_k (fix[k] + (variable[k] ? |x_k| : 0)): cbo_refine_set's pair.
+struct CostTable {
+    double fix[CBO_MAX_DIM];
+    int variable[CBO_MAX_DIM];
+};
+// cost[j] = c(raw row j) for j < m, in the refinement kernel's (and one_row_cost's) operation order
+void launch_cands_cost(hipStream_t s, const double *raw, int64_t m, int d, const CostTable &t, double *cost);
+// launch_pointwise_acq's pass with the candidates' own costs as a fifth operand stream: acquisition_of at cost 1 over cost[j]
+// (the IEEE quotient), or log_ei_of with log(cost[j]) when log_form.  p.cost must be 1.
+void launch_pointcost_acq(hipStream_t s, bool log_form, const double *q, const double *mu, const double *pm, const double *pv,
+                          const double *cost, int64_t m, const AcqParams &p, double *mean_out, double *var_out,
+                          double *acq_out, double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks);
 // out[0] (device) = min (CBO_TASK_MIN) or max of mean[0:n), NaN if any of them is
 void launch_plugin_incumbent(hipStream_t s, const double *mean, int64_t n, int task, double *out);
 // out[g] = mean of in[g*group .. (g+1)*group)

@@ -674,6 +674,15 @@ __device__ __forceinline__ void small_fetch_cand(const cbo_small_set &st, int64_
     cpv_c = st.cpv ? st.cpv[cc] : 0.0;
 }
 
+// ... and its own cost from the set's cost vector, under the same clamp
+__device__ __forceinline__ void small_fetch_cand(const cbo_small_set &st, int64_t c, double (&xc)[CBO_MAX_DIM], double &csq,
+                                                 double &csv, double &cpm_c, double &cpv_c, const double *__restrict__ cost,
+                                                 double &cost_c)
+{
+    small_fetch_cand(st, c, xc, csq, csv, cpm_c, cpv_c);
+    cost_c = cost[(c < st.m) ? c : st.m - 1];
+}
+
 // K(X, X*) of one wave's 16 candidates, straight into the MFMA result layout: small_kstar_tiles<d> (d uniform)
 __device__ __forceinline__ void small_kstar_tiles_of(const SmallShared &sh, const cbo_small_set &st, int tiles,
                                                      const double *xc, double csq, double csv, double inv_l2, int kq,

@@ -69,6 +69,74 @@ void launch_pointwise_acq(hipStream_t s, int kind, const double *q, const double
     launch(s, q, mu, pm, pv, m, p, mean_out, var_out, acq_out, part_val, part_idx, index_offset, n_blocks);
 }
 
+// ---- per-candidate intervention costs ------------------------------------------------------------------
+// cost[j] = c(x_j) = sum_k (fix[k] + (variable[k] ? |x_jk| : 0)) from the set's raw AoS points: the refinement kernel's order
+// (small_sets_refine_kernel) and the host's one_row_cost -- terms added from 0.0 in column order, no contraction.  A NaN
+// coordinate of a variable column gives a NaN cost.
+__global__ __launch_bounds__(256) void cands_cost_kernel(const double *__restrict__ raw, int64_t m, int d, const CostTable t,
+                                                         double *__restrict__ cost)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride) {
+        double c = 0.0;
+#pragma unroll
+        for (int k = 0; k < CBO_MAX_DIM; ++k)
+            if (k < d) c = c + (t.variable[k] ? t.fix[k] + fabs(raw[j * d + k]) : t.fix[k]);
+        cost[j] = c;
+    }
+}
+
+void launch_cands_cost(hipStream_t s, const double *raw, int64_t m, int d, const CostTable &t, double *cost)
+{
+    const int64_t want = (m + 255) / 256;
+    hipLaunchKernelGGL(cands_cost_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, s, raw, m, d, t, cost);
+}
+
+// acq_pass with the cost stream (COST), scored per candidate over its own cost.  LOG false: acquisition_of at cost 1 -- the
+// Expected Improvement itself -- then the IEEE quotient by cost[j] (numpy's `/`); true: log_ei_of with log(cost[j]), the
+// device library's logarithm.  mean and var are acq_kernel's bits.  p.cost must be 1.
+template <bool LOG, bool CAUSAL, bool MV>
+__global__ __launch_bounds__(256) void pointcost_acq_kernel(const double *__restrict__ q, const double *__restrict__ mu,
+                                                            const double *__restrict__ pm, const double *__restrict__ pv,
+                                                            const double *__restrict__ cost, int64_t m, AcqParams p,
+                                                            double *__restrict__ mean_out, double *__restrict__ var_out,
+                                                            double *__restrict__ acq_out, double *__restrict__ part_val,
+                                                            int64_t *__restrict__ part_idx, int64_t index_offset)
+{
+    double bv = -INFINITY;
+    int64_t bi = kNoIndex;
+    if (!MV) { mean_out = nullptr; var_out = nullptr; }
+    auto score = [&](d2 mean2, d2 var2, d2 cost2) {
+        if constexpr (LOG)
+            return d2{log_ei_of(mean2[0], var2[0], p, log(cost2[0])), log_ei_of(mean2[1], var2[1], p, log(cost2[1]))};
+        else
+            return d2{acquisition_of(mean2[0], var2[0], p) / cost2[0], acquisition_of(mean2[1], var2[1], p) / cost2[1]};
+    };
+    acq_pass<CAUSAL, decltype(score), true>(q, mu, pm, pv, m, p, true, mean_out, var_out, acq_out, index_offset, score, bv, bi,
+                                            cost);
+    block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
+}
+
+template <bool LOG>
+static void launch_pointcost_form(hipStream_t s, const double *q, const double *mu, const double *pm, const double *pv,
+                                  const double *cost, int64_t m, const AcqParams &p, double *mean_out, double *var_out,
+                                  double *acq_out, double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks)
+{
+    const bool causal = pv != nullptr, mv = mean_out || var_out;
+    auto kernel = causal ? (mv ? pointcost_acq_kernel<LOG, true, true> : pointcost_acq_kernel<LOG, true, false>)
+                         : (mv ? pointcost_acq_kernel<LOG, false, true> : pointcost_acq_kernel<LOG, false, false>);
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(256), 0, s, q, mu, pm, pv, cost, m, p, mean_out, var_out, acq_out,
+                       part_val, part_idx, index_offset);
+}
+
+void launch_pointcost_acq(hipStream_t s, bool log_form, const double *q, const double *mu, const double *pm, const double *pv,
+                          const double *cost, int64_t m, const AcqParams &p, double *mean_out, double *var_out,
+                          double *acq_out, double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks)
+{
+    auto launch = log_form ? launch_pointcost_form<true> : launch_pointcost_form<false>;
+    launch(s, q, mu, pm, pv, cost, m, p, mean_out, var_out, acq_out, part_val, part_idx, index_offset, n_blocks);
+}
+
 // out[0] = min (task 'min') or max of mean[0:n), NaN if any of them is (np.min / np.max): one workgroup, each lane a
 // strided share, then the waves' and the workgroup's reduction.  n is a model's observation count: next to the prediction
 // that produced the means this is nothing.

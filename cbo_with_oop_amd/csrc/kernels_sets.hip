@@ -27,6 +27,9 @@ static_assert(sizeof(SmallShared) + kMesMaxSamples * sizeof(double) + sizeof(int
 // candidates, ahead of the factorisation; parked in LDS behind K*'s barrier), the epilogue is mes_of.  kPredictKind: the
 // epilogue stores mean and variance at the set's offset in aux's workspace; no arg-max, the record carries the status word.
 // kLogEiKind: the epilogue is log_ei_of, log EI - log cost -- cbo_acq_sweep_logei's bits; nothing from aux.
+// kEiPointKind / kLogEiPointKind: the lane that holds candidate c reads cost[c] from the set's cost vector
+// (aux.cost[set], fetched with the candidate) and scores over it: acquisition_of at cost 1 / cost[c], or log_ei_of with
+// log(cost[c]) -- cbo_acq_sweep_pointcost's bits.
 // phases 3: every workgroup factors the model itself, into its own scratch slot; 1: one workgroup per set factors it into
 // the set's slot 0, nothing else; 2: the set's slot 0 holds the factor.
 template <int KIND, bool BYVAL>
@@ -63,7 +66,11 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
     // this wave's 16 candidates
     const int64_t c = (int64_t)blk * 64 + wave * 16 + lc;
     double xc[CBO_MAX_DIM], csq, csv, cpm_c, cpv_c;
-    small_fetch_cand(st, c, xc, csq, csv, cpm_c, cpv_c);
+    [[maybe_unused]] double cost_c = 1.0;
+    if constexpr (KIND == kEiPointKind || KIND == kLogEiPointKind)
+        small_fetch_cand(st, c, xc, csq, csv, cpm_c, cpv_c, aux.cost[set], cost_c);
+    else
+        small_fetch_cand(st, c, xc, csq, csv, cpm_c, cpv_c);
     [[maybe_unused]] cbo_small_aux ax{};
     [[maybe_unused]] double my_min = 0.0;                          // thread t < count: the set's sample t
     if constexpr (KIND == kMesKind || KIND == kPredictKind) ax = aux.per_set[set];
@@ -116,6 +123,10 @@ __global__ __launch_bounds__(256) void small_sets_kernel(const SmallSetArgs byva
             } else {
                 if constexpr (KIND == kLogEiKind)
                     bv = log_ei_of(mean, var, p);
+                else if constexpr (KIND == kLogEiPointKind)
+                    bv = log_ei_of(mean, var, p, log(cost_c));
+                else if constexpr (KIND == kEiPointKind)
+                    bv = acquisition_of(mean, var, p) / cost_c;  // (p.cost is 1: the EI itself, then the IEEE quotient)
                 else
                     bv = (KIND == kEiKind || KIND == CBO_ACQ_MPEI) ? acquisition_of(mean, var, p)
                                                                    : pointwise_of<KIND>(mean, var, p);
@@ -168,6 +179,8 @@ void launch_small_sets(hipStream_t s, int kind, const cbo_small_set *sets, int n
         case kMesKind: CBO_LAUNCH_KIND(kMesKind); break;
         case kPredictKind: CBO_LAUNCH_KIND(kPredictKind); break;
         case kLogEiKind: CBO_LAUNCH_KIND(kLogEiKind); break;
+        case kEiPointKind: CBO_LAUNCH_KIND(kEiPointKind); break;
+        case kLogEiPointKind: CBO_LAUNCH_KIND(kLogEiPointKind); break;
         default: CBO_LAUNCH_KIND(kEiKind); break;
     }
 #undef CBO_LAUNCH_KIND

@@ -45,6 +45,9 @@ static_assert(2 * 4 * (16 / 2) <= 64 && kRefineHistory * CBO_MAX_DIM <= 64, "one
 // (mean, var) as the host classes form them (CausalExpectedImprovement.evaluate_with_gradients; pointwise_acquisitions.py).
 // The value is the sweep's own (acquisition_of / pointwise_of<KIND> / log_ei_of); the coefficients repeat its intermediate steps.
 // kLogEiKind: the value is log EI - log cost and (a, b) are the coefficients of d logEI itself -- not over the cost.
+// kEiPointKind / kLogEiPointKind: kEiKind's and kLogEiKind's values and coefficients -- the first at cost 1:
+// the caller divides by the point's cost itself, as the sweeps of these kinds do -- and the caller adds the cost's own
+// derivative, d c / d x_k = variable_k sign(x_k), to the gradient.
 
 // log EI - log cost, s, and the coefficients of d logEI = (-A d mean + B d sd) / s, d mean's sign flipped for 'max'
 // (log_h_of<true>).  The value is log_ei_of's, operation for operation.
@@ -74,7 +77,7 @@ __device__ __forceinline__ double value_and_coefficients(double mean, double var
     bool special;
     sqrt_and_reciprocal(var, s, rs, special);
     const double sign = (p.task == CBO_TASK_MIN) ? 1.0 : -1.0;
-    if constexpr (KIND == kEiKind || KIND == CBO_ACQ_MPEI || KIND == CBO_ACQ_PI) {
+    if constexpr (KIND == kEiKind || KIND == CBO_ACQ_MPEI || KIND == CBO_ACQ_PI || KIND == kEiPointKind) {
         const double u = (p.y_best - (mean + p.ei_jitter)) / s;
         const double e = exp_nonpositive(-(u * u) / 2.0);
         const double pdf = e * 0.3989422804014327;
@@ -88,7 +91,7 @@ __device__ __forceinline__ double value_and_coefficients(double mean, double var
             b = sign * pdf;
             return acquisition_of(mean, var, p);
         }
-    } else if constexpr (KIND == kLogEiKind) {
+    } else if constexpr (KIND == kLogEiKind || KIND == kLogEiPointKind) {
         // (the caller does NOT divide this kind by the cost: the cost's gradient is the reference's zero)
         const LogEiTerms t = log_ei_value_and_coefficients(mean, var, p.y_best, p.ei_jitter, p.task, p.cost);
         s = t.s;
@@ -266,14 +269,22 @@ __global__ __launch_bounds__(256) void small_sets_refine_kernel(const SmallSetAr
 #pragma unroll
             for (int k = 0; k < CBO_MAX_DIM; ++k)
                 if (k < d) cost = cost + (rf.variable[k] ? rf.fix[k] + fabs(xt[k]) : rf.fix[k]);
-            p.cost = cost;
+            p.cost = (KIND == kEiPointKind) ? 1.0 : cost;
             double s, a, b;
-            const double value = value_and_coefficients<KIND>(mean, var, p, s, a, b);
+            double value = value_and_coefficients<KIND>(mean, var, p, s, a, b);
+            if constexpr (KIND == kEiPointKind) value = value / cost;      // (the sweep's: EI at cost 1, the IEEE quotient)
             double grad[CBO_MAX_DIM];
 #pragma unroll
             for (int k = 0; k < CBO_MAX_DIM; ++k) {
                 grad[k] = a * dmean[k] + b * (dvar[k] / (2.0 * s));
-                if constexpr (KIND != kLogEiKind) grad[k] = grad[k] / cost;
+                if constexpr (KIND == kEiPointKind || KIND == kLogEiPointKind) {
+                    // the quotient rule with the cost's own derivative, sign(0) = 0
+                    const double dc = (k < d && rf.variable[k]) ? (xt[k] > 0.0 ? 1.0 : (xt[k] < 0.0 ? -1.0 : 0.0)) : 0.0;
+                    if constexpr (KIND == kEiPointKind) grad[k] = (grad[k] - value * dc) / cost;
+                    else grad[k] = grad[k] - dc / cost;
+                } else if constexpr (KIND != kLogEiKind) {
+                    grad[k] = grad[k] / cost;
+                }
             }
             refine_feed(rs, lo, hi, value, grad, max_rounds);
         }
@@ -331,6 +342,11 @@ void launch_small_sets_refine(hipStream_t s, int kind, bool prior, const cbo_sma
         case CBO_ACQ_MPEI: CBO_LAUNCH_KIND(CBO_ACQ_MPEI); break;
         // (log EI: plain sets alone -- the causal instantiation is not built, refine_sets_impl declines such a set)
         case kLogEiKind: byval ? CBO_LAUNCH_AS(kLogEiKind, true, false) : CBO_LAUNCH_AS(kLogEiKind, false, false); break;
+        // (the point-cost kinds likewise)
+        case kEiPointKind: byval ? CBO_LAUNCH_AS(kEiPointKind, true, false) : CBO_LAUNCH_AS(kEiPointKind, false, false); break;
+        case kLogEiPointKind:
+            byval ? CBO_LAUNCH_AS(kLogEiPointKind, true, false) : CBO_LAUNCH_AS(kLogEiPointKind, false, false);
+            break;
         default: CBO_LAUNCH_KIND(kEiKind); break;
     }
 #undef CBO_LAUNCH_KIND

@@ -1,9 +1,10 @@
 """Mirror of the reference package ``src.utils_functions`` for the names on the hot path
 (/root/reference/src/utils_functions/__init__.py star-imports the same modules)."""
-from .causal_acquisition_functions import AcquisitionQuotient, CausalExpectedImprovement, CandidateGrid  # noqa: F401
+from .causal_acquisition_functions import (AcquisitionQuotient, CausalExpectedImprovement, CandidateGrid,  # noqa: F401
+                                           PointCostQuotient)
 from .causal_optimizer import CausalGradientAcquisitionOptimizer  # noqa: F401
 from .constrained import AcquisitionProduct, ProbabilityOfFeasibility  # noqa: F401
-from .cost_functions import Cost, total_cost  # noqa: F401
+from .cost_functions import Cost, PointwiseCost, total_cost  # noqa: F401
 from .greedy_batch import GreedyBatchPointCalculator  # noqa: F401
 from .integrated_hyper import IntegratedHyperParameterAcquisition, hmc_sample  # noqa: F401
 from .integrated_variance import IntegratedVarianceReduction  # noqa: F401

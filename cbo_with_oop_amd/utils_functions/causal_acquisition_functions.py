@@ -157,7 +157,11 @@ class CausalExpectedImprovement:
 
     def __truediv__(self, cost):
         """``CausalExpectedImprovement(...) / Cost(...)`` as in src/utils_functions/utils.py:34 (emukit's
-        ``Acquisition.__truediv__`` builds a Quotient there)."""
+        ``Acquisition.__truediv__`` builds a Quotient there).  Over a ``PointwiseCost`` the quotient is per candidate
+        (``PointCostQuotient``)."""
+        from .cost_functions import PointwiseCost
+        if isinstance(cost, PointwiseCost):
+            return PointCostQuotient(self, cost)
         return AcquisitionQuotient(self, cost)
 
     def __mul__(self, other):
@@ -199,3 +203,84 @@ class AcquisitionQuotient:
     @property
     def has_gradients(self):
         return True
+
+
+class PointCostQuotient(AcquisitionQuotient):
+    """``CausalExpectedImprovement(...) / PointwiseCost(...)`` and ``CausalLogExpectedImprovement(...) / PointwiseCost(...)``
+    (DESIGN.md §4y): every candidate over its OWN cost -- ``EI(x) / c(x)``, or ``log EI(x) - log c(x)`` -- where
+    ``AcquisitionQuotient`` divides the whole batch by one scalar.  ``sweep`` gives the grid its cost vector once
+    (``cbo_cands_set_cost``) and scores through ``cbo_acq_sweep_pointcost``; ``evaluate_with_gradients`` is the quotient
+    rule with the cost's own gradient, ``variable_k sign(x_k)``."""
+    pointwise_cost = True
+
+    def __init__(self, numerator, denominator):
+        from .cost_functions import PointwiseCost
+        from .pointwise_acquisitions import CausalLogExpectedImprovement
+        if not isinstance(denominator, PointwiseCost):
+            raise ValueError("PointCostQuotient divides by a PointwiseCost")
+        if type(numerator) is CausalLogExpectedImprovement:
+            self.is_log = True
+        elif type(numerator) is CausalExpectedImprovement:
+            self.is_log = False
+        else:
+            raise ValueError("a PointwiseCost prices the causal EI or its logarithm alone, not "
+                             f"{type(numerator).__name__}")
+        super().__init__(numerator, denominator)
+
+    def _scalars(self):
+        num = self.numerator
+        y_best = float(np.asarray(num.current_global_min, dtype=np.float64).reshape(-1)[0])
+        return y_best, num.task, float(num.jitter)
+
+    def set_grid_cost(self, grid):
+        """The grid's cost vector under this quotient's table: formed on the device once per ``CandidateGrid``."""
+        cost = self.denominator
+        key = (cost.fix.tobytes(), cost.variable.tobytes())
+        if getattr(grid, "_cost_key", None) != key:
+            if grid.points.shape[1] != cost.fix.shape[0]:
+                raise ValueError(f"the cost table has {cost.fix.shape[0]} variables, the candidates {grid.points.shape[1]} columns")
+            _lib.check(_lib.load().cbo_cands_set_cost(grid._handle, _lib.dptr(cost.fix),
+                                                      cost.variable.ctypes.data_as(_lib.c_int_p)))
+            grid._cost_key = key
+
+    def sweep(self, candidates, want_acq=False, want_posterior=False):
+        """dict(best_val, best_idx, acq, mean, var) of ``cbo_acq_sweep_pointcost``: ``best_val`` is the winner's value over
+        its own cost -- there is nothing to re-price."""
+        y_best, task, jitter = self._scalars()
+        model = self.numerator.model
+        own = not isinstance(candidates, CandidateGrid)
+        grid = CandidateGrid(candidates, model) if own else candidates
+        m = len(grid)
+        acq = np.empty(m) if want_acq else None
+        mean = np.empty(m) if want_posterior else None
+        var = np.empty(m) if want_posterior else None
+        best_val = ctypes.c_double(0.0)
+        best_idx = ctypes.c_int64(-1)
+        try:
+            self.set_grid_cost(grid)
+            model.ensure_fitted()
+            _lib.check(_lib.load().cbo_acq_sweep_pointcost(
+                model._handle, grid._handle, int(self.is_log), y_best, _lib.TASK_CODE[task], jitter, _lib.dptr(acq),
+                _lib.dptr(mean), _lib.dptr(var), ctypes.byref(best_val), ctypes.byref(best_idx)))
+        finally:
+            if own:
+                grid.close()
+        col = lambda a: None if a is None else a[:, None]      # noqa: E731
+        return {"best_val": best_val.value, "best_idx": best_idx.value, "acq": col(acq), "mean": col(mean),
+                "var": col(var)}
+
+    def sweep_batch(self, candidates, batch_size, **kwargs):
+        raise ValueError("batch selection is not defined over a PointwiseCost")
+
+    def evaluate(self, x):
+        return self.sweep(x, want_acq=True)["acq"]
+
+    def evaluate_with_gradients(self, x):
+        """The quotient rule with the true cost gradient: ``(d EI - (EI / c) d c) / c``, or ``d log EI - d c / c``."""
+        x = _lib.as_f64(x)
+        f, df = self.numerator.evaluate_with_gradients(x)
+        c, dc = self.denominator.evaluate_with_gradients(x)
+        if self.is_log:
+            return f - np.log(c), df - dc / c
+        value = f / c
+        return value, (df - value * dc) / c

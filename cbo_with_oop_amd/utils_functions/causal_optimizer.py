@@ -76,7 +76,8 @@ class CausalGradientAcquisitionOptimizer:
         return lockstep_lbfgs(lambda X: _values_and_gradients(acquisition, X), np.asarray(x0, dtype=np.float64), lo, hi,
                               max_rounds=max_rounds, history=history)
 
-    def optimize(self, acquisition, context=None, refine=False, num_starts=1, device=False, device_prior=False):
+    def optimize(self, acquisition, context=None, refine=False, num_starts=1, device=False, device_prior=False,
+                 cost_mode="batch"):
         """(x_max (1,d), acquisition value at x_max (1,1)) -- emukit ``AcquisitionOptimizerBase.optimize``.
         ``acquisition`` is ``CausalExpectedImprovement(...) / Cost(...)`` (an ``AcquisitionQuotient``) or a bare
         ``CausalExpectedImprovement``.  ``refine=True`` adds the reference's gradient stage: from the best grid point
@@ -86,7 +87,16 @@ class CausalGradientAcquisitionOptimizer:
         raises ``ValueError`` when the set is not eligible for it: a causal, large or fp32 model, a cost that is not the
         graphs' own, an acquisition the launch does not know.  ``device_prior=True`` (with ``refine=True`` and
         ``device=True``) lets a causal set into the launch through a device-resident do-calculus prior (``DoPrior``, DESIGN.md
-        §4u) when ``prior_spec`` recognises its closures.  The default is today's path."""
+        §4u) when ``prior_spec`` recognises its closures.  The default is today's path.
+        ``cost_mode="pointwise"`` says that ``acquisition`` is a quotient by a ``PointwiseCost``: the grid is
+        scored per candidate over its own cost and the device form of the refinement climbs with the cost's own gradient
+        (``cbo_acq_refine_sets_pointcost``); a mismatch between the keyword and the quotient raises ``ValueError``."""
+        from .cost_functions import checked_cost_mode
+        if (checked_cost_mode(cost_mode) == "pointwise") != bool(getattr(acquisition, "pointwise_cost", False)):
+            raise ValueError("cost_mode='pointwise' goes with acquisition / PointwiseCost(...), cost_mode='batch' with "
+                             "acquisition / Cost(...)")
+        if cost_mode == "pointwise" and device_prior:
+            raise ValueError("cost_mode='pointwise' refines causal sets through the host route: device_prior must be False")
         if device_prior and not refine:
             raise ValueError("device_prior=True selects the device form of a causal set's refinement: refine must be True")
         if device_prior and not device:
@@ -118,7 +128,7 @@ class CausalGradientAcquisitionOptimizer:
             else:
                 starts = x
             (xs, fs, status), = refine_sets([model], [starts], [self.bounds], y_best, task, [cost], kind=kind,
-                                            host_fallback=False, device_prior=device_prior)
+                                            host_fallback=False, device_prior=device_prior, cost_mode=cost_mode)
             if status[0] == _lib.REFINE_DECLINED:
                 raise ValueError("device=True: the device launch declined the set (its model is not positive definite "
                                  "without jitter, or the one-workgroup kernels are switched off with CBO_HIP_SMALL_SETS=0)")
@@ -162,7 +172,7 @@ def _values_and_gradients(acquisition, X):
     for all rows come from one batched device call; a cost that depends on the point (cost_functions.py:11-17 sums
     |x| over the batch it is given) is evaluated row by row, as k single-point calls of the reference would."""
     num = getattr(acquisition, "numerator", None)
-    if num is None:
+    if num is None or getattr(acquisition, "pointwise_cost", False):   # (PointCostQuotient prices every row itself)
         f, df = acquisition.evaluate_with_gradients(X)
         return f[:, 0], df
     f, df = num.evaluate_with_gradients(X)
@@ -331,7 +341,8 @@ def _acquisition_of_kind(kind, model, current_global_best, task, cost):
     return _acquisition_for(kind[0], model, current_global_best, task, None, None if kind[0] == "VAR" else kind[1]) / cost
 
 
-def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, task, param, max_rounds, out):
+def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, task, param, max_rounds, out,
+                      pointwise=False):
     """``refine_sets``' one library call for the sets ``dev`` (``priors``: the ``DoPrior`` of each causal one): fills ``out[i]``
     of every set the launch took."""
     import ctypes
@@ -357,7 +368,13 @@ def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, ta
     rounds, status = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32)
     gps = (ctypes.c_void_p * n)(*[models[i]._handle for i in dev])
     yb = np.full(n, y_best)
-    if kind[0] == _lib.LOGEI:                        # (no kind code: an entry point of its own; refine_sets has refused priors)
+    if pointwise:                                    # (the gradient carries the cost's own derivative)
+        _lib.check(_lib.load().cbo_acq_refine_sets_pointcost(
+            n, gps, sets, int(kind[0] == _lib.LOGEI), _lib.dptr(yb), _lib.TASK_CODE[task], param, max_rounds,
+            _lib.dptr(x_out), _lib.dptr(v_out), _lib.dptr(g_out), rounds.ctypes.data_as(_lib.c_int_p),
+            status.ctypes.data_as(_lib.c_int_p)))
+        outs = None
+    elif kind[0] == _lib.LOGEI:                      # (no kind code: an entry point of its own; refine_sets has refused priors)
         _lib.check(_lib.load().cbo_acq_refine_sets_logei(
             n, gps, sets, _lib.dptr(yb), _lib.TASK_CODE[task], param, max_rounds, _lib.dptr(x_out), _lib.dptr(v_out),
             _lib.dptr(g_out), rounds.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p)))
@@ -382,7 +399,7 @@ def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, ta
 
 
 def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=("EI", None), max_rounds=200,
-                host_fallback=True, device_prior=False):
+                host_fallback=True, device_prior=False, cost_mode="batch"):
     """The reference's second stage (causal_optimizer.py:59-65) for every exploration set at once: from every row of
     ``starts[s]`` ((k_s, d_s), 1 <= k_s <= 64) a projected L-BFGS ascent of ``acquisition / Cost`` inside ``bounds[s]``
     (``lockstep_lbfgs``'s iteration), returning per set ``(points (k_s, d_s), values (k_s,), status (k_s,) int)``.
@@ -402,10 +419,14 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
     (``cbo_acq_refine_sets_prior``); the priors are built for this call and closed after it.  A causal set that misses one of
     these takes today's route.  The default does exactly what it did.
     ``kind=("LOGEI", jitter)``: value ``log EI - log cost``, gradient ``d log EI``, through
-    ``cbo_acq_refine_sets_logei``; a causal set takes the host route, and ``device_prior=True`` raises ``ValueError``."""
+    ``cbo_acq_refine_sets_logei``; a causal set takes the host route, and ``device_prior=True`` raises ``ValueError``.
+    ``cost_mode="pointwise"`` (``("EI", ...)`` and ``("LOGEI", ...)`` alone, no ``device_prior``): the same
+    values with the TRUE gradient of ``EI / c`` or ``log EI - log c`` -- ``d c / d x_k = variable_k sign(x_k)`` -- through
+    ``cbo_acq_refine_sets_pointcost``; the sets the launch does not take go through ``refine_batched`` with
+    ``acquisition / PointwiseCost``, the same gradient on the host.  Every cost must be one ``cost_structure`` recognises."""
     import ctypes
     import math
-    from .utils import checked_log_ei, sets_acquisition
+    from .utils import checked_log_ei, checked_pointwise_cost, sets_acquisition
     if not (isinstance(kind, tuple) and len(kind) == 2):
         raise ValueError(f"refine_sets: kind must be a (name, parameter) pair, not {kind!r}")
     if kind[0] == "MES":
@@ -418,6 +439,11 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
     else:
         kind = sets_acquisition(kind[0], None if kind[0] in ("EI", "VAR") else kind[1])
     checked_log_ei(kind, device_prior)
+    pointwise = checked_pointwise_cost(cost_mode, kind, device_prior=device_prior)
+    if pointwise:
+        from .cost_functions import PointwiseCost
+        costs = [c if isinstance(c, PointwiseCost) else PointwiseCost(getattr(c, "costs_functions", None) or {},
+                                                                      getattr(c, "evaluated_set", ())) for c in costs]
     s = len(models)
     if not (len(starts) == len(bounds) == len(costs) == s) or s == 0:
         raise ValueError("refine_sets: models, starts, bounds and costs must have one entry per exploration set")
@@ -459,7 +485,7 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
                     priors.pop(i).close()
                 dev.remove(i)                  # (unsupported graph GP: today's route)
     try:
-        _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, task, param, max_rounds, out)
+        _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, task, param, max_rounds, out, pointwise)
     finally:
         for p in priors.values():
             p.close()

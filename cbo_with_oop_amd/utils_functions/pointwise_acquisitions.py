@@ -314,6 +314,10 @@ class CausalLogExpectedImprovement(_PointwiseAcquisition):
         return log_h + np.log(standard_deviation), gradient
 
     def __truediv__(self, cost):
+        from .cost_functions import PointwiseCost
+        if isinstance(cost, PointwiseCost):              # (every candidate over its own cost)
+            from .causal_acquisition_functions import PointCostQuotient
+            return PointCostQuotient(self, cost)
         return LogAcquisitionQuotient(self, cost)
 
 

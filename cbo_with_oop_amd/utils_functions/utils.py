@@ -118,7 +118,7 @@ def default_grid_shape(d, budget=None):
 
 def find_next_y_point(space, model, current_global_best, evaluated_set, costs_functions, task='min',
                       grid_shape=None, candidates=None, anchors="grid", num_anchor_points=None, acquisition="EI",
-                      batch_size=None, hyper_samples=None, constraints=None):
+                      batch_size=None, hyper_samples=None, cost_mode="batch", constraints=None):
     """utils.py:29-37.  Returns (y_acquisition (1,1), x_new (1,d)).
 
     ``candidates`` (optional (M,d) array or CandidateGrid) overrides the regular grid over ``space``.
@@ -146,7 +146,33 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     defaults): the grid is scored with the EI marginalised over the samples, over the cost, in one device call
     (integrated_hyper.py, ``cbo_acq_sweep_hyper``); together with ``acquisition="MES"``, ``constraints``, ``batch_size`` or
     ``anchors="uniform"`` it raises ``ValueError``.  ``None``: nothing changes.
+    ``cost_mode="pointwise"``: every candidate is scored over its OWN cost, ``EI(x) / c(x)`` or, with
+    ``acquisition="LOGEI"``, ``log EI(x) - log c(x)`` (``acquisition / PointwiseCost``, ``cbo_acq_sweep_pointcost``); the value
+    returned is the winner's own, with no re-pricing step.  Another acquisition, ``constraints``, ``hyper_samples``,
+    ``batch_size`` and a cost table ``cost_structure`` does not recognise raise ``ValueError`` before any device call.
+    ``"batch"`` (default) is the reference's one scalar per batch: nothing changes.
     """
+    if checked_pointwise_cost(cost_mode, (acquisition, None), constraints, hyper_samples, batch_size):
+        from .cost_functions import PointwiseCost
+        quotient = _acquisition_for(acquisition, model, current_global_best, task, space) / \
+            PointwiseCost(costs_functions, evaluated_set)
+        if anchors == "uniform":
+            from .causal_optimizer import CausalGradientAcquisitionOptimizer
+            optimizer = CausalGradientAcquisitionOptimizer(space, num_anchor_points=num_anchor_points, anchors="uniform")
+            x_new, _ = optimizer.optimize(quotient)
+            return quotient.evaluate(x_new), x_new
+        own = not isinstance(candidates, CandidateGrid)
+        if candidates is None:
+            bounds = space_bounds(space)
+            candidates = meshgrid_candidates(bounds, grid_shape or default_grid_shape(len(bounds)))
+        grid = CandidateGrid(candidates, model) if own else candidates
+        try:
+            res = quotient.sweep(grid)
+            x_new = grid.points[res["best_idx"] - grid.index_offset][None, :].copy()
+        finally:
+            if own:
+                grid.close()
+        return np.array([[res["best_val"]]]), x_new
     if hyper_samples is not None:
         if acquisition != "EI":
             raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI'")
@@ -333,7 +359,7 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
 
 def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
                        acquisition="EI", acquisition_param=None, hyper_samples=None, spaces=None, batch_size=None,
-                       update_incumbent=False, refine=False, device_prior=False, constraints=None):
+                       update_incumbent=False, refine=False, device_prior=False, cost_mode="batch", constraints=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -386,10 +412,20 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     logarithm of the cost for every set in the same one call (``cbo_acq_sweep_sets_logei``) -- per set what
     ``find_next_y_point(acquisition="LOGEI")`` returns -- and, with ``refine=True``, refined by ``cbo_acq_refine_sets_logei``
     (causal sets through the host route).  Together with non-empty ``constraints``, ``hyper_samples``, ``batch_size``,
-    ``device_prior=True`` or ``raw=True`` it raises ``ValueError`` before any device call."""
+    ``device_prior=True`` or ``raw=True`` it raises ``ValueError`` before any device call.
+    ``cost_mode="pointwise"`` with ``"EI"`` or ``"LOGEI"``: every candidate over its own cost for every set in
+    one call (``cbo_acq_sweep_sets_pointcost``) -- per set what ``find_next_y_point(cost_mode="pointwise")`` returns, the
+    winner's value being its own ``EI / c(x)`` with no re-pricing -- and, with ``refine=True``, refined with the cost's own
+    gradient (``refine_sets(cost_mode="pointwise")``).  Another acquisition, non-empty ``constraints``, ``hyper_samples``,
+    ``batch_size``, ``device_prior=True``, ``raw=True`` and a cost ``cost_structure`` does not recognise raise ``ValueError``
+    before any device call.  ``"batch"`` (default) takes exactly today's calls."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    if checked_pointwise_cost(cost_mode, kind, constraints, hyper_samples, batch_size, device_prior, raw):
+        checked_refine(refine, kind, None, None, None, False, spaces, len(models))
+        return _next_y_points_pointwise(models, current_global_best, evaluated_sets, costs_functions, task, grids, kind,
+                                        refine, spaces)
     checked_device_prior(device_prior, refine)
     checked_log_ei(kind, device_prior, raw)
     checked_refine(refine, kind, constraints, hyper_samples, batch_size, raw, spaces, len(models))
@@ -497,6 +533,67 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     xs, ys = winners_to_points(st, models, grids, current_global_best, task)
     if refine:
         xs, ys = refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind, device_prior)
+    return xs, ys
+
+
+def checked_pointwise_cost(cost_mode, kind=("EI", None), constraints=None, hyper_samples=None, batch_size=None,
+                           device_prior=False, raw=False):
+    """``cost_mode`` of a sweep, a path or an agent, checked on the host before any device call: True for ``"pointwise"``
+    (DESIGN.md §4y), which prices the causal EI or its logarithm alone -- no constraints, hyper-parameter samples, batches,
+    device-resident priors or several ranks; False for ``"batch"``, today's behaviour."""
+    from .cost_functions import checked_cost_mode
+    if checked_cost_mode(cost_mode) == "batch":
+        return False
+    if kind[0] not in ("EI", LOG_EI):
+        raise ValueError(f"cost_mode='pointwise' prices the causal EI or its logarithm: acquisition must be 'EI' or 'LOGEI', "
+                         f"not {kind[0]!r}")
+    if constraints is not None and any(constraints):
+        raise ValueError("cost_mode='pointwise' is not defined for constrained acquisitions: constraints must be None or empty")
+    if hyper_samples is not None:
+        raise ValueError("cost_mode='pointwise' is not defined for the marginalised EI: hyper_samples must be None")
+    if batch_size is not None:
+        raise ValueError("cost_mode='pointwise' is not defined for batches: batch_size must be None")
+    if device_prior:
+        raise ValueError("cost_mode='pointwise' refines causal sets through the host route: device_prior must be False")
+    if raw:
+        raise ValueError("cost_mode='pointwise' is not defined across several ranks (raw=True)")
+    return True
+
+
+def _next_y_points_pointwise(models, current_global_best, evaluated_sets, costs_functions, task, grids, kind, refine, spaces):
+    """``find_next_y_points(cost_mode="pointwise")``: one ``cbo_acq_sweep_sets_pointcost`` call over grids that carry their
+    cost vectors, then -- ``refine=True`` -- ``refine_sets(cost_mode="pointwise")`` from the winners."""
+    import ctypes
+    from .. import _lib
+    from .cost_functions import PointwiseCost
+    s = len(models)
+    if task not in _lib.TASK_CODE:
+        raise ValueError(f"task must be 'min' or 'max', not {task!r}")
+    costs = [PointwiseCost(costs_functions, evaluated_sets[i]) for i in range(s)]
+    jitter = 0.0 if kind[1] is None else float(kind[1])
+    y_best = float(np.asarray(current_global_best, dtype=np.float64).reshape(-1)[0])
+    if any(not (o._handle.value or 0) for o in list(models) + list(grids)):
+        raise ValueError("find_next_y_points: a model or candidate grid has been closed")
+    for i in range(s):
+        (_acquisition_for(kind[0], models[i], current_global_best, task, None, kind[1]) / costs[i]).set_grid_cost(grids[i])
+    vals, idxs = np.empty(s), np.empty(s, dtype=np.int64)
+    _lib.check(_lib.load().cbo_acq_sweep_sets_pointcost(
+        s, (ctypes.c_void_p * s)(*[m._handle for m in models]), (ctypes.c_void_p * s)(*[g._handle for g in grids]),
+        int(kind[0] == LOG_EI), _lib.dptr(np.full(s, y_best)), _lib.TASK_CODE[task], jitter, _lib.dptr(vals),
+        idxs.ctypes.data_as(_lib.c_int64_p)))
+    for m in models:
+        if not m.small:                          # (the general path fitted it on the way)
+            m.stale = False
+    xs = [grids[i].points[int(idxs[i]) - grids[i].index_offset][None, :].copy() for i in range(s)]
+    ys = [np.array([[float(vals[i])]]) for i in range(s)]
+    if refine:
+        from .causal_optimizer import refine_sets
+        res = refine_sets(models, xs, [space_bounds(sp) for sp in spaces], current_global_best, task, costs, kind=kind,
+                          cost_mode="pointwise")
+        for i, (pts, fs, _) in enumerate(res):
+            best = int(np.argmax(fs))
+            if fs[best] >= ys[i][0, 0]:
+                xs[i], ys[i] = pts[best][None, :].copy(), np.array([[fs[best]]])
     return xs, ys
 
 

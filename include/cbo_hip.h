@@ -387,6 +387,20 @@ int cbo_gp_plugin_incumbent(cbo_gp *gp, int task, double *incumbent_out);
 int cbo_acq_sweep_logei(cbo_gp *gp, cbo_cands *cands, double y_best, int task, double jitter, double cost,
                         double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx);
 
+/* The Expected Improvement, or its logarithm, of every candidate over the candidate's OWN cost: what the CBO
+ * papers write as EI(x) / c(x).  cands must carry a cost vector (cbo_cands_set_cost).
+ *     log_form 0:  acq[j] = EI_j / cost[j]  -- cbo_acq_sweep's value at cost 1, then the IEEE quotient (numpy's `/`)
+ *     log_form 1:  acq[j] = cbo_acq_sweep_logei's value at cost 1 with log(cost[j]) in the place of log cost
+ * mean_out / var_out are cbo_acq_sweep's bits; the tie rule (lowest index, NaN maximal, index_offset applied), the outputs that
+ * may be NULL and the route to q, mu (cached copies, a kept solution, an appended row, else the substitution) are
+ * cbo_acq_sweep's.  A NaN cost gives a NaN acquisition.  The candidate pass reads the costs as a fifth 8-byte stream.
+ * CBO_ERR_INVALID, scalars first: log_form other than 0 / 1, a bad task, a non-finite jitter or y_best; then cbo_acq_sweep's
+ * argument checks; then a set without a cost vector.  Unfitted model: CBO_ERR_NOT_FITTED.
+ * Out of scope: point-wise costs for the other acquisitions, constraints, hyper-marginalisation, batches, a one-call trial
+ * step. */
+int cbo_acq_sweep_pointcost(cbo_gp *gp, cbo_cands *cands, int log_form, double y_best, int task, double jitter,
+                            double *acq_out, double *mean_out, double *var_out, double *best_val, int64_t *best_idx);
+
 /* Hyper-parameter MLE support (GPy model.optimize() reached from src/CBO.py:173 and
  * src/utils_functions/utils.py:44).  cbo_gp_set_hyper replaces kernel variance, lengthscale(s) and noise
  * variance (the model must be refitted with cbo_gp_fit); cbo_gp_log_marginal returns GPy's
@@ -492,6 +506,17 @@ void cbo_cands_destroy(cbo_cands *c);
  * extended with cbo_gp_append, the next sweep adds ONE row to V (O(n m)) instead of redoing the substitution
  * (O(n^2 m)).  Off by default. */
 int cbo_cands_keep_solution(cbo_cands *c, int on);
+/* Per-candidate intervention costs.  cbo_cands_set_cost gives the set a cost vector,
+ *     cost[j] = c(x_j) = sum_k (fix[k] + (variable[k] ? |x_jk| : 0)),   k < d,
+ * formed on the device from the set's raw points in cbo_acq_refine_sets' order (terms added from 0.0 in column order, no
+ * contraction): the reference's variable-cost table, priced per candidate and not over the batch column.  fix and variable
+ * hold d entries each.  The vector stays with the set (m doubles), whose points never change; cbo_cands_get_cost copies it to
+ * out[0..m), cbo_cands_clear_cost drops it.  A NaN coordinate of a variable column gives a NaN cost.
+ * CBO_ERR_INVALID: NULL arguments, a non-finite fixed cost, a flag other than 0 / 1, a fixed-cost sum that is not positive
+ * (so c(x) > 0 everywhere); cbo_cands_get_cost on a set without a cost vector. */
+int cbo_cands_set_cost(cbo_cands *c, const double *fix, const int *variable);
+int cbo_cands_get_cost(const cbo_cands *c, double *out);
+int cbo_cands_clear_cost(cbo_cands *c);
 
 /* ---- acquisition sweep -------------------------------------------------------------------------
  * Replaces the batched `acquisition.evaluate(X)` of the anchor scoring step
@@ -628,6 +653,16 @@ int cbo_trial_step_kind(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands,
  * or NaN, and cbo_acq_sweep_sets' argument checks. */
 int cbo_acq_sweep_sets_logei(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
                              double jitter, const double *costs, double *best_vals, int64_t *best_idxs);
+
+/* cbo_acq_sweep_sets with every candidate priced at its own cost: cbo_acq_sweep_sets_logei's argument list
+ * with log_form in front of y_best and without costs -- every cands[i] carries its cost vector.  Routing is
+ * cbo_acq_sweep_sets' (one launch of small_sets_kernel for fp64 models of at most 128 observations; larger and fp32 models:
+ * cbo_gp_fit if unfitted, then cbo_acq_sweep_pointcost, inside the same call); per set, bit for bit, what
+ * cbo_acq_sweep_pointcost returns on a fitted twin; models the launch takes are left untouched.
+ * CBO_ERR_INVALID, before any model is touched: cbo_acq_sweep_pointcost's scalar checks, cbo_acq_sweep_sets' argument checks,
+ * a set without a cost vector. */
+int cbo_acq_sweep_sets_pointcost(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, int log_form, const double *y_best,
+                                 int task, double jitter, double *best_vals, int64_t *best_idxs);
 
 /* cbo_acq_sweep_sets for the constrained acquisition of cbo_acq_sweep_constrained: set i is an objective pair
  * (gps[i], cands[i]) and n_con[i] constraint pairs, whose five con_* entries lie set-major in arrays of sum(n_con) entries
@@ -778,6 +813,16 @@ int cbo_acq_refine_sets(int n_sets, cbo_gp *const *gps, const cbo_refine_set *se
 int cbo_acq_refine_sets_logei(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, const double *y_best, int task,
                               double jitter, int max_rounds, double *x_out, double *val_out, double *grad_out,
                               int *rounds_out, int *status_out);
+
+/* cbo_acq_refine_sets / _logei with the TRUE gradient of the quotient: the values are theirs -- at a point,
+ * bit for bit, what cbo_acq_sweep_sets_pointcost returns for a one-point grid there -- and the gradient carries the cost's
+ * own derivative, d c / d x_k = variable[k] sign(x_k) with sign(0) = 0:
+ *     log_form 0:  (d EI_k - (EI / c) d c_k) / c          log_form 1:  d logEI_k - d c_k / c
+ * so the search climbs the function the point-cost sweeps score.  cbo_refine_set is used as it is.  Causal sets, larger and
+ * fp32 models are DECLINED.  CBO_ERR_INVALID: cbo_acq_sweep_pointcost's scalar checks, then cbo_acq_refine_sets' checks. */
+int cbo_acq_refine_sets_pointcost(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int log_form,
+                                  const double *y_best, int task, double jitter, int max_rounds, double *x_out,
+                                  double *val_out, double *grad_out, int *rounds_out, int *status_out);
 
 /* The do-calculus prior of an RBF graph GP as a device-resident handle (src/DoCalculus.py:34-89).  With the
  * graph GP's inputs X_g, the observed rows O (n_obs x d_in) and the intervened columns I,
