@@ -29,6 +29,7 @@ static_assert(sizeof(SmallShared) + 4 * kSmallLmlTerms * sizeof(double) + sizeof
               "the workgroup's static LDS (the reduction's partial sums, the search's state, the published theta, the priors "
               "and their gradient) beside SmallShared: one CU");
 static_assert(kMleMaxParams == CBO_MAX_DIM + 2, "variance, one lengthscale per dimension, noise variance");
+static_assert(kMleRingDoubles == 2 * kRefineHistory * kMleMaxParams, "a run's ring slot holds the search's S and Y");
 
 // PRIOR: some run of the launch has a prior (hyper_prior.h).  The instantiation without is the kernel as it
 // was before priors existed: a launch without priors runs that code and gives those bits.
