@@ -117,7 +117,8 @@ class CBOAcquisitionPath:
     causal sets into that device call through a device-resident do-calculus prior.
     ``mle_optimizer="device"`` (with ``mle_restarts`` starts per model, 1..16) runs the hyper-parameter MLEs this path
     starts -- the one in front of the device HMC -- as one-launch searches; ``"host"`` (default) is scipy's
-    L-BFGS-B, unchanged.
+    L-BFGS-B, unchanged.  ``mle_device_rows`` (128, or 256 with ``"device"``) is the largest model the agent's
+    one-launch searches take (``CBO``); the MLE in front of the device HMC keeps 128.
     ``hyper_priors`` (a dict ``"variance"`` / ``"lengthscale"`` / ``"noise_var"`` -> a prior of ``utils_functions.priors``):
     every exploration-set model carries these priors whenever it is built or rebuilt (``HipGaussianProcess.set_prior``,
     DESIGN.md §4w), so the MLEs and the HMC of this path work on the log posterior; ``None`` (default) sets none."""
@@ -126,12 +127,13 @@ class CBOAcquisitionPath:
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
                  update_incumbent=False, refine=False, hyper_sampler="host", device_prior=False, mle_optimizer="host",
-                 mle_restarts=1, hyper_priors=None, cost_mode="batch"):
-        from .GaussianProcessFactory import checked_mle_optimizer
+                 mle_restarts=1, hyper_priors=None, cost_mode="batch", mle_device_rows=128):
+        from .GaussianProcessFactory import checked_mle_device_rows, checked_mle_optimizer
         from .utils_functions.priors import checked_priors
         from .utils_functions.utils import (checked_device_prior, checked_log_ei, checked_pointwise_cost, checked_refine,
                                             sets_acquisition_or_default as sets_acquisition)
         self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
+        self.mle_device_rows = checked_mle_device_rows(mle_device_rows, mle_optimizer)
         self.device_prior = checked_device_prior(device_prior, refine)
         # priors on every exploration-set model's hyper-parameters (name -> prior), or None: today's behaviour
         self.hyper_priors = checked_priors(hyper_priors) or None
@@ -529,7 +531,10 @@ class CBO(CBOAcquisitionPath):
     ``mle_optimizer="device"`` (with ``mle_restarts`` starts per model, 1..16): every hyper-parameter MLE of the agent -- the
     graph GPs of ``run()``'s first fit and of ``observe()``, and the closing ``optimize()`` of ``intervene()``, the chosen
     set's constraint models included, in one call -- is a one-launch device search (DESIGN.md §4v) instead of scipy's
-    L-BFGS-B with a device call per evaluation; ``"host"`` (default) changes nothing.
+    L-BFGS-B with a device call per evaluation; ``"host"`` (default) changes nothing.  ``mle_device_rows=256`` (with
+    ``"device"``) keeps graph GPs of 129..256 observational rows inside that launch -- from the second observe
+    step of a default run they have that many -- instead of sending them to the lockstep host route; 128 (default) changes
+    nothing.
     ``hyper_priors`` (a dict ``"variance"`` / ``"lengthscale"`` / ``"noise_var"`` -> a prior of ``utils_functions.priors``):
     priors on the hyper-parameters of every exploration-set model, applied whenever one is built or rebuilt (DESIGN.md §4w);
     the graph-level GPs take none.  ``None`` (default): no priors, today's behaviour to the bit."""
@@ -542,10 +547,10 @@ class CBO(CBOAcquisitionPath):
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
                  constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False,
                  hyper_sampler="host", device_prior=False, mle_optimizer="host", mle_restarts=1, hyper_priors=None,
-                 cost_mode="batch"):
+                 cost_mode="batch", mle_device_rows=128):
         from .DoCalculus import DoCalculus
-        from .GaussianProcessFactory import GaussianProcessType, checked_mle_optimizer
-        checked_mle_optimizer(mle_optimizer, mle_restarts)
+        from .GaussianProcessFactory import GaussianProcessType, checked_mle_device_rows, checked_mle_optimizer
+        checked_mle_device_rows(mle_device_rows, checked_mle_optimizer(mle_optimizer, mle_restarts))
         from .utils_functions.priors import checked_priors
         checked_priors(hyper_priors)                           # (on the host, before any device call)
         from .graphs import _columns
@@ -616,7 +621,7 @@ class CBO(CBOAcquisitionPath):
                          constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
                          update_incumbent=update_incumbent, refine=refine, hyper_sampler=hyper_sampler,
                          device_prior=device_prior, mle_optimizer=mle_optimizer, mle_restarts=mle_restarts,
-                         hyper_priors=hyper_priors, cost_mode=cost_mode)
+                         hyper_priors=hyper_priors, cost_mode=cost_mode, mle_device_rows=mle_device_rows)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions
@@ -672,7 +677,7 @@ class CBO(CBOAcquisitionPath):
         closing = [self.models[intervention]] + list(self.constraint_models[intervention] if self.constraints else ())
         if self.mle_optimizer == "device":
             from .GaussianProcessFactory import optimize_together
-            optimize_together(closing, optimizer="device", num_restarts=self.mle_restarts)
+            optimize_together(closing, optimizer="device", num_restarts=self.mle_restarts, device_rows=self.mle_device_rows)
             return
         for model in closing:
             model.optimize()
@@ -681,7 +686,8 @@ class CBO(CBOAcquisitionPath):
         """What ``fit_all_gaussian_processes`` is told beside the reference's arguments: nothing on the default route."""
         if self.mle_optimizer == "host":
             return {}
-        return {"optimizer": self.mle_optimizer, "num_restarts": self.mle_restarts}
+        rows = {} if self.mle_device_rows == 128 else {"device_rows": self.mle_device_rows}
+        return {"optimizer": self.mle_optimizer, "num_restarts": self.mle_restarts, **rows}
 
     @property
     def epsilon(self):

@@ -582,7 +582,7 @@ class HipGaussianProcess:
         prior = log_prior_batch([self])[0] if _has_priors(self) else None
         return _objective_value(self, theta, self._last_lml, dv, dls, dn, transform, prior)
 
-    def optimize(self, max_iters=1000, transform="logexp", optimizer="host", **kwargs):
+    def optimize(self, max_iters=1000, transform="logexp", optimizer="host", device_rows=128, **kwargs):
         """Hyper-parameter MLE (emukit ``GPyModelWrapper.optimize`` -> GPy ``optimize_restarts(1, robust=True)`` -- one run from
         the current parameters, nothing drawn --, src/CBO.py:173; ``gp.optimize()`` in src/utils_functions/utils.py:44):
         maximise the log marginal likelihood over kernel variance, lengthscale(s) and -- unless fixed, as for graph-level
@@ -594,25 +594,28 @@ class HipGaussianProcess:
         by construction, not by comparison (parity unpinned).
         ``optimizer="device"``: the whole search inside one device launch (``optimize_together([self], ...,
         optimizer="device")``, DESIGN.md §4v: ``lockstep_lbfgs``' iteration, not scipy's); ``"host"`` is the run described
-        above, unchanged."""
+        above, unchanged.  ``device_rows=256`` lets the launch take a model of 129..256 observations."""
         from scipy.optimize import fmin_l_bfgs_b
-        if checked_mle_optimizer(optimizer) == "device":
-            return optimize_together([self], max_iters, transform, optimizer="device")[0]
+        checked_mle_device_rows(device_rows, checked_mle_optimizer(optimizer))
+        if optimizer == "device":
+            return optimize_together([self], max_iters, transform, optimizer="device", device_rows=device_rows)[0]
         theta0, x0 = _optimizer_start(self, transform)
         x_opt, f_opt, info = fmin_l_bfgs_b(lambda x: self._objective(x, transform), x0, maxfun=int(max_iters),
                                            maxiter=int(max_iters))
         f_opt = self._objective(x_opt, transform)[0]          # opt_lbfgsb: f_opt = f_fp(x_opt)[0]; the model sits at x_opt
         return _optimizer_finish(self, theta0, x_opt, f_opt, info, transform)
 
-    def optimize_restarts(self, num_restarts=10, max_iters=1000, optimizer="device", **kwargs):
+    def optimize_restarts(self, num_restarts=10, max_iters=1000, optimizer="device", device_rows=128, **kwargs):
         """GPy ``model.optimize_restarts(num_restarts)``: the MLE from the current parameters and from ``num_restarts - 1``
         randomised starts (``mle_restart_starts``: paramz ``randomize()``, a standard normal in the Logexp space, numpy's
         global generator), the model left at the best end point.  Every start is one workgroup of ONE device launch
         (DESIGN.md §4v); ``optimizer="host"`` would be ``num_restarts`` optimiser runs one after another and is not offered
         (ValueError for more than one start).  Returns the ``optimization_result``; its ``runs`` hold every start's record.
         A model with priors (``set_prior``): a parameter that has one is drawn from it, as paramz does, and the best end point
-        is the one with the highest log posterior (every run's ``lml`` then includes the log prior)."""
-        return optimize_together([self], max_iters, "logexp", optimizer=optimizer, num_restarts=num_restarts)[0]
+        is the one with the highest log posterior (every run's ``lml`` then includes the log prior).
+        ``device_rows=256``: a model of 129..256 observations has its restarts inside the launch too."""
+        return optimize_together([self], max_iters, "logexp", optimizer=optimizer, num_restarts=num_restarts,
+                                 device_rows=device_rows)[0]
 
     def generate_hyperparameters_samples(self, n_samples=20, n_burnin=100, subsample_interval=10, step_size=1e-1,
                                          leapfrog_steps=20, sampler="host"):
@@ -821,6 +824,17 @@ def checked_mle_optimizer(optimizer, num_restarts=1):
     return optimizer
 
 
+def checked_mle_device_rows(device_rows, optimizer="device"):
+    """``device_rows``: the largest model the one-launch search takes -- 128 (``cbo_gp_mle_sets``) or 256 (the
+    two-block form beside it, ``cbo_gp_mle_sets_rows``; ``optimizer="device"`` alone) -- checked on the host,
+    before any device call.  Returns ``device_rows``."""
+    if isinstance(device_rows, bool) or not isinstance(device_rows, (int, np.integer)) or device_rows not in (128, 256):
+        raise ValueError(f"device_rows must be 128 or 256, not {device_rows!r}")
+    if device_rows == 256 and optimizer != "device":
+        raise ValueError("device_rows=256 chooses the models the device launch takes: it needs optimizer='device'")
+    return int(device_rows)
+
+
 def mle_restart_starts(P, num_restarts, priors=None, fit_noise=True):
     """The randomised starts of ``optimize_restarts``: ``num_restarts - 1`` rows ``x = np.random.randn(P)`` in the Logexp
     space (paramz ``randomize()``: a standard normal for every transformed parameter), one ``randn(P)`` call per row from
@@ -860,11 +874,13 @@ def mle_best_run(lmls, statuses):
     return best
 
 
-def mle_runs_device(models, theta0s, max_rounds):
-    """One ``cbo_gp_mle_sets`` call: model k's searches from the rows of ``theta0s[k]`` ((n_starts, P) parameters).  Returns
-    per model dict(declined, status (n_starts,), rounds, theta (n_starts, P), lml, grad): every run's reason for stopping
+def mle_runs_device(models, theta0s, max_rounds, device_rows=128):
+    """One ``cbo_gp_mle_sets`` call -- with ``device_rows=256`` one ``cbo_gp_mle_sets_rows`` call, which also takes the fp64
+    models of 129..256 observations --: model k's searches from the rows of ``theta0s[k]`` ((n_starts, P)
+    parameters).  Returns per model dict(declined, status (n_starts,), rounds, theta (n_starts, P), lml, grad): every run's reason for stopping
     (``_lib.REFINE_*`` or ``_lib.MLE_NOT_PD``), rounds and end point with the likelihood and its gradients there --
     meaningless for a ``NOT_PD`` run and for a declined model.  The models are only read."""
+    device_rows = checked_mle_device_rows(device_rows)
     k = len(models)
     lib = _lib.load()
     handles = (ctypes.c_void_p * k)(*[m._handle for m in models])
@@ -885,13 +901,16 @@ def mle_runs_device(models, theta0s, max_rounds):
         r.status_out, r.rounds_out = o["status"].ctypes.data_as(_lib.c_int_p), o["rounds"].ctypes.data_as(_lib.c_int_p)
         out.append(o)
         keep.append(theta0)
-    _lib.check(lib.cbo_gp_mle_sets(k, handles, runs, model_status.ctypes.data_as(_lib.c_int_p)))
+    if device_rows == 128:
+        _lib.check(lib.cbo_gp_mle_sets(k, handles, runs, model_status.ctypes.data_as(_lib.c_int_p)))
+    else:
+        _lib.check(lib.cbo_gp_mle_sets_rows(k, handles, runs, device_rows, model_status.ctypes.data_as(_lib.c_int_p)))
     for o, st in zip(out, model_status):
         o["declined"] = int(st) == _lib.MLE_DECLINED
     return out
 
 
-def _optimize_on_device(models, max_iters, num_restarts, host_fallback):
+def _optimize_on_device(models, max_iters, num_restarts, host_fallback, device_rows=128):
     """``optimize_together``'s device route: the results, None where the model has to take the host route."""
     from scipy.optimize import OptimizeResult
     max_rounds = min(int(max_iters), _lib.MLE_MAX_ROUNDS)
@@ -900,7 +919,7 @@ def _optimize_on_device(models, max_iters, num_restarts, host_fallback):
         theta0, _ = _optimizer_start(m, "logexp")
         extra = mle_restart_starts(theta0.size, num_restarts, getattr(m, "_priors", None) or None, not m.fix_noise)
         theta0s.append(np.vstack([theta0[None], logexp_f(extra)]) if extra.size else theta0[None])
-    answers = mle_runs_device(models, theta0s, max_rounds)
+    answers = mle_runs_device(models, theta0s, max_rounds, device_rows)
     results = [None] * len(models)
     for j, (m, a) in enumerate(zip(models, answers)):
         back = a["declined"] or int(a["status"][0]) == _lib.MLE_NOT_PD
@@ -928,7 +947,8 @@ def _optimize_on_device(models, max_iters, num_restarts, host_fallback):
     return results
 
 
-def optimize_together(models, max_iters=1000, transform="logexp", optimizer="host", num_restarts=1, host_fallback=True):
+def optimize_together(models, max_iters=1000, transform="logexp", optimizer="host", num_restarts=1, host_fallback=True,
+                      device_rows=128):
     """``[m.optimize(max_iters, transform) for m in models]`` with the models' L-BFGS-B runs in lockstep: every round
     evaluates the likelihood and gradients of all models that asked for a value in ONE device call
     (``lml_gradients_batch``).  A model of at most 128 observations follows the trajectory ``optimize`` gives it alone,
@@ -947,6 +967,9 @@ def optimize_together(models, max_iters=1000, transform="logexp", optimizer="hos
     ``CBO_HIP_SMALL_SETS=0``) or whose own start has a Ky that is not positive definite as assembled goes through the
     lockstep route described above inside the same call (``host_fallback=False``: RuntimeError instead).
     ``transform="log"`` with ``"device"``, and ``num_restarts`` > 1 with ``"host"``, raise ValueError.
+    ``device_rows=256`` (with ``"device"``): the call is ``cbo_gp_mle_sets_rows`` and also takes the fp64 models
+    of 129..256 observations -- the same search around the two-block likelihood, restarts included -- so only larger models
+    are declined; 128, the default, is the call described above.  Any other value, and 256 with ``"host"``, raise ValueError.
     Models with priors (``set_prior``): both routes minimise ``-log_likelihood - log_prior`` -- the device
     launch adds the prior inside the kernel, the host route through one ``log_prior_batch`` call per round for all models --
     ``fun`` is that objective, the restarts draw such parameters from their priors, and ``transform="log"`` raises
@@ -954,12 +977,13 @@ def optimize_together(models, max_iters=1000, transform="logexp", optimizer="hos
     from .utils_functions.lockstep_lbfgsb import lockstep_fmin_l_bfgs_b
     models = list(models)
     checked_mle_optimizer(optimizer, num_restarts)
+    checked_mle_device_rows(device_rows, optimizer)
     if optimizer == "device":
         if transform != "logexp":
             raise ValueError("optimizer='device' searches the Logexp-transformed parameters: transform must be 'logexp'")
         if not models:
             return []
-        results = _optimize_on_device(models, max_iters, int(num_restarts), host_fallback)
+        results = _optimize_on_device(models, max_iters, int(num_restarts), host_fallback, int(device_rows))
         rest = [j for j, r in enumerate(results) if r is None]
         for j, r in zip(rest, optimize_together([models[j] for j in rest], max_iters, transform) if rest else []):
             results[j] = r

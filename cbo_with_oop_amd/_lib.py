@@ -237,6 +237,7 @@ SIGNATURES = {
     "cbo_do_prior_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_hmc_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboHmcChain), c_int_p]),
     "cbo_gp_mle_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboMleRun), c_int_p]),
+    "cbo_gp_mle_sets_rows": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboMleRun), ctypes.c_int, c_int_p]),
     "cbo_gp_set_priors": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(CboHyperPrior)]),
     "cbo_gp_get_priors": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(CboHyperPrior)]),
     "cbo_gp_log_prior_batch": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(c_double_p), c_double_p, c_double_p,

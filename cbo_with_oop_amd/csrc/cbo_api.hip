@@ -4408,14 +4408,19 @@ extern "C" int cbo_gp_hmc_sets(int n_models, cbo_gp *const *gps, const cbo_hmc_c
     return CBO_OK;
 }
 
-// ---- every model's hyper-parameter MLE (kernels_mle.hip) -----------------------------------------------------
+// ---- every model's hyper-parameter MLE (kernels_mle.hip; kernels_mle_mid.hip, §4z) ---------------------------
 // cbo_gp_hmc_sets' skeleton with one workgroup, scratch slot and info word per RUN (a (model, start) pair) instead of per
-// model: the models small_lml_gradients would take go into one launch, the others are declined here, their status alone
-// written.  The models are only read; the call returns every run and chooses none.
-extern "C" int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_run *runs, int *model_status_out)
+// model: the models small_lml_gradients would take go into one mle_sets_kernel launch; with max_rows = 256 those the batched
+// likelihood takes in its two-block form go into one mle_mid_kernel launch on the same stream, behind one synchronisation for
+// both; the others are declined here, their status alone written.  The small runs come first in every per-run buffer, the
+// mid runs behind them.  The models are only read; the call returns every run and chooses none.
+constexpr int kMaxMidRuns = 256;       // one workgroup per CU and about 256 MB of slabs
+extern "C" int cbo_gp_mle_sets_rows(int n_models, cbo_gp *const *gps, const cbo_mle_run *runs, int max_rows,
+                                    int *model_status_out)
 {
     if (n_models <= 0) return fail(CBO_ERR_INVALID, "n_models must be positive");
     if (!gps || !runs || !model_status_out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (max_rows != kPadN && max_rows != 2 * kPadN) return fail(CBO_ERR_INVALID, "max_rows must be 128 or 256");
     int rc = check_model_handles(n_models, gps);
     if (rc != CBO_OK) return rc;
     for (int i = 0; i < n_models; ++i) {
@@ -4439,24 +4444,34 @@ extern "C" int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_r
     }
     cbo_ctx *c = gps[0]->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    std::vector<int> small;
-    partition_small(n_models, [&](int i) { return small_lml_eligible(gps[i]); }, [](int) { return (int64_t)1; }, small);
-    const int ns = (int)small.size();
-    int64_t total = 0;
-    for (int i = 0, j = 0; i < n_models; ++i) {
-        if (j < ns && small[(size_t)j] == i) { ++j; total += runs[i].n_starts; model_status_out[i] = CBO_OK; }
-        else model_status_out[i] = CBO_MLE_DECLINED;
-    }
-    if (small.empty()) return CBO_OK;
-    if (total > kMaxGridBlocks) return fail(CBO_ERR_INVALID, "more than 65535 runs in one call");
-    const int nr = (int)total;
-    // a scratch slot (factor + L^-1), an info word and a ring slot per run
-    const size_t stride = small_lml_scratch_doubles(), per_block = small_sets_scratch_doubles(1, 1);
+    // the launch's models in launch order: the small ones, then the mid ones
+    std::vector<int> taken, mid;
+    partition_small(n_models, [&](int i) { return small_lml_eligible(gps[i]); }, [](int) { return (int64_t)1; }, taken);
+    const int ns = (int)taken.size();
+    if (max_rows == 2 * kPadN)
+        partition_small(n_models, [&](int i) { return mid_lml_eligible(gps[i]); }, [](int) { return (int64_t)1; }, mid);
+    const int nm = (int)mid.size();
+    int64_t total_small = 0, total_mid = 0;
+    for (int j = 0; j < ns; ++j) total_small += runs[taken[(size_t)j]].n_starts;
+    for (int j = 0; j < nm; ++j) total_mid += runs[mid[(size_t)j]].n_starts;
+    if (total_small > kMaxGridBlocks) return fail(CBO_ERR_INVALID, "more than 65535 runs in one call");
+    if (total_mid > kMaxMidRuns)
+        return fail(CBO_ERR_INVALID, "more than 256 runs of models of 129..256 observations in one call (one workgroup per "
+                                     "compute unit, about 1 MB of scratch each): split the call");
+    for (int i = 0; i < n_models; ++i) model_status_out[i] = CBO_MLE_DECLINED;
+    taken.insert(taken.end(), mid.begin(), mid.end());
+    for (int i : taken) model_status_out[i] = CBO_OK;
+    if (taken.empty()) return CBO_OK;
+    const int nr_small = (int)total_small, nr_mid = (int)total_mid, nr = nr_small + nr_mid;
+    // per run: a scratch slot (factor + L^-1; a mid run's two-block slab with its point region), an info word, a ring slot
+    const size_t stride = small_lml_scratch_doubles(), mid_stride = mid_mle_scratch_doubles();
+    const size_t per_block = small_sets_scratch_doubles(1, 1);
+    const size_t need = (size_t)nr_small * stride + (size_t)nr_mid * mid_stride;
     const size_t cap = nr < 32 ? (size_t)32 : (size_t)nr;
     constexpr int kFinal = 2 * CBO_HMC_MAX_PARAMS + 1;
     rc = ensure_small_buffers(c, nr, (int)((stride + per_block - 1) / per_block));
-    if (rc == CBO_OK && (size_t)nr * stride > c->small_scratch.cap)
-        rc = fail(CBO_ERR_INVALID, "MLE runs: scratch smaller than expected");
+    if (rc == CBO_OK && nr_mid > 0) rc = grow(c, c->small_scratch, need);
+    if (rc == CBO_OK && need > c->small_scratch.cap) rc = fail(CBO_ERR_INVALID, "MLE runs: scratch smaller than expected");
     if (rc == CBO_OK) rc = grow(c, c->mle_host, cap);
     if (rc == CBO_OK) rc = grow(c, c->mle_final, cap * (size_t)kFinal);
     if (rc == CBO_OK) rc = grow(c, c->mle_status, cap);
@@ -4464,8 +4479,8 @@ extern "C" int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_r
     if (rc == CBO_OK) rc = grow(c, c->mle_rings, cap * (size_t)kMleRingDoubles);
     if (rc != CBO_OK) return rc;
     constexpr int kNoStatus = -2;                               // (a launch that never ran answers nothing)
-    for (int j = 0, q = 0; j < ns; ++j) {
-        const int i = small[(size_t)j];
+    for (int j = 0, q = 0; j < ns + nm; ++j) {
+        const int i = taken[(size_t)j];
         const cbo_mle_run &r = runs[i];
         c->sets_host[j] = cbo_small_set{};
         fill_small_model(c->sets_host[j], gps[i]);
@@ -4473,19 +4488,26 @@ extern "C" int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_r
             cbo_small_mle &rn = c->mle_host[q];
             std::memset(&rn, 0, sizeof(rn));
             std::memcpy(rn.theta0, r.theta0 + (size_t)s * (size_t)r.n_params, sizeof(double) * (size_t)r.n_params);
-            rn.model = j; rn.n_params = r.n_params; rn.n_ls = gps[i]->h.ard ? gps[i]->d : 1; rn.fit_noise = r.fit_noise;
+            rn.model = j < ns ? j : j - ns;                     // (its descriptor's index within its own launch)
+            rn.n_params = r.n_params; rn.n_ls = gps[i]->h.ard ? gps[i]->d : 1; rn.fit_noise = r.fit_noise;
             rn.max_rounds = r.max_rounds;
             rn.n_prior = copy_run_priors(gps[i], r.n_params, rn.priors);
             c->mle_status[q] = kNoStatus;
         }
     }
-    launch_mle_sets(c->stream, c->sets_host, ns, c->mle_host, nr, c->small_scratch, (int64_t)stride, c->small_info, c->mle_rings,
-                    c->mle_final, c->mle_status, c->mle_rounds);
+    if (nr_small > 0)
+        launch_mle_sets(c->stream, c->sets_host, ns, c->mle_host, nr_small, c->small_scratch, (int64_t)stride, c->small_info,
+                        c->mle_rings, c->mle_final, c->mle_status, c->mle_rounds);
+    if (nr_mid > 0)
+        launch_mle_mid(c->stream, c->sets_host.p + ns, nm, c->mle_host.p + nr_small, nr_mid,
+                       c->small_scratch.p + (size_t)nr_small * stride, (int64_t)mid_stride, c->small_info.p + nr_small,
+                       c->mle_rings.p + (size_t)nr_small * kMleRingDoubles, c->mle_final.p + (size_t)nr_small * kFinal,
+                       c->mle_status.p + nr_small, c->mle_rounds.p + nr_small);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     std::atomic_thread_fence(std::memory_order_acquire);
-    for (int j = 0, q = 0; j < ns; ++j) {
-        const cbo_mle_run &r = runs[small[(size_t)j]];
+    for (int j = 0, q = 0; j < ns + nm; ++j) {
+        const cbo_mle_run &r = runs[taken[(size_t)j]];
         const size_t P = (size_t)r.n_params;
         for (int s = 0; s < r.n_starts; ++s, ++q) {
             if (c->mle_status[q] == kNoStatus) return fail(CBO_ERR_HIP, "MLE kernel: no status for a run it was given");
@@ -4499,6 +4521,11 @@ extern "C" int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_r
         }
     }
     return CBO_OK;
+}
+
+extern "C" int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_run *runs, int *model_status_out)
+{
+    return cbo_gp_mle_sets_rows(n_models, gps, runs, kPadN, model_status_out);
 }
 
 static int general_lml_gradients(cbo_gp *g, double *lml_out, double *dvariance_out, double *dlengthscale_out,

@@ -479,6 +479,13 @@ constexpr int kMleRingDoubles = 2 * 8 * CBO_HMC_MAX_PARAMS;
 void launch_mle_sets(hipStream_t s, const cbo_small_set *sets, int n_models, const cbo_small_mle *runs, int n_runs,
                      double *scratch, int64_t stride, int *info, double *rings, double *final_out, int *status_out,
                      int *rounds_out);
+// ... and for models of 128 < n <= 256 observations (kernels_mle_mid.hip, mle_mid_kernel): the same
+// arguments and outputs; scratch: `stride` >= mid_mle_scratch_doubles() doubles per RUN -- the two-block slab of
+// mid_lml_scratch_doubles() and behind it the region the run's points are prepared into.
+size_t mid_mle_scratch_doubles();
+void launch_mle_mid(hipStream_t s, const cbo_small_set *sets, int n_models, const cbo_small_mle *runs, int n_runs,
+                    double *scratch, int64_t stride, int *info, double *rings, double *final_out, int *status_out,
+                    int *rounds_out);
 // ---- the hyper-parameters' log prior of many models in one launch (kernels_prior.hip) -------------------------
 // One lane per model: hyper_prior_at over the model's n_params entries at theta.  items (pinned, device-mapped) are read and
 // written by the kernel directly; the caller synchronises the stream before it reads lp / dlp.

@@ -67,12 +67,14 @@ class _Graph:
         """src/graphs/GraphInterface.py:37-43."""
         return "gp_" + "_".join(interventions)
 
-    def fit_all_gaussian_processes(self, measurements=None, lockstep=True, optimizer="host", num_restarts=1):
+    def fit_all_gaussian_processes(self, measurements=None, lockstep=True, optimizer="host", num_restarts=1,
+                                   device_rows=128):
         """CompleteGraph.py:114-137 / CoralGraph.py:186-212 / SimplifiedCoralGraph.py:194-220: one graph-level GP per fit
         dependency (``fit_gaussian_process``, i.e. GPy's ``gp.optimize()`` on each), returned as {``gp_<deps>``: model}.
         All of them are optimised together, one device call per L-BFGS round (``fit_gaussian_processes``;
         ``lockstep=False`` fits them one by one -- the same models; ``optimizer="device"``, with ``num_restarts`` starts per
-        model: every model's whole search in one device launch).
+        model: every model's whole search in one device launch; ``device_rows=256``: models of 129..256
+        rows inside it too).
 
         Deviation, documented: the reference builds the inputs from ``self.measurements`` -- the data the graph was
         constructed with -- but the outputs from the ``measurements`` argument, so after the first observe the rows of
@@ -89,7 +91,7 @@ class _Graph:
         ys = [data[o] for o in outputs]
         names = [self.get_gp_name(d) for d in deps]
         models = fit_gaussian_processes(xs, ys, self.fit_parameters, lockstep=lockstep, optimizer=optimizer,
-                                        num_restarts=num_restarts)
+                                        num_restarts=num_restarts, device_rows=device_rows)
         return dict(zip(names, models))
 
     @classmethod

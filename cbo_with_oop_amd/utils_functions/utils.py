@@ -32,35 +32,37 @@ def find_current_global(current_y, dict_interventions, task):
     return dict_values[opt_variable]
 
 
-def fit_gaussian_process(x, y, parameter_list, optimizer="host", num_restarts=1):
+def fit_gaussian_process(x, y, parameter_list, optimizer="host", num_restarts=1, device_rows=128):
     """utils.py:40-45: graph-level GP, RBF(lengthscale=p[0], variance=p[1], ARD=p[3]), noise fixed 1e-2.
     ``gp.optimize()`` (hyper-parameter MLE) is called as in the reference.  ``optimizer="device"`` (with
-    ``num_restarts`` starts): the one-launch search of DESIGN.md §4v instead."""
-    from ..GaussianProcessFactory import (GaussianProcessFactory, GaussianProcessType, checked_mle_optimizer,
-                                          optimize_together)
-    checked_mle_optimizer(optimizer, num_restarts)
+    ``num_restarts`` starts): the one-launch search of DESIGN.md §4v instead; ``device_rows=256`` lets it take a model of
+    129..256 rows."""
+    from ..GaussianProcessFactory import (GaussianProcessFactory, GaussianProcessType, checked_mle_device_rows,
+                                          checked_mle_optimizer, optimize_together)
+    checked_mle_device_rows(device_rows, checked_mle_optimizer(optimizer, num_restarts))
     gp = GaussianProcessFactory.create(GaussianProcessType.GRAPH_GP, x, y, parameter_list)
     if optimizer == "device":
-        optimize_together([gp], optimizer=optimizer, num_restarts=num_restarts)
+        optimize_together([gp], optimizer=optimizer, num_restarts=num_restarts, device_rows=device_rows)
     else:
         gp.optimize()
     return gp
 
 
-def fit_gaussian_processes(xs, ys, parameter_lists, lockstep=True, optimizer="host", num_restarts=1):
+def fit_gaussian_processes(xs, ys, parameter_lists, lockstep=True, optimizer="host", num_restarts=1, device_rows=128):
     """``[fit_gaussian_process(x, y, p) for ...]`` -- the graph-level GPs of an observe step -- with the hyper-parameter
     MLEs run together: every round of the models' L-BFGS-B runs is ONE device call for all of them
     (``GaussianProcessFactory.optimize_together``).  Models of at most 128 rows get the trajectories and results of
     fitting them one by one, bit for bit; those of 128 < n <= 256 are evaluated by the device's two-block form without
     refits (the same values to rounding).  ``lockstep=False`` fits them one by one.  ``optimizer="device"`` (with
     ``num_restarts`` starts per model): every model's whole search in ONE device launch, whatever
-    ``lockstep`` says."""
-    from ..GaussianProcessFactory import (GaussianProcessFactory, GaussianProcessType, checked_mle_optimizer,
-                                          optimize_together)
-    if checked_mle_optimizer(optimizer, num_restarts) == "device":
+    ``lockstep`` says; ``device_rows=256``: models of 129..256 rows inside that launch too."""
+    from ..GaussianProcessFactory import (GaussianProcessFactory, GaussianProcessType, checked_mle_device_rows,
+                                          checked_mle_optimizer, optimize_together)
+    checked_mle_device_rows(device_rows, checked_mle_optimizer(optimizer, num_restarts))
+    if optimizer == "device":
         models = [GaussianProcessFactory.create(GaussianProcessType.GRAPH_GP, x, y, p)
                   for x, y, p in zip(xs, ys, parameter_lists)]
-        optimize_together(models, optimizer=optimizer, num_restarts=num_restarts)
+        optimize_together(models, optimizer=optimizer, num_restarts=num_restarts, device_rows=device_rows)
         return models
     if not lockstep:
         return [fit_gaussian_process(x, y, p) for x, y, p in zip(xs, ys, parameter_lists)]

@@ -932,6 +932,16 @@ typedef struct cbo_mle_run {            /* one model: n_starts runs */
     int *status_out, *rounds_out;       /* n_starts */
 } cbo_mle_run;
 int cbo_gp_mle_sets(int n_models, cbo_gp *const *gps, const cbo_mle_run *runs, int *model_status_out);
+/* The same call with the band of models the launch takes chosen by the caller: max_rows = 128 IS
+ * cbo_gp_mle_sets.  max_rows = 256: the models of at most 128 observations go into the mle_sets_kernel launch exactly as
+ * above, with the same bits; the fp64 models of 129..256 observations (CBO_HIP_SMALL_SETS not 0) go into one mle_mid_kernel
+ * launch on the same stream -- the same search around the two-block likelihood, one workgroup per run with about 1 MB of
+ * scratch -- and one synchronisation waits for both; everything else is CBO_MLE_DECLINED.  For such a run lml_out and
+ * grad_out are, bit for bit, what cbo_gp_lml_gradients_batch answers for the model at theta_out (cbo_gp_lml_gradients
+ * alone refits a model of that size and takes the general path: the same values to rounding).
+ * CBO_ERR_INVALID before any device work, beside the cases above: max_rows other than 128 or 256; more than 256 runs of
+ * models of 129..256 observations in one call (one workgroup per compute unit, about 256 MB of scratch). */
+int cbo_gp_mle_sets_rows(int n_models, cbo_gp *const *gps, const cbo_mle_run *runs, int max_rows, int *model_status_out);
 
 /* Priors on the hyper-parameters: GPy's set_prior with priors.Gaussian / LogGaussian / Gamma /
  * InverseGamma, restated in csrc/hyper_prior.h (from memory, parity with GPy unpinned).  Priors are state of the model
