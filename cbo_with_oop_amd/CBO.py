@@ -27,8 +27,9 @@ def checked_path_constraints(constraints, kind=("EI", None)):
     from .utils_functions.constrained import MAX_CONSTRAINTS, SENSE_CODE
     if not constraints:
         return []
-    if kind[0] != "EI":
-        raise ValueError("constraints multiply the causal EI: acquisition must be 'EI'")
+    if kind[0] not in ("EI", "LOGCEI"):
+        raise ValueError("constraints multiply the causal EI: acquisition must be 'EI' (or 'LOGCEI', the sum of the "
+                         "logarithms)")
     if len(constraints) > MAX_CONSTRAINTS:
         raise ValueError(f"at most {MAX_CONSTRAINTS} constraints, not {len(constraints)}")
     out = []
@@ -98,7 +99,10 @@ class CBOAcquisitionPath:
     ``">="``) with ``constraint_data_y`` (``constraint_data_y[s][c]`` is (n_s, 1): the values of node ``c`` at ``data_x[s]``)
     make every set's score ``EI * prod PoF / cost``: the path keeps ``constraint_models[s][c]`` --
     non-causal models from the factory on ``data_x[s]`` -- rebuilds them with the objectives and passes them on.  They need
-    ``acquisition="EI"`` and a single process.
+    ``acquisition="EI"`` and a single process -- or ``acquisition="LOGCEI"`` (``acquisition_param``: the log EI's jitter,
+    default 0), which scores every set with ``log EI + sum log PoF - log cost``: finite and ordered where
+    every product is an exact 0.0 and set 0 would win the tie.  ``"LOGCEI"`` needs constraints, no hyper-parameter samples,
+    no batch, no ``refine``, no ``device_prior``, ``cost_mode="batch"`` and a single process.
     ``hyper_samples`` (a positive int H, or a callable ``sampler(model, set_index) -> (H, P)`` samples in GPy's parameter
     order) makes every set's score the causal EI marginalised over hyper-parameter samples of its own model:
     an int draws ``model.generate_hyperparameters_samples(H)`` with emukit's defaults.  The path keeps ``hyper_rows[s]`` and
@@ -130,8 +134,8 @@ class CBOAcquisitionPath:
                  mle_restarts=1, hyper_priors=None, cost_mode="batch", mle_device_rows=128):
         from .GaussianProcessFactory import checked_mle_device_rows, checked_mle_optimizer
         from .utils_functions.priors import checked_priors
-        from .utils_functions.utils import (checked_device_prior, checked_log_ei, checked_pointwise_cost, checked_refine,
-                                            sets_acquisition_or_default as sets_acquisition)
+        from .utils_functions.utils import (checked_device_prior, checked_log_cei, checked_log_ei, checked_pointwise_cost,
+                                            checked_refine, sets_acquisition_or_default as sets_acquisition)
         self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
         self.mle_device_rows = checked_mle_device_rows(mle_device_rows, mle_optimizer)
         self.device_prior = checked_device_prior(device_prior, refine)
@@ -142,6 +146,7 @@ class CBOAcquisitionPath:
         self._kind = sets_acquisition(acquisition, acquisition_param)
         self.acquisition, self.acquisition_param = acquisition, acquisition_param
         checked_log_ei(self._kind, self.device_prior)
+        checked_log_cei(self._kind, constraints or None, hyper_samples, batch_size, refine, device_prior, False, cost_mode)
         if self._kind[0] == "MES" and task != "min":
             raise ValueError("acquisition='MES' minimises: task must be 'min'")
         self.constraints = checked_path_constraints(constraints, self._kind)
@@ -420,7 +425,7 @@ class CBOAcquisitionPath:
         st = self._call_cache.get("sweep_sets")
         model = self.models[s] if (s is not None and self.models) else None
         fast = (st is not None and model is not None and not self.constraints and self.hyper_samples is None
-                and self._kind[0] not in ("MES", "LOGEI") and self.batch_size is None and not self.refine
+                and self._kind[0] not in ("MES", "LOGEI", "LOGCEI") and self.batch_size is None and not self.refine
                 and self.cost_mode == "batch"
                 and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
@@ -515,7 +520,8 @@ class CBO(CBOAcquisitionPath):
     of set s to the (M, 1) values of the node -- by default ``compute_interventions`` on the graph's SEM with
     ``target_variable=node``.  A constrained node that is the target, or that some exploration set manipulates, raises
     ``ValueError``.  The incumbent stays the plain best observation (``find_current_global``), as in emukit's recipe; the
-    monitor records ``constraint_values`` and ``feasible`` per trial.
+    monitor records ``constraint_values`` and ``feasible`` per trial.  With ``acquisition="LOGCEI"`` the score is the sum of
+    the logarithms, ``log EI + sum log PoF - log cost``, as for ``CBOAcquisitionPath``.
     ``hyper_samples`` (a positive int or a callable sampler, as for ``CBOAcquisitionPath``): ``intervene()`` scores every set
     with the EI marginalised over hyper-parameter samples of its model; the closing ``optimize()`` of the
     chosen set's model stays, as in the reference.  ``hyper_sampler="device"`` draws them by the one-launch HMC (DESIGN.md
@@ -591,6 +597,9 @@ class CBO(CBOAcquisitionPath):
         data_y = [np.asarray(y, dtype=np.float64).reshape(-1, 1) for _, y in interventional_data]
         if len(data_x) != len(exploration):
             raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
+        from .utils_functions.utils import checked_log_cei
+        checked_log_cei(sets_acquisition(acquisition, acquisition_param), path_constraints or None, hyper_samples, batch_size,
+                        refine, device_prior, False, cost_mode)
         path_constraints = checked_path_constraints(path_constraints, sets_acquisition(acquisition, acquisition_param))
         checked_path_hyper_samples(hyper_samples, sets_acquisition(acquisition, acquisition_param), path_constraints)
         checked_hyper_sampler(hyper_sampler, hyper_samples)

@@ -6,7 +6,7 @@ from .utils_functions import (CandidateGrid, CausalExpectedImprovement, CausalMe
                               CausalNegativeLowerConfidenceBound, CausalProbabilityOfImprovement, Cost, ModelVariance,
                               IntegratedHyperParameterAcquisition, IntegratedVarianceReduction, MaxValueEntropySearch, find_current_global, find_next_y_point, total_cost)
 from .utils_functions import AcquisitionProduct, ProbabilityOfFeasibility, find_next_y_points  # noqa: F401
-from .utils_functions import CausalLogExpectedImprovement  # noqa: F401
+from .utils_functions import CausalLogExpectedImprovement, ConstrainedLogExpectedImprovement  # noqa: F401
 from .utils_functions import PointCostQuotient, PointwiseCost  # noqa: F401
 from .CBO import CBOAcquisitionPath  # noqa: F401
 from .DoCalculus import DoCalculus, do_prior_functions  # noqa: F401

@@ -154,6 +154,14 @@ SIGNATURES = {
                                                  ctypes.c_double, ctypes.c_double, ctypes.c_int, c_void_pp, c_void_pp,
                                                  c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p,
                                                  c_double_p, c_int64_p]),
+    # the constrained acquisition in log space
+    "cbo_acq_sweep_constrained_log": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
+                                                     ctypes.c_double, ctypes.c_double, ctypes.c_int, c_void_pp, c_void_pp,
+                                                     c_double_p, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p,
+                                                     c_double_p, c_int64_p]),
+    "cbo_acq_sweep_sets_constrained_log": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, ctypes.c_int,
+                                                          ctypes.c_double, c_double_p, c_int_p, c_void_pp, c_void_pp,
+                                                          c_double_p, c_double_p, c_int_p, c_double_p, c_int64_p]),
     "cbo_acq_sweep_hyper": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_double,
                                            ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_int64_p]),
     "cbo_acq_sweep_kind": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,

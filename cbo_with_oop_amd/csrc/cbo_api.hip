@@ -2027,11 +2027,12 @@ extern "C" int cbo_acq_sweep_mes(cbo_gp *g, cbo_cands *k, int n_samples, const d
 // EI times the constraints' probabilities of feasibility over a cost, one pass with the arg-max.  Every (model, set) pair is
 // brought up to date by the sweep's own steps (enqueue_vectors, settle_vectors), one after the other on the stream, its
 // vectors ending in the set's own buffers; then the one epilogue reads them all.
-extern "C" int cbo_acq_sweep_constrained(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
-                                         int n_con, cbo_gp *const *con_gps, cbo_cands *const *con_cands,
-                                         const double *con_value, const double *con_jitter, const int *con_sense,
-                                         double *acq_out, double *ei_out, double *pof_out, double *best_val,
-                                         int64_t *best_idx)
+// log_form (cbo_acq_sweep_constrained_log): the same steps, the epilogue's log instantiation; ei_out and
+// pof_out then carry log EI and the log probabilities.
+static int sweep_constrained_impl(bool log_form, cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter,
+                                  double cost, int n_con, cbo_gp *const *con_gps, cbo_cands *const *con_cands,
+                                  const double *con_value, const double *con_jitter, const int *con_sense, double *acq_out,
+                                  double *ei_out, double *pof_out, double *best_val, int64_t *best_idx)
 {
     if (n_con < 0 || n_con > CBO_MAX_CONSTRAINTS)
         return fail(CBO_ERR_INVALID, "the number of constraints must be in 0.." + std::to_string(CBO_MAX_CONSTRAINTS));
@@ -2042,6 +2043,8 @@ extern "C" int cbo_acq_sweep_constrained(cbo_gp *g, cbo_cands *k, double y_best,
     if (n_con > 0 && (!con_gps || !con_cands || !con_value || !con_jitter || !con_sense))
         return fail(CBO_ERR_INVALID, "NULL argument");
     if (!(cost > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    if (log_form && objective && !std::isfinite(ei_jitter)) return fail(CBO_ERR_INVALID, "jitter must be finite");
+    if (log_form && objective && !std::isfinite(y_best)) return fail(CBO_ERR_INVALID, "y_best must be finite");
     cbo_gp *gps[kConMaxModels];
     cbo_cands *sets[kConMaxModels];
     int nm = 0;
@@ -2100,7 +2103,7 @@ extern "C" int cbo_acq_sweep_constrained(cbo_gp *g, cbo_cands *k, double y_best,
     {
         PhaseScope ps(c, PH_ACQ);
         launch_constrained_acq(c->stream, p, m, acq_out ? c->acq.p : nullptr, c->part_val, c->part_idx, sets[0]->index_offset,
-                               nb);
+                               nb, log_form);
         launch_argmax_final(c->stream, c->part_val, c->part_idx, nb, c->h_best_val, c->h_best_idx);
     }
     HIP_TRY(hipGetLastError());
@@ -2112,6 +2115,28 @@ extern "C" int cbo_acq_sweep_constrained(cbo_gp *g, cbo_cands *k, double y_best,
     HIP_TRY(hipStreamSynchronize(c->stream));
     complete_finish(c, best_val, best_idx);
     return CBO_OK;
+}
+
+extern "C" int cbo_acq_sweep_constrained(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
+                                         int n_con, cbo_gp *const *con_gps, cbo_cands *const *con_cands,
+                                         const double *con_value, const double *con_jitter, const int *con_sense,
+                                         double *acq_out, double *ei_out, double *pof_out, double *best_val,
+                                         int64_t *best_idx)
+{
+    return sweep_constrained_impl(false, g, k, y_best, task, ei_jitter, cost, n_con, con_gps, con_cands, con_value, con_jitter,
+                                  con_sense, acq_out, ei_out, pof_out, best_val, best_idx);
+}
+
+// log EI plus the constraints' log probabilities of feasibility less log cost: finite and ordered where
+// the product above is an exact 0.  With no constraint cbo_acq_sweep_logei's bits.
+extern "C" int cbo_acq_sweep_constrained_log(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
+                                             int n_con, cbo_gp *const *con_gps, cbo_cands *const *con_cands,
+                                             const double *con_value, const double *con_jitter, const int *con_sense,
+                                             double *acq_out, double *logei_out, double *logpof_out, double *best_val,
+                                             int64_t *best_idx)
+{
+    return sweep_constrained_impl(true, g, k, y_best, task, ei_jitter, cost, n_con, con_gps, con_cands, con_value, con_jitter,
+                                  con_sense, acq_out, logei_out, logpof_out, best_val, best_idx);
 }
 
 // Refit and sweep in one call, the two overlapped: what CBO.intervene() does for the set it has just
@@ -3018,19 +3043,21 @@ extern "C" int cbo_acq_refine_sets_prior(int n_sets, cbo_gp *const *gps, const c
 // cbo_acq_sweep_sets' routing applied to every model of a set: a set all of whose 1 + n_con[i] models are fp64 with at most
 // 128 observations is factored AND swept, model after model, by the workgroups of one launch; every other set -- and a set one
 // of whose models met a non-positive pivot there -- takes cbo_gp_fit on its unfitted models and cbo_acq_sweep_constrained.
-extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best,
-                                              int task, double ei_jitter, const double *costs, const int *n_con,
-                                              cbo_gp *const *con_gps, cbo_cands *const *con_cands, const double *con_value,
-                                              const double *con_jitter, const int *con_sense, double *best_vals,
-                                              int64_t *best_idxs)
+// log_form (cbo_acq_sweep_sets_constrained_log): the same routing with the log epilogues on both paths.
+static int sweep_sets_constrained_impl(bool log_form, int n_sets, cbo_gp *const *gps, cbo_cands *const *cands,
+                                       const double *y_best, int task, double ei_jitter, const double *costs, const int *n_con,
+                                       cbo_gp *const *con_gps, cbo_cands *const *con_cands, const double *con_value,
+                                       const double *con_jitter, const int *con_sense, double *best_vals, int64_t *best_idxs)
 {
     // what needs no handle first
     if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
     if (!y_best || !costs || !n_con || !best_vals || !best_idxs)
         return fail(CBO_ERR_INVALID, "NULL argument: y_best, costs, n_con, best_vals and best_idxs must be given");
     if (task != CBO_TASK_MIN && task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
+    if (log_form && !std::isfinite(ei_jitter)) return fail(CBO_ERR_INVALID, "jitter must be finite");
     int64_t total_con = 0;
     for (int i = 0; i < n_sets; ++i) {
+        if (log_form && !std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite");
         if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive (set " + std::to_string(i) + ")");
         if (n_con[i] < 0 || n_con[i] > CBO_MAX_CONSTRAINTS)
             return fail(CBO_ERR_INVALID, "n_con of set " + std::to_string(i) + " must be in 0.." +
@@ -3107,20 +3134,44 @@ extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cb
         return CBO_OK;
     };
     return run_small_or_general(
-        c, "cbo_acq_sweep_sets_constrained", "multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
-        [&](const SmallLaunch &L) { launch_small_sets_con(c->stream, c->sets_host, n_pairs, ns, max_pairs, blocks, L); },
+        c, log_form ? "cbo_acq_sweep_sets_constrained_log" : "cbo_acq_sweep_sets_constrained",
+        "multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
+        [&](const SmallLaunch &L) {
+            launch_small_sets_con(c->stream, c->sets_host, n_pairs, ns, max_pairs, blocks, L, log_form);
+        },
         [&](int j, int i) { return harvest_winner(c, j, i, best_vals, best_idxs); },
         [&](int i) -> int {
             const int64_t f = first[(size_t)i];
             int rc = ensure_fitted(gps[i]);
             for (int64_t j = f; rc == CBO_OK && j < first[(size_t)i + 1]; ++j) rc = ensure_fitted(con_gps[j]);
             if (rc != CBO_OK) return rc;
-            return cbo_acq_sweep_constrained(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], n_con[i],
-                                             n_con[i] ? con_gps + f : nullptr, n_con[i] ? con_cands + f : nullptr,
-                                             n_con[i] ? con_value + f : nullptr, n_con[i] ? con_jitter + f : nullptr,
-                                             n_con[i] ? con_sense + f : nullptr, nullptr, nullptr, nullptr, &best_vals[i],
-                                             &best_idxs[i]);
+            return sweep_constrained_impl(log_form, gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], n_con[i],
+                                          n_con[i] ? con_gps + f : nullptr, n_con[i] ? con_cands + f : nullptr,
+                                          n_con[i] ? con_value + f : nullptr, n_con[i] ? con_jitter + f : nullptr,
+                                          n_con[i] ? con_sense + f : nullptr, nullptr, nullptr, nullptr, &best_vals[i],
+                                          &best_idxs[i]);
         });
+}
+
+extern "C" int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best,
+                                              int task, double ei_jitter, const double *costs, const int *n_con,
+                                              cbo_gp *const *con_gps, cbo_cands *const *con_cands, const double *con_value,
+                                              const double *con_jitter, const int *con_sense, double *best_vals,
+                                              int64_t *best_idxs)
+{
+    return sweep_sets_constrained_impl(false, n_sets, gps, cands, y_best, task, ei_jitter, costs, n_con, con_gps, con_cands,
+                                       con_value, con_jitter, con_sense, best_vals, best_idxs);
+}
+
+// The log form for every set of a trial: per set cbo_acq_sweep_constrained_log's bits on fitted twins.
+extern "C" int cbo_acq_sweep_sets_constrained_log(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands,
+                                                  const double *y_best, int task, double ei_jitter, const double *costs,
+                                                  const int *n_con, cbo_gp *const *con_gps, cbo_cands *const *con_cands,
+                                                  const double *con_value, const double *con_jitter, const int *con_sense,
+                                                  double *best_vals, int64_t *best_idxs)
+{
+    return sweep_sets_constrained_impl(true, n_sets, gps, cands, y_best, task, ei_jitter, costs, n_con, con_gps, con_cands,
+                                       con_value, con_jitter, con_sense, best_vals, best_idxs);
 }
 
 // ---- the causal EI marginalised over hyper-parameter samples (kernels_hyper.hip) -------------------------

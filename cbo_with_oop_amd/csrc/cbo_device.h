@@ -250,8 +250,9 @@ __device__ __forceinline__ double ndtr_with_exp(double a, double e)
 //     a < -1:  log(erfcx(-t) / 2) - t^2          else:  log1p(-erfc(t) / 2)
 // with cephes' erf / erfc as in ndtr_with_exp.  scipy's erfcx is the Faddeeva package's; here erfcx(y) for y > 1 / sqrt 2 is
 // cephes erfc's rational function without its exponential (P / Q below 8, R / S beyond: the same relative accuracy as
-// erfc itself) and exp(y^2) (1 - erf(y)) below 1.  Only the Gumbel fit of max-value entropy search calls it (a few
-// hundred thousand evaluations per fit): IEEE divisions and the device library's exp / log / log1p throughout.
+// erfc itself) and exp(y^2) (1 - erf(y)) below 1.  The Gumbel fit of max-value entropy search calls it (a few hundred
+// thousand evaluations per fit), and log_feasibility_of below, once per constraint and candidate: IEEE divisions and the
+// device library's exp / log / log1p throughout.
 __device__ __forceinline__ double log_ndtr(double a)
 {
 #pragma clang fp contract(off)
@@ -498,6 +499,23 @@ __device__ __forceinline__ double log_ei_of(double mean, double var, const AcqPa
 __device__ __forceinline__ double log_ei_of(double mean, double var, const AcqParams &p)
 {
     return log_ei_of(mean, var, p, log(p.cost));
+}
+
+// log of feasibility_of: the same u -- the same operations, the same special case, the sign flipped for
+// CBO_CON_GE: feasibility_of's bits -- then log_ndtr(u), finite where ndtr(u) itself underflows to 0 (u below about -38).
+// A NaN mean or variance gives NaN.
+__device__ __forceinline__ double log_feasibility_of(double mean, double var, double value, double jitter, int sense)
+{
+#pragma clang fp contract(off)
+    double s, rs;
+    bool special;
+    sqrt_and_reciprocal(var, s, rs, special);
+    const double a = value - (mean + jitter);
+    double u = a * rs;
+    u = fma(fma(-u, s, a), rs, u);
+    if (__builtin_expect(special, 0)) u = a / s;                    // (a zero or infinite variance: the IEEE quotient)
+    if (sense != CBO_CON_LE) u = -u;                                // (uniform)
+    return log_ndtr(u);
 }
 
 // ---- max-value entropy search: the epilogue of mes_acq_kernel (kernels_mes.hip) and of small_sets_kernel<kMesKind>

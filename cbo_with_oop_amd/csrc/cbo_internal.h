@@ -516,9 +516,10 @@ void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_set
 // one descriptor per (model, candidate set) pair, a set's pairs consecutive with the objective first; a constraint's value,
 // jitter and sense ride in y_best, ei_jitter and task; pairs[s].pad_ = index of set s's first pair.  max_pairs = the most
 // pairs of one set (<= 1 + CBO_MAX_CONSTRAINTS).  scratch, part_val, part_idx: n_sets * blocks_per_set slots; info, ticket,
-// out: one per SET, as above
+// out: one per SET, as above.  log_form: the sum of the terms' logarithms less log(cost), the general log
+// pass's bits
 void launch_small_sets_con(hipStream_t s, const cbo_small_set *pairs, int n_pairs, int n_sets, int max_pairs,
-                           int blocks_per_set, const SmallLaunch &L);
+                           int blocks_per_set, const SmallLaunch &L, bool log_form = false);
 
 // ---- hyper-parameter-marginalised EI (kernels_hyper.hip) ----------------------------------------------
 // One launch (schedule 1) or two (2; 0 = by the number of candidate blocks) for a model of at most 128 observations: st is
@@ -609,9 +610,11 @@ struct ConParams {
 };
 // acq = (((t_0 t_1) t_2) ...) / cost for i < m (acq_out may be null), t_0 = acquisition_of at cost 1 when has_objective,
 // every other t_k = ndtr(+-(value - (mean + jitter)) / sqrt(var)) of acq_kernel's mean and variance (noise included);
-// launch grid and arg-max partials as launch_acq (acq_blocks_for)
+// launch grid and arg-max partials as launch_acq (acq_blocks_for).
+// log_form: acq = (((l_0 + l_1) + l_2) ...) - log(cost), l_0 = log_ei_of at log cost 0.0 (task 'max' the
+// mirror), every other l_k = log_ndtr of the same u: finite where the product underflows
 void launch_constrained_acq(hipStream_t s, const ConParams &p, int64_t m, double *acq_out, double *part_val,
-                            int64_t *part_idx, int64_t index_offset, int n_blocks);
+                            int64_t *part_idx, int64_t index_offset, int n_blocks, bool log_form = false);
 // ---- point-wise acquisitions (kernels_pointwise.hip) -------------------------------------------------
 // kind CBO_ACQ_LCB / _PI / _VAR: acq_kernel's mean and variance (noise included), then the kind's value / cost.  p.ei_jitter
 // carries the kind's parameter (beta; PI's jitter), p.y_best PI's incumbent; p.want_ei and p.y_best_dev are not read.

@@ -26,7 +26,11 @@ namespace cbo {
 // the kernel arguments (scalar loads).
 // CAUSAL: some model's candidates carry a prior mean / variance (the others skip those loads: uniform); OUT: per-candidate
 // results are written (acq, and each model's own term where its `out` is set).  The common call asks for neither.
-template <bool CAUSAL, bool OUT>
+// LOG: the sum of logarithms in the place of the product -- log_ei_of at log cost 0.0 for the objective (the
+// mirror for task 'max', not the product form's -EI), log_feasibility_of for a constraint, ((logEI + l_0) + l_1) + ... left to
+// right, then one subtraction of log(cost): cbo_acq_sweep_logei's bits with no constraint, for every cost.  The product
+// form's instantiations are what they were.
+template <bool CAUSAL, bool OUT, bool LOG>
 __global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64_t m, double *__restrict__ acq_out,
                                                               double *__restrict__ part_val,
                                                               int64_t *__restrict__ part_idx, int64_t index_offset)
@@ -46,6 +50,7 @@ __global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64
     AcqParams ap;                                                // the fields posterior_of / acquisition_of read, per model
     ap.y_best = p.y_best; ap.ei_jitter = p.ei_jitter; ap.cost = 1.0;
     ap.task = p.task; ap.include_noise = 1; ap.want_ei = 1;
+    const double log_cost = LOG ? log(p.cost) : 0.0;             // (uniform: once per launch)
     d2 qn = {0.0, 0.0}, mun = {0.0, 0.0}, pmn = {0.0, 0.0}, pvn = {0.0, 0.0};
     // results waiting for the next step's store: one model's term, and the finished product of a pair
     d2 term_done = {0.0, 0.0}, acq_done = {0.0, 0.0};
@@ -79,7 +84,17 @@ __global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64
                 mean2[e] = mean;
                 var2[e] = var;
             }
-            if (k == 0 && p.has_objective) {                     // (uniform) cbo_acq_sweep's acq at cost 1
+            if (LOG) {
+                if (k == 0 && p.has_objective) {                 // (uniform) cbo_acq_sweep_logei's acq at cost 1
+                    t2[0] = log_ei_of(mean2[0], var2[0], ap, 0.0);
+                    t2[1] = log_ei_of(mean2[1], var2[1], ap, 0.0);
+                } else {
+                    t2[0] = log_feasibility_of(mean2[0], var2[0], md.value, md.jitter, md.sense);
+                    t2[1] = log_feasibility_of(mean2[1], var2[1], md.value, md.jitter, md.sense);
+                }
+                if (k == 0) acc = t2;
+                else acc = acc + t2;
+            } else if (k == 0 && p.has_objective) {              // (uniform) cbo_acq_sweep's acq at cost 1
                 t2[0] = acquisition_of(mean2[0], var2[0], ap);
                 t2[1] = acquisition_of(mean2[1], var2[1], ap);
                 acc = t2;
@@ -91,7 +106,10 @@ __global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64
             }
             if (OUT) { term_dst = md.out; term_base = cu; term_done = t2; }
         }
-        if (nm == 1 && p.has_objective) {
+        if (LOG) {
+            acc[0] = acc[0] - log_cost;
+            acc[1] = acc[1] - log_cost;
+        } else if (nm == 1 && p.has_objective) {
             // no constraint: acquisition_of's own quotient (the reciprocal of the cost, corrected by the remainder), so that
             // the result is cbo_acq_sweep's bits for every cost
             const double rc = 1.0 / p.cost;
@@ -116,15 +134,18 @@ __global__ __launch_bounds__(256) void constrained_acq_kernel(ConParams p, int64
 }
 
 void launch_constrained_acq(hipStream_t s, const ConParams &p, int64_t m, double *acq_out, double *part_val,
-                            int64_t *part_idx, int64_t index_offset, int n_blocks)
+                            int64_t *part_idx, int64_t index_offset, int n_blocks, bool log_form)
 {
     bool causal = false, out = acq_out != nullptr;
     for (int k = 0; k < p.n_models; ++k) {
         causal = causal || p.mdl[k].pv != nullptr;
         out = out || p.mdl[k].out != nullptr;
     }
-    auto kernel = causal ? (out ? constrained_acq_kernel<true, true> : constrained_acq_kernel<true, false>)
-                         : (out ? constrained_acq_kernel<false, true> : constrained_acq_kernel<false, false>);
+    auto kernel = causal ? (out ? constrained_acq_kernel<true, true, false> : constrained_acq_kernel<true, false, false>)
+                         : (out ? constrained_acq_kernel<false, true, false> : constrained_acq_kernel<false, false, false>);
+    if (log_form)
+        kernel = causal ? (out ? constrained_acq_kernel<true, true, true> : constrained_acq_kernel<true, false, true>)
+                        : (out ? constrained_acq_kernel<false, true, true> : constrained_acq_kernel<false, false, true>);
     hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(256), 0, s, p, m, acq_out, part_val, part_idx, index_offset);
 }
 

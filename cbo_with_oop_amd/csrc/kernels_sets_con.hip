@@ -24,7 +24,10 @@ static_assert(1 + CBO_MAX_CONSTRAINTS <= kSmallTwoPhaseFromBlocks, "a set's pair
 // ei_jitter and task; the objective's descriptor carries the EI's scalars and the set's cost.
 // phases: 1 = workgroup (p, set) factors pair p of the set into its slot, nothing else; 2 = the factors are in the slots;
 // 3 = everything in one launch, the workgroup's own slot serving its models one after the other.
-template <bool BYVAL>
+// LOG: the running register holds logEI, then (logEI + l_0), then ((logEI + l_0) + l_1), ... -- log_ei_of at
+// log cost 0.0 and log_feasibility_of, constrained_acq_kernel<.., true>'s terms and its closing subtraction of log(cost):
+// cbo_acq_sweep_constrained_log's bits.
+template <bool BYVAL, bool LOG>
 __global__ __launch_bounds__(256) void small_sets_con_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
                                                              int n_pairs, double *scratch, int blocks_per_set,
                                                              double *__restrict__ part_val, int64_t *__restrict__ part_idx,
@@ -51,6 +54,7 @@ __global__ __launch_bounds__(256) void small_sets_con_kernel(const SmallSetArgs 
     const int64_t c = (int64_t)blk * 64 + wave * 16 + lc;
 
     double run = 0.0;                                             // EI, then EI * pof_0, then (EI * pof_0) * pof_1, ...
+                                                                  // (LOG: logEI, then logEI + l_0, ...)
     double cost = 1.0;
     int64_t m = 0, index_offset = 0;
     for (int p = p0; p < p1; ++p) {                               // (uniform)
@@ -93,14 +97,18 @@ __global__ __launch_bounds__(256) void small_sets_con_kernel(const SmallSetArgs 
         double mean, var;
         if (p == p0) {
             posterior_of(qacc, macc, cpm_c, cpv_c, st.sv != nullptr, ap, mean, var);
-            run = acquisition_of(mean, var, ap);                  // cbo_acq_sweep's acq at cost 1
+            if (LOG) run = log_ei_of(mean, var, ap, 0.0);         // cbo_acq_sweep_logei's acq at cost 1
+            else run = acquisition_of(mean, var, ap);             // cbo_acq_sweep's acq at cost 1
         } else {
             ap.y_best = 0.0; ap.ei_jitter = 0.0; ap.task = CBO_TASK_MIN;
             posterior_of(qacc, macc, cpm_c, cpv_c, st.sv != nullptr, ap, mean, var);
-            run = run * feasibility_of(mean, var, st.y_best, st.ei_jitter, st.task);
+            if (LOG) run = run + log_feasibility_of(mean, var, st.y_best, st.ei_jitter, st.task);
+            else run = run * feasibility_of(mean, var, st.y_best, st.ei_jitter, st.task);
         }
     }
-    if (p1 - p0 == 1) {
+    if (LOG) {
+        run = run - log(cost);
+    } else if (p1 - p0 == 1) {
         // no constraint: acquisition_of's own quotient (the reciprocal of the cost, corrected by the remainder)
         const double rc = 1.0 / cost;
         const double qv = run * rc;
@@ -117,15 +125,15 @@ __global__ __launch_bounds__(256) void small_sets_con_kernel(const SmallSetArgs 
     small_set_finish(bv, bi, set, slot, blocks_per_set, part_val, part_idx, info, ticket, out, seq, &last_flag);
 }
 
-template <bool BYVAL>
+template <bool BYVAL, bool LOG>
 static void launch_small_sets_con_as(hipStream_t s, const SmallSetArgs &args, const cbo_small_set *pairs, int n_pairs,
                                      int n_sets, int max_pairs, int blocks_per_set, double *scratch, double *part_val,
                                      int64_t *part_idx, int *info, int *ticket, cbo_small_result *out, int seq)
 {
     static std::atomic<unsigned long long> opted{0};
-    small_lds_opt_in(reinterpret_cast<const void *>(small_sets_con_kernel<BYVAL>), opted);
+    small_lds_opt_in(reinterpret_cast<const void *>(small_sets_con_kernel<BYVAL, LOG>), opted);
     auto launch = [&](const dim3 &g, int phases) {
-        hipLaunchKernelGGL((small_sets_con_kernel<BYVAL>), g, dim3(256), sizeof(SmallShared), s, args, pairs, n_pairs, scratch,
+        hipLaunchKernelGGL((small_sets_con_kernel<BYVAL, LOG>), g, dim3(256), sizeof(SmallShared), s, args, pairs, n_pairs, scratch,
                            blocks_per_set, part_val, part_idx, info, ticket, out, seq, phases);
     };
     if (blocks_per_set >= kSmallTwoPhaseFromBlocks) {
@@ -138,17 +146,15 @@ static void launch_small_sets_con_as(hipStream_t s, const SmallSetArgs &args, co
 
 // launch_small_sets for the constrained epilogue (cbo_internal.h)
 void launch_small_sets_con(hipStream_t s, const cbo_small_set *pairs, int n_pairs, int n_sets, int max_pairs,
-                           int blocks_per_set, const SmallLaunch &L)
+                           int blocks_per_set, const SmallLaunch &L, bool log_form)
 {
     SmallSetArgs args{};
-    if (n_pairs <= kSmallByValue) {
-        std::memcpy(args.s, pairs, sizeof(cbo_small_set) * (size_t)n_pairs);
-        launch_small_sets_con_as<true>(s, args, pairs, n_pairs, n_sets, max_pairs, blocks_per_set, L.scratch, L.part_val,
-                                       L.part_idx, L.info, L.ticket, L.out, L.seq);
-    } else {
-        launch_small_sets_con_as<false>(s, args, pairs, n_pairs, n_sets, max_pairs, blocks_per_set, L.scratch, L.part_val,
-                                        L.part_idx, L.info, L.ticket, L.out, L.seq);
-    }
+    const bool byval = n_pairs <= kSmallByValue;
+    if (byval) std::memcpy(args.s, pairs, sizeof(cbo_small_set) * (size_t)n_pairs);
+    auto launch = byval ? (log_form ? launch_small_sets_con_as<true, true> : launch_small_sets_con_as<true, false>)
+                        : (log_form ? launch_small_sets_con_as<false, true> : launch_small_sets_con_as<false, false>);
+    launch(s, args, pairs, n_pairs, n_sets, max_pairs, blocks_per_set, L.scratch, L.part_val, L.part_idx, L.info, L.ticket,
+           L.out, L.seq);
 }
 
 }  // namespace cbo

@@ -3,7 +3,8 @@
 from .causal_acquisition_functions import (AcquisitionQuotient, CausalExpectedImprovement, CandidateGrid,  # noqa: F401
                                            PointCostQuotient)
 from .causal_optimizer import CausalGradientAcquisitionOptimizer  # noqa: F401
-from .constrained import AcquisitionProduct, ProbabilityOfFeasibility  # noqa: F401
+from .constrained import (AcquisitionProduct, ConstrainedLogExpectedImprovement,  # noqa: F401
+                          ProbabilityOfFeasibility)
 from .cost_functions import Cost, PointwiseCost, total_cost  # noqa: F401
 from .greedy_batch import GreedyBatchPointCalculator  # noqa: F401
 from .integrated_hyper import IntegratedHyperParameterAcquisition, hmc_sample  # noqa: F401

@@ -78,6 +78,8 @@ class AcquisitionProduct:
     """emukit ``Product`` of acquisitions, flattened: at most one ``CausalExpectedImprovement`` (the objective) and the
     ``ProbabilityOfFeasibility`` factors in the order they were multiplied.  The value is
     ``((EI * pof_0) * pof_1) * ...`` -- what nested emukit Products compute -- formed on the device."""
+    _call = "cbo_acq_sweep_constrained"          # the device call of ``sweep``
+    _term_names = ("ei", "pof")                  # the keys of ``sweep``'s per-factor outputs
 
     def __init__(self, factors):
         flat = []
@@ -182,7 +184,7 @@ class AcquisitionProduct:
             senses = (ctypes.c_int * max(n_con, 1))(*[SENSE_CODE[c.sense] for c in self.constraints])
             for f in self.factors:
                 f.model.ensure_fitted()
-            _lib.check(_lib.load().cbo_acq_sweep_constrained(
+            _lib.check(getattr(_lib.load(), self._call)(
                 obj.model._handle if obj is not None else None, grids[0]._handle if obj is not None else None,
                 float(np.asarray(obj.current_global_min).reshape(-1)[0]) if obj is not None else 0.0,
                 _lib.TASK_CODE[obj.task] if obj is not None else 0, float(obj.jitter) if obj is not None else 0.0,
@@ -192,8 +194,8 @@ class AcquisitionProduct:
             if own:
                 self._close(grids)
         col = lambda a: None if a is None else a[:, None]
-        return {"best_val": best_val.value, "best_idx": best_idx.value, "acq": col(acq), "ei": col(ei),
-                "pof": None if pof is None else np.ascontiguousarray(pof.T)}
+        return {"best_val": best_val.value, "best_idx": best_idx.value, "acq": col(acq), self._term_names[0]: col(ei),
+                self._term_names[1]: None if pof is None else np.ascontiguousarray(pof.T)}
 
     def evaluate(self, x):
         """(M,1) value of the product (emukit ``Product.evaluate``)."""
@@ -214,3 +216,70 @@ class AcquisitionProduct:
             self.close()
         except Exception:
             pass
+
+
+class ConstrainedLogExpectedImprovement(AcquisitionProduct):
+    """The constrained acquisition in log space: ``log EI + sum_k log PoF_k`` -- and, under a ``Cost``,
+    ``- log cost`` -- formed on the device by ``cbo_acq_sweep_constrained_log``.  ``log_ei`` is a
+    ``CausalLogExpectedImprovement``, ``constraints`` a list of at most 8 ``ProbabilityOfFeasibility``.  Where the EI, a
+    probability or their product underflows to an exact 0.0 -- most of a grid for the noise-free models the exploration
+    sets carry -- this is finite and strictly ordered; where the product is representable it is its logarithm.
+    ``task='max'`` is ``CausalLogExpectedImprovement``'s mirror, not the product form's ``-EI``.
+
+    The candidate-grid handling is ``AcquisitionProduct``'s; ``sweep`` returns dict(best_val, best_idx, acq, logei,
+    logpof)."""
+    _call = "cbo_acq_sweep_constrained_log"
+    _term_names = ("logei", "logpof")
+
+    def __init__(self, log_ei, constraints):
+        from .pointwise_acquisitions import CausalLogExpectedImprovement
+        if type(log_ei) is not CausalLogExpectedImprovement:
+            raise ValueError(f"log_ei must be a CausalLogExpectedImprovement, not {type(log_ei).__name__}")
+        constraints = list(constraints)
+        for c in constraints:
+            if not isinstance(c, ProbabilityOfFeasibility):
+                raise ValueError(f"a constraint must be a ProbabilityOfFeasibility, not {type(c).__name__}")
+        if len(constraints) > MAX_CONSTRAINTS:
+            raise ValueError(f"at most {MAX_CONSTRAINTS} ProbabilityOfFeasibility constraints, not {len(constraints)}")
+        self.objective = log_ei
+        self.constraints = constraints
+        self.factors = [log_ei] + constraints
+        self.model = log_ei.model
+        self._cached = None
+
+    def __mul__(self, other):
+        raise TypeError("a ConstrainedLogExpectedImprovement is a sum of logarithms: it is not multiplied")
+
+    def __truediv__(self, cost):
+        """``log EI + sum log PoF - log cost``: a ``LogAcquisitionQuotient`` (the device call subtracts the logarithm)."""
+        from .pointwise_acquisitions import LogAcquisitionQuotient
+        return LogAcquisitionQuotient(self, cost)
+
+    @staticmethod
+    def log_feasibility(mean, sd, max_value, jitter=0.0, sense="<="):
+        """The device's constraint term in numpy / scipy (the host reference): ``log_ndtr(+-(max_value - (mean + jitter)) /
+        sd)``."""
+        import scipy.special
+        u = (float(max_value) - (np.asarray(mean, dtype=np.float64) + jitter)) / np.asarray(sd, dtype=np.float64)
+        return scipy.special.log_ndtr(u if sense == "<=" else -u)
+
+    def evaluate_with_gradients(self, x):
+        """(value (M,1), gradient (M,d)) on the host: the log EI's own gradient plus, per constraint,
+        ``exp(log pdf(u) - log cdf(u)) du/dx`` -- the ratio from the two logarithms, never from an underflowed ``pdf`` over
+        an underflowed ``cdf`` -- with ``du/dx = -(dmean/dx + u dsd/dx) / sd``, the sign flipped for ``">="``."""
+        import scipy.special
+        x = _lib.as_f64(x)
+        f, df = self.objective.evaluate_with_gradients(x)
+        for c in self.constraints:
+            mean, variance = c.model.predict(x)
+            sd = np.sqrt(variance)
+            dmean_dx, dvariance_dx = c.model.get_prediction_gradients(x)
+            dsd_dx = dvariance_dx / (2 * sd)
+            u = (float(c.max_value) - (mean + c.jitter)) / sd
+            du_dx = -(dmean_dx + u * dsd_dx) / sd
+            if c.sense != "<=":
+                u, du_dx = -u, -du_dx
+            log_cdf = scipy.special.log_ndtr(u)
+            ratio = np.exp((-(u * u) / 2.0 - 0.918938533204672741780) - log_cdf)
+            f, df = f + log_cdf, df + ratio * du_dx
+        return f, df

@@ -153,7 +153,13 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     returned is the winner's own, with no re-pricing step.  Another acquisition, ``constraints``, ``hyper_samples``,
     ``batch_size`` and a cost table ``cost_structure`` does not recognise raise ``ValueError`` before any device call.
     ``"batch"`` (default) is the reference's one scalar per batch: nothing changes.
+    ``acquisition="LOGCEI"`` with ``constraints``: the constrained acquisition in log space, ``log EI + sum
+    log PoF - log cost`` (``ConstrainedLogExpectedImprovement / Cost``, ``cbo_acq_sweep_constrained_log``) -- finite and
+    ordered where ``EI * prod PoF`` is an exact 0.  An empty list scores ``"LOGEI"``'s bits; ``constraints=None``,
+    ``hyper_samples``, ``batch_size``, ``cost_mode="pointwise"`` and ``anchors="uniform"`` raise ``ValueError`` before any
+    device call.
     """
+    checked_log_cei((acquisition, None), constraints, hyper_samples, batch_size, cost_mode=cost_mode, anchors=anchors)
     if checked_pointwise_cost(cost_mode, (acquisition, None), constraints, hyper_samples, batch_size):
         from .cost_functions import PointwiseCost
         quotient = _acquisition_for(acquisition, model, current_global_best, task, space) / \
@@ -195,7 +201,7 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
             raise ValueError("batch selection is not defined for constrained acquisitions: constraints must be None")
         if anchors != "grid":
             raise ValueError("batch selection picks from the grid: anchors must be 'grid'")
-    if acquisition not in ("EI", "MES", LOG_EI) + POINTWISE_ACQUISITIONS:
+    if acquisition not in ("EI", "MES", LOG_EI, LOG_CEI) + POINTWISE_ACQUISITIONS:
         raise ValueError(f"acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR', not {acquisition!r}")
     if acquisition == "MES":
         if task != "min":
@@ -203,8 +209,9 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
         if anchors != "grid":
             raise ValueError("acquisition='MES' has no gradients: anchors must be 'grid'")
     if constraints is not None:
-        if acquisition != "EI":
-            raise ValueError("constraints multiply the causal EI: acquisition must be 'EI'")
+        if acquisition not in ("EI", LOG_CEI):
+            raise ValueError("constraints multiply the causal EI: acquisition must be 'EI' (or 'LOGCEI', the sum of the "
+                             "logarithms)")
         if anchors != "grid":
             raise ValueError("constraints are scored over the grid: anchors must be 'grid'")
     cost_acquisition = Cost(costs_functions, evaluated_set)
@@ -216,8 +223,10 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
         return acquisition.evaluate(x_new), x_new
     ei = _acquisition_for(acquisition, model, current_global_best, task, space)
     if constraints:
-        from .constrained import AcquisitionProduct
-        ei = AcquisitionProduct([ei] + list(constraints))      # the sets of the constraints' models follow the grid's
+        from .constrained import AcquisitionProduct, ConstrainedLogExpectedImprovement
+        # the sets of the constraints' models follow the grid's
+        ei = (ConstrainedLogExpectedImprovement(ei, constraints) if acquisition == LOG_CEI
+              else AcquisitionProduct([ei] + list(constraints)))
     if hyper_samples is not None:
         from .integrated_hyper import IntegratedHyperParameterAcquisition
         generator = lambda mdl: CausalExpectedImprovement(current_global_best, task, mdl)      # noqa: E731
@@ -256,6 +265,7 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
 
 POINTWISE_ACQUISITIONS = ("LCB", "PI", "MPEI", "VAR")
 LOG_EI = "LOGEI"      # the log Expected Improvement: a name of its own, routed to the cbo_acq_*_logei calls
+LOG_CEI = "LOGCEI"    # log EI + sum log PoF - log cost: routed by name to the cbo_acq_*_constrained_log calls
 
 
 def _acquisition_for(name, model, current_global_best, task, space, param=None):
@@ -264,7 +274,7 @@ def _acquisition_for(name, model, current_global_best, task, space, param=None):
     if name == "MES":
         from .max_value_entropy import MaxValueEntropySearch
         return MaxValueEntropySearch(model, space)
-    if name == LOG_EI:
+    if name in (LOG_EI, LOG_CEI):                  # (LOGCEI's objective; its constraints are the caller's to add)
         from .pointwise_acquisitions import CausalLogExpectedImprovement
         return CausalLogExpectedImprovement(current_global_best, task, model, 0.0 if param is None else param)
     if name in POINTWISE_ACQUISITIONS:
@@ -284,8 +294,9 @@ def sets_acquisition(acquisition="EI", acquisition_param=None):
     """(name, parameter) of the acquisition a multi-set sweep scores with, checked on the host before any device call:
     ``"EI"`` (no parameter: today's call, ``None``), ``"LCB"`` (beta, default 1, finite and not negative), ``"PI"`` and
     ``"MPEI"`` (the jitter, default 0, finite), ``"LOGEI"`` (the log Expected Improvement of DESIGN.md §4x: the jitter, as
-    PI's), ``"VAR"`` (no parameter: 0 travels), ``"MES"`` with a pair of ints
-    ``(num_samples, grid_size)``, ``num_samples`` in 1..64, ``grid_size`` at least 1 (the parameter returned is that pair).
+    PI's), ``"LOGCEI"`` (its constrained form, DESIGN.md §4aa: the log EI's jitter, checked as LOGEI's), ``"VAR"`` (no
+    parameter: 0 travels), ``"MES"`` with a pair of ints ``(num_samples, grid_size)``, ``num_samples`` in 1..64,
+    ``grid_size`` at least 1 (the parameter returned is that pair).
     Anything else raises ``ValueError`` -- a bare ``"MES"`` too: this function never answered for it and has no default for
     it; ``sets_acquisition_or_default`` -- what ``find_next_y_points``, ``CBOAcquisitionPath`` and ``CBO`` call -- puts
     emukit's defaults (10 samples, a Gumbel grid of 5000) in the place of a ``None`` first.
@@ -295,7 +306,7 @@ def sets_acquisition(acquisition="EI", acquisition_param=None):
         name, param = acquisition                 # an earlier answer of this function (a path keeps its own): checked again
         sets_acquisition(name, None if name in ("EI", "VAR") else param)
         return acquisition
-    if not isinstance(acquisition, str) or acquisition not in ("EI", "MES", LOG_EI) + POINTWISE_ACQUISITIONS:
+    if not isinstance(acquisition, str) or acquisition not in ("EI", "MES", LOG_EI, LOG_CEI) + POINTWISE_ACQUISITIONS:
         raise ValueError("acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR' in a multi-set sweep, "
                          f"not {acquisition!r}")
     if acquisition == "MES":
@@ -420,10 +431,17 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     winner's value being its own ``EI / c(x)`` with no re-pricing -- and, with ``refine=True``, refined with the cost's own
     gradient (``refine_sets(cost_mode="pointwise")``).  Another acquisition, non-empty ``constraints``, ``hyper_samples``,
     ``batch_size``, ``device_prior=True``, ``raw=True`` and a cost ``cost_structure`` does not recognise raise ``ValueError``
-    before any device call.  ``"batch"`` (default) takes exactly today's calls."""
+    before any device call.  ``"batch"`` (default) takes exactly today's calls.
+    ``acquisition="LOGCEI"`` with ``acquisition_param`` (the log EI's jitter, default 0) and ``constraints``:
+    every set is scored with ``log EI + sum log PoF - log cost`` in the same one call
+    (``cbo_acq_sweep_sets_constrained_log``) -- per set what ``find_next_y_point(acquisition="LOGCEI", constraints=[...])``
+    returns; a set with an empty list scores ``"LOGEI"``'s bits.  ``constraints=None``, ``hyper_samples``, ``batch_size``,
+    ``refine=True``, ``device_prior=True``, ``cost_mode="pointwise"`` and ``raw=True`` raise ``ValueError`` before any device
+    call."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    checked_log_cei(kind, constraints, hyper_samples, batch_size, refine, device_prior, raw, cost_mode)
     if checked_pointwise_cost(cost_mode, kind, constraints, hyper_samples, batch_size, device_prior, raw):
         checked_refine(refine, kind, None, None, None, False, spaces, len(models))
         return _next_y_points_pointwise(models, current_global_best, evaluated_sets, costs_functions, task, grids, kind,
@@ -493,7 +511,7 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
                                                         _lib.dptr(batch_cost), _lib.dptr(vals),
                                                         idxs.ctypes.data_as(_lib.c_int64_p)))
     elif constraints is not None:
-        _sweep_sets_constrained(st, models, grids, constraints, task)
+        _sweep_sets_constrained(st, models, grids, constraints, task, kind)
     elif kind[0] == "MES":
         from .max_value_entropy import mes_sets_parameters
         st.pop("trial_args", None)               # (a trial step with MES takes the three-call route)
@@ -505,7 +523,7 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
         _lib.check(_lib.load().cbo_acq_sweep_sets_mes(s, st["gps"], st["cds"], st["mes_args"][0], st["mes_args"][1],
                                                       _lib.dptr(batch_cost), _lib.dptr(vals),
                                                       idxs.ctypes.data_as(_lib.c_int64_p)))
-    elif kind[0] == LOG_EI:
+    elif kind[0] in (LOG_EI, LOG_CEI):           # (LOGCEI whose every list is empty: LOGEI's call, LOGEI's bits)
         st.pop("trial_args", None)               # (a trial step with the log EI takes the three-call route)
         _lib.check(_lib.load().cbo_acq_sweep_sets_logei(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task],
                                                         kind[1], _lib.dptr(batch_cost), _lib.dptr(vals),
@@ -597,6 +615,33 @@ def _next_y_points_pointwise(models, current_global_best, evaluated_sets, costs_
             if fs[best] >= ys[i][0, 0]:
                 xs[i], ys[i] = pts[best][None, :].copy(), np.array([[fs[best]]])
     return xs, ys
+
+
+def checked_log_cei(kind, constraints, hyper_samples=None, batch_size=None, refine=False, device_prior=False, raw=False,
+                    cost_mode="batch", anchors="grid"):
+    """What the constrained acquisition in log space (``"LOGCEI"``) does not combine with, checked on the
+    host before any device call: it needs ``constraints`` (possibly empty lists) and is scored over the grid, once, with
+    one cost per set, by a single process."""
+    if kind[0] != LOG_CEI:
+        return
+    what = "acquisition='LOGCEI'"
+    if constraints is None:
+        raise ValueError(f"{what} sums the logarithms of the constraints' probabilities: constraints must be given "
+                         "(without constraints the acquisition is 'LOGEI')")
+    if hyper_samples is not None:
+        raise ValueError(f"{what} is not defined for the marginalised EI: hyper_samples must be None")
+    if batch_size is not None:
+        raise ValueError(f"{what} is not defined for batches: batch_size must be None")
+    if refine:
+        raise ValueError(f"{what} has no refinement kernel: refine must be False")
+    if device_prior:
+        raise ValueError(f"{what} has no refinement kernel: device_prior must be False")
+    if cost_mode != "batch":
+        raise ValueError(f"{what} takes one cost per set: cost_mode must be 'batch', not {cost_mode!r}")
+    if anchors != "grid":
+        raise ValueError(f"{what} is scored over the grid: anchors must be 'grid'")
+    if raw:
+        raise ValueError(f"{what} is not defined across several ranks (raw=True)")
 
 
 def checked_device_prior(device_prior, refine):
@@ -762,8 +807,9 @@ def checked_set_constraints(constraints, n_sets, kind=("EI", None), raw=False):
         raise ValueError(f"constraints must have one entry per exploration set ({n_sets}), not {len(constraints)}")
     if not any(constraints):
         return None
-    if kind[0] != "EI":
-        raise ValueError("constraints multiply the causal EI: acquisition must be 'EI'")
+    if kind[0] not in ("EI", LOG_CEI):
+        raise ValueError("constraints multiply the causal EI: acquisition must be 'EI' (or 'LOGCEI', the sum of the "
+                         "logarithms)")
     if raw:
         raise ValueError("constraints are not defined across several ranks (raw=True)")
     for i, cons in enumerate(constraints):
@@ -782,9 +828,10 @@ def checked_set_constraints(constraints, n_sets, kind=("EI", None), raw=False):
     return constraints
 
 
-def _sweep_sets_constrained(st, models, grids, constraints, task):
+def _sweep_sets_constrained(st, models, grids, constraints, task, kind=("EI", None)):
     """The constrained form of ``find_next_y_points``' device call: the constraint models' candidate grids from the cache
-    entry ``st`` (rebuilt where a model object changed), then ``cbo_acq_sweep_sets_constrained`` into ``st``'s winners."""
+    entry ``st`` (rebuilt where a model object changed), then ``cbo_acq_sweep_sets_constrained`` -- for ``kind``
+    ``("LOGCEI", jitter)`` ``cbo_acq_sweep_sets_constrained_log`` -- into ``st``'s winners."""
     import ctypes
     from .. import _lib
     from .causal_acquisition_functions import CandidateGrid
@@ -817,8 +864,11 @@ def _sweep_sets_constrained(st, models, grids, constraints, task):
             values.append(float(c.max_value)); jitters.append(float(c.jitter)); senses.append(SENSE_CODE[c.sense])
     n = len(con_gps)
     n_con = (ctypes.c_int * len(models))(*[len(cons) for cons in constraints])
-    _lib.check(_lib.load().cbo_acq_sweep_sets_constrained(
-        len(models), st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0, _lib.dptr(st["batch_cost"]),
+    log_form = kind[0] == LOG_CEI
+    call = _lib.load().cbo_acq_sweep_sets_constrained_log if log_form else _lib.load().cbo_acq_sweep_sets_constrained
+    _lib.check(call(
+        len(models), st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task],
+        float(kind[1]) if log_form else 0.0, _lib.dptr(st["batch_cost"]),
         n_con, (ctypes.c_void_p * n)(*con_gps), (ctypes.c_void_p * n)(*con_cds), _lib.dptr(np.array(values)),
         _lib.dptr(np.array(jitters)), (ctypes.c_int * n)(*senses), _lib.dptr(st["vals"]),
         st["idxs"].ctypes.data_as(_lib.c_int64_p)))
@@ -845,9 +895,13 @@ def winners_to_points(st, models, grids, current_global_best, task):
             generator = lambda mdl, c=costs[i]: CausalExpectedImprovement(current_global_best, task, mdl) / c   # noqa: E731
             y = IntegratedHyperParameterAcquisition(models[i], generator, samples=hyper_rows[i]).evaluate(x_new)
         elif constraints is not None and constraints[i]:
-            from .constrained import AcquisitionProduct
-            ei = CausalExpectedImprovement(current_global_best, task, models[i])
-            y = (AcquisitionProduct([ei] + list(constraints[i])) / costs[i]).evaluate(x_new)
+            from .constrained import AcquisitionProduct, ConstrainedLogExpectedImprovement
+            if name == LOG_CEI:
+                log_ei = _acquisition_for(name, models[i], current_global_best, task, None, param)
+                y = (ConstrainedLogExpectedImprovement(log_ei, constraints[i]) / costs[i]).evaluate(x_new)
+            else:
+                ei = CausalExpectedImprovement(current_global_best, task, models[i])
+                y = (AcquisitionProduct([ei] + list(constraints[i])) / costs[i]).evaluate(x_new)
         elif name == "MES":
             # the set's own draw: a fresh MaxValueEntropySearch would refit the Gumbel and draw again
             from .max_value_entropy import MaxValueEntropySearch

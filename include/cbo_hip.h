@@ -300,6 +300,22 @@ int cbo_acq_sweep_constrained(cbo_gp *gp, cbo_cands *cands, double y_best, int t
                               double *acq_out, double *ei_out, double *pof_out /* n_con * m, constraint-major */,
                               double *best_val, int64_t *best_idx);
 
+/* The constrained acquisition in log space: cbo_acq_sweep_constrained's argument list, ei_out and pof_out
+ * becoming logei_out and logpof_out, ei_jitter the log EI's jitter:
+ *     acq_out[i] = (((logEI_i + l_0i) + l_1i) + ...) - log(cost)                    (additions left to right, log(cost) once)
+ * logEI_i is what cbo_acq_sweep_logei(gp, cands, y_best, task, ei_jitter, 1.0, ...) writes to acq_out[i] -- task 'max' its
+ * mirror, the improvement of a maximiser, not the product form's -EI -- and l_ki = log_ndtr(u_ki) with u_ki the very
+ * argument whose ndtr cbo_acq_sweep_constrained multiplies in.  Finite and ordered where EI, a probability or their
+ * product is an exact 0.  Contracts: n_con = 0 gives cbo_acq_sweep_logei's acq_out, best_val and best_idx bit for bit for
+ * every cost; logei_out is its acq_out at cost 1; per-candidate outputs do not change the values; the arg-max is
+ * numpy.argmax(acq_out) + index_offset (lowest index on ties, NaN maximal, -inf an ordinary value).
+ * Errors are cbo_acq_sweep_constrained's, and with an objective a non-finite ei_jitter or y_best. */
+int cbo_acq_sweep_constrained_log(cbo_gp *gp, cbo_cands *cands, double y_best, int task, double ei_jitter, double cost,
+                                  int n_con, cbo_gp *const *con_gps, cbo_cands *const *con_cands,
+                                  const double *con_value, const double *con_jitter, const int *con_sense,
+                                  double *acq_out, double *logei_out, double *logpof_out /* n_con * m, constraint-major */,
+                                  double *best_val, int64_t *best_idx);
+
 /* The causal EI over a cost, marginalised over hyper-parameter samples, with the arg-max -- emukit's
  * IntegratedHyperParameterAcquisition(model, acquisition_generator, n_samples) around ExpectedImprovement / Cost, whose
  * evaluate() is `for sample in samples: model.fix_model_hyperparameters(sample); acquisition_value += acquisition.evaluate(x)`
@@ -690,6 +706,17 @@ int cbo_acq_sweep_sets_constrained(int n_sets, cbo_gp *const *gps, cbo_cands *co
                                    double ei_jitter, const double *costs, const int *n_con, cbo_gp *const *con_gps,
                                    cbo_cands *const *con_cands, const double *con_value, const double *con_jitter,
                                    const int *con_sense, double *best_vals, int64_t *best_idxs);
+
+/* cbo_acq_sweep_sets_constrained in log space: the same argument list, the same routing (the one launch is
+ * small_sets_con_kernel's log instantiation, the running sum in a register; the general path ends in
+ * cbo_acq_sweep_constrained_log), the same untouched models.  Contract: for every set, best_vals[i] and best_idxs[i] are
+ * bit for bit what cbo_acq_sweep_constrained_log returns for the set on freshly fitted twins.  Errors are the sibling's,
+ * and a non-finite ei_jitter or y_best[i], refused with the other scalars before any handle is looked at. */
+int cbo_acq_sweep_sets_constrained_log(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best,
+                                       int task, double ei_jitter, const double *costs, const int *n_con,
+                                       cbo_gp *const *con_gps, cbo_cands *const *con_cands, const double *con_value,
+                                       const double *con_jitter, const int *con_sense, double *best_vals,
+                                       int64_t *best_idxs);
 
 /* cbo_acq_sweep_sets for the marginalised EI of cbo_acq_sweep_hyper: set i is (gps[i], cands[i]) with its
  * own n_samples[i] in 1..CBO_MAX_HYPER_SAMPLES rows hyper[i] of (variance, lengthscale x L_i, noise_var), cbo_acq_sweep_hyper's
