@@ -114,6 +114,10 @@ class CBOAcquisitionPath:
     picks in one device call (``find_next_y_points(batch_size=B)``): ``xs[s]`` is (B, d), ``ys[s]`` (B, 1); the
     set is chosen by pick 0, as before.  It needs ``acquisition="EI"``, no constraints, no hyper-parameter samples and a
     single process, and its ``trial_step`` takes the three-call route.
+    ``refine_constrained=True`` (with ``constraints`` and ``acquisition`` ``"EI"`` or ``"LOGCEI"``): every set's
+    constrained winner is refined by L-BFGS on the constrained acquisition inside the set's box from ``space_list``
+    (``find_next_y_points(refine_constrained=True)``), all sets in one further device call, single process; ``trial_step``
+    takes the multi-call route, as it does under constraints anyway.  ``refine=True`` with constraints keeps raising.
     ``refine=True`` adds the reference's second stage (``find_next_y_points(refine=True)``): every set's
     winner is refined by L-BFGS inside the set's box from ``space_list``, all sets in one further device call, and kept only
     if it is not lower.  It needs ``"EI"`` or a point-wise kind, no constraints, no hyper-parameter samples, no batch and a
@@ -131,11 +135,12 @@ class CBOAcquisitionPath:
                  var_functions=None, grid_shapes=None, keep_solutions=True, comm="env", acquisition="EI",
                  acquisition_param=None, constraints=None, constraint_data_y=None, hyper_samples=None, batch_size=None,
                  update_incumbent=False, refine=False, hyper_sampler="host", device_prior=False, mle_optimizer="host",
-                 mle_restarts=1, hyper_priors=None, cost_mode="batch", mle_device_rows=128):
+                 mle_restarts=1, hyper_priors=None, cost_mode="batch", mle_device_rows=128, refine_constrained=False):
         from .GaussianProcessFactory import checked_mle_device_rows, checked_mle_optimizer
         from .utils_functions.priors import checked_priors
         from .utils_functions.utils import (checked_device_prior, checked_log_cei, checked_log_ei, checked_pointwise_cost,
-                                            checked_refine, sets_acquisition_or_default as sets_acquisition)
+                                            checked_refine, checked_refine_constrained,
+                                            sets_acquisition_or_default as sets_acquisition)
         self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
         self.mle_device_rows = checked_mle_device_rows(mle_device_rows, mle_optimizer)
         self.device_prior = checked_device_prior(device_prior, refine)
@@ -164,6 +169,10 @@ class CBOAcquisitionPath:
         self.update_incumbent = bool(update_incumbent)
         self.refine = checked_refine(refine, self._kind, self.constraints, self.hyper_samples, self.batch_size, False,
                                      space_list, len(exploration_set))
+        # the constrained winners' second stage: off by default, refine=True with constraints keeps raising
+        self.refine_constrained = checked_refine_constrained(
+            refine_constrained, self._kind, [self.constraints] * len(exploration_set) if self.constraints else None,
+            hyper_samples, batch_size, False, space_list, len(exploration_set), device_prior, cost_mode)
         # "batch": the reference's one scalar per grid; "pointwise" (DESIGN.md §4y): every candidate over its own cost
         self.cost_mode = "pointwise" if checked_pointwise_cost(cost_mode, self._kind, self.constraints, self.hyper_samples,
                                                                self.batch_size, self.device_prior) else "batch"
@@ -341,7 +350,7 @@ class CBOAcquisitionPath:
             raise ValueError(f"max-value entropy search is scored by a single process: the placement is {mode!r}")
         if self.batch_size is not None and mode != "single":
             raise ValueError(f"batch selection is scored by a single process: the placement is {mode!r}")
-        if self.refine and mode != "single":
+        if (self.refine or self.refine_constrained) and mode != "single":
             raise ValueError(f"gradient refinement is run by a single process: the placement is {mode!r}")
         if self._kind[0] == "LOGEI" and mode != "single":
             raise ValueError(f"the log Expected Improvement is scored by a single process: the placement is {mode!r}")
@@ -352,9 +361,11 @@ class CBOAcquisitionPath:
             return find_next_y_points(self.models, current_best, self.exploration_set, self.costs, self.task, grids,
                                       cache=self._call_cache, acquisition=self._kind, constraints=self.set_constraints(),
                                       hyper_samples=None if self.hyper_samples is None else list(self.hyper_rows),
-                                      spaces=self.space_list if (self._kind[0] == "MES" or self.refine) else None,
+                                      spaces=self.space_list if (self._kind[0] == "MES" or self.refine
+                                                                 or self.refine_constrained) else None,
                                       batch_size=self.batch_size, update_incumbent=self.update_incumbent,
-                                      refine=self.refine, device_prior=self.device_prior, cost_mode=self.cost_mode)
+                                      refine=self.refine, device_prior=self.device_prior, cost_mode=self.cost_mode,
+                                      refine_constrained=self.refine_constrained)
         from .sharding import ERROR_CANDIDATE, NO_CANDIDATE
         from .utils_functions.cost_functions import Cost
         # A rank that fails (a model that is not positive definite, a device error) must not leave the others blocked in
@@ -530,6 +541,8 @@ class CBO(CBOAcquisitionPath):
     the chosen set side by side: the monitor evaluates the B rows, appends them in order and records
     ``chosen`` as ``(set, x (B, d))``; the trial's cost is the sum of the B interventions' costs.  ``None``: the reference's
     one intervention per trial.
+    ``refine_constrained=True`` (with ``constraints``): the constrained winners are refined likewise, on the constrained
+    acquisition (``CBOAcquisitionPath(refine_constrained=True)``).
     ``refine=True``: every set's winner is refined by L-BFGS inside the set's interventional ranges before the set is chosen
     (``CBOAcquisitionPath(refine=True)``) -- the reference's continuous optimum instead of a grid point.
     ``device_prior=True`` (with ``refine=True`` and ``causal_prior=True``): the causal sets are refined inside the device launch,
@@ -553,7 +566,7 @@ class CBO(CBOAcquisitionPath):
                  lockstep=True, verbose=False, acquisition="EI", acquisition_param=None, constraints=None,
                  constraint_functions=None, hyper_samples=None, batch_size=None, update_incumbent=False, refine=False,
                  hyper_sampler="host", device_prior=False, mle_optimizer="host", mle_restarts=1, hyper_priors=None,
-                 cost_mode="batch", mle_device_rows=128):
+                 cost_mode="batch", mle_device_rows=128, refine_constrained=False):
         from .DoCalculus import DoCalculus
         from .GaussianProcessFactory import GaussianProcessType, checked_mle_device_rows, checked_mle_optimizer
         checked_mle_device_rows(mle_device_rows, checked_mle_optimizer(mle_optimizer, mle_restarts))
@@ -608,6 +621,11 @@ class CBO(CBOAcquisitionPath):
                        False, [self.graph.bounds(s) for s in exploration], len(exploration))
         if device_prior and not refine:
             raise ValueError("device_prior=True puts causal sets into the refinement's device launch: refine must be True")
+        from .utils_functions.utils import checked_refine_constrained
+        checked_refine_constrained(refine_constrained, sets_acquisition(acquisition, acquisition_param),
+                                   [path_constraints] * len(exploration) if path_constraints else None, hyper_samples,
+                                   batch_size, False, [self.graph.bounds(s) for s in exploration], len(exploration), device_prior,
+                                   cost_mode)
         from .utils_functions.utils import checked_log_ei
         checked_log_ei(sets_acquisition(acquisition, acquisition_param), device_prior)
         from .utils_functions.utils import checked_pointwise_cost
@@ -630,7 +648,8 @@ class CBO(CBOAcquisitionPath):
                          constraint_data_y=constraint_data_y, hyper_samples=hyper_samples, batch_size=batch_size,
                          update_incumbent=update_incumbent, refine=refine, hyper_sampler=hyper_sampler,
                          device_prior=device_prior, mle_optimizer=mle_optimizer, mle_restarts=mle_restarts,
-                         hyper_priors=hyper_priors, cost_mode=cost_mode, mle_device_rows=mle_device_rows)
+                         hyper_priors=hyper_priors, cost_mode=cost_mode, mle_device_rows=mle_device_rows,
+                         refine_constrained=refine_constrained)
         if target_functions is None:
             from functools import partial
             from .utils_functions.graph_functions import compute_interventions

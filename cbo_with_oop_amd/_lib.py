@@ -208,6 +208,11 @@ SIGNATURES = {
     "cbo_acq_refine_sets_pointcost": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), ctypes.c_int,
                                                      c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p,
                                                      c_double_p, c_double_p, c_int_p, c_int_p]),
+    # gradient refinement under constraints
+    "cbo_acq_refine_sets_constrained": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), ctypes.c_int,
+                                                       c_double_p, ctypes.c_int, ctypes.c_double, c_int_p, c_void_pp,
+                                                       c_double_p, c_double_p, c_int_p, ctypes.c_int, c_double_p, c_double_p,
+                                                       c_double_p, c_int_p, c_int_p]),
     "cbo_gp_append": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                      c_int_p]),
     "cbo_gp_append_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,

@@ -177,6 +177,7 @@ struct cbo_ctx {
     PinnedBuf<double> refine_starts, refine_x, refine_grad, refine_val;
     PinnedBuf<int> refine_rounds, refine_status;
     GrowBuf<int> refine_info;
+    PinnedBuf<cbo_small_refine_pair> refine_pair_host;  // cbo_acq_refine_sets_constrained: every model's own lengthscales
     // cbo_gp_hmc_sets: the chains' descriptors and draws as the kernel reads them, rows, accept flags, final states and
     // status words as it writes them (all pinned)
     PinnedBuf<cbo_small_hmc> hmc_host;
@@ -2838,6 +2839,51 @@ struct cbo_do_prior {
     DoPriorView *view = nullptr;     // the same view on the device
 };
 
+// the rows of one set of a refinement launch from the context's pinned buffers to the caller's arrays: a set one of whose
+// starts the kernel left declined (a non-positive pivot) is declined whole, its status entries alone written
+static void harvest_refined(const cbo_ctx *c, const cbo_small_refine &rf, int d, double *x_out, double *val_out,
+                            double *grad_out, int *rounds_out, int *status_out)
+{
+    bool declined = false;
+    for (int s = 0; s < rf.k; ++s) declined = declined || c->refine_status[rf.out_off + s] == CBO_REFINE_DECLINED;
+    for (int s = 0; s < rf.k; ++s) {
+        status_out[rf.out_off + s] = declined ? CBO_REFINE_DECLINED : c->refine_status[rf.out_off + s];
+        if (declined) continue;
+        rounds_out[rf.out_off + s] = c->refine_rounds[rf.out_off + s];
+        val_out[rf.out_off + s] = c->refine_val[rf.out_off + s];
+        std::memcpy(x_out + rf.row_off + (int64_t)s * d, c->refine_x.p + rf.row_off + (int64_t)s * d, sizeof(double) * (size_t)d);
+        std::memcpy(grad_out + rf.row_off + (int64_t)s * d, c->refine_grad.p + rf.row_off + (int64_t)s * d, sizeof(double) * (size_t)d);
+    }
+}
+
+// one set's handle, box, cost table and starts as every refinement entry point checks them, before anything is touched
+static int check_refine_set(cbo_gp *const *gps, const cbo_refine_set *sets, int i)
+{
+    const std::string where = " (set " + std::to_string(i) + ")";
+    const cbo_refine_set &rs = sets[i];
+    if (!gps[i]) return fail(CBO_ERR_INVALID, "NULL gp" + where);
+    if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
+    if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data" + where);
+    if (rs.k < 1 || rs.k > CBO_REFINE_MAX_STARTS)
+        return fail(CBO_ERR_INVALID, "the number of starts must be in 1.." + std::to_string(CBO_REFINE_MAX_STARTS) + where);
+    if (!rs.starts || !rs.lo || !rs.hi || !rs.cost_fix || !rs.cost_variable)
+        return fail(CBO_ERR_INVALID, "NULL argument: starts, lo, hi, cost_fix and cost_variable must be given" + where);
+    const int d = gps[i]->d;
+    double fix_sum = 0.0;
+    for (int k = 0; k < d; ++k) {
+        if (!std::isfinite(rs.lo[k]) || !std::isfinite(rs.hi[k])) return fail(CBO_ERR_INVALID, "the bounds must be finite" + where);
+        if (rs.lo[k] > rs.hi[k]) return fail(CBO_ERR_INVALID, "a lower bound exceeds its upper bound" + where);
+        if (!std::isfinite(rs.cost_fix[k])) return fail(CBO_ERR_INVALID, "the fixed costs must be finite" + where);
+        if (rs.cost_variable[k] != 0 && rs.cost_variable[k] != 1)
+            return fail(CBO_ERR_INVALID, "cost_variable must be 0 or 1" + where);
+        fix_sum += rs.cost_fix[k];
+    }
+    if (!(fix_sum > 0.0)) return fail(CBO_ERR_INVALID, "the fixed costs must sum to a positive cost" + where);
+    for (int64_t e = 0; e < (int64_t)rs.k * d; ++e)
+        if (!std::isfinite(rs.starts[e])) return fail(CBO_ERR_INVALID, "the starts must be finite" + where);
+    return CBO_OK;
+}
+
 // ---- gradient refinement of every set's starts (kernels_sets_refine.hip) -----------------------------------
 // One launch for every set the kernel takes (small_sweep_model, no prior); the others are declined here, their status
 // entries alone written.  The models are only read.  Of the routing policy this call shares the partition alone: it has no
@@ -2868,27 +2914,9 @@ static int refine_sets_impl(int n_sets, cbo_gp *const *gps, const cbo_refine_set
     }
     for (int i = 0; i < n_sets; ++i) {
         const std::string where = " (set " + std::to_string(i) + ")";
-        const cbo_refine_set &rs = sets[i];
-        if (!gps[i]) return fail(CBO_ERR_INVALID, "NULL gp" + where);
-        if (gps[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "all sets must live on one context");
-        if (gps[i]->n <= 0 || gps[i]->n_pad <= 0) return fail(CBO_ERR_INVALID, "a gp holds no data" + where);
-        if (rs.k < 1 || rs.k > CBO_REFINE_MAX_STARTS)
-            return fail(CBO_ERR_INVALID, "the number of starts must be in 1.." + std::to_string(CBO_REFINE_MAX_STARTS) + where);
-        if (!rs.starts || !rs.lo || !rs.hi || !rs.cost_fix || !rs.cost_variable)
-            return fail(CBO_ERR_INVALID, "NULL argument: starts, lo, hi, cost_fix and cost_variable must be given" + where);
+        const int rc = check_refine_set(gps, sets, i);
+        if (rc != CBO_OK) return rc;
         const int d = gps[i]->d;
-        double fix_sum = 0.0;
-        for (int k = 0; k < d; ++k) {
-            if (!std::isfinite(rs.lo[k]) || !std::isfinite(rs.hi[k])) return fail(CBO_ERR_INVALID, "the bounds must be finite" + where);
-            if (rs.lo[k] > rs.hi[k]) return fail(CBO_ERR_INVALID, "a lower bound exceeds its upper bound" + where);
-            if (!std::isfinite(rs.cost_fix[k])) return fail(CBO_ERR_INVALID, "the fixed costs must be finite" + where);
-            if (rs.cost_variable[k] != 0 && rs.cost_variable[k] != 1)
-                return fail(CBO_ERR_INVALID, "cost_variable must be 0 or 1" + where);
-            fix_sum += rs.cost_fix[k];
-        }
-        if (!(fix_sum > 0.0)) return fail(CBO_ERR_INVALID, "the fixed costs must sum to a positive cost" + where);
-        for (int64_t e = 0; e < (int64_t)rs.k * d; ++e)
-            if (!std::isfinite(rs.starts[e])) return fail(CBO_ERR_INVALID, "the starts must be finite" + where);
         if (kind == kEiKind && !std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite" + where);
         if (priors && priors[i]) {
             if (priors[i]->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "a prior lives on another context" + where);
@@ -2976,21 +3004,8 @@ static int refine_sets_impl(int n_sets, cbo_gp *const *gps, const cbo_refine_set
                                  c->refine_rounds, c->refine_status);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int j = 0; j < ns; ++j) {
-        const int i = small[(size_t)j];
-        const cbo_small_refine &rf = c->refine_host[j];
-        const int d = gps[i]->d;
-        bool declined = false;
-        for (int s = 0; s < rf.k; ++s) declined = declined || c->refine_status[rf.out_off + s] == CBO_REFINE_DECLINED;
-        for (int s = 0; s < rf.k; ++s) {
-            status_out[rf.out_off + s] = declined ? CBO_REFINE_DECLINED : c->refine_status[rf.out_off + s];
-            if (declined) continue;
-            rounds_out[rf.out_off + s] = c->refine_rounds[rf.out_off + s];
-            val_out[rf.out_off + s] = c->refine_val[rf.out_off + s];
-            std::memcpy(x_out + rf.row_off + (int64_t)s * d, c->refine_x.p + rf.row_off + (int64_t)s * d, sizeof(double) * (size_t)d);
-            std::memcpy(grad_out + rf.row_off + (int64_t)s * d, c->refine_grad.p + rf.row_off + (int64_t)s * d, sizeof(double) * (size_t)d);
-        }
-    }
+    for (int j = 0; j < ns; ++j)
+        harvest_refined(c, c->refine_host[j], gps[small[(size_t)j]]->d, x_out, val_out, grad_out, rounds_out, status_out);
     return CBO_OK;
 }
 
@@ -3037,6 +3052,195 @@ extern "C" int cbo_acq_refine_sets_prior(int n_sets, cbo_gp *const *gps, const c
 {
     return refine_sets_impl(n_sets, gps, sets, priors, kind, y_best, task, param, max_rounds, x_out, val_out, grad_out,
                             rounds_out, status_out);
+}
+
+// ---- gradient refinement of every set's CONSTRAINED acquisition (kernels_sets_refine_con.hip) ---------------
+// The sets without constraints take cbo_acq_refine_sets' / _logei's own route (refine_sets_impl on the sub-list: their
+// bits); the sets with constraints go to one launch of small_sets_refine_con_kernel on the same stream -- those all of
+// whose 1 + n_con[i] models are fp64, non-causal and of at most 128 observations; the others are declined, as is a set one
+// of whose models meets a non-positive pivot in the launch.  No general path inside the call; the models are only read.
+extern "C" int cbo_acq_refine_sets_constrained(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int log_form,
+                                               const double *y_best, int task, double ei_jitter, const int *n_con,
+                                               cbo_gp *const *con_gps, const double *con_value, const double *con_jitter,
+                                               const int *con_sense, int max_rounds, double *x_out, double *val_out,
+                                               double *grad_out, int *rounds_out, int *status_out)
+{
+    // what needs no handle first
+    if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
+    if (log_form != 0 && log_form != 1) return fail(CBO_ERR_INVALID, "log_form must be 0 or 1");
+    if (!gps || !sets || !y_best || !n_con || !x_out || !val_out || !grad_out || !rounds_out || !status_out)
+        return fail(CBO_ERR_INVALID, "NULL argument");
+    if (max_rounds < 0 || max_rounds > CBO_REFINE_ROUNDS_LIMIT)
+        return fail(CBO_ERR_INVALID, "max_rounds must be in 0.." + std::to_string(CBO_REFINE_ROUNDS_LIMIT));
+    if (task != CBO_TASK_MIN && task != CBO_TASK_MAX) return fail(CBO_ERR_INVALID, "task must be 0 (min) or 1 (max)");
+    if (!std::isfinite(ei_jitter)) return fail(CBO_ERR_INVALID, "the jitter must be finite");
+    std::vector<int64_t> first((size_t)n_sets + 1, 0);       // set i's constraints: [first[i], first[i + 1])
+    for (int i = 0; i < n_sets; ++i) {
+        if (!std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite (set " + std::to_string(i) + ")");
+        if (n_con[i] < 0 || n_con[i] > CBO_MAX_CONSTRAINTS)
+            return fail(CBO_ERR_INVALID, "n_con of set " + std::to_string(i) + " must be in 0.." +
+                                             std::to_string(CBO_MAX_CONSTRAINTS));
+        first[(size_t)i + 1] = first[(size_t)i] + n_con[i];
+    }
+    const int64_t total_con = first[(size_t)n_sets];
+    if (total_con > 0) {
+        if (!con_gps) return fail(CBO_ERR_INVALID, "con_gps is NULL with constraints");
+        if (!con_value) return fail(CBO_ERR_INVALID, "con_value is NULL with constraints");
+        if (!con_jitter) return fail(CBO_ERR_INVALID, "con_jitter is NULL with constraints");
+        if (!con_sense) return fail(CBO_ERR_INVALID, "con_sense is NULL with constraints");
+        for (int64_t j = 0; j < total_con; ++j) {
+            if (!std::isfinite(con_value[j])) return fail(CBO_ERR_INVALID, "con_value must be finite");
+            if (!std::isfinite(con_jitter[j])) return fail(CBO_ERR_INVALID, "con_jitter must be finite");
+            if (con_sense[j] != CBO_CON_LE && con_sense[j] != CBO_CON_GE)
+                return fail(CBO_ERR_INVALID, "con_sense must be CBO_CON_LE or CBO_CON_GE");
+        }
+    }
+    // the handles
+    for (int i = 0; i < n_sets; ++i) {
+        const int rc = check_refine_set(gps, sets, i);
+        if (rc != CBO_OK) return rc;
+        const std::string where = " (set " + std::to_string(i) + ")";
+        for (int64_t j = first[(size_t)i]; j < first[(size_t)i + 1]; ++j) {
+            const cbo_gp *g = con_gps[j];
+            if (!g) return fail(CBO_ERR_INVALID, "NULL constraint gp" + where);
+            if (g->ctx != gps[0]->ctx) return fail(CBO_ERR_INVALID, "a constraint model lives on another context" + where);
+            if (g->n <= 0 || g->n_pad <= 0) return fail(CBO_ERR_INVALID, "a constraint gp holds no data" + where);
+            if (g->d != gps[i]->d)
+                return fail(CBO_ERR_INVALID, "a constraint model's d (" + std::to_string(g->d) + ") differs from the set's (" +
+                                                 std::to_string(gps[i]->d) + ")" + where);
+        }
+    }
+    cbo_ctx *c = gps[0]->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int64_t> row_off((size_t)n_sets);
+    std::vector<int> out_off((size_t)n_sets);
+    int64_t rows = 0;
+    int outs = 0;
+    for (int i = 0; i < n_sets; ++i) {
+        row_off[(size_t)i] = rows;
+        out_off[(size_t)i] = outs;
+        rows += (int64_t)sets[i].k * gps[i]->d;
+        outs += sets[i].k;
+    }
+
+    // ---- the sets without constraints: the existing launch on their sub-list, its outputs put where the caller's rows are
+    std::vector<int> plain;
+    for (int i = 0; i < n_sets; ++i)
+        if (n_con[i] == 0) plain.push_back(i);
+    if (!plain.empty()) {
+        const size_t np = plain.size();
+        std::vector<cbo_gp *> pg(np);
+        std::vector<cbo_refine_set> ps(np);
+        std::vector<double> py(np);
+        int64_t prows = 0;
+        int pouts = 0;
+        for (size_t a = 0; a < np; ++a) {
+            const int i = plain[a];
+            pg[a] = gps[i]; ps[a] = sets[i]; py[a] = y_best[i];
+            prows += (int64_t)sets[i].k * gps[i]->d;
+            pouts += sets[i].k;
+        }
+        std::vector<double> px((size_t)prows), pgr((size_t)prows), pv((size_t)pouts);
+        std::vector<int> pr((size_t)pouts), pst((size_t)pouts);
+        const int rc = refine_sets_impl((int)np, pg.data(), ps.data(), nullptr, log_form ? kLogEiKind : kEiKind, py.data(), task,
+                                        ei_jitter, max_rounds, px.data(), pv.data(), pgr.data(), pr.data(), pst.data(),
+                                        log_form != 0);
+        if (rc != CBO_OK) return rc;
+        int64_t r0 = 0;
+        int o0 = 0;
+        for (size_t a = 0; a < np; ++a) {
+            const int i = plain[a], k = sets[i].k, d = gps[i]->d;
+            std::copy_n(pst.data() + o0, k, status_out + out_off[(size_t)i]);
+            if (pst[(size_t)o0] != CBO_REFINE_DECLINED) {        // (a declined set's other entries are not written)
+                std::copy_n(px.data() + r0, (size_t)k * d, x_out + row_off[(size_t)i]);
+                std::copy_n(pgr.data() + r0, (size_t)k * d, grad_out + row_off[(size_t)i]);
+                std::copy_n(pv.data() + o0, k, val_out + out_off[(size_t)i]);
+                std::copy_n(pr.data() + o0, k, rounds_out + out_off[(size_t)i]);
+            }
+            r0 += (int64_t)k * d;
+            o0 += k;
+        }
+    }
+
+    // ---- the sets with constraints: which of them the launch takes, and the widest of those
+    std::vector<int> small;
+    const int blocks = partition_small(n_sets, [&](int i) {
+        if (n_con[i] == 0) return false;
+        bool ok = small_sweep_model(gps[i]) && gps[i]->X.sv == nullptr;
+        for (int64_t j = first[(size_t)i]; ok && j < first[(size_t)i + 1]; ++j)
+            ok = small_sweep_model(con_gps[j]) && con_gps[j]->X.sv == nullptr;
+        return ok;
+    }, [&](int i) {
+        const int per = small_refine_starts_per_block(gps[i]->d);
+        return (int64_t)((sets[i].k + per - 1) / per);
+    }, small);
+    const int ns = (int)small.size();
+    for (int i = 0, j = 0; i < n_sets; ++i) {
+        if (j < ns && small[(size_t)j] == i) ++j;
+        else if (n_con[i] > 0) std::fill_n(status_out + out_off[(size_t)i], sets[i].k, (int)CBO_REFINE_DECLINED);
+    }
+    if (small.empty()) return CBO_OK;
+    int n_pairs = 0, slots = 1;
+    for (int i : small) {
+        n_pairs += 1 + n_con[i];
+        if (1 + n_con[i] > slots) slots = 1 + n_con[i];
+    }
+    // descriptors for every pair, a search record and a status word per set, scratch per workgroup, the pinned rows
+    int rc = ensure_small_buffers(c, n_pairs, 1);
+    const size_t cap = ns < 32 ? (size_t)32 : (size_t)ns;
+    if (rc == CBO_OK) rc = grow(c, c->small_scratch, small_refine_con_scratch_doubles(ns, blocks, slots));
+    if (rc == CBO_OK) rc = grow(c, c->refine_pair_host, n_pairs < 32 ? (size_t)32 : (size_t)n_pairs);
+    if (rc == CBO_OK) rc = grow(c, c->refine_host, cap);
+    if (rc == CBO_OK) rc = grow(c, c->refine_info, cap);
+    if (rc == CBO_OK) rc = grow(c, c->refine_starts, (size_t)rows);
+    if (rc == CBO_OK) rc = grow(c, c->refine_x, (size_t)rows);
+    if (rc == CBO_OK) rc = grow(c, c->refine_grad, (size_t)rows);
+    if (rc == CBO_OK) rc = grow(c, c->refine_val, (size_t)outs);
+    if (rc == CBO_OK) rc = grow(c, c->refine_rounds, (size_t)outs);
+    if (rc == CBO_OK) rc = grow(c, c->refine_status, (size_t)outs);
+    if (rc != CBO_OK) return rc;
+    int p = 0;
+    std::vector<int> first_pair((size_t)ns, 0);
+    for (int j = 0; j < ns; ++j) {
+        const int i = small[(size_t)j];
+        first_pair[(size_t)j] = p;
+        for (int a = 0; a <= n_con[i]; ++a, ++p) {
+            const int64_t cj = first[(size_t)i] + a - 1;
+            const cbo_gp *g = a == 0 ? gps[i] : con_gps[cj];
+            cbo_small_set &st = c->sets_host[p];
+            fill_small_model(st, g);
+            st.cxs = st.csq = st.csv = st.cpm = st.cpv = nullptr;
+            st.cld = 0; st.m = 0; st.index_offset = 0;
+            // (a constraint's sense, value and jitter ride in task, y_best and ei_jitter)
+            st.task = a == 0 ? task : con_sense[cj];
+            st.y_best = a == 0 ? y_best[i] : con_value[cj];
+            st.ei_jitter = a == 0 ? ei_jitter : con_jitter[cj];
+            st.cost = 1.0;                                     // (the kernel prices every point itself)
+            for (int k = 0; k < CBO_MAX_DIM; ++k) c->refine_pair_host[p].ls[k] = (k < g->d && g->h.ard) ? g->ls[(size_t)k] : 1.0;
+        }
+        cbo_small_refine &rf = c->refine_host[j];
+        std::memset(&rf, 0, sizeof(rf));
+        const int d = gps[i]->d;
+        for (int k = 0; k < d; ++k) {
+            rf.lo[k] = sets[i].lo[k]; rf.hi[k] = sets[i].hi[k];
+            rf.fix[k] = sets[i].cost_fix[k]; rf.variable[k] = sets[i].cost_variable[k];
+            rf.ls[k] = 1.0;                                    // (every model's own are in refine_pair_host)
+        }
+        rf.row_off = row_off[(size_t)i]; rf.out_off = out_off[(size_t)i];
+        rf.k = sets[i].k;
+        std::memcpy(c->refine_starts.p + rf.row_off, sets[i].starts, sizeof(double) * (size_t)rf.k * (size_t)d);
+        for (int s = 0; s < rf.k; ++s) c->refine_status[rf.out_off + s] = CBO_REFINE_DECLINED;
+    }
+    for (int j = 0; j < ns; ++j) c->sets_host[j].pad_ = first_pair[(size_t)j];      // the table: set j's first pair
+    HIP_TRY(hipMemsetAsync(c->refine_info, 0, sizeof(int) * (size_t)ns, c->stream));
+    launch_small_sets_refine_con(c->stream, log_form != 0, c->sets_host, c->refine_pair_host, n_pairs, c->refine_host,
+                                 c->refine_starts, ns, blocks, slots, c->small_scratch, c->refine_info, max_rounds, c->refine_x,
+                                 c->refine_val, c->refine_grad, c->refine_rounds, c->refine_status);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int j = 0; j < ns; ++j)
+        harvest_refined(c, c->refine_host[j], gps[small[(size_t)j]]->d, x_out, val_out, grad_out, rounds_out, status_out);
+    return CBO_OK;
 }
 
 // ---- constrained acquisition for every set of a trial (kernels_sets_con.hip) ------------------------------

@@ -285,6 +285,51 @@ __device__ __forceinline__ double log_ndtr(double a)
     return log1p(-(c / 2.0));
 }
 
+// log_ndtr(a) and the hazard ratio rho(a) = phi(a) / Phi(a) = d log_ndtr / d a beside it (the gradient of a
+// log feasibility).  The value is log_ndtr's, operation for operation.  rho is never an underflowed density over an
+// underflowed distribution: above -1 it is the plain ratio (the density's exponential shared with cephes ndtr, as
+// acquisition_of has it; Phi >= 0.158 there), below it is sqrt(2 / pi) / erfcx(-a / sqrt 2) from the erfcx the value forms
+// anyway -- exp(-a^2 / 2) cancels analytically.  A NaN argument gives NaN twice.
+// Inlined here; its one caller in a kernel (constraint_term of kernels_sets_refine_con.hip) is the function that is NOT
+// inlined, for log_ei_value_and_coefficients' reason (kernels_sets_refine.hip) -- a second call level below that one would
+// make it a non-leaf function, whose saved return address costs 16 bytes of scratch memory per lane.
+struct LogNdtrRatio {
+    double value, rho;
+};
+__device__ __forceinline__ LogNdtrRatio log_ndtr_and_ratio(double a)
+{
+#pragma clang fp contract(off)
+    const double SQRTH = 7.07106781186547524401E-1, MAXLOG = 7.09782712893383996843E2, SQRT_2_OVER_PI = 0.797884560802865355880;
+    const double t = a * SQRTH;
+    double p, q;
+    if (a < -1.0) {
+        const double y = -t;                           // > 1 / sqrt 2
+        double erfcx;
+        if (y < 1.0) {
+            erfcx = exp(y * y) * (1.0 - cephes_erf_small(y));
+        } else {
+            if (y < 8.0) cephes_erfc_pq(y, p, q);
+            else cephes_erfc_rs(y, p, q);
+            erfcx = p / q;
+        }
+        return LogNdtrRatio{log(erfcx / 2.0) - t * t, SQRT_2_OVER_PI / erfcx};
+    }
+    const double e = exp_nonpositive(-(a * a) / 2.0);
+    const double rho = (e * 0.3989422804014327) / ndtr_with_exp(a, e);
+    const double z = fabs(t);
+    double c;
+    if (z < 1.0) {
+        c = 1.0 - cephes_erf_small(t);
+    } else if (z * z > MAXLOG) {
+        c = 0.0;                                       // (t >= 1 here: erfc underflows)
+    } else {
+        if (z < 8.0) cephes_erfc_pq(z, p, q);
+        else cephes_erfc_rs(z, p, q);
+        c = (exp(-(z * z)) * p) / q;
+    }
+    return LogNdtrRatio{log1p(-(c / 2.0)), rho};
+}
+
 // (va, ia) beats (vb, ib): larger value, NaN maximal (numpy.argmax), lowest index on ties
 __device__ __forceinline__ bool better(double va, int64_t ia, double vb, int64_t ib)
 {
@@ -516,6 +561,24 @@ __device__ __forceinline__ double log_feasibility_of(double mean, double var, do
     if (__builtin_expect(special, 0)) u = a / s;                    // (a zero or infinite variance: the IEEE quotient)
     if (sense != CBO_CON_LE) u = -u;                                // (uniform)
     return log_ndtr(u);
+}
+// ... with what its gradient needs: sd, the oriented u and rho(u) = phi(u) / Phi(u) -- d log PoF =
+// rho(u) du, du = -+(d mean + u_le d sd) / sd.  The value is log_feasibility_of's to the bit.
+__device__ __forceinline__ double log_feasibility_of(double mean, double var, double value, double jitter, int sense,
+                                                     double &s, double &u, double &rho)
+{
+#pragma clang fp contract(off)
+    double rs;
+    bool special;
+    sqrt_and_reciprocal(var, s, rs, special);
+    const double a = value - (mean + jitter);
+    u = a * rs;
+    u = fma(fma(-u, s, a), rs, u);
+    if (__builtin_expect(special, 0)) u = a / s;                    // (a zero or infinite variance: the IEEE quotient)
+    if (sense != CBO_CON_LE) u = -u;                                // (uniform)
+    const LogNdtrRatio r = log_ndtr_and_ratio(u);
+    rho = r.rho;
+    return r.value;
 }
 
 // ---- max-value entropy search: the epilogue of mes_acq_kernel (kernels_mes.hip) and of small_sets_kernel<kMesKind>

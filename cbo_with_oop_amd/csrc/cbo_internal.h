@@ -397,6 +397,24 @@ int small_refine_starts_per_block(int d);              // 4 floor(16 / (1 + d)):
 void launch_small_sets_refine(hipStream_t s, int kind, bool prior, const cbo_small_set *sets, const cbo_small_refine *refs,
                               const double *starts, int n_sets, int blocks_per_set, double *scratch, int *info, int max_rounds,
                               double *x_out, double *val_out, double *grad_out, int *rounds_out, int *status_out);
+// ---- ... of every set's CONSTRAINED acquisition (kernels_sets_refine_con.hip) --------------------------------
+// A set is 1 + n_con consecutive descriptors of `pairs`, the objective first (launch_small_sets_con's convention: set s's
+// first descriptor rides in pairs[s].pad_; a constraint's value, jitter and sense in y_best, ei_jitter and task; no
+// candidates); pair_ls[p] holds descriptor p's per-dimension lengthscales (read when its model is ARD); refs[s] the set's box,
+// cost table, starts and offsets (ls, ard and prior are not read).  Every model of a set has the set's d; none is causal.
+// slots: the most models a set of the launch has.  scratch: small_refine_con_scratch_doubles(n_sets, blocks_per_set, slots)
+// -- per workgroup `slots` factor slots of kSmallScratch doubles, then the rings of its at most 32 starts.  info, the
+// outputs and max_rounds as for launch_small_sets_refine.
+struct cbo_small_refine_pair {
+    double ls[CBO_MAX_DIM];
+};
+constexpr int kRefineConRing = 64;                     // doubles of one ring (8 curvature pairs of at most CBO_MAX_DIM)
+constexpr int kRefineConRings = 32 * 2 * kRefineConRing;   // a workgroup's: 32 starts (d = 1), S and Y each
+size_t small_refine_con_scratch_doubles(int n_sets, int blocks_per_set, int slots);
+void launch_small_sets_refine_con(hipStream_t s, bool log_form, const cbo_small_set *pairs, const cbo_small_refine_pair *pair_ls,
+                                  int n_pairs, const cbo_small_refine *refs, const double *starts, int n_sets,
+                                  int blocks_per_set, int slots, double *scratch, int *info, int max_rounds, double *x_out,
+                                  double *val_out, double *grad_out, int *rounds_out, int *status_out);
 // ---- the device-resident do-calculus prior (kernels_do_prior.hip, do_prior_device.h) ------------------------
 constexpr int kDoPriorMaxN = CBO_DO_PRIOR_MAX_N;   // rows of a graph GP a handle takes
 constexpr int kDoPriorGroup = 256;                 // lanes that evaluate one point together: a whole workgroup

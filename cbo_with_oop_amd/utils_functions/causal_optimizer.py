@@ -127,8 +127,10 @@ class CausalGradientAcquisitionOptimizer:
                 starts = pts[top[np.argsort(-acq[top], kind="stable")]]
             else:
                 starts = x
+            cons = _product_constraints(_numerator(acquisition))
             (xs, fs, status), = refine_sets([model], [starts], [self.bounds], y_best, task, [cost], kind=kind,
-                                            host_fallback=False, device_prior=device_prior, cost_mode=cost_mode)
+                                            host_fallback=False, device_prior=device_prior, cost_mode=cost_mode,
+                                            constraints=None if cons is None else [cons])
             if status[0] == _lib.REFINE_DECLINED:
                 raise ValueError("device=True: the device launch declined the set (its model is not positive definite "
                                  "without jitter, or the one-workgroup kernels are switched off with CBO_HIP_SMALL_SETS=0)")
@@ -297,10 +299,28 @@ def _device_refinable(acquisition, device_prior=False):
     ``ValueError`` says why another cannot."""
     from .causal_acquisition_functions import CausalExpectedImprovement
     from . import pointwise_acquisitions as pw
+    from .constrained import ConstrainedLogExpectedImprovement
     from .cost_functions import Cost
     num, cost = getattr(acquisition, "numerator", None), getattr(acquisition, "denominator", None)
     if num is None or not isinstance(cost, Cost):
         raise ValueError("device=True refines acquisition / Cost(...): the acquisition must be such a quotient")
+    cons = _product_constraints(num)
+    if cons is not None:                             # (DESIGN.md §4ab: the constrained launch; the objective names the form)
+        if device_prior:
+            raise ValueError("device=True: constraints are not refined with a device-resident prior: device_prior must be False")
+        obj = num.objective
+        if isinstance(num, ConstrainedLogExpectedImprovement):
+            y_best, task, param = obj._scalars()
+            kind = ("LOGCEI", param)
+        else:
+            kind = ("EI", float(obj.jitter) if obj.jitter != 0.0 else None)
+            y_best, task = float(np.asarray(obj.current_global_min, dtype=np.float64).reshape(-1)[0]), obj.task
+        why = _not_eligible(obj.model, cost)
+        for c in cons:
+            why = why or _constraint_not_eligible(obj.model, c.model)
+        if why:
+            raise ValueError(f"device=True: {why}")
+        return kind, obj.model, y_best, task, cost
     if type(num) is CausalExpectedImprovement:
         kind = ("EI", None)
         if num.jitter != 0.0:
@@ -315,6 +335,15 @@ def _device_refinable(acquisition, device_prior=False):
     if why:
         raise ValueError(f"device=True: {why}")
     return kind, num.model, y_best, task, cost
+
+
+def _product_constraints(numerator):
+    """The ``ProbabilityOfFeasibility`` factors of a numerator the constrained launch refines -- an ``AcquisitionProduct`` with
+    an objective, or a ``ConstrainedLogExpectedImprovement`` -- else ``None``."""
+    from .constrained import AcquisitionProduct
+    if isinstance(numerator, AcquisitionProduct) and numerator.objective is not None:
+        return list(numerator.constraints)
+    return None
 
 
 def _not_eligible(model, cost, device_prior=False):
@@ -349,23 +378,7 @@ def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, ta
     if not dev:
         return
     n = len(dev)
-    structs = [cost_structure(costs[i]) for i in dev]
-    for i, (fix, _) in zip(dev, structs):
-        if not fix.sum() > 0.0:
-            raise ValueError(f"refine_sets: the fixed costs of set {i} must sum to a positive cost")
-    sets = (_lib.CboRefineSet * n)()
-    for j, i in enumerate(dev):
-        fix, variable = structs[j]
-        sets[j].k = X0[i].shape[0]
-        sets[j].starts = X0[i].ctypes.data_as(_lib.c_double_p)
-        sets[j].lo = los[i].ctypes.data_as(_lib.c_double_p)
-        sets[j].hi = his[i].ctypes.data_as(_lib.c_double_p)
-        sets[j].cost_fix = fix.ctypes.data_as(_lib.c_double_p)
-        sets[j].cost_variable = variable.ctypes.data_as(_lib.c_int_p)
-    rows = sum(X0[i].size for i in dev)
-    total = sum(X0[i].shape[0] for i in dev)
-    x_out, g_out, v_out = np.zeros(rows), np.zeros(rows), np.zeros(total)
-    rounds, status = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32)
+    sets, structs, (x_out, v_out, g_out, rounds, status) = _refine_call_arrays(dev, X0, los, his, costs)
     gps = (ctypes.c_void_p * n)(*[models[i]._handle for i in dev])
     yb = np.full(n, y_best)
     if pointwise:                                    # (the gradient carries the cost's own derivative)
@@ -389,6 +402,34 @@ def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, ta
         _lib.check(_lib.load().cbo_acq_refine_sets_prior(n, gps, sets, handles, *outs))
     else:
         _lib.check(_lib.load().cbo_acq_refine_sets(n, gps, sets, *outs))
+    _refine_call_harvest(dev, X0, x_out, v_out, status, out)
+
+
+def _refine_call_arrays(dev, X0, los, his, costs):
+    """The ``cbo_refine_set`` array of the sets ``dev``, the cost tables it points into (kept alive by the caller) and the
+    five output arrays of a refinement call, laid out as the library lays them out."""
+    n = len(dev)
+    structs = [cost_structure(costs[i]) for i in dev]
+    for i, (fix, _) in zip(dev, structs):
+        if not fix.sum() > 0.0:
+            raise ValueError(f"refine_sets: the fixed costs of set {i} must sum to a positive cost")
+    sets = (_lib.CboRefineSet * n)()
+    for j, i in enumerate(dev):
+        fix, variable = structs[j]
+        sets[j].k = X0[i].shape[0]
+        sets[j].starts = X0[i].ctypes.data_as(_lib.c_double_p)
+        sets[j].lo = los[i].ctypes.data_as(_lib.c_double_p)
+        sets[j].hi = his[i].ctypes.data_as(_lib.c_double_p)
+        sets[j].cost_fix = fix.ctypes.data_as(_lib.c_double_p)
+        sets[j].cost_variable = variable.ctypes.data_as(_lib.c_int_p)
+    rows = sum(X0[i].size for i in dev)
+    total = sum(X0[i].shape[0] for i in dev)
+    return sets, structs, (np.zeros(rows), np.zeros(total), np.zeros(rows), np.zeros(total, dtype=np.int32),
+                           np.zeros(total, dtype=np.int32))
+
+
+def _refine_call_harvest(dev, X0, x_out, v_out, status, out):
+    """``out[i]`` of every set of ``dev`` the launch took, from the call's flat output arrays."""
     r0 = o0 = 0
     for i in dev:
         k, d = X0[i].shape
@@ -398,8 +439,88 @@ def _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, ta
         o0 += k
 
 
+def _checked_refine_constraints(constraints, n_sets, kind, device_prior, cost_mode):
+    """``refine_sets``' ``constraints``, checked on the host before any device call: per set a list of at most 8
+    ``ProbabilityOfFeasibility`` under the product form (``"EI"``) or the log form (``"LOGCEI"``) alone, with one cost per
+    point from the sets' tables and no device-resident prior."""
+    from .constrained import MAX_CONSTRAINTS, ProbabilityOfFeasibility
+    if kind[0] == "LOGCEI" and constraints is None:
+        raise ValueError("refine_sets: kind 'LOGCEI' sums the logarithms of the constraints' probabilities: constraints must "
+                         "be given (without constraints the kind is 'LOGEI')")
+    if constraints is None:
+        return None
+    if kind[0] not in ("EI", "LOGCEI"):
+        raise ValueError("refine_sets: constraints multiply the causal EI: kind must be ('EI', jitter or None) or "
+                         f"('LOGCEI', jitter), not {kind[0]!r}")
+    if device_prior:
+        raise ValueError("refine_sets: constraints are not refined with a device-resident prior: device_prior must be False")
+    if cost_mode != "batch":
+        raise ValueError("refine_sets: constraints are refined with the reference's zero cost gradient: cost_mode must be "
+                         f"'batch', not {cost_mode!r}")
+    if not hasattr(constraints, "__len__") or len(constraints) != n_sets:
+        raise ValueError(f"refine_sets: constraints must have one list per exploration set ({n_sets})")
+    checked = []
+    for i, cons in enumerate(constraints):
+        cons = list(cons or [])
+        if len(cons) > MAX_CONSTRAINTS:
+            raise ValueError(f"refine_sets: at most {MAX_CONSTRAINTS} constraints per set, not {len(cons)} (set {i})")
+        for c in cons:
+            if not isinstance(c, ProbabilityOfFeasibility):
+                raise ValueError(f"refine_sets: a constraint must be a ProbabilityOfFeasibility, not {type(c).__name__} "
+                                 f"(set {i})")
+        checked.append(cons)
+    return checked
+
+
+def _constrained_acquisition(kind, model, current_global_best, task, cost, cons):
+    """The host acquisition of a constrained set: ``AcquisitionProduct([EI] + cons) / cost`` or
+    ``ConstrainedLogExpectedImprovement(log EI, cons) / cost`` -- what the device launch climbs."""
+    from .causal_acquisition_functions import CausalExpectedImprovement
+    from .constrained import AcquisitionProduct, ConstrainedLogExpectedImprovement
+    jitter = 0.0 if kind[1] is None else float(kind[1])
+    if kind[0] == "LOGCEI":
+        from .pointwise_acquisitions import CausalLogExpectedImprovement
+        return ConstrainedLogExpectedImprovement(CausalLogExpectedImprovement(current_global_best, task, model, jitter),
+                                                 cons) / cost
+    return AcquisitionProduct([CausalExpectedImprovement(current_global_best, task, model, jitter)] + list(cons)) / cost
+
+
+def _constraint_not_eligible(model, con_model):
+    """Why the constrained launch does not take a set with this constraint model, or None when it does."""
+    if getattr(con_model, "causal", False):
+        return "a causal constraint model's prior closures are Python"
+    if not getattr(con_model, "small", False):
+        return "a constraint model has more than 128 observations or is fp32"
+    if con_model.input_dim != model.input_dim:
+        return "a constraint model's input dimension differs from the set's"
+    return None
+
+
+def _refine_constrained_on_device(dev, models, cons, X0, los, his, costs, kind, y_best, task, param, max_rounds, out):
+    """``refine_sets``' one library call for the sets ``dev`` under constraints (``cbo_acq_refine_sets_constrained``, DESIGN.md
+    §4ab): fills ``out[i]`` of every set the launch took."""
+    import ctypes
+    from .constrained import SENSE_CODE
+    if not dev:
+        return
+    n = len(dev)
+    sets, structs, (x_out, v_out, g_out, rounds, status) = _refine_call_arrays(dev, X0, los, his, costs)
+    gps = (ctypes.c_void_p * n)(*[models[i]._handle for i in dev])
+    flat = [c for i in dev for c in cons[i]]
+    n_con = (ctypes.c_int * n)(*[len(cons[i]) for i in dev])
+    con_gps = (ctypes.c_void_p * max(len(flat), 1))(*[c.model._handle for c in flat])
+    values = np.array([float(c.max_value) for c in flat] or [0.0])
+    jitters = np.array([float(c.jitter) for c in flat] or [0.0])
+    senses = (ctypes.c_int * max(len(flat), 1))(*[SENSE_CODE[c.sense] for c in flat])
+    _lib.check(_lib.load().cbo_acq_refine_sets_constrained(
+        n, gps, sets, int(kind[0] == "LOGCEI"), _lib.dptr(np.full(n, y_best)), _lib.TASK_CODE[task], param, n_con, con_gps,
+        _lib.dptr(values), _lib.dptr(jitters), senses, max_rounds, _lib.dptr(x_out), _lib.dptr(v_out), _lib.dptr(g_out),
+        rounds.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p)))
+    _refine_call_harvest(dev, X0, x_out, v_out, status, out)
+
+
 def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=("EI", None), max_rounds=200,
-                host_fallback=True, device_prior=False, cost_mode="batch"):
+                host_fallback=True, device_prior=False, cost_mode="batch", constraints=None):
     """The reference's second stage (causal_optimizer.py:59-65) for every exploration set at once: from every row of
     ``starts[s]`` ((k_s, d_s), 1 <= k_s <= 64) a projected L-BFGS ascent of ``acquisition / Cost`` inside ``bounds[s]``
     (``lockstep_lbfgs``'s iteration), returning per set ``(points (k_s, d_s), values (k_s,), status (k_s,) int)``.
@@ -423,7 +544,14 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
     ``cost_mode="pointwise"`` (``("EI", ...)`` and ``("LOGEI", ...)`` alone, no ``device_prior``): the same
     values with the TRUE gradient of ``EI / c`` or ``log EI - log c`` -- ``d c / d x_k = variable_k sign(x_k)`` -- through
     ``cbo_acq_refine_sets_pointcost``; the sets the launch does not take go through ``refine_batched`` with
-    ``acquisition / PointwiseCost``, the same gradient on the host.  Every cost must be one ``cost_structure`` recognises."""
+    ``acquisition / PointwiseCost``, the same gradient on the host.  Every cost must be one ``cost_structure`` recognises.
+    ``constraints`` (per set a list of at most 8 ``ProbabilityOfFeasibility``, possibly empty) with
+    ``kind=("EI", jitter | None)`` -- ``EI prod PoF / cost`` -- or ``("LOGCEI", jitter)`` -- ``log EI + sum log PoF - log cost``:
+    the sets all of whose models are non-causal, fp64, of at most 128 observations and of the set's dimension advance inside
+    one launch of ``cbo_acq_refine_sets_constrained`` (a set with an empty list inside the unconstrained launch of the same
+    call); every other set, and every set the launch declines, goes through ``refine_batched`` with ``AcquisitionProduct([...])
+    / cost`` or ``ConstrainedLogExpectedImprovement(...) / cost``.  Another kind, ``device_prior=True`` and
+    ``cost_mode="pointwise"`` raise ``ValueError`` with constraints, as does ``"LOGCEI"`` without them."""
     import ctypes
     import math
     from .utils import checked_log_ei, checked_pointwise_cost, sets_acquisition
@@ -439,12 +567,13 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
     else:
         kind = sets_acquisition(kind[0], None if kind[0] in ("EI", "VAR") else kind[1])
     checked_log_ei(kind, device_prior)
+    s = len(models)
+    constraints = _checked_refine_constraints(constraints, s, kind, device_prior, cost_mode)
     pointwise = checked_pointwise_cost(cost_mode, kind, device_prior=device_prior)
     if pointwise:
         from .cost_functions import PointwiseCost
         costs = [c if isinstance(c, PointwiseCost) else PointwiseCost(getattr(c, "costs_functions", None) or {},
                                                                       getattr(c, "evaluated_set", ())) for c in costs]
-    s = len(models)
     if not (len(starts) == len(bounds) == len(costs) == s) or s == 0:
         raise ValueError("refine_sets: models, starts, bounds and costs must have one entry per exploration set")
     if task not in _lib.TASK_CODE:
@@ -485,7 +614,12 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
                     priors.pop(i).close()
                 dev.remove(i)                  # (unsupported graph GP: today's route)
     try:
-        _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, task, param, max_rounds, out, pointwise)
+        if constraints is not None:
+            dev = [i for i in dev if all(_constraint_not_eligible(models[i], c.model) is None for c in constraints[i])]
+            _refine_constrained_on_device(dev, models, constraints, X0, los, his, costs, kind, y_best, task, param, max_rounds,
+                                          out)
+        else:
+            _refine_on_device(dev, priors, models, X0, los, his, costs, kind, y_best, task, param, max_rounds, out, pointwise)
     finally:
         for p in priors.values():
             p.close()
@@ -494,7 +628,8 @@ def refine_sets(models, starts, bounds, current_global_best, task, costs, kind=(
         if out[i] is None and not host_fallback:
             out[i] = (X0[i].copy(), np.full(X0[i].shape[0], np.nan), np.full(X0[i].shape[0], _lib.REFINE_DECLINED, dtype=np.int32))
         if out[i] is None:
-            acq = _acquisition_of_kind(kind, models[i], current_global_best, task, costs[i])
+            acq = (_acquisition_of_kind(kind, models[i], current_global_best, task, costs[i]) if constraints is None else
+                   _constrained_acquisition(kind, models[i], current_global_best, task, costs[i], constraints[i]))
             x, f = CausalGradientAcquisitionOptimizer(list(zip(los[i].tolist(), his[i].tolist()))).refine_batched(
                 acq, X0[i], max_rounds=max_rounds)
             out[i] = (x, f, np.full(X0[i].shape[0], _lib.REFINE_DECLINED, dtype=np.int32))

@@ -263,6 +263,19 @@ class ConstrainedLogExpectedImprovement(AcquisitionProduct):
         u = (float(max_value) - (np.asarray(mean, dtype=np.float64) + jitter)) / np.asarray(sd, dtype=np.float64)
         return scipy.special.log_ndtr(u if sense == "<=" else -u)
 
+    @staticmethod
+    def hazard_ratio(u):
+        """``pdf(u) / cdf(u) = d log_ndtr / du`` as the device forms it for the refinement under constraints (DESIGN.md §4ab,
+        ``log_ndtr_and_ratio``), in numpy / scipy: the plain ratio above ``u = -1``; below, ``sqrt(2 / pi) / erfcx(-u / sqrt
+        2)`` -- ``exp(-u^2 / 2)`` cancels analytically, so nothing underflows down to ``u = -1e300``."""
+        import scipy.special
+        u = np.asarray(u, dtype=np.float64)
+        low = u < -1.0
+        safe_low, safe_high = np.where(low, u, -2.0), np.where(low, 0.0, u)
+        below = 0.797884560802865355880 / scipy.special.erfcx(-safe_low * 7.07106781186547524401E-1)
+        above = (np.exp(-(safe_high * safe_high) / 2.0) * 0.3989422804014327) / scipy.special.ndtr(safe_high)
+        return np.where(np.isnan(u), np.nan, np.where(low, below, above))
+
     def evaluate_with_gradients(self, x):
         """(value (M,1), gradient (M,d)) on the host: the log EI's own gradient plus, per constraint,
         ``exp(log pdf(u) - log cdf(u)) du/dx`` -- the ratio from the two logarithms, never from an underflowed ``pdf`` over

@@ -372,7 +372,8 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
 
 def find_next_y_points(models, current_global_best, evaluated_sets, costs_functions, task, grids, cache=None, raw=False,
                        acquisition="EI", acquisition_param=None, hyper_samples=None, spaces=None, batch_size=None,
-                       update_incumbent=False, refine=False, device_prior=False, cost_mode="batch", constraints=None):
+                       update_incumbent=False, refine=False, device_prior=False, cost_mode="batch", refine_constrained=False,
+                       constraints=None):
     """``find_next_y_point`` for every exploration set of a trial in ONE device call (``cbo_acq_sweep_sets``): the loop
     of src/CBO.py:249-257.  ``grids[s]`` is the CandidateGrid of set s.  Models with at most 128 observations -- all
     the reference builds -- are factored and swept inside one launch and need not be fitted; the others go through
@@ -437,10 +438,19 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     (``cbo_acq_sweep_sets_constrained_log``) -- per set what ``find_next_y_point(acquisition="LOGCEI", constraints=[...])``
     returns; a set with an empty list scores ``"LOGEI"``'s bits.  ``constraints=None``, ``hyper_samples``, ``batch_size``,
     ``refine=True``, ``device_prior=True``, ``cost_mode="pointwise"`` and ``raw=True`` raise ``ValueError`` before any device
-    call."""
+    call.
+    ``refine_constrained=True`` with ``acquisition`` ``"EI"`` or ``"LOGCEI"``, non-empty ``constraints`` and
+    ``spaces``: every set's constrained winner is the start of an L-BFGS ascent of the constrained acquisition inside the set's
+    box, all of them in one further device call (``refine_sets(constraints=...)``, ``cbo_acq_refine_sets_constrained``; sets the
+    launch does not take go through ``refine_batched``).  The refined point replaces the winner only if its value at its own
+    cost is not lower.  Another acquisition, ``constraints`` that are ``None`` or all empty, missing ``spaces``, ``raw=True``,
+    ``hyper_samples``, ``batch_size``, ``device_prior=True`` and ``cost_mode="pointwise"`` raise ``ValueError`` before any device
+    call.  ``False`` takes exactly today's calls; ``refine=True`` with constraints keeps raising."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    checked_refine_constrained(refine_constrained, kind, constraints, hyper_samples, batch_size, raw, spaces, len(models),
+                               device_prior, cost_mode)
     checked_log_cei(kind, constraints, hyper_samples, batch_size, refine, device_prior, raw, cost_mode)
     if checked_pointwise_cost(cost_mode, kind, constraints, hyper_samples, batch_size, device_prior, raw):
         checked_refine(refine, kind, None, None, None, False, spaces, len(models))
@@ -553,6 +563,8 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     xs, ys = winners_to_points(st, models, grids, current_global_best, task)
     if refine:
         xs, ys = refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind, device_prior)
+    if refine_constrained:
+        xs, ys = refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind, constraints=constraints)
     return xs, ys
 
 
@@ -685,12 +697,43 @@ def checked_refine(refine, kind, constraints=None, hyper_samples=None, batch_siz
     return True
 
 
-def refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind, device_prior=False):
+def checked_refine_constrained(refine_constrained, kind, constraints=None, hyper_samples=None, batch_size=None, raw=False,
+                               spaces=None, n_sets=None, device_prior=False, cost_mode="batch"):
+    """``refine_constrained`` of a multi-set sweep, a path or an agent, checked on the host before any device
+    call: the constrained winners are refined under the product form (``"EI"``) or the log form (``"LOGCEI"``) alone, with
+    constraints to refine under, inside the sets' boxes, one winner per set, on a single rank, with one cost per point from
+    the sets' tables and no device-resident prior."""
+    if not refine_constrained:
+        return False
+    what = "refine_constrained=True"
+    if kind[0] not in ("EI", LOG_CEI):
+        raise ValueError(f"{what} refines the constrained causal EI: acquisition must be 'EI' or 'LOGCEI', not {kind[0]!r}")
+    if constraints is None or not hasattr(constraints, "__len__") or not any(constraints):
+        raise ValueError(f"{what} refines under constraints: constraints must be given and not all empty (without "
+                         "constraints the keyword is refine)")
+    if raw:
+        raise ValueError(f"{what} is not defined across several ranks (raw=True)")
+    if hyper_samples is not None:
+        raise ValueError(f"{what} is not defined for the marginalised EI: hyper_samples must be None")
+    if batch_size is not None:
+        raise ValueError(f"{what} is not defined for batches: batch_size must be None")
+    if device_prior:
+        raise ValueError(f"{what} has no causal instantiation: device_prior must be False")
+    if cost_mode != "batch":
+        raise ValueError(f"{what} climbs with the reference's zero cost gradient: cost_mode must be 'batch', not {cost_mode!r}")
+    if spaces is None or not hasattr(spaces, "__len__") or (n_sets is not None and len(spaces) != n_sets):
+        raise ValueError(f"{what} searches inside the sets' boxes: spaces must have one entry per exploration set"
+                         + ("" if n_sets is None else f" ({n_sets})"))
+    return True
+
+
+def refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kind, device_prior=False, constraints=None):
     """``find_next_y_points(refine=True)``'s second stage: every set's winner refined by ``refine_sets``; the refined point
-    replaces it only if its value -- over the point's own cost, as ``winners_to_points`` prices the winner -- is not lower."""
+    replaces it only if its value -- over the point's own cost, as ``winners_to_points`` prices the winner -- is not lower.
+    ``constraints`` (``refine_constrained=True``): the same rule with the constrained value."""
     from .causal_optimizer import refine_sets
     res = refine_sets(models, xs, [space_bounds(sp) for sp in spaces], current_global_best, task, costs, kind=kind,
-                      device_prior=device_prior)
+                      device_prior=device_prior, constraints=constraints)
     xs, ys = list(xs), list(ys)
     for i, (pts, vals, _) in enumerate(res):
         best = int(np.argmax(vals))

@@ -851,6 +851,29 @@ int cbo_acq_refine_sets_pointcost(int n_sets, cbo_gp *const *gps, const cbo_refi
                                   const double *y_best, int task, double jitter, int max_rounds, double *x_out,
                                   double *val_out, double *grad_out, int *rounds_out, int *status_out);
 
+/* The second stage under constraints: cbo_acq_refine_sets for
+ *     log_form 0:  EI(x) prod_k PoF_k(x) / c(x)                 log_form 1:  log EI(x) + sum_k log PoF_k(x) - log c(x)
+ * -- the functions cbo_acq_sweep_sets_constrained / _constrained_log score.  Set i has n_con[i] (0..CBO_MAX_CONSTRAINTS)
+ * constraints; con_gps, con_value, con_jitter and con_sense are set-major with sum(n_con) entries, as in
+ * cbo_acq_sweep_sets_constrained, and may be NULL when every n_con[i] is 0.  Output layout and status codes are
+ * cbo_acq_refine_sets'.  The value reported at a point is, bit for bit, what the constrained multi-set sweep of the same form
+ * returns for a one-point grid there with costs[i] = c(x).  The gradient is the host classes' (AcquisitionProduct,
+ * ConstrainedLogExpectedImprovement): the product rule left to right, then over c(x) -- the reference's zero cost gradient --
+ * or d logEI + sum_k rho(u_k) d u_k, rho = pdf / cdf formed without underflow, not divided by the cost.
+ * Routing: the sets with n_con[i] = 0 take cbo_acq_refine_sets' (kind 0) or cbo_acq_refine_sets_logei's launch and return
+ * their bits; the sets with constraints go to one launch of their own on the same stream: every model of the set factored
+ * once, reloaded every round.  A set is DECLINED when one of its models is causal, has more than 128 observations or is fp32,
+ * or meets a non-positive pivot as assembled.  The models are only read: fit state, caches and kept solutions stay.
+ * CBO_ERR_INVALID, before any launch: cbo_acq_refine_sets' checks; log_form other than 0 / 1; a non-finite ei_jitter or
+ * y_best[i]; n_con[i] outside 0..CBO_MAX_CONSTRAINTS; a NULL con_* array with some n_con[i] > 0; a NULL constraint handle; a
+ * constraint model without data, on another context, or whose d differs from the set's; a non-finite con_value /
+ * con_jitter; a sense that is neither CBO_CON_LE nor CBO_CON_GE. */
+int cbo_acq_refine_sets_constrained(int n_sets, cbo_gp *const *gps, const cbo_refine_set *sets, int log_form,
+                                    const double *y_best, int task, double ei_jitter, const int *n_con,
+                                    cbo_gp *const *con_gps, const double *con_value, const double *con_jitter,
+                                    const int *con_sense, int max_rounds, double *x_out, double *val_out,
+                                    double *grad_out, int *rounds_out, int *status_out);
+
 /* The do-calculus prior of an RBF graph GP as a device-resident handle (src/DoCalculus.py:34-89).  With the
  * graph GP's inputs X_g, the observed rows O (n_obs x d_in) and the intervened columns I,
  *     a_i(x) = exp(-1/2 sum_{c in I} ((x_c - X_g[i,c]) / l_c)^2),      b_ri = the same over c not in I at O_rc,
