@@ -55,8 +55,9 @@ def checked_path_hyper_samples(hyper_samples, kind=("EI", None), constraints=())
     from . import _lib
     if hyper_samples is None:
         return None
-    if kind[0] != "EI":
-        raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI'")
+    if kind[0] not in ("EI", "LOGMEI"):
+        raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI' (or 'LOGMEI', the "
+                         "logarithm of the average)")
     if constraints:
         raise ValueError("the marginalised EI is not defined with constraints: constraints must be None")
     if callable(hyper_samples):
@@ -110,6 +111,11 @@ class CBOAcquisitionPath:
     ``hyper_sampler="device"`` (with an int ``hyper_samples``) draws them by the one-launch HMC: every set's
     rows in one ``cbo_gp_hmc_sets`` call after ``update_all_gaussian_processes``, the rebuilt set's in a one-model call;
     ``"host"`` (default) is the per-model host chain.
+    ``acquisition="LOGMEI"`` (``acquisition_param``: the log EI's jitter, default 0) with ``hyper_samples``
+    scores every set with the LOGARITHM of that marginalised EI, ``log((1 / H) sum_h EI_h) - log cost`` -- not the average of
+    the logarithms -- which stays finite and ordered where the average itself is an exact 0.0 on every grid (small models with
+    noise 1e-10, early in a run) and set 0 would win the tie.  It needs ``hyper_samples`` (either ``hyper_sampler``), no
+    constraints, no batch, no ``refine`` / ``refine_constrained`` / ``device_prior``, ``cost_mode="batch"`` and a single process.
     ``batch_size`` (an int B in 1..64) with ``update_incumbent`` makes every set's answer a greedy batch of B Kriging-believer
     picks in one device call (``find_next_y_points(batch_size=B)``): ``xs[s]`` is (B, d), ``ys[s]`` (B, 1); the
     set is chosen by pick 0, as before.  It needs ``acquisition="EI"``, no constraints, no hyper-parameter samples and a
@@ -138,11 +144,13 @@ class CBOAcquisitionPath:
                  mle_restarts=1, hyper_priors=None, cost_mode="batch", mle_device_rows=128, refine_constrained=False):
         from .GaussianProcessFactory import checked_mle_device_rows, checked_mle_optimizer
         from .utils_functions.priors import checked_priors
-        from .utils_functions.utils import (checked_device_prior, checked_log_cei, checked_log_ei, checked_pointwise_cost,
-                                            checked_refine, checked_refine_constrained,
+        from .utils_functions.utils import (checked_device_prior, checked_log_cei, checked_log_ei, checked_log_mei,
+                                            checked_pointwise_cost, checked_refine, checked_refine_constrained,
                                             sets_acquisition_or_default as sets_acquisition)
         self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
         self.mle_device_rows = checked_mle_device_rows(mle_device_rows, mle_optimizer)
+        checked_log_mei(sets_acquisition(acquisition, acquisition_param), hyper_samples, constraints or None, batch_size, refine,
+                        refine_constrained, device_prior, False, cost_mode)
         self.device_prior = checked_device_prior(device_prior, refine)
         # priors on every exploration-set model's hyper-parameters (name -> prior), or None: today's behaviour
         self.hyper_priors = checked_priors(hyper_priors) or None
@@ -352,7 +360,7 @@ class CBOAcquisitionPath:
             raise ValueError(f"batch selection is scored by a single process: the placement is {mode!r}")
         if (self.refine or self.refine_constrained) and mode != "single":
             raise ValueError(f"gradient refinement is run by a single process: the placement is {mode!r}")
-        if self._kind[0] == "LOGEI" and mode != "single":
+        if self._kind[0] in ("LOGEI", "LOGMEI") and mode != "single":
             raise ValueError(f"the log Expected Improvement is scored by a single process: the placement is {mode!r}")
         if self.cost_mode == "pointwise" and mode != "single":
             raise ValueError(f"cost_mode='pointwise' is scored by a single process: the placement is {mode!r}")
@@ -537,6 +545,9 @@ class CBO(CBOAcquisitionPath):
     with the EI marginalised over hyper-parameter samples of its model; the closing ``optimize()`` of the
     chosen set's model stays, as in the reference.  ``hyper_sampler="device"`` draws them by the one-launch HMC (DESIGN.md
     §4s), as for ``CBOAcquisitionPath``.
+    ``acquisition="LOGMEI"`` (with ``hyper_samples``) scores every set with the logarithm of that marginalised
+    EI, ``log((1 / H) sum_h EI_h) - log cost``, which still ranks the sets where the average is an exact 0.0 everywhere, as
+    for ``CBOAcquisitionPath``.
     ``batch_size`` (an int B in 1..64) with ``update_incumbent``: ``intervene()`` runs the B interventions of a greedy batch on
     the chosen set side by side: the monitor evaluates the B rows, appends them in order and records
     ``chosen`` as ``(set, x (B, d))``; the trial's cost is the sum of the B interventions' costs.  ``None``: the reference's
@@ -610,7 +621,9 @@ class CBO(CBOAcquisitionPath):
         data_y = [np.asarray(y, dtype=np.float64).reshape(-1, 1) for _, y in interventional_data]
         if len(data_x) != len(exploration):
             raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
-        from .utils_functions.utils import checked_log_cei
+        from .utils_functions.utils import checked_log_cei, checked_log_mei
+        checked_log_mei(sets_acquisition(acquisition, acquisition_param), hyper_samples, path_constraints or None, batch_size,
+                        refine, refine_constrained, device_prior, False, cost_mode)
         checked_log_cei(sets_acquisition(acquisition, acquisition_param), path_constraints or None, hyper_samples, batch_size,
                         refine, device_prior, False, cost_mode)
         path_constraints = checked_path_constraints(path_constraints, sets_acquisition(acquisition, acquisition_param))

@@ -136,6 +136,7 @@ struct cbo_ctx {
     PinnedBuf<double> hyper_host;
     PinnedBuf<HyperSet> hyper_sets_host;                        // cbo_acq_sweep_sets_hyper: one descriptor per set
     GrowBuf<double> hyper_sum;
+    GrowBuf<double> hyper_lse_s;                                // the log form's S beside hyper_sum as M
     // cbo_acq_sweep_sets_mes, cbo_gp_mes_gumbel_sets: one (offset, count) per set and the sets' Gumbel samples as the kernel
     // reads them (pinned); the grids' mean / var workspace, every set's points one after the other; the bisections' table,
     // quantiles and status words
@@ -3381,8 +3382,11 @@ extern "C" int cbo_acq_sweep_sets_constrained_log(int n_sets, cbo_gp *const *gps
 // ---- the causal EI marginalised over hyper-parameter samples (kernels_hyper.hip) -------------------------
 // The general path of cbo_acq_sweep_hyper: per sample the model's own set_hyper + fit + sweep, the acquisition kept on the
 // device and added into the running sum; then the division with the arg-max; then the model back as it was.
+// log_form: per sample cbo_acq_sweep_logei's steps at cost 1 in the place of cbo_acq_sweep's, the term pushed
+// into the streaming log-sum-exp's (M, S) = (hyper_sum, hyper_lse_s); the close subtracts log H and the log cost.
 static int hyper_general_path(cbo_gp *g, cbo_cands *k, int n_samples, int n_ls, const double *hyper, double y_best, int task,
-                              double ei_jitter, double cost, double *acq_out, double *best_val, int64_t *best_idx)
+                              double ei_jitter, double cost, double *acq_out, double *best_val, int64_t *best_idx,
+                              bool log_form = false)
 {
     cbo_ctx *c = g->ctx;
     const double variance0 = g->h.variance, noise0 = g->noise_var;
@@ -3390,6 +3394,7 @@ static int hyper_general_path(cbo_gp *g, cbo_cands *k, int n_samples, int n_ls, 
     const bool was_fitted = g->fitted;
     const int nb = acq_blocks_for(k->m);
     int rc = grow(c, c->hyper_sum, (size_t)k->m_pad);
+    if (rc == CBO_OK && log_form) rc = grow(c, c->hyper_lse_s, (size_t)k->m_pad);
     for (int h = 0; h < n_samples && rc == CBO_OK; ++h) {
         const double *row = hyper + (size_t)h * (size_t)(n_ls + 2);
         rc = cbo_gp_set_hyper(g, row[0], row + 1, row[1 + n_ls]);
@@ -3398,15 +3403,20 @@ static int hyper_general_path(cbo_gp *g, cbo_cands *k, int n_samples, int n_ls, 
         const double *q_src = nullptr, *mu_src = nullptr;
         if (rc == CBO_OK) rc = settle_vectors(g, k, false, &q_src, &mu_src);
         // (acq_out only says that the per-candidate values are wanted: they stay in the context's vector)
-        if (rc == CBO_OK) rc = enqueue_finish(g, k, y_best, task, ei_jitter, cost, c->acq, nullptr, nullptr, q_src, mu_src,
-                                              false, false);
+        if (rc == CBO_OK) rc = enqueue_finish(g, k, y_best, task, ei_jitter, log_form ? 1.0 : cost, c->acq, nullptr, nullptr,
+                                              q_src, mu_src, false, false, nullptr, log_form ? kLogEiKind : 0);
         if (rc != CBO_OK) break;
-        launch_hyper_accumulate(c->stream, c->hyper_sum, c->acq, k->m, h == 0, nb);
+        if (log_form) launch_hyper_lse_accumulate(c->stream, c->hyper_sum, c->hyper_lse_s, c->acq, k->m, h == 0, nb);
+        else launch_hyper_accumulate(c->stream, c->hyper_sum, c->acq, k->m, h == 0, nb);
         if (hipGetLastError() != hipSuccess) rc = fail(CBO_ERR_HIP, "hyper_accumulate_kernel launch");
     }
     if (rc == CBO_OK) {
-        launch_hyper_finish(c->stream, c->hyper_sum, k->m, n_samples, acq_out ? c->acq.p : nullptr, c->part_val, c->part_idx,
-                            k->index_offset, nb);
+        if (log_form)
+            launch_hyper_lse_finish(c->stream, c->hyper_sum, c->hyper_lse_s, k->m, n_samples, cost,
+                                    acq_out ? c->acq.p : nullptr, c->part_val, c->part_idx, k->index_offset, nb);
+        else
+            launch_hyper_finish(c->stream, c->hyper_sum, k->m, n_samples, acq_out ? c->acq.p : nullptr, c->part_val,
+                                c->part_idx, k->index_offset, nb);
         launch_argmax_final(c->stream, c->part_val, c->part_idx, nb, c->h_best_val, c->h_best_idx);
         if (hipGetLastError() != hipSuccess) rc = fail(CBO_ERR_HIP, "hyper_finish_kernel launch");
         if (rc == CBO_OK) rc = copy_posterior_out(c, k, acq_out, nullptr, nullptr);
@@ -3421,8 +3431,11 @@ static int hyper_general_path(cbo_gp *g, cbo_cands *k, int n_samples, int n_ls, 
     return back;
 }
 
-extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const double *hyper, double y_best, int task,
-                                   double ei_jitter, double cost, double *acq_out, double *best_val, int64_t *best_idx)
+// cbo_acq_sweep_hyper and, with log_form, cbo_acq_sweep_hyper_log: the same checks, routing and paths, the
+// kernels' other instantiation
+static int sweep_hyper_impl(const char *name, bool log_form, cbo_gp *g, cbo_cands *k, int n_samples, const double *hyper,
+                            double y_best, int task, double ei_jitter, double cost, double *acq_out, double *best_val,
+                            int64_t *best_idx)
 {
     int rc = check_sweep_args(g, k, task);
     if (rc != CBO_OK) return rc;
@@ -3457,11 +3470,11 @@ extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const
         fill_hyper_set(st, g, k, task, y_best, ei_jitter, cost);
         auto launch = [&](int seq) -> int {
             launch_hyper_avg(c->stream, st, k->raw, c->hyper_host, n_samples, n_ls, acq_out ? c->acq.p : nullptr, blocks,
-                             c->hyper_schedule, small_launch(c, seq));
+                             c->hyper_schedule, small_launch(c, seq), log_form);
             HIP_TRY(hipGetLastError());
             return CBO_OK;
         };
-        rc = polled_launch(c, "cbo_acq_sweep_hyper", c->small_out.p, 1, "marginalised sweep: no result record", launch);
+        rc = polled_launch(c, name, c->small_out.p, 1, "marginalised sweep: no result record", launch);
         if (rc != CBO_OK) return rc;
         if (c->small_out[0].info == 0) {
             if (acq_out) {
@@ -3474,7 +3487,26 @@ extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const
         }
         // a sample that is not positive definite as assembled: the jitchol ladder of the general path
     }
-    return hyper_general_path(g, k, n_samples, n_ls, hyper, y_best, task, ei_jitter, cost, acq_out, best_val, best_idx);
+    return hyper_general_path(g, k, n_samples, n_ls, hyper, y_best, task, ei_jitter, cost, acq_out, best_val, best_idx,
+                              log_form);
+}
+
+extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const double *hyper, double y_best, int task,
+                                   double ei_jitter, double cost, double *acq_out, double *best_val, int64_t *best_idx)
+{
+    return sweep_hyper_impl("cbo_acq_sweep_hyper", false, g, k, n_samples, hyper, y_best, task, ei_jitter, cost, acq_out,
+                            best_val, best_idx);
+}
+
+// The log of the marginalised EI: log((1 / H) sum_h EI_h) - log cost, the log-sum-exp of cbo_acq_sweep_logei's
+// terms at cost 1.  cbo_acq_sweep_logei's scalar refusals first (a non-finite jitter or y_best), then cbo_acq_sweep_hyper's.
+extern "C" int cbo_acq_sweep_hyper_log(cbo_gp *g, cbo_cands *k, int n_samples, const double *hyper, double y_best, int task,
+                                       double jitter, double cost, double *acq_out, double *best_val, int64_t *best_idx)
+{
+    if (!std::isfinite(jitter)) return fail(CBO_ERR_INVALID, "jitter must be finite");
+    if (!std::isfinite(y_best)) return fail(CBO_ERR_INVALID, "y_best must be finite");
+    return sweep_hyper_impl("cbo_acq_sweep_hyper_log", true, g, k, n_samples, hyper, y_best, task, jitter, cost, acq_out,
+                            best_val, best_idx);
 }
 
 // ---- the marginalised EI for every set of a trial (hyper_sets_kernel) ------------------------------------
@@ -3482,9 +3514,9 @@ extern "C" int cbo_acq_sweep_hyper(cbo_gp *g, cbo_cands *k, int n_samples, const
 // and swept, sample after sample, by the workgroups of one launch (two from kSmallTwoPhaseFromBlocks blocks per set on, when
 // the slots fit); every other set -- and a set whose record reports a non-positive pivot at any sample -- takes
 // hyper_general_path, which restores its model.
-extern "C" int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
-                                        const double *const *hyper, const double *y_best, int task, double ei_jitter,
-                                        const double *costs, double *best_vals, int64_t *best_idxs)
+static int sweep_sets_hyper_impl(const char *name, bool log_form, int n_sets, cbo_gp *const *gps, cbo_cands *const *cands,
+                                 const int *n_samples, const double *const *hyper, const double *y_best, int task,
+                                 double ei_jitter, const double *costs, double *best_vals, int64_t *best_idxs)
 {
     // what needs no handle first
     if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
@@ -3497,7 +3529,10 @@ extern "C" int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cand
                                              std::to_string(CBO_MAX_HYPER_SAMPLES));
         if (!hyper[i]) return fail(CBO_ERR_INVALID, "hyper of set " + std::to_string(i) + " is NULL");
         if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive (set " + std::to_string(i) + ")");
+        if (log_form && !std::isfinite(y_best[i]))
+            return fail(CBO_ERR_INVALID, "y_best must be finite (set " + std::to_string(i) + ")");
     }
+    if (log_form && !std::isfinite(ei_jitter)) return fail(CBO_ERR_INVALID, "jitter must be finite");
     // the handles, then the rows (whose length is the model's)
     if (!gps || !cands) return fail(CBO_ERR_INVALID, "NULL argument: gps and cands must be given");
     int rc = check_set_handles(n_sets, gps, cands, task);
@@ -3556,14 +3591,63 @@ extern "C" int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cand
         return CBO_OK;
     };
     return run_small_or_general(
-        c, "cbo_acq_sweep_sets_hyper", "marginalised multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
-        [&](const SmallLaunch &L) { launch_hyper_sets(c->stream, c->hyper_sets_host, ns, blocks, (int)total, two_phase, L); },
+        c, name, "marginalised multi-set sweep: no result record", n_sets, small, c->small_out, prepare,
+        [&](const SmallLaunch &L) {
+            launch_hyper_sets(c->stream, c->hyper_sets_host, ns, blocks, (int)total, two_phase, L, log_form);
+        },
         [&](int j, int i) { return harvest_winner(c, j, i, best_vals, best_idxs); },
         // a larger or fp32 model, or a sample that is not positive definite as assembled: the general path, model restored
         [&](int i) {
             return hyper_general_path(gps[i], cands[i], n_samples[i], n_ls[(size_t)i], hyper[i], y_best[i], task, ei_jitter,
-                                      costs[i], nullptr, &best_vals[i], &best_idxs[i]);
+                                      costs[i], nullptr, &best_vals[i], &best_idxs[i], log_form);
         });
+}
+
+extern "C" int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
+                                        const double *const *hyper, const double *y_best, int task, double ei_jitter,
+                                        const double *costs, double *best_vals, int64_t *best_idxs)
+{
+    return sweep_sets_hyper_impl("cbo_acq_sweep_sets_hyper", false, n_sets, gps, cands, n_samples, hyper, y_best, task,
+                                 ei_jitter, costs, best_vals, best_idxs);
+}
+
+// cbo_acq_sweep_sets_hyper for the log form: per set cbo_acq_sweep_hyper_log's bits
+extern "C" int cbo_acq_sweep_sets_hyper_log(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
+                                            const double *const *hyper, const double *y_best, int task, double jitter,
+                                            const double *costs, double *best_vals, int64_t *best_idxs)
+{
+    return sweep_sets_hyper_impl("cbo_acq_sweep_sets_hyper_log", true, n_sets, gps, cands, n_samples, hyper, y_best, task,
+                                 jitter, costs, best_vals, best_idxs);
+}
+
+// The general path's reduction over terms the caller hands in: row h of `terms` goes through
+// hyper_lse_accumulate_kernel in order, hyper_lse_finish_kernel closes with n_rows and the cost -- the kernels, and so the bits,
+// of cbo_acq_sweep_hyper_log's general path, and by lse_stream.h of its one-launch path.
+extern "C" int cbo_lse_rows(cbo_ctx *c, int n_rows, int64_t m, const double *terms, double cost, double *out)
+{
+    if (!c || !terms || !out) return fail(CBO_ERR_INVALID, "NULL argument");
+    if (n_rows < 1 || n_rows > CBO_MAX_HYPER_SAMPLES)
+        return fail(CBO_ERR_INVALID, "n_rows must be in 1.." + std::to_string(CBO_MAX_HYPER_SAMPLES));
+    if (m < 1) return fail(CBO_ERR_INVALID, "m must be positive");
+    if (!(cost > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive");
+    HIP_TRY(hipSetDevice(c->device));
+    const int nb = acq_blocks_for(m);
+    int rc = grow(c, c->hyper_sum, (size_t)m);
+    if (rc == CBO_OK) rc = grow(c, c->hyper_lse_s, (size_t)m);
+    if (rc == CBO_OK) rc = grow(c, c->acq, (size_t)m);
+    if (rc != CBO_OK) return rc;
+    for (int h = 0; h < n_rows; ++h) {
+        // (pageable memory: the copy has read row h when it returns; the stream orders it behind the previous row's kernel)
+        HIP_TRY(hipMemcpyAsync(c->acq, terms + (size_t)h * (size_t)m, sizeof(double) * (size_t)m, hipMemcpyHostToDevice,
+                               c->stream));
+        launch_hyper_lse_accumulate(c->stream, c->hyper_sum, c->hyper_lse_s, c->acq, m, h == 0, nb);
+        HIP_TRY(hipGetLastError());
+    }
+    launch_hyper_lse_finish(c->stream, c->hyper_sum, c->hyper_lse_s, m, n_rows, cost, c->acq, c->part_val, c->part_idx, 0, nb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, c->acq, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CBO_OK;
 }
 
 // One reference-scale trial in ONE call (src/CBO.py:143-173, CBO.intervene): the model of the set that was intervened on

@@ -546,8 +546,10 @@ void launch_small_sets_con(hipStream_t s, const cbo_small_set *pairs, int n_pair
 // or null.  scratch: hyper_avg_scratch_doubles(blocks, n_samples); part_val / part_idx: `blocks` entries; info[0], ticket[0]
 // zero on entry (zero again afterwards); the record out[0] (pinned) carries the winner and the status word.
 size_t hyper_avg_scratch_doubles(int blocks, int n_samples);
+// log_form: the kernels' log instantiation -- log((1 / H) sum_h EI_h) - log cost by the streaming
+// log-sum-exp of lse_stream.h over log_ei_of's terms at log cost 0
 void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
-                      int n_ls, double *acq_out, int blocks, int schedule, const SmallLaunch &L);
+                      int n_ls, double *acq_out, int blocks, int schedule, const SmallLaunch &L, bool log_form = false);
 // The multi-set form (hyper_sets_kernel).  One descriptor per set: hyper_avg_kernel's arguments (acq_out
 // null) and `first`, the sum of the n_samples of the sets before it -- the scratch slot of the set's sample 0 in the
 // two-launch form.  sets may be pinned host memory (read by the kernel directly beyond kSmallByValue sets).
@@ -567,12 +569,17 @@ struct HyperSet {
 // total_samples workgroups factors every sample of every set once, the sweep reads the factors back.
 size_t hyper_sets_scratch_doubles(int n_sets, int blocks_per_set, int total_samples, bool two_phase);
 void launch_hyper_sets(hipStream_t s, const HyperSet *sets, int n_sets, int blocks_per_set, int total_samples, bool two_phase,
-                       const SmallLaunch &L);
+                       const SmallLaunch &L, bool log_form = false);
 // the general path: sum[i] = (first ? 0 : sum[i]) + acq[i] for i < m; then acq_out[i] = sum[i] / n_samples (acq_out may be
 // null) with arg-max partials per workgroup (n_blocks <= 2048) for launch_argmax_final
 void launch_hyper_accumulate(hipStream_t s, double *sum, const double *acq, int64_t m, bool first, int n_blocks);
 void launch_hyper_finish(hipStream_t s, const double *sum, int64_t m, int n_samples, double *acq_out, double *part_val,
                          int64_t *part_idx, int64_t index_offset, int n_blocks);
+// the log form's general path: (M, S)[i] = lse_start(term[i]) when first, else lse_push(term[i]) into them;
+// then acq_out[i] = lse_close(M[i], S[i], n_samples, log(cost)) (acq_out may be null) with the arg-max partials as above
+void launch_hyper_lse_accumulate(hipStream_t s, double *M, double *S, const double *term, int64_t m, bool first, int n_blocks);
+void launch_hyper_lse_finish(hipStream_t s, const double *M, const double *S, int64_t m, int n_samples, double cost,
+                             double *acq_out, double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks);
 
 struct AcqParams {
     double variance, noise_var, y_best, ei_jitter, cost;

@@ -14,9 +14,14 @@
 // functions -- workgroup (block, set) walks its own set's samples.
 // The accumulate / finish kernels at the end serve the general path (larger, fp32 or jitter-needing models), whose
 // per-sample terms come from cbo_acq_sweep itself.
+// LOG: the log-space form, log((1 / H) sum_h EI_h) - log cost.  The term is log_ei_of at log cost 0 --
+// cbo_acq_sweep_logei's value at cost 1 -- the per-lane state the streaming log-sum-exp's (M, S) in the place of the sum,
+// and the close lse_close in the place of the division (lse_stream.h); everything before the term is the same code.  The
+// general path's kernels are hyper_lse_accumulate_kernel / hyper_lse_finish_kernel, from the same header.
 #include <cstring>
 
 #include "cbo_small_lml_device.h"
+#include "lse_stream.h"
 
 #pragma clang fp contract(off)
 
@@ -48,12 +53,31 @@ __device__ __forceinline__ HyperLane hyper_lane(const cbo_small_set &st, int blk
     return L;
 }
 
+// The log form's term pushed into the lane's (M, S): log_ei_of at log cost 0 under the sample's scalars, lse_start for the
+// first sample, lse_push after it.  Out of line, the state returned in registers: inlined, log_h_of's three ranges and the
+// push's exp would share the sweep's 256 VGPRs with the factor's registers (DESIGN.md §4ac has the figures).
+struct LseState {
+    double M, S;
+};
+__device__ __attribute__((noinline)) LseState hyper_lse_term(double mean, double var, double y_best, double jitter, int task,
+                                                             bool first, double M, double S)
+{
+    AcqParams p{};
+    p.y_best = y_best; p.ei_jitter = jitter; p.task = task; p.cost = 1.0;
+    const double l = log_ei_of(mean, var, p, 0.0);
+    if (first) lse_start(l, M, S);
+    else lse_push(l, M, S);
+    return LseState{M, S};
+}
+
 // One sample: the points with the sample's lengthscales, the factor (factored here into `slot` when `factor`, else read from
 // `slot`, where a first launch left it), K*, the solve, and sum = sum + acquisition_of(...) on the lanes that own a candidate
+// (LOG: (sum, S) is the log-sum-exp's (M, S), started by the `first` sample)
+template <bool LOG>
 __device__ __forceinline__ void hyper_add_sample(SmallShared &sh, const cbo_small_set &st, const double *__restrict__ craw,
                                                  const double *__restrict__ row, int n_ls, int tiles, double rhs, double *slot,
                                                  bool factor, int *info_word, const HyperLane &L, int lane, int wave,
-                                                 double &sum)
+                                                 bool first, double &sum, double &S)
 {
     const int lc = lane & 15, kq = lane >> 4;
     const double *ls = st.ard ? row + 1 : nullptr;
@@ -93,25 +117,35 @@ __device__ __forceinline__ void hyper_add_sample(SmallShared &sh, const cbo_smal
     if (kq == 0 && L.c < st.m) {
         double mean, var;
         posterior_of(qacc, macc, L.cpm_c, L.cpv_c, L.causal, p, mean, var);
-        sum = __dadd_rn(sum, acquisition_of(mean, var, p));
+        if constexpr (LOG) {
+            const LseState t = hyper_lse_term(mean, var, p.y_best, p.ei_jitter, p.task, first, sum, S);
+            sum = t.M;
+            S = t.S;
+        } else {
+            sum = __dadd_rn(sum, acquisition_of(mean, var, p));
+        }
     }
 }
 
-// The mean over the samples (one IEEE division) and the workgroup's arg-max of it: thread 0's (bv, bi) on return
-__device__ __forceinline__ void hyper_mean_argmax(SmallShared &sh, const cbo_small_set &st, double sum, int n_samples,
+// The mean over the samples (one IEEE division; LOG: lse_close over the lane's (M, S) = (sum, S)) and the workgroup's
+// arg-max of it: thread 0's (bv, bi) on return
+template <bool LOG>
+__device__ __forceinline__ void hyper_mean_argmax(SmallShared &sh, const cbo_small_set &st, double sum, double S, int n_samples,
                                                   double *acq_out, const HyperLane &L, int lane, int wave, double &bv,
                                                   int64_t &bi)
 {
     bv = -INFINITY;
     bi = INT64_MAX;
     if ((lane >> 4) == 0 && L.c < st.m) {
-        bv = __ddiv_rn(sum, (double)n_samples);
+        if constexpr (LOG) bv = lse_close(sum, S, n_samples, log(st.cost));
+        else bv = __ddiv_rn(sum, (double)n_samples);
         bi = L.c + st.index_offset;
         if (acq_out) acq_out[L.c] = bv;
     }
     small_block_argmax(sh, lane, wave, bv, bi);
 }
 
+template <bool LOG>
 __global__ __launch_bounds__(256) void hyper_avg_kernel(const HyperArgs a, double *scratch, int blocks,
                                                         double *__restrict__ part_val, int64_t *__restrict__ part_idx,
                                                         int *__restrict__ info, int *__restrict__ ticket,
@@ -134,15 +168,15 @@ __global__ __launch_bounds__(256) void hyper_avg_kernel(const HyperArgs a, doubl
         return;
     }
     const HyperLane L = hyper_lane(st, blk, wave, lane & 15);
-    double sum = 0.0;
+    double sum = 0.0, S = 0.0;
     for (int h = 0; h < a.n_samples; ++h)
         // phases 3: the workgroup's own slot, sample after sample; phases 2: slot h holds sample h's factor
-        hyper_add_sample(sh, st, a.craw, a.hyper + (int64_t)h * row_len, a.n_ls, tiles, rhs,
-                         scratch + (int64_t)(phases == 2 ? h : blk) * kSmallScratch, (phases & 1) != 0, &info[0], L, lane, wave,
-                         sum);
+        hyper_add_sample<LOG>(sh, st, a.craw, a.hyper + (int64_t)h * row_len, a.n_ls, tiles, rhs,
+                              scratch + (int64_t)(phases == 2 ? h : blk) * kSmallScratch, (phases & 1) != 0, &info[0], L, lane,
+                              wave, h == 0, sum, S);
     double bv;
     int64_t bi;
-    hyper_mean_argmax(sh, st, sum, a.n_samples, a.acq_out, L, lane, wave, bv, bi);
+    hyper_mean_argmax<LOG>(sh, st, sum, S, a.n_samples, a.acq_out, L, lane, wave, bv, bi);
     small_set_finish(bv, bi, 0, blk, blocks, part_val, part_idx, info, ticket, out, seq, &last_flag);
 }
 
@@ -154,7 +188,7 @@ __global__ __launch_bounds__(256) void hyper_avg_kernel(const HyperArgs a, doubl
 //   phases 2: grid (blocks_per_set, n_sets): the sweep reads slot first_s + h back.
 // A workgroup beyond its set's own candidate blocks (a set narrower than the widest) reads nothing of the set and writes no
 // scratch: it only hands in the empty winner, as small_sets_kernel's does, so that the set's ticket counts blocks_per_set.
-template <bool BYVAL>
+template <bool BYVAL, bool LOG>
 __global__ __launch_bounds__(256) void hyper_sets_kernel(const HyperSetArgs byval, const HyperSet *__restrict__ sets,
                                                          int n_sets, double *scratch, int blocks_per_set,
                                                          double *__restrict__ part_val, int64_t *__restrict__ part_idx,
@@ -193,14 +227,14 @@ __global__ __launch_bounds__(256) void hyper_sets_kernel(const HyperSetArgs byva
     const int row_len = hs.a.n_ls + 2;
     const double rhs = hyper_rhs(st);
     const HyperLane L = hyper_lane(st, blk, wave, lane & 15);
-    double sum = 0.0;
+    double sum = 0.0, S = 0.0;
     for (int h = 0; h < hs.a.n_samples; ++h)
-        hyper_add_sample(sh, st, hs.a.craw, hs.a.hyper + (int64_t)h * row_len, hs.a.n_ls, tiles, rhs,
-                         scratch + (int64_t)(phases == 2 ? hs.first + h : slot) * kSmallScratch, (phases & 1) != 0, &info[set],
-                         L, lane, wave, sum);
+        hyper_add_sample<LOG>(sh, st, hs.a.craw, hs.a.hyper + (int64_t)h * row_len, hs.a.n_ls, tiles, rhs,
+                              scratch + (int64_t)(phases == 2 ? hs.first + h : slot) * kSmallScratch, (phases & 1) != 0,
+                              &info[set], L, lane, wave, h == 0, sum, S);
     double bv;
     int64_t bi;
-    hyper_mean_argmax(sh, st, sum, hs.a.n_samples, nullptr, L, lane, wave, bv, bi);
+    hyper_mean_argmax<LOG>(sh, st, sum, S, hs.a.n_samples, nullptr, L, lane, wave, bv, bi);
     small_set_finish(bv, bi, set, slot, blocks_per_set, part_val, part_idx, info, ticket, out, seq, &last_flag);
 }
 
@@ -211,23 +245,31 @@ size_t hyper_avg_scratch_doubles(int blocks, int n_samples)
 
 // schedule 0: from kSmallTwoPhaseFromBlocks candidate blocks on, the samples are factored once by a first launch of n_samples
 // workgroups and the sweep reads the factors back (phases 1 + 2); below, every workgroup factors every sample itself (phases 3)
-void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
-                      int n_ls, double *acq_out, int blocks, int schedule, const SmallLaunch &L)
+template <bool LOG>
+static void launch_hyper_avg_as(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
+                                int n_ls, double *acq_out, int blocks, int schedule, const SmallLaunch &L)
 {
     static std::atomic<unsigned long long> opted{0};
-    small_lds_opt_in(reinterpret_cast<const void *>(hyper_avg_kernel), opted);
+    small_lds_opt_in(reinterpret_cast<const void *>(hyper_avg_kernel<LOG>), opted);
     HyperArgs a{};
     a.st = st; a.craw = craw; a.hyper = hyper; a.n_samples = n_samples; a.n_ls = n_ls; a.acq_out = acq_out;
     const bool two_phase = schedule == 2 || (schedule != 1 && blocks >= kSmallTwoPhaseFromBlocks);
     if (two_phase) {
-        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)n_samples), dim3(256), sizeof(SmallShared), s, a, L.scratch, blocks,
-                           L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 1);
-        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, L.scratch, blocks,
-                           L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 2);
+        hipLaunchKernelGGL(hyper_avg_kernel<LOG>, dim3((unsigned)n_samples), dim3(256), sizeof(SmallShared), s, a, L.scratch,
+                           blocks, L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 1);
+        hipLaunchKernelGGL(hyper_avg_kernel<LOG>, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, L.scratch,
+                           blocks, L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 2);
     } else {
-        hipLaunchKernelGGL(hyper_avg_kernel, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, L.scratch, blocks,
-                           L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 3);
+        hipLaunchKernelGGL(hyper_avg_kernel<LOG>, dim3((unsigned)blocks), dim3(256), sizeof(SmallShared), s, a, L.scratch,
+                           blocks, L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, 3);
     }
+}
+
+void launch_hyper_avg(hipStream_t s, const cbo_small_set &st, const double *craw, const double *hyper, int n_samples,
+                      int n_ls, double *acq_out, int blocks, int schedule, const SmallLaunch &L, bool log_form)
+{
+    if (log_form) launch_hyper_avg_as<true>(s, st, craw, hyper, n_samples, n_ls, acq_out, blocks, schedule, L);
+    else launch_hyper_avg_as<false>(s, st, craw, hyper, n_samples, n_ls, acq_out, blocks, schedule, L);
 }
 
 // The two-launch form needs one scratch slot per sample of the call, the single launch one per workgroup
@@ -236,16 +278,16 @@ size_t hyper_sets_scratch_doubles(int n_sets, int blocks_per_set, int total_samp
     return (two_phase ? (size_t)total_samples : (size_t)n_sets * (size_t)blocks_per_set) * kSmallScratch;
 }
 
-template <bool BYVAL>
+template <bool BYVAL, bool LOG>
 static void launch_hyper_sets_as(hipStream_t s, const HyperSetArgs &args, const HyperSet *sets, int n_sets, int blocks_per_set,
                                  int total_samples, bool two_phase, double *scratch, double *part_val, int64_t *part_idx,
                                  int *info, int *ticket, cbo_small_result *out, int seq)
 {
     static std::atomic<unsigned long long> opted{0};
-    small_lds_opt_in(reinterpret_cast<const void *>(hyper_sets_kernel<BYVAL>), opted);
+    small_lds_opt_in(reinterpret_cast<const void *>(hyper_sets_kernel<BYVAL, LOG>), opted);
     const dim3 grid((unsigned)blocks_per_set, (unsigned)n_sets);
     auto launch = [&](const dim3 &g, int phases) {
-        hipLaunchKernelGGL((hyper_sets_kernel<BYVAL>), g, dim3(256), sizeof(SmallShared), s, args, sets, n_sets, scratch,
+        hipLaunchKernelGGL((hyper_sets_kernel<BYVAL, LOG>), g, dim3(256), sizeof(SmallShared), s, args, sets, n_sets, scratch,
                            blocks_per_set, part_val, part_idx, info, ticket, out, seq, phases);
     };
     if (two_phase) {
@@ -257,17 +299,15 @@ static void launch_hyper_sets_as(hipStream_t s, const HyperSetArgs &args, const 
 }
 
 void launch_hyper_sets(hipStream_t s, const HyperSet *sets, int n_sets, int blocks_per_set, int total_samples, bool two_phase,
-                       const SmallLaunch &L)
+                       const SmallLaunch &L, bool log_form)
 {
     HyperSetArgs args{};
-    if (n_sets <= kSmallByValue) {
-        std::memcpy(args.s, sets, sizeof(HyperSet) * (size_t)n_sets);
-        launch_hyper_sets_as<true>(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, L.scratch, L.part_val,
-                                   L.part_idx, L.info, L.ticket, L.out, L.seq);
-    } else {
-        launch_hyper_sets_as<false>(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, L.scratch, L.part_val,
-                                    L.part_idx, L.info, L.ticket, L.out, L.seq);
-    }
+    const bool byval = n_sets <= kSmallByValue;
+    if (byval) std::memcpy(args.s, sets, sizeof(HyperSet) * (size_t)n_sets);
+    auto launch = byval ? (log_form ? launch_hyper_sets_as<true, true> : launch_hyper_sets_as<true, false>)
+                        : (log_form ? launch_hyper_sets_as<false, true> : launch_hyper_sets_as<false, false>);
+    launch(s, args, sets, n_sets, blocks_per_set, total_samples, two_phase, L.scratch, L.part_val, L.part_idx, L.info, L.ticket,
+           L.out, L.seq);
 }
 
 // ---- the general path's two kernels ------------------------------------------------------------------------------------
@@ -292,6 +332,54 @@ __global__ __launch_bounds__(256) void hyper_finish_kernel(const double *__restr
         if (better(v, i + index_offset, bv, bi)) { bv = v; bi = i + index_offset; }
     }
     block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
+}
+
+// The log form's general path: term[i] is sample h's log EI at cost 1 (pointwise_acq_kernel<kLogEiKind>'s
+// output); (M[i], S[i]) the streaming log-sum-exp's state, started by the first sample
+__global__ __launch_bounds__(256) void hyper_lse_accumulate_kernel(double *__restrict__ M, double *__restrict__ S,
+                                                                   const double *__restrict__ term, int64_t m, int first)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        double Mi = 0.0, Si = 0.0;
+        if (first) {
+            lse_start(term[i], Mi, Si);
+        } else {
+            Mi = M[i];
+            Si = S[i];
+            lse_push(term[i], Mi, Si);
+        }
+        M[i] = Mi;
+        S[i] = Si;
+    }
+}
+
+// acq[i] = lse_close(M[i], S[i], n_samples, log cost) (acq_out may be null) and the workgroups' arg-max partials
+__global__ __launch_bounds__(256) void hyper_lse_finish_kernel(const double *__restrict__ M, const double *__restrict__ S,
+                                                               int64_t m, int n_samples, double cost,
+                                                               double *__restrict__ acq_out, double *__restrict__ part_val,
+                                                               int64_t *__restrict__ part_idx, int64_t index_offset)
+{
+    const double log_cost = log(cost);                            // (uniform: once per launch)
+    double bv = -INFINITY;
+    int64_t bi = kNoIndex;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = lse_close(M[i], S[i], n_samples, log_cost);
+        if (acq_out) acq_out[i] = v;
+        if (better(v, i + index_offset, bv, bi)) { bv = v; bi = i + index_offset; }
+    }
+    block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
+}
+
+void launch_hyper_lse_accumulate(hipStream_t s, double *M, double *S, const double *term, int64_t m, bool first, int n_blocks)
+{
+    hipLaunchKernelGGL(hyper_lse_accumulate_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, M, S, term, m, first ? 1 : 0);
+}
+
+void launch_hyper_lse_finish(hipStream_t s, const double *M, const double *S, int64_t m, int n_samples, double cost,
+                             double *acq_out, double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks)
+{
+    hipLaunchKernelGGL(hyper_lse_finish_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, M, S, m, n_samples, cost, acq_out,
+                       part_val, part_idx, index_offset);
 }
 
 void launch_hyper_accumulate(hipStream_t s, double *sum, const double *acq, int64_t m, bool first, int n_blocks)

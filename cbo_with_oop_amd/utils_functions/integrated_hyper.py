@@ -140,7 +140,12 @@ class IntegratedHyperParameterAcquisition:
     """emukit's ``IntegratedHyperParameterAcquisition`` for the causal EI: its signature plus ``samples``, an (H, P) array
     that skips the sampler.  ``acquisition_generator(model)`` must return a ``CausalExpectedImprovement`` or that over a
     ``Cost``; the average over the samples runs on the device, the model is not touched when it is small.
-    ``sampler="device"`` draws the samples by the one-launch HMC; ``"host"`` (default) is the host chain."""
+    ``sampler="device"`` draws the samples by the one-launch HMC; ``"host"`` (default) is the host chain.
+
+    A generator returning a ``CausalLogExpectedImprovement`` (bare, or over a ``Cost``: ``LogAcquisitionQuotient``) selects the
+    log form (``cbo_acq_sweep_hyper_log``): ``log((1 / H) sum_h EI_h) - log cost`` -- the LOGARITHM OF THE
+    AVERAGE the EI form computes, finite and ordered where that average is an exact 0.0.  It is not the average of the
+    logarithms, which is what emukit's class would form from such a generator.  ``is_log`` tells the two apart."""
 
     def __init__(self, model, acquisition_generator, n_samples=10, n_burnin=100, subsample_interval=10, step_size=1e-1,
                  leapfrog_steps=20, samples=None, sampler="host"):
@@ -150,8 +155,10 @@ class IntegratedHyperParameterAcquisition:
         self.model = model
         self.acquisition_generator = acquisition_generator
         acquisition = acquisition_generator(model)
+        from .pointwise_acquisitions import CausalLogExpectedImprovement
         inner = acquisition.numerator if isinstance(acquisition, AcquisitionQuotient) else acquisition
-        if not isinstance(inner, CausalExpectedImprovement):
+        self.is_log = isinstance(inner, CausalLogExpectedImprovement)
+        if not self.is_log and not isinstance(inner, CausalExpectedImprovement):
             raise TypeError("IntegratedHyperParameterAcquisition supports CausalExpectedImprovement and "
                             f"CausalExpectedImprovement / Cost, not {type(acquisition).__name__}")
         if samples is None and (isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1):
@@ -178,8 +185,8 @@ class IntegratedHyperParameterAcquisition:
 
     def sweep(self, candidates, cost=None, want_acq=False):
         """dict(best_val, best_idx, acq, mean, var) as ``CausalExpectedImprovement.sweep`` returns it (mean and var are
-        None: they differ per sample) from ONE ``cbo_acq_sweep_hyper`` call.  ``cost``: the batch's scalar cost; by
-        default the generator's ``Cost`` over the candidates, or 1."""
+        None: they differ per sample) from ONE ``cbo_acq_sweep_hyper`` call (``cbo_acq_sweep_hyper_log`` for a log
+        generator).  ``cost``: the batch's scalar cost; by default the generator's ``Cost`` over the candidates, or 1."""
         model = self.model
         own = not isinstance(candidates, CandidateGrid)
         grid = CandidateGrid(candidates, model) if own else candidates
@@ -189,7 +196,8 @@ class IntegratedHyperParameterAcquisition:
         best_val = ctypes.c_double(0.0)
         best_idx = ctypes.c_int64(-1)
         try:
-            _lib.check(_lib.load().cbo_acq_sweep_hyper(
+            lib = _lib.load()
+            _lib.check((lib.cbo_acq_sweep_hyper_log if self.is_log else lib.cbo_acq_sweep_hyper)(
                 model._handle, grid._handle, self.samples.shape[0], _lib.dptr(self.samples),
                 float(np.asarray(self._ei.current_global_min).reshape(-1)[0]), _lib.TASK_CODE[self._ei.task],
                 float(self._ei.jitter), float(cost), _lib.dptr(acq), ctypes.byref(best_val), ctypes.byref(best_idx)))

@@ -158,7 +158,13 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     ordered where ``EI * prod PoF`` is an exact 0.  An empty list scores ``"LOGEI"``'s bits; ``constraints=None``,
     ``hyper_samples``, ``batch_size``, ``cost_mode="pointwise"`` and ``anchors="uniform"`` raise ``ValueError`` before any
     device call.
+    ``acquisition="LOGMEI"`` with ``hyper_samples``: the marginalised EI in log space, ``log((1 / H) sum_h
+    EI_h) - log cost`` (``IntegratedHyperParameterAcquisition`` over a ``CausalLogExpectedImprovement`` generator,
+    ``cbo_acq_sweep_hyper_log``) -- the logarithm of the average ``hyper_samples`` with ``"EI"`` scores, not the average of the
+    logarithms; finite and ordered where that average is an exact 0.  Without ``hyper_samples``, or with ``constraints``,
+    ``batch_size``, ``cost_mode="pointwise"`` or ``anchors="uniform"``, it raises ``ValueError`` before any device call.
     """
+    checked_log_mei((acquisition, None), hyper_samples, constraints, batch_size, cost_mode=cost_mode, anchors=anchors)
     checked_log_cei((acquisition, None), constraints, hyper_samples, batch_size, cost_mode=cost_mode, anchors=anchors)
     if checked_pointwise_cost(cost_mode, (acquisition, None), constraints, hyper_samples, batch_size):
         from .cost_functions import PointwiseCost
@@ -182,8 +188,9 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
                 grid.close()
         return np.array([[res["best_val"]]]), x_new
     if hyper_samples is not None:
-        if acquisition != "EI":
-            raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI'")
+        if acquisition not in ("EI", LOG_MEI):
+            raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI' (or 'LOGMEI', the "
+                             "logarithm of the average)")
         if constraints is not None:
             raise ValueError("the marginalised EI is not defined with constraints: constraints must be None")
         if batch_size is not None:
@@ -201,7 +208,7 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
             raise ValueError("batch selection is not defined for constrained acquisitions: constraints must be None")
         if anchors != "grid":
             raise ValueError("batch selection picks from the grid: anchors must be 'grid'")
-    if acquisition not in ("EI", "MES", LOG_EI, LOG_CEI) + POINTWISE_ACQUISITIONS:
+    if acquisition not in ("EI", "MES", LOG_EI, LOG_CEI, LOG_MEI) + POINTWISE_ACQUISITIONS:
         raise ValueError(f"acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR', not {acquisition!r}")
     if acquisition == "MES":
         if task != "min":
@@ -229,7 +236,10 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
               else AcquisitionProduct([ei] + list(constraints)))
     if hyper_samples is not None:
         from .integrated_hyper import IntegratedHyperParameterAcquisition
-        generator = lambda mdl: CausalExpectedImprovement(current_global_best, task, mdl)      # noqa: E731
+        if acquisition == LOG_MEI:
+            generator = lambda mdl: _acquisition_for(LOG_EI, mdl, current_global_best, task, space)      # noqa: E731
+        else:
+            generator = lambda mdl: CausalExpectedImprovement(current_global_best, task, mdl)      # noqa: E731
         if isinstance(hyper_samples, (int, np.integer)):
             ei = IntegratedHyperParameterAcquisition(model, generator, n_samples=int(hyper_samples))
         else:
@@ -266,6 +276,7 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
 POINTWISE_ACQUISITIONS = ("LCB", "PI", "MPEI", "VAR")
 LOG_EI = "LOGEI"      # the log Expected Improvement: a name of its own, routed to the cbo_acq_*_logei calls
 LOG_CEI = "LOGCEI"    # log EI + sum log PoF - log cost: routed by name to the cbo_acq_*_constrained_log calls
+LOG_MEI = "LOGMEI"    # log((1 / H) sum_h EI_h) - log cost: routed by name to the cbo_acq_sweep*_hyper_log calls
 
 
 def _acquisition_for(name, model, current_global_best, task, space, param=None):
@@ -294,7 +305,8 @@ def sets_acquisition(acquisition="EI", acquisition_param=None):
     """(name, parameter) of the acquisition a multi-set sweep scores with, checked on the host before any device call:
     ``"EI"`` (no parameter: today's call, ``None``), ``"LCB"`` (beta, default 1, finite and not negative), ``"PI"`` and
     ``"MPEI"`` (the jitter, default 0, finite), ``"LOGEI"`` (the log Expected Improvement of DESIGN.md §4x: the jitter, as
-    PI's), ``"LOGCEI"`` (its constrained form, DESIGN.md §4aa: the log EI's jitter, checked as LOGEI's), ``"VAR"`` (no
+    PI's), ``"LOGCEI"`` (its constrained form, DESIGN.md §4aa: the log EI's jitter, checked as LOGEI's), ``"LOGMEI"`` (its
+    hyper-marginalised form, DESIGN.md §4ac: the log EI's jitter, checked as LOGEI's), ``"VAR"`` (no
     parameter: 0 travels), ``"MES"`` with a pair of ints ``(num_samples, grid_size)``, ``num_samples`` in 1..64,
     ``grid_size`` at least 1 (the parameter returned is that pair).
     Anything else raises ``ValueError`` -- a bare ``"MES"`` too: this function never answered for it and has no default for
@@ -306,7 +318,8 @@ def sets_acquisition(acquisition="EI", acquisition_param=None):
         name, param = acquisition                 # an earlier answer of this function (a path keeps its own): checked again
         sets_acquisition(name, None if name in ("EI", "VAR") else param)
         return acquisition
-    if not isinstance(acquisition, str) or acquisition not in ("EI", "MES", LOG_EI, LOG_CEI) + POINTWISE_ACQUISITIONS:
+    if not isinstance(acquisition, str) \
+            or acquisition not in ("EI", "MES", LOG_EI, LOG_CEI, LOG_MEI) + POINTWISE_ACQUISITIONS:
         raise ValueError("acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR' in a multi-set sweep, "
                          f"not {acquisition!r}")
     if acquisition == "MES":
@@ -445,10 +458,18 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     launch does not take go through ``refine_batched``).  The refined point replaces the winner only if its value at its own
     cost is not lower.  Another acquisition, ``constraints`` that are ``None`` or all empty, missing ``spaces``, ``raw=True``,
     ``hyper_samples``, ``batch_size``, ``device_prior=True`` and ``cost_mode="pointwise"`` raise ``ValueError`` before any device
-    call.  ``False`` takes exactly today's calls; ``refine=True`` with constraints keeps raising."""
+    call.  ``False`` takes exactly today's calls; ``refine=True`` with constraints keeps raising.
+    ``acquisition="LOGMEI"`` with ``acquisition_param`` (the log EI's jitter, default 0) and ``hyper_samples`` (DESIGN.md
+    §4ac): every set's score is the LOGARITHM of the EI marginalised over its samples, ``log((1 / H) sum_h EI_h) - log cost``
+    -- not the average of the logarithms -- in the same one call (``cbo_acq_sweep_sets_hyper_log``): per set what
+    ``find_next_y_point(acquisition="LOGMEI", hyper_samples=rows_s)`` returns, finite and ordered where the marginalised EI
+    is an exact 0.  Without ``hyper_samples``, or with non-empty ``constraints``, ``batch_size``, ``refine``,
+    ``refine_constrained``, ``device_prior``, ``cost_mode="pointwise"`` or ``raw=True``, it raises ``ValueError`` before any
+    device call."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    checked_log_mei(kind, hyper_samples, constraints, batch_size, refine, refine_constrained, device_prior, raw, cost_mode)
     checked_refine_constrained(refine_constrained, kind, constraints, hyper_samples, batch_size, raw, spaces, len(models),
                                device_prior, cost_mode)
     checked_log_cei(kind, constraints, hyper_samples, batch_size, refine, device_prior, raw, cost_mode)
@@ -516,10 +537,11 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
         # (the entry keeps the row arrays and the pointer array alive; the rows change from trial to trial)
         st["hyper_args"] = ((ctypes.c_int * s)(*[r.shape[0] for r in hyper_rows]),
                             (ctypes.c_void_p * s)(*[r.ctypes.data for r in hyper_rows]))
-        _lib.check(_lib.load().cbo_acq_sweep_sets_hyper(s, st["gps"], st["cds"], st["hyper_args"][0], st["hyper_args"][1],
-                                                        _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
-                                                        _lib.dptr(batch_cost), _lib.dptr(vals),
-                                                        idxs.ctypes.data_as(_lib.c_int64_p)))
+        log_form = kind[0] == LOG_MEI            # (the same list, the log EI's jitter in the jitter's place)
+        call = _lib.load().cbo_acq_sweep_sets_hyper_log if log_form else _lib.load().cbo_acq_sweep_sets_hyper
+        _lib.check(call(s, st["gps"], st["cds"], st["hyper_args"][0], st["hyper_args"][1], _lib.dptr(st["y_best"]),
+                        _lib.TASK_CODE[task], float(kind[1]) if log_form else 0.0, _lib.dptr(batch_cost), _lib.dptr(vals),
+                        idxs.ctypes.data_as(_lib.c_int64_p)))
     elif constraints is not None:
         _sweep_sets_constrained(st, models, grids, constraints, task, kind)
     elif kind[0] == "MES":
@@ -646,6 +668,35 @@ def checked_log_cei(kind, constraints, hyper_samples=None, batch_size=None, refi
         raise ValueError(f"{what} is not defined for batches: batch_size must be None")
     if refine:
         raise ValueError(f"{what} has no refinement kernel: refine must be False")
+    if device_prior:
+        raise ValueError(f"{what} has no refinement kernel: device_prior must be False")
+    if cost_mode != "batch":
+        raise ValueError(f"{what} takes one cost per set: cost_mode must be 'batch', not {cost_mode!r}")
+    if anchors != "grid":
+        raise ValueError(f"{what} is scored over the grid: anchors must be 'grid'")
+    if raw:
+        raise ValueError(f"{what} is not defined across several ranks (raw=True)")
+
+
+def checked_log_mei(kind, hyper_samples, constraints=None, batch_size=None, refine=False, refine_constrained=False,
+                    device_prior=False, raw=False, cost_mode="batch", anchors="grid"):
+    """What the hyper-marginalised EI in log space (``"LOGMEI"``) needs and does not combine with, checked on
+    the host before any device call: it needs ``hyper_samples`` and is scored over the grid, once, with one cost per set,
+    without constraints, by a single process."""
+    if kind[0] != LOG_MEI:
+        return
+    what = "acquisition='LOGMEI'"
+    if hyper_samples is None:
+        raise ValueError(f"{what} is the logarithm of the EI averaged over hyper-parameter samples: hyper_samples must be "
+                         "given (without samples the acquisition is 'LOGEI')")
+    if constraints is not None and (not hasattr(constraints, "__len__") or any(constraints)):
+        raise ValueError(f"{what} is not defined with constraints: constraints must be None or empty")
+    if batch_size is not None:
+        raise ValueError(f"{what} picks one point: batch_size must be None")
+    if refine:
+        raise ValueError(f"{what} has no refinement kernel: refine must be False")
+    if refine_constrained:
+        raise ValueError(f"{what} has no refinement kernel: refine_constrained must be False")
     if device_prior:
         raise ValueError(f"{what} has no refinement kernel: device_prior must be False")
     if cost_mode != "batch":
@@ -807,8 +858,9 @@ def checked_set_hyper_samples(hyper_samples, models, kind=("EI", None), constrai
     can be refused is refused before a model draws (an int) and before any device call."""
     if hyper_samples is None:
         return None
-    if kind[0] != "EI":
-        raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI'")
+    if kind[0] not in ("EI", LOG_MEI):
+        raise ValueError("hyper-parameter samples marginalise the causal EI: acquisition must be 'EI' (or 'LOGMEI', the "
+                         "logarithm of the average)")
     if constraints is not None:
         raise ValueError("the marginalised EI is not defined with constraints: constraints must be None or empty")
     if raw:
@@ -935,7 +987,11 @@ def winners_to_points(st, models, grids, current_global_best, task):
             y = np.array(((values[i],),))
         elif hyper_rows is not None:
             from .integrated_hyper import IntegratedHyperParameterAcquisition
-            generator = lambda mdl, c=costs[i]: CausalExpectedImprovement(current_global_best, task, mdl) / c   # noqa: E731
+            if name == LOG_MEI:                  # (the log generator: re-priced by cbo_acq_sweep_hyper_log)
+                generator = lambda mdl, c=costs[i]: _acquisition_for(LOG_EI, mdl, current_global_best, task, None,   # noqa: E731
+                                                                     param) / c
+            else:
+                generator = lambda mdl, c=costs[i]: CausalExpectedImprovement(current_global_best, task, mdl) / c   # noqa: E731
             y = IntegratedHyperParameterAcquisition(models[i], generator, samples=hyper_rows[i]).evaluate(x_new)
         elif constraints is not None and constraints[i]:
             from .constrained import AcquisitionProduct, ConstrainedLogExpectedImprovement

@@ -397,7 +397,8 @@ int cbo_gp_plugin_incumbent(cbo_gp *gp, int task, double *incumbent_out);
  * negative -EI and has none.  mean_out / var_out are cbo_acq_sweep_kind's bits; s and the quotient u are formed as
  * cbo_acq_sweep forms them; the tie rule, the outputs that may be NULL and the route to q, mu are cbo_acq_sweep_kind's.  A NaN
  * mean or variance gives NaN.  The multi-set and refinement forms are cbo_acq_sweep_sets_logei and cbo_acq_refine_sets_logei,
- * below; a one-call trial step, the constrained, hyper-marginalised, plug-in and batch forms are out of scope.
+ * below; a one-call trial step, the constrained, hyper-marginalised, plug-in and batch forms are out of scope.  (Since built:
+ * the constrained form, cbo_acq_sweep_constrained_log, and the hyper-marginalised one, cbo_acq_sweep_hyper_log.)
  * CBO_ERR_INVALID, scalars first: a bad task, a non-finite jitter or y_best, cost <= 0 or NaN; then cbo_acq_sweep's argument
  * checks.  Unfitted model: CBO_ERR_NOT_FITTED. */
 int cbo_acq_sweep_logei(cbo_gp *gp, cbo_cands *cands, double y_best, int task, double jitter, double cost,
@@ -741,6 +742,41 @@ int cbo_acq_sweep_sets_constrained_log(int n_sets, cbo_gp *const *gps, cbo_cands
 int cbo_acq_sweep_sets_hyper(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
                              const double *const *hyper, const double *y_best, int task, double ei_jitter,
                              const double *costs, double *best_vals, int64_t *best_idxs);
+
+/* The marginalised EI in log space, for the models whose EI is an exact 0.0 over most of a grid under every
+ * sample (noise 1e-10, a few dozen observations), where cbo_acq_sweep_hyper's average is 0.0 too and orders nothing:
+ *     acq_i = log((1 / H) sum_h EI_h,i) - log cost = LSE_h(l_h,i) - log H - log cost
+ * l_h,i being, bit for bit, what cbo_acq_sweep_logei(gp_h, cands, y_best, task, jitter, 1.0, ...) writes to acq_out[i] on a
+ * fitted twin gp_h carrying sample h's hyper-parameters; task 'max' is cbo_acq_sweep_logei's mirror, not cbo_acq_sweep_hyper's
+ * -EI.  This is the LOGARITHM OF THE AVERAGE that cbo_acq_sweep_hyper forms, not the average of the logarithms (what emukit's
+ * IntegratedHyperParameterAcquisition would form from a generator of log acquisitions).  The reduction is one stated sequence,
+ * in sample order, one rounding per operation, the device library's exp and log:
+ *     M = l_0, S = 1;   for h = 1..H-1:  l > M: S = S exp(M - l) + 1, M = l;   l == M: S = S + 1;   else S = S + exp(l - M);
+ *     acq = ((M + log S) - log (double)H) - log cost
+ * so that NaN propagates (and is maximal in the arg-max), -inf is an ordinary value (all samples at -inf give -inf), and H = 1
+ * gives cbo_acq_sweep_logei's acq_out, best_val and best_idx bit for bit.  Error against the exact log-sum-exp of the same
+ * terms: at most 4 * 2^-53 * (H + |acq|).
+ * cbo_acq_sweep_hyper_log: cbo_acq_sweep_hyper's argument list (ei_jitter being the log EI's jitter), its routing -- one
+ * launch for an fp64 model of at most 128 observations, which touches nothing; the general path otherwise, per sample
+ * cbo_acq_sweep_logei's steps at cost 1 with the term kept on the device, restoring the model as described there -- and its
+ * error returns, plus cbo_acq_sweep_logei's scalar ones (checked first): a non-finite jitter or y_best.
+ * cbo_acq_sweep_sets_hyper_log: cbo_acq_sweep_sets_hyper's list, routing and two-launch rule; per set, bit for bit, what
+ * cbo_acq_sweep_hyper_log returns.  Its error returns, plus a non-finite jitter or y_best[i].
+ * cbo_lse_rows: the reduction alone, over terms the caller hands in -- out[i] = the sequence above over terms[0][i], ...,
+ * terms[n_rows - 1][i] with the cost given, by the kernels of the general path (and, by construction, the bits of the
+ * one-launch path): what the sweeps compute from their terms can be pinned without restating the device's exp and log on
+ * the host.  n_rows in 1..CBO_MAX_HYPER_SAMPLES, m >= 1, cost > 0; terms is n_rows x m, row-major, host memory; out m doubles.
+ * Out of scope: constraints, batches, the plug-in EI, MES and per-candidate costs under marginalisation, refinement, a
+ * one-call trial step, several ranks. */
+int cbo_acq_sweep_hyper_log(cbo_gp *gp, cbo_cands *cands, int n_samples,
+                            const double *hyper /* n_samples rows of (variance, lengthscale x L, noise_var) */,
+                            double y_best, int task, double jitter, double cost, double *acq_out /* m, may be NULL */,
+                            double *best_val, int64_t *best_idx);
+int cbo_acq_sweep_sets_hyper_log(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const int *n_samples,
+                                 const double *const *hyper, const double *y_best, int task, double jitter,
+                                 const double *costs, double *best_vals, int64_t *best_idxs);
+int cbo_lse_rows(cbo_ctx *ctx, int n_rows, int64_t m, const double *terms /* n_rows x m, host */, double cost,
+                 double *out /* m */);
 
 /* Max-value entropy search for every exploration set of a trial, in two calls with the host's draw of the
  * Gumbel samples between them (mins = log(-log(1 - u)) * b + a, u from the caller's generator).
