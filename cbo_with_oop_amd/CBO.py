@@ -120,6 +120,12 @@ class CBOAcquisitionPath:
     picks in one device call (``find_next_y_points(batch_size=B)``): ``xs[s]`` is (B, d), ``ys[s]`` (B, 1); the
     set is chosen by pick 0, as before.  It needs ``acquisition="EI"``, no constraints, no hyper-parameter samples and a
     single process, and its ``trial_step`` takes the three-call route.
+    ``acquisition="LOGBEI"`` (``acquisition_param``: the log EI's jitter, default 0) with ``batch_size`` scores
+    every pick of that batch with ``log EI - log cost`` (``cbo_acq_sweep_sets_batch_logei``): where the incumbent lies below a
+    set's own data -- every set but the best one -- the EI of every pick is an exact 0.0 and ``"EI"`` returns the grid's first
+    point B times; the log form returns B distinct, ordered picks.  It needs ``batch_size``, no constraints, no
+    hyper-parameter samples, no ``refine`` / ``refine_constrained`` / ``device_prior``, ``cost_mode="batch"`` and a single
+    process, and its ``trial_step`` takes the multi-call route.
     ``refine_constrained=True`` (with ``constraints`` and ``acquisition`` ``"EI"`` or ``"LOGCEI"``): every set's
     constrained winner is refined by L-BFGS on the constrained acquisition inside the set's box from ``space_list``
     (``find_next_y_points(refine_constrained=True)``), all sets in one further device call, single process; ``trial_step``
@@ -144,11 +150,13 @@ class CBOAcquisitionPath:
                  mle_restarts=1, hyper_priors=None, cost_mode="batch", mle_device_rows=128, refine_constrained=False):
         from .GaussianProcessFactory import checked_mle_device_rows, checked_mle_optimizer
         from .utils_functions.priors import checked_priors
-        from .utils_functions.utils import (checked_device_prior, checked_log_cei, checked_log_ei, checked_log_mei,
-                                            checked_pointwise_cost, checked_refine, checked_refine_constrained,
-                                            sets_acquisition_or_default as sets_acquisition)
+        from .utils_functions.utils import (checked_device_prior, checked_log_bei, checked_log_cei, checked_log_ei,
+                                            checked_log_mei, checked_pointwise_cost, checked_refine,
+                                            checked_refine_constrained, sets_acquisition_or_default as sets_acquisition)
         self.mle_optimizer, self.mle_restarts = checked_mle_optimizer(mle_optimizer, mle_restarts), int(mle_restarts)
         self.mle_device_rows = checked_mle_device_rows(mle_device_rows, mle_optimizer)
+        checked_log_bei(sets_acquisition(acquisition, acquisition_param), batch_size, constraints or None, hyper_samples, refine,
+                        refine_constrained, device_prior, False, cost_mode)
         checked_log_mei(sets_acquisition(acquisition, acquisition_param), hyper_samples, constraints or None, batch_size, refine,
                         refine_constrained, device_prior, False, cost_mode)
         self.device_prior = checked_device_prior(device_prior, refine)
@@ -360,7 +368,7 @@ class CBOAcquisitionPath:
             raise ValueError(f"batch selection is scored by a single process: the placement is {mode!r}")
         if (self.refine or self.refine_constrained) and mode != "single":
             raise ValueError(f"gradient refinement is run by a single process: the placement is {mode!r}")
-        if self._kind[0] in ("LOGEI", "LOGMEI") and mode != "single":
+        if self._kind[0] in ("LOGEI", "LOGMEI", "LOGBEI") and mode != "single":
             raise ValueError(f"the log Expected Improvement is scored by a single process: the placement is {mode!r}")
         if self.cost_mode == "pointwise" and mode != "single":
             raise ValueError(f"cost_mode='pointwise' is scored by a single process: the placement is {mode!r}")
@@ -444,7 +452,7 @@ class CBOAcquisitionPath:
         st = self._call_cache.get("sweep_sets")
         model = self.models[s] if (s is not None and self.models) else None
         fast = (st is not None and model is not None and not self.constraints and self.hyper_samples is None
-                and self._kind[0] not in ("MES", "LOGEI", "LOGCEI") and self.batch_size is None and not self.refine
+                and self._kind[0] not in ("MES", "LOGEI", "LOGCEI", "LOGBEI") and self.batch_size is None and not self.refine
                 and self.cost_mode == "batch"
                 and (self.comm is None or self.comm.world == 1)
                 and model.mean_function is self.mean_functions[s] and model.variance_adjustment is self.var_functions[s]
@@ -551,7 +559,8 @@ class CBO(CBOAcquisitionPath):
     ``batch_size`` (an int B in 1..64) with ``update_incumbent``: ``intervene()`` runs the B interventions of a greedy batch on
     the chosen set side by side: the monitor evaluates the B rows, appends them in order and records
     ``chosen`` as ``(set, x (B, d))``; the trial's cost is the sum of the B interventions' costs.  ``None``: the reference's
-    one intervention per trial.
+    one intervention per trial.  ``acquisition="LOGBEI"`` (with ``batch_size``) scores the batch's picks in log
+    space, as for ``CBOAcquisitionPath``: B distinct interventions where ``"EI"`` would run the same one B times.
     ``refine_constrained=True`` (with ``constraints``): the constrained winners are refined likewise, on the constrained
     acquisition (``CBOAcquisitionPath(refine_constrained=True)``).
     ``refine=True``: every set's winner is refined by L-BFGS inside the set's interventional ranges before the set is chosen
@@ -621,7 +630,9 @@ class CBO(CBOAcquisitionPath):
         data_y = [np.asarray(y, dtype=np.float64).reshape(-1, 1) for _, y in interventional_data]
         if len(data_x) != len(exploration):
             raise ValueError(f"interventional_data has {len(data_x)} sets, the exploration set {len(exploration)}")
-        from .utils_functions.utils import checked_log_cei, checked_log_mei
+        from .utils_functions.utils import checked_log_bei, checked_log_cei, checked_log_mei
+        checked_log_bei(sets_acquisition(acquisition, acquisition_param), batch_size, path_constraints or None, hyper_samples,
+                        refine, refine_constrained, device_prior, False, cost_mode)
         checked_log_mei(sets_acquisition(acquisition, acquisition_param), hyper_samples, path_constraints or None, batch_size,
                         refine, refine_constrained, device_prior, False, cost_mode)
         checked_log_cei(sets_acquisition(acquisition, acquisition_param), path_constraints or None, hyper_samples, batch_size,

@@ -40,6 +40,7 @@ ACQ_KIND_CODE = {"LCB": 1, "PI": 2, "VAR": 3, "MPEI": 4}      # CBO_ACQ_LCB, _PI
 REFINE_KIND_CODE = dict(ACQ_KIND_CODE, EI=0)                  # cbo_acq_refine_sets: 0 = the causal Expected Improvement
 LOGEI = "LOGEI"              # the log Expected Improvement: entry points of its own (cbo_acq_*_logei), no kind code -- routed by name
 LOGMEI = "LOGMEI"            # the log of the hyper-marginalised EI (cbo_acq_sweep*_hyper_log): routed by name too
+LOGBEI = "LOGBEI"            # the Kriging-believer batch on the log EI (cbo_acq_sweep*_batch_logei): routed by name too
 REFINE_MAX_STARTS = 64       # CBO_REFINE_MAX_STARTS
 REFINE_ROUNDS_LIMIT = 1000   # CBO_REFINE_ROUNDS_LIMIT
 REFINE_PGTOL, REFINE_FTOL, REFINE_STEP, REFINE_MAX_ROUNDS, REFINE_NAN_START, REFINE_DECLINED = range(6)   # CBO_REFINE_*
@@ -228,6 +229,9 @@ SIGNATURES = {
     "cbo_acq_sweep_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
                                            ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p,
                                            c_int64_p, c_double_p, c_double_p, c_double_p]),
+    "cbo_acq_sweep_batch_logei": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, c_double_p,
+                                                 c_int64_p, c_double_p, c_double_p, c_double_p]),
     "cbo_gp_fit_sweep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
                                         ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_double_p,
                                         c_double_p, c_int64_p, c_int_p, c_double_p]),
@@ -246,6 +250,9 @@ SIGNATURES = {
                                               c_int64_p]),
     "cbo_acq_sweep_sets_batch": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, ctypes.c_int, ctypes.c_double,
                                                 c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, c_int64_p]),
+    "cbo_acq_sweep_sets_batch_logei": (ctypes.c_int, [ctypes.c_int, c_void_pp, c_void_pp, c_double_p, ctypes.c_int,
+                                                      ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
+                                                      c_int64_p]),
     "cbo_acq_refine_sets": (ctypes.c_int, [ctypes.c_int, c_void_pp, ctypes.POINTER(CboRefineSet), ctypes.c_int, c_double_p,
                                            ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                            c_int_p, c_int_p]),

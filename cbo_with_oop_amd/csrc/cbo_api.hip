@@ -1891,12 +1891,24 @@ extern "C" int cbo_acq_sweep(cbo_gp *g, cbo_cands *k, double y_best, int task, d
 // emukit GreedyBatchPointCalculator over a candidate set without touching the model: pick 0 is the plain sweep; every
 // further pick is one pass over the resident V = L^-1 K* whose pivot the device reads from the previous pick's winner,
 // then the EI / arg-max epilogue on the working copy of q.  Everything is queued; the call synchronises once.
-extern "C" int cbo_acq_sweep_batch(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
-                                   int batch_size, int update_incumbent, double *best_vals, int64_t *best_idxs,
-                                   double *acq_out, double *mean_out, double *var_out)
+// log_form (cbo_acq_sweep_batch_logei): the same sequence, every pick scored by the log-EI candidate pass
+// (pointwise_acq_kernel<kLogEiKind>; under update_incumbent its variant that reads the moved incumbent from the device) --
+// the scalars are checked first, as the log-EI calls check them (check_kind_args), then the handles.
+static int check_kind_args(int n_sets, int kind, const double *y_best, int *task, double *param, const double *costs,
+                           bool logei);
+static int sweep_batch_impl(bool log_form, cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
+                            int batch_size, int update_incumbent, double *best_vals, int64_t *best_idxs, double *acq_out,
+                            double *mean_out, double *var_out)
 {
-    int rc = check_sweep_args(g, k, task);
+    int rc = log_form ? check_kind_args(1, kLogEiKind, &y_best, &task, &ei_jitter, &cost, true) : CBO_OK;
     if (rc != CBO_OK) return rc;
+    if (log_form && (batch_size < 1 || batch_size > CBO_MAX_BATCH))
+        return fail(CBO_ERR_INVALID, "batch_size must be in 1.." + std::to_string(CBO_MAX_BATCH));
+    if (log_form && update_incumbent != 0 && update_incumbent != 1)
+        return fail(CBO_ERR_INVALID, "update_incumbent must be 0 or 1");
+    rc = check_sweep_args(g, k, task);
+    if (rc != CBO_OK) return rc;
+    const int kind = log_form ? kLogEiKind : 0;
     if (batch_size < 1 || batch_size > CBO_MAX_BATCH)
         return fail(CBO_ERR_INVALID, "batch_size must be in 1.." + std::to_string(CBO_MAX_BATCH));
     if (batch_size > k->m) return fail(CBO_ERR_INVALID, "batch_size exceeds the number of candidates");
@@ -1908,12 +1920,13 @@ extern "C" int cbo_acq_sweep_batch(cbo_gp *g, cbo_cands *k, double y_best, int t
     HIP_TRY(hipSetDevice(c->device));
     const bool f32 = g->dtype == CBO_DTYPE_F32;
     if (batch_size == 1 && !f32)
-        return sweep_impl(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_vals, best_idxs, nullptr);
+        return sweep_impl(g, k, y_best, task, ei_jitter, cost, acq_out, mean_out, var_out, best_vals, best_idxs, nullptr, kind);
     int64_t chunk = 0, ld_ws = 0;
     rc = ensure_workspaces(c, g->n_pad, k->m_pad, &chunk, &ld_ws);
     if (rc != CBO_OK) return rc;
     if (batch_size > 1 && chunk < k->m_pad)
-        return fail(CBO_ERR_UNSUPPORTED, "cbo_acq_sweep_batch needs L^-1 K* of all " + std::to_string(k->m_pad) +
+        return fail(CBO_ERR_UNSUPPORTED, std::string(log_form ? "cbo_acq_sweep_batch_logei" : "cbo_acq_sweep_batch") +
+                                             " needs L^-1 K* of all " + std::to_string(k->m_pad) +
                                              " padded candidates resident at once; the workspace holds " +
                                              std::to_string(chunk) + " columns: raise CBO_HIP_WORKSPACE_MB");
     // q, mu of pick 0 as cbo_acq_sweep reaches them; an fp32 model answers from its fp64 factor and leaves the
@@ -1985,9 +1998,14 @@ extern "C" int cbo_acq_sweep_batch(cbo_gp *g, cbo_cands *k, double y_best, int t
                 q_cur = c->batch_q;
                 if (update_incumbent) p.y_best_dev = &c->batch_state.p->y_best;
             }
-            launch_acq(c->stream, q_cur, mu_src, pm, pv, k->m, p, (last && mean_out) ? c->mean.p : nullptr,
-                       (last && var_out) ? c->var.p : nullptr, (last && acq_out) ? c->acq.p : nullptr, c->part_val,
-                       c->part_idx, k->index_offset, nb);
+            double *mean_dst = (last && mean_out) ? c->mean.p : nullptr, *var_dst = (last && var_out) ? c->var.p : nullptr;
+            double *acq_dst = (last && acq_out) ? c->acq.p : nullptr;
+            if (log_form)
+                launch_pointwise_acq(c->stream, kLogEiKind, q_cur, mu_src, pm, pv, k->m, p, mean_dst, var_dst, acq_dst,
+                                     c->part_val, c->part_idx, k->index_offset, nb);
+            else
+                launch_acq(c->stream, q_cur, mu_src, pm, pv, k->m, p, mean_dst, var_dst, acq_dst, c->part_val, c->part_idx,
+                           k->index_offset, nb);
             launch_argmax_final(c->stream, c->part_val, c->part_idx, nb, c->best_val, c->best_idx);
         }
         launch_batch_record(c->stream, c->best_val, c->best_idx, batch_size - 1, c->batch_h_vals, c->batch_h_idxs);
@@ -2002,6 +2020,24 @@ extern "C" int cbo_acq_sweep_batch(cbo_gp *g, cbo_cands *k, double y_best, int t
     }
     if (c->profiling) c->timers.n_sweep += 1;
     return CBO_OK;
+}
+
+extern "C" int cbo_acq_sweep_batch(cbo_gp *g, cbo_cands *k, double y_best, int task, double ei_jitter, double cost,
+                                   int batch_size, int update_incumbent, double *best_vals, int64_t *best_idxs,
+                                   double *acq_out, double *mean_out, double *var_out)
+{
+    return sweep_batch_impl(false, g, k, y_best, task, ei_jitter, cost, batch_size, update_incumbent, best_vals, best_idxs,
+                            acq_out, mean_out, var_out);
+}
+
+// The Kriging believer on the log Expected Improvement: cbo_acq_sweep_batch's picks scored by log EI - log
+// cost, finite and ordered where every pick's EI is an exact 0.  batch_size == 1 on an fp64 model is cbo_acq_sweep_logei.
+extern "C" int cbo_acq_sweep_batch_logei(cbo_gp *g, cbo_cands *k, double y_best, int task, double jitter, double cost,
+                                         int batch_size, int update_incumbent, double *best_vals, int64_t *best_idxs,
+                                         double *acq_out, double *mean_out, double *var_out)
+{
+    return sweep_batch_impl(true, g, k, y_best, task, jitter, cost, batch_size, update_incumbent, best_vals, best_idxs, acq_out,
+                            mean_out, var_out);
 }
 
 // ---- max-value entropy search (kernels_mes.hip) ------------------------------------------------------------------------
@@ -2772,9 +2808,11 @@ static int ensure_small_batch_buffers(cbo_ctx *c, int n_sets, int blocks, int ba
     return rc;
 }
 
-extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
-                                        double ei_jitter, const double *costs, int batch_size, int update_incumbent,
-                                        double *best_vals, int64_t *best_idxs)
+// log_form (cbo_acq_sweep_sets_batch_logei): small_sets_batch_kernel's LOG instantiation, the general path
+// cbo_acq_sweep_batch_logei, a batch of one cbo_acq_sweep_sets_logei; ei_jitter is the log EI's jitter and must be finite.
+static int sweep_sets_batch_impl(bool log_form, int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best,
+                                 int task, double ei_jitter, const double *costs, int batch_size, int update_incumbent,
+                                 double *best_vals, int64_t *best_idxs)
 {
     // what needs no handle first
     if (n_sets <= 0) return fail(CBO_ERR_INVALID, "n_sets must be positive");
@@ -2784,6 +2822,7 @@ extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cand
     if (batch_size < 1 || batch_size > CBO_MAX_BATCH)
         return fail(CBO_ERR_INVALID, "batch_size must be in 1.." + std::to_string(CBO_MAX_BATCH));
     if (update_incumbent != 0 && update_incumbent != 1) return fail(CBO_ERR_INVALID, "update_incumbent must be 0 or 1");
+    if (log_form && !std::isfinite(ei_jitter)) return fail(CBO_ERR_INVALID, "jitter must be finite");
     for (int i = 0; i < n_sets; ++i) {
         if (!(costs[i] > 0.0)) return fail(CBO_ERR_INVALID, "cost must be positive (set " + std::to_string(i) + ")");
         if (!std::isfinite(y_best[i])) return fail(CBO_ERR_INVALID, "y_best must be finite (set " + std::to_string(i) + ")");
@@ -2796,7 +2835,8 @@ extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cand
             return fail(CBO_ERR_INVALID, "batch_size exceeds the number of candidates (set " + std::to_string(i) + ")");
     }
     if (batch_size == 1)
-        return sweep_sets_impl(n_sets, gps, cands, y_best, task, ei_jitter, costs, best_vals, best_idxs, -1, kEiKind);
+        return sweep_sets_impl(n_sets, gps, cands, y_best, task, ei_jitter, costs, best_vals, best_idxs, -1,
+                               log_form ? kLogEiKind : kEiKind);
     cbo_ctx *c = gps[0]->ctx;
     const size_t B = (size_t)batch_size;
     std::vector<int> small;
@@ -2814,10 +2854,11 @@ extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cand
         return rc;
     };
     return run_small_or_general(
-        c, "cbo_acq_sweep_sets_batch", "multi-set batch sweep: no result record", n_sets, small, c->small_out, prepare,
+        c, log_form ? "cbo_acq_sweep_sets_batch_logei" : "cbo_acq_sweep_sets_batch", "multi-set batch sweep: no result record",
+        n_sets, small, c->small_out, prepare,
         [&](const SmallLaunch &L) {
             launch_small_sets_batch(c->stream, c->sets_host, ns, blocks, L, c->sets_batch_scratch, batch_size, update_incumbent,
-                                    c->sets_batch_h_vals, c->sets_batch_h_idxs);
+                                    c->sets_batch_h_vals, c->sets_batch_h_idxs, log_form);
         },
         [&](int j, int i) {                                      // the set's winners, complete when its record is
             std::memcpy(best_vals + (size_t)i * B, c->sets_batch_h_vals.p + (size_t)j * B, sizeof(double) * B);
@@ -2827,9 +2868,28 @@ extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cand
         [&](int i) -> int {
             const int rc = ensure_fitted(gps[i]);
             if (rc != CBO_OK) return rc;
-            return cbo_acq_sweep_batch(gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], batch_size, update_incumbent,
-                                       best_vals + (size_t)i * B, best_idxs + (size_t)i * B, nullptr, nullptr, nullptr);
+            return sweep_batch_impl(log_form, gps[i], cands[i], y_best[i], task, ei_jitter, costs[i], batch_size,
+                                    update_incumbent, best_vals + (size_t)i * B, best_idxs + (size_t)i * B, nullptr, nullptr,
+                                    nullptr);
         });
+}
+
+extern "C" int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
+                                        double ei_jitter, const double *costs, int batch_size, int update_incumbent,
+                                        double *best_vals, int64_t *best_idxs)
+{
+    return sweep_sets_batch_impl(false, n_sets, gps, cands, y_best, task, ei_jitter, costs, batch_size, update_incumbent,
+                                 best_vals, best_idxs);
+}
+
+// cbo_acq_sweep_sets_batch on the log Expected Improvement: per set cbo_acq_sweep_batch_logei's bits on a
+// fitted twin, in the one launch
+extern "C" int cbo_acq_sweep_sets_batch_logei(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best,
+                                              int task, double jitter, const double *costs, int batch_size,
+                                              int update_incumbent, double *best_vals, int64_t *best_idxs)
+{
+    return sweep_sets_batch_impl(true, n_sets, gps, cands, y_best, task, jitter, costs, batch_size, update_incumbent, best_vals,
+                                 best_idxs);
 }
 
 // a device-resident do-calculus prior (cbo_do_prior_create, below)

@@ -519,7 +519,8 @@ void launch_log_prior(hipStream_t s, cbo_prior_item *items, int n_models);
 // scratch (1 MiB per set at the cap) and the call's widest set has at most 16 candidate blocks.  batch_scratch:
 // small_sets_batch_doubles(...) doubles (V [128][m_pad], W [batch_size - 1][m_pad], q and mu [m_pad] per set, m_pad =
 // 64 blocks_per_set); h_vals / h_idxs (pinned, device-mapped): n_sets x batch_size winners, set-major, complete when
-// the set's record is; everything else as launch_small_sets.
+// the set's record is; everything else as launch_small_sets.  log_form: the kernel's LOG instantiation, every
+// pick scored by log EI - log cost.
 constexpr int kSmallBatchMaxCands = 1024;
 struct SmallBatchArgs {
     double *V, *W, *q, *mu;
@@ -529,7 +530,8 @@ struct SmallBatchArgs {
 };
 size_t small_sets_batch_doubles(int n_sets, int blocks_per_set, int batch_size);
 void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, const SmallLaunch &L,
-                             double *batch_scratch, int batch_size, int update_incumbent, double *h_vals, int64_t *h_idxs);
+                             double *batch_scratch, int batch_size, int update_incumbent, double *h_vals, int64_t *h_idxs,
+                             bool log_form = false);
 // the same launch with the constrained epilogue (kernels_sets_con.hip, small_sets_con_kernel): `pairs` holds
 // one descriptor per (model, candidate set) pair, a set's pairs consecutive with the objective first; a constraint's value,
 // jitter and sense ride in y_best, ei_jitter and task; pairs[s].pad_ = index of set s's first pair.  max_pairs = the most
@@ -642,7 +644,8 @@ void launch_constrained_acq(hipStream_t s, const ConParams &p, int64_t m, double
                             int64_t *part_idx, int64_t index_offset, int n_blocks, bool log_form = false);
 // ---- point-wise acquisitions (kernels_pointwise.hip) -------------------------------------------------
 // kind CBO_ACQ_LCB / _PI / _VAR: acq_kernel's mean and variance (noise included), then the kind's value / cost.  p.ei_jitter
-// carries the kind's parameter (beta; PI's jitter), p.y_best PI's incumbent; p.want_ei and p.y_best_dev are not read.
+// carries the kind's parameter (beta; PI's jitter), p.y_best PI's incumbent; p.want_ei is not read, p.y_best_dev by kLogEiKind alone: when set, the
+// log EI's incumbent is read from there (cbo_acq_sweep_batch_logei's moved incumbent).
 // Launch grid and arg-max partials as launch_acq (acq_blocks_for).
 void launch_pointwise_acq(hipStream_t s, int kind, const double *q, const double *mu, const double *pm, const double *pv,
                           int64_t m, const AcqParams &p, double *mean_out, double *var_out, double *acq_out,

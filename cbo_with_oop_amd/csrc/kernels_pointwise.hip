@@ -47,6 +47,31 @@ __global__ __launch_bounds__(256) void pointwise_acq_kernel(const double *__rest
     block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
 }
 
+// pointwise_acq_kernel<kLogEiKind> whose incumbent is read from p.y_best_dev, device memory, as acq_kernel reads it: the
+// log-EI pass of a batch's further picks under update_incumbent (cbo_acq_sweep_batch_logei), where the
+// incumbent moves on the device (BatchState::y_best).  A kernel of its own: routing the read through a shared body moved
+// instructions in the arg-max tail of the existing instantiations, which stay the parent's code this way.
+template <bool CAUSAL, bool MV>
+__global__ __launch_bounds__(256) void logei_moved_incumbent_kernel(const double *__restrict__ q, const double *__restrict__ mu,
+                                                                    const double *__restrict__ pm,
+                                                                    const double *__restrict__ pv, int64_t m, AcqParams p,
+                                                                    double *__restrict__ mean_out,
+                                                                    double *__restrict__ var_out, double *__restrict__ acq_out,
+                                                                    double *__restrict__ part_val,
+                                                                    int64_t *__restrict__ part_idx, int64_t index_offset)
+{
+    double bv = -INFINITY;
+    int64_t bi = kNoIndex;
+    p.y_best = *p.y_best_dev;                                        // (uniform)
+    if (!MV) { mean_out = nullptr; var_out = nullptr; }
+    const double log_cost = log(p.cost);                             // (uniform: once per launch)
+    auto score = [&](d2 mean2, d2 var2) {
+        return d2{log_ei_of(mean2[0], var2[0], p, log_cost), log_ei_of(mean2[1], var2[1], p, log_cost)};
+    };
+    acq_pass<CAUSAL>(q, mu, pm, pv, m, p, true, mean_out, var_out, acq_out, index_offset, score, bv, bi);
+    block_argmax(bv, bi, &part_val[blockIdx.x], &part_idx[blockIdx.x]);
+}
+
 template <int KIND>
 static void launch_pointwise_kind(hipStream_t s, const double *q, const double *mu, const double *pm, const double *pv,
                                   int64_t m, const AcqParams &p, double *mean_out, double *var_out, double *acq_out,
@@ -63,6 +88,14 @@ void launch_pointwise_acq(hipStream_t s, int kind, const double *q, const double
                           int64_t m, const AcqParams &p, double *mean_out, double *var_out, double *acq_out,
                           double *part_val, int64_t *part_idx, int64_t index_offset, int n_blocks)
 {
+    if (kind == kLogEiKind && p.y_best_dev) {
+        const bool causal = pv != nullptr, mv = mean_out || var_out;
+        auto kernel = causal ? (mv ? logei_moved_incumbent_kernel<true, true> : logei_moved_incumbent_kernel<true, false>)
+                             : (mv ? logei_moved_incumbent_kernel<false, true> : logei_moved_incumbent_kernel<false, false>);
+        hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(256), 0, s, q, mu, pm, pv, m, p, mean_out, var_out, acq_out, part_val,
+                           part_idx, index_offset);
+        return;
+    }
     auto launch = kind == CBO_ACQ_LCB ? launch_pointwise_kind<CBO_ACQ_LCB>
                   : kind == CBO_ACQ_PI ? launch_pointwise_kind<CBO_ACQ_PI>
                   : kind == kLogEiKind ? launch_pointwise_kind<kLogEiKind> : launch_pointwise_kind<CBO_ACQ_VAR>;

@@ -9,6 +9,8 @@
 //     the arg-max over all m candidates.  The arithmetic of a pick is cbo_device.h's (batch_*), which the general path's
 //     three kernels call too: per set the picks are cbo_acq_sweep_batch's, bit for bit.
 // Nothing waits for another workgroup: the ticket is the only dependency.
+// LOG (cbo_acq_sweep_sets_batch_logei): the same picks scored by log EI - log cost (log_ei_of, st.ei_jitter
+// being the log EI's jitter) -- finite and ordered where the EI of every pick is an exact 0.  Only the two epilogues differ.
 #include <cstring>
 
 #include "cbo_small_device.h"
@@ -32,12 +34,23 @@ struct SmallBatchShared {
 static_assert(sizeof(SmallBatchShared) <= sizeof(SmallShared), "the last arriver's state lives in the dead SmallShared");
 static_assert(sizeof(SmallShared) + sizeof(int) <= 163840, "the workgroup's static LDS (the ticket flag) beside SmallShared: one CU");
 
+// The log form's score of one candidate: log_ei_of, kept out of line -- log_h_of's three ranges inlined twice into a kernel
+// that already holds the factor's registers would spill.  pointwise_acq_kernel<kLogEiKind>'s bits.
+__device__ __attribute__((noinline)) double batch_log_ei(double mean, double var, double y_best, double jitter, int task,
+                                                         double log_cost)
+{
+    AcqParams p{};
+    p.y_best = y_best; p.ei_jitter = jitter; p.task = task;
+    return log_ei_of(mean, var, p, log_cost);
+}
+
 // Picks 1 .. B - 1 of one set by its last workgroup; (bv, bi) = pick 0's winner in every thread on entry.  V, W, q, mu: the
-// set's scratch (row stride mp); hv, hi: the set's slots 1.. of the winners array (thread 0 stores).
-template <int D>
+// set's scratch (row stride mp); hv, hi: the set's slots 1.. of the winners array (thread 0 stores).  log_cost: log(st.cost),
+// read by the log form alone.
+template <int D, bool LOG>
 __device__ __forceinline__ void small_batch_picks(SmallBatchShared &bs, const cbo_small_set &st, const SmallBatchArgs &ba,
                                                   const double *V, double *W, double *q, const double *mu, double *hv,
-                                                  int64_t *hi, double bv, int64_t bi)
+                                                  int64_t *hi, double bv, int64_t bi, [[maybe_unused]] double log_cost)
 {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -109,7 +122,9 @@ __device__ __forceinline__ void small_batch_picks(SmallBatchShared &bs, const cb
             // ---- epilogue on the updated q
             double mean, var;
             posterior_of(qn, mu[j], causal ? st.cpm[j] : 0.0, causal ? st.cpv[j] : 0.0, causal, p, mean, var);
-            const double a = acquisition_of(mean, var, p);
+            double a;
+            if constexpr (LOG) a = batch_log_ei(mean, var, p.y_best, p.ei_jitter, p.task, log_cost);
+            else a = acquisition_of(mean, var, p);
             const int64_t aj = (int64_t)j + st.index_offset;
             if (better(a, aj, bv, bi)) { bv = a; bi = aj; }
         }
@@ -134,7 +149,7 @@ __device__ __forceinline__ void small_batch_picks(SmallBatchShared &bs, const cb
 }
 
 // phases as small_sets_kernel's.  ba: the call's scratch, m_pad = 64 blocks_per_set columns per row for every set.
-template <bool BYVAL>
+template <bool BYVAL, bool LOG>
 __global__ __launch_bounds__(256) void small_sets_batch_kernel(const SmallSetArgs byval, const cbo_small_set *__restrict__ sets,
                                                                double *scratch, int blocks_per_set, double *part_val,
                                                                int64_t *part_idx, int *__restrict__ info,
@@ -160,6 +175,7 @@ __global__ __launch_bounds__(256) void small_sets_batch_kernel(const SmallSetArg
     double *Ws = ba.W + (int64_t)set * (ba.batch_size - 1) * mp;
     double *qs = ba.q + (int64_t)set * mp, *mus = ba.mu + (int64_t)set * mp;
 
+    [[maybe_unused]] const double log_cost = LOG ? log(st.cost) : 0.0;   // (uniform: once per set)
     double bv = -INFINITY;
     int64_t bi = INT64_MAX;
     if ((int64_t)blk * 64 < st.m) {                               // (uniform) a workgroup with candidates
@@ -193,7 +209,8 @@ __global__ __launch_bounds__(256) void small_sets_batch_kernel(const SmallSetArg
             mus[c] = macc;
             double mean, var;
             posterior_of(qacc, macc, cpm_c, cpv_c, st.sv != nullptr, p, mean, var);
-            bv = acquisition_of(mean, var, p);
+            if constexpr (LOG) bv = batch_log_ei(mean, var, p.y_best, p.ei_jitter, p.task, log_cost);
+            else bv = acquisition_of(mean, var, p);
             bi = c + st.index_offset;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's V, q, mu have left (the barriers follow)
@@ -225,7 +242,7 @@ __global__ __launch_bounds__(256) void small_sets_batch_kernel(const SmallSetArg
     status = bs.status;
     __syncthreads();
     if (status == 0) {                                            // (uniform) else: the general path, from the host
-        CBO_FOR_DIM(st.d, small_batch_picks<D>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0));
+        CBO_FOR_DIM(st.d, (small_batch_picks<D, LOG>(bs, st, ba, Vs, Ws, qs, mus, hv, hi, v0, i0, log_cost)));
     }
     if (tid == 0) small_set_record(v0, i0, status, set, info, ticket, out, seq);   // (after thread 0's winners)
 }
@@ -235,16 +252,16 @@ size_t small_sets_batch_doubles(int n_sets, int blocks_per_set, int batch_size)
     return (size_t)n_sets * (size_t)(128 + (batch_size - 1) + 2) * (size_t)(64 * blocks_per_set);
 }
 
-template <bool BYVAL>
+template <bool BYVAL, bool LOG>
 static void launch_small_sets_batch_as(hipStream_t s, const SmallSetArgs &args, const cbo_small_set *sets, int n_sets,
                                        int blocks_per_set, double *scratch, double *part_val, int64_t *part_idx, int *info,
                                        int *ticket, cbo_small_result *out, int seq, const SmallBatchArgs &ba)
 {
     static std::atomic<unsigned long long> opted{0};
-    small_lds_opt_in(reinterpret_cast<const void *>(small_sets_batch_kernel<BYVAL>), opted);
+    small_lds_opt_in(reinterpret_cast<const void *>(small_sets_batch_kernel<BYVAL, LOG>), opted);
     const dim3 grid((unsigned)blocks_per_set, (unsigned)n_sets);
     auto launch = [&](const dim3 &g, int phases) {
-        hipLaunchKernelGGL((small_sets_batch_kernel<BYVAL>), g, dim3(256), sizeof(SmallShared), s, args, sets, scratch,
+        hipLaunchKernelGGL((small_sets_batch_kernel<BYVAL, LOG>), g, dim3(256), sizeof(SmallShared), s, args, sets, scratch,
                            blocks_per_set, part_val, part_idx, info, ticket, out, seq, phases, ba);
     };
     if (blocks_per_set >= kSmallTwoPhaseFromBlocks) {
@@ -256,7 +273,8 @@ static void launch_small_sets_batch_as(hipStream_t s, const SmallSetArgs &args, 
 }
 
 void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_sets, int blocks_per_set, const SmallLaunch &L,
-                             double *batch_scratch, int batch_size, int update_incumbent, double *h_vals, int64_t *h_idxs)
+                             double *batch_scratch, int batch_size, int update_incumbent, double *h_vals, int64_t *h_idxs,
+                             bool log_form)
 {
     SmallBatchArgs ba;
     const size_t mp = (size_t)64 * (size_t)blocks_per_set, ns = (size_t)n_sets;
@@ -270,12 +288,9 @@ void launch_small_sets_batch(hipStream_t s, const cbo_small_set *sets, int n_set
     SmallSetArgs args{};
     const bool byval = n_sets <= kSmallByValue;
     if (byval) std::memcpy(args.s, sets, sizeof(cbo_small_set) * (size_t)n_sets);
-    if (byval)
-        launch_small_sets_batch_as<true>(s, args, sets, n_sets, blocks_per_set, L.scratch, L.part_val, L.part_idx, L.info,
-                                         L.ticket, L.out, L.seq, ba);
-    else
-        launch_small_sets_batch_as<false>(s, args, sets, n_sets, blocks_per_set, L.scratch, L.part_val, L.part_idx, L.info,
-                                          L.ticket, L.out, L.seq, ba);
+    auto launch = byval ? (log_form ? launch_small_sets_batch_as<true, true> : launch_small_sets_batch_as<true, false>)
+                        : (log_form ? launch_small_sets_batch_as<false, true> : launch_small_sets_batch_as<false, false>);
+    launch(s, args, sets, n_sets, blocks_per_set, L.scratch, L.part_val, L.part_idx, L.info, L.ticket, L.out, L.seq, ba);
 }
 
 }  // namespace cbo

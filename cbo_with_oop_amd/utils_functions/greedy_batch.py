@@ -22,14 +22,16 @@ def check_batch_size(batch_size):
 
 class GreedyBatchPointCalculator:
     def __init__(self, model, acquisition, acquisition_optimizer, batch_size):
-        """emukit's constructor.  ``acquisition``: a ``CausalExpectedImprovement``, bare or over a ``Cost``;
+        """emukit's constructor.  ``acquisition``: a ``CausalExpectedImprovement`` -- or a ``CausalLogExpectedImprovement``,
+        the same believer scored in log space (``cbo_acq_sweep_batch_logei``, DESIGN.md §4ad) -- bare or over a ``Cost``;
         ``acquisition_optimizer``: a ``CausalGradientAcquisitionOptimizer`` with ``anchors="grid"`` (no gradient stage is
         defined between picks).  Anything else raises ``ValueError``."""
+        from .pointwise_acquisitions import CausalLogExpectedImprovement
         self.batch_size = check_batch_size(batch_size)
         numerator = acquisition.numerator if isinstance(acquisition, AcquisitionQuotient) else acquisition
-        if not isinstance(numerator, CausalExpectedImprovement) or (
+        if not isinstance(numerator, (CausalExpectedImprovement, CausalLogExpectedImprovement)) or (
                 isinstance(acquisition, AcquisitionQuotient) and not isinstance(acquisition.denominator, Cost)):
-            raise ValueError("greedy batch selection is defined for the causal EI, bare or over a Cost, not for "
+            raise ValueError("greedy batch selection is defined for the causal EI or its logarithm, bare or over a Cost, not for "
                              f"{type(acquisition).__name__}")
         if getattr(acquisition_optimizer, "anchors", "grid") != "grid":
             raise ValueError("greedy batch selection picks from the optimiser's grid: anchors must be 'grid'")

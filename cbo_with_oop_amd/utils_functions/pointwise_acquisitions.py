@@ -302,6 +302,35 @@ class CausalLogExpectedImprovement(_PointwiseAcquisition):
         return {"best_val": best_val.value, "best_idx": best_idx.value, "acq": col(acq), "mean": col(mean),
                 "var": col(var)}
 
+    def sweep_batch(self, candidates, batch_size, cost=1.0, update_incumbent=False, want_acq=False, want_posterior=False):
+        """Greedy batch selection (the Kriging believer) on the log EI in ONE device call (``cbo_acq_sweep_batch_logei``,
+        DESIGN.md §4ad): ``CausalExpectedImprovement.sweep_batch``'s picks, its arguments and its result dictionary, every
+        pick scored by ``log EI - log cost`` -- finite and ordered where the EI of every pick is an exact 0.0 and the EI
+        form returns candidate 0 ``batch_size`` times.  Pick 0 is ``sweep``'s result, bit for bit."""
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+            raise ValueError(f"batch_size must be a positive int, not {batch_size!r}")
+        batch_size = int(batch_size)
+        y_best, task, jitter = self._scalars()
+        own = not isinstance(candidates, CandidateGrid)
+        grid = CandidateGrid(candidates, self.model) if own else candidates
+        m = len(grid)
+        acq = np.empty(m) if want_acq else None
+        mean = np.empty(m) if want_posterior else None
+        var = np.empty(m) if want_posterior else None
+        best_vals = np.empty(batch_size)
+        best_idxs = np.empty(batch_size, dtype=np.int64)
+        try:
+            self.model.ensure_fitted()
+            _lib.check(_lib.load().cbo_acq_sweep_batch_logei(
+                self.model._handle, grid._handle, y_best, _lib.TASK_CODE[task], jitter, float(cost), batch_size,
+                int(bool(update_incumbent)), _lib.dptr(best_vals), best_idxs.ctypes.data_as(_lib.c_int64_p), _lib.dptr(acq),
+                _lib.dptr(mean), _lib.dptr(var)))
+        finally:
+            if own:
+                grid.close()
+        col = lambda a: None if a is None else a[:, None]      # noqa: E731
+        return {"best_val": best_vals, "best_idx": best_idxs, "acq": col(acq), "mean": col(mean), "var": col(var)}
+
     def evaluate_with_gradients(self, x):
         """(log EI (M,1), d log EI / d x (M,d)): posterior and its gradients from the device, ``A`` and ``B`` on the host."""
         x = _lib.as_f64(x)
@@ -323,8 +352,8 @@ class CausalLogExpectedImprovement(_PointwiseAcquisition):
 
 class LogAcquisitionQuotient(AcquisitionQuotient):
     """``CausalLogExpectedImprovement(...) / Cost(...)``: the logarithm of the quotient, ``log EI - log cost``.  ``sweep`` hands
-    the cost to the device call as ``AcquisitionQuotient`` does (the call subtracts its logarithm); with the reference's zero
-    cost gradient the gradient is ``d log EI`` itself."""
+    the cost to the device call as ``AcquisitionQuotient`` does (the call subtracts its logarithm), and so does
+    ``sweep_batch`` (inherited); with the reference's zero cost gradient the gradient is ``d log EI`` itself."""
     is_log = True
 
     def evaluate_with_gradients(self, x):

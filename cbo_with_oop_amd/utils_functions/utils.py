@@ -163,7 +163,13 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     ``cbo_acq_sweep_hyper_log``) -- the logarithm of the average ``hyper_samples`` with ``"EI"`` scores, not the average of the
     logarithms; finite and ordered where that average is an exact 0.  Without ``hyper_samples``, or with ``constraints``,
     ``batch_size``, ``cost_mode="pointwise"`` or ``anchors="uniform"``, it raises ``ValueError`` before any device call.
+    ``acquisition="LOGBEI"`` with ``batch_size``: the greedy batch scored in log space -- the same believer,
+    every pick's score ``log EI - log cost`` (``CausalLogExpectedImprovement.sweep_batch``, ``cbo_acq_sweep_batch_logei``):
+    finite and ordered where the EI of every pick is an exact 0 and ``"EI"`` returns candidate 0 ``batch_size`` times.
+    Without ``batch_size`` (the acquisition is then ``"LOGEI"``), or with ``constraints``, ``hyper_samples``,
+    ``cost_mode="pointwise"`` or ``anchors="uniform"``, it raises ``ValueError`` before any device call.
     """
+    checked_log_bei((acquisition, None), batch_size, constraints, hyper_samples, cost_mode=cost_mode, anchors=anchors)
     checked_log_mei((acquisition, None), hyper_samples, constraints, batch_size, cost_mode=cost_mode, anchors=anchors)
     checked_log_cei((acquisition, None), constraints, hyper_samples, batch_size, cost_mode=cost_mode, anchors=anchors)
     if checked_pointwise_cost(cost_mode, (acquisition, None), constraints, hyper_samples, batch_size):
@@ -202,13 +208,14 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     if batch_size is not None:
         if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
             raise ValueError(f"batch_size must be a positive int, not {batch_size!r}")
-        if acquisition != "EI":
-            raise ValueError("batch selection believes the causal EI's model: acquisition must be 'EI'")
+        if acquisition not in ("EI", LOG_BEI):
+            raise ValueError("batch selection believes the causal EI's model: acquisition must be 'EI' (or 'LOGBEI', the "
+                             "same batch scored in log space)")
         if constraints is not None:
             raise ValueError("batch selection is not defined for constrained acquisitions: constraints must be None")
         if anchors != "grid":
             raise ValueError("batch selection picks from the grid: anchors must be 'grid'")
-    if acquisition not in ("EI", "MES", LOG_EI, LOG_CEI, LOG_MEI) + POINTWISE_ACQUISITIONS:
+    if acquisition not in ("EI", "MES", LOG_EI, LOG_CEI, LOG_MEI, LOG_BEI) + POINTWISE_ACQUISITIONS:
         raise ValueError(f"acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR', not {acquisition!r}")
     if acquisition == "MES":
         if task != "min":
@@ -256,7 +263,7 @@ def find_next_y_point(space, model, current_global_best, evaluated_set, costs_fu
     try:
         batch_cost = float(cost_acquisition.evaluate(grid.points))      # ONE scalar for the batch (Quotient)
         if batch_size is not None:
-            return _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, int(batch_size))
+            return _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, int(batch_size), acquisition == LOG_BEI)
         res = ei.sweep(grid, cost=batch_cost)
         x_new = grid.points[res["best_idx"] - grid.index_offset][None, :].copy()
         # utils.py:36 re-evaluates the acquisition at x_new alone; only variable costs change the value
@@ -277,6 +284,7 @@ POINTWISE_ACQUISITIONS = ("LCB", "PI", "MPEI", "VAR")
 LOG_EI = "LOGEI"      # the log Expected Improvement: a name of its own, routed to the cbo_acq_*_logei calls
 LOG_CEI = "LOGCEI"    # log EI + sum log PoF - log cost: routed by name to the cbo_acq_*_constrained_log calls
 LOG_MEI = "LOGMEI"    # log((1 / H) sum_h EI_h) - log cost: routed by name to the cbo_acq_sweep*_hyper_log calls
+LOG_BEI = "LOGBEI"    # the Kriging-believer batch on log EI - log cost: routed by name to cbo_acq_sweep*_batch_logei
 
 
 def _acquisition_for(name, model, current_global_best, task, space, param=None):
@@ -285,7 +293,7 @@ def _acquisition_for(name, model, current_global_best, task, space, param=None):
     if name == "MES":
         from .max_value_entropy import MaxValueEntropySearch
         return MaxValueEntropySearch(model, space)
-    if name in (LOG_EI, LOG_CEI):                  # (LOGCEI's objective; its constraints are the caller's to add)
+    if name in (LOG_EI, LOG_CEI, LOG_BEI):         # (LOGCEI's objective; its constraints are the caller's to add.  LOGBEI's picks)
         from .pointwise_acquisitions import CausalLogExpectedImprovement
         return CausalLogExpectedImprovement(current_global_best, task, model, 0.0 if param is None else param)
     if name in POINTWISE_ACQUISITIONS:
@@ -306,7 +314,8 @@ def sets_acquisition(acquisition="EI", acquisition_param=None):
     ``"EI"`` (no parameter: today's call, ``None``), ``"LCB"`` (beta, default 1, finite and not negative), ``"PI"`` and
     ``"MPEI"`` (the jitter, default 0, finite), ``"LOGEI"`` (the log Expected Improvement of DESIGN.md §4x: the jitter, as
     PI's), ``"LOGCEI"`` (its constrained form, DESIGN.md §4aa: the log EI's jitter, checked as LOGEI's), ``"LOGMEI"`` (its
-    hyper-marginalised form, DESIGN.md §4ac: the log EI's jitter, checked as LOGEI's), ``"VAR"`` (no
+    hyper-marginalised form, DESIGN.md §4ac: the log EI's jitter, checked as LOGEI's), ``"LOGBEI"`` (its greedy batch, DESIGN.md
+    §4ad: the log EI's jitter, checked as LOGEI's; the callers require a ``batch_size`` with it), ``"VAR"`` (no
     parameter: 0 travels), ``"MES"`` with a pair of ints ``(num_samples, grid_size)``, ``num_samples`` in 1..64,
     ``grid_size`` at least 1 (the parameter returned is that pair).
     Anything else raises ``ValueError`` -- a bare ``"MES"`` too: this function never answered for it and has no default for
@@ -319,7 +328,7 @@ def sets_acquisition(acquisition="EI", acquisition_param=None):
         sets_acquisition(name, None if name in ("EI", "VAR") else param)
         return acquisition
     if not isinstance(acquisition, str) \
-            or acquisition not in ("EI", "MES", LOG_EI, LOG_CEI, LOG_MEI) + POINTWISE_ACQUISITIONS:
+            or acquisition not in ("EI", "MES", LOG_EI, LOG_CEI, LOG_MEI, LOG_BEI) + POINTWISE_ACQUISITIONS:
         raise ValueError("acquisition must be 'EI', 'MES', 'LCB', 'PI', 'MPEI' or 'VAR' in a multi-set sweep, "
                          f"not {acquisition!r}")
     if acquisition == "MES":
@@ -368,10 +377,18 @@ def sets_acquisition_or_default(acquisition="EI", acquisition_param=None):
     return sets_acquisition(acquisition, acquisition_param)
 
 
-def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
+def _repriced(value, batch_cost, point_cost, log_form):
+    """A later pick's value moved from the batch's cost to the point's own: the quotient rescaled, or -- the log form,
+    ``log EI - log cost`` -- the two logarithms exchanged."""
+    if log_form:
+        return (value + np.log(batch_cost)) - np.log(point_cost)
+    return value * batch_cost / point_cost
+
+
+def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size, log_form=False):
     """``find_next_y_point(batch_size=B)``: (y (B,1), x (B,d)) of one ``sweep_batch``.  y[t] is the pick's acquisition over
     the point's own cost where variable costs make that differ from the batch's (utils.py:36): pick 0 by the single-point
-    path's re-evaluation, the later picks -- whose believed model exists on the device only -- by rescaling."""
+    path's re-evaluation, the later picks -- whose believed model exists on the device only -- by rescaling (``_repriced``)."""
     res = ei.sweep_batch(grid, batch_size, cost=batch_cost)
     x_new = grid.points[res["best_idx"] - grid.index_offset].copy()
     y = np.asarray(res["best_val"], dtype=np.float64).reshape(-1, 1).copy()
@@ -379,7 +396,7 @@ def _next_y_points_batch(ei, grid, cost_acquisition, batch_cost, batch_size):
         point_cost = float(cost_acquisition.evaluate(x_new[t:t + 1]))
         if point_cost != batch_cost:
             y[t, 0] = (ei.sweep(x_new[t:t + 1], cost=point_cost, want_acq=True)["acq"][0, 0] if t == 0
-                       else y[t, 0] * batch_cost / point_cost)
+                       else _repriced(y[t, 0], batch_cost, point_cost, log_form))
     return y, x_new
 
 
@@ -465,10 +482,17 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
     ``find_next_y_point(acquisition="LOGMEI", hyper_samples=rows_s)`` returns, finite and ordered where the marginalised EI
     is an exact 0.  Without ``hyper_samples``, or with non-empty ``constraints``, ``batch_size``, ``refine``,
     ``refine_constrained``, ``device_prior``, ``cost_mode="pointwise"`` or ``raw=True``, it raises ``ValueError`` before any
-    device call."""
+    device call.
+    ``acquisition="LOGBEI"`` with ``acquisition_param`` (the log EI's jitter, default 0), ``batch_size`` and
+    ``update_incumbent``: every set's greedy batch scored in log space in ONE device call
+    (``cbo_acq_sweep_sets_batch_logei``) -- per set what ``find_next_y_point(acquisition="LOGBEI", batch_size=B)`` returns,
+    distinct and ordered picks where ``"EI"`` with a ``batch_size`` returns candidate 0 B times.  Without ``batch_size``, or
+    with non-empty ``constraints``, ``hyper_samples``, ``refine``, ``refine_constrained``, ``device_prior``,
+    ``cost_mode="pointwise"`` or ``raw=True``, it raises ``ValueError`` before any device call."""
     import ctypes
     from .. import _lib
     kind = sets_acquisition_or_default(acquisition, acquisition_param)
+    checked_log_bei(kind, batch_size, constraints, hyper_samples, refine, refine_constrained, device_prior, raw, cost_mode)
     checked_log_mei(kind, hyper_samples, constraints, batch_size, refine, refine_constrained, device_prior, raw, cost_mode)
     checked_refine_constrained(refine_constrained, kind, constraints, hyper_samples, batch_size, raw, spaces, len(models),
                                device_prior, cost_mode)
@@ -532,7 +556,7 @@ def find_next_y_points(models, current_global_best, evaluated_sets, costs_functi
         st.pop("trial_args", None)               # (a batch takes the three-call route; back at None the call is made anew)
     st["batch_size"] = batch_size
     if batch_size is not None:
-        return _sweep_sets_batch(st, models, grids, current_global_best, task, batch_size, bool(update_incumbent))
+        return _sweep_sets_batch(st, models, grids, current_global_best, task, batch_size, bool(update_incumbent), kind)
     if hyper_rows is not None:
         # (the entry keeps the row arrays and the pointer array alive; the rows change from trial to trial)
         st["hyper_args"] = ((ctypes.c_int * s)(*[r.shape[0] for r in hyper_rows]),
@@ -707,6 +731,35 @@ def checked_log_mei(kind, hyper_samples, constraints=None, batch_size=None, refi
         raise ValueError(f"{what} is not defined across several ranks (raw=True)")
 
 
+def checked_log_bei(kind, batch_size, constraints=None, hyper_samples=None, refine=False, refine_constrained=False,
+                    device_prior=False, raw=False, cost_mode="batch", anchors="grid"):
+    """What the greedy batch in log space (``"LOGBEI"``) needs and does not combine with, checked on the host
+    before any device call: it needs a ``batch_size`` and picks from the grid, with one cost per set, without constraints or
+    hyper-parameter samples, unrefined, by a single process."""
+    if kind[0] != LOG_BEI:
+        return
+    what = "acquisition='LOGBEI'"
+    if batch_size is None:
+        raise ValueError(f"{what} is the greedy batch scored in log space: batch_size must be given (without a batch the "
+                         "acquisition is 'LOGEI')")
+    if constraints is not None and (not hasattr(constraints, "__len__") or any(constraints)):
+        raise ValueError(f"{what} is not defined with constraints: constraints must be None or empty")
+    if hyper_samples is not None:
+        raise ValueError(f"{what} is not defined for the marginalised EI: hyper_samples must be None")
+    if refine:
+        raise ValueError(f"{what} has no refinement between picks: refine must be False")
+    if refine_constrained:
+        raise ValueError(f"{what} has no refinement between picks: refine_constrained must be False")
+    if device_prior:
+        raise ValueError(f"{what} has no refinement between picks: device_prior must be False")
+    if cost_mode != "batch":
+        raise ValueError(f"{what} takes one cost per set: cost_mode must be 'batch', not {cost_mode!r}")
+    if anchors != "grid":
+        raise ValueError(f"{what} picks from the grid: anchors must be 'grid'")
+    if raw:
+        raise ValueError(f"{what} is not defined across several ranks (raw=True)")
+
+
 def checked_device_prior(device_prior, refine):
     """``device_prior`` of a multi-set sweep, a path or an agent: it selects how causal sets are REFINED."""
     if device_prior and not refine:
@@ -795,7 +848,8 @@ def refine_winners(xs, ys, models, spaces, current_global_best, task, costs, kin
 
 def checked_batch_size(batch_size, kind=("EI", None), constraints=None, hyper_samples=None, raw=False):
     """``batch_size`` of a multi-set sweep, a path or an agent, checked on the host before any device call: ``None``, or
-    an int in 1..64 -- with the causal EI, no (non-empty) constraints, no hyper-parameter samples and a single rank."""
+    an int in 1..64 -- with the causal EI (``"EI"``, or ``"LOGBEI"``: the same batch scored in log space), no (non-empty)
+    constraints, no hyper-parameter samples and a single rank."""
     if batch_size is None:
         return None
     from .. import _lib
@@ -803,8 +857,9 @@ def checked_batch_size(batch_size, kind=("EI", None), constraints=None, hyper_sa
         raise ValueError(f"batch_size must be a positive int, not {batch_size!r}")
     if batch_size > _lib.MAX_BATCH:
         raise ValueError(f"batch_size must be at most {_lib.MAX_BATCH}, not {batch_size}")
-    if kind[0] != "EI":
-        raise ValueError("batch selection believes the causal EI's model: acquisition must be 'EI'")
+    if kind[0] not in ("EI", LOG_BEI):
+        raise ValueError("batch selection believes the causal EI's model: acquisition must be 'EI' (or 'LOGBEI', the same "
+                         "batch scored in log space)")
     if constraints is not None and any(constraints):
         raise ValueError("batch selection is not defined for constrained acquisitions: constraints must be None or empty")
     if hyper_samples is not None:
@@ -814,18 +869,21 @@ def checked_batch_size(batch_size, kind=("EI", None), constraints=None, hyper_sa
     return int(batch_size)
 
 
-def _sweep_sets_batch(st, models, grids, current_global_best, task, batch_size, update_incumbent):
-    """The batch form of ``find_next_y_points``' device call: one ``cbo_acq_sweep_sets_batch``, its set-major winners as
-    (B, d) points and (B, 1) values per set (``_next_y_points_batch``'s treatment of variable costs)."""
+def _sweep_sets_batch(st, models, grids, current_global_best, task, batch_size, update_incumbent, kind=("EI", None)):
+    """The batch form of ``find_next_y_points``' device call: one ``cbo_acq_sweep_sets_batch`` -- for ``kind``
+    ``("LOGBEI", jitter)`` one ``cbo_acq_sweep_sets_batch_logei`` -- its set-major winners as (B, d) points and (B, 1) values
+    per set (``_next_y_points_batch``'s treatment of variable costs)."""
     from .. import _lib
     s = len(models)
+    log_form = kind[0] == LOG_BEI
     for i in range(s):
         if batch_size > grids[i].points.shape[0]:
             raise ValueError(f"batch_size {batch_size} exceeds the {grids[i].points.shape[0]} candidates of set {i}")
     vals, idxs = np.empty(s * batch_size), np.empty(s * batch_size, dtype=np.int64)
-    _lib.check(_lib.load().cbo_acq_sweep_sets_batch(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], 0.0,
-                                                    _lib.dptr(st["batch_cost"]), batch_size, int(update_incumbent),
-                                                    _lib.dptr(vals), idxs.ctypes.data_as(_lib.c_int64_p)))
+    call = _lib.load().cbo_acq_sweep_sets_batch_logei if log_form else _lib.load().cbo_acq_sweep_sets_batch
+    _lib.check(call(s, st["gps"], st["cds"], _lib.dptr(st["y_best"]), _lib.TASK_CODE[task], float(kind[1]) if log_form else 0.0,
+                    _lib.dptr(st["batch_cost"]), batch_size, int(update_incumbent), _lib.dptr(vals),
+                    idxs.ctypes.data_as(_lib.c_int64_p)))
     vals, idxs = vals.reshape(s, batch_size), idxs.reshape(s, batch_size)
     st["vals"][:], st["idxs"][:] = vals[:, 0], idxs[:, 0]
     xs, ys = [], []
@@ -844,9 +902,9 @@ def _sweep_sets_batch(st, models, grids, current_global_best, task, batch_size, 
         for t in range(batch_size):
             point_cost = float(st["costs"][i].evaluate(x_new[t:t + 1]))
             if point_cost != batch_cost:
-                y[t, 0] = (CausalExpectedImprovement(current_global_best, task, models[i]).sweep(
+                y[t, 0] = (_acquisition_for(kind[0], models[i], current_global_best, task, None, kind[1]).sweep(
                     x_new[t:t + 1], cost=point_cost, want_acq=True)["acq"][0, 0] if t == 0
-                           else y[t, 0] * batch_cost / point_cost)
+                           else _repriced(y[t, 0], batch_cost, point_cost, log_form))
         xs.append(x_new)
         ys.append(y)
     return xs, ys

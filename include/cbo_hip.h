@@ -578,6 +578,24 @@ int cbo_acq_sweep_batch(cbo_gp *gp, cbo_cands *cands, double y_best, int task, d
                         int batch_size, int update_incumbent, double *best_vals, int64_t *best_idxs, double *acq_out,
                         double *mean_out, double *var_out);
 
+/* cbo_acq_sweep_batch on the log Expected Improvement: the same believer -- pivot column, fantasy rows W,
+ * the update of q, update_incumbent's moved incumbent -- with every pick scored by cbo_acq_sweep_logei's pass,
+ *     acq_j = log EI_j - log cost    on the updated q (jitter: the log EI's jitter; task 'max' is LOGEI's mirror),
+ * and the same arg-max.  The EI of a pick is an exact 0.0 over the whole grid wherever the incumbent lies well below the
+ * model's data (every exploration set but the best one, in CBO): cbo_acq_sweep_batch then returns candidate 0 for that and
+ * every later pick; the log form stays finite and ordered there.  Where the EI is representable the two calls pick the same
+ * indices (ties and near-ties apart).
+ *  - batch_size == 1 on an fp64 model is cbo_acq_sweep_logei(gp, cands, y_best, task, jitter, cost, ...): its bits.
+ *  - acq_out / mean_out / var_out: the state at the LAST pick; best_vals[t] is acq[best_idxs[t]] of pick t's state.
+ *  - An fp32 model answers from its fp64 factor.  Model and candidates are left as they were.
+ * CBO_ERR_INVALID, scalars first (as cbo_acq_sweep_logei checks them): a bad task; a non-finite jitter or y_best; cost <= 0 or
+ * NaN; batch_size outside 1..CBO_MAX_BATCH; update_incumbent other than 0 or 1; then cbo_acq_sweep_batch's checks of the
+ * handles, batch_size above the candidate count and NULL best_vals / best_idxs.  CBO_ERR_UNSUPPORTED and CBO_ERR_NOT_FITTED
+ * as cbo_acq_sweep_batch. */
+int cbo_acq_sweep_batch_logei(cbo_gp *gp, cbo_cands *cands, double y_best, int task, double jitter, double cost,
+                              int batch_size, int update_incumbent, double *best_vals, int64_t *best_idxs, double *acq_out,
+                              double *mean_out, double *var_out);
+
 /* Refit (as cbo_gp_fit, jitchol ladder included) and sweep (as cbo_acq_sweep) in one call, overlapped: the
  * sweep's substitution advances panel by panel on a second stream while the factorisation's chain of short
  * kernels runs.  This is the pair of calls CBO.intervene() makes for the set it has just intervened on
@@ -835,6 +853,16 @@ int cbo_gp_mes_gumbel_sets(int n_sets, cbo_gp *const *gps, cbo_cands *const *gri
 int cbo_acq_sweep_sets_batch(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
                              double ei_jitter, const double *costs, int batch_size, int update_incumbent,
                              double *best_vals, int64_t *best_idxs);
+
+/* cbo_acq_sweep_sets_batch on the log Expected Improvement.  Contract: for every set i the batch_size
+ * (value, index) pairs are bit for bit those of cbo_acq_sweep_batch_logei(gps[i], cands[i], y_best[i], task, jitter, costs[i],
+ * batch_size, update_incumbent, ...) on a fitted twin.  Routing, scratch, the untouched models and the general path inside
+ * the call are cbo_acq_sweep_sets_batch's (the launch is small_sets_batch_kernel's log instantiation; the general path is
+ * cbo_gp_fit if unfitted, then cbo_acq_sweep_batch_logei); batch_size == 1 IS cbo_acq_sweep_sets_logei.
+ * CBO_ERR_INVALID: cbo_acq_sweep_sets_batch's checks, and a non-finite jitter. */
+int cbo_acq_sweep_sets_batch_logei(int n_sets, cbo_gp *const *gps, cbo_cands *const *cands, const double *y_best, int task,
+                                   double jitter, const double *costs, int batch_size, int update_incumbent,
+                                   double *best_vals, int64_t *best_idxs);
 
 /* The second stage of the reference's optimiser for every exploration set of a trial: from each of set
  * i's k starts a box-constrained L-BFGS ascent of acquisition / cost -- lockstep_lbfgs of utils_functions/causal_optimizer.py,
